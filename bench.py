@@ -9,6 +9,8 @@ python bench.py --gpus N --steps K --warmup W
   N > 1 under torch.distributed.run (RANK / WORLD_SIZE set): one rank per GPU, gradients over RCCL.
 Rank 0 prints ONE compact JSON line on stdout (< 4 KB; contract in the task statement) carrying `roofline`, `cpu_baseline`, `f32_row`, `cfg3` and
 `search_cfg5` summaries; the full result (per arithmetic mode tables, per-kernel tables, notes) goes to gpurun_out/bench_detail.json (--detail PATH).
+--dump-outputs DIR writes what the last timed step of each timed mode computed as .npy files (same arguments = same inputs), so that two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -563,6 +565,42 @@ def percentiles(ms):
     return dict(p10=q(0.10), p50=q(0.50), p90=q(0.90), min=round(s[0], 4), max=round(s[-1], 4))
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# --dump-outputs DIR: what the timed path computed in its LAST timed step, as a caller of gr_train_r_step receives it - R's updated
+# parameters, its clamped gradient, Adam's moments and BatchNorm running statistics, G's images and R's predictions of that step -
+# as DIR/<workload>_<mode>_<name>.npy (float32).  An array above DUMP_MAX_ELEMS elements is stored as a fixed seeded sample of its
+# flattened elements (the indices depend on the array's size only), which keeps a run's dump under DUMP_MAX_BYTES.
+DUMP_MAX_ELEMS = 1 << 19
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240601
+_dump_bytes = [0]
+
+
+def dump_sample(a):
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.size <= DUMP_MAX_ELEMS:
+        return a
+    return a.reshape(-1)[np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).permutation(a.size)[:DUMP_MAX_ELEMS])]
+
+
+def dump_step_outputs(dirpath, prefix, ctx, gnet, rnet, B, dims, nd):
+    import numpy as np
+    m, v = rnet.adam_state()
+    bn = [np.concatenate(rnet.get_bn_running(i)) for i in range(rnet.n_bn())]      # per BatchNorm: running_mean, then running_var
+    arrays = dict(r_params=rnet.get_params(), r_grads=rnet.get_grads(), adam_m=m, adam_v=v,
+                  r_bn_running=np.concatenate(bn) if bn else np.zeros(0, np.float32),
+                  g_images=ctx.download(gnet.lib.gr_net_output_dev(gnet.h), (B,) + tuple(dims)),
+                  r_output=ctx.download(rnet.lib.gr_net_output_dev(rnet.h), (B, nd)))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        path = os.path.join(dirpath, f"{prefix}_{name}.npy")
+        np.save(path, dump_sample(a))
+        _dump_bytes[0] += os.path.getsize(path)
+    if _dump_bytes[0] > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs wrote {_dump_bytes[0]} bytes (limit {DUMP_MAX_BYTES})")
+
+
 def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, traffic_from, dist, torch):
     """One workload (cfg2 / cfg3) through the timed loop in every requested arithmetic mode.  Returns the line's fields for
     it (rank 0) or None."""
@@ -635,6 +673,8 @@ def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, tra
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         per_step = [ctx.event_elapsed_ms(i, i + 1) for i in range(args.steps)]
+        if args.dump_outputs and rank == 0:
+            dump_step_outputs(args.dump_outputs, f"{wl_key}_{mode}", ctx, gnet, rnet, B, dims, nd)
         loss = step(want_loss=True)
         # the timed steps must have run the arithmetic the line names: a tripped range guard moves the context to bf16x6 (csrc/net.hip)
         # (reported, not fatal: the row is then labelled with what ran)
@@ -841,10 +881,16 @@ def main():
     ap.add_argument("--traffic", default="live", choices=["live", "file", "off"],
                     help="roofline.traffic: measured in this run by rocprofv3 --pmc children (N = 1), read from profiles/traffic.json, or omitted")
     ap.add_argument("--detail", default=DETAIL_FILE, help="file the FULL result (mode tables, per-kernel tables, notes) is written to; stdout carries the compact headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after each timed mode, write what its last timed step computed (R's parameters, gradient, Adam moments, BatchNorm running "
+                         "statistics, G's images, R's predictions) as DIR/<workload>_<mode>_<name>.npy, float32; arrays above "
+                         f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample; at most {DUMP_MAX_BYTES // 10 ** 6} MB in all")
     ap.add_argument("--quiet-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))                       # this process has not touched a GPU

@@ -298,6 +298,25 @@ def test_bench_launches_its_own_ranks():
     assert bad.returncode != 0 and "WORLD_SIZE=2" in bad.stderr
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded():
+    """bench.py --dump-outputs: an array above DUMP_MAX_ELEMS elements is stored as the same seeded sample in every run (sorted indices that depend on
+    its size only), a smaller one whole; the largest dump a run can write (--workload both: three modes of cfg2 and one of cfg3, each five arrays of at
+    most DUMP_MAX_ELEMS floats plus R's predictions and BatchNorm statistics) fits DUMP_MAX_BYTES; --steps below 1 is refused."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    small = synth.normal((3, 7), 1)
+    assert np.array_equal(bench.dump_sample(small), small)
+    big = np.arange(3 * bench.DUMP_MAX_ELEMS + 5, dtype=np.float32)
+    s1, s2 = bench.dump_sample(big), bench.dump_sample(big.copy())
+    assert s1.dtype == np.float32 and s1.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    worst_predictions = max(w["batch"] * w["nd"] for w in bench.WORKLOADS.values())
+    assert 4 * 4 * (5 * bench.DUMP_MAX_ELEMS + worst_predictions + 4096) < bench.DUMP_MAX_BYTES
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_bench_gpus_8_dry_run_forms_eight_ranks():
     """cfg4's launch shape (BASELINE configs[3]: 8 ranks): `python bench.py --gpus 8` spawns eight rank processes that meet in the gloo control group, each
     bound to its LOCAL_RANK's device, and rank 0 relays ONE line with n_gpus = 8 and the eight (rank, device) pairs; per-rank batch and global batch are the

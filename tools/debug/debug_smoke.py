@@ -1,5 +1,5 @@
 import sys, os
-ROOT="/root/repo"
+ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (os.path.join(ROOT,"gan-reverser_amd"), ROOT, os.path.join(ROOT,"tests")): sys.path.insert(0,p)
 import numpy as np
 import ganrev._lib as L

@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes over the conv micro-benchmark (run on the GPU box): usage tools/pmc_conv.sh <shape-filter> <batch>
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp
 F=${1:-conv2}; B=${2:-256}
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM" "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   tag=$(echo $set | cut -d' ' -f1)

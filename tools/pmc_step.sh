@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes over bench.py (run on the GPU box): per-kernel counters of the real training step.  usage: tools/pmc_step.sh [kernel-substring] [cfg2|cfg3]
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp
 F=${1:-conv3x3}; WL=${2:-cfg2}
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INST_CYCLES_VMEM SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL" "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   tag=$(echo $set | cut -d' ' -f1)

@@ -4,7 +4,7 @@
 #  (2) by request size: TCC_EA0_RDREQ_{32B,64B,128B}_sum and TCC_EA0_WRREQ_{sum,64B_sum}: bytes = 32 a + 64 b + 128 c, no correction factor.
 # tools/probe/fetch_probe calibrates (1) against known byte counts: the factor 2 holds for every vector load / LDS-DMA shape whose contiguous
 # piece is a whole 128-byte line; 64-byte pieces read 1.36-1.55, scalar-cache loads 1.0 (profiles/r04_fetch_calibration.txt).
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp
 WL=${1:-cfg2}; F=${2:-}
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do

@@ -1,6 +1,6 @@
 #!/bin/bash
 # on the GPU box: tools/probe/run_fetch_probe.sh  ->  gpurun_out/fetch_calibration.txt
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/../.." && pwd); cd /tmp
 rm -rf $R/gpurun_out/fetchcal
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/fetchcal -- $R/tools/probe/fetch_probe > $R/gpurun_out/fetchcal.log 2>&1
 python3 - <<PY > $R/gpurun_out/fetch_calibration.txt

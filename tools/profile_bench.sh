@@ -9,7 +9,7 @@
 # ONE workload and ONE arithmetic per trace.  The stats pass runs `--modes f16x3 --no-search --no-gan` so that every AverageNs in
 # profiles/<tag>_<workload>_kernel_stats.csv belongs to that workload's training step (no embed / GAN / f32 / bf16x6 launches mixed into a kernel's average);
 # the cfg5 embed + search pipeline gets a pass of its own: tools/profile_bench.sh embed.
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; WL=${1:-cfg2}; shift
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/.." && pwd); WL=${1:-cfg2}; shift
 cd /tmp
 if [ "$WL" = embed ]; then
   rm -rf $R/gpurun_out/prof_stats_embed

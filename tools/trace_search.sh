@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel trace of the cfg5 search (tools/search_profile.py): per-kernel durations and the gaps between the three launches of one call
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp
 rm -rf $R/gpurun_out/trace_search
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/trace_search -- python3 $R/tools/search_profile.py > $R/gpurun_out/trace_search.log 2>&1
 python3 - <<PY
