@@ -34,14 +34,13 @@ struct ConvArgs {
   const float* in; const float* wt; const float* bias; float* out;
   int B, Cin, Cout, H, W;
   int up, nchunks, cout_pad, tiles_x, tiles_y, n_otiles;
-  int n_tiles = 0;      // wide kernel: logical tiles (a workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...)
+  int n_tiles = 0;      // logical tiles (xcd_remap's range)
   ConvEpilogue ep;      // ep.mean != nullptr: evaluate()-mode BatchNorm + activation applied before the store
   const unsigned *amax_in = nullptr, *amax_w = nullptr;   // f16x3 mode: bit patterns of max|in| and max|weights| (device)
   unsigned* amax_out = nullptr;                           // nullable: slot that receives max|out|
   // nullable: per-channel (sum, sum of squares) of the stored output over this workgroup's pixels, [Cout][stat_tiles][2]
   // (training-mode BatchNorm statistics without a second pass over y; summed in a fixed order by bn_stats_finalize_tiles)
   double* stat_part = nullptr; int stat_tiles = 0;
-  int nt_out = 0;        // non-temporal output stores (kernels.h store4; launchers set it from g_nt_stores)
   // evaluate() mode, f16x3 (kernels.h P16Out): the epilogue's result as the consuming convolution's operand-ready image, scaled by the
   // bound in p16_scale; `out` may then be null (no fp32 copy)
   uint4* p16_out = nullptr; const unsigned* p16_scale = nullptr;
@@ -576,7 +575,6 @@ static void launch_conv_t(const ConvArgs& a0, hipStream_t s) {
   hipLaunchKernelGGL((conv3x3_mfma_kernel<MT, TW, NG, NI>), dim3(grid), dim3(256), lds, s, a);
 }
 
-int g_conv_variant = 0;   // tuning hook (GR_CONV_VARIANT env): 0 = default heuristics
 template <int MT, int NG>
 static void launch_conv_mt(const ConvArgs& a, hipStream_t s) {
   if (a.W <= 8) launch_conv_t<MT, 8, 2>(a, s);
@@ -593,13 +591,12 @@ void launch_conv3x3(const float* in, const float* wt, const float* bias, float* 
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.up = up ? 1 : 0;
   a.nchunks = L.cin_pad / CONV_CK; a.cout_pad = L.cout_pad;
   if (w_native && Cout <= 4 && !up && W % 4 == 0 && W >= 16) {
-    static const int fo_split = GR_KNOB("GR_FEWOUT_SPLIT", 4);     // 0: 32-row tiles, 1: two channel groups on 16-row tiles, 4: four on 8-row tiles
+    // small planes (too few 32-row tiles per image to fill the chip): four channel groups on 8-row tiles, else two on 16-row tiles
     // (decided by the plane alone, not by the batch: a row must get the same bits whatever batch it travels in)
-    const bool ks2 = fo_split && H % 16 == 0 && ((W + 31) / 32) * ((H + 31) / 32) < 4;      // small planes: too few 32-row tiles per image to fill the chip
-    const bool ks4 = fo_split == 4 && ks2 && H % 8 == 0;
+    const bool ks2 = H % 16 == 0 && ((W + 31) / 32) * ((H + 31) / 32) < 4;
+    const bool ks4 = ks2 && H % 8 == 0;
     // planes whose width is a multiple of 64: one 64-wide x 16-row tile per workgroup (no halo columns fetched from a neighbour's lines)
-    static const bool fo_wide = !GR_KNOB_SET("GR_FEWOUT_NO_WIDE");
-    const bool wide64 = fo_wide && !ks2 && W % 64 == 0;
+    const bool wide64 = !ks2 && W % 64 == 0;
     a.tiles_x = wide64 ? W / 64 : (W + 31) / 32; a.tiles_y = wide64 ? (H + 15) / 16 : (ks4 ? H / 8 : (ks2 ? H / 16 : (H + 31) / 32)); a.n_otiles = 1;
     const int grid = B * a.tiles_x * a.tiles_y;
     const double px = (double)B * H * W;
@@ -629,18 +626,11 @@ void launch_conv3x3(const float* in, const float* wt, const float* bias, float* 
     }
     return;
   }
-  static int variant = -1;
-  if (variant < 0) { variant = GR_KNOB("GR_CONV_VARIANT", 0); }
-  const bool big_img = (long)H * W >= 512;            // a 512-pixel tile needs at least that many pixels per image
   if (L.cout_pad % 64 != 0) { launch_conv_mt<1, 2>(a, s); return; }
   // measured on MI355X (B=256): 512-pixel tiles (NG=4) beat 256-pixel ones on 32x32 planes (G.convB 1333 -> 1198 us);
-  // 128-channel row blocks with one workgroup per CU (MT=4) do not (G.convA 1212 -> 1269 us).
-  if (variant == 1 && L.cout_pad % 128 == 0) launch_conv_mt<4, 2>(a, s);
-  else if (variant == 2) launch_conv_mt<2, 2>(a, s);
-  else if (big_img && W >= 32) launch_conv_mt<2, 4>(a, s);
-  // two stacked 16x16 images per 512-pixel tile: correct, but register-staged prefetch spills at 128 accumulators
-  // (R.conv5 172 -> 318 us); kept behind the tuning hook until the staging moves to LDS-DMA
-  else if (variant == 4 && H == 16 && W == 16 && B >= 2) launch_conv_t<2, 16, 4, 2>(a, s);
+  // 128-channel row blocks with one workgroup per CU (MT=4) do not (G.convA 1212 -> 1269 us), nor do two stacked
+  // 16x16 images per 512-pixel tile (register-staged prefetch spills at 128 accumulators: R.conv5 172 -> 318 us).
+  if ((long)H * W >= 512 && W >= 32) launch_conv_t<2, 32, 4>(a, s);
   else launch_conv_mt<2, 2>(a, s);
 }
 
@@ -688,21 +678,9 @@ __device__ __forceinline__ f32x16 split_mma(const uint4* av, const uint4* bv, f3
     GR_M_(2, 0) GR_M_(1, 1) GR_M_(0, 2) GR_M_(1, 0) GR_M_(0, 1) GR_M_(0, 0)
 #undef GR_M_
   } else {
-#ifdef GR_PROBE_SHAPE16
-    // TIMING-ONLY probe build (tools/build_probe.sh; results are wrong by design): every v_mfma_f32_32x32x16_f16 replaced by two
-    // v_mfma_f32_16x16x32_f16 on the same operand registers and quarters of the same accumulator - same LDS reads, same multiply-adds,
-    // same register footprint.  What the instruction SHAPE alone would buy these kernels, before any re-tiling is written.
-    f32x4 q0 = {acc[0], acc[1], acc[2], acc[3]}, q1 = {acc[4], acc[5], acc[6], acc[7]}, q2 = {acc[8], acc[9], acc[10], acc[11]}, q3 = {acc[12], acc[13], acc[14], acc[15]};
-#define GR_Q_(i, j, qa, qb) qa = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[i]), __builtin_bit_cast(f16x8, bv[j]), qa, 0, 0, 0); \
-                            qb = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[i]), __builtin_bit_cast(f16x8, bv[j]), qb, 0, 0, 0);
-    GR_Q_(1, 0, q0, q1) GR_Q_(0, 1, q2, q3) GR_Q_(0, 0, q0, q1)
-#undef GR_Q_
-    acc = f32x16{q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3], q2[0], q2[1], q2[2], q2[3], q3[0], q3[1], q3[2], q3[3]};
-#else
 #define GR_M_(i, j) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[i]), __builtin_bit_cast(f16x8, bv[j]), acc, 0, 0, 0);
     GR_M_(1, 0) GR_M_(0, 1) GR_M_(0, 0)
 #undef GR_M_
-#endif
   }
   return acc;
 }
@@ -1198,9 +1176,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_wide_kernel(ConvArgs a, 
 // fp32.  A chunk's patch image [term][half][position] is then a pure gather of 16-byte vectors: it goes HBM -> LDS by
 // LDS-DMA (buffer_load_dwordx4 ... lds: 64 consecutive LDS slots per wave-instruction, per-lane source address; positions
 // outside the image are parked past the descriptor's range and arrive as zeros = the padding), the weight slab likewise.
-// No staging registers, no VALU work, no ds_write: per chunk a wave issues ~10 DMA instructions next to its 108 MFMAs.
-// Two LDS images; the DMA of the next chunk IN THE STREAM (tiles are walked persistently, so that is the next tile's first
-// chunk at a tile's end) is issued at the top of a chunk and waited for (vmcnt(0) + barrier) at its bottom.
+// No staging registers, no VALU work, no ds_write: per chunk a wave issues a few DMA instructions next to its MFMAs.
 constexpr int P16_PAD = 64;          // LDS regions are multiples of one wave-instruction's 64 vectors
 // Barrier that PUBLISHES LDS-DMA data: every wave first waits for its own DMA (s_waitcnt vmcnt(0), written out: hipcc's own
 // wait in front of __syncthreads() came out as vmcnt(8) in conv3x3_p16_quad_kernel - a wave could pass the barrier with DMA
@@ -1219,236 +1195,8 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, uint4* ld
   (void)rsrc; (void)lds_dst; (void)voff; (void)soff;
 #endif
 }
-// the same with the non-temporal cache policy (aux = 2): for streams that one workgroup reads once
-__device__ __forceinline__ void lds_dma16_nt(__amdgpu_buffer_rsrc_t rsrc, uint4* lds_dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 2);
-#else
-  (void)rsrc; (void)lds_dst; (void)voff; (void)soff;
-#endif
-}
-template <int TW, int NI>
-__global__ __launch_bounds__(512, 2) void conv3x3_p16_wide_kernel(ConvArgs a, const uint4* __restrict__ wsplit, const uint4* __restrict__ xin) {
-  constexpr int MT = 2, NTERM = 2;
-  constexpr int NG = 2, PT = 512, TR = PT / TW, IH = PT / (NI * TW), PR = NI * (IH + 2), PC = TW + 2, PS = PR * PC, CT = 32 * MT;
-  constexpr int PV = NTERM * 2 * PS, PVP = (PV + P16_PAD - 1) / P16_PAD * P16_PAD;      // patch vectors (padded to whole instructions)
-  constexpr int WROWS = NTERM * 9 * 2, WV = WROWS * CT;                                 // weight vectors: one instruction per row
-  constexpr int LBUF = PVP + WV;
-  constexpr int NPI = PVP / 64, NPS = (NPI + 7) / 8, NWS = (WROWS + 7) / 8;            // DMA instructions per chunk / per wave
-  static_assert((TW == 32 && NI == 1) || (TW == 16 && NI == 2), "tile_pixel assumes these tilings");
-  static_assert(CT == 64, "one weight row = one wave-instruction");
-  static_assert(2 * LBUF * 16 <= 160 * 1024, "LDS");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  uint4* lds = reinterpret_cast<uint4*>(smem_raw);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
-  const int H = a.H, W = a.W, HW = H * W;
-  const int G = a.Cin >> 3;                                        // 8-channel groups (Cin % 16 == 0 on this path)
-  struct Geo { int y0, x0, o0, b, tile; };
-  auto tile_geo = [&](int L) {
-    int bid = xcd_remap(L, a.n_tiles);
-    Geo g; g.tile = bid / a.n_otiles;
-    const int ot = bid % a.n_otiles; bid /= a.n_otiles;
-    const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y; g.b = (bid / a.tiles_y) * NI;
-    g.y0 = ty * TR; g.x0 = tx * TW; g.o0 = ot * CT;
-    return g;
-  };
-  const int nchunks = a.Cin / BF_CK;
-  // one descriptor for the whole activation tensor (< 2 GB), one for the weight image
-  const size_t xbytes = (size_t)a.B * G * 2 * HW * 16;
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(xin), 0, (int)(xbytes < 0x7FFFF000ul ? xbytes : 0x7FFFF000ul), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wsplit), 0,
-      (int)((size_t)nchunks * WROWS * a.cout_pad * 16), 0x00020000);
-  const int ktot = f16_scale_exp(absmax_read(a.amax_in)) + f16_scale_exp(absmax_read(a.amax_w));
-  // byte offset (chunk 0) of the source vector of patch slot e = 64 * (wave + 8 j) + lane, for this tile; parked when the
-  // slot is padding, outside the image, or past the batch
-  auto stage_offsets = [&](const Geo& g, int (&voff_)[NPS]) {
-#pragma unroll
-    for (int j = 0; j < NPS; ++j) {
-      const int e = 64 * (wave + 8 * j) + lane;
-      const int q = e / PS, pos = e - q * PS, t = q >> 1, hh = q & 1;     // plane q = term * 2 + half
-      const int rr = pos / PC, c = pos - rr * PC;
-      const int img = NI > 1 ? rr / (IH + 2) : 0, r = NI > 1 ? rr - img * (IH + 2) : rr;
-      const int yy = g.y0 + r - 1, xx = g.x0 + c - 1;
-      const bool inb = e < PV && yy >= 0 && yy < H && xx >= 0 && xx < W && g.b + img < a.B;
-      voff_[j] = inb ? ((((g.b + img) * G + hh) * 2 + t) * HW + (int)p16_pos((unsigned)(yy * W + xx))) * 16 : (int)0x7FFFF000;
-    }
-  };
-  int woff[NWS];                                                     // weight row r = wave + 8 j of the chunk's slab
-  auto weight_offsets = [&](const Geo& g) {
-#pragma unroll
-    for (int j = 0; j < NWS; ++j) { const int r = wave + 8 * j; woff[j] = r < WROWS ? (r * a.cout_pad + g.o0 + lane) * 16 : (int)0x7FFFF000; }
-  };
-  // LDS-DMA of chunk ch of the tile described by (voff_, woff) into image buf_
-#define GR_P16_DMA(buf_, ch_, voff_)                                                                      \
-  {                                                                                                       \
-    uint4* img_ = lds + (buf_) * LBUF;                                                                    \
-    const int psoff_ = (ch_) * HW * 64;                               /* 2 groups x 2 terms x HW x 16 B per chunk */ \
-    _Pragma("unroll") for (int j = 0; j < NPS; ++j) {                                                     \
-      const int i_ = wave + 8 * j;                                                                        \
-      if (i_ < NPI) lds_dma16(rin, img_ + 64 * i_, voff_[j], psoff_);                                     \
-    }                                                                                                     \
-    const int wsoff_ = (ch_) * WROWS * a.cout_pad * 16;                                                   \
-    _Pragma("unroll") for (int j = 0; j < NWS; ++j) {                                                     \
-      const int r_ = wave + 8 * j;                                                                        \
-      if (r_ < WROWS) lds_dma16(rwt, img_ + PVP + 64 * r_, woff[j], wsoff_);                              \
-    }                                                                                                     \
-  }
-  f32x16 acc[MT][NG];
-  int pix[NG];
-#pragma unroll
-  for (int ng = 0; ng < NG; ++ng) {
-    const int p = (wave * NG + ng) * 32 + l31; int prr, pc; tile_pixel<TW>(p, prr, pc);
-    const int pr = NI > 1 ? prr + 2 * (prr / IH) : prr;                   // skip the padding rows between stacked images
-    pix[ng] = h * PS + pr * PC + pc;
-  }
-#define GR_BF_OPS(patch, wts, tap_, av_, bv_)                                                            \
-    {                                                                                                     \
-      const int toff_ = ((tap_) / 3) * PC + ((tap_) % 3);                                                 \
-      _Pragma("unroll") for (int s = 0; s < NTERM; ++s) {                                                 \
-        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) av_[mt][s] = wts[((s * 9 + (tap_)) * 2 + h) * CT + mt * 32 + l31]; \
-        _Pragma("unroll") for (int ng = 0; ng < NG; ++ng) bv_[ng][s] = patch[s * 2 * PS + pix[ng] + toff_]; \
-      }                                                                                                   \
-    }
-#define GR_BF_MMA(av_, bv_)                                                                               \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                     \
-    _Pragma("unroll") for (int ng = 0; ng < NG; ++ng) acc[mt][ng] = split_mma<NTERM>(av_[mt], bv_[ng], acc[mt][ng]);
-#define GR_BF_PIN() __builtin_amdgcn_sched_group_barrier(0x100, (MT + NG) * NTERM, 0); __builtin_amdgcn_sched_group_barrier(0x008, MT * NG * 3, 0);
-  float omax = 0.f;
-  const int dbg = GR_DBG(a.up);                                              // diagnostic bit mask (0 in production): see g_p16_debug
-  int L = blockIdx.x;
-  Geo g = tile_geo(L);
-  int voff[NPS];
-  stage_offsets(g, voff);
-  weight_offsets(g);
-  int cc = 0;                                                        // chunks consumed so far: image cc & 1 holds the current one
-  GR_P16_DMA(0, 0, voff)
-  dma_publish_barrier();
-  for (;;) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int ng = 0; ng < NG; ++ng)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][ng][r] = 0.f;
-    const int Ln = L + (int)gridDim.x;
-    const bool more = Ln < a.n_tiles;
-    Geo gn = g; int voffn[NPS];
-#pragma unroll
-    for (int j = 0; j < NPS; ++j) voffn[j] = voff[j];
-    for (int ch = 0; ch < nchunks; ++ch, ++cc) {
-      // the other image is free since the barrier that ended the previous chunk: fetch the next chunk of the stream into it
-      if (ch + 1 < nchunks) { if (!(dbg & 4)) GR_P16_DMA((cc + 1) & 1, ch + 1, voff) }
-      else if (more) {                                               // last chunk of this tile: the next tile's first chunk
-        gn = tile_geo(Ln); stage_offsets(gn, voffn); weight_offsets(gn);
-        if (!(dbg & 4)) GR_P16_DMA((cc + 1) & 1, 0, voffn)
-      }
-      const uint4* pc_ = lds + (cc & 1) * LBUF; const uint4* wc_ = pc_ + PVP;
-      if (!(dbg & 8)) {
-      uint4 avA[MT][NTERM], bvA[NG][NTERM], avB[MT][NTERM], bvB[NG][NTERM];
-      GR_BF_OPS(pc_, wc_, 0, avA, bvA)
-      GR_BF_OPS(pc_, wc_, 1, avB, bvB) GR_BF_MMA(avA, bvA) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 2, avA, bvA) GR_BF_MMA(avB, bvB) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 3, avB, bvB) GR_BF_MMA(avA, bvA) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 4, avA, bvA) GR_BF_MMA(avB, bvB) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 5, avB, bvB) GR_BF_MMA(avA, bvA) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 6, avA, bvA) GR_BF_MMA(avB, bvB) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 7, avB, bvB) GR_BF_MMA(avA, bvA) GR_BF_PIN()
-      GR_BF_OPS(pc_, wc_, 8, avA, bvA) GR_BF_MMA(avB, bvB) GR_BF_PIN()
-      GR_BF_MMA(avA, bvA)
-      }
-      dma_publish_barrier();                                         // the DMA issued above has landed; every wave is past image cc & 1
-    }
-    const int y0 = g.y0, x0 = g.x0, o0 = g.o0, b = g.b;
-    bool pin[NG]; size_t obase[NG];
-#pragma unroll
-    for (int ng = 0; ng < NG; ++ng) {
-      const int p = (wave * NG + ng) * 32 + l31; int prr, pc; tile_pixel<TW>(p, prr, pc);
-      const int img = NI > 1 ? prr / IH : 0, pr = NI > 1 ? prr - img * IH : prr;
-      const int y = y0 + pr, x = x0 + pc;
-      pin[ng] = y < H && x < W && b + img < a.B;
-      obase[ng] = ((size_t)(b + img) * a.Cout * H + y) * W + x;
-    }
-    // scale back + bias in place
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int o = o0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const float bvv = (a.bias && o < a.Cout) ? a.bias[o] : 0.f;
-#pragma unroll
-        for (int ng = 0; ng < NG; ++ng) acc[mt][ng][r] = ldexpf(acc[mt][ng][r], -ktot) + bvv;
-      }
-    if (a.stat_part && !(dbg & 2)) {
-      // BatchNorm batch statistics of what is about to be stored (as in conv3x3_split_wide_kernel).  Scratch = the image the
-      // last chunk was read from (cc - 1): the other one already holds the next tile's first chunk.
-      float* red = reinterpret_cast<float*>(lds + ((cc - 1) & 1) * LBUF);   // [8 waves][2][32 channels][33]
-      float* rowsum = red + 8 * 2 * 32 * 33;                       // [512]
-      static_assert((8 * 2 * 32 * 33 + 512) * 4 <= LBUF * 16, "statistics scratch fits one image");
-      const int tile = g.tile;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float sv = 0.f, qv = 0.f;
-#pragma unroll
-          for (int ng = 0; ng < NG; ++ng) { const float v = pin[ng] ? acc[mt][ng][r] : 0.f; sv += v; qv += v * v; }
-          const int chl = (r & 3) + 8 * (r >> 2) + 4 * h;            // channel within this 32-channel block
-          red[((wave * 2 + 0) * 32 + chl) * 33 + l31] = sv;
-          red[((wave * 2 + 1) * 32 + chl) * 33 + l31] = qv;
-        }
-        __syncthreads();
-        {
-          const float* row = red + tid * 33;                         // row tid = (wave, quantity, channel)
-          float t = 0.f;
-#pragma unroll
-          for (int i = 0; i < 32; ++i) t += row[i];
-          rowsum[tid] = t;
-        }
-        __syncthreads();
-        if (tid < 64) {                                              // (quantity, channel): the 8 waves in order
-          const int wh = tid >> 5, chl = tid & 31;
-          double t = 0.0;
-#pragma unroll
-          for (int w = 0; w < 8; ++w) t += (double)rowsum[(w * 2 + wh) * 32 + chl];
-          const int o = o0 + mt * 32 + chl;
-          if (o < a.Cout) a.stat_part[((size_t)o * a.stat_tiles + tile) * 2 + wh] = t;
-        }
-        __syncthreads();
-      }
-    }
-#pragma unroll
-    for (int ng = 0; ng < NG; ++ng) {
-      if (pin[ng] && !(dbg & 1)) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int o = o0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (o < a.Cout) {
-            const float res = conv_epilogue(a.ep, acc[mt][ng][r], o);
-            a.out[obase[ng] + (size_t)o * H * W] = res;
-            omax = fmaxf(omax, fabsf(res));
-          }
-        }
-      }
-    }
-    if (!more) break;
-    L = Ln; g = gn;
-#pragma unroll
-    for (int j = 0; j < NPS; ++j) voff[j] = voffn[j];
-  }
-#undef GR_BF_OPS
-#undef GR_BF_MMA
-#undef GR_BF_PIN
-#undef GR_P16_DMA
-  if (a.amax_out) absmax_commit(omax, a.amax_out);
-}
-
-// ---------------------------------------------------------------- the same, as TWO independent workgroups per CU
-// Ablation of conv3x3_p16_wide_kernel on R.conv2 at cfg2 (tools/ablate_p16.py): skeleton 10.7 us + MFMA and LDS reads 35.5 +
-// output stores 22 + DMA 9 = the 76 us it takes - its eight waves move through DMA issue, multiply and epilogue in lock-step and
-// nothing overlaps.  Here a workgroup is FOUR waves (one per SIMD) that own the same 512-pixel x 64-channel tile, 128 pixels x
+// TWO independent workgroups per CU.  Round 2's eight-wave persistent kernel (two operand images) took 76 us on R.conv2 at cfg2,
+// its waves moving through DMA issue, multiply and epilogue in lock-step (docs/HISTORY.md).  Here a workgroup is FOUR waves (one per SIMD) that own a 512-pixel x 64-channel tile, 128 pixels x
 // 64 channels = 8 accumulator blocks per wave, with ONE operand image (76.8 KB): two workgroups are resident per CU and run
 // out of phase by themselves, so while one waits for its DMA or stores its tile the other one has the matrix pipe.  An operand
 // vector feeds more MFMAs than before (12 reads per 24 MFMAs per tap); staging and compute of ONE workgroup are serial
@@ -1477,7 +1225,6 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int H = a.H, W = a.W, HW = H * W;
   const int G = a.Cin >> 3;
-  const int dbg = GR_DBG(a.up);
   int bid = xcd_remap(blockIdx.x, a.n_tiles);
   const int tile = bid / a.n_otiles;
   const int ot = bid % a.n_otiles; bid /= a.n_otiles;
@@ -1511,7 +1258,7 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
     const int psoff_ = (ch_) * HW * 64;                                                                   \
     _Pragma("unroll") for (int j = 0; j < NPS; ++j) {                                                     \
       const int i_ = wave + NW * j;                                                                       \
-      if (i_ < NPI) { if (dbg & 16) lds_dma16_nt(rin, lds + 64 * i_, voff[j], psoff_); else lds_dma16(rin, lds + 64 * i_, voff[j], psoff_); } \
+      if (i_ < NPI) lds_dma16(rin, lds + 64 * i_, voff[j], psoff_);                                    \
     }                                                                                                     \
     const int wsoff_ = (ch_) * WROWS * a.cout_pad * 16;                                                   \
     _Pragma("unroll") for (int j = 0; j < NWS; ++j) {                                                     \
@@ -1534,27 +1281,6 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mt][ng][r] = 0.f;
   const uint4* patch = lds; const uint4* wts = lds + PVP;
-  // diagnostic build path (dbg & 32, never in production): wave 0 stamps its phases into a.wt (reused as a debug buffer)
-  unsigned long long* stamps = (dbg & 32) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(a.wt)) + (size_t)blockIdx.x * 32 : nullptr;
-  int nstamp = 0;
-#define GR_STAMP() if (stamps && tid == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamps[nstamp++] = t_; }
-  if (stamps && tid == 0) {
-    stamps[nstamp++] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | ((32 - 1) << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | ((32 - 1) << 11)) << 32);
-    unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamps[nstamp++] = t_;
-  }
-  GR_STAMP()
-  // The two workgroups of a CU should alternate (one multiplies while the other stages / stores).  A grid that fits the chip
-  // in one round starts them all together, in phase; the workgroups dispatched second (ids >= 256: observed placement, used
-  // for speed only) therefore start half a compute phase late.
-  // (which two workgroups share a CU is the dispatcher's business: the second one to arrive finds its waves in the odd wave
-  // slots of the SIMDs - HW_ID.wave_id - whatever its block index is)
-  if (a.nchunks > 0) {
-    const unsigned hwid = __builtin_amdgcn_s_getreg(4 | (0 << 6) | ((4 - 1) << 11));     // HW_REG_HW_ID bits [3:0] = wave slot on its SIMD
-    if (hwid & 1) {
-#pragma unroll 1
-      for (int i = 0; i < a.nchunks; ++i) __builtin_amdgcn_s_sleep(8);  // a.nchunks (unused otherwise on this path) = the delay in units of 8 x 64 clocks
-    }
-  }
   // PO: the evaluate()-mode BatchNorm coefficients of this workgroup's CT channels wait in LDS behind the operand image (the epilogue's 4 values per
   // channel as lane-dependent global loads - 64 per lane and 32-channel block, a round trip each - cost more than the multiplies of a 64-channel layer)
   float* bnp = reinterpret_cast<float*>(smem_raw + (size_t)LBUF * 16);
@@ -1564,33 +1290,27 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
       bnp[tid] = a.ep.mean[o]; bnp[CT + tid] = a.ep.invstd[o]; bnp[2 * CT + tid] = a.ep.gamma[o]; bnp[3 * CT + tid] = a.ep.beta[o];
     }
   }
-  if (!(dbg & 4)) GR_P16_DMA(0)
+  GR_P16_DMA(0)
   for (int ch = 0; ch < nchunks; ++ch) {
     dma_publish_barrier();                                           // the image holds chunk ch
-    GR_STAMP()
-    if (dbg & 256) __builtin_amdgcn_s_setprio(1);                     // experiment (GR_P16_DEBUG bit 256): the multiplying workgroup outranks its CU partner's epilogue / DMA issue
-    if (!(dbg & 8)) {
 #pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int toff = (tap / 3) * PC + (tap % 3);
-        uint4 av[MT][NTERM], bv[NG][NTERM];
+    for (int tap = 0; tap < 9; ++tap) {
+      const int toff = (tap / 3) * PC + (tap % 3);
+      uint4 av[MT][NTERM], bv[NG][NTERM];
 #pragma unroll
-        for (int s = 0; s < NTERM; ++s) {
+      for (int s = 0; s < NTERM; ++s) {
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) av[mt][s] = wts[((s * 9 + tap) * 2 + h) * CT + mt * 32 + l31];
+        for (int mt = 0; mt < MT; ++mt) av[mt][s] = wts[((s * 9 + tap) * 2 + h) * CT + mt * 32 + l31];
 #pragma unroll
-          for (int ng = 0; ng < NG; ++ng) bv[ng][s] = patch[s * 2 * PS + pix[ng] + toff];
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int ng = 0; ng < NG; ++ng) acc[mt][ng] = split_mma<NTERM>(av[mt], bv[ng], acc[mt][ng]);
+        for (int ng = 0; ng < NG; ++ng) bv[ng][s] = patch[s * 2 * PS + pix[ng] + toff];
       }
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int ng = 0; ng < NG; ++ng) acc[mt][ng] = split_mma<NTERM>(av[mt], bv[ng], acc[mt][ng]);
     }
-    if (dbg & 256) __builtin_amdgcn_s_setprio(0);
     __syncthreads();                                                 // every wave is past the image
-    GR_STAMP()
-    if (ch + 1 < nchunks && !(dbg & 4)) GR_P16_DMA(ch + 1)
+    if (ch + 1 < nchunks) GR_P16_DMA(ch + 1)
   }
 #undef GR_P16_DMA
   bool pin[NG]; size_t obase[NG];
@@ -1611,7 +1331,7 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
 #pragma unroll
       for (int ng = 0; ng < NG; ++ng) acc[mt][ng][r] = ldexpf(acc[mt][ng][r], -ktot) + bvv;
     }
-  if (a.stat_part && !(dbg & 2)) {
+  if (a.stat_part) {
     // BatchNorm batch statistics of what is about to be stored: per (wave, channel) 128 pixels = four per lane over 32 lanes;
     // the per-lane sums go through LDS transposed ([wave][quantity][channel][lane], row stride 33), one thread adds a row in
     // lane order, then the 4 waves are added in fp64 - a fixed order.  The operand image is dead by now.
@@ -1665,7 +1385,7 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
     const int pq = (wave * NG + (kq >> 3)) * 32 + 4 * (kq & 7); int prrq, pcq; tile_pixel<TW>(pq, prrq, pcq);
     const int imgq = NI > 1 ? prrq / IH : 0, prq = NI > 1 ? prrq - imgq * IH : prrq;
     const int yq = y0 + prq, xq = x0 + pcq;
-    const bool inq = yq < H && xq < W && b + imgq < a.B && !(dbg & 1);
+    const bool inq = yq < H && xq < W && b + imgq < a.B;
     float* outq = a.out + ((size_t)(b + imgq) * a.Cout * H + yq) * W + xq;
     // (training-mode stages store the raw output: the per-element epilogue switch is taken once per workgroup, not 128 times)
     const bool plain = a.ep.mean == nullptr && a.ep.act == ACT_NONE;
@@ -1726,8 +1446,8 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
               const int p = (wave * NG + ng) * 32 + l31; int prr, pc; tile_pixel<TW>(p, prr, pc);
               const int img = NI > 1 ? prr / IH : 0, pr = NI > 1 ? prr - img * IH : prr;
               uint4* dst = a.p16_out + ((size_t)(b + img) * Gout + grp) * 2 * HW + (size_t)(y0 + pr) * W + (x0 + pc);
-              store4(dst, make_uint4(X[ng][0][0], X[ng][0][1], X[ng][1][0], X[ng][1][1]), false);
-              store4(dst + HW, make_uint4(X[ng][0][2], X[ng][0][3], X[ng][1][2], X[ng][1][3]), false);
+              store4(dst, make_uint4(X[ng][0][0], X[ng][0][1], X[ng][1][0], X[ng][1][1]));
+              store4(dst + HW, make_uint4(X[ng][0][2], X[ng][0][3], X[ng][1][2], X[ng][1][3]));
             }
           }
         }
@@ -1759,7 +1479,7 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
         const int chl = CPI * i + hq, o = o0 + mt * 32 + chl;
         const float4 v = *reinterpret_cast<const float4*>(stg + chl * RS + 4 * kq);
         if (inq && o < a.Cout) {
-          store4(outq + (size_t)o * H * W, v, a.nt_out != 0);
+          store4(outq + (size_t)o * H * W, v);
           if (want_max) omax = absmax4(omax, v);
         }
       }
@@ -1767,8 +1487,6 @@ __device__ __forceinline__ void conv_p16_quad_body(const ConvArgs& a, const uint
     }
     }
   }
-  if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); GR_STAMP() if (tid == 0) { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamps[nstamp++] = t_; stamps[31] = nstamp; } }
-#undef GR_STAMP
   if (a.amax_out) absmax_commit(omax, a.amax_out);
 }
 template <int TW, int NI, int NG = 4, int MT = 2>
@@ -1966,10 +1684,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p16_k32_kernel(ConvArgs a, con
         if (o < a.Cout) a.stat_part[((size_t)o * a.stat_tiles + e_tile) * 2 + wh] = t;
       }
       lds_only_barrier();
-      if (GR_DBG(a.wt != nullptr)) {      // ablation build, GR_K32_FENCE_PROBE=1: what a release + arrival per unit would cost (a BatchNorm finalisation by the last arriver needs it)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        if (tid == 0) atomicAdd(reinterpret_cast<unsigned*>(const_cast<float*>(a.wt)) + (e_o0 / CT) * 32, 1u);
-      }
     }
     // output stores through the per-wave LDS transpose of the kernel above: [channel][pixel of the wave's 64] -> four consecutive pixels of a channel per lane
     float omax = 0.f;
@@ -1993,7 +1707,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p16_k32_kernel(ConvArgs a, con
         const int chl = CPI * i2 + hq, o = e_o0 + chl;
         const float4 v = *reinterpret_cast<const float4*>(stg + chl * RS + 4 * kq);
         if (inimg && o < a.Cout) {
-          store4(outq + (size_t)o * H * W, v, a.nt_out != 0);
+          store4(outq + (size_t)o * H * W, v);
           if (want_max) omax = absmax4(omax, v);
         }
       }
@@ -2255,7 +1969,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_up2_f16x3_kernel(ConvArgs a, c
           const int o = o0 + mb * 16 + q * 4 + r;
           const float4 res = up2_pair_rows(v + (mb * 4 + r) * 4, odd);   // every lane takes part in the exchange
           if (pin && o < a.Cout) {
-            store4(orow + (size_t)o * a.H * a.W, res, a.nt_out != 0);
+            store4(orow + (size_t)o * a.H * a.W, res);
             omax = absmax4(omax, res);
           }
         }
@@ -2314,7 +2028,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_up2q_f16x3_kernel(ConvArgs a, 
   const int kin = f16_scale_exp(absmax_read(a.amax_in));
   const int ktot = kin + f16_scale_exp(absmax_read(a.amax_w)) - 2;   // summed weights: up to 4 max|w|
   const float sc_in = pow2f(kin);
-  const int dbg = GR_DBG(a.up >> 1);            // diagnostic ablations (gr_set_tuning "up2_debug"; outputs are then wrong by design): 1 no stores, 2 no MFMA, 4 no activation staging, 8 no weight DMA
   int voff[NSL], eoff[NSL];
 #pragma unroll
   for (int s = 0; s < NSL; ++s) {
@@ -2376,28 +2089,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_up2q_f16x3_kernel(ConvArgs a, 
     pix[nb] = hh * PSL + prr * PC + pc + dxq;                       // patch row prr = source row y - 1; column slot dx reads x - 1 + b + dx
   }
   const int wq = dxq * 64 + hh * 32 + l15;
-  // The two workgroups of a CU run the same program from (almost) the same start: left alone they stay IN phase - both convert,
-  // both multiply (sharing the matrix pipe), both store - and the phases add up instead of overlapping (ablation, round 3:
-  // skeleton 38 + MFMA 122 + staging 62 + stores 34 = 256 us against 246 measured on G.convB at cfg2).  The workgroup whose waves
-  // sit in the odd wave slots of their SIMDs (HW_ID.wave_id: the one that arrived second, whatever its block index) starts late
-  // by a.nchunks x 512 clocks (gr_set_tuning "up2_stagger"), about half a chunk iteration.
-  if (a.nchunks > 0) {
-    const unsigned hwid = __builtin_amdgcn_s_getreg(4 | (0 << 6) | ((4 - 1) << 11));     // HW_REG_HW_ID bits [3:0] = wave slot on its SIMD
-    if (hwid & 1) {
-#pragma unroll 1
-      for (int i = 0; i < a.nchunks; ++i) __builtin_amdgcn_s_sleep(8);
-    }
-  }
-  if (!(dbg & 4)) GR_UQ_LOAD(0)
-  if (!(dbg & 8)) GR_UQ_DMAW(0)
+  // (the two workgroups of a CU run in phase, their phases adding up - round 3: skeleton 38 + MFMA 122 + staging 62 + stores 34 =
+  // 256 us against 246 measured on G.convB at cfg2; a start delay for the second one did not help)
+  GR_UQ_LOAD(0)
+  GR_UQ_DMAW(0)
   for (int ch = 0; ch < nchunks; ++ch) {
-    if (!(dbg & 4)) GR_UQ_STORE(ch)                                // the image is free: every wave passed the barrier below
+    GR_UQ_STORE(ch)                                                // the image is free: every wave passed the barrier below
     dma_publish_barrier();                                         // this chunk's weights have landed, every wave's patch stores are visible
-    if (ch + 1 < nchunks && !(dbg & 4)) GR_UQ_LOAD(ch + 1)         // lands behind the MFMAs
-    if (!(dbg & 2))
-    { GR_UP16_ROW(patch, wts, 0) GR_UP16_ROW(patch, wts, 1) GR_UP16_ROW(patch, wts, 2) }
+    if (ch + 1 < nchunks) GR_UQ_LOAD(ch + 1)                       // lands behind the MFMAs
+    GR_UP16_ROW(patch, wts, 0) GR_UP16_ROW(patch, wts, 1) GR_UP16_ROW(patch, wts, 2)
     __syncthreads();                                               // every wave is past the image
-    if (ch + 1 < nchunks && !(dbg & 8)) GR_UQ_DMAW(ch + 1)
+    if (ch + 1 < nchunks) GR_UQ_DMAW(ch + 1)
   }
 #undef GR_UQ_LOAD
 #undef GR_UQ_DMAW
@@ -2410,7 +2112,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_up2q_f16x3_kernel(ConvArgs a, 
   for (int nb = 0; nb < NB; ++nb) {
     const int p = (wave * NB + nb) * 16 + l15; int prr, pc; tile_pixel<TW>(p, prr, pc);
     const int y = y0 + prr, x = x0 + pc;
-    const bool pin = y < Hs && x < Ws && b < a.B && !(dbg & 1);
+    const bool pin = y < Hs && x < Ws && b < a.B;
     float v[32];                                                   // [mb][r][pa][pb]
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
@@ -2438,7 +2140,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_up2q_f16x3_kernel(ConvArgs a, 
           const int o = o0 + mb * 16 + q * 4 + r;
           const float4 res = up2_pair_rows(v + (mb * 4 + r) * 4, odd);
           if (pin && o < a.Cout) {
-            store4(orow + (size_t)o * a.H * a.W, res, a.nt_out != 0);
+            store4(orow + (size_t)o * a.H * a.W, res);
             omax = absmax4(omax, res);
           }
         }
@@ -2519,14 +2221,7 @@ template <int TW, int NI>
 static void launch_conv_up2_t(const ConvArgs& a, const void* wup, hipStream_t s) {
   constexpr int IH = 512 / (NI * TW), PS = NI * (IH + 2) * (TW + 2), PSL = (PS + 15) / 16 * 16;
   constexpr bool FITS = 2 * 16 * (2 * 2 * PSL + 2 * 2 * 8 * 2 * 32) + 5 * 32 * 4 <= 160 * 1024;    // two LDS images where they fit (not the 8-wide tile)
-#ifdef GR_ABLATE      // GR_UP2_DB=0: one LDS image where two fit (the A/B control; the shipping library instantiates the kernel it launches)
-  static int db = -1;
-  if (db < 0) { db = GR_KNOB("GR_UP2_DB", 1); }
-  if (FITS && db) launch_conv_up2_db<TW, NI, FITS>(a, wup, s);
-  else launch_conv_up2_db<TW, NI, false>(a, wup, s);
-#else
   launch_conv_up2_db<TW, NI, FITS>(a, wup, s);
-#endif
 }
 template <int TW, int NI>
 static void launch_conv_up2q(ConvArgs a, const void* wup, hipStream_t s) {
@@ -2534,7 +2229,6 @@ static void launch_conv_up2q(ConvArgs a, const void* wup, hipStream_t s) {
   const int Hs = a.H / 2, Ws = a.W / 2;
   a.tiles_x = (Ws + TW - 1) / TW; a.tiles_y = (Hs + TR - 1) / TR;
   a.cout_pad = round_up(a.Cout, 32); a.n_otiles = a.cout_pad / 32;
-  a.nchunks = g_up2_stagger;
   const size_t lds = 16 * (size_t)(PVP + 2 * 2 * 8 * 2 * 32) + 5 * 32 * 4;       // + the epilogue's per-channel block
   const int grid = a.B * a.tiles_x * a.tiles_y * a.n_otiles;
   static bool attr_set = false;
@@ -2549,16 +2243,14 @@ void launch_conv3x3_up2_f16x3(const float* in, const void* wup, const float* bia
                               hipStream_t s, const ConvEpilogue* ep, const unsigned* amax_in, const unsigned* amax_w, unsigned* amax_out) {
   ConvArgs a{};
   if (ep) a.ep = *ep;
-  a.in = in; a.bias = bias; a.out = out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.up = 1 | (g_up2_debug << 1); a.nt_out = (g_nt_stores >> 1) & 1;
+  a.in = in; a.bias = bias; a.out = out; a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.up = 1;
   a.amax_in = amax_in; a.amax_w = amax_w; a.amax_out = amax_out;
-  const int Ws = W / 2, Hs = H / 2;
-  const int quad = g_up2_quad;                                       // 0: the eight-wave kernels everywhere (A/B runs: gr_set_tuning "up2_quad", GR_UP2_QUAD)
+  const int Ws = W / 2;
   if (Ws == 8) launch_conv_up2_t<8, 8>(a, wup, s);
   // four-wave kernel: measured (round 3, same process, interleaved): 32-wide source tiles 1591 us against 1689 (G.convB at cfg3), 16x16
   // source planes 1499 against 1464 (G.convA at cfg3) and 210 against 203 (G.convB at cfg2) - so only the 32-wide tiles take it
-  // (quad = 2 forces it onto the 16x16 planes too: tools/ablate_up2.py)
-  else if (Ws == 16) { if (quad >= 2 && Hs == 16) launch_conv_up2q<16, 1>(a, wup, s); else launch_conv_up2_t<16, 2>(a, wup, s); }
-  else { if (quad) launch_conv_up2q<32, 1>(a, wup, s); else launch_conv_up2_t<32, 1>(a, wup, s); }
+  else if (Ws == 16) launch_conv_up2_t<16, 2>(a, wup, s);
+  else launch_conv_up2q<32, 1>(a, wup, s);
 }
 
 // ---------------------------------------------------------------- max|x| of a tensor (f16x3 scale tracking)
@@ -2653,11 +2345,9 @@ static void launch_conv_split_wide_db(ConvArgs a, const void* wsplit, hipStream_
   a.n_tiles = ((a.B + NI - 1) / NI) * a.tiles_x * a.tiles_y * a.n_otiles;
   a.stat_tiles = a.n_tiles / a.n_otiles;
   // persistent workgroups: one per CU with two LDS images, two with one (a multiple of 8 so that a workgroup's tiles stay
-  // on its XCD); GR_CONV_PERSIST=0 launches one workgroup per tile
-  static int persist = -1;
-  if (persist < 0) { persist = GR_KNOB("GR_CONV_PERSIST", 1); }
+  // on its XCD)
   const int resident = 256 * (DB ? 1 : 2);
-  const int grid = (persist && a.n_tiles > resident) ? resident : a.n_tiles;
+  const int grid = a.n_tiles > resident ? resident : a.n_tiles;
   static bool attr_set = false;
   if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_wide_kernel<TW, NI, NTERM, DB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
   // as rocprofv3 prints it: <TW, NI, NTERM (3 = bf16x6, 2 = f16x3), double-buffered>
@@ -2669,15 +2359,8 @@ static void launch_conv_split_wide_db(ConvArgs a, const void* wsplit, hipStream_
 template <int TW, int NI, int NTERM>
 static void launch_conv_split_wide(const ConvArgs& a, const void* wsplit, hipStream_t s) {
   // two f16x3 images fit the 160 KB LDS (152-157 KB): double-buffered; three-term bf16 images do not
-#ifdef GR_ABLATE      // GR_CONV_DB=0: single-buffered f16x3 images (the A/B control)
-  static int db = -1;
-  if (db < 0) { db = GR_KNOB("GR_CONV_DB", 1); }
-  if (NTERM == 2 && db) launch_conv_split_wide_db<TW, NI, 2, true>(a, wsplit, s);
-  else launch_conv_split_wide_db<TW, NI, NTERM, false>(a, wsplit, s);
-#else
   if constexpr (NTERM == 2) launch_conv_split_wide_db<TW, NI, 2, true>(a, wsplit, s);
   else launch_conv_split_wide_db<TW, NI, NTERM, false>(a, wsplit, s);
-#endif
 }
 
 // returns the number of statistics tiles written per channel (0: the chosen kernel does not produce them)
@@ -2687,22 +2370,19 @@ static int launch_conv3x3_split_n(ConvArgs a, const void* wsplit, hipStream_t s)
   const double* want_stats = a.stat_part;
   a.stat_part = nullptr;
   ConvArgs aw = a; aw.stat_part = const_cast<double*>(want_stats);      // only the 512-pixel kernels fill it
-  static int variant = -1;
-  if (variant < 0) { variant = GR_KNOB("GR_BF16X6_VARIANT", 0); }
-  const bool wide = round_up(Cout, 32) % 64 == 0 && variant != 1;      // 64 output channels per workgroup (8 waves share one patch)
-  static const bool stack8 = !GR_KNOB_SET("GR_NO_STACK8");
+  const bool wide = round_up(Cout, 32) % 64 == 0;      // 64 output channels per workgroup (8 waves share one patch)
   // four 8x8 images per tile - while that still leaves half a workgroup per CU (batch 32 of the GAN game: 32 workgroups stacked, 0.38 -> 0.45 ms;
   // batch 256: 1.37 -> 0.5 ms)
   const long st_tiles = (B + 3) / 4, cp32 = round_up(Cout, 32) / 32;
-  if (stack8 && W == 8 && H == 8 && !a.up && wide && st_tiles * (cp32 / 2) >= g_stack8_min_wgs) launch_conv_split_t<8, 2, NTERM, 4>(a, wsplit, s);
-  else if (stack8 && W == 8 && H == 8 && !a.up && st_tiles * cp32 >= g_stack8_min_wgs) launch_conv_split_t<8, 1, NTERM, 4>(a, wsplit, s);
+  if (W == 8 && H == 8 && !a.up && wide && st_tiles * (cp32 / 2) >= g_stack8_min_wgs) launch_conv_split_t<8, 2, NTERM, 4>(a, wsplit, s);
+  else if (W == 8 && H == 8 && !a.up && st_tiles * cp32 >= g_stack8_min_wgs) launch_conv_split_t<8, 1, NTERM, 4>(a, wsplit, s);
   else if (W <= 8) launch_conv_split_t<8, 1, NTERM>(a, wsplit, s);
   else if (W <= 16) {
     // two stacked 16x16 images per 512-pixel tile (G.convA 799 -> 716 us) when that still leaves a workgroup for every CU
-    if (wide && variant != 4 && H == 16 && W == 16 && (long)((B + 1) / 2) * (round_up(Cout, 32) / 64) >= 256) { launch_conv_split_wide<16, 2, NTERM>(aw, wsplit, s); return want_stats ? ((B + 1) / 2) : 0; }
+    if (wide && H == 16 && W == 16 && (long)((B + 1) / 2) * (round_up(Cout, 32) / 64) >= 256) { launch_conv_split_wide<16, 2, NTERM>(aw, wsplit, s); return want_stats ? ((B + 1) / 2) : 0; }
     else if (wide) launch_conv_split_t<16, 2, NTERM>(a, wsplit, s); else launch_conv_split_t<16, 1, NTERM>(a, wsplit, s);
   }
-  else if (wide && variant != 4 && (long)H * W >= 512 && (long)B * ((H * W + 511) / 512) * (round_up(Cout, 32) / 64) >= 256) { launch_conv_split_wide<32, 1, NTERM>(aw, wsplit, s); return want_stats ? B * ((W + 31) / 32) * ((H + 15) / 16) : 0; }   // measured: -6 % vs the 256-pixel tile
+  else if (wide && (long)H * W >= 512 && (long)B * ((H * W + 511) / 512) * (round_up(Cout, 32) / 64) >= 256) { launch_conv_split_wide<32, 1, NTERM>(aw, wsplit, s); return want_stats ? B * ((W + 31) / 32) * ((H + 15) / 16) : 0; }   // measured: -6 % vs the 256-pixel tile
   else { if (wide) launch_conv_split_t<32, 2, NTERM>(a, wsplit, s); else launch_conv_split_t<32, 1, NTERM>(a, wsplit, s); }
   return 0;
 }
@@ -2747,25 +2427,15 @@ void launch_conv3x3_split(const float* in, const void* wsplit, const float* bias
   if (stat_tiles) *stat_tiles = nt;
 }
 
-// f16x3 convolution on an operand-ready (P16) activation: see conv3x3_p16_wide_kernel
-int g_p16_debug = 0;
-int g_up2_quad = GR_KNOB("GR_UP2_QUAD", 1);
-int g_up2_stagger = GR_KNOB("GR_UP2_STAGGER", 0);
-int g_nt_stores = GR_KNOB("GR_NT_STORES", 0);      // kernels.h store4: which kernels store non-temporally (measured: no effect; off)
-int g_up2_debug = 0;       // diagnostic ablations of conv3x3_up2q_f16x3_kernel (gr_set_tuning "up2_debug")
-void* g_p16_stamps = nullptr;     // diagnostic: device buffer of 32 x 8 bytes per workgroup (gr_debug_stamps)
+// f16x3 convolution on an operand-ready (P16) activation: see conv3x3_p16_quad_kernel
 int g_stack8_min_wgs = 128;     // smallest grid at which 8x8 planes are stacked four to a tile (gr_set_tuning("stack8_min_wgs"): tests force the path)
 int g_p16_min_tiles = 128;      // below half a workgroup per CU the 256-pixel-tile kernels fill the chip better (gr_set_tuning("p16_min_tiles"): tests force the path)
 bool conv_p16_supported(int B, int Cin, int Cout, int H, int W) {
-  static int on = -1;
-  if (on < 0) { on = GR_KNOB_SET("GR_NO_P16") ? 0 : 1; }
-  if (!on || Cin % 16 != 0 || (H * W) % 256 != 0 || round_up(Cout, 32) % 64 != 0 || (size_t)B * Cin * H * W * 4 >= 0x7FFFF000ul) return false;
+  if (Cin % 16 != 0 || (H * W) % 256 != 0 || round_up(Cout, 32) % 64 != 0 || (size_t)B * Cin * H * W * 4 >= 0x7FFFF000ul) return false;
   const long otiles = round_up(Cout, 32) / 64;
   if (H == 16 && W == 16) return (long)((B + 1) / 2) * otiles >= g_p16_min_tiles;
   return W >= 32 && W % 32 == 0 && H % 16 == 0 && (long)B * (H / 16) * (W / 32) * otiles >= g_p16_min_tiles;
 }
-int g_p16_stagger = 0;           // start delay (x 512 clocks) of the second-dispatched workgroups: measured useless (tools/stagger_p16.py), kept as a knob
-int g_p16_variant = 1;          // 1: four-wave workgroups, two per CU (conv3x3_p16_quad_kernel); 0: eight-wave persistent (conv3x3_p16_wide_kernel)
 template <int TW, int NI, int NG = 4, int MT = 2>
 static int launch_conv_p16_quad(ConvArgs a, const void* wsplit, const void* xin, hipStream_t s) {
   constexpr int PT = 128 * NG, TR = PT / TW, IH = PT / (NI * TW), PS = NI * (IH + 2) * (TW + 2), CT = 32 * MT;
@@ -2776,13 +2446,7 @@ static int launch_conv_p16_quad(ConvArgs a, const void* wsplit, const void* xin,
   a.n_tiles = ((a.B + NI - 1) / NI) * a.tiles_x * a.tiles_y * a.n_otiles;
   a.stat_tiles = a.n_tiles / a.n_otiles;
   static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_p16_quad_kernel<TW, NI, NG, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true;
-    if (GR_KNOB_SET("GR_DEBUG_OCC")) {
-      int nb = -1; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv3x3_p16_quad_kernel<TW, NI, NG, MT>), 256, lds);
-      fprintf(stderr, "conv3x3_p16_quad_kernel<%d, %d> (NG %d): %zu B LDS per workgroup, occupancy query says %d workgroups per CU\n", TW, NI, NG, lds, nb);
-    }
-  }
+  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_p16_quad_kernel<TW, NI, NG, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
   static const std::string name = "conv3x3_p16_quad_kernel<" + std::to_string(TW) + ", " + std::to_string(NI) + ", " + std::to_string(NG) + ", " + std::to_string(MT) + ">";   // as rocprofv3 prints it (default template arguments included)
   const double px = (double)a.B * a.H * a.W;
   if (a.p16_out) {      // evaluate() mode: the result leaves operand-ready (same kernel body, its own symbol)
@@ -2799,30 +2463,7 @@ static int launch_conv_p16_quad(ConvArgs a, const void* wsplit, const void* xin,
   hipLaunchKernelGGL((conv3x3_p16_quad_kernel<TW, NI, NG, MT>), dim3(a.n_tiles), dim3(256), lds, s, a, reinterpret_cast<const uint4*>(wsplit), reinterpret_cast<const uint4*>(xin));
   return a.stat_tiles;
 }
-template <int TW, int NI>
-static int launch_conv_p16_t(ConvArgs a, const void* wsplit, const void* xin, hipStream_t s) {
-#ifndef GR_ABLATE      // the eight-wave persistent kernel (conv3x3_p16_wide_kernel, round 2) lost to the four-wave one: ablation build only ("p16_variant" 0)
-  return launch_conv_p16_quad<TW, NI>(a, wsplit, xin, s);
-#else
-  if (g_p16_variant == 1) return launch_conv_p16_quad<TW, NI>(a, wsplit, xin, s);
-  constexpr int TR = 512 / TW, IH = 512 / (NI * TW), PS = NI * (IH + 2) * (TW + 2), CT = 64;
-  constexpr int PVP = (4 * PS + P16_PAD - 1) / P16_PAD * P16_PAD, LBUF = PVP + 36 * CT;
-  a.tiles_x = (a.W + TW - 1) / TW; a.tiles_y = NI > 1 ? 1 : (a.H + TR - 1) / TR;
-  a.cout_pad = round_up(a.Cout, 32); a.n_otiles = a.cout_pad / CT;
-  const size_t lds = 2 * 16 * (size_t)LBUF;
-  a.n_tiles = ((a.B + NI - 1) / NI) * a.tiles_x * a.tiles_y * a.n_otiles;
-  a.stat_tiles = a.n_tiles / a.n_otiles;
-  const int grid = a.n_tiles > 256 ? 256 : a.n_tiles;                 // persistent: one workgroup per CU walks the tiles
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_p16_wide_kernel<TW, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-  static const std::string name = "conv3x3_p16_wide_kernel<" + std::to_string(TW) + ", " + std::to_string(NI) + ">";   // as rocprofv3 prints it
-  const double px = (double)a.B * a.H * a.W;
-  KtScope kt(name.c_str(), 2.0 * px * a.Cout * a.Cin * 9.0, 4.0 * (px * a.Cin + px * a.Cout + 9.0 * a.Cin * a.Cout), s);
-  hipLaunchKernelGGL((conv3x3_p16_wide_kernel<TW, NI>), dim3(grid), dim3(512), lds, s, a, reinterpret_cast<const uint4*>(wsplit), reinterpret_cast<const uint4*>(xin));
-  return a.stat_tiles;
-#endif
-}
-bool conv_p16_out_supported(int Cout) { return g_p16_variant == 1 && Cout % 8 == 0; }
+bool conv_p16_out_supported(int Cout) { return Cout % 8 == 0; }
 // 256-pixel x 32-channel tiles, 32-channel chunks on v_mfma_f32_16x16x32_f16 (conv3x3_p16_k32_kernel): training-mode output only
 template <int TW>
 static int launch_conv_p16_k32(ConvArgs a, const void* wsplit, const void* xin, hipStream_t s) {
@@ -2837,13 +2478,9 @@ static int launch_conv_p16_k32(ConvArgs a, const void* wsplit, const void* xin, 
   static const std::string name = "conv3x3_p16_k32_kernel<" + std::to_string(TW) + ">";
   const double px = (double)a.B * a.H * a.W;
   KtScope kt(name.c_str(), 2.0 * px * a.Cout * a.Cin * 9.0, 4.0 * (px * a.Cin + px * a.Cout + 9.0 * a.Cin * a.Cout), s);
-  // two resident workgroups per CU walk the units (a multiple of 8 workgroups: blockIdx.x & 7 = the XCD, and xcd_remap keys the unit's place on that);
-  // GR_K32_PERSIST=0 (ablation build): one workgroup per unit, as in rounds 3-4
-  static const int persist = GR_KNOB("GR_K32_PERSIST", 1);
-#ifdef GR_ABLATE
-  { static unsigned* probe = nullptr; if (GR_KNOB("GR_K32_FENCE_PROBE", 0)) { if (!probe) { (void)hipMalloc((void**)&probe, 4096); (void)hipMemset(probe, 0, 4096); } a.wt = reinterpret_cast<const float*>(probe); } }
-#endif
-  const int grid = (persist && a.n_tiles > 512) ? 512 : a.n_tiles;
+  // two resident workgroups per CU walk the units (a multiple of 8 workgroups: blockIdx.x & 7 = the XCD, and xcd_remap keys the unit's place on that;
+  // one workgroup per unit, as in rounds 3-4, measured slower: profiles/r05_ab_k32_persistent_cfg2.txt)
+  const int grid = a.n_tiles > 512 ? 512 : a.n_tiles;
   hipLaunchKernelGGL(conv3x3_p16_k32_kernel<TW>, dim3(grid), dim3(256), lds, s, a, reinterpret_cast<const uint4*>(wsplit), reinterpret_cast<const uint4*>(xin));
   return a.stat_tiles;
 }
@@ -2852,27 +2489,19 @@ void launch_conv3x3_p16(const void* x_p16, const void* wsplit, const float* bias
                         double* stat_part, int* stat_tiles, const P16Out* p16o) {
   ConvArgs a{};
   if (ep) a.ep = *ep;
-  if (p16o && p16o->p16 && g_p16_variant == 1) { a.p16_out = reinterpret_cast<uint4*>(p16o->p16); a.p16_scale = p16o->scale; }
-  a.in = nullptr; a.wt = (g_p16_debug & 32) ? reinterpret_cast<const float*>(g_p16_stamps) : nullptr; a.bias = bias; a.out = out;
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.up = g_p16_debug; a.nchunks = g_p16_stagger; a.nt_out = g_nt_stores & 1;
+  if (p16o && p16o->p16) { a.p16_out = reinterpret_cast<uint4*>(p16o->p16); a.p16_scale = p16o->scale; }
+  a.in = nullptr; a.wt = nullptr; a.bias = bias; a.out = out;
+  a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.up = 0;
   a.amax_in = amax_in; a.amax_w = amax_w; a.amax_out = amax_out;
   a.stat_part = stat_tiles ? stat_part : nullptr;
-  // 16x16 planes: two-image tiles when they still give two workgroups per CU, single-image tiles otherwise
-  static const int single = GR_KNOB("GR_P16_SINGLE", 1);
+  // 16x16 planes: two-image tiles when they still give two workgroups per CU; single-image tiles otherwise, with 32-channel output tiles
+  // (four workgroups per CU: six launches 0.303 -> 0.294 ms at cfg2), as 32-channel chunks on the 16x16x32 MFMA where the output is plain
   const long two_img_tiles = (long)((B + 1) / 2) * (round_up(Cout, 32) / 64);
-  int nt;
-  static const int narrow = GR_KNOB("GR_P16_NARROW", 1);     // 32-channel output tiles on single-image tiles: four workgroups per CU (six launches 0.303 -> 0.294 ms at cfg2: small, the L2 -> LDS traffic doubles)
-  static const int k32 = GR_KNOB("GR_P16_K32", 1);      // 32-channel chunks on the 16x16x32 MFMA where the single-image narrow tiles run (0: the 32x32x16 kernel, the A/B control)
   const bool plain_out = a.ep.mean == nullptr && a.ep.act == ACT_NONE && !a.p16_out && out != nullptr;
-  if (H == 16 && W == 16 && k32 && single && narrow && g_p16_variant == 1 && two_img_tiles < 512 && Cin % 32 == 0 && plain_out && !g_p16_debug) nt = launch_conv_p16_k32<16>(a, wsplit, x_p16, s);
-  else if (k32 >= 2 && !(H == 16 && W == 16) && g_p16_variant == 1 && W % 32 == 0 && H % 8 == 0 && Cin % 32 == 0 && plain_out && !g_p16_debug) nt = launch_conv_p16_k32<32>(a, wsplit, x_p16, s);      // experiment: 8-row tiles of 32-wide planes
-  else if (H == 16 && W == 16) nt = (single && g_p16_variant == 1 && two_img_tiles < 512) ? (narrow ? launch_conv_p16_quad<16, 1, 2, 1>(a, wsplit, x_p16, s) : launch_conv_p16_quad<16, 1, 2>(a, wsplit, x_p16, s))
-                                                                                  : launch_conv_p16_t<16, 2>(a, wsplit, x_p16, s);
-  else {
-    static const int half32 = GR_KNOB("GR_P16_HALF32", 0);     // 256-pixel tiles (8 rows x 32) on wider planes
-    const long tiles512 = (long)B * ((H + 15) / 16) * ((W + 31) / 32) * (round_up(Cout, 32) / 64);
-    nt = (half32 && g_p16_variant == 1 && H % 8 == 0 && tiles512 < half32) ? launch_conv_p16_quad<32, 1, 2>(a, wsplit, x_p16, s) : launch_conv_p16_t<32, 1>(a, wsplit, x_p16, s);
-  }
+  int nt;
+  if (H == 16 && W == 16 && two_img_tiles < 512 && Cin % 32 == 0 && plain_out) nt = launch_conv_p16_k32<16>(a, wsplit, x_p16, s);
+  else if (H == 16 && W == 16) nt = two_img_tiles < 512 ? launch_conv_p16_quad<16, 1, 2, 1>(a, wsplit, x_p16, s) : launch_conv_p16_quad<16, 2>(a, wsplit, x_p16, s);
+  else nt = launch_conv_p16_quad<32, 1>(a, wsplit, x_p16, s);
   if (stat_tiles) *stat_tiles = stat_part ? nt : 0;
 }
 
@@ -3750,54 +3379,15 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_tiled_kernel(const f
   }
 }
 
-#ifdef GR_ABLATE
-// Probe (ablation build, GR_WGRAD_REDUCE_PROBE=1): what "the LAST ARRIVER of an (output block, channel block) tile sums its tile's
-// splits" costs - ONE workgroup per tile walks the tile's 9 x 64 x 64 / 4 float4 positions and adds the nsplit slabs in split order, exactly the reads the
-// folded epilogue would issue from the last workgroup of the producer (a lower bound: the real thing also waits for the slowest split).  Result discarded
-// (written to the slab's first split, which nobody reads afterwards).  Timed by the kernel timer as "wgrad_reduce_one_wg_probe".
-__global__ __launch_bounds__(512) void conv3x3_wgrad_reduce_one_wg_probe_kernel(float4* __restrict__ slab, int n_ob, int n_cb, int nsplit, long n4) {
-  const int tile = blockIdx.x;                                    // (tap-major slab: tile t owns positions [tap][t][1024 float4] for the 9 taps)
-  for (int i = threadIdx.x; i < 9 * 1024; i += 512) {
-    const int tap = i >> 10, w = i & 1023;
-    const long f = ((long)tap * n_ob * n_cb + tile) * 1024 + w;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    int k = 0;
-    for (; k + 8 <= nsplit; k += 8) {
-      float4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = slab[(size_t)(k + u) * n4 + f];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
-    }
-    for (; k < nsplit; ++k) { const float4 v = slab[(size_t)k * n4 + f]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-    slab[f] = s;
-  }
-}
-#endif
-__global__ void conv3x3_wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw,
-                                            int Cin, int Cout, int cinp, int coutp, int nsplit) {
-  const long n = (long)9 * Cout * cinp;
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int ci = (int)(i % cinp); long r = i / cinp;
-  const int o = (int)(r % Cout); const int tap = (int)(r / Cout);
-  if (ci >= Cin) return;
-  const size_t stride = (size_t)9 * coutp * cinp;
-  const float* p = slab + ((size_t)tap * coutp + o) * cinp + ci;
-  float s = 0.f;
-  for (int k = 0; k < nsplit; ++k) s += p[(size_t)k * stride];
-  gw[((size_t)o * Cin + ci) * 9 + tap] += s;
-}
-
 // ---------------------------------------------------------------- weight gradient on operand-ready (P16) x and dy
 // gw[o][ci][ky][kx] += sum over (b, y, x) of dy[b, o, y, x] * x[b, ci, y + ky - 1, x + kx - 1]  as nine GEMMs with
 // M = o, N = ci, K = pixels, three f16 MFMA products per 16-pixel step (dy0 x0, dy0 x1, dy1 x0).  Both operands sit in HBM as
 // [pixel][8 channels] fp16 vectors (P16) whose K index - the pixel - is the ROW of the LDS image, so the MFMA fragments (8
 // consecutive k of one channel per lane) come out of LDS by the transposing read ds_read_b64_tr_b16 (4 pixels x 16 channels
 // per 16 lanes), and a tap is nothing but a row offset into the zero-padded x patch: no shifted copies, no v_alignbit, no
-// conversion - the image of 64 pixels (dy: 16 KB) and its padded x patch (35 KB) arrive by LDS-DMA.  Workgroup = 4 waves =
-// 64 o x 64 ci (wave: 32 x 32, nine accumulators), single LDS image, two workgroups per CU; K is split over workgroups
-// (contiguous runs of 64-pixel chunks), partial sums go to the slab the existing reduction adds up.
+// conversion - the image of 64 pixels (dy: 16 KB) and its padded x patch (35 KB) arrive by LDS-DMA.  A half-workgroup of 4 waves
+// owns 64 o x 64 ci (wave: 32 x 32, nine accumulators) with one LDS image; K is split over workgroups (contiguous runs of 64-pixel
+// chunks), partial sums go to the slab the existing reduction adds up.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 lds_tr16(const uint4* vec, int byte_off) {     // vec: a 16-byte LDS vector; byte_off: 0 or 8
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -3811,8 +3401,6 @@ struct WgradP16Args {
   const uint4* x; const uint4* dy; float* slab;
   int B, Cin, Cout, H, W, n_ob, n_cb, nsplit, cinp, coutp, units;     // units = B * H * W / 64 chunks of 64 pixels
   const unsigned *amax_x, *amax_dy;
-  int dy_nt;               // non-temporal LDS-DMA of the dy stream (four-wave kernel)
-  int plain_order;         // GR_WGRAD_PLAIN_ORDER=1: consecutive block ids = the combinations of one split (A/B of the XCD-aware numbering)
 };
 // MFMA shape: v_mfma_f32_16x16x32_f16, K = 32 pixels per step, the wave's 32 x 32 block per tap as 2 x 2 accumulator blocks of 16 x 16 (a
 // 16-lane group of a transposing read covers 8 pixels of ONE 16-channel block).  Round 3, same box, against the 32x32x16 version (16 pixels
@@ -3825,7 +3413,7 @@ struct WgradP16Args {
 // walk the splits.  Speed only: any placement computes the same slabs.
 __device__ __forceinline__ void wgrad_p16_block(const WgradP16Args& a, int bid, int& cb, int& ob, int& split) {
   const int C = a.n_cb * a.n_ob;
-  if (C > 1 && a.nsplit % 8 == 0 && !a.plain_order) {
+  if (C > 1 && a.nsplit % 8 == 0) {
     const int grp = bid / (8 * C), rem = bid - grp * 8 * C, combo = rem >> 3;
     split = grp * 8 + (rem & 7);
     cb = combo % a.n_cb; ob = combo / a.n_cb;
@@ -3834,150 +3422,14 @@ __device__ __forceinline__ void wgrad_p16_block(const WgradP16Args& a, int bid, 
     ob = bid % a.n_ob; split = bid / a.n_ob;
   }
 }
-template <int W_>
-__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_p16_kernel(WgradP16Args a) {
-  constexpr int R = 64 / W_ > 0 ? 64 / W_ : 1;                 // image rows per 64-pixel chunk (W_ = 16, 32 or 64)
-  constexpr int PR = R + 2, PC = W_ + 2, PS = PR * PC;          // x patch positions
-  // plane strides (vectors) padded to 2 (mod 8): the four 8-channel groups a transposing read touches then start 64 bytes apart
-  // in the 256-byte bank row (unpadded: 32-wide planes put all four on the same banks, and the dy planes of every width)
-  constexpr int PSP = PS + (10 - PS % 8) % 8, DSP = 66;
-  constexpr int XV = 16 * PSP, XVP = (XV + 63) / 64 * 64, DV = (16 * DSP + 63) / 64 * 64;      // vectors: 8 groups x 2 terms x positions
-  constexpr int NXI = XVP / 64, NXS = (NXI + 3) / 4, NDS = 4;   // DMA instructions per wave: x patch, dy (16 planes / 4 waves)
-  static_assert(W_ == 16 || W_ == 32 || W_ == 64, "plane widths of this path");
-  static_assert(2 * (XVP + DV) * 16 <= 160 * 1024, "two workgroups per CU");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  uint4* xs = reinterpret_cast<uint4*>(smem_raw);               // [ci group 8][term 2][PS]
-  uint4* ds = xs + XVP;                                         // [o group 8][term 2][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
-  // wave tile: ALL 64 output channels x the wave's 16 input channels x 9 taps.  A tap's x fragment cannot be shared between taps, so what a B read
-  // feeds is the number of output-channel blocks it meets: four here (52 transposing-read pairs per 108 MFMAs) against two with 32 x 32 tiles
-  // (80 per 108) - these kernels sat at 87-92 % LDS-active on the counters (round 3, profiles/r03_pmc_step_conv_cfg3.txt)
-  int cb, ob, split;
-  wgrad_p16_block(a, blockIdx.x, cb, ob, split);
-  const int H = a.H, HW = H * W_, Gin = a.Cin >> 3, Gout = a.Cout >> 3;
-  const int cpi = HW / 64;                                      // chunks per image
-  const int u0 = (int)((long)split * a.units / a.nsplit), u1 = (int)((long)(split + 1) * a.units / a.nsplit);
-  const size_t xbytes = (size_t)a.B * Gin * 2 * HW * 16, dbytes = (size_t)a.B * Gout * 2 * HW * 16;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(a.x), 0, (int)(xbytes < 0x7FFFF000ul ? xbytes : 0x7FFFF000ul), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(a.dy), 0, (int)(dbytes < 0x7FFFF000ul ? dbytes : 0x7FFFF000ul), 0x00020000);
-  const int ktot = f16_scale_exp(absmax_read(a.amax_x)) + f16_scale_exp(absmax_read(a.amax_dy));
-  f32x4 acc[9][4];                                              // [tap][16-o block]: lane = ci (16 wave + li), register = o 16 mo + 4 G + r
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[t][m][r] = 0.f;
-  // transposing-read addresses for v_mfma_f32_16x16x32_f16 (K = 32 pixels per step): 16-lane group G = lane >> 4 covers pixels 8 G .. +3
-  // (+4 for the second read) of ONE 16-channel block; lane 4q + p of the group points at pixel row q, channels 4p .. 4p+3 of that block
-  const int li = lane & 15, q = li >> 2, pp = li & 3, G = lane >> 4;
-  const int chg = pp >> 1, boff = 8 * (pp & 1);                  // 8-channel group within the 16-channel block, byte offset in the vector
-  const int pxl = 8 * G + q;                                     // pixel within a 32-pixel step (first read; second: + 4)
-  // per-lane vector addresses of step 0, block 0; a step or a block adds a uniform offset.  x patch: 32 pixels are two rows of a 16-wide plane
-  const uint4* abase = ds + chg * 2 * DSP + pxl;
-  const uint4* bbase = xs + (wave * 2 + chg) * 2 * PSP + (W_ == 16 ? (pxl >> 4) * PC + (pxl & 15) : pxl);
-  // DMA addresses: the flat index -> (plane, row, column) decomposition of a patch vector does not depend on the chunk, only the
-  // image (scalar offset of the instruction) and the chunk's first row do.  Per lane and instruction: static byte offset with the
-  // patch row in its low 4 bits (15 = never valid).  (Recomputing it per chunk cost ~30 VALU instructions per DMA instruction:
-  // 7 VALU per MFMA on the counters.)
-  int xst[NXS], dst_[NDS];
-#pragma unroll
-  for (int j = 0; j < NXS; ++j) {
-    const int i = wave + 4 * j, e = 64 * i + lane;
-    const int pl = e / PSP, pos = e - pl * PSP, g = pl >> 1, t = pl & 1, rr = pos / PC, c = pos - rr * PC, xx = c - 1;
-    const bool valid = i < NXI && e < XV && pos < PS && xx >= 0 && xx < W_;
-    xst[j] = valid ? (((((cb * 8 + g) * 2 + t) * HW + (rr - 1) * W_ + xx) * 16 + W_ * 16) | rr) : 15;      // (+ one row: rr - 1 may be -1; taken off again below)
-  }
-#pragma unroll
-  for (int j = 0; j < NDS; ++j) {
-    const int pl = wave + 4 * j, g = pl >> 1, t = pl & 1;
-    dst_[j] = (((ob * 8 + g) * 2 + t) * HW + lane) * 16;
-  }
-  for (int u = u0; u < u1; ++u) {
-    const int b = u / cpi, cidx = u - b * cpi, p0 = cidx * 64, y0 = p0 / W_;      // the chunk's 64 pixels: rows y0 .. y0 + R - 1 (W_ = 64: one row)
-    __syncthreads();                                             // every wave is past the previous chunk's image
-    // x patch: flat vector index e = 64 i + lane over [group][term][position]
-    const int xsoff = b * Gin * 2 * HW * 16, dsoff = b * Gout * 2 * HW * 16;      // the image: scalar offsets (uniform)
-    const int yrow = (y0 - 1) * W_ * 16, p0b = p0 * 16;
-#pragma unroll
-    for (int j = 0; j < NXS; ++j) {
-      const int i = wave + 4 * j, rr = xst[j] & 15;
-      const bool inb = rr != 15 && (unsigned)(y0 + rr - 1) < (unsigned)H;
-      const int voff = inb ? (xst[j] & ~15) + yrow : (int)0x7FFFF000;
-      if (i < NXI) lds_dma16(rx, xs + 64 * i, voff, xsoff);
-    }
-    // dy is streamed once per (input-channel block): with the non-temporal policy its lines do not push the x rows - re-read by the next
-    // chunk - out of the XCD's L2 (a.dy_nt: GR_WGRAD_DY_NT)
-    if (a.dy_nt) {
-#pragma unroll
-      for (int j = 0; j < NDS; ++j) lds_dma16_nt(rd, ds + DSP * (wave + 4 * j), dst_[j] + p0b, dsoff);
-    } else {
-#pragma unroll
-      for (int j = 0; j < NDS; ++j) lds_dma16(rd, ds + DSP * (wave + 4 * j), dst_[j] + p0b, dsoff);      // plane = (o group, term): 64 pixels = one instruction
-    }
-    dma_publish_barrier();                                       // the image has landed
-#pragma unroll 1
-    for (int ks = 0; ks < 2; ++ks) {
-      const int srow = (32 * ks) / W_, scol = 32 * ks - srow * W_;     // the step's 32 pixels start at row srow of the chunk, column scol
-      // A = dy: [o][k]; two transposing reads (4 pixels each) per term and 16-channel block
-      uint4 av[4][2];
-#pragma unroll
-      for (int mo = 0; mo < 4; ++mo)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const uint4* base = abase + (mo * 4 + t) * DSP + 32 * ks;
-          const uint2 lo = lds_tr16(base, boff), hi = lds_tr16(base + 4, boff);
-          av[mo][t] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-        }
-      const uint4* bstep = bbase + srow * PC + scol;
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int ky = tap / 3, kx = tap - 3 * ky;
-        uint4 bv[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          // (the second read is 4 pixels further along x: same row - 8-pixel runs never straddle a row, W_ % 16 == 0)
-          const uint4* base = bstep + t * PSP + ky * PC + kx;
-          const uint2 lo = lds_tr16(base, boff), hi = lds_tr16(base + 4, boff);
-          bv[t] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-        }
-#pragma unroll
-        for (int mo = 0; mo < 4; ++mo) {
-          f32x4 c_ = acc[tap][mo];
-          c_ = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[mo][1]), __builtin_bit_cast(f16x8, bv[0]), c_, 0, 0, 0);
-          c_ = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[mo][0]), __builtin_bit_cast(f16x8, bv[1]), c_, 0, 0, 0);
-          c_ = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[mo][0]), __builtin_bit_cast(f16x8, bv[0]), c_, 0, 0, 0);
-          acc[tap][mo] = c_;
-        }
-      }
-    }
-  }
-  // Slab in the ACCUMULATORS' own order, [split][tap][ob][cb][wo][wc][q = r / 4][lane] float4 = registers 4q .. 4q+3 of a lane (four
-  // output channels of one input channel): 36 16-byte stores per lane, every wave-instruction 1 KB contiguous.  The [tap][o][ci]
-  // order it replaces (round 3) took 144 dword stores per lane - a store-ISSUE-bound tail (MI355X_MICROARCH.md: dword / dwordx2
-  // store tails run at a few bytes per clock per CU) that was most of the kernel's fixed ~23 us.  conv3x3_wgrad_reduce_tiled_kernel
-  // reads the same order back with 16-byte loads and scatters only the final 9 * Cout * Cin values.
-  float4* slp = reinterpret_cast<float4*>(a.slab) + (size_t)split * 9 * a.coutp * a.cinp / 4;
-  // (accumulator block mo of wave w, lane group G: output channels 16 mo + 4 G .. + 3 of input channel 16 w + li - entered at the slab position
-  // [wo][wc][q][lane] that a 32 x 32 accumulator layout gives that (o, ci) quad: the format conv3x3_wgrad_reduce_tiled_kernel reads)
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-    for (int mo = 0; mo < 4; ++mo) {
-      const int wo = mo >> 1, wc = wave >> 1, qs = 2 * (mo & 1) + (G >> 1), ls = 32 * (G & 1) + 16 * (wave & 1) + li;
-      const size_t f = ((((((size_t)tap * a.n_ob + ob) * a.n_cb + cb) * 2 + wo) * 2 + wc) * 4 + qs) * 64 + ls;
-      const f32x4 c_ = acc[tap][mo];
-      slp[f] = make_float4(ldexpf(c_[0], -ktot), ldexpf(c_[1], -ktot), ldexpf(c_[2], -ktot), ldexpf(c_[3], -ktot));
-    }
-}
-// The same with the two workgroups of a CU fused into ONE of eight waves whose halves PING-PONG: while half A multiplies its
-// chunk, half B requests its next chunk by DMA and waits for it; a workgroup barrier swaps the roles.  Four-wave workgroups
-// left this to chance (both resident workgroups often loaded, or multiplied, at the same time); here a multiplying half always
+// ONE workgroup of eight waves per CU, in two halves.  On 16-wide planes the halves PING-PONG: while half A multiplies its
+// chunk, half B requests its next chunk by DMA and waits for it; a workgroup barrier swaps the roles.  Two four-wave workgroups per CU
+// (rounds 2-4) left this to chance (both resident workgroups often loaded, or multiplied, at the same time); here a multiplying half always
 // has the matrix pipe to itself and a loading half always has a full multiply phase to hide its DMA behind.  Each half
 // accumulates its own part of the workgroup's pixel range; at the end half B's accumulators go through LDS into half A's, so
 // the kernel leaves HALF as many slabs (one per CU instead of two): half the slab write and half the reduction.
 // FREE (round 5): the halves do NOT alternate - each runs load -> multiply over its own chunks behind a barrier of its own four waves (an LDS arrival counter:
-// gfx950 has no named barriers), exactly as two four-wave workgroups of conv3x3_wgrad_p16_kernel would, and they meet only for the hand-over at the end.  On
+// gfx950 has no named barriers), exactly as two four-wave workgroups would, and they meet only for the hand-over at the end.  On
 // 32-wide planes strict alternation lost (70 -> 98 us: the load phase is longer than the multiply phase); free-running halves keep the four-wave kernel's
 // timing and still leave ONE slab per CU instead of two - half the slab write and half the reduction.
 __device__ __forceinline__ void half_barrier(unsigned* cnt, unsigned& target, int lane) {
@@ -4170,27 +3622,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_p16_pp_kernel(WgradP16Ar
       slp[f] = make_float4(ldexpf(c_[0], -ktot), ldexpf(c_[1], -ktot), ldexpf(c_[2], -ktot), ldexpf(c_[3], -ktot));
     }
 }
-// GR_WGRAD_PP: 1 (default) = the ping-pong kernel on 16-wide planes only, 2 = everywhere, 0 = never.  Measured at cfg2 per launch:
-// 16-wide 52 -> 50 us, and the slab reduction 16.5 -> 10.8 us; 32-wide 70 -> 98 us (its 34 KB x patch per 64 pixels makes the
-// load phase longer than the multiply phase, and strict alternation then idles the matrix pipe more than chance did).
-static int wgrad_pp_mode() { static int v = -1; if (v < 0) { v = GR_KNOB("GR_WGRAD_PP", 1); } return v; }
-// GR_WGRAD_FREE (ablation build): planes at least this wide take the free-running halves (default 32: the 32- and 64-wide layers); 0 = never (rounds 3-4)
-static int wgrad_free_from() { static const int v = GR_KNOB("GR_WGRAD_FREE", 32); return v; }
-static bool wgrad_free(int W) { return wgrad_free_from() > 0 && W >= wgrad_free_from() && wgrad_pp_mode() != 2; }
-static bool wgrad_pp(int W) { const int m = wgrad_pp_mode(); return m == 2 || (m == 1 && W == 16) || wgrad_free(W); }
-template <int W_, bool FREE_>
-static void launch_wgrad_p16_pp_tf(const WgradP16Args& a, int grid, size_t lds, hipStream_t s) {
+// Ping-pong on 16-wide planes, free-running halves on the 32- and 64-wide ones.  Measured at cfg2 per launch against two four-wave
+// workgroups per CU: 16-wide 52 -> 50 us, and the slab reduction 16.5 -> 10.8 us; 32-wide ping-pong 70 -> 98 us (its 34 KB x patch per
+// 64 pixels makes the load phase longer than the multiply phase, and strict alternation then idles the matrix pipe more than chance did).
+template <int W_>
+static void launch_wgrad_p16_pp_t(const WgradP16Args& a, int grid, size_t lds, hipStream_t s) {
+  constexpr bool FREE_ = W_ >= 32;
   static bool st = false;
   if (!st) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wgrad_p16_pp_kernel<W_, FREE_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + 64); st = true; }
   hipLaunchKernelGGL((conv3x3_wgrad_p16_pp_kernel<W_, FREE_>), dim3(grid), dim3(512), lds + (FREE_ ? 64 : 0), s, a);
-}
-template <int W_>
-static void launch_wgrad_p16_pp_t(const WgradP16Args& a, int grid, size_t lds, hipStream_t s) {
-#ifdef GR_ABLATE      // every (width, variant) pair exists in the ablation build only; the shipping library instantiates what it launches: <16, false>, <32, true>, <64, true>
-  if (wgrad_free(W_)) launch_wgrad_p16_pp_tf<W_, true>(a, grid, lds, s); else launch_wgrad_p16_pp_tf<W_, false>(a, grid, lds, s);
-#else
-  launch_wgrad_p16_pp_tf<W_, (W_ >= 32)>(a, grid, lds, s);
-#endif
 }
 
 static bool wgrad_use_vec(int W) { return W >= 16 && W % 4 == 0; }
@@ -4210,7 +3650,11 @@ static void wgrad_geometry(int B, int Cin, int Cout, int H, int W, WgradArgs& a,
   // measured (B=256): 32-wide planes 512 splits (two workgroups per CU overlap convert/store with MFMAs), 16-wide planes 256
   // measured (f16x3): 512 partial blocks pay off on 32-wide planes once there are many row steps per block (cfg3: 1.75 vs 1.93 ms),
   // 256 otherwise (cfg2: the slab round trip of the extra blocks costs more than the overlap gains, -0.02 ms)
-  else if (split) { want = GR_KNOB("GR_WGRAD_SPLITS", ((TW == 32 && (long)B * H * a.tiles_x >= 16384) ? 512 : 256)) / (a.n_ob * a.n_cb); }
+  else if (split) {
+    constexpr int SPLIT_BLOCKS_MANY = 512, SPLIT_BLOCKS = 256;
+    constexpr long MANY_ROW_STEPS = 16384;          // B x H x tiles_x
+    want = ((TW == 32 && (long)B * H * a.tiles_x >= MANY_ROW_STEPS) ? SPLIT_BLOCKS_MANY : SPLIT_BLOCKS) / (a.n_ob * a.n_cb);
+  }
   if (want < 1) want = 1;
   if (want > a.tiles_total) want = a.tiles_total;
   a.nsplit = (int)want;
@@ -4224,43 +3668,27 @@ size_t conv_wgrad_workspace_bytes(int B, int Cin, int Cout, int H, int W, int mo
 }
 
 template <int NTERM>
-static void launch_wgrad_split(const WgradArgs& a, int TW, int rps, int wv, int grid_, hipStream_t s) {
+static void launch_wgrad_split(const WgradArgs& a, int TW, int rps, int grid_, hipStream_t s) {
   if (rps > 0) {
     if (TW == 16) hipLaunchKernelGGL((conv3x3_wgrad_split_roll_kernel<16, NTERM>), dim3(grid_), dim3(256), 0, s, a, rps);
     else hipLaunchKernelGGL((conv3x3_wgrad_split_roll_kernel<32, NTERM>), dim3(grid_), dim3(256), 0, s, a, rps);
-  } else if (TW == 16) {
-    if (wv == 1) hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<16, 1, NTERM>), dim3(grid_), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<16, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);
-  } else {
-    if (wv == 1) hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<32, 1, NTERM>), dim3(grid_), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<32, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);
-  }
+  } else if (TW == 16) hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<16, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<32, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);
 }
 
 bool conv_wgrad_p16_supported(int B, int Cin, int Cout, int H, int W) {
-  static int on = -1;
-  if (on < 0) { on = GR_KNOB_SET("GR_NO_P16_WGRAD") ? 0 : 1; }
-  return on && Cin % 64 == 0 && Cout % 64 == 0 && (W == 16 || W == 32 || W == 64) && (H * W) % 256 == 0 &&
+  return Cin % 64 == 0 && Cout % 64 == 0 && (W == 16 || W == 32 || W == 64) && (H * W) % 256 == 0 &&
          (size_t)B * (Cin > Cout ? Cin : Cout) * H * W * 4 < 0x7FFFF000ul;
 }
 static int wgrad_p16_splits(int B, int Cin, int Cout, int H, int W) {
   const int blocks = (Cin / 64) * (Cout / 64);
-  static int wgs_env = -1;
-  if (wgs_env < 0) { wgs_env = GR_KNOB("GR_WGRAD_P16_WGS", 0); }
-  const int wgs = wgs_env ? wgs_env : (wgrad_pp(W) ? 256 : 512);      // ping-pong: ONE eight-wave workgroup per CU; else two four-wave ones
-  int want = wgs / blocks; if (want < 1) want = 1;
+  int want = 256 / blocks; if (want < 1) want = 1;                    // ONE eight-wave workgroup per CU
   const long units = (long)B * H * W / 64;
   if (want > units) want = (int)units;
   return want;
 }
 size_t conv_wgrad_p16_workspace_bytes(int B, int Cin, int Cout, int H, int W) {
   return sizeof(float) * (size_t)wgrad_p16_splits(B, Cin, Cout, H, W) * 9 * Cin * Cout;
-}
-template <int W_>
-static void launch_wgrad_p16_t(const WgradP16Args& a, int grid, size_t lds, hipStream_t s) {
-  static bool st = false;
-  if (!st) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wgrad_p16_kernel<W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); st = true; }
-  hipLaunchKernelGGL(conv3x3_wgrad_p16_kernel<W_>, dim3(grid), dim3(256), lds, s, a);
 }
 void launch_conv3x3_wgrad_p16(const void* x_p16, const void* dy_p16, float* gw, void* workspace, int B, int Cin, int Cout, int H, int W,
                               hipStream_t s, const unsigned* amax_x, const unsigned* amax_dy) {
@@ -4269,34 +3697,19 @@ void launch_conv3x3_wgrad_p16(const void* x_p16, const void* dy_p16, float* gw, 
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.n_ob = Cout / 64; a.n_cb = Cin / 64; a.cinp = Cin; a.coutp = Cout;
   a.nsplit = wgrad_p16_splits(B, Cin, Cout, H, W); a.units = (int)((long)B * H * W / 64);
   a.amax_x = amax_x; a.amax_dy = amax_dy;
-  { static const int plain = GR_KNOB("GR_WGRAD_PLAIN_ORDER", 0); a.plain_order = plain; }
-  { static const int dynt = GR_KNOB("GR_WGRAD_DY_NT", 0); a.dy_nt = dynt; }
   const int grid = a.nsplit * a.n_ob * a.n_cb;
   const double px = (double)B * H * W;
   {
     const int R = 64 / W > 0 ? 64 / W : 1, PS = (R + 2) * (W + 2), PSP = PS + (10 - PS % 8) % 8;
     const size_t lds = 16 * (size_t)((16 * PSP + 63) / 64 * 64 + (16 * 66 + 63) / 64 * 64);
-    const std::string nm = "conv3x3_wgrad_p16_kernel<" + std::to_string(W) + ">";
-    const std::string nm2 = "conv3x3_wgrad_p16_pp_kernel<" + std::to_string(W) + (wgrad_free(W) ? ", true>" : ", false>");      // as rocprofv3 prints them (FREE = true: free-running halves)
-    KtScope kt(wgrad_pp(W) ? nm2.c_str() : nm.c_str(), 2.0 * px * Cout * Cin * 9.0, 4.0 * (px * Cin + px * Cout + 9.0 * Cin * Cout), s);
-    if (wgrad_pp(W)) {
-      if (W == 16) launch_wgrad_p16_pp_t<16>(a, grid, 2 * lds, s); else if (W == 32) launch_wgrad_p16_pp_t<32>(a, grid, 2 * lds, s); else launch_wgrad_p16_pp_t<64>(a, grid, 2 * lds, s);
-    }
-#ifdef GR_ABLATE      // two four-wave workgroups per CU (rounds 2-4): an A/B control now
-    else if (W == 16) launch_wgrad_p16_t<16>(a, grid, lds, s); else if (W == 32) launch_wgrad_p16_t<32>(a, grid, lds, s); else launch_wgrad_p16_t<64>(a, grid, lds, s);
-#endif
+    const std::string nm = "conv3x3_wgrad_p16_pp_kernel<" + std::to_string(W) + (W >= 32 ? ", true>" : ", false>");      // as rocprofv3 prints it (FREE = true: free-running halves)
+    KtScope kt(nm.c_str(), 2.0 * px * Cout * Cin * 9.0, 4.0 * (px * Cin + px * Cout + 9.0 * Cin * Cout), s);
+    if (W == 16) launch_wgrad_p16_pp_t<16>(a, grid, 2 * lds, s); else if (W == 32) launch_wgrad_p16_pp_t<32>(a, grid, 2 * lds, s); else launch_wgrad_p16_pp_t<64>(a, grid, 2 * lds, s);
   }
   const long n_ = (long)9 * Cout * a.cinp;
   KtScope kt("conv3x3_wgrad_reduce_tiled_kernel", (double)n_ * a.nsplit, 4.0 * n_ * (a.nsplit + 2.0), s);
   hipLaunchKernelGGL(conv3x3_wgrad_reduce_tiled_kernel, dim3((unsigned)((n_ / 4 + 31) / 32)), dim3(256), 0, s, reinterpret_cast<const float4*>(a.slab), gw,
                      Cin, Cout, a.n_ob, a.n_cb, a.nsplit);
-#ifdef GR_ABLATE
-  { static const int probe = GR_KNOB("GR_WGRAD_REDUCE_PROBE", 0);
-    if (probe) {
-      KtScope kt2("wgrad_reduce_one_wg_probe", (double)n_ * a.nsplit, 4.0 * n_ * a.nsplit, s);
-      hipLaunchKernelGGL(conv3x3_wgrad_reduce_one_wg_probe_kernel, dim3(a.n_ob * a.n_cb), dim3(512), 0, s, reinterpret_cast<float4*>(a.slab), a.n_ob, a.n_cb, a.nsplit, n_ / 4);
-    } }
-#endif
 }
 
 void launch_conv3x3_wgrad(const float* x, const float* dy, float* gw, void* workspace,
@@ -4310,11 +3723,9 @@ void launch_conv3x3_wgrad(const float* x, const float* dy, float* gw, void* work
     const double px_ = (double)B * H * W;
     {
       const int grid_ = a.nsplit * a.n_ob * a.n_cb;
-      static int wv = -1;
-      if (wv < 0) { wv = GR_KNOB("GR_WGRAD_VARIANT", 2); }   // 2: rolling-window kernel; 1: per-tile kernel (AGPR accumulators)
       const int TRr = 32 / TW;
-      int rps = 0;                                                 // rows per segment of the rolling-window kernel
-      if (wv == 2 && H % TRr == 0) {
+      int rps = 0;                                                 // rows per segment of the rolling-window kernel (0: the per-tile kernel)
+      if (H % TRr == 0) {
         // longest run of rows (a divisor of H, multiple of TR) that still yields >= grid_ segments
         for (int cand = H; cand >= TRr; --cand)
           if (H % cand == 0 && cand % TRr == 0) {
@@ -4324,9 +3735,9 @@ void launch_conv3x3_wgrad(const float* x, const float* dy, float* gw, void* work
       }
       const std::string nt_ = mode == 2 ? "2>" : "3>";      // as rocprofv3 prints them: last template argument = number of split terms
       const std::string nm_ = rps > 0 ? std::string("conv3x3_wgrad_split_roll_kernel<") + (TW == 16 ? "16, " : "32, ") + nt_
-                                      : std::string("conv3x3_wgrad_split_kernel<") + (TW == 16 ? "16, " : "32, ") + (wv == 1 ? "1, " : "2, ") + nt_;
+                                      : std::string("conv3x3_wgrad_split_kernel<") + (TW == 16 ? "16, 2, " : "32, 2, ") + nt_;
       KtScope kt(nm_.c_str(), 2.0 * px_ * Cout * Cin * 9.0, 4.0 * (px_ * Cin + px_ * Cout + 9.0 * Cin * Cout), s);
-      if (mode == 2) launch_wgrad_split<2>(a, TW, rps, wv, grid_, s); else launch_wgrad_split<3>(a, TW, rps, wv, grid_, s);
+      if (mode == 2) launch_wgrad_split<2>(a, TW, rps, grid_, s); else launch_wgrad_split<3>(a, TW, rps, grid_, s);
     }
     const long n_ = (long)9 * Cout * a.cinp;
     KtScope kt("conv3x3_wgrad_reduce8_kernel", (double)n_ * a.nsplit, 4.0 * n_ * (a.nsplit + 2.0), s);

@@ -55,8 +55,6 @@ __device__ __forceinline__ void post_specialize(PostArgs& f) {
   if (CB == 11) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_SCALE; f.pool = 1; f.m2.kind = MASK_NONE; }
 }
 inline int post_combo(const PostArgs& f) {
-  static const bool on = !GR_KNOB_SET("GR_POST_GENERIC");
-  if (!on) return 0;
   if (!f.has_bn && f.m2.kind == MASK_NONE) {
     if (f.act == ACT_PRELU && f.m1.kind == MASK_NONE && !f.pool) return 4;
     if (f.act == ACT_NONE && f.m1.kind == MASK_SPATIAL && f.pool) return 5;
@@ -205,13 +203,12 @@ __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(
 // what does get reused.  Measured in the real step (round 3, same box, interleaved): cfg3 (268 / 537 MB tensors) pass A 1.02-1.04 ->
 // 0.955-0.964 ms, pass B 1.105 -> 0.991 ms; cfg2 (34 / 67 MB tensors, which pass B finds in the cache) pass B 0.168 -> 0.182 ms
 // (slower, and mostly because a non-temporal pass A no longer leaves the tensors in the cache for it).  So: passes A and B above 128 MB
-// only (launchers; GR_POST_NT overrides: bit 0 pass A, 1 pass B, 2 forward).
+// only (launchers).
 typedef float nt_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld4_maybe_nt(const float* p, bool nt) {
   if (nt) { const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
   return *reinterpret_cast<const float4*>(p);
 }
-inline int post_nt_mode() { static const int m = GR_KNOB("GR_POST_NT", -1); return m; }   // -1: the size rule; else bit 0 pass A, 1 pass B, 2 forward
 inline bool post_big(const PostArgs& f) { return 4.0 * f.B * f.C * f.H * f.W >= 128.0 * 1024 * 1024; }
 
 template <int CB>
@@ -393,10 +390,8 @@ __global__ __launch_bounds__(256) void to_p16_kernel(const float* __restrict__ x
     }
   }
 }
-// LDS tile of the 8-channel-group pipeline kernels: 2 = 256 pixels (9 KB per workgroup, eight workgroups per CU; default), 1 = 512,
-// 0 = 1024 (34 KB, four per CU).  Measured per step, pass B / forward: cfg2 0.228 / 0.148 -> 0.207 / 0.135 -> 0.199 / 0.139 ms,
-// cfg3 1.74 / 1.09 -> 1.23 / 0.80 -> 1.21 / 0.81 ms.
-static int g8_half_tiles() { static int v = -1; if (v < 0) { v = GR_KNOB("GR_G8_HALF_TILES", 2); } return v; }
+// LDS tile of the 8-channel-group pipeline kernels: 256 pixels (9 KB per workgroup, eight workgroups per CU).  Measured per step against
+// 1024- and 512-pixel tiles, pass B / forward: cfg2 0.228 / 0.148 -> 0.207 / 0.135 -> 0.199 / 0.139 ms, cfg3 1.74 / 1.09 -> 1.23 / 0.80 -> 1.21 / 0.81 ms.
 void launch_to_p16(const float* x, void* p16, int B, int C, int HW, const unsigned* slot, hipStream_t s) {
   long blocks = ((long)B * (C / 8) * (HW / 4) + 255) / 256;
   if (blocks > 16384) blocks = 16384;
@@ -405,33 +400,18 @@ void launch_to_p16(const float* x, void* p16, int B, int C, int HW, const unsign
 
 void launch_post_forward(const PostArgs& a0, hipStream_t s) {
   PostArgs a = a0;
-  a.nt_st = (g_nt_stores >> 2) & 1;
-  a.nt = post_nt_mode() >= 0 ? (post_nt_mode() >> 2) & 1 : 0;        // forward: measured no gain at either size (0.7356 -> 0.7385 ms at cfg3)
+  a.nt_st = 0;
+  a.nt = 0;        // forward: non-temporal loads measured no gain at either size (0.7356 -> 0.7385 ms at cfg3)
   const long n = (long)a.B * a.C * (a.pool ? (a.H >> 1) * (a.W >> 1) : a.H * a.W);
   if (a.p16) {      // caller checked post_g8_supported
     const long hwo = a.pool ? (long)(a.H >> 1) * (a.W >> 1) : (long)a.H * a.W;
     long blocks = (long)a.B * (a.C / 8) * (hwo > T8_PXT ? hwo / T8_PXT : 1);      // one (image, 8-channel group, pixel tile) per block step
     if (blocks > 4096 && hwo > 256) blocks = 4096;
     KtScope kt("post_forward_g8_kernel", 0.0, 4.0 * ((double)a.B * a.C * a.H * a.W + (a.out ? 2.0 : 1.0) * (double)n), s);
-    if (hwo <= 256) {
-      if (blocks > 8192) blocks = 8192;
-      if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<true, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-      else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<false, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-    } else if (g8_half_tiles() == 2) {
-      blocks *= 4; if (blocks > 8192) blocks = 8192;
-      if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<true, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-      else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<false, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-    }
-#ifdef GR_ABLATE      // GR_G8_HALF_TILES=1 / 0: 512- and 1024-pixel LDS tiles (round 2's measurements; the shipping library runs 256-pixel tiles everywhere)
-    else if (g8_half_tiles() && hwo % 512 == 0) {
-      blocks *= 2; if (blocks > 8192) blocks = 8192;
-      if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<true, 512, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-      else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<false, 512, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-    } else {
-      if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<true, 1024, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-      else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<false, 1024, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-    }
-#endif
+    if (hwo > 256) blocks *= 4;                                       // 256-pixel tiles: four per T8_PXT step
+    if (blocks > 8192) blocks = 8192;
+    if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<true, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
+    else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<false, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
     return;
   }
   const bool vec = (a.pool ? (a.W % 8 == 0 && a.H % 2 == 0) : (a.W % 4 == 0)) && (long)a.B * a.C * a.H * a.W < (1l << 32);
@@ -776,8 +756,8 @@ __global__ __launch_bounds__(256) void post_backward_a_vec_kernel(PostBwdArgs a,
     // groups - four per thread - so without this every thread waits out one memory round trip per group); post_bwd_load4 /
     // post_bwd_dz_of are the two halves of post_bwd_dz4, same operations in the same order
     // A block owns several rounds of 1024 groups whenever its batch slice holds more than 4096 elements per channel (cfg3: 8 images of 64 x 64 = 8 rounds;
-    // cfg2: one round); round k + 1 is requested before round k is worked on.  (The ablation launcher GR_PASSA_SPLIT_DIV, which MAKES blocks longer at
-    // cfg2, measured no gain: profiles/r05_ab_passa_prefetch_cfg2.txt - the second buffer set is for the naturally long blocks.)
+    // cfg2: one round); round k + 1 is requested before round k is worked on.  (Making blocks longer at
+    // cfg2 measured no gain: profiles/r05_ab_passa_prefetch_cfg2.txt - the second buffer set is for the naturally long blocks.)
     BwdRaw r[4], rn[4]; unsigned ee[4], een[4];
     auto request = [&](unsigned j0, BwdRaw* rr, unsigned* e_) {
 #pragma unroll
@@ -880,8 +860,7 @@ __global__ __launch_bounds__(256) void post_backward_b_vec_kernel(PostBwdArgs a,
 // dy_p16[b][g][term][pixel], scaled by the power of two of the bound K * max|dz| (K from the forward's statistics, max|dz| from
 // pass A) that it also leaves in amax_dy, and as fp32 only when a consumer still needs that (a.dy != null).
 template <int PXT, int CB>
-__global__ __launch_bounds__(256) void post_backward_b_g8_kernel(PostBwdArgs a, int splits, int slices, double n, int dbg_) {
-  const int dbg = GR_DBG(dbg_);
+__global__ __launch_bounds__(256) void post_backward_b_g8_kernel(PostBwdArgs a, int splits, int slices, double n) {
   post_specialize<CB>(a.f);
   constexpr int RSB = PXT * 2 + 64;
   __shared__ __attribute__((aligned(16))) unsigned char img[16 * RSB];
@@ -937,8 +916,7 @@ __global__ __launch_bounds__(256) void post_backward_b_g8_kernel(PostBwdArgs a, 
         for (int u = 0; u < 4; ++u) {
           const unsigned qi = q0 + 32 * (k0 + u), i = tile * qpt + qi;
           if (k0 + u < qpt / 32) {
-            if (!(dbg & 128)) raw[u] = post_bwd_load4(a, bcj, bcj * HW + i * 4, i, bcj * HWo, wq, Wo);
-            else { raw[u].g = make_float4(1, 2, 3, 4); raw[u].y = make_float4(1, 1, 1, 1); raw[u].id2 = 0; raw[u].m1w = raw[u].m2w = 15; raw[u].t0 = 0; }
+            raw[u] = post_bwd_load4(a, bcj, bcj * HW + i * 4, i, bcj * HWo, wq, Wo);
           }
         }
 #pragma unroll
@@ -960,7 +938,7 @@ __global__ __launch_bounds__(256) void post_backward_b_g8_kernel(PostBwdArgs a, 
         }
       }
       __syncthreads();
-      if (!(dbg & 64)) t8_emit<RSB>(img, (int)npx, p16 + ((size_t)b * G + g) * 2 * HW + (size_t)tile * npx, HW, f.nt_st != 0);
+      t8_emit<RSB>(img, (int)npx, p16 + ((size_t)b * G + g) * 2 * HW + (size_t)tile * npx, HW, f.nt_st != 0);
       __syncthreads();
     }
   // bias gradient: per-channel sums of dy = the 32 threads of a channel (one half-wave), added in a fixed shuffle tree
@@ -1042,9 +1020,9 @@ void launch_post_backward(const PostBwdArgs& a0, hipStream_t s, BiasJobs* defer,
   if (sync) aB.gscale = a.gscale = sync->grad_scale;
   // pass A and the operand-ready pass B: tensors the Infinity Cache cannot hold (at cfg2's 34 / 67 MB a non-temporal pass A takes from
   // pass B what it would have found in the cache: A 0.169 -> 0.161 ms but B 0.163 -> 0.181); the float4 pass B measured no gain
-  a.nt = post_nt_mode() >= 0 ? post_nt_mode() & 1 : (post_big(a0.f) ? 1 : 0);
-  aB.f.nt_st = (g_nt_stores >> 3) & 1;
-  aB.nt = post_nt_mode() >= 0 ? (post_nt_mode() >> 1) & 1 : ((post_big(a0.f) && a0.dy_p16) ? 1 : 0);
+  a.nt = post_big(a0.f) ? 1 : 0;
+  aB.f.nt_st = 0;
+  aB.nt = (post_big(a0.f) && a0.dy_p16) ? 1 : 0;
   const PostArgs& f = a.f;
   const long n = (long)f.B * f.H * f.W;
   int splits = stat_splits(n);
@@ -1052,10 +1030,6 @@ void launch_post_backward(const PostBwdArgs& a0, hipStream_t s, BiasJobs* defer,
   const bool vec = (f.pool ? (f.W % 8 == 0 && f.H % 2 == 0) : (f.W % 4 == 0)) && f.H * f.W >= 64 && pre < 4.0e9;
   if (vec) {
     splits = batch_splits(n, f.B);
-    {
-      static const int div = GR_KNOB("GR_PASSA_SPLIT_DIV", 1);
-      if (div > 1 && !post_big(a0.f)) { int s2 = splits / div; if (s2 < 1) s2 = 1; const int per = (f.B + s2 - 1) / s2; splits = (f.B + per - 1) / per; }
-    }
     KtScope kt("post_backward_a_vec_kernel", 0.0, 4.0 * ((f.has_bn ? 1.0 : 2.0) * pre + post), s);   // with BN: dz is not stored
     with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL(post_backward_a_vec_kernel<decltype(cb)::value>, dim3(f.C, splits), dim3(256), 0, s, a, splits); });
   } else {
@@ -1084,12 +1058,7 @@ void launch_post_backward(const PostBwdArgs& a0, hipStream_t s, BiasJobs* defer,
     // 35 for the per-channel kernel): the batch is sliced down to single images instead, up to PB_SPLITS slices
     int slices = f.B < PB_SPLITS ? f.B : PB_SPLITS;
     { const int per = (f.B + slices - 1) / slices; slices = (f.B + per - 1) / per; }
-    if (f.H * f.W <= 256) with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_b_g8_kernel<256, decltype(cb)::value>), dim3(f.C / 8, slices), dim3(256), 0, s, aB, psplits, slices, nb, g_p16_debug); });
-    else if (g8_half_tiles() == 2) with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_b_g8_kernel<256, decltype(cb)::value>), dim3(f.C / 8, slices), dim3(256), 0, s, aB, psplits, slices, nb, g_p16_debug); });
-#ifdef GR_ABLATE
-    else if (g8_half_tiles() && (f.H * f.W) % 512 == 0) with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_b_g8_kernel<512, decltype(cb)::value>), dim3(f.C / 8, slices), dim3(256), 0, s, aB, psplits, slices, nb, g_p16_debug); });
-    else with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_b_g8_kernel<1024, decltype(cb)::value>), dim3(f.C / 8, slices), dim3(256), 0, s, aB, psplits, slices, nb, g_p16_debug); });
-#endif
+    with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_b_g8_kernel<256, decltype(cb)::value>), dim3(f.C / 8, slices), dim3(256), 0, s, aB, psplits, slices, nb); });
     if (a.gbias) {
       BiasJobs one{}; one.n = 0;
       BiasJobs* q = defer ? defer : &one;
@@ -1229,7 +1198,6 @@ struct HeadArgs {
   unsigned* amax_dy;
   unsigned* bar; unsigned bar_base;
   unsigned* fault; int spin_limit; // sticky device word a timed-out barrier sets (penalty_clamp_adam_kernel skips its update while it is set; the host turns it into GR_ERR_STATE)
-  unsigned long long* stamps;      // ablation build: [workgroup][8] wall-clock stamps of the phases (tools/debug/debug_head.py)
 };
 constexpr int HEAD_FW = 8, HEAD_RG = 32, HEAD_RMAX = 16;
 // Bounded: a launch that cannot become resident as a whole (a partitioned device, CUs held by other work for seconds) does not hang the GPU.  ANY workgroup
@@ -1264,8 +1232,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int B = a.B, C1 = a.C1, nd = a.nd;
   const double n = (double)B;
   bool alive = true;
-#define HEAD_STAMP(i_) if (GR_DBG(a.stamps != nullptr) && tid == 0) a.stamps[blockIdx.x * 8 + (i_)] = wall_clock64();
-  HEAD_STAMP(0)
   // Loops below run a FIXED number of steps with clamped indices and zero weights past the ends (rows past B, outputs past nd, columns past C1) and guard
   // only their stores: the first version predicated every step of 16-fold unrollings and came to 35 000 lines of ISA, slower than the 14 launches it replaced.
   // ---------------------------------------------------------------- phase 1: features f0 .. f0 + 7, all rows
@@ -1315,9 +1281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
     }
   }
-  HEAD_STAMP(1)
   alive = head_grid_barrier(a.bar, a.bar_base + (unsigned)NW, a.fault, a.spin_limit) && alive;
-  HEAD_STAMP(2)
   // ---------------------------------------------------------------- phase 2: rows r0 .. r0 + nrows - 1, all features
   // Every global load of the phase that does not depend on its own arithmetic goes out at its top - the slice's out1 rows, the first eight W2 rows of each
   // wave, fc2's bias, the criterion's targets, y1 / Dropout words of the slice - and is waited for ONCE; later batches (more than 32 outputs) are requested one
@@ -1424,7 +1388,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       } else if (i < RT * nd) gy2_s[i] = 0.f;                     // rows past B: zero gradient
     }
     lacc = block_reduce_sum(lacc, sh_loss8);
-    HEAD_STAMP(3)
     __syncthreads();
     if (tid == 0) a.loss_part[wg] = lacc;
     // gx = gy2 W2 for the rows of this slice, then through the Dropout mask and the activation's derivative: dz
@@ -1478,9 +1441,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
     }
   }
-  HEAD_STAMP(4)
   alive = head_grid_barrier(a.bar, a.bar_base + 2u * (unsigned)NW, a.fault, a.spin_limit) && alive;
-  HEAD_STAMP(5)
   // ---------------------------------------------------------------- phase 3: features f0 .. f0 + 7, all rows
   {
     const float mean = sh_mean[ff], invstd = sh_inv[ff], gm = a.gamma[f];
@@ -1565,7 +1526,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if (c < HEAD_FW) a.gW2[(long)oo * C1 + f0 + c] += t;
       else if (wg == 0) a.gb2[oo] += t;
     }
-    HEAD_STAMP(6)
     if (wg == 0 && tid == 0) {
       double t = 0;
       for (int k = 0; k < NW; ++k) t += a.loss_part[k];
@@ -1582,7 +1542,7 @@ size_t head_lds_bytes(int B, int C1, int nd, int rows_per_wg) {
 bool head_supported(int B, int C1, int nd) {
   if (B < 2 || C1 % 64 != 0 || C1 < 64 || C1 > 512 || nd < 1 || nd > 128) return false;
   const int NW = C1 / HEAD_FW, R = (B + NW - 1) / NW;
-  // Measured (in-kernel stamps, tools/debug/head_stamps.py): cfg2's head (256 rows, nd 32: 4 rows per workgroup) 48.6 us against 79 us for the 14 launches it
+  // Measured (in-kernel stamps): cfg2's head (256 rows, nd 32: 4 rows per workgroup) 48.6 us against 79 us for the 14 launches it
   // replaces; cfg3's (512 rows, nd 100: 8 rows per workgroup, four batches of W2 per wave) 141 us against ~95 - its fc2 forward is a chain of 256 dependent
   // (LDS read, 8 FMAs, DPP wave sum) steps per wave.  The kernel is used where it wins: at most 4 rows per workgroup and nd <= 32.
   return R <= 4 && nd <= 32 && head_lds_bytes(B, C1, nd, 4) <= 60 * 1024;
@@ -1599,7 +1559,7 @@ void launch_head_fwd_bwd(const HeadLaunch& h, hipStream_t s) {
   a.target = h.target; a.inv_n = 1.0 / (double)h.n_global; a.norm = (float)(2.0 / (double)h.n_global); a.loss = h.loss; a.loss_part = h.loss_part;
   a.gout = h.gout; a.gy2 = h.gy2; a.dy1 = h.dy1;
   a.gW2 = h.gW2; a.gb2 = h.gb2; a.ggamma = h.ggamma; a.gbeta = h.gbeta; a.gb1 = h.gb1;
-  a.amax_dy = h.amax_dy; a.bar = h.bar; a.bar_base = h.bar_base; a.fault = h.fault; a.spin_limit = h.spin_limit > 0 ? h.spin_limit : (1 << 22); a.stamps = reinterpret_cast<unsigned long long*>(g_p16_stamps);
+  a.amax_dy = h.amax_dy; a.bar = h.bar; a.bar_base = h.bar_base; a.fault = h.fault; a.spin_limit = h.spin_limit > 0 ? h.spin_limit : (1 << 22);
   const size_t lds = head_lds_bytes(h.B, h.C1, h.nd, 4);      // (head_supported: at most 4 rows per workgroup)
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_fwd_bwd_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); attr = true; }

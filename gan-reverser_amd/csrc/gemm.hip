@@ -17,7 +17,6 @@ struct GemmArgs {
   int M, N, K, klen, nsplit, accumulate;
   ConvEpilogue ep;       // optional per-column epilogue (evaluate()-mode BatchNorm over the N features + activation); nsplit == 1 only
   int has_ep;
-  int vec_store;         // big kernel: whole blocks leave through the LDS transpose (16-byte stores); 0 = the dword stores (GR_GEMM_DWORD_STORES: A/B control)
   unsigned* amax_out;    // nullable (nsplit == 1): max|C| folded into this f16x3 scale slot
   const unsigned *amax_a, *amax_b;   // f16x3 kernel: scale slots (max|A|, max|B|)
 };
@@ -101,7 +100,7 @@ __device__ __forceinline__ void gemm_store_block(const GemmArgs& a, const f32x16
 // and reads them back four consecutive columns per lane: 4 store instructions of 8 rows x 128 bytes.  For blocks that lie whole inside the
 // matrix, with N and ldc multiples of 4 and no accumulation into C; everything else takes gemm_store_block.  mb0 = the block's first row.
 __device__ __forceinline__ bool gemm_block_vec_ok(const GemmArgs& a, int mb0, int nb0) {
-  return a.vec_store && !a.accumulate && mb0 + 32 <= a.M && nb0 + 32 <= a.N && (a.N & 3) == 0 && (a.ldc & 3) == 0 && (((uintptr_t)a.C | (uintptr_t)a.slab) & 15) == 0;
+  return !a.accumulate && mb0 + 32 <= a.M && nb0 + 32 <= a.N && (a.N & 3) == 0 && (a.ldc & 3) == 0 && (((uintptr_t)a.C | (uintptr_t)a.slab) & 15) == 0;
 }
 __device__ __forceinline__ void gemm_store_block_vec(const GemmArgs& a, const f32x16& acc, int mb0, int nb0, int shift, float& omax, float* stg, int lane) {
   const int l31 = lane & 31, h = lane >> 5, n = nb0 + l31;
@@ -483,9 +482,9 @@ static void gemm_plan(int M, int N, int K, int& nsplit, int& klen, int tile = 64
     // (Round 6, profiles/r06_gemm_plan_sweep.txt: R.fc1's three GEMMs take 26-28 us at cfg2 and 86 us at cfg3 under EVERY plan - 256 ... 2048 workgroups, K runs of
     //  64 ... 512, 64- or 128-wide tiles - and an XCD-aware tile order that keeps a split's tiles on one L2 changed nothing either (r06_ab_gemm_xcd_order.txt):
     //  the kernels are bound by splitting their operands while staging, 9-12 VALU instructions per MFMA on the counters (r06_pmc_gemm_cfg3.txt), not by the plan.)
-    static const int wgs_want = GR_KNOB("GR_GEMM_WGS", 512), min_klen = GR_KNOB("GR_GEMM_MIN_KLEN", 128);      // (ablation build: workgroups aimed for, shortest K run per split)
-    long want = (wgs_want + tiles - 1) / tiles;
-    const long maxs = K / min_klen;
+    constexpr int WGS_WANT = 512, MIN_KLEN = 128;      // workgroups aimed for, shortest K run per split
+    long want = (WGS_WANT + tiles - 1) / tiles;
+    const long maxs = K / MIN_KLEN;
     if (want > maxs) want = maxs;
     if (want < 1) want = 1;
     nsplit = (int)want;
@@ -509,12 +508,9 @@ void launch_gemm(const float* A, long rsA, long ksA, const float* Bm, long rsB, 
                  const unsigned* amax_a, const unsigned* amax_b) {
   GemmArgs a{};
   if (ep) { a.ep = *ep; a.has_ep = 1; }
-  static const int vec_store = GR_KNOB_SET("GR_GEMM_DWORD_STORES") ? 0 : 1;
-  a.vec_store = vec_store;
   a.amax_out = amax_out; a.amax_a = amax_a; a.amax_b = amax_b;
   const bool f16 = amax_a != nullptr && amax_b != nullptr;
-  static const bool big_on = !GR_KNOB_SET("GR_GEMM_SMALL_TILES");
-  bool big = f16 && big_on && M >= 128 && N >= 128;
+  bool big = f16 && M >= 128 && N >= 128;
   a.A = A; a.Bm = Bm; a.C = C; a.slab = reinterpret_cast<float*>(workspace); a.bias = bias;
   a.rsA = rsA; a.ksA = ksA; a.rsB = rsB; a.ksB = ksB; a.ldc = ldc;
   a.M = M; a.N = N; a.K = K; a.accumulate = accumulate ? 1 : 0;

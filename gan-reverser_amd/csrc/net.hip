@@ -42,7 +42,6 @@ struct gr_ctx {
   int head_fault_inject = 0;           // gr_set_tuning "head_fault_inject" (test hook): the NEXT head launch waits at its barriers for an arrival count that never comes
   int cu_count = 0;                    // the grid barrier needs every workgroup of the head kernel resident at once: head_plan refuses devices with fewer CUs than workgroups
   int fused_head = 1;                  // gr_set_tuning "fused_head" (1 default; 0 = the stage-by-stage path: the A/B control and what every other entry point runs)
-  hipEvent_t ev_prep_go = nullptr, ev_prep_done = nullptr;    // ablation build: R's per-step preparation on the side stream beside G's forward (GR_PREP_OVERLAP=1; it lost its A/B)
   int side_wgrad = -1;                 // gr_set_tuning "side_wgrad" / GR_SIDE_WGRAD: 1 on, 0 off, -1 (default) by size.  The MFMA kernels take the whole register file of a
                                        // CU (2 waves x 256 VGPRs per SIMD), so nothing becomes resident beside a weight gradient and only kernel tails overlap.  Round 5,
                                        // same box, interleaved (profiles/r05_ab_side_wgrad_*.txt): cfg2 1.976 -> 1.998 ms (slower: the tails are a few us and two streams
@@ -77,7 +76,7 @@ struct gr_ctx {
 
 // ---- per-kernel event timer (gr_set_timing(ctx, 2)) -------------------------------------------------------------
 namespace gr { KernelTimer* g_ktimer = nullptr; }
-static int g_eval_p16 = GR_KNOB_SET("GR_NO_EVAL_P16") ? 0 : 1;      // gr_set_tuning "eval_p16"
+static int g_eval_p16 = 1;      // gr_set_tuning "eval_p16"
 static int g_kphase = 0;      // which part of gr_train_r_step is launching: 0 outside, 1 G forward, 2 R forward, 3 loss, 4 R backward, 5 Adam
 struct EventTimer : gr::KernelTimer {
   struct Rec { std::string name; int phase; double flops, bytes; hipEvent_t e0, e1; bool ok; };
@@ -262,12 +261,10 @@ extern "C" int gr_init(int device, gr_ctx** out) {
   (void)hipMemsetAsync(c->d_loss, 0, 64, c->stream);
   memset(c->h_loss, 0, 64);
   { const char* d = getenv("GR_RANGE_GUARD"); if (d) c->range_guard = atoi(d); }
-  gr::g_p16_debug = GR_KNOB("GR_P16_DEBUG", 0);      // diagnostic ablations (probe build only: tools/ablate_p16.py)
   { const char* m = getenv("GR_CONV_MODE"); if (m) c->conv_mode = (!strcmp(m, "f32") || !strcmp(m, "0")) ? 0 : ((!strcmp(m, "bf16x6") || !strcmp(m, "1")) ? 1 : 2); }
   (void)hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking);
   (void)hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking);
   (void)hipEventCreateWithFlags(&c->ev_dy_ready, hipEventDisableTiming);
-  (void)hipEventCreateWithFlags(&c->ev_prep_go, hipEventDisableTiming); (void)hipEventCreateWithFlags(&c->ev_prep_done, hipEventDisableTiming);
   for (auto& e : c->ev_wgrad_done) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   { const char* e = getenv("GR_SIDE_WGRAD"); if (e) c->side_wgrad = atoi(e); }
   { const char* e = getenv("GR_FUSED_HEAD"); if (e) c->fused_head = atoi(e) != 0; }
@@ -290,8 +287,6 @@ extern "C" int gr_shutdown(gr_ctx* c) {
   if (c->ev_dy_ready) (void)hipEventDestroy(c->ev_dy_ready);
   if (c->head_bar) (void)hipFree(c->head_bar);
   if (c->head_loss_part) (void)hipFree(c->head_loss_part);
-  if (c->ev_prep_go) (void)hipEventDestroy(c->ev_prep_go);
-  if (c->ev_prep_done) (void)hipEventDestroy(c->ev_prep_done);
   for (auto& e : c->ev_wgrad_done) if (e) (void)hipEventDestroy(e);
   if (c->guard_chmax) (void)hipFree(c->guard_chmax);
   if (c->sync_buf) (void)hipFree(c->sync_buf);
@@ -326,21 +321,10 @@ extern "C" int gr_set_conv_mode(gr_ctx* c, int mode) {
   return GR_OK;
 }
 extern "C" int gr_get_conv_mode(gr_ctx* c) { return c ? c->conv_mode : GR_ERR_INVALID; }
-// diagnostic: give the P16 kernels a device buffer (32 x 8 bytes per workgroup) for in-kernel time stamps ("p16_debug" bit 32)
-extern "C" int gr_debug_stamps(gr_ctx* c, void* dev_buf) { if (!c) return GR_ERR_INVALID; gr::g_p16_stamps = dev_buf; return GR_OK; }
 extern "C" int gr_set_tuning(gr_ctx* c, const char* key, int value) {
   if (!c || !key) return GR_ERR_INVALID;
   if (!strcmp(key, "p16_min_tiles")) { gr::g_p16_min_tiles = value; return GR_OK; }
   if (!strcmp(key, "stack8_min_wgs")) { gr::g_stack8_min_wgs = value; return GR_OK; }      // four 8x8 images per convolution tile from this many workgroups on (default 128)
-#ifdef GR_ABLATE   // ablation build only (make ablate): variants that lost their A/B, and ablation bits that make kernels compute wrong results by design
-  if (!strcmp(key, "p16_stagger")) { gr::g_p16_stagger = value; return GR_OK; }
-  if (!strcmp(key, "p16_variant")) { gr::g_p16_variant = value; return GR_OK; }
-  if (!strcmp(key, "p16_debug")) { gr::g_p16_debug = value; return GR_OK; }
-  if (!strcmp(key, "up2_debug")) { gr::g_up2_debug = value; return GR_OK; }     // diagnostic ablations of the four-wave up-sampling kernel
-  if (!strcmp(key, "nt_stores")) { gr::g_nt_stores = value; return GR_OK; }        // bit mask: which kernels store their outputs non-temporally (kernels.h)
-  if (!strcmp(key, "up2_stagger")) { gr::g_up2_stagger = value; return GR_OK; }   // start delay of a CU's second workgroup, x 512 clocks
-  if (!strcmp(key, "up2_quad")) { gr::g_up2_quad = value; return GR_OK; }       // 1 (default): four-wave up-sampling kernel where it applies; 0: eight-wave     // diagnostic ablations (outputs are then wrong by design)
-#endif
   if (!strcmp(key, "eval_p16")) { g_eval_p16 = value; return GR_OK; }           // evaluate()-mode stages hand their output over operand-ready (1, default) or as fp32 (0: the A/B control)
   if (!strcmp(key, "side_wgrad")) { c->side_wgrad = value; return GR_OK; }
   if (!strcmp(key, "fused_head")) { c->fused_head = value != 0; return GR_OK; }   // gr_train_r_step: R's last two stages + the criterion, forward and backward, in one launch
@@ -507,7 +491,6 @@ struct gr_net {
   bool dy_slots_zeroed = false, w_slots_zeroed = false;   // set by forward_impl's single fill, consumed by backward / weight prep
   bool last_fwd_training = true;     // mode of the last forward (a backward after an evaluate()-mode forward is checked against THAT, not against the current mode)
   bool head_fused = false;           // gr_train_r_step: this forward stops after fc1's GEMM and this backward starts at fc1's GEMMs - the head kernel does what lies between
-  int begun_B = 0;                   // > 0: forward_begin has already run for the next forward of this batch size (gr_train_r_step ran it on the side stream)
   int amax_prezeroed_groups = 0;     // > 0: the caller (gr_train_r_step's one fill per step) has just zeroed that many slot groups: the next forward skips its own fill
   bool keep_fp32 = false;            // range-guarded host calls: no lean (operand-ready only) tensors, so a backward can still fall back to bf16x6
   bool last_fwd_fell_back = false;   // the last guarded forward ran on bf16x6: its backward does too
@@ -841,20 +824,18 @@ static int ensure_batch(gr_net* n, int B) {
 // bf16x6 mode: every plain convolution runs on the split kernel except few-output-channel layers the HBM-bound VALU
 // kernel covers (same predicate as launch_conv3x3); only the split images are kept current in that mode.
 static bool fewout_applies(const Stage& s) {
-  // GR_FEWOUT_MAX=0 sends the few-output layers to the MFMA split kernels too (A/B, round 3: G's last convolution 0.388 -> 0.53 ms at cfg3,
-  // 39 -> 73 us at cfg2 - a 32-channel output block for 1-3 real channels)
-  static const int maxc = GR_KNOB("GR_FEWOUT_MAX", 4);
-  return s.ksz == 3 && s.Cout <= maxc && !s.up && s.W % 4 == 0 && s.W >= 16;
+  // the MFMA split kernels measured slower on these layers (round 3: G's last convolution 0.53 -> 0.388 ms at cfg3, 73 -> 39 us at cfg2 -
+  // a 32-channel output block for 1-3 real channels)
+  constexpr int FEWOUT_MAX = 4;
+  return s.ksz == 3 && s.Cout <= FEWOUT_MAX && !s.up && s.W % 4 == 0 && s.W >= 16;
 }
 // f16x3 GEMM for the large nn.Linear layers (R.fc1: 90-97 % of R's parameters); small ones stay on the fp32 MFMA kernel
 static bool use_f16_gemm(gr_net* n, const Stage& s) {
-  static const bool on = !GR_KNOB_SET("GR_NO_F16_GEMM");
-  return on && n->ctx->conv_mode == 2 && s.kind == ST_LINEAR && (int64_t)s.Cin * s.Cout >= (1 << 20);
+  return n->ctx->conv_mode == 2 && s.kind == ST_LINEAR && (int64_t)s.Cin * s.Cout >= (1 << 20);
 }
 // the 5x5 layer of the D network (models.lua:297) on the f16x3 split kernel (round 4; bf16x6 / f32 modes keep convk.hip's fp32 VALU kernels)
 static bool convk_split(gr_net* n, const Stage& s) {
-  static const bool on = !GR_KNOB_SET("GR_NO_CONV5_SPLIT");
-  return on && n->ctx->conv_mode == 2 && s.kind == ST_CONV && s.ksz == 5 && !s.up && !s.fullconv && s.ws_fwd && conv5x5_split_supported(s.Cin, s.Cout, s.H, s.W);
+  return n->ctx->conv_mode == 2 && s.kind == ST_CONV && s.ksz == 5 && !s.up && !s.fullconv && s.ws_fwd && conv5x5_split_supported(s.Cin, s.Cout, s.H, s.W);
 }
 static bool use_bf16x6(gr_net* n, const Stage& s) { return (n->ctx->conv_mode >= 1 && s.kind == ST_CONV && s.ksz == 3 && !fewout_applies(s)) || convk_split(n, s); }   // either split flavour
 // Re-lay every convolution's weights (one launch) when the parameters changed since the last time.  bf16x6 mode needs the
@@ -1041,8 +1022,9 @@ static int guard_scan_activation(gr_ctx* c, const float* t, int B, int C, int H,
 }
 
 // The per-forward preparation that depends on nothing but the parameters and the batch size: counters, the one fill of the f16x3 scale slots, the weight
-// images / maxima of the current parameters, the Dropout noise.  Launches on c->stream - gr_train_r_step points that at the side stream for R, so that these
-// three to four small launches (25 us at cfg2: each is a launch-latency floor, not work) run beside G's forward instead of between G and R.
+// images / maxima of the current parameters, the Dropout noise: three to four small launches (25 us at cfg2: each is a launch-latency floor, not work).
+// Run on the side stream beside G's forward, they made gr_train_r_step SLOWER (round 5: 1.920-1.942 -> 1.960-1.968 ms at cfg2,
+// profiles/r05_ab_prep_overlap_cfg2.txt): they run in line.
 static int forward_begin(gr_net* n, int B) {
   gr_ctx* c = n->ctx;
   const int prezeroed_groups = n->amax_prezeroed_groups;      // consumed on EVERY path out of this call (an early error return must not leave it set for a later forward)
@@ -1088,15 +1070,13 @@ static int forward_begin(gr_net* n, int B) {
     launch_gen_mask_batch(jobs, n->seed, n->fwd_counter, c->stream);
     LAUNCHCHK(c);
   }
-  n->begun_B = B;
   return GR_OK;
 }
 
 static int forward_stages(gr_net* n, const float* in_dev, int B) {
   gr_ctx* c = n->ctx;
   int r = GR_OK;
-  if (n->begun_B != B) { r = forward_begin(n, B); if (r) { n->begun_B = 0; return r; } }
-  n->begun_B = 0;
+  r = forward_begin(n, B); if (r) return r;
   n->last_fwd_training = n->training;
   const float* x = in_dev;
   const bool f16 = c->conv_mode == 2;
@@ -1133,11 +1113,9 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
         ep.act = s.act; ep.slope = s.slope; epp = &ep; dst = s.out; s.fused_epilogue = true;
       }
       // training-mode BatchNorm: the conv epilogue also leaves the per-channel (sum, sum of squares) of what it stores
-      static const bool epi_stats_on = !GR_KNOB_SET("GR_NO_EPI_STATS");
-      const bool want_stats = epi_stats_on && n->training && s.has_bn && s.stat_part && !s.fused_epilogue;
+      const bool want_stats = n->training && s.has_bn && s.stat_part && !s.fused_epilogue;
       int stat_tiles = 0;
-      static const bool fewin_on = !GR_KNOB_SET("GR_NO_FEWIN");
-      const bool is_fewin = fewin_on && !s.fullconv && conv_fewin_applies(s.Cin, s.W, s.up);
+      const bool is_fewin = !s.fullconv && conv_fewin_applies(s.Cin, s.W, s.up);
       const bool in_p16 = f16 && !s.up && s.x_p16 && s.x_p16_gen == n->amax_gen && use_bf16x6(n, s);      // this stage's input arrived operand-ready
       // evaluate() mode, f16x3 (round 4: apply_r.lua:145-153's corpus pipeline): the next convolution's input leaves THIS stage operand-ready
       // too - straight from the conv epilogue (`po`: BatchNorm + activation fused, scale = the weight-norm bound of launch_eval_bound) or, for
@@ -1169,7 +1147,6 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
         if (last_writer && nx) nx->amax_x_fwd = n->amax_gen;
       } else if (use_bf16x6(n, s)) {
         const int nterm = c->conv_mode == 2 ? 2 : 3;
-        static const bool up2_on = !GR_KNOB_SET("GR_NO_UP2");
         if (nterm == 2 && in_p16) {
           // the previous stage's pipeline kernel left this stage's input operand-ready, scaled by the bound in amax_x
           launch_conv3x3_p16(s.x_p16, s.ws_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, s.amax_x, s.amax_w, conv_amax_out,
@@ -1177,7 +1154,7 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
         } else {
           // input not produced by a tracking kernel (the net's own input, a GEMM, a VALU conv): take its maximum now
           if (nterm == 2 && s.amax_x_fwd != n->amax_gen) { launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream, true); s.amax_x_fwd = n->amax_gen; }
-          if (nterm == 2 && s.up && s.ws_up && up2_on)
+          if (nterm == 2 && s.up && s.ws_up)
             launch_conv3x3_up2_f16x3(x, s.ws_up, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, s.amax_x, s.amax_w,
                                      last_writer ? amax_next : nullptr);
           else
@@ -1277,8 +1254,7 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
     // The fp32 copy of the stage output has one more reader than the next convolution's forward: that convolution's weight
     // gradient.  When it will take the operand-ready image too (every condition is fixed by the shapes and this forward), the
     // fp32 tensor is not written at all: the pipeline kernel writes 4 bytes per element, as it did before it wrote two formats.
-    static const bool lean_on = !GR_KNOB_SET("GR_P16_KEEP_FP32");
-    s.out_skipped = lean_on && !n->keep_fp32 && p16_out && nx->has_bn && n->dy_p16 && post_g8_supported(nx->Cout, nx->H, nx->W, nx->pool, true) &&
+    s.out_skipped = !n->keep_fp32 && p16_out && nx->has_bn && n->dy_p16 && post_g8_supported(nx->Cout, nx->H, nx->W, nx->pool, true) &&
                     conv_wgrad_p16_supported(B, nx->Cin, nx->Cout, nx->H, nx->W) && nx->stat_part;
     if (post_p16) s.out_skipped = true;               // evaluate(): nothing else reads the fp32 tensor
     if (s.out_skipped) pa.out = nullptr;
@@ -1504,8 +1480,7 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
     pb.dy_p16 = dy_p16 ? dyp : nullptr; pb.amax_dz = dy_p16 ? s.amax_dz : nullptr; pb.kb = s.amax_kb;
     if (s.kind == ST_CONV && si > 0 && n->st[si - 1].out_skipped && !wgrad_p16)
       return fail(c, GR_ERR_STATE, "stage %d: the forward left this stage's input operand-ready only (f16x3); backward in another arithmetic mode needs a new forward", si);
-    static const bool lean_on = !GR_KNOB_SET("GR_P16_KEEP_FP32");
-    if (lean_on && !n->keep_fp32 && wgrad_p16 && (dgrad_p16 || !need_gin)) pb.dy = nullptr;      // no fp32 reader of dy is left
+    if (!n->keep_fp32 && wgrad_p16 && (dgrad_p16 || !need_gin)) pb.dy = nullptr;      // no fp32 reader of dy is left
     if (s.act == ACT_PRELU && !head_here) {
       // nn.PReLU accGradParameters: the stage ends at the PReLU, so g is its gradOutput and the raw main-op output (the stage
       // input for an element-wise stage) its input
@@ -1866,7 +1841,7 @@ extern "C" int gr_train_r_step(gr_net* g, gr_net* rn, const float* noise_dev, in
   int r;
   // Per-step state of the two nets that must not outlive this call on ANY exit (an early error return used to leave head_fused set: a later gr_net_forward_* /
   // gr_net_backward_* on the same net then skipped its last two stages silently; likewise the 'slots already zeroed' and 'forward already begun' notes)
-  struct StepState { gr_net* g; gr_net* rn; ~StepState() { rn->head_fused = false; g->amax_prezeroed_groups = rn->amax_prezeroed_groups = 0; rn->begun_B = 0; } } step_state{g, rn};
+  struct StepState { gr_net* g; gr_net* rn; ~StepState() { rn->head_fused = false; g->amax_prezeroed_groups = rn->amax_prezeroed_groups = 0; } } step_state{g, rn};
   // Range guard of the device-resident loop: no synchronisation is allowed here, so the parameter scans (weights, BatchNorm
   // scales of G and R) run every GUARD_PERIOD-th step and their verdict is read, without waiting, by a later call.  Once a
   // hostile spread shows, the context stays on bf16x6 (gr_set_tuning "range_guard" 0 clears it).  Latency: under 2 periods.
@@ -1892,41 +1867,21 @@ extern "C" int gr_train_r_step(gr_net* g, gr_net* rn, const float* noise_dev, in
     // ONE fill per step: the f16x3 scale slots of both nets (what their forwards would each zero themselves) and R's gradient vector
     // (train_r.lua:143 gradParameters:zero()) - three hipMemsetAsync kernels of ~6 us each at batch 256 otherwise
     ZeroJobs z{}; z.n = 0;
-    static const bool one_fill = !GR_KNOB_SET("GR_NO_STEP_FILL");       // A/B control: every forward zeroes its own slots, the gradients get their own fill
-    if (c->conv_mode == 2 && one_fill) {
+    if (c->conv_mode == 2) {
       const int gg = AG_KB;                                                                      // G: evaluate() mode
       const int gr_ = rn->prepped_version[2] != rn->params_version ? AMAX_GROUPS : AG_W;         // R: training; the w group when the weight images are stale
       z.ptr[z.n] = g->amax; z.n16[z.n++] = (long)(sizeof(unsigned) * AMAX_WORDS * g->st.size() * gg / 16);
       z.ptr[z.n] = rn->amax; z.n16[z.n++] = (long)(sizeof(unsigned) * AMAX_WORDS * rn->st.size() * gr_ / 16);
       g->amax_prezeroed_groups = gg; rn->amax_prezeroed_groups = gr_;
     }
-    if (one_fill && rn->n_params % 4 == 0 && ((uintptr_t)rn->grads & 15) == 0) { z.ptr[z.n] = rn->grads; z.n16[z.n++] = (long)(rn->n_params / 4); }
+    if (rn->n_params % 4 == 0 && ((uintptr_t)rn->grads & 15) == 0) { z.ptr[z.n] = rn->grads; z.n16[z.n++] = (long)(rn->n_params / 4); }
     else { r = gr_net_zero_grads(rn); if (r) return r; }
     g_kphase = 1;
     launch_zero_regions(z, c->stream);
     LAUNCHCHK(c);
   }
   g_kphase = 1;
-  // R's preparation for this step (weight images and maxima of the parameters Adam just wrote, Dropout noise) depends on nothing G computes and could run on
-  // the side stream beside G's forward.  Measured (round 5, same box, interleaved: profiles/r05_ab_prep_overlap_cfg2.txt): the step gets SLOWER, 1.920-1.942 ->
-  // 1.960-1.968 ms at cfg2 - the three launches cost 25 us in line, the two event hand-overs and the small kernels' workgroups squeezing in between G's
-  // matrix-pipe-filling workgroups cost more.  Ablation build only (GR_PREP_OVERLAP=1); the shipping library runs them in line.
-  static const int prep_overlap = GR_KNOB("GR_PREP_OVERLAP", 0);
-  const bool prep_side = prep_overlap && c->side_stream != nullptr && gr::g_ktimer == nullptr && rn->capB >= B;
-  if (prep_side) {
-    HIPCHK(c, hipEventRecord(c->ev_prep_go, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_prep_go, 0));
-    hipStream_t main_stream = c->stream;
-    c->stream = c->side_stream;
-    g_kphase = 2;
-    r = forward_begin(rn, B);
-    g_kphase = 1;
-    c->stream = main_stream;
-    if (r) { rn->begun_B = 0; return r; }
-    HIPCHK(c, hipEventRecord(c->ev_prep_done, c->side_stream));
-  }
-  { PhaseRange pr("G forward"); r = forward_impl(g, noise_dev, B); } if (r) { rn->begun_B = 0; return r; }          // train_r.lua:139
-  if (prep_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_prep_done, 0));
+  { PhaseRange pr("G forward"); r = forward_impl(g, noise_dev, B); } if (r) return r;          // train_r.lua:139
   const float* images = g->st.back().out;
   if (tm) (void)hipEventRecord(c->ev[1], c->stream);
   g_kphase = 2;
@@ -2010,10 +1965,9 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
     HIPCHK(c, hipHostMalloc(&c->pin, res_bytes * 2));
     c->pin_bytes = res_bytes * 2;
   }
-  static const bool filter_on = !GR_KNOB_SET("GR_SEARCH_UNFILTERED");
   // A handful of needles (the reference's five): their rows travel in the kernel arguments and the kernels write idx | scores | status
   // straight into the pinned result block (host memory the device can address): no upload, no copy-out - launches, one wait.
-  if (filter_on && cosine_topk_small_path(N, d, Q, k)) {
+  if (cosine_topk_small_path(N, d, Q, k)) {
     void* pin_dev = nullptr;
     HIPCHK(c, hipHostGetDevicePointer(&pin_dev, c->pin, 0));
     char* pd = static_cast<char*>(pin_dev);
@@ -2035,9 +1989,8 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
     // The selection kernel publishes one completion word per needle behind its results (system-scope release): poll them instead of
     // synchronising the stream (measured: 1-3 us of a 0.15 ms search).  Bounded: after 20 ms the stream is synchronised after all (a fault
     // shows up there).
-    static const bool poll_on = !GR_KNOB_SET("GR_SEARCH_NO_POLL");
     bool seen = false;
-    if (lr == 2 && poll_on) {
+    if (lr == 2) {
       volatile unsigned* dw = c->pin_done;
       const auto t0 = std::chrono::steady_clock::now();
       for (unsigned spins = 0;; ++spins) {
@@ -2060,8 +2013,8 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
     c->search_reruns++;       // a candidate list overflowed (adversarial row order): the unfiltered search below decides
   }
   HIPCHK(c, hipMemcpyAsync(d_q, qrows, sizeof(long) * Q, hipMemcpyHostToDevice, c->stream));
-  const bool small_failed = filter_on && cosine_topk_small_path(N, d, Q, k);
-  for (int unfiltered = (filter_on && !small_failed) ? 0 : 1; unfiltered < 2; ++unfiltered) {
+  const bool small_failed = cosine_topk_small_path(N, d, Q, k);
+  for (int unfiltered = small_failed ? 1 : 0; unfiltered < 2; ++unfiltered) {
     if (launch_cosine_topk(emb, N, d, d_q, Q, k, d_idx, d_sc, accf, c->ws, c->stream, d_status, unfiltered, qrows)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
     LAUNCHCHK(c);
     HIPCHK(c, hipMemcpyAsync(c->pin, d_idx, res_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2174,7 +2127,7 @@ static int conv_split_once(gr_ctx* c, const float* w, int cin, int cout, bool bw
 }
 extern "C" int gr_conv3_forward_dev(gr_ctx* c, const float* in, const float* w, const float* bias, float* out, int B, int cin, int cout, int h, int wd, int up) {
   if (!c || !in || !w || !out) return GR_ERR_INVALID;
-  if (c->conv_mode == 2 && up && conv_up2_supported(cin, cout, h, wd) && !GR_KNOB_SET("GR_NO_UP2")) {
+  if (c->conv_mode == 2 && up && conv_up2_supported(cin, cout, h, wd)) {
     // the fused up-sampling layer as four 2x2 convolutions (the path a net takes for such a stage in f16x3 mode)
     void* wup = nullptr;
     HIPCHK(c, hipMalloc(&wup, conv_weight_up2_bytes(cin, cout)));
@@ -2251,9 +2204,6 @@ extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, in
   HIPCHK(c, hipMalloc((void**)&x, sizeof(float) * nin)); HIPCHK(c, hipMalloc((void**)&y, sizeof(float) * nout));
   HIPCHK(c, hipMalloc((void**)&w, sizeof(float) * nw)); HIPCHK(c, hipMalloc((void**)&gw, sizeof(float) * nw));
   launch_fill_normal(x, (long)nin, 11, c->stream); launch_fill_normal(y, (long)nout, 12, c->stream); launch_fill_normal(w, (long)nw, 13, c->stream);
-  if (GR_KNOB_SET("GR_BENCH_ZERO")) {   // DVFS diagnostic: all-zero operands draw less power (MI355X_MICROARCH.md, DVFS give-back item 1)
-    (void)hipMemsetAsync(x, 0, sizeof(float) * nin, c->stream); (void)hipMemsetAsync(y, 0, sizeof(float) * nout, c->stream); (void)hipMemsetAsync(w, 0, sizeof(float) * nw, c->stream);
-  }
   (void)hipMemsetAsync(gw, 0, sizeof(float) * nw, c->stream);
   int r = with_prepped(c, w, cin, cout, which == 1, &wt); if (r) return r;
   void* wsp = nullptr;
@@ -2261,8 +2211,7 @@ extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, in
   const int nterm = c->conv_mode == 2 ? 2 : 3;
   if (split) { r = conv_split_once(c, w, cin, cout, which == 1, &wsp); if (r) return r; }
   r = ensure_ws(c, conv_wgrad_workspace_bytes(B, cin, cout, h, wd, c->conv_mode)); if (r) return r;
-  // f16x3 scales: taken once outside the timed loop (in a net the producing kernel tracks them), or per launch with GR_BENCH_ABSMAX
-  const bool amax_each = GR_KNOB_SET("GR_BENCH_ABSMAX");
+  // f16x3 scales: taken once outside the timed loop (in a net the producing kernel tracks them)
   if (c->conv_mode == 2) { launch_absmax(x, (long)nin, c->amax, c->stream); launch_absmax(y, (long)nout, c->amax + AMAX_WORDS, c->stream); }
   void* wup = nullptr;
   if (which == 3) {      // fused up-sampling layer: x is the source plane [B, cin, h/2, wd/2] (a quarter of the buffer), y the output
@@ -2281,7 +2230,6 @@ extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, in
   auto run = [&]() {
     if (which == 4 || which == 5) { int st = 0; launch_conv3x3_p16(xp16, wsp, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr, which == 5 ? statp : nullptr, which == 5 ? &st : nullptr); return; }
     if (which == 3) { launch_conv3x3_up2_f16x3(x, wup, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr); return; }
-    if (amax_each && c->conv_mode == 2) { if (which != 1) launch_absmax(x, (long)nin, c->amax, c->stream); if (which != 0) launch_absmax(y, (long)nout, c->amax + AMAX_WORDS, c->stream); }
     if (split && which == 0) launch_conv3x3_split(x, wsp, nullptr, y, B, cin, cout, h, wd, false, c->stream, nullptr, nterm, c->amax, c->amax + 2 * AMAX_WORDS);
     else if (split && which == 1) launch_conv3x3_split(y, wsp, nullptr, x, B, cout, cin, h, wd, false, c->stream, nullptr, nterm, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
     else if (which == 0) launch_conv3x3(x, wt, nullptr, y, B, cin, cout, h, wd, false, c->stream, w);

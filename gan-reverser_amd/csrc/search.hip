@@ -74,8 +74,7 @@ template <bool ACCF, int MODE, int NQ, int DC>
 __global__ __launch_bounds__(ROWS) void cos_keys_kernel(const float* __restrict__ emb, long N, int d,
                                                          const float* __restrict__ needles, const float* __restrict__ w22,
                                                          int q0, unsigned long long* __restrict__ keys, long stride,
-                                                         const unsigned long long* __restrict__ bound, unsigned* __restrict__ counts, int dbg_) {
-  const int dbg = GR_DBG(dbg_);
+                                                         const unsigned long long* __restrict__ bound, unsigned* __restrict__ counts) {
   typedef typename std::conditional<ACCF, float, double>::type acc_t;
   constexpr int TS = ((DC / 4) & 1) ? DC + 8 : DC + 4;
   __shared__ __attribute__((aligned(16))) float tile[ROWS * TS];
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(ROWS) void cos_keys_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < DC / 4; ++i) {
       const int e = tid + i * ROWS, r = e / (DC / 4), c = (e - r * (DC / 4)) * 4;
-      const bool ok = r0 + r < N && c < dc && !(dbg & 1);
+      const bool ok = r0 + r < N && c < dc;
       const long row = ok ? (MODE == 1 ? (r0 + r) * stride : r0 + r) : 0;
       v[i] = *reinterpret_cast<const float4*>(emb + row * (long)d + (ok ? c0 + c : 0));
       if (!ok) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -127,7 +126,6 @@ __global__ __launch_bounds__(ROWS) void cos_keys_kernel(const float* __restrict_
     if (vec && c0 + DC < d) fetch(c0 + DC);
     const float4* row4 = reinterpret_cast<const float4*>(tile + tid * TS);
     const float4* nd4 = reinterpret_cast<const float4*>(ndt);
-    if (!(dbg & 2))
 #pragma unroll
     for (int c4 = 0; c4 < DC / 4; ++c4) {
       const float4 bv = row4[c4];
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(ROWS) void cos_keys_kernel(const float* __restrict_
     __syncthreads();
   }
   const long j = r0 + tid;
-  if (j < N && !(dbg & 4)) {
+  if (j < N) {
     float w32 = (float)s3;
     w32 = w32 + 1e-12f;
     w32 = 1.f / w32;
@@ -168,7 +166,7 @@ __global__ __launch_bounds__(ROWS) void cos_keys_kernel(const float* __restrict_
   }
   if (MODE == 2) {
     __syncthreads();
-    if (tid < NQ) counts[(long)(q0 + tid) * gridDim.x + blockIdx.x] = (dbg & 4) ? 0u : lds_cnt[tid];     // every workgroup writes its count: no fill needed
+    if (tid < NQ) counts[(long)(q0 + tid) * gridDim.x + blockIdx.x] = lds_cnt[tid];     // every workgroup writes its count: no fill needed
   }
 }
 
@@ -371,8 +369,7 @@ __global__ __launch_bounds__(256, 2) void cos_mfma_kernel(const float* __restric
   float* taut = sw22t + 128;                                                     // [2][64]
   unsigned* lds_cnt = reinterpret_cast<unsigned*>(taut + 128);                   // [Q] (MODE 1)
   // MODE 1: a queue of passing (needle, row, score) entries per WAVE, [4][qcap] x 8 bytes behind the counters (launcher: whatever two workgroups per CU leave, 0 = none)
-  const int dbg = GR_DBG(qcap >> 16);                                            // ablation build: GR_BATCHED_DEBUG bits 1 no epilogue, 2 no MFMA, 4 no row loads (results wrong by design)
-  qcap &= 0xffff;
+  qcap &= 0xffff;      // (a bound the compiler can use on the queue offsets below: without it cos_mfma_kernel<1, 8> spills 59 VGPRs)
   unsigned* wg_ovf = lds_cnt + (((Q > 128 ? Q : 128) + 1) & ~1);                  // [2]: some wave's queue overflowed
   unsigned long long* wqueue = reinterpret_cast<unsigned long long*>(wg_ovf + 2) + (size_t)(threadIdx.x >> 6) * qcap;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
@@ -388,7 +385,7 @@ __global__ __launch_bounds__(256, 2) void cos_mfma_kernel(const float* __restric
 #pragma unroll
       for (int u = 0; u < HALF; ++u) {
         const int e = tid + 256 * (part * HALF + u), r = e / C4, c = (e - r * C4) * 4;
-        const bool ok = e < TOT && c < d && r0 + r < N && !(dbg & 4);
+        const bool ok = e < TOT && c < d && r0 + r < N;
         const long row = ok ? (MODE == 0 ? (r0 + r) * stride : r0 + r) : 0;
         v[u] = *reinterpret_cast<const float4*>(emb + row * (long)d + (ok ? c : 0));
         if (!ok) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -479,7 +476,6 @@ __global__ __launch_bounds__(256, 2) void cos_mfma_kernel(const float* __restric
       for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nb][rb][r] = 0.f;
-    if (!(dbg & 2))
 #pragma unroll
     for (int kk = 0; kk < NK; ++kk) {
       uint4 a[2];
@@ -505,8 +501,7 @@ __global__ __launch_bounds__(256, 2) void cos_mfma_kernel(const float* __restric
       if (qp < Q) out[(long)qp * gridDim.x + blockIdx.x] = unorderable(lds_cnt[(cur ^ 1) * 64 + tid]) * sw22t[(cur ^ 1) * 64 + tid];
       lds_cnt[(cur ^ 1) * 64 + tid] = 0u;
     }
-    if (MODE == 1 && (dbg & 1)) {
-    } else if (MODE == 1 && qcap > 0) {
+    if (MODE == 1 && qcap > 0) {
       // (Round 6, measured and removed - git history, profiles/r06_ab_search_block_prefilter.txt: testing a 16-register block as a whole - d = value - threshold
       //  by one fma per register, their maximum by v_max3, ONE vote per block, and only lanes with a hit walking their registers into LDS atomics - was
       //  bit-identical and SLOWER: main pass 415 -> 495 us for 1024 needles.  The ablation of this epilogue (r06_ablate_search_batched.txt: 167 of the pass's
@@ -816,7 +811,6 @@ struct ApproxArgs {
   unsigned* cand_idx; float* cand_sc; unsigned* counts;   // main pass: [Q][nwg][ASLOT], [Q][nwg]
   unsigned* status;
   int Q, k, accf; float eps2;
-  int dbg;                                       // diagnostic ablations of the sample launch (GR_SEARCH_DEBUG bits 8, 16, 32: results then rely on an earlier call's thresholds)
 };
 template <int D4, int NQ, int MODE>
 __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict__ emb, long N, long stride, SmallQ qr, ApproxArgs a) {
@@ -870,7 +864,6 @@ __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict_
   for (int q = 0; q < NQ; ++q) { tauq[q] = (MODE == 1 && q < Q) ? a.tau[q] : INFINITY; cnt[q] = 0u; wmax[q] = -INFINITY; }
   int buf = 0;
   for (long t = wg; t < ntiles; t += nwg, buf = buf + 1 == NB ? 0 : buf + 1) {
-    if (MODE == 0 && (GR_DBG(a.dbg) & 32)) break;                         // ablation: no sample tile
     if (NB == 1) request(t, 0);                                   // (the sample: one tile per workgroup)
     // tile t has landed once at most the requests issued AFTER it are outstanding: V per tile already requested behind it (vmcnt counts in issue order)
     if (NB >= 3 && t + (long)(NB - 2) * nwg < ntiles) {
@@ -989,7 +982,6 @@ __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict_
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (GR_DBG(a.dbg) & 16) return;                                          // ablation: no arrival, no threshold
   unsigned arrived = 0u;
   if (lane == 0) arrived = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   arrived = (unsigned)__shfl((int)arrived, 0, 64);
@@ -997,7 +989,6 @@ __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict_
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (lane == 0) __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next search
-  if (GR_DBG(a.dbg) & 8) return;                                           // ablation: the last workgroup's threshold computation (leaves the bins dirty)
   constexpr int BPL = SBINS / 64;                                  // bins per lane: lane L owns bins [BPL L, BPL L + BPL)
   unsigned hb[NQ][BPL];
 #pragma unroll
@@ -1194,9 +1185,8 @@ __global__ __launch_bounds__(NT) void small_select_kernel(const float* __restric
 }
 
 bool cosine_topk_small_path(long N, int d, int Q, int k) {
-  static const bool on = !GR_KNOB_SET("GR_SEARCH_NO_APPROX");
   const int d4 = d / 4;
-  return on && Q >= 1 && Q <= AQ_MAX && (d & 3) == 0 && (d4 == 8 || d4 == 16 || d4 == 25 || d4 == 32) && N >= FILTER_MIN_ROWS && k <= 128 &&
+  return Q >= 1 && Q <= AQ_MAX && (d & 3) == 0 && (d4 == 8 || d4 == 16 || d4 == 25 || d4 == 32) && N >= FILTER_MIN_ROWS && k <= 128 &&
          (size_t)N * d * 4 < 0x7FFFF000ul;
 }
 template <int D4, int MODE>
@@ -1231,13 +1221,12 @@ size_t cosine_topk_workspace_bytes(long N, int d, int Q, int k) {
   return sizeof(float) * ((size_t)Q * d + Q + 8) + sizeof(unsigned) * (size_t)(Q + 8) + 1024 + keys;
 }
 
-int g_search_debug = 0;      // diagnostic ablations (GR_SEARCH_DEBUG: 1 no global loads, 2 no arithmetic, 4 no epilogue; results are then wrong by design)
 template <bool ACCF, int MODE>
 static void launch_keys_nq(int nq, unsigned nb, hipStream_t s, const float* emb, long N, int d, const float* needles, const float* w22, int q0,
                            unsigned long long* keys, long stride, const unsigned long long* bound, unsigned* counts) {
   const bool dc20 = d % 20 == 0 && d % 32 != 0;
-#define GR_KEYS(NQ_) do { if (dc20) hipLaunchKernelGGL((cos_keys_kernel<ACCF, MODE, NQ_, 20>), dim3(nb), dim3(ROWS), 0, s, emb, N, d, needles, w22, q0, keys, stride, bound, counts, g_search_debug); \
-                          else hipLaunchKernelGGL((cos_keys_kernel<ACCF, MODE, NQ_, 32>), dim3(nb), dim3(ROWS), 0, s, emb, N, d, needles, w22, q0, keys, stride, bound, counts, g_search_debug); } while (0)
+#define GR_KEYS(NQ_) do { if (dc20) hipLaunchKernelGGL((cos_keys_kernel<ACCF, MODE, NQ_, 20>), dim3(nb), dim3(ROWS), 0, s, emb, N, d, needles, w22, q0, keys, stride, bound, counts); \
+                          else hipLaunchKernelGGL((cos_keys_kernel<ACCF, MODE, NQ_, 32>), dim3(nb), dim3(ROWS), 0, s, emb, N, d, needles, w22, q0, keys, stride, bound, counts); } while (0)
   switch (nq) {
     case 1: GR_KEYS(1); break; case 2: GR_KEYS(2); break; case 3: GR_KEYS(3); break; case 4: GR_KEYS(4); break;
     case 5: GR_KEYS(5); break; case 6: GR_KEYS(6); break; case 7: GR_KEYS(7); break; default: GR_KEYS(8); break;
@@ -1262,7 +1251,6 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
                        long* idx_out, float* score_out, int accf, void* workspace, hipStream_t s, unsigned* status_dev, int unfiltered,
                        const long* query_rows_host, unsigned* arrival_counter, unsigned* done_words, unsigned seq) {
   if (k > 1024 || k < 1 || k > N || N >= 0xFFFFFFFFl || d < 1 || d > 4096 * 4) return -1;
-  g_search_debug = GR_KNOB("GR_SEARCH_DEBUG", 0);
   // workspace carve: needles [Q][d] | w22 [Q] | counts [Q] | keys A | keys B | keys C
   char* w = reinterpret_cast<char*>(workspace);
   float* needles = reinterpret_cast<float*>(w); w += sizeof(float) * (size_t)Q * d;
@@ -1286,7 +1274,7 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
     SmallQ qr{}; for (int q = 0; q < AQ_MAX; ++q) qr.rows[q] = query_rows_host[q < Q ? q : 0];
     ApproxArgs a{};
     a.needles = needles; a.w22 = w22; a.hist = hist; a.counter = counter; a.tau = tau; a.cand_idx = cidx; a.cand_sc = csc; a.counts = wcnt;
-    a.status = status_dev; a.Q = Q; a.k = k; a.accf = accf; a.eps2 = 2.f * (float)(2 * d + 16) * 5.9604645e-8f; a.dbg = g_search_debug;
+    a.status = status_dev; a.Q = Q; a.k = k; a.accf = accf; a.eps2 = 2.f * (float)(2 * d + 16) * 5.9604645e-8f;
     {
       KtScope kt("cos_approx_kernel (sample + bound)", 0.0, 4.0 * S * d, s);
       launch_approx<0>(d / 4, Q, swg, s, emb, S, stride, qr, a);
@@ -1295,8 +1283,7 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
       KtScope kt("cos_approx_kernel", 2.0 * N * d * Q, 4.0 * N * d, s);
       launch_approx<1>(d / 4, Q, (unsigned)awgs, s, emb, N, 1L, qr, a);
     }
-    static const bool old_select = GR_KNOB_SET("GR_SEARCH_OLD_SELECT");       // A/B: round 4's first selection kernel (no completion words: the caller synchronises)
-    if (old_select || k > SSEL_MAX / 2) {
+    if (k > SSEL_MAX / 2) {      // round 4's first selection kernel (no completion words: the caller synchronises)
       KtScope kt("batched_select_kernel", 0.0, 0.0, s);
       if (accf) hipLaunchKernelGGL(batched_select_kernel<true>, dim3(Q), dim3(1024), 0, s, emb, d, needles, w22, cidx, csc, wcnt, (long)awgs, k, idx_out, score_out, status_dev, ASLOT, a.eps2, qr, 1);
       else hipLaunchKernelGGL(batched_select_kernel<false>, dim3(Q), dim3(1024), 0, s, emb, d, needles, w22, cidx, csc, wcnt, (long)awgs, k, idx_out, score_out, status_dev, ASLOT, a.eps2, qr, 1);
@@ -1309,9 +1296,7 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
   }
   if (accf) hipLaunchKernelGGL(needle_prep_kernel<true>, dim3((Q + 63) / 64), dim3(64), 0, s, emb, d, query_rows_dev, Q, needles, w22, counts, status_dev);
   else hipLaunchKernelGGL(needle_prep_kernel<false>, dim3((Q + 63) / 64), dim3(64), 0, s, emb, d, query_rows_dev, Q, needles, w22, counts, status_dev);
-  static const bool batched_on = !GR_KNOB_SET("GR_SEARCH_NO_BATCHED");
-  static const int batch_min_q = GR_KNOB("GR_BATCH_MIN_Q", BATCH_MIN_Q);
-  if (filter && batched_on && Q >= batch_min_q && Q <= BQ_MAX && d <= BD_MAX && k <= 128 && N >= 2 * BSAMPLE_ROWS) {      // (k distinct workgroup maxima must exist: 256 workgroups)
+  if (filter && Q >= BATCH_MIN_Q && Q <= BQ_MAX && d <= BD_MAX && k <= 128 && N >= 2 * BSAMPLE_ROWS) {      // (k distinct workgroup maxima must exist: 256 workgroups)
     // keys A = sample scores [Q][S] | tau [Qpad] | sqrt(w22) [Qpad] | bf16 needles [Qpad][KS] | candidate rows [Q][nwg][BSLOT] | scores | counts [Q][nwg]
     // sample: BSAMPLE_ROWS strided rows in workgroups of 256; each leaves its maximum per needle, tau from the k-th largest of those
     const long S = BSAMPLE_ROWS, nwg = (N + 255) / 256, stride = N / S, swg = S / 256;
@@ -1321,11 +1306,11 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
     unsigned* cidx = reinterpret_cast<unsigned*>(nb16 + (size_t)Qpad * KS); float* csc = reinterpret_cast<float*>(cidx + (size_t)Q * nwg * BSLOT);
     unsigned* wcnt = reinterpret_cast<unsigned*>(csc + (size_t)Q * nwg * BSLOT);
     const size_t lds0 = (size_t)256 * KS * 2 + sizeof(float) * (256 + 128 + 128) + sizeof(unsigned) * (size_t)((((Q > 128 ? Q : 128) + 1) & ~1) + 2);
-    // the main pass's per-wave hit queues: what two workgroups per CU leave of the LDS, at most 256 entries per wave (~20 expected per tile); none below 32
-    int qcap = (int)(((size_t)80 * 1024 - lds0) / (4 * 8)); qcap = qcap > 256 ? 256 : (qcap < 32 ? 0 : qcap & ~31);
-    qcap = GR_KNOB("GR_BATCHED_QCAP", qcap);                   // ablation build: 0 = round 4's direct hit path
+    // the main pass's per-wave hit queues: what two workgroups per CU leave of the LDS, at most QCAP_MAX entries per wave (~20 expected per tile);
+    // none below QCAP_MIN (then round 4's direct hit path)
+    constexpr int QCAP_MAX = 256, QCAP_MIN = 32;
+    int qcap = (int)(((size_t)80 * 1024 - lds0) / (4 * 8)); qcap = qcap > QCAP_MAX ? QCAP_MAX : (qcap < QCAP_MIN ? 0 : qcap & ~31);
     const size_t lds = lds0 + (size_t)4 * 8 * qcap;
-    qcap |= GR_KNOB("GR_BATCHED_DEBUG", 0) << 16;
     hipLaunchKernelGGL(needles_bf16_kernel, dim3((unsigned)(((long)Qpad * KS + 255) / 256)), dim3(256), 0, s, needles, w22, Q, Qpad, d, KS, nb16, sw22s, tau);
 #define GR_MFMA(MODE_, grid_, gy_, N_, stride_, tau_, out_, ci_, cs_, wc_)                                                                  \
     do {                                                                                                                              \
@@ -1338,11 +1323,11 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
     } while (0)
     {
       KtScope kt("cos_mfma_kernel (sample)", 2.0 * S * d * Q, 4.0 * S * d, s);
-      const int tiles_q = (Q + 63) / 64, gy = GR_KNOB("GR_BATCHED_SAMPLE_Y", tiles_q >= 16 ? 4 : (tiles_q >= 4 ? 2 : 1));
+      // sample grid: the needle tiles of 64 split over gy workgroup rows (4 from 16 tiles, 2 from 4)
+      const int tiles_q = (Q + 63) / 64, gy = tiles_q >= 16 ? 4 : (tiles_q >= 4 ? 2 : 1);
       GR_MFMA(0, (unsigned)((S + 255) / 256), (unsigned)gy, S, stride, (const float*)nullptr, samp, (unsigned*)nullptr, (float*)nullptr, (unsigned*)nullptr);
     }
-    static const bool old_tail = GR_KNOB_SET("GR_BATCHED_OLD_TAIL");      // A/B: round 4's first threshold and selection kernels (bitonic sorts of 1024 per-thread maxima)
-    if (old_tail || swg > 256) {
+    if (swg > 256) {      // round 4's first threshold kernel (bitonic sorts of 1024 per-thread maxima)
       KtScope kt("batched_tau_kernel", 0.0, 4.0 * swg * Q, s);
       hipLaunchKernelGGL(batched_tau_kernel, dim3(Q), dim3(1024), 0, s, samp, swg, k, sw22s, tau, w22);
     } else {

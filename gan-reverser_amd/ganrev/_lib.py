@@ -111,7 +111,6 @@ _SIGS = {
     "gr_range_guard_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gr_range_guard_scan_params": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "gr_search_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
-    "gr_debug_stamps": (C.c_int, [_P, _P]),
     "gr_set_timing": (C.c_int, [_P, C.c_int]),
     "gr_last_step_times": (C.c_int, [_P, _P]),
     "gr_event_record": (C.c_int, [_P, C.c_int]),

@@ -178,9 +178,8 @@ int gr_train_r_step(gr_net* gnet, gr_net* rnet, const float* noise_dev, int batc
 int gr_set_conv_mode(gr_ctx* ctx, int mode);
 int gr_get_conv_mode(gr_ctx* ctx);
 /* Runtime knobs.  These are ALL the keys the shipping library answers (anything else: GR_ERR_INVALID); environment variables read once in gr_init:
- * GR_CONV_MODE (f32 | bf16x6 | f16x3, default f16x3), GR_RANGE_GUARD (0 | 1), GR_SIDE_WGRAD (-1 | 0 | 1), GR_FUSED_HEAD (0 | 1).  Every other GR_* switch
- * of earlier rounds - A/B controls of variants that lost their measurement, ablation bits that make kernels compute wrong results by design - exists only in
- * the ablation build (make -C gan-reverser_amd/csrc ablate -> libganrev_ablate.so, never loaded by the tests or bench.py).
+ * GR_CONV_MODE (f32 | bf16x6 | f16x3, default f16x3), GR_RANGE_GUARD (0 | 1), GR_SIDE_WGRAD (-1 | 0 | 1), GR_FUSED_HEAD (0 | 1).  Nothing else selects
+ * kernels at run time: variants that lost their A/B measurement are not in the sources (docs/HISTORY.md names them).
  *   "p16_min_tiles"  (default 128, process-wide) smallest tile count at which a 3x3 convolution takes the operand-ready (P16) kernels; tests set 1 to
  *                    exercise that path on small shapes
  *   "stack8_min_wgs" (default 128, process-wide) smallest grid at which 8x8 planes are stacked four to a convolution tile; tests force the path
@@ -226,7 +225,6 @@ int gr_range_guard_stats(gr_ctx* ctx, int64_t* scans, int64_t* fallbacks);
  * the net's weights and BatchNorm scales; a hostile spread keeps the context on bf16x6 (as gr_train_r_step's sampled scan does).
  * tripped_out (nullable): 1 when the context's guard has tripped. */
 int gr_range_guard_scan_params(gr_net* net, int* tripped_out);
-int gr_debug_stamps(gr_ctx* ctx, void* dev_buf);   /* diagnostic builds: device buffer for in-kernel time stamps (tools/stamps_p16.py) */
 int gr_set_timing(gr_ctx* ctx, int mode /*0 off, 1 per-phase events in gr_train_r_step, 2 per-kernel events*/);
 /* mode 2: JSON array of {kernel, phase, launches, total_ms, flops, bytes} (algorithmic flops/bytes) accumulated since it was
  * enabled; phase = the part of gr_train_r_step that launched it ("G forward", "R forward", "loss", "R backward", "adam") or "" */

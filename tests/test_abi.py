@@ -111,17 +111,20 @@ def test_lua_ffi_cdef_matches_the_header():
 
 
 def test_every_runtime_knob_is_documented_and_the_shipping_library_reads_few_environment_variables():
-    """the shipping library keeps <= 10 documented runtime knobs.  Every gr_set_tuning key of the non-ablation build must be
-    described in include/ganrev.h's comment on gr_set_tuning, every environment variable gr_init reads must be named there and in README.md, and the kernels'
-    sources may call getenv at most 10 times (everything else is GR_KNOB: a constant outside the ablation build)."""
+    """the library keeps <= 10 documented runtime knobs.  There is one library flavour: no ablation switch or probe branch
+    is left in the sources, and the environment variables read are exactly the four gr_init documents.  Every gr_set_tuning key must be described in
+    include/ganrev.h's comment on gr_set_tuning and listed in README.md; every environment variable must be named in both."""
     import os, re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "gan-reverser_amd", "csrc")
-    net = open(os.path.join(csrc, "net.hip")).read()
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) or f == "Makefile"}
+    for f, src in sources.items():
+        stale = sorted(set(re.findall(r"\bGR_(?:KNOB\w*|DBG|ABLATE|PROBE_\w*)", src)))
+        assert not stale, f"{f}: {stale} (the ablation build is retired: one library, whose source says what it runs)"
+    net = sources["net.hip"]
     body = net[net.index('extern "C" int gr_set_tuning('):]
     body = body[:body.index("\n}\n")]
-    shipping = re.sub(r"#ifdef GR_ABLATE.*?#endif", "", body, flags=re.S)
-    keys = re.findall(r'!strcmp\(key, "(\w+)"\)', shipping)
+    keys = re.findall(r'!strcmp\(key, "(\w+)"\)', body)
     assert 1 <= len(keys) <= 10, keys
     header = open(os.path.join(root, "include", "ganrev.h")).read()
     doc = header[header.index("/* Runtime knobs."):header.index("int gr_set_tuning(")]
@@ -130,11 +133,10 @@ def test_every_runtime_knob_is_documented_and_the_shipping_library_reads_few_env
         assert f'"{k}"' in doc, f"gr_set_tuning key {k} is not documented in include/ganrev.h"
         assert f"`{k}`" in readme, f"gr_set_tuning key {k} is not listed in README.md"
     n_getenv, envs = 0, set()
-    for f in os.listdir(csrc):
-        if f.endswith(".hip"):
-            src = open(os.path.join(csrc, f)).read()
-            n_getenv += len(re.findall(r"\bgetenv\(", src))
-            envs |= set(re.findall(r'getenv\("(GR_\w+)"\)', src))
+    for src in sources.values():
+        n_getenv += len(re.findall(r"\bgetenv\(", src))
+        envs |= set(re.findall(r'getenv\("(GR_\w+)"\)', src))
     assert n_getenv <= 10, n_getenv
+    assert envs == {"GR_CONV_MODE", "GR_RANGE_GUARD", "GR_SIDE_WGRAD", "GR_FUSED_HEAD"}, sorted(envs)
     for e in envs:
         assert e in doc and e in readme, f"environment variable {e} is read by the library but not documented"

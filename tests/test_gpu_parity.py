@@ -228,7 +228,7 @@ def test_R_operand_ready_path_vs_oracle(oracle, f16_path, dims, nd, B):
     """f16x3 with the operand-ready (P16) pipeline forced onto small shapes (conftest.f16_path): the pipeline kernels of a
     stage write the next convolution's input - and pass B of the backward the data-gradient convolution's input - as
     [8-channel group][term][pixel] fp16 hi/lo vectors scaled by an A-PRIORI bound of the tensor's maximum (BatchNorm
-    statistics + max|y|; K * max|dz|), and conv3x3_p16_wide_kernel stages them by LDS-DMA.  32x32 planes (one image = two
+    statistics + max|y|; K * max|dz|), and conv3x3_p16_quad_kernel stages them by LDS-DMA.  32x32 planes (one image = two
     tiles), 16x16 planes (two stacked images per tile; odd batch: a half-empty tile), 64x64 (two column tiles).  Same bars as
     every other R case; the default-selection run of the same shapes is the control."""
     from ganrev import models, synth

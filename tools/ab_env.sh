@@ -1,5 +1,6 @@
 #!/bin/bash
-# same-box interleaved A/B of an environment switch over bench.py (headline arithmetic only): tools/ab_env.sh VAR=1 [cfg2|cfg3] [rounds] [kernel filter regex]
+# same-box interleaved A/B of one of the four environment variables the library reads (GR_CONV_MODE, GR_RANGE_GUARD, GR_SIDE_WGRAD, GR_FUSED_HEAD)
+# over bench.py (headline arithmetic only): tools/ab_env.sh VAR=VALUE [cfg2|cfg3] [rounds] [kernel filter regex]
 # prints ms/step and the matching per-kernel rows with the switch off (A) and on (B)
 V=$1; WL=${2:-cfg3}; N=${3:-2}; F=${4:-.}
 for i in $(seq 1 $N); do

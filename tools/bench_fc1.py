@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel HIP-event times of R.fc1's three GEMMs (nn.Linear(128 h w -> 512), models.lua:447: forward, gradInput, accGradParameters) at the cfg2 / cfg3 shapes,
-training mode, f16x3:   python tools/bench_fc1.py        (ablation build: GR_GEMM_WGS / GR_GEMM_MIN_KLEN / GR_GEMM_SMALL_TILES select the split-K plan)"""
+training mode, f16x3:   python tools/bench_fc1.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "gan-reverser_amd"), ROOT]
