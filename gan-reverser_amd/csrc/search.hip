@@ -628,18 +628,9 @@ __device__ __forceinline__ unsigned kth_of_maxima(unsigned mine, unsigned* list,
 // tau[q] from the approximate sample scores [Q][S]
 // (a needle whose squared norm 1 / w22 - 1e-12 lies outside the fp16 pass's range gets -inf: every row passes, every list overflows, the call reruns unbatched)
 __device__ __forceinline__ bool batched_needle_ok(float w22q) { const float n2 = 1.f / w22q; return n2 >= GR_BNRM_MIN && n2 <= GR_BNRM_MAX; }
-__global__ __launch_bounds__(1024) void batched_tau_kernel(const float* __restrict__ samp, long S, int k, const float* __restrict__ sw22s, float* __restrict__ tau, const float* __restrict__ w22) {
-  __shared__ unsigned list[1024];
-  const int q = blockIdx.x;
-  unsigned mine = 0u;
-  for (long i = threadIdx.x; i < S; i += 1024) { const unsigned o = orderable(samp[(long)q * S + i]); mine = o > mine ? o : mine; }
-  const unsigned kth = kth_of_maxima(mine, list, k);
-  // stored divided by sqrt(w22): cos_mfma_kernel compares (dot * sqrt(w32)) with it; the rounding of the division is far inside the 2 BERR slack
-  if (threadIdx.x == 0) tau[q] = (kth && batched_needle_ok(w22[q])) ? (unorderable(kth) - 2.f * GR_BERR) / sw22s[q] : -INFINITY;
-}
-// the same threshold by ONE wave per needle (four needles per workgroup): the <= 256 sample maxima as orderable bit patterns, four per lane, and the exact
-// k-th largest built bit by bit from the top (res |= bit while at least k patterns are >= the trial value) - no LDS, no block barriers (the 1024-thread
-// bitonic sort above took 23 us for 1024 needles)
+// ONE wave per needle (four needles per workgroup): the <= 256 sample maxima as orderable bit patterns, four per lane, and the exact k-th largest
+// built bit by bit from the top (res |= bit while at least k patterns are >= the trial value) - no LDS, no block barriers (round 4's 1024-thread
+// bitonic sort of the maxima took 23 us for 1024 needles; removed with the branch that could never launch it, git history)
 __global__ __launch_bounds__(256) void batched_tau_wave_kernel(const float* __restrict__ samp, int S, int Q, int k, const float* __restrict__ sw22s, float* __restrict__ tau, const float* __restrict__ w22) {
   const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= Q) return;
@@ -653,6 +644,7 @@ __global__ __launch_bounds__(256) void batched_tau_wave_kernel(const float* __re
     const int c = __popcll(__ballot(ov[0] >= t)) + __popcll(__ballot(ov[1] >= t)) + __popcll(__ballot(ov[2] >= t)) + __popcll(__ballot(ov[3] >= t));
     if (c >= k) res = t;
   }
+  // stored divided by sqrt(w22): cos_mfma_kernel compares (dot * sqrt(w32)) with it; the rounding of the division is far inside the 2 BERR slack
   if (lane == 0) tau[q] = (res && batched_needle_ok(w22[q])) ? (unorderable(res) - 2.f * GR_BERR) / sw22s[q] : -INFINITY;
 }
 // per needle: second cut on the approximate scores, exact re-score of what is left, sort, decode
@@ -1028,6 +1020,8 @@ __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict_
 //   done    every thread's stores fenced at system scope, then ONE word per needle = the call's sequence number: the host polls it (no stream
 //           synchronisation: 1-3 us per search, measured).
 constexpr int SSEL_BINS = 2048, SSEL_MAX = 256;
+constexpr int SMALL_K_MAX = 128;      // largest k of the small path (cosine_topk_small_path)
+static_assert(SSEL_MAX / 2 >= SMALL_K_MAX, "small_select_kernel keeps up to SSEL_MAX rows past its cut: twice the small path's k");
 // NT threads (256: the small path's <= 2048 lists per needle; 512: the batched path's N / 256 lists), SLOT entries per list, FROM_ROWS: the needle is row
 // qr.rows[q] of the table and its norm is formed here (small path) / the needle and its 1 / (|a|^2 + 1e-12) come from needle_prep_kernel's arrays (batched);
 // lo_scale (nullable): tau[q] * lo_scale[q] is the lower edge of the candidates' scores (the batched path stores tau divided by sqrt(w22)).
@@ -1186,7 +1180,7 @@ __global__ __launch_bounds__(NT) void small_select_kernel(const float* __restric
 
 bool cosine_topk_small_path(long N, int d, int Q, int k) {
   const int d4 = d / 4;
-  return Q >= 1 && Q <= AQ_MAX && (d & 3) == 0 && (d4 == 8 || d4 == 16 || d4 == 25 || d4 == 32) && N >= FILTER_MIN_ROWS && k <= 128 &&
+  return Q >= 1 && Q <= AQ_MAX && (d & 3) == 0 && (d4 == 8 || d4 == 16 || d4 == 25 || d4 == 32) && N >= FILTER_MIN_ROWS && k <= SMALL_K_MAX &&
          (size_t)N * d * 4 < 0x7FFFF000ul;
 }
 template <int D4, int MODE>
@@ -1283,12 +1277,6 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
       KtScope kt("cos_approx_kernel", 2.0 * N * d * Q, 4.0 * N * d, s);
       launch_approx<1>(d / 4, Q, (unsigned)awgs, s, emb, N, 1L, qr, a);
     }
-    if (k > SSEL_MAX / 2) {      // round 4's first selection kernel (no completion words: the caller synchronises)
-      KtScope kt("batched_select_kernel", 0.0, 0.0, s);
-      if (accf) hipLaunchKernelGGL(batched_select_kernel<true>, dim3(Q), dim3(1024), 0, s, emb, d, needles, w22, cidx, csc, wcnt, (long)awgs, k, idx_out, score_out, status_dev, ASLOT, a.eps2, qr, 1);
-      else hipLaunchKernelGGL(batched_select_kernel<false>, dim3(Q), dim3(1024), 0, s, emb, d, needles, w22, cidx, csc, wcnt, (long)awgs, k, idx_out, score_out, status_dev, ASLOT, a.eps2, qr, 1);
-      return 0;
-    }
     KtScope kt("small_select_kernel", 0.0, 0.0, s);
     if (accf) hipLaunchKernelGGL((small_select_kernel<true, 256, ASLOT, true>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
     else hipLaunchKernelGGL((small_select_kernel<false, 256, ASLOT, true>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
@@ -1307,7 +1295,8 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
     unsigned* wcnt = reinterpret_cast<unsigned*>(csc + (size_t)Q * nwg * BSLOT);
     const size_t lds0 = (size_t)256 * KS * 2 + sizeof(float) * (256 + 128 + 128) + sizeof(unsigned) * (size_t)((((Q > 128 ? Q : 128) + 1) & ~1) + 2);
     // the main pass's per-wave hit queues: what two workgroups per CU leave of the LDS, at most QCAP_MAX entries per wave (~20 expected per tile);
-    // none below QCAP_MIN (then round 4's direct hit path)
+    // none below QCAP_MIN (then round 4's direct hit path).  For Q <= BQ_MAX that cannot happen: the largest lds0 (Q = 2048, NK = 8) is 79 880 bytes, which
+    // leaves qcap = 32 and 80 904 bytes in all; the direct hit path of cos_mfma_kernel (qcap == 0) stays for a larger BQ_MAX
     constexpr int QCAP_MAX = 256, QCAP_MIN = 32;
     int qcap = (int)(((size_t)80 * 1024 - lds0) / (4 * 8)); qcap = qcap > QCAP_MAX ? QCAP_MAX : (qcap < QCAP_MIN ? 0 : qcap & ~31);
     const size_t lds = lds0 + (size_t)4 * 8 * qcap;
@@ -1327,10 +1316,8 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
       const int tiles_q = (Q + 63) / 64, gy = tiles_q >= 16 ? 4 : (tiles_q >= 4 ? 2 : 1);
       GR_MFMA(0, (unsigned)((S + 255) / 256), (unsigned)gy, S, stride, (const float*)nullptr, samp, (unsigned*)nullptr, (float*)nullptr, (unsigned*)nullptr);
     }
-    if (swg > 256) {      // round 4's first threshold kernel (bitonic sorts of 1024 per-thread maxima)
-      KtScope kt("batched_tau_kernel", 0.0, 4.0 * swg * Q, s);
-      hipLaunchKernelGGL(batched_tau_kernel, dim3(Q), dim3(1024), 0, s, samp, swg, k, sw22s, tau, w22);
-    } else {
+    static_assert(BSAMPLE_ROWS / 256 <= 256, "batched_tau_wave_kernel takes the k-th of at most 256 sample maxima (four per lane)");
+    {
       KtScope kt("batched_tau_wave_kernel", 0.0, 4.0 * swg * Q, s);
       hipLaunchKernelGGL(batched_tau_wave_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, samp, (int)swg, Q, k, sw22s, tau, w22);
     }

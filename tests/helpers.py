@@ -379,3 +379,24 @@ def sharded_search_in_process(local_topk, emb, bounds, needles, k):
         sharded_cosine_topk(local_topk, emb[lo:hi], lo, needles, k, c)
         ci.append(c.got[0]); cs.append(c.got[1])
     return merge_candidates(ci, cs, k)
+
+
+# ------------------------------------------------------------------ search reference, needles in parallel
+def oracle_topk_parallel(oracle, emb, needles, k, accumulate_in_float=False, workers=None):
+    """oracle.cosine_topk over slices of the needle list on a pool of threads, each running the oracle on one core (the oracle is a ctypes library:
+    its calls release the GIL).  Every needle's answer is computed on its own (oracle_net.c: one full sort per needle), so the slicing changes no
+    bit of the result.  The OpenMP thread count is per calling thread, so each worker sets its own."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    needles = np.ascontiguousarray(needles, dtype=np.int64)
+    emb = np.ascontiguousarray(emb, dtype=np.float32)
+    workers = max(1, min(16, os.cpu_count() or 1, needles.size) if workers is None else workers)
+    parts = [p for p in np.array_split(needles, workers) if p.size]
+    oracle.lib()                    # (loaded once, here: the loader is not meant for several threads at once)
+
+    def run(part):
+        oracle.set_threads(1)
+        return oracle.cosine_topk(emb, part, k, accumulate_in_float=accumulate_in_float)
+    with ThreadPoolExecutor(max_workers=len(parts)) as ex:
+        res = list(ex.map(run, parts))
+    return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])
