@@ -404,6 +404,16 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
 constexpr int SEARCH_STATE_WORDS = 16 + 8 * 1024;
 bool cosine_topk_small_path(long N, int d, int Q, int k);     // the filtered search takes the fp32-filter path (query rows by value, no device copy of them needed)
 
+// ---------------------------------------------------------------- exact L2 nearest neighbours (sample.lua:130-148; neighbours.hip)
+size_t l2_nearest_workspace_bytes(long n, int Q);
+bool l2_nearest_direct(long n);          // small tables: the exact path outright
+double l2_filter_eps(int d, bool vec);   // relative bound |S~ - S| <= eps S of the streaming pass
+// x [n][d], qs [Q][d], idx_out / dist_out [Q][k], status [Q]: all device.  exact = 0: streaming pass + candidate selection; status[q] = 1 means
+// query q's candidate list overflowed and the call must be repeated with exact = 1 (every row scored exactly; status untouched).  Returns -1
+// for a shape outside 1 <= d <= 65536, 1 <= k <= min(128, n).
+int launch_l2_nearest(const float* x, long n, int d, const float* qs, int Q, int k, long* idx_out, double* dist_out, unsigned* status,
+                      void* workspace, int exact, int num_cus, hipStream_t s);
+
 // ---------------------------------------------------------------- k-means + nearest-centroid pass (apply_r.lua:197-217)
 size_t kmeans_workspace_bytes(long N, int d, int k);
 // all pointers device; cent [k][d] holds the initial centroids on entry and the final ones on return; returns 1 when the

@@ -2110,6 +2110,53 @@ extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* 
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ sample.lua:130-148 findClosestNeighboursOf (neighbours.hip)
+extern "C" int gr_l2_nearest_dev(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
+                                 int64_t* idx_out, double* dist_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table || !queries || !idx_out || !dist_out || n <= 0 || d < 1 || d > 65536 || Q < 1 || Q > 64 || k < 1 || k > n)
+    return fail(c, GR_ERR_INVALID, "gr_l2_nearest: bad arguments (n %lld, d %lld, q %d, k %d)", (long long)n, (long long)d, Q, k);
+  if (k > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: k > 128");
+  if (n >= 0xFFFFFFFFll) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: n >= 2^32 - 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t wsb = (l2_nearest_workspace_bytes(n, Q) + 255) & ~(size_t)255;
+  const size_t res = sizeof(long) * (size_t)Q * k + sizeof(double) * (size_t)Q * k + sizeof(unsigned) * (size_t)Q;
+  int r = ensure_ws(c, wsb + res + 256); if (r) return r;
+  long* d_idx = (long*)((char*)c->ws + wsb); double* d_dist = (double*)(d_idx + (size_t)Q * k); unsigned* d_status = (unsigned*)(d_dist + (size_t)Q * k);
+  std::vector<char> h(res);
+  for (int exact = l2_nearest_direct(n) ? 1 : 0; exact < 2; ++exact) {
+    if (launch_l2_nearest(table, n, (int)d, queries, Q, k, d_idx, d_dist, d_status, c->ws, exact, c->cu_count, c->stream))
+      return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: unsupported size");
+    LAUNCHCHK(c);
+    HIPCHK(c, hipMemcpyAsync(h.data(), d_idx, res, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bool over = false;
+    for (int q = 0; q < Q && !exact; ++q) { unsigned st; memcpy(&st, h.data() + res - sizeof(unsigned) * (size_t)(Q - q), sizeof st); over = over || st != 0u; }
+    if (!over) break;             // (the exact path does not write the status words)
+  }
+  memcpy(idx_out, h.data(), sizeof(long) * (size_t)Q * k);
+  memcpy(dist_out, h.data() + sizeof(long) * (size_t)Q * k, sizeof(double) * (size_t)Q * k);
+  return GR_OK;
+}
+extern "C" int gr_l2_nearest_host(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
+                                  int64_t* idx_out, double* dist_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table || !queries || !idx_out || !dist_out || n <= 0 || d < 1 || d > 65536 || Q < 1 || Q > 64 || k < 1 || k > n)
+    return fail(c, GR_ERR_INVALID, "gr_l2_nearest: bad arguments (n %lld, d %lld, q %d, k %d)", (long long)n, (long long)d, Q, k);
+  if (k > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: k > 128");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t tb = sizeof(float) * (size_t)n * d, qb = sizeof(float) * (size_t)Q * d;
+  float* dev = nullptr;
+  HIPCHK(c, hipMalloc((void**)&dev, tb + ((qb + 255) & ~(size_t)255) + 256));
+  float* dq = (float*)((char*)dev + ((tb + 255) & ~(size_t)255));
+  hipError_t e = hipMemcpyAsync(dev, table, tb, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dq, queries, qb, hipMemcpyHostToDevice, c->stream);
+  int r = e == hipSuccess ? gr_l2_nearest_dev(c, dev, n, d, dq, Q, k, idx_out, dist_out) : fail(c, GR_ERR_HIP, "upload failed");
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipFree(dev);
+  return r;
+}
+
 // ------------------------------------------------------------------ single-kernel entry points
 static int with_prepped(gr_ctx* c, const float* w, int cin, int cout, bool bwd, float** wt) {
   const ConvWeightLayout L = bwd ? conv_weight_layout(cout, cin) : conv_weight_layout(cin, cout);

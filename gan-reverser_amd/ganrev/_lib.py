@@ -120,6 +120,8 @@ _SIGS = {
     "gr_cosine_topk_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gr_cosine_similarity_host": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_float)]),
     "gr_l2_distance_rows_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "gr_l2_nearest_host": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
+    "gr_l2_nearest_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     "gr_kmeans_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gr_cosine_assign_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "gr_malloc": (C.c_int, [_P, C.c_int64, C.POINTER(_P)]),
@@ -286,6 +288,35 @@ class Context:
         self.check(self.lib.gr_l2_distance_rows_host(self.h, _ptr(a2), _ptr(b2), n, a2.shape[1], _ptr(out)), "gr_l2_distance_rows_host")
         return out
 
+    L2_NEAREST_MAX_Q = 64       # queries per gr_l2_nearest_* call (include/ganrev.h)
+
+    def l2_nearest(self, table, queries, k, table_dev=None, n=None, d=None):
+        """sample.lua:130-148 findClosestNeighboursOf: the k nearest rows of `table` [n x d] for each row of `queries` [q x d] by
+        torch.dist, ordered by (distance, row) -> (idx int64 [q, k], dist float64 [q, k]).  table_dev (with n, d): the table is already
+        in device memory (gr_l2_nearest_dev; the queries are uploaded per call).  More than 64 queries take several calls."""
+        if table_dev is None:
+            table = f32(table)
+            n = table.shape[0]
+            d = int(np.prod(table.shape[1:]))
+        n, d = int(n), int(d)
+        qs = f32(queries).reshape(-1, d)
+        nq = qs.shape[0]
+        idx = np.empty((nq, int(k)), dtype=np.int64)
+        dist = np.empty((nq, int(k)), dtype=np.float64)
+        for q0 in range(0, nq, self.L2_NEAREST_MAX_Q):
+            part = np.ascontiguousarray(qs[q0:q0 + self.L2_NEAREST_MAX_Q])
+            oi, od = idx[q0:q0 + len(part)], dist[q0:q0 + len(part)]
+            if table_dev is None:
+                rc = self.lib.gr_l2_nearest_host(self.h, _ptr(table), n, d, _ptr(part), len(part), int(k), _ptr(oi), _ptr(od))
+            else:
+                qd = self.upload(part)
+                try:
+                    rc = self.lib.gr_l2_nearest_dev(self.h, _ptr(table_dev), n, d, _ptr(qd), len(part), int(k), _ptr(oi), _ptr(od))
+                finally:
+                    self.free(qd)
+            self.check(rc, "gr_l2_nearest")
+        return idx, dist
+
     def kmeans(self, x, k, niter, centroids0):
         """unsup.kmeans(x, k, niter) (apply_r.lua:198) from the given initial centroids -> (centroids, totalcounts, labels)."""
         x = f32(x)
@@ -440,6 +471,15 @@ class Net:
         if getattr(self, "h", None):
             self.lib.gr_net_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        # a net nobody holds any more gives its device buffers back (they are sized by the largest batch it ran); not after its
+        # context was shut down - gr_shutdown has released the context the net points to
+        try:
+            if getattr(self, "h", None) and getattr(getattr(self, "ctx", None), "h", None):
+                self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: nothing to report to)
+            pass
 
     def _c(self, rc, what):
         self.ctx.check(rc, what)

@@ -78,3 +78,33 @@ def createNoiseInputs(N, noiseDim, method="normal", seed=1):
     if method == "normal":
         return synth.normal((N, noiseDim), seed)
     raise ValueError(f"Unknown noise method '{method}'")   # utils/nn_utils.lua:48
+
+
+def createImagesFromNoise(model_g, noiseInputs, batchSize):
+    """utils/nn_utils.lua:57-81 — G's images for every noise row, batchSize rows per forward (the reference reads MODEL_G and
+    OPT.batchSize from globals; here they are arguments).  Always a tensor: outputAsList only changed the container."""
+    return forwardBatched(model_g, noiseInputs, batchSize)
+
+
+def createImages(model_g, N, noiseDim, batchSize, method="normal", seed=1):
+    """utils/nn_utils.lua:83-91 — createImagesFromNoise(createNoiseInputs(N))."""
+    return createImagesFromNoise(model_g, createNoiseInputs(N, noiseDim, method, seed), batchSize)
+
+
+def predictionOrder(predictions, ascending, nbMaxOut):
+    """The ordering step of sortImagesByPrediction (utils/nn_utils.lua:116-127): positions of the first min(nbMaxOut, N) predictions,
+    ascending or descending.  Equal predictions keep ascending input order (a stable sort); the reference's table.sort is unstable,
+    so its order among ties is unspecified."""
+    p = np.asarray(predictions, dtype=np.float64).reshape(-1)
+    order = np.argsort(p if ascending else -p, kind="stable")
+    return order[:max(0, min(int(nbMaxOut), p.size))]
+
+
+def sortImagesByPrediction(model_d, images, ascending, nbMaxOut, batchSize):
+    """utils/nn_utils.lua:101-129 — D's prediction for every image (batchSize images per forward; D as it is, the caller puts it in
+    evaluate mode as sample.lua:203 does), then the images ordered by it -> (images [m x C x H x W], predictions [m]),
+    m = min(nbMaxOut, N).  Descending puts what D takes for real first.  Ties: see predictionOrder."""
+    images = np.asarray(images, dtype=np.float32)
+    predictions = forwardBatched(model_d, images, batchSize).reshape(len(images), -1)[:, 0]
+    order = predictionOrder(predictions, ascending, nbMaxOut)
+    return images[order], predictions[order]

@@ -60,6 +60,10 @@ int gr_embed_dev(gr_net* gnet, gr_net* const* rnets, int n_rnets, const float* n
                  float* images_out_dev, float* const* attr_out_dev);                                       /* apply_r.lua:145-153 */
 int gr_cosine_topk_dev(gr_ctx*, const float* emb_dev, int64_t n, int d, const int64_t* rows, int q, int k,
                        int64_t* idx, float* score, int accumulate_in_float);
+int gr_l2_nearest_host(gr_ctx*, const float* table, int64_t n, int64_t d, const float* queries, int q, int k,
+                       int64_t* idx, double* dist);                                                        /* sample.lua:130-148 */
+int gr_l2_nearest_dev(gr_ctx*, const float* table_dev, int64_t n, int64_t d, const float* queries_dev, int q, int k,
+                      int64_t* idx, double* dist);
 int gr_synchronize(gr_ctx*);
 int gr_adam_reset(gr_net*);
 int gr_train_r_step(gr_net* gnet, gr_net* rnet, const float* noise_dev, int batch, int global_batch,

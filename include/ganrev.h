@@ -255,6 +255,27 @@ int gr_search_stats(gr_ctx* ctx, int64_t* reruns);
 /* ---- apply_r.lua:355-372 (detectAnomalies): out[i] = torch.dist(a[i], b[i]) = sqrt(sum_j (a_ij - b_ij)^2), rows of length d ---- */
 int gr_l2_distance_rows_host(gr_ctx* ctx, const float* a_host, const float* b_host, int64_t n, int64_t d, double* out_host);
 
+/* ---- sample.lua:130-148 findClosestNeighboursOf: the k nearest table rows of each query by torch.dist ----
+ * Contract: for each query q [d] and table row x_j [d] (table [n x d], fp32, contiguous)
+ *   S(q, j) = sum_{i = 0 .. d-1} (double)(t_i * t_i), t_i = |q_i - x_ji| in fp32, t_i * t_i rounded to fp32 (no fused multiply-add),
+ *             summed left to right in fp64;  dist(q, j) = sqrt(S) in fp64
+ * (the torch.dist convention of gr_l2_distance_rows_host).  Results are ordered by (dist ascending, row index ascending) and the first k
+ * are returned: idx_out_host / dist_out_host [q x k], row-major per query, on the host; the call is synchronous.  k = 1 is sample.lua's
+ * loop (its strict < keeps the first minimum).  +inf (fp32 overflow of t * t) is an ordinary value; a NaN distance orders after every
+ * number, +inf included.  One divergence: the reference loop starts from row 1's distance, so a NaN there is returned by it, never here.
+ * Distances are bit-identical to the sequential fp64 sum, indices those of a full sort.
+ * How: one streaming pass sums the same fp32 terms per lane in fp32 and combines the lanes in fp64 (S~, |S~ - S| <= eps S with
+ * eps = (T + 2) 2^-24 + (d + 64) 2^-51, T = terms per lane <= 4 ceil(d / 256)); the rows with S~ within that window of a bound on the
+ * k-th smallest are re-scored exactly.  Tables of at most 4096 rows, and calls where a candidate list overflows (hundreds of exact
+ * copies of the nearest row, a constant table, sums near the fp32 range), score every row exactly instead (kernel "l2_exact_kernel"
+ * in gr_kernel_times).  Queries are taken 16 per pass over the table.
+ * Limits: 1 <= d <= 65536, 1 <= q <= 64, 1 <= k <= n; null pointers or n <= 0 return GR_ERR_INVALID, k > 128 GR_ERR_UNSUPPORTED.
+ * _host uploads the table and the queries; _dev takes both in device memory (16-byte alignment and d % 4 == 0 select 16-byte loads). */
+int gr_l2_nearest_host(gr_ctx* ctx, const float* table_host, int64_t n, int64_t d, const float* queries_host, int q, int k,
+                       int64_t* idx_out_host, double* dist_out_host);
+int gr_l2_nearest_dev(gr_ctx* ctx, const float* table_dev, int64_t n, int64_t d, const float* queries_dev, int q, int k,
+                      int64_t* idx_out_host, double* dist_out_host);
+
 /* ---- apply_r.lua:197-217 (createClusterImages): clustering of the recovered noise vectors ----
  * gr_kmeans_host replaces `unsup.kmeans(attributes, nbClusters, nbIterations)` (apply_r.lua:198; un-vendored luarock, restated
  * from memory - see csrc/kmeans.hip): centroids_inout [k x d] carries the INITIAL centroids in (upstream draws them from
