@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include <rccl/rccl.h>
 #include <roctracer/roctx.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -59,7 +60,7 @@ struct gr_ctx {
   // f16x3 range guard (kernels.h "range guard"): the alarm word lives behind the loss scalar (d_loss + 16 bytes,
   // mirrored at h_loss + 16), chmax is the per-channel scratch of the scans
   int range_guard = 1;                 // 1: on (gr_set_tuning "range_guard")
-  unsigned* guard_chmax = nullptr; size_t guard_chmax_cap = 0;
+  unsigned* guard_chmax = nullptr; size_t guard_chmax_cap = 0;     // (capacity in bytes)
   long guard_scans = 0, guard_fallbacks = 0;
   long search_reruns = 0;              // searches whose sample-bound filter overflowed and ran again unfiltered
   void* pin = nullptr; size_t pin_bytes = 0;   // pinned staging for small results (search)
@@ -199,23 +200,22 @@ static const StatSync* stat_sync(gr_ctx* c, StatSync& ss, int C, double n_local)
 // roctx range of one phase of gr_train_r_step (shows up in rocprofv3 --marker-trace / the rocprof timeline; a no-op without a tool)
 struct PhaseRange { explicit PhaseRange(const char* name) { roctxRangePushA(name); } ~PhaseRange() { roctxRangePop(); } };
 
-static int ensure_ws(gr_ctx* c, size_t bytes) {
-  if (bytes <= c->ws_bytes) return GR_OK;
-  if (c->ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->ws)); c->ws = nullptr; c->ws_bytes = 0; }
-  bytes = (bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-  HIPCHK(c, hipMalloc(&c->ws, bytes));
-  c->ws_bytes = bytes;
+// Device buffers p[0..nbuf) that share the capacity `cap` (bytes) get `bytes` each when they hold less.  The old ones are freed once
+// stream s, the one that may still read them, has drained (a buffer of capacity 0 was never handed to a kernel).  Contents are not kept.
+template <class T> static int grow_dev(gr_ctx* c, T** p, size_t& cap, size_t bytes, hipStream_t s, int nbuf = 1) {
+  if (bytes <= cap) return GR_OK;
+  if (cap) HIPCHK(c, hipStreamSynchronize(s));
+  for (int i = 0; i < nbuf; ++i) { HIPCHK(c, hipFree(p[i])); p[i] = nullptr; }
+  cap = 0;
+  for (int i = 0; i < nbuf; ++i) HIPCHK(c, hipMalloc((void**)&p[i], bytes));
+  cap = bytes;
   return GR_OK;
 }
+// the workspaces grow past the next MiB boundary
+static size_t past_next_mib(size_t bytes) { return (bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1); }
+static int ensure_ws(gr_ctx* c, size_t bytes) { return bytes <= c->ws_bytes ? GR_OK : grow_dev(c, &c->ws, c->ws_bytes, past_next_mib(bytes), c->stream); }
 // workspace of the side stream (weight gradients running beside the rest of backward)
-static int ensure_ws2(gr_ctx* c, size_t bytes) {
-  if (bytes <= c->ws2_bytes) return GR_OK;
-  if (c->ws2) { HIPCHK(c, hipStreamSynchronize(c->side_stream)); HIPCHK(c, hipFree(c->ws2)); c->ws2 = nullptr; c->ws2_bytes = 0; }
-  bytes = (bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-  HIPCHK(c, hipMalloc(&c->ws2, bytes));
-  c->ws2_bytes = bytes;
-  return GR_OK;
-}
+static int ensure_ws2(gr_ctx* c, size_t bytes) { return bytes <= c->ws2_bytes ? GR_OK : grow_dev(c, &c->ws2, c->ws2_bytes, past_next_mib(bytes), c->side_stream); }
 
 // The head kernel's sticky fault word (elem.hip head_grid_barrier).  Read - one 4-byte copy, only when a head kernel has run since the last look - by every
 // call that synchronises the stream anyway: gr_train_r_step with a loss_out, gr_synchronize, gr_net_get_params / gr_net_get_grads.  Set means: a grid
@@ -422,7 +422,7 @@ enum { ST_CONV = 1, ST_LINEAR = 2, ST_ELEM = 3 };
 struct MaskSlot {
   int layer = -1, kind = MASK_NONE; float p = 0; int flags = 0;
   int C = 0, H = 0, W = 0;           // tensor the noise is drawn for (per sample)
-  uint32_t* bits = nullptr; size_t words_cap = 0;
+  uint32_t* bits = nullptr; size_t bits_cap = 0;     // (capacity in bytes)
   bool injected = false; int64_t n_last = 0;
 };
 
@@ -432,7 +432,7 @@ struct Stage {
   bool up = false, fullconv = false;
   int Cin = 0, Cout = 0, H = 0, W = 0;       // main-op output channels / spatial dims (ELEM: the input dims)
   int64_t w_off = -1, b_off = -1;
-  bool has_bn = false; int64_t g_off = -1, be_off = -1; int bn_idx = -1;
+  bool has_bn = false; int64_t g_off = -1, be_off = -1;
   int act = ACT_NONE; float slope = 0;
   int ksz = 3;                              // window of the main convolution: 3 (conv.hip kernels) or an odd K convk.hip covers (GR_CONVK)
   int64_t slope_off = -1;                   // nn.PReLU: offset of its one learnable slope in the flat vectors
@@ -440,13 +440,13 @@ struct Stage {
   bool has_post = false;
   int outC = 0, outH = 0, outW = 0;
   float *y = nullptr, *out = nullptr; uint8_t* pool_idx = nullptr;
-  float *wt_fwd = nullptr, *wt_bwd = nullptr; uint64_t wt_version = 0;
+  float *wt_fwd = nullptr, *wt_bwd = nullptr;
   void *ws_fwd = nullptr, *ws_bwd = nullptr; uint64_t ws_version = 0;     // bf16x6 / f16x3 split images
   void* ws_up = nullptr; uint64_t ws_up_version = 0;   // f16x3 image of the fused up-sampling kernel (four 2x2 convolutions)
   uint64_t amax_x_fwd = 0;                  // gr_net::amax_gen at which amax_x was last taken
   unsigned *amax_x = nullptr, *amax_dy = nullptr, *amax_w = nullptr;   // f16x3: slots (in gr_net::amax) for max|x_in|, max|dy|, max|w|
   unsigned *amax_y = nullptr, *amax_kb = nullptr, *amax_dz = nullptr;  // max|y| (raw main-op output), the backward bound factor K (BnBounds), max|dz|
-  void* x_p16 = nullptr; size_t x_p16_cap = 0;   // operand-ready copy of this stage's INPUT, written by the previous stage's pipeline kernel
+  void* x_p16 = nullptr;                          // operand-ready copy of this stage's INPUT, written by the previous stage's pipeline kernel
   uint64_t x_p16_gen = 0;                         // gr_net::amax_gen at which x_p16 (and the bound in amax_x) was written
   // evaluate() mode (round 4): a convolution EPILOGUE writes the next stage's x_p16, scaled by an a-priori weight-norm bound in amax_x
   // (launch_eval_bound); the true max|x| it measures while storing goes to amax_xt and feeds the bound of the stage after
@@ -482,7 +482,7 @@ struct gr_net {
   void* dy_p16 = nullptr;            // operand-ready copy of dy_buf for the data-gradient convolution
   float* dy_buf_b = nullptr; void* dy_p16_b = nullptr;   // second pair: stages alternate, so stage s - 1 can write its dy while stage s's weight gradient (side stream) still reads
   bool wg_pending[2] = {false, false};                   // a side-stream weight gradient may still be reading dy pair k
-  float* up_tmp[2] = {nullptr, nullptr}; size_t up_cap = 0;    // backward of a fused up-sampling stage: up-sampled input / data gradient at the up-sampled size
+  float* up_tmp[2] = {nullptr, nullptr}; size_t up_cap = 0;    // backward of a fused up-sampling stage: up-sampled input / data gradient at the up-sampled size (capacity in bytes, each)
   size_t max_y = 0, max_in = 0;      // per-sample element counts
   uint8_t* mask_stage = nullptr; size_t mask_stage_cap = 0;
   PrepJob* jobs_dev[3] = {nullptr, nullptr, nullptr}; int njobs[3] = {0, 0, 0};   // [0] fp32 k-major images, [1] bf16x6, [2] f16x3 split images
@@ -598,7 +598,7 @@ extern "C" int gr_net_create(gr_ctx* c, const gr_layer_desc* L, int nl, int in_c
         // follows it - dropout, pooling - is the next, element-wise stage), and behind a BatchNorm it opens a stage of its own
         if (d.kind == GR_PRELU && s.has_bn) break;
         phase = ph; s.has_post = true;
-        if (ph == 0) { s.has_bn = true; s.g_off = woff[i]; s.be_off = boff[i]; s.bn_idx = (int)n->bn_stage.size(); n->bn_stage.push_back((int)n->st.size()); }
+        if (ph == 0) { s.has_bn = true; s.g_off = woff[i]; s.be_off = boff[i]; n->bn_stage.push_back((int)n->st.size()); }
         else if (ph == 1) { s.act = d.kind; s.slope = d.p; if (d.kind == GR_PRELU) { s.slope_off = woff[i]; ++i; break; } }
         else if (ph == 3) { s.pool = true; h /= 2; w /= 2; }
         else {
@@ -750,25 +750,13 @@ static MaskSlot* find_mask(gr_net* n, int layer) { for (auto& m : n->masks) if (
 static int64_t mask_elems(const MaskSlot& m, int B) { return m.kind == MASK_ELEM ? (int64_t)B * vol3(m.C, m.H, m.W) : (int64_t)B * m.C; }
 extern "C" int64_t gr_net_mask_size(gr_net* n, int layer, int B) { if (!n) return -1; MaskSlot* m = find_mask(n, layer); return m ? mask_elems(*m, B) : -1; }
 
-static int ensure_mask_bits(gr_net* n, MaskSlot& m, int64_t elems) {
-  const size_t words = (size_t)((elems + 31) / 32) + 4;
-  if (words > m.words_cap) {
-    gr_ctx* c = n->ctx;
-    if (m.bits) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(m.bits)); m.bits = nullptr; }
-    HIPCHK(c, hipMalloc((void**)&m.bits, sizeof(uint32_t) * words));
-    m.words_cap = words;
-  }
-  return GR_OK;
-}
+static int ensure_mask_bits(gr_net* n, MaskSlot& m, int64_t elems) { return grow_dev(n->ctx, &m.bits, m.bits_cap, sizeof(uint32_t) * ((size_t)((elems + 31) / 32) + 4), n->ctx->stream); }
 extern "C" int gr_net_set_mask(gr_net* n, int layer, const uint8_t* keep, int64_t cnt) {
   if (!n || !keep || cnt <= 0) return GR_ERR_INVALID;
   gr_ctx* c = n->ctx; MaskSlot* m = find_mask(n, layer);
   if (!m) return fail(c, GR_ERR_INVALID, "layer %d is not a Dropout / SpatialDropout", layer);
-  if ((size_t)cnt > n->mask_stage_cap) {
-    if (n->mask_stage) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(n->mask_stage)); n->mask_stage = nullptr; }
-    HIPCHK(c, hipMalloc((void**)&n->mask_stage, (size_t)cnt)); n->mask_stage_cap = (size_t)cnt;
-  }
-  int r = ensure_mask_bits(n, *m, cnt); if (r) return r;
+  int r = grow_dev(c, &n->mask_stage, n->mask_stage_cap, (size_t)cnt, c->stream); if (r) return r;
+  r = ensure_mask_bits(n, *m, cnt); if (r) return r;
   HIPCHK(c, hipMemcpyAsync(n->mask_stage, keep, (size_t)cnt, hipMemcpyHostToDevice, c->stream));
   launch_pack_mask(n->mask_stage, m->bits, cnt, c->stream); LAUNCHCHK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -779,10 +767,7 @@ extern "C" int gr_net_get_mask(gr_net* n, int layer, uint8_t* keep, int64_t cnt)
   if (!n || !keep || cnt <= 0) return GR_ERR_INVALID;
   gr_ctx* c = n->ctx; MaskSlot* m = find_mask(n, layer);
   if (!m || !m->bits || cnt > m->n_last) return fail(c, GR_ERR_STATE, "no noise recorded for layer %d", layer);
-  if ((size_t)cnt > n->mask_stage_cap) {
-    if (n->mask_stage) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(n->mask_stage)); n->mask_stage = nullptr; }
-    HIPCHK(c, hipMalloc((void**)&n->mask_stage, (size_t)cnt)); n->mask_stage_cap = (size_t)cnt;
-  }
+  int r = grow_dev(c, &n->mask_stage, n->mask_stage_cap, (size_t)cnt, c->stream); if (r) return r;
   launch_unpack_mask(m->bits, n->mask_stage, cnt, c->stream); LAUNCHCHK(c);
   HIPCHK(c, hipMemcpyAsync(keep, n->mask_stage, (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -906,6 +891,19 @@ static PostArgs post_args(gr_net* n, Stage& s, int B) {
   return a;
 }
 
+// the pipeline backward's: g (wrt the stage output) -> dy (wrt the raw main-op output; an element-wise stage's is its input gradient)
+static PostBwdArgs post_bwd_args(gr_net* n, Stage& s, int B, const float* g, float* dy) {
+  PostBwdArgs pb{};
+  pb.f = post_args(n, s, B);
+  if (!s.has_post) pb.f.out = nullptr;
+  pb.gout = g; pb.dy = dy;
+  pb.partials = s.partials; pb.partials_b = s.partials_b; pb.coef = s.coef;
+  pb.ggamma = s.has_bn ? n->grads + s.g_off : nullptr; pb.gbeta = s.has_bn ? n->grads + s.be_off : nullptr;
+  pb.gbias = s.kind == ST_ELEM ? nullptr : n->grads + s.b_off;
+  pb.amax_dy = (n->ctx->conv_mode == 2 && (s.kind == ST_CONV || use_f16_gemm(n, s))) ? s.amax_dy : nullptr;
+  return pb;
+}
+
 // ------------------------------------------------------------------ f16x3 range guard
 // f16x3 scales each tensor by ONE power of two: an entry 2^k below the tensor's maximum keeps about 40 - k bits (fp16's exponent
 // range ends 2^-40 below the scaled maximum).  bf16x6 has fp32's exponent range and no such limit.  What a lost bit costs depends
@@ -934,13 +932,10 @@ static volatile unsigned* guard_alarm_host(gr_ctx* c) { return reinterpret_cast<
 static bool f16_consumer(gr_net* n, const Stage& s) { return use_bf16x6(n, s) || use_f16_gemm(n, s); }     // (context in f16x3 mode)
 static int guard_scan(gr_ctx* c, const float* t, int B, int C, long HW, long sB, long sC, int side) {
   if (C < 2) return GR_OK;
-  if ((size_t)C > c->guard_chmax_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->guard_chmax) (void)hipFree(c->guard_chmax);
-    c->guard_chmax = nullptr; c->guard_chmax_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->guard_chmax, sizeof(unsigned) * (size_t)C));
-    HIPCHK(c, hipMemsetAsync(c->guard_chmax, 0, sizeof(unsigned) * (size_t)C, c->stream));
-    c->guard_chmax_cap = (size_t)C;
+  const size_t cb = sizeof(unsigned) * (size_t)C;
+  if (cb > c->guard_chmax_cap) {      // (the scans leave the per-channel words zero: only a new buffer is cleared)
+    const int r = grow_dev(c, &c->guard_chmax, c->guard_chmax_cap, cb, c->stream); if (r) return r;
+    HIPCHK(c, hipMemsetAsync(c->guard_chmax, 0, cb, c->stream));
   }
   launch_channel_absmax(t, B, C, HW, sB, sC, c->guard_chmax, c->stream);
   launch_spread_verdict(c->guard_chmax, C, guard_alarm_dev(c), side, c->stream);
@@ -985,6 +980,17 @@ static int guard_verdict(gr_ctx* c, unsigned* alarm) {
   *alarm = *guard_alarm_host(c);
   return GR_OK;
 }
+// The verdict of gr_train_r_step's sampled scan, once it has landed (wait: for it; else only when it is there already): a hostile
+// spread trips the context's guard, and a tripped guard keeps the context on bf16x6.
+static int guard_take_pending(gr_ctx* c, bool wait) {
+  if (c->guard_pending && wait) HIPCHK(c, hipEventSynchronize(c->ev_guard));
+  if (c->guard_pending && (wait || hipEventQuery(c->ev_guard) == hipSuccess)) {
+    c->guard_pending = false;
+    if (guard_over_budget(*guard_alarm_host(c)) && !c->guard_tripped) { c->guard_tripped = true; c->guard_fallbacks++; }
+  }
+  if (c->guard_tripped && c->conv_mode == 2) c->conv_mode = 1;
+  return GR_OK;
+}
 static bool guard_applies(gr_net* n) {
   gr_ctx* c = n->ctx;
   if (c->conv_mode != 2 || !c->range_guard) return false;
@@ -1000,14 +1006,9 @@ extern "C" int gr_range_guard_scan_params(gr_net* n, int* tripped) {
   gr_ctx* c = n->ctx;
   // a sampled scan of gr_train_r_step may still be in flight on this context: its verdict lands in the same host word the
   // synchronous scan below overwrites, so it is consumed first (otherwise a hostile range of the OTHER nets would go unnoticed)
-  if (c->guard_pending) {
-    HIPCHK(c, hipEventSynchronize(c->ev_guard));
-    c->guard_pending = false;
-    if (guard_over_budget(*guard_alarm_host(c)) && !c->guard_tripped) { c->guard_tripped = true; c->guard_fallbacks++; }
-  }
-  if (c->guard_tripped && c->conv_mode == 2) c->conv_mode = 1;
+  int r = guard_take_pending(c, true); if (r) return r;
   if (guard_applies(n)) {
-    int r = guard_scan_params(n); if (r) return r;
+    r = guard_scan_params(n); if (r) return r;
     unsigned sides = 0;
     r = guard_verdict(c, &sides); if (r) return r;
     if (guard_over_budget(sides) && !c->guard_tripped) { c->guard_tripped = true; c->guard_fallbacks++; c->conv_mode = 1; }
@@ -1073,10 +1074,183 @@ static int forward_begin(gr_net* n, int B) {
   return GR_OK;
 }
 
-static int forward_stages(gr_net* n, const float* in_dev, int B) {
+// f16x3 scale of a stage's input by a pass of its own (the input did not come from a kernel that tracks it), unless this forward has taken it.
+// fwd: into the slot forward_begin has just zeroed, marking it current; backward (arithmetic mode switched since the forward): refilled, unmarked.
+static void input_absmax(gr_net* n, Stage& s, const float* x, int B, bool fwd) {
+  if (s.amax_x_fwd == n->amax_gen) return;
+  launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, n->ctx->stream, fwd);
+  if (fwd) s.amax_x_fwd = n->amax_gen;
+}
+// evaluate() mode: mean / invstd of the current running statistics
+static void bn_eval_ready(gr_net* n, Stage& s) { if (!s.eval_ready) launch_bn_eval_prepare(s.run_mean, s.run_var, s.mean, s.invstd, s.Cout, n->ctx->stream); s.eval_ready = true; }
+// evaluate() mode: BatchNorm is a per-channel affine map of running statistics, so BN + activation ride in the epilogue of the main op and
+// its raw output is never written.  Needs: no pool, no active dropout noise, no PReLU; a Linear also needs a GEMM without split-K.  Fills ep.
+static bool eval_epilogue(gr_net* n, Stage& s, int B, ConvEpilogue& ep) {
+  bool nb1 = false, nb2 = false;
+  if (n->training || !s.has_post || s.pool || s.act == ACT_PRELU || mask_ref(n, s.m1, nb1).kind != MASK_NONE || mask_ref(n, s.m2, nb2).kind != MASK_NONE) return false;
+  if (s.kind == ST_LINEAR && !(s.H == 1 && s.W == 1 && gemm_epilogue_possible(B, s.Cout, s.Cin))) return false;
+  if (s.has_bn) { bn_eval_ready(n, s); ep.mean = s.mean; ep.invstd = s.invstd; ep.gamma = n->params + s.g_off; ep.beta = n->params + s.be_off; }
+  ep.act = s.act; ep.slope = s.slope;
+  return true;
+}
+// Stage t can take its input operand-ready (P16, written by the stage before it) at batch B
+static bool p16_input_ok(gr_net* n, const Stage& t, int B) { return t.kind == ST_CONV && t.ksz == 3 && !t.up && !t.fullconv && t.x_p16 && use_bf16x6(n, t) && conv_p16_supported(B, t.Cin, t.Cout, t.H, t.W); }
+// Stage t's pipeline backward can write dy operand-ready too (for its data and weight gradients)
+static bool p16_dy_ok(gr_net* n, const Stage& t) { return t.kind == ST_CONV && t.ksz == 3 && !t.up && !t.fullconv && t.has_bn && n->dy_p16 && post_g8_supported(t.Cout, t.H, t.W, t.pool, true); }
+// Stage t's weight gradient can read both operands operand-ready at batch B: its input image and pass B's dy image (shapes and buffers;
+// whether THIS forward wrote them is the caller's x_p16_gen / kb_gen test).  The contract between the passes: the forward may drop the
+// fp32 copy of t's input (out_skipped) only when this holds, and the backward then takes this weight gradient.
+static bool p16_wgrad_ok(gr_net* n, const Stage& t, int B) { return p16_dy_ok(n, t) && t.x_p16 && t.stat_part && conv_wgrad_p16_supported(B, t.Cin, t.Cout, t.H, t.W); }
+// ---- forward steps.  nx: the next stage when it is an f16x3 consumer (its scale slot amax_x is amax_next), else null.
+// K x K convolution (the D network's 5x5 layer): raw output always written, statistics by the pipeline
+static int fwd_convk(gr_net* n, Stage& s, const float* x, int B) {
+  gr_ctx* c = n->ctx;
+  s.stat_tiles_last = 0;
+  if (convk_split(n, s)) {
+    input_absmax(n, s, x, B, true);
+    launch_conv5x5_split(x, s.ws_fwd, n->params + s.b_off, s.y, B, s.Cin, s.Cout, s.H, s.W, c->stream, s.amax_x, s.amax_w);
+    return GR_OK;
+  }
+  const int r = ensure_ws(c, convk_workspace_bytes(B, s.Cin, s.Cout, s.ksz)); if (r) return r;
+  launch_convk_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
+  return GR_OK;
+}
+// 3x3 convolution: few-input-channel VALU, bf16x6 / f16x3 split, operand-ready (P16) input, fused up-sampling, fp32.  post_p16 (out):
+// this stage's pipeline kernel is to write the next convolution's input operand-ready.
+static int fwd_conv3(gr_net* n, Stage& s, const float* x, int B, Stage* nx, unsigned* amax_next, bool f16, bool& post_p16) {
+  gr_ctx* c = n->ctx;
+  ConvEpilogue ep;
+  s.fused_epilogue = eval_epilogue(n, s, B, ep);      // (G on this path)
+  const ConvEpilogue* epp = s.fused_epilogue ? &ep : nullptr;
+  float* dst = s.fused_epilogue ? s.out : s.y;
+  // training-mode BatchNorm: the conv epilogue also leaves the per-channel (sum, sum of squares) of what it stores
+  const bool want_stats = n->training && s.has_bn && s.stat_part && !s.fused_epilogue;
+  int stat_tiles = 0;
+  double* const stat_part = want_stats ? s.stat_part : nullptr; int* const stat_tiles_out = want_stats ? &stat_tiles : nullptr;
+  const bool is_fewin = !s.fullconv && conv_fewin_applies(s.Cin, s.W, s.up);
+  const bool in_p16 = f16 && !s.up && s.x_p16 && s.x_p16_gen == n->amax_gen && use_bf16x6(n, s);      // this stage's input arrived operand-ready
+  // evaluate() mode, f16x3 (round 4: apply_r.lua:145-153's corpus pipeline): the next convolution's input leaves THIS stage operand-ready
+  // too - straight from the conv epilogue (`po`: BatchNorm + activation fused, scale = the weight-norm bound of launch_eval_bound) or, for
+  // a stage with a pipeline kernel (pooling), from that kernel (`post_p16`: scale bounded from max|y|, which the conv epilogue measures).
+  // Pure functions of the stage's input and parameters: the host-tensor mirror (gr_net_forward_host) computes the same bits.
+  const bool nx_p16 = g_eval_p16 && f16 && !n->training && nx && p16_input_ok(n, *nx, B) && !s.up && !s.fullconv && s.wl1;
+  const bool po = nx_p16 && s.fused_epilogue &&
+                  (is_fewin ? conv_fewin_p16_out_supported(s.Cout, s.H, s.W) : (in_p16 && conv_p16_out_supported(s.Cout)));
+  post_p16 = nx_p16 && !s.fused_epilogue && s.has_post && s.act != ACT_PRELU && post_g8_supported(s.Cout, s.H, s.W, s.pool) && (is_fewin || use_bf16x6(n, s));
+  // f16x3 training: max|y| of the raw output rides along (slot amax_y): with the batch statistics it bounds max|pipeline
+  // output| and max|dy| BEFORE the kernels that write those tensors run, so they can write them operand-ready (P16)
+  const bool track_y = (f16 && want_stats) || post_p16;
+  const bool last_writer = s.fused_epilogue || !s.has_post;
+  unsigned* conv_amax_out = last_writer ? amax_next : (track_y ? s.amax_y : nullptr);
+  P16Out p16o;
+  if (po) {
+    if (s.wl1_version != n->params_version) { launch_conv_weight_l1(n->params + s.w_off, s.Cout, s.Cin * 9, s.wl1, c->stream); s.wl1_version = n->params_version; }
+    const unsigned* mslot = s.amax_x;                       // the true max|x| of this stage's input ...
+    if (in_p16 && !is_fewin) mslot = s.x_true ? s.x_true : s.amax_x;                                  // ... tracked beside the bound its image is scaled by
+    else input_absmax(n, s, x, B, true);
+    launch_eval_bound(s.wl1, n->params + s.b_off, &ep, s.Cout, 1.f, mslot, nx->amax_x, c->stream);
+    p16o.p16 = nx->x_p16; p16o.scale = nx->amax_x;
+    conv_amax_out = nx->amax_xt; dst = nullptr;
+  }
+  if (is_fewin) {
+    launch_conv3x3_fewin(x, n->params + s.w_off, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, conv_amax_out,
+                         stat_part, stat_tiles_out, po ? &p16o : nullptr);
+  } else if (use_bf16x6(n, s)) {
+    const int nterm = f16 ? 2 : 3;
+    if (nterm == 2 && in_p16) {
+      // the previous stage's pipeline kernel left this stage's input operand-ready, scaled by the bound in amax_x
+      launch_conv3x3_p16(s.x_p16, s.ws_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, s.amax_x, s.amax_w, conv_amax_out,
+                         stat_part, stat_tiles_out, po ? &p16o : nullptr);
+    } else {
+      // input not produced by a tracking kernel (the net's own input, a GEMM, a VALU conv): take its maximum now
+      if (nterm == 2) input_absmax(n, s, x, B, true);
+      if (nterm == 2 && s.up && s.ws_up)
+        launch_conv3x3_up2_f16x3(x, s.ws_up, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, s.amax_x, s.amax_w,
+                                 last_writer ? amax_next : nullptr);
+      else
+        launch_conv3x3_split(x, s.ws_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, s.up, c->stream, epp, nterm, s.amax_x, s.amax_w,
+                             (nterm == 2 && !s.up) ? conv_amax_out : (last_writer ? amax_next : nullptr), stat_part, stat_tiles_out);
+    }
+  }
+  else launch_conv3x3(x, s.wt_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, s.up, c->stream, s.fullconv ? nullptr : n->params + s.w_off, epp);
+  if (last_writer && nx && (is_fewin || use_bf16x6(n, s))) nx->amax_x_fwd = n->amax_gen;
+  if (po) { nx->x_p16_gen = n->amax_gen; nx->x_true = nx->amax_xt; s.out_skipped = true; }      // (no fp32 copy: gr_net_layer_output says so)
+  if (!s.fused_epilogue) s.stat_tiles_last = stat_tiles;
+  return GR_OK;
+}
+// nn.Linear: fused evaluate()-mode epilogue (G's first stage, models.lua:115-117: the raw output - 268 MB at cfg3 - is never written),
+// f16x3 GEMM for the large layers, fp32 MFMA GEMM for the rest
+static int fwd_linear(gr_net* n, Stage& s, const float* x, int B, Stage* nx, unsigned* amax_next) {
+  gr_ctx* c = n->ctx;
+  const int r = ensure_ws(c, gemm_workspace_bytes(B, s.Cout, s.Cin)); if (r) return r;
+  ConvEpilogue ep;
+  s.fused_epilogue = eval_epilogue(n, s, B, ep);
+  const bool f16g = use_f16_gemm(n, s);
+  if (f16g) input_absmax(n, s, x, B, true);
+  launch_gemm(x, s.Cin, 1, n->params + s.w_off, s.Cin, 1, s.fused_epilogue ? s.out : s.y, s.Cout, n->params + s.b_off, false, B, s.Cout, s.Cin, c->ws, c->stream,
+              s.fused_epilogue ? &ep : nullptr, s.fused_epilogue ? amax_next : nullptr, f16g ? s.amax_x : nullptr, f16g ? s.amax_w : nullptr);
+  if (s.fused_epilogue && nx) nx->amax_x_fwd = n->amax_gen;
+  return GR_OK;
+}
+// BatchNorm statistics (training: from the conv epilogue's tiles - synchronised across ranks or not - or by a pass of their own; evaluate():
+// from the running statistics) and the pipeline kernel, which can also write the next convolution's input operand-ready (p16_out)
+static int fwd_post(gr_net* n, Stage& s, const float* x, int B, Stage* nx, unsigned* amax_next, bool f16, bool post_p16) {
   gr_ctx* c = n->ctx;
   int r = GR_OK;
-  r = forward_begin(n, B); if (r) return r;
+  PostArgs pa = post_args(n, s, B); bool p16_out = false;
+  if (s.has_bn) {
+    if (n->training) s.eval_ready = false;          // mean / invstd become batch statistics, the running statistics move
+    if (n->training && s.kind == ST_CONV && s.stat_tiles_last > 0) {
+      // f16x3: the statistics kernel also folds the a-priori bounds (BnBounds) - into the NEXT convolution's scale slot when
+      // this stage's pipeline kernel can write that convolution's input operand-ready, and into this stage's backward factor
+      BnBounds bd{}; const BnBounds* bdp = nullptr;
+      if (f16 && !s.up && !s.fullconv) {
+        p16_out = nx && p16_input_ok(n, *nx, B) && post_g8_supported(s.Cout, s.H, s.W, s.pool);
+        bd.amax_y = s.amax_y; bd.gamma = pa.gamma; bd.beta = pa.beta; bd.act = s.act;
+        bd.mask_scale = fmaxf(1.f, pa.m1.scale) * fmaxf(1.f, pa.m2.scale);
+        bd.bound_out = p16_out ? nx->amax_x : nullptr; bd.kb_out = s.amax_kb;
+        bdp = &bd; s.kb_gen = n->amax_gen;
+      }
+      StatSync ss; const StatSync* sync = stat_sync(c, ss, s.Cout, (double)B * s.H * s.W);
+      if (c->coll_rc) { r = c->coll_rc; c->coll_rc = 0; return r; }
+      if (sync) {     // synchronised BatchNorm: the ranks' per-channel (sum, sum of squares) are added before the statistics are formed
+        launch_pair_sums(s.stat_part, s.stat_tiles_last, s.stat_tiles_last, s.Cout, sync->buf, c->stream);
+        r = small_allreduce(c, sync->buf, 2L * s.Cout, 1); if (r) return r;
+        launch_bn_stats_from_tiles(sync->buf, 1, s.Cout, sync->n_global, s.mean, s.invstd, s.run_mean, s.run_var, c->stream, bdp);
+      } else
+      launch_bn_stats_from_tiles(s.stat_part, s.stat_tiles_last, s.Cout, (double)B * s.H * s.W, s.mean, s.invstd, s.run_mean, s.run_var, c->stream, bdp);
+    }
+    else if (n->training) {
+      StatSync ss;
+      launch_bn_stats(s.kind == ST_ELEM ? x : s.y, B, s.Cout, s.H * s.W, s.partials, s.mean, s.invstd, s.run_mean, s.run_var, 1, c->stream, stat_sync(c, ss, s.Cout, (double)B * s.H * s.W));
+      if (c->coll_rc) { r = c->coll_rc; c->coll_rc = 0; return r; }
+    }
+    else bn_eval_ready(n, s);
+  }
+  if (post_p16) {
+    // evaluate() mode: bound of max|pipeline output| from max|y| (the conv epilogue's) and the running statistics, as the statistics
+    // kernel folds it in training mode
+    ConvEpilogue e2;
+    if (s.has_bn) { e2.mean = s.mean; e2.invstd = s.invstd; e2.gamma = pa.gamma; e2.beta = pa.beta; }
+    e2.act = s.act; e2.slope = s.slope;
+    launch_eval_bound(nullptr, nullptr, &e2, s.Cout, fmaxf(1.f, pa.m1.scale) * fmaxf(1.f, pa.m2.scale), s.amax_y, nx->amax_x, c->stream);
+    p16_out = true; nx->x_true = nx->amax_x;
+  }
+  pa.amax_out = p16_out ? nullptr : amax_next;      // operand-ready: the slot already holds the bound and must not move
+  pa.p16 = p16_out ? nx->x_p16 : nullptr; pa.p16_scale = p16_out ? nx->amax_x : nullptr;
+  // The fp32 copy of the stage output has one more reader than the next convolution's forward: that convolution's weight
+  // gradient.  When it will take the operand-ready image too (every condition is fixed by the shapes and this forward), the
+  // fp32 tensor is not written at all: the pipeline kernel writes 4 bytes per element, as it did before it wrote two formats.
+  s.out_skipped = (!n->keep_fp32 && p16_out && p16_wgrad_ok(n, *nx, B)) || post_p16;      // evaluate(): nothing else reads the fp32 tensor
+  if (s.out_skipped) pa.out = nullptr;
+  launch_post_forward(pa, c->stream);
+  if (p16_out) nx->x_p16_gen = n->amax_gen;
+  if (nx) nx->amax_x_fwd = n->amax_gen;
+  return GR_OK;
+}
+static int forward_stages(gr_net* n, const float* in_dev, int B) {
+  gr_ctx* c = n->ctx;
+  int r = forward_begin(n, B); if (r) return r;
   n->last_fwd_training = n->training;
   const float* x = in_dev;
   const bool f16 = c->conv_mode == 2;
@@ -1086,120 +1260,14 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
     // f16x3: the kernel that writes this stage's output also tracks its max|.| for the convolution that consumes it
     Stage* nx = (f16 && si + 1 < nst && (use_bf16x6(n, n->st[si + 1]) || use_f16_gemm(n, n->st[si + 1]))) ? &n->st[si + 1] : nullptr;
     unsigned* amax_next = nx ? nx->amax_x : nullptr;
-    s.x_in = x;
-    s.fused_epilogue = false; s.out_skipped = false;
+    s.x_in = x; s.fused_epilogue = false; s.out_skipped = false;
     bool post_p16 = false;
-    if (s.kind == ST_CONV && s.ksz != 3) {
-      // K x K convolution (the D network's 5x5 layer): fp32 direct kernel, raw output always written, statistics by the pipeline
-      if (convk_split(n, s)) {
-        if (s.amax_x_fwd != n->amax_gen) { launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream, true); s.amax_x_fwd = n->amax_gen; }
-        launch_conv5x5_split(x, s.ws_fwd, n->params + s.b_off, s.y, B, s.Cin, s.Cout, s.H, s.W, c->stream, s.amax_x, s.amax_w);
-      } else {
-      r = ensure_ws(c, convk_workspace_bytes(B, s.Cin, s.Cout, s.ksz)); if (r) return r;
-      launch_convk_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
-      }
-      s.stat_tiles_last = 0;
-    } else if (s.kind == ST_CONV) {
-      // evaluate() mode: BatchNorm is a per-channel affine map of running statistics, so BN + activation ride in the conv
-      // epilogue and the raw conv output is never written (G on this path).  Needs: no pool, no active dropout noise.
-      ConvEpilogue ep; const ConvEpilogue* epp = nullptr; float* dst = s.y;
-      bool nb1 = false, nb2 = false;
-      const MaskRef r1 = mask_ref(n, s.m1, nb1), r2 = mask_ref(n, s.m2, nb2);
-      if (!n->training && s.has_post && !s.pool && r1.kind == MASK_NONE && r2.kind == MASK_NONE && s.act != ACT_PRELU) {
-        if (s.has_bn) {
-          if (!s.eval_ready) { launch_bn_eval_prepare(s.run_mean, s.run_var, s.mean, s.invstd, s.Cout, c->stream); s.eval_ready = true; }
-          ep.mean = s.mean; ep.invstd = s.invstd; ep.gamma = n->params + s.g_off; ep.beta = n->params + s.be_off;
-        }
-        ep.act = s.act; ep.slope = s.slope; epp = &ep; dst = s.out; s.fused_epilogue = true;
-      }
-      // training-mode BatchNorm: the conv epilogue also leaves the per-channel (sum, sum of squares) of what it stores
-      const bool want_stats = n->training && s.has_bn && s.stat_part && !s.fused_epilogue;
-      int stat_tiles = 0;
-      const bool is_fewin = !s.fullconv && conv_fewin_applies(s.Cin, s.W, s.up);
-      const bool in_p16 = f16 && !s.up && s.x_p16 && s.x_p16_gen == n->amax_gen && use_bf16x6(n, s);      // this stage's input arrived operand-ready
-      // evaluate() mode, f16x3 (round 4: apply_r.lua:145-153's corpus pipeline): the next convolution's input leaves THIS stage operand-ready
-      // too - straight from the conv epilogue (`po`: BatchNorm + activation fused, scale = the weight-norm bound of launch_eval_bound) or, for
-      // a stage with a pipeline kernel (pooling), from that kernel (`post_p16`: scale bounded from max|y|, which the conv epilogue measures).
-      // Pure functions of the stage's input and parameters: the host-tensor mirror (gr_net_forward_host) computes the same bits.
-      const bool nx_p16 = g_eval_p16 && f16 && !n->training && nx && nx->kind == ST_CONV && nx->ksz == 3 && !nx->up && !nx->fullconv && nx->x_p16 &&
-                          use_bf16x6(n, *nx) && conv_p16_supported(B, nx->Cin, nx->Cout, nx->H, nx->W) && !s.up && !s.fullconv && s.wl1;
-      const bool po = nx_p16 && s.fused_epilogue &&
-                      (is_fewin ? conv_fewin_p16_out_supported(s.Cout, s.H, s.W) : (in_p16 && conv_p16_out_supported(s.Cout)));
-      post_p16 = nx_p16 && !s.fused_epilogue && s.has_post && s.act != ACT_PRELU && post_g8_supported(s.Cout, s.H, s.W, s.pool) && (is_fewin || use_bf16x6(n, s));
-      // f16x3 training: max|y| of the raw output rides along (slot amax_y): with the batch statistics it bounds max|pipeline
-      // output| and max|dy| BEFORE the kernels that write those tensors run, so they can write them operand-ready (P16)
-      const bool track_y = (f16 && want_stats) || post_p16;
-      const bool last_writer = s.fused_epilogue || !s.has_post;
-      unsigned* conv_amax_out = last_writer ? amax_next : (track_y ? s.amax_y : nullptr);
-      P16Out p16o;
-      if (po) {
-        if (s.wl1_version != n->params_version) { launch_conv_weight_l1(n->params + s.w_off, s.Cout, s.Cin * 9, s.wl1, c->stream); s.wl1_version = n->params_version; }
-        const unsigned* mslot = s.amax_x;                       // the true max|x| of this stage's input ...
-        if (in_p16 && !is_fewin) mslot = s.x_true ? s.x_true : s.amax_x;                                  // ... tracked beside the bound its image is scaled by
-        else if (s.amax_x_fwd != n->amax_gen) { launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream, true); s.amax_x_fwd = n->amax_gen; }
-        launch_eval_bound(s.wl1, n->params + s.b_off, &ep, s.Cout, 1.f, mslot, nx->amax_x, c->stream);
-        p16o.p16 = nx->x_p16; p16o.scale = nx->amax_x;
-        conv_amax_out = nx->amax_xt; dst = nullptr;
-      }
-      if (is_fewin) {
-        launch_conv3x3_fewin(x, n->params + s.w_off, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, conv_amax_out,
-                             want_stats ? s.stat_part : nullptr, want_stats ? &stat_tiles : nullptr, po ? &p16o : nullptr);
-        if (last_writer && nx) nx->amax_x_fwd = n->amax_gen;
-      } else if (use_bf16x6(n, s)) {
-        const int nterm = c->conv_mode == 2 ? 2 : 3;
-        if (nterm == 2 && in_p16) {
-          // the previous stage's pipeline kernel left this stage's input operand-ready, scaled by the bound in amax_x
-          launch_conv3x3_p16(s.x_p16, s.ws_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, s.amax_x, s.amax_w, conv_amax_out,
-                             want_stats ? s.stat_part : nullptr, want_stats ? &stat_tiles : nullptr, po ? &p16o : nullptr);
-        } else {
-          // input not produced by a tracking kernel (the net's own input, a GEMM, a VALU conv): take its maximum now
-          if (nterm == 2 && s.amax_x_fwd != n->amax_gen) { launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream, true); s.amax_x_fwd = n->amax_gen; }
-          if (nterm == 2 && s.up && s.ws_up)
-            launch_conv3x3_up2_f16x3(x, s.ws_up, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, c->stream, epp, s.amax_x, s.amax_w,
-                                     last_writer ? amax_next : nullptr);
-          else
-            launch_conv3x3_split(x, s.ws_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, s.up, c->stream, epp, nterm, s.amax_x, s.amax_w,
-                                 (nterm == 2 && !s.up) ? conv_amax_out : (last_writer ? amax_next : nullptr),
-                                 want_stats ? s.stat_part : nullptr, want_stats ? &stat_tiles : nullptr);
-        }
-        if (last_writer && nx) nx->amax_x_fwd = n->amax_gen;
-      }
-      else launch_conv3x3(x, s.wt_fwd, n->params + s.b_off, dst, B, s.Cin, s.Cout, s.H, s.W, s.up, c->stream, s.fullconv ? nullptr : n->params + s.w_off, epp);
-      if (po) { nx->x_p16_gen = n->amax_gen; nx->x_true = nx->amax_xt; s.out_skipped = true; }      // (no fp32 copy: gr_net_layer_output says so)
-      if (s.fused_epilogue) { LAUNCHCHK(c); x = s.out; continue; }
-      s.stat_tiles_last = stat_tiles;
-    } else if (s.kind == ST_LINEAR) {
-      const size_t wsb = gemm_workspace_bytes(B, s.Cout, s.Cin);
-      r = ensure_ws(c, wsb); if (r) return r;
-      // evaluate() mode: per-feature BatchNorm + activation ride in the GEMM epilogue (G's first stage, models.lua:115-117:
-      // the raw Linear output - 268 MB at cfg3 - is never written)
-      bool nb1 = false, nb2 = false;
-      const MaskRef r1 = mask_ref(n, s.m1, nb1), r2 = mask_ref(n, s.m2, nb2);
-      if (!n->training && s.has_post && !s.pool && r1.kind == MASK_NONE && r2.kind == MASK_NONE && s.H == 1 && s.W == 1 && s.act != ACT_PRELU &&
-          gemm_epilogue_possible(B, s.Cout, s.Cin)) {
-        ConvEpilogue ep;
-        if (s.has_bn) {
-          if (!s.eval_ready) { launch_bn_eval_prepare(s.run_mean, s.run_var, s.mean, s.invstd, s.Cout, c->stream); s.eval_ready = true; }
-          ep.mean = s.mean; ep.invstd = s.invstd; ep.gamma = n->params + s.g_off; ep.beta = n->params + s.be_off;
-        }
-        ep.act = s.act; ep.slope = s.slope;
-        const bool f16g = use_f16_gemm(n, s);
-        if (f16g && s.amax_x_fwd != n->amax_gen) { launch_absmax(x, (long)B * s.Cin, s.amax_x, c->stream, true); s.amax_x_fwd = n->amax_gen; }
-        launch_gemm(x, s.Cin, 1, n->params + s.w_off, s.Cin, 1, s.out, s.Cout, n->params + s.b_off, false, B, s.Cout, s.Cin, c->ws, c->stream, &ep, amax_next,
-                    f16g ? s.amax_x : nullptr, f16g ? s.amax_w : nullptr);
-        if (nx) nx->amax_x_fwd = n->amax_gen;
-        s.fused_epilogue = true;
-        LAUNCHCHK(c);
-        x = s.out; continue;
-      }
-      if (use_f16_gemm(n, s)) {
-        if (s.amax_x_fwd != n->amax_gen) { launch_absmax(x, (long)B * s.Cin, s.amax_x, c->stream, true); s.amax_x_fwd = n->amax_gen; }
-        launch_gemm(x, s.Cin, 1, n->params + s.w_off, s.Cin, 1, s.y, s.Cout, n->params + s.b_off, false, B, s.Cout, s.Cin, c->ws, c->stream,
-                    nullptr, nullptr, s.amax_x, s.amax_w);
-      } else
-      launch_gemm(x, s.Cin, 1, n->params + s.w_off, s.Cin, 1, s.y, s.Cout, n->params + s.b_off, false, B, s.Cout, s.Cin, c->ws, c->stream);
-    }
+    if (s.kind == ST_CONV && s.ksz != 3) r = fwd_convk(n, s, x, B);
+    else if (s.kind == ST_CONV) r = fwd_conv3(n, s, x, B, nx, amax_next, f16, post_p16);
+    else if (s.kind == ST_LINEAR) r = fwd_linear(n, s, x, B, nx, amax_next);
+    if (r) return r;
     LAUNCHCHK(c);
+    if (s.fused_epilogue) { x = s.out; continue; }
     if (n->head_fused && si + 2 == nst) {      // fc1's raw output is complete: the head kernel (gr_train_r_step) takes it from here, through fc2, the criterion and back
       s.eval_ready = false;
       Stage& s2 = n->st[si + 1];
@@ -1207,60 +1275,7 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
       break;
     }
     if (!s.has_post) { s.out = s.y; x = s.out; continue; }
-    const float* yv = s.kind == ST_ELEM ? x : s.y;
-    PostArgs pa = post_args(n, s, B);
-    bool p16_out = false;
-    if (s.has_bn) {
-      if (n->training) s.eval_ready = false;          // mean / invstd become batch statistics, the running statistics move
-      if (n->training && s.kind == ST_CONV && s.stat_tiles_last > 0) {
-        // f16x3: the statistics kernel also folds the a-priori bounds (BnBounds) - into the NEXT convolution's scale slot when
-        // this stage's pipeline kernel can write that convolution's input operand-ready, and into this stage's backward factor
-        BnBounds bd{}; const BnBounds* bdp = nullptr;
-        if (f16 && !s.up && !s.fullconv) {
-          p16_out = nx && nx->kind == ST_CONV && nx->x_p16 && !nx->up && !nx->fullconv && use_bf16x6(n, *nx) &&
-                    post_g8_supported(s.Cout, s.H, s.W, s.pool) && conv_p16_supported(B, nx->Cin, nx->Cout, nx->H, nx->W);
-          bd.amax_y = s.amax_y; bd.gamma = pa.gamma; bd.beta = pa.beta; bd.act = s.act;
-          bd.mask_scale = fmaxf(1.f, pa.m1.scale) * fmaxf(1.f, pa.m2.scale);
-          bd.bound_out = p16_out ? nx->amax_x : nullptr; bd.kb_out = s.amax_kb;
-          bdp = &bd; s.kb_gen = n->amax_gen;
-        }
-        StatSync ss; const StatSync* sync = stat_sync(c, ss, s.Cout, (double)B * s.H * s.W);
-        if (c->coll_rc) { r = c->coll_rc; c->coll_rc = 0; return r; }
-        if (sync) {     // synchronised BatchNorm: the ranks' per-channel (sum, sum of squares) are added before the statistics are formed
-          launch_pair_sums(s.stat_part, s.stat_tiles_last, s.stat_tiles_last, s.Cout, sync->buf, c->stream);
-          r = small_allreduce(c, sync->buf, 2L * s.Cout, 1); if (r) return r;
-          launch_bn_stats_from_tiles(sync->buf, 1, s.Cout, sync->n_global, s.mean, s.invstd, s.run_mean, s.run_var, c->stream, bdp);
-        } else
-        launch_bn_stats_from_tiles(s.stat_part, s.stat_tiles_last, s.Cout, (double)B * s.H * s.W, s.mean, s.invstd, s.run_mean, s.run_var, c->stream, bdp);
-      }
-      else if (n->training) {
-        StatSync ss;
-        launch_bn_stats(yv, B, s.Cout, s.H * s.W, s.partials, s.mean, s.invstd, s.run_mean, s.run_var, 1, c->stream, stat_sync(c, ss, s.Cout, (double)B * s.H * s.W));
-        if (c->coll_rc) { r = c->coll_rc; c->coll_rc = 0; return r; }
-      }
-      else if (!s.eval_ready) { launch_bn_eval_prepare(s.run_mean, s.run_var, s.mean, s.invstd, s.Cout, c->stream); s.eval_ready = true; }
-    }
-    if (post_p16) {
-      // evaluate() mode: bound of max|pipeline output| from max|y| (the conv epilogue's) and the running statistics, as the statistics
-      // kernel folds it in training mode
-      ConvEpilogue e2;
-      if (s.has_bn) { e2.mean = s.mean; e2.invstd = s.invstd; e2.gamma = pa.gamma; e2.beta = pa.beta; }
-      e2.act = s.act; e2.slope = s.slope;
-      launch_eval_bound(nullptr, nullptr, &e2, s.Cout, fmaxf(1.f, pa.m1.scale) * fmaxf(1.f, pa.m2.scale), s.amax_y, nx->amax_x, c->stream);
-      p16_out = true; nx->x_true = nx->amax_x;
-    }
-    pa.amax_out = p16_out ? nullptr : amax_next;      // operand-ready: the slot already holds the bound and must not move
-    pa.p16 = p16_out ? nx->x_p16 : nullptr; pa.p16_scale = p16_out ? nx->amax_x : nullptr;
-    // The fp32 copy of the stage output has one more reader than the next convolution's forward: that convolution's weight
-    // gradient.  When it will take the operand-ready image too (every condition is fixed by the shapes and this forward), the
-    // fp32 tensor is not written at all: the pipeline kernel writes 4 bytes per element, as it did before it wrote two formats.
-    s.out_skipped = !n->keep_fp32 && p16_out && nx->has_bn && n->dy_p16 && post_g8_supported(nx->Cout, nx->H, nx->W, nx->pool, true) &&
-                    conv_wgrad_p16_supported(B, nx->Cin, nx->Cout, nx->H, nx->W) && nx->stat_part;
-    if (post_p16) s.out_skipped = true;               // evaluate(): nothing else reads the fp32 tensor
-    if (s.out_skipped) pa.out = nullptr;
-    launch_post_forward(pa, c->stream);
-    if (p16_out) nx->x_p16_gen = n->amax_gen;
-    if (nx) nx->amax_x_fwd = n->amax_gen;
+    r = fwd_post(n, s, x, B, nx, amax_next, f16, post_p16); if (r) return r;
     LAUNCHCHK(c);
     x = s.out;
   }
@@ -1429,6 +1444,87 @@ static int reduce_bucket(gr_net* n, int64_t lo, int64_t hi) {
 }
 constexpr int64_t BUCKET_MIN_ELEMS = 1 << 20;
 
+// ---- backward steps: the main op's gradients from dy (dyb; dyp its operand-ready image).  gx: where the data gradient goes, null when none is wanted.
+// K x K convolution: the data gradient is the same convolution on the transposed + flipped weights (Cout -> Cin); max|dy| was folded into amax_dy
+// by the pipeline backward
+static int bwd_convk(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
+  gr_ctx* c = n->ctx;
+  const int r = ensure_ws(c, convk_workspace_bytes(B, s.Cin, s.Cout, s.ksz)); if (r) return r;
+  launch_convk_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
+  if (!gx) return GR_OK;
+  if (convk_split(n, s) && conv5x5_split_supported(s.Cout, s.Cin, s.H, s.W)) launch_conv5x5_split(dyb, s.ws_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, c->stream, s.amax_dy, s.amax_w);
+  else launch_convk_backward_data(dyb, n->params + s.w_off, gx, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
+  return GR_OK;
+}
+// 3x3 data gradient = the convolution Cout -> Cin on the backward weight images.  Plain stages: P16 when dy is operand-ready, else split in
+// either split mode.  Up-sampling / full-conv stages take split only above 4 input channels (why the rules differ is not recorded).
+static void dgrad3(gr_net* n, Stage& s, const float* dyb, const void* dyp, float* gx, int B, bool p16) {
+  gr_ctx* c = n->ctx;
+  if (p16) launch_conv3x3_p16(dyp, s.ws_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, c->stream, nullptr, s.amax_dy, s.amax_w, nullptr, nullptr, nullptr);
+  else if (c->conv_mode >= 1 && ((!s.up && !s.fullconv) || s.Cin > 4))
+    launch_conv3x3_split(dyb, s.ws_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, s.amax_dy, s.amax_w);
+  else launch_conv3x3(dyb, s.wt_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, false, c->stream);
+}
+// 3x3 convolution.  dk: the dy pair (a side-stream weight gradient marks it busy); dgrad_p16 / wgrad_p16: backward_impl's operand-ready choices.
+static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, const void* dyp, float* gx, int B, int dk, bool dgrad_p16, bool wgrad_p16) {
+  gr_ctx* c = n->ctx;
+  const bool f16 = c->conv_mode == 2;
+  int r = GR_OK;
+  if (s.up) {
+    // SpatialUpSamplingNearest(2) + SpatialConvolution backward (adversarial.lua:37-205 trains G through it): the weight
+    // gradient needs the up-sampled input, the data gradient is folded back by summing each 2x2 block
+    r = grow_dev(c, n->up_tmp, n->up_cap, sizeof(float) * (size_t)B * vol3(s.Cin, s.H, s.W), c->stream, 2); if (r) return r;
+    launch_upsample2(x, n->up_tmp[0], B, s.Cin, s.H, s.W, c->stream);
+    r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
+    if (f16 && conv_wgrad_is_split(2, s.Cin, s.W)) input_absmax(n, s, x, B, false);
+    launch_conv3x3_wgrad(n->up_tmp[0], dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.H, s.W, c->stream, c->conv_mode, s.amax_x, s.amax_dy);
+    if (gx) { dgrad3(n, s, dyb, dyp, n->up_tmp[1], B, false); launch_downsum2(n->up_tmp[1], gx, B, s.Cin, s.H / 2, s.W / 2, c->stream); }
+    return GR_OK;
+  }
+  if (s.fullconv) {
+    // nn.SpatialFullConvolution:accGradParameters: gradWeight[i][o] += x[i] (x) gradOutput[o] = the weight gradient of the convolution
+    // Cout -> Cin with the roles of input and gradOutput swapped; gradInput = that convolution's forward of gradOutput
+    r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cout, s.Cin, s.H, s.W, c->conv_mode)); if (r) return r;
+    if (f16 && conv_wgrad_is_split(2, s.Cout, s.W)) input_absmax(n, s, x, B, false);
+    launch_conv3x3_wgrad(dyb, x, n->grads + s.w_off, c->ws, B, s.Cout, s.Cin, s.H, s.W, c->stream, c->conv_mode, s.amax_dy, s.amax_x);
+    if (gx) dgrad3(n, s, dyb, dyp, gx, B, false);
+    return GR_OK;
+  }
+  r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
+  // max|dy| was folded into s.amax_dy by the pipeline-backward kernel that wrote dy_buf
+  // x's maximum is current when this stage's forward ran on the f16x3 kernel; otherwise (few-channel input, mode switched) take it now
+  if (f16 && conv_wgrad_is_split(2, s.Cin, s.W)) input_absmax(n, s, x, B, false);
+  // The weight gradient has no consumer before Adam / the gradient all-reduce: it runs on the side stream, beside this
+  // stage's data gradient and the memory-bound pipeline kernels of the stages after it (they leave the matrix pipe idle).
+  // Its own workspace; the dy pair it reads is not rewritten before ev_wgrad_done[dk] (waited for two stages on).
+  const bool side_want = c->side_wgrad < 0 ? (int64_t)B * vol3(s.Cout, s.H, s.W) >= ((int64_t)1 << 26) : c->side_wgrad != 0;
+  const bool side = side_want && c->side_stream != nullptr && gr::g_ktimer == nullptr;
+  hipStream_t ws_ = side ? c->side_stream : c->stream;
+  void* wsp_ = c->ws;
+  if (side) {
+    r = ensure_ws2(c, wgrad_p16 ? conv_wgrad_p16_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W) : conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
+    wsp_ = c->ws2;
+    HIPCHK(c, hipEventRecord(c->ev_dy_ready, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_dy_ready, 0));
+  } else if (wgrad_p16) { r = ensure_ws(c, conv_wgrad_p16_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W)); if (r) return r; wsp_ = c->ws; }
+  if (wgrad_p16) launch_conv3x3_wgrad_p16(s.x_p16, dyp, n->grads + s.w_off, wsp_, B, s.Cin, s.Cout, s.H, s.W, ws_, s.amax_x, s.amax_dy);
+  else launch_conv3x3_wgrad(x, dyb, n->grads + s.w_off, wsp_, B, s.Cin, s.Cout, s.H, s.W, ws_, c->conv_mode, s.amax_x, s.amax_dy);
+  if (side) { HIPCHK(c, hipEventRecord(c->ev_wgrad_done[dk], c->side_stream)); n->wg_pending[dk] = true; }
+  if (gx) dgrad3(n, s, dyb, dyp, gx, B, dgrad_p16);
+  return GR_OK;
+}
+// nn.Linear: gW[o][i] += sum_b dy[b][o] x[b][i], gx[b][i] = sum_o dy[b][o] W[o][i]
+static int bwd_linear(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
+  gr_ctx* c = n->ctx;
+  const int r = ensure_ws(c, std::max(gemm_workspace_bytes(s.Cout, s.Cin, B), gemm_workspace_bytes(B, s.Cin, s.Cout))); if (r) return r;
+  const bool f16g = use_f16_gemm(n, s);
+  if (f16g) input_absmax(n, s, x, B, false);   // (mode switched since the forward)
+  launch_gemm(dyb, 1, s.Cout, x, 1, s.Cin, n->grads + s.w_off, s.Cin, nullptr, true, s.Cout, s.Cin, B, c->ws, c->stream,
+              nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_x : nullptr);
+  if (gx) launch_gemm(dyb, s.Cout, 1, n->params + s.w_off, 1, s.Cin, gx, s.Cin, nullptr, false, B, s.Cin, s.Cout, c->ws, c->stream,
+                      nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_w : nullptr);
+  return GR_OK;
+}
 static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, int B, float* gin_dev, bool reduce = false) {
   gr_ctx* c = n->ctx;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1439,7 +1535,7 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
   reduce = reduce && have_peers(c);
   int64_t bucket_hi = n->n_params;            // everything in [stage first offset, bucket_hi) is final but not yet reduced
   BiasJobs bias_jobs{}; bias_jobs.n = 0;
-  { int r = prep_weights(n); if (r) return r; }   // no-op unless the arithmetic mode changed since the forward
+  int r = prep_weights(n); if (r) return r;   // no-op unless the arithmetic mode changed since the forward
   const bool f16 = c->conv_mode == 2;
   if (f16 && !n->dy_slots_zeroed)   // the dy slots (already zero when this is the first backward after a training-mode forward)
     HIPCHK(c, hipMemsetAsync(n->amax + AMAX_WORDS * AG_DY * n->st.size(), 0, sizeof(unsigned) * AMAX_WORDS * 2 * n->st.size(), c->stream));   // dy and dz groups
@@ -1460,22 +1556,13 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
     const int dk = si & 1;
     float* const dyb = dk ? n->dy_buf_b : n->dy_buf; void* const dyp = dk ? n->dy_p16_b : n->dy_p16;
     if (n->wg_pending[dk]) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_wgrad_done[dk], 0)); n->wg_pending[dk] = false; }
-    PostBwdArgs pb{};
-    pb.f = post_args(n, s, B);
-    if (!s.has_post) { pb.f.out = nullptr; }
-    pb.gout = g;
-    pb.dy = s.kind == ST_ELEM ? gin : dyb;
-    pb.partials = s.partials; pb.partials_b = s.partials_b; pb.coef = s.coef;
-    pb.ggamma = s.has_bn ? n->grads + s.g_off : nullptr; pb.gbeta = s.has_bn ? n->grads + s.be_off : nullptr;
-    pb.gbias = s.kind == ST_ELEM ? nullptr : n->grads + s.b_off;
-    pb.amax_dy = (f16 && (s.kind == ST_CONV || use_f16_gemm(n, s))) ? s.amax_dy : nullptr;
+    PostBwdArgs pb = post_bwd_args(n, s, B, g, s.kind == ST_ELEM ? gin : dyb);
     // operand-ready dy for the data-gradient convolution: needs the forward's bound factor of THIS forward (kb_gen)
-    const bool dy_ok = f16 && s.kind == ST_CONV && s.ksz == 3 && !s.up && !s.fullconv && s.has_bn && n->dy_p16 && s.kb_gen == n->amax_gen &&
-                       post_g8_supported(s.Cout, s.H, s.W, s.pool, true);
+    const bool dy_ok = f16 && s.kb_gen == n->amax_gen && p16_dy_ok(n, s);
     const bool dgrad_p16 = dy_ok && need_gin && conv_p16_supported(B, s.Cout, s.Cin, s.H, s.W);
     // weight gradient with both operands operand-ready: this stage's input image (written by the previous stage's forward
     // pipeline kernel in THIS forward) and pass B's dy image
-    const bool wgrad_p16 = dy_ok && s.x_p16 && s.x_p16_gen == n->amax_gen && conv_wgrad_p16_supported(B, s.Cin, s.Cout, s.H, s.W);
+    const bool wgrad_p16 = dy_ok && s.x_p16_gen == n->amax_gen && p16_wgrad_ok(n, s, B);
     const bool dy_p16 = dgrad_p16 || wgrad_p16;
     pb.dy_p16 = dy_p16 ? dyp : nullptr; pb.amax_dz = dy_p16 ? s.amax_dz : nullptr; pb.kb = s.amax_kb;
     if (s.kind == ST_CONV && si > 0 && n->st[si - 1].out_skipped && !wgrad_p16)
@@ -1484,7 +1571,7 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
     if (s.act == ACT_PRELU && !head_here) {
       // nn.PReLU accGradParameters: the stage ends at the PReLU, so g is its gradOutput and the raw main-op output (the stage
       // input for an element-wise stage) its input
-      int r = ensure_ws(c, prelu_grad_workspace_bytes()); if (r) return r;
+      r = ensure_ws(c, prelu_grad_workspace_bytes()); if (r) return r;
       launch_prelu_grad(g, s.kind == ST_ELEM ? x : s.y, (long)B * vol3(s.Cout, s.H, s.W), static_cast<double*>(c->ws), n->grads + s.slope_off, c->stream);
     }
     if (!head_here) {
@@ -1493,105 +1580,20 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
       if (c->coll_rc) { const int rc = c->coll_rc; c->coll_rc = 0; return rc; }
     }
     LAUNCHCHK(c);
-    if (s.kind == ST_CONV && s.ksz != 3) {
-      int r = ensure_ws(c, convk_workspace_bytes(B, s.Cin, s.Cout, s.ksz)); if (r) return r;
-      launch_convk_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
-      if (need_gin) {
-        // the data gradient = the same convolution on the transposed + flipped weights (Cout -> Cin); max|dy| was folded into amax_dy by the pipeline backward
-        if (convk_split(n, s) && conv5x5_split_supported(s.Cout, s.Cin, s.H, s.W)) launch_conv5x5_split(dyb, s.ws_bwd, nullptr, gin, B, s.Cout, s.Cin, s.H, s.W, c->stream, s.amax_dy, s.amax_w);
-        else launch_convk_backward_data(dyb, n->params + s.w_off, gin, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
-      }
-      LAUNCHCHK(c);
-    } else if (s.kind == ST_CONV) {
-      if (s.up) {
-        // SpatialUpSamplingNearest(2) + SpatialConvolution backward (adversarial.lua:37-205 trains G through it): the weight
-        // gradient needs the up-sampled input, the data gradient is folded back by summing each 2x2 block
-        const size_t need = (size_t)B * vol3(s.Cin, s.H, s.W);
-        if (need > n->up_cap) {
-          HIPCHK(c, hipStreamSynchronize(c->stream));
-          (void)hipFree(n->up_tmp[0]); (void)hipFree(n->up_tmp[1]); n->up_tmp[0] = n->up_tmp[1] = nullptr; n->up_cap = 0;
-          HIPCHK(c, hipMalloc((void**)&n->up_tmp[0], sizeof(float) * need)); HIPCHK(c, hipMalloc((void**)&n->up_tmp[1], sizeof(float) * need));
-          n->up_cap = need;
-        }
-        launch_upsample2(x, n->up_tmp[0], B, s.Cin, s.H, s.W, c->stream);
-        int r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
-        if (c->conv_mode == 2 && conv_wgrad_is_split(2, s.Cin, s.W) && s.amax_x_fwd != n->amax_gen) launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream);
-        launch_conv3x3_wgrad(n->up_tmp[0], dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.H, s.W, c->stream, c->conv_mode, s.amax_x, s.amax_dy);
-        if (need_gin) {
-          if (c->conv_mode >= 1 && s.Cin > 4) launch_conv3x3_split(dyb, s.ws_bwd, nullptr, n->up_tmp[1], B, s.Cout, s.Cin, s.H, s.W, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, s.amax_dy, s.amax_w);
-          else launch_conv3x3(dyb, s.wt_bwd, nullptr, n->up_tmp[1], B, s.Cout, s.Cin, s.H, s.W, false, c->stream);
-          launch_downsum2(n->up_tmp[1], gin, B, s.Cin, s.H / 2, s.W / 2, c->stream);
-        }
-        LAUNCHCHK(c);
-      } else if (s.fullconv) {
-        // nn.SpatialFullConvolution:accGradParameters: gradWeight[i][o] += x[i] (x) gradOutput[o] = the weight gradient of the convolution
-        // Cout -> Cin with the roles of input and gradOutput swapped; gradInput = that convolution's forward of gradOutput
-        int r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cout, s.Cin, s.H, s.W, c->conv_mode)); if (r) return r;
-        if (c->conv_mode == 2 && conv_wgrad_is_split(2, s.Cout, s.W) && s.amax_x_fwd != n->amax_gen) launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream);
-        launch_conv3x3_wgrad(dyb, x, n->grads + s.w_off, c->ws, B, s.Cout, s.Cin, s.H, s.W, c->stream, c->conv_mode, s.amax_dy, s.amax_x);
-        if (need_gin) {
-          if (c->conv_mode >= 1 && s.Cin > 4) launch_conv3x3_split(dyb, s.ws_bwd, nullptr, gin, B, s.Cout, s.Cin, s.H, s.W, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, s.amax_dy, s.amax_w);
-          else launch_conv3x3(dyb, s.wt_bwd, nullptr, gin, B, s.Cout, s.Cin, s.H, s.W, false, c->stream);
-        }
-        LAUNCHCHK(c);
-      } else {
-      int r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
-      if (c->conv_mode == 2) {
-        // max|dy| was folded into s.amax_dy by the pipeline-backward kernel that wrote dy_buf
-        // x's maximum is current when this stage's forward ran on the f16x3 kernel; otherwise (few-channel input, mode switched) take it now
-        if (conv_wgrad_is_split(2, s.Cin, s.W) && s.amax_x_fwd != n->amax_gen) launch_absmax(x, (long)B * vol3(s.inC, s.inH, s.inW), s.amax_x, c->stream);
-      }
-      // The weight gradient has no consumer before Adam / the gradient all-reduce: it runs on the side stream, beside this
-      // stage's data gradient and the memory-bound pipeline kernels of the stages after it (they leave the matrix pipe idle).
-      // Its own workspace; the dy pair it reads is not rewritten before ev_wgrad_done[dk] (waited for two stages on).
-      const bool side_want = c->side_wgrad < 0 ? (int64_t)B * vol3(s.Cout, s.H, s.W) >= ((int64_t)1 << 26) : c->side_wgrad != 0;
-      const bool side = side_want && c->side_stream != nullptr && gr::g_ktimer == nullptr;
-      hipStream_t ws_ = side ? c->side_stream : c->stream;
-      void* wsp_ = c->ws;
-      if (side) {
-        r = ensure_ws2(c, wgrad_p16 ? conv_wgrad_p16_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W) : conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
-        wsp_ = c->ws2;
-        HIPCHK(c, hipEventRecord(c->ev_dy_ready, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_dy_ready, 0));
-      }
-      if (wgrad_p16) {
-        if (!side) { r = ensure_ws(c, conv_wgrad_p16_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W)); if (r) return r; wsp_ = c->ws; }
-        launch_conv3x3_wgrad_p16(s.x_p16, dyp, n->grads + s.w_off, wsp_, B, s.Cin, s.Cout, s.H, s.W, ws_, s.amax_x, s.amax_dy);
-      } else
-      launch_conv3x3_wgrad(x, dyb, n->grads + s.w_off, wsp_, B, s.Cin, s.Cout, s.H, s.W, ws_, c->conv_mode, s.amax_x, s.amax_dy);
-      if (side) { HIPCHK(c, hipEventRecord(c->ev_wgrad_done[dk], c->side_stream)); n->wg_pending[dk] = true; }
-      if (need_gin) {
-        // backward-data = the same convolution on the transposed + flipped weights (Cout -> Cin)
-        if (dgrad_p16) launch_conv3x3_p16(dyp, s.ws_bwd, nullptr, gin, B, s.Cout, s.Cin, s.H, s.W, c->stream, nullptr, s.amax_dy, s.amax_w, nullptr, nullptr, nullptr);
-        else if (c->conv_mode >= 1) launch_conv3x3_split(dyb, s.ws_bwd, nullptr, gin, B, s.Cout, s.Cin, s.H, s.W, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, s.amax_dy, s.amax_w);
-        else launch_conv3x3(dyb, s.wt_bwd, nullptr, gin, B, s.Cout, s.Cin, s.H, s.W, false, c->stream);
-      }
-      LAUNCHCHK(c);
-      }
-    } else if (s.kind == ST_LINEAR) {
-      size_t wsb = gemm_workspace_bytes(s.Cout, s.Cin, B);
-      const size_t wsb2 = gemm_workspace_bytes(B, s.Cin, s.Cout);
-      if (wsb2 > wsb) wsb = wsb2;
-      int r = ensure_ws(c, wsb); if (r) return r;
-      const bool f16g = use_f16_gemm(n, s);
-      if (f16g && s.amax_x_fwd != n->amax_gen) launch_absmax(x, (long)B * s.Cin, s.amax_x, c->stream);   // (mode switched since the forward)
-      // gW[o][i] += sum_b dy[b][o] x[b][i]
-      launch_gemm(dyb, 1, s.Cout, x, 1, s.Cin, n->grads + s.w_off, s.Cin, nullptr, true, s.Cout, s.Cin, B, c->ws, c->stream,
-                  nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_x : nullptr);
-      // gx[b][i] = sum_o dy[b][o] W[o][i]
-      if (need_gin) launch_gemm(dyb, s.Cout, 1, n->params + s.w_off, 1, s.Cin, gin, s.Cin, nullptr, false, B, s.Cin, s.Cout, c->ws, c->stream,
-                                nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_w : nullptr);
-      LAUNCHCHK(c);
-    }
+    float* const gx = need_gin ? gin : nullptr;
+    if (s.kind == ST_CONV && s.ksz != 3) r = bwd_convk(n, s, x, dyb, gx, B);
+    else if (s.kind == ST_CONV) r = bwd_conv3(n, s, x, dyb, dyp, gx, B, dk, dgrad_p16, wgrad_p16);
+    else if (s.kind == ST_LINEAR) r = bwd_linear(n, s, x, dyb, gx, B);
+    if (r) return r;
+    LAUNCHCHK(c);
     g = gin;
     if (reduce) {
       // lowest parameter offset this stage owns (its BN parameters follow its main op in flat order)
-      int64_t lo = -1;
-      if (s.w_off >= 0) lo = s.w_off; else if (s.g_off >= 0) lo = s.g_off;
+      const int64_t lo = s.w_off >= 0 ? s.w_off : s.g_off;
       if (lo >= 0 && (bucket_hi - lo >= BUCKET_MIN_ELEMS || si == 0)) {
         for (int k2 = 0; k2 < 2; ++k2) if (n->wg_pending[k2]) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_wgrad_done[k2], 0)); n->wg_pending[k2] = false; }   // ... and final weight gradients
         launch_bias_grad_batch(bias_jobs, c->stream);             // the bucket must hold final bias gradients
-        int r = reduce_bucket(n, lo, bucket_hi); if (r) return r;
+        r = reduce_bucket(n, lo, bucket_hi); if (r) return r;
         bucket_hi = lo;
       }
     }
@@ -1600,7 +1602,7 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
   launch_bias_grad_batch(bias_jobs, c->stream);
   LAUNCHCHK(c);
   if (reduce) {
-    int r = reduce_bucket(n, 0, bucket_hi); if (r) return r;
+    r = reduce_bucket(n, 0, bucket_hi); if (r) return r;
     if (!c->xchg) {
       // Adam (compute stream) must see every reduced bucket
       HIPCHK(c, hipEventRecord(c->ev_done, c->comm_stream));
@@ -1847,11 +1849,7 @@ extern "C" int gr_train_r_step(gr_net* g, gr_net* rn, const float* noise_dev, in
   // hostile spread shows, the context stays on bf16x6 (gr_set_tuning "range_guard" 0 clears it).  Latency: under 2 periods.
   enum { GUARD_PERIOD = 64 };
   g->keep_fp32 = rn->keep_fp32 = false; g->last_fwd_fell_back = rn->last_fwd_fell_back = false;
-  if (c->guard_pending && hipEventQuery(c->ev_guard) == hipSuccess) {
-    c->guard_pending = false;
-    if (guard_over_budget(*guard_alarm_host(c)) && !c->guard_tripped) { c->guard_tripped = true; c->guard_fallbacks++; }
-  }
-  if (c->guard_tripped && c->conv_mode == 2) c->conv_mode = 1;
+  r = guard_take_pending(c, false); if (r) return r;
   if (c->conv_mode == 2 && c->range_guard && !c->guard_pending && t % GUARD_PERIOD == 1) {
     r = guard_scan_params(g); if (r) return r;
     r = guard_scan_params(rn); if (r) return r;
