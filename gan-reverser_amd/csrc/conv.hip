@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(ConvArgs a) {
 // M = Cout <= 4 would waste 7/8 of a 32-row MFMA block and the layer is HBM-bound anyway (reads 128 planes to emit 1-3), so
 // this is a VALU kernel: one thread = 4 consecutive output pixels x all CO channels; input channels stream through LDS in
 // chunks of 8 (register-prefetched float4 rows + scalar halo columns), weights come in through the scalar cache.
-// KS = 2 / 4: the tile is 16 / 8 rows and the KS groups of the workgroup each take 1/KS of every chunk's channels for the
+// KS = 4: the tile is 8 rows (16 / KS in general) and the KS groups of the workgroup each take 1/KS of every chunk's channels for the
 // same pixels, added through LDS (in group order) at the end - KS times the workgroups (a batch-256 layer on 32x32 planes
 // has one 32-row tile per CU: 4 waves per CU, every chunk's load latency exposed; cfg2: 57 -> 47.5 us with two groups, 38.8
 // with four, 3.5 TB/s).
@@ -591,27 +591,23 @@ void launch_conv3x3(const float* in, const float* wt, const float* bias, float* 
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.up = up ? 1 : 0;
   a.nchunks = L.cin_pad / CONV_CK; a.cout_pad = L.cout_pad;
   if (w_native && Cout <= 4 && !up && W % 4 == 0 && W >= 16) {
-    // small planes (too few 32-row tiles per image to fill the chip): four channel groups on 8-row tiles, else two on 16-row tiles
-    // (decided by the plane alone, not by the batch: a row must get the same bits whatever batch it travels in)
-    const bool ks2 = H % 16 == 0 && ((W + 31) / 32) * ((H + 31) / 32) < 4;
-    const bool ks4 = ks2 && H % 8 == 0;
+    // small planes (too few 32-row tiles per image to fill the chip) whose height is a multiple of 16: four channel groups on 8-row tiles
+    // (KS = 2 on 16-row tiles, once the alternative for such planes, is not launched); decided by the plane alone, not by the batch: a row
+    // must get the same bits whatever batch it travels in
+    const bool ks4 = H % 16 == 0 && ((W + 31) / 32) * ((H + 31) / 32) < 4;
     // planes whose width is a multiple of 64: one 64-wide x 16-row tile per workgroup (no halo columns fetched from a neighbour's lines)
-    const bool wide64 = !ks2 && W % 64 == 0;
-    a.tiles_x = wide64 ? W / 64 : (W + 31) / 32; a.tiles_y = wide64 ? (H + 15) / 16 : (ks4 ? H / 8 : (ks2 ? H / 16 : (H + 31) / 32)); a.n_otiles = 1;
+    const bool wide64 = !ks4 && W % 64 == 0;
+    a.tiles_x = wide64 ? W / 64 : (W + 31) / 32; a.tiles_y = wide64 ? (H + 15) / 16 : (ks4 ? H / 8 : (H + 31) / 32); a.n_otiles = 1;
     const int grid = B * a.tiles_x * a.tiles_y;
     const double px = (double)B * H * W;
-    const std::string fo_name = "conv3x3_fewout_kernel<" + std::to_string(Cout <= 3 ? Cout : 4) + ">";
+    // as rocprofv3 prints it: <CO, KS, TW>
+    const std::string fo_name = "conv3x3_fewout_kernel<" + std::to_string(Cout) + (ks4 ? ", 4, 32>" : (wide64 ? ", 1, 64>" : ", 1, 32>"));
     KtScope kt(fo_name.c_str(), 2.0 * px * Cout * Cin * 9.0, 4.0 * (px * Cin + px * Cout + 9.0 * Cin * Cout), s);
     if (ks4) switch (Cout) {
       case 1: hipLaunchKernelGGL((conv3x3_fewout_kernel<1, 4>), dim3(grid), dim3(256), 0, s, a, w_native); break;
       case 2: hipLaunchKernelGGL((conv3x3_fewout_kernel<2, 4>), dim3(grid), dim3(256), 0, s, a, w_native); break;
       case 3: hipLaunchKernelGGL((conv3x3_fewout_kernel<3, 4>), dim3(grid), dim3(256), 0, s, a, w_native); break;
       default: hipLaunchKernelGGL((conv3x3_fewout_kernel<4, 4>), dim3(grid), dim3(256), 0, s, a, w_native); break;
-    } else if (ks2) switch (Cout) {
-      case 1: hipLaunchKernelGGL((conv3x3_fewout_kernel<1, 2>), dim3(grid), dim3(256), 0, s, a, w_native); break;
-      case 2: hipLaunchKernelGGL((conv3x3_fewout_kernel<2, 2>), dim3(grid), dim3(256), 0, s, a, w_native); break;
-      case 3: hipLaunchKernelGGL((conv3x3_fewout_kernel<3, 2>), dim3(grid), dim3(256), 0, s, a, w_native); break;
-      default: hipLaunchKernelGGL((conv3x3_fewout_kernel<4, 2>), dim3(grid), dim3(256), 0, s, a, w_native); break;
     } else if (wide64) switch (Cout) {
       case 1: hipLaunchKernelGGL((conv3x3_fewout_kernel<1, 1, 64>), dim3(grid), dim3(256), 0, s, a, w_native); break;
       case 2: hipLaunchKernelGGL((conv3x3_fewout_kernel<2, 1, 64>), dim3(grid), dim3(256), 0, s, a, w_native); break;
@@ -3672,8 +3668,7 @@ static void launch_wgrad_split(const WgradArgs& a, int TW, int rps, int grid_, h
   if (rps > 0) {
     if (TW == 16) hipLaunchKernelGGL((conv3x3_wgrad_split_roll_kernel<16, NTERM>), dim3(grid_), dim3(256), 0, s, a, rps);
     else hipLaunchKernelGGL((conv3x3_wgrad_split_roll_kernel<32, NTERM>), dim3(grid_), dim3(256), 0, s, a, rps);
-  } else if (TW == 16) hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<16, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<32, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);
+  } else hipLaunchKernelGGL((conv3x3_wgrad_split_kernel<16, 2, NTERM>), dim3(grid_), dim3(256), 0, s, a);   // rps = 0 only on 16-wide tiles (below)
 }
 
 bool conv_wgrad_p16_supported(int B, int Cin, int Cout, int H, int W) {
@@ -3725,6 +3720,7 @@ void launch_conv3x3_wgrad(const float* x, const float* dy, float* gw, void* work
       const int grid_ = a.nsplit * a.n_ob * a.n_cb;
       const int TRr = 32 / TW;
       int rps = 0;                                                 // rows per segment of the rolling-window kernel (0: the per-tile kernel)
+      // rps = 0 exactly when H % TRr != 0: TRr = 2, i.e. 16-wide tiles (split tiles are 16 or 32 wide), the only per-tile kernel there is
       if (H % TRr == 0) {
         // longest run of rows (a divisor of H, multiple of TR) that still yields >= grid_ segments
         for (int cand = H; cand >= TRr; --cand)
@@ -3732,10 +3728,11 @@ void launch_conv3x3_wgrad(const float* x, const float* dy, float* gw, void* work
             const long nsegs = (long)B * (H / cand) * a.tiles_x;         // balanced: a multiple of the splits, or many per split
             if (nsegs >= a.nsplit && (nsegs % a.nsplit == 0 || nsegs >= 4L * a.nsplit || cand == TRr)) { rps = cand; break; }
           }
+        if (rps == 0) rps = TRr;                                   // (not taken: at cand = TRr, nsegs = tiles_total >= nsplit)
       }
       const std::string nt_ = mode == 2 ? "2>" : "3>";      // as rocprofv3 prints them: last template argument = number of split terms
       const std::string nm_ = rps > 0 ? std::string("conv3x3_wgrad_split_roll_kernel<") + (TW == 16 ? "16, " : "32, ") + nt_
-                                      : std::string("conv3x3_wgrad_split_kernel<") + (TW == 16 ? "16, 2, " : "32, 2, ") + nt_;
+                                      : std::string("conv3x3_wgrad_split_kernel<16, 2, ") + nt_;
       KtScope kt(nm_.c_str(), 2.0 * px_ * Cout * Cin * 9.0, 4.0 * (px_ * Cin + px_ * Cout + 9.0 * Cin * Cout), s);
       if (mode == 2) launch_wgrad_split<2>(a, TW, rps, grid_, s); else launch_wgrad_split<3>(a, TW, rps, grid_, s);
     }

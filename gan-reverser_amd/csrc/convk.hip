@@ -257,8 +257,7 @@ static void convk_direct(const float* in, const float* w, const float* bias, flo
     convk_weight_image_kernel<<<(unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024), 256, 0, s>>>(w, wt, Cin, Cout, K, bwd ? 1 : 0, CiP, CoP);
   }
   const int tiles_x = (W + KC_TILE - 1) / KC_TILE, tiles_y = (H + KC_TILE - 1) / KC_TILE;
-  KtScope kt(bwd ? "convk_direct_kernel(dgrad)" : "convk_direct_kernel", 2.0 * B * H * W * (double)Cin * Cout * K * K,
-             4.0 * B * H * W * (Cin + Cout), s);
+  const double flops = 2.0 * B * H * W * (double)Cin * Cout * K * K, bytes = 4.0 * B * H * W * (Cin + Cout);
   constexpr int COT = 16;
   // two images per workgroup (each weight load used twice) measured SLOWER at the D network's shape, 430 vs 364 us (84 instead
   // of 50 VGPRs, twice the LDS): the scalar cache is not what bounds the one-image kernel.
@@ -266,10 +265,15 @@ static void convk_direct(const float* in, const float* w, const float* bias, flo
   constexpr long SLICED_BELOW_WGS = 1024;
   if ((long)tiles_x * tiles_y * (CoP / COT) * B < SLICED_BELOW_WGS) {
     dim3 grid(tiles_x * tiles_y, CoP / COT, B);
+    static const std::string nm = "convk_direct_sliced_kernel<" + std::to_string(K) + ", " + std::to_string(COT) + ", " + std::to_string(KC_KS) + ">",
+                             nm_bwd = nm + "(dgrad)";   // as rocprofv3 prints it
+    KtScope kt(bwd ? nm_bwd.c_str() : nm.c_str(), flops, bytes, s);
     convk_direct_sliced_kernel<K, COT, KC_KS><<<grid, 256 * KC_KS, 0, s>>>(in, wt, bias, out, cin_eff, cout_eff, CoP, H, W, tiles_x);
     return;
   }
   dim3 grid(tiles_x * tiles_y, CoP / COT, B);
+  static const std::string nm = "convk_direct_kernel<" + std::to_string(K) + ", " + std::to_string(COT) + ", 1>", nm_bwd = nm + "(dgrad)";
+  KtScope kt(bwd ? nm_bwd.c_str() : nm.c_str(), flops, bytes, s);
   convk_direct_kernel<K, COT, 1><<<grid, 256, 0, s>>>(in, wt, bias, out, B, cin_eff, cout_eff, CoP, H, W, tiles_x);
 }
 
