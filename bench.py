@@ -3,14 +3,20 @@
    noise -> G forward (evaluate) -> R forward/backward (training) -> [RCCL all-reduce] -> L2+clamp+Adam
    (reference train_r.lua:138-170) at BASELINE.json configs[1]: 32x32 grayscale, noise=32, batch=256 per GPU.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--full]
   N > 1 without a torch.distributed.run environment: this process (which never touches a GPU) starts the N ranks itself
   (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>) and exits with their code.
   N > 1 under torch.distributed.run (RANK / WORLD_SIZE set): one rank per GPU, gradients over RCCL.
-Rank 0 prints ONE compact JSON line on stdout (< 4 KB; contract in the task statement) carrying `roofline`, `cpu_baseline`, `f32_row`, `cfg3` and
-`search_cfg5` summaries; the full result (per arithmetic mode tables, per-kernel tables, notes) goes to gpurun_out/bench_detail.json (--detail PATH).
+A plain run times the headline only: the headline workload in the headline arithmetic (W untimed steps, then K timed ones), and rank 0
+prints ONE compact JSON line on stdout with the contract's keys.
+--full adds everything else the benchmark measures or checks: the other arithmetic modes, the cfg3 rider, the per-kernel tables and
+roofline (with rocprofv3 traffic children and the bare MFMA loop), the cfg5 search and embedding pipeline, the GAN batch and the CPU
+baselines.  Its line also carries `roofline`, `cpu_baseline`, `f32_row`, `cfg3` and `search_cfg5` summaries (< 4 KB); the full result
+(per arithmetic mode tables, per-kernel tables, notes) goes to the --detail file.  The --no-* switches, --modes, --traffic and
+--embed-* only shape a --full run.
 --dump-outputs DIR writes what the last timed step of each timed mode computed as .npy files (same arguments = same inputs), so that two
-builds can be compared output for output.
+builds can be compared output for output.  It writes the files of a --full run in a plain run too: every mode and workload is stepped
+as --full steps it, and only the headline is reported.
 """
 import argparse
 import json
@@ -76,7 +82,7 @@ def measure_traffic(args, workload):
     if shutil.which("rocprofv3") is None:
         return None, "rocprofv3 not on PATH"
     out, base = {}, tempfile.mkdtemp(prefix="ganrev_pmc_")
-    child = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", "2", "--warmup", "1", "--conv-mode", args.conv_mode,
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--workload", workload, "--steps", "2", "--warmup", "1", "--conv-mode", args.conv_mode,
              "--modes", args.conv_mode, "--traffic", "off", "--no-cpu-baseline", "--no-search", "--no-gan", "--no-sustained", "--quiet-child"]
     env = dict(os.environ, TMPDIR="/tmp")
     try:
@@ -601,6 +607,13 @@ def dump_step_outputs(dirpath, prefix, ctx, gnet, rnet, B, dims, nd):
         raise SystemExit(f"bench.py: --dump-outputs wrote {_dump_bytes[0]} bytes (limit {DUMP_MAX_BYTES})")
 
 
+def every_mode(args):
+    """Whether this run steps every mode and workload: --full times and reports them all; --dump-outputs runs the same steps without
+    the reports, so that it writes the same files, with the same contents, as a --full run.  The sequence of steps matters: a mode's
+    dropout noise continues the Philox counter of the steps before it (gr_net_set_seed restarts it once, at the net's creation)."""
+    return args.full or bool(args.dump_outputs)
+
+
 def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, traffic_from, dist, torch):
     """One workload (cfg2 / cfg3) through the timed loop in every requested arithmetic mode.  Returns the line's fields for
     it (rank 0) or None."""
@@ -675,7 +688,7 @@ def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, tra
         per_step = [ctx.event_elapsed_ms(i, i + 1) for i in range(args.steps)]
         if args.dump_outputs and rank == 0:
             dump_step_outputs(args.dump_outputs, f"{wl_key}_{mode}", ctx, gnet, rnet, B, dims, nd)
-        loss = step(want_loss=True)
+        loss = step(want_loss=True) if every_mode(args) else None         # the loss the --full tables report costs one more step
         # the timed steps must have run the arithmetic the line names: a tripped range guard moves the context to bf16x6 (csrc/net.hip)
         # (reported, not fatal: the row is then labelled with what ran)
         if ctx.conv_mode() != mode or ctx.range_guard_stats()[1] != falls0:
@@ -683,6 +696,8 @@ def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, tra
             if rank == 0:
                 print(f"bench.py: the f16x3 range guard moved the context from {mode} to {ctx.conv_mode()} during the timed steps "
                       f"({ctx.range_guard_stats()[1] - falls0} fallbacks): the {mode} row of {wl_key} is labelled accordingly", file=sys.stderr)
+        if not every_mode(args):
+            return dt, per_step, loss, None
         # roofline leg: per-kernel HIP events (on the launch stream) over extra steps of the same workload.  Every rank runs
         # these steps (they contain the collective); only rank 0 instruments and reports.
         nprof = 3
@@ -695,13 +710,13 @@ def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, tra
         if rank == 0:
             kt = ctx.kernel_times()
             ctx.set_timing(0)
-            rep = kernel_report(kt, nprof, dims, nd, B, traffic if mode == args.conv_mode else None)
+            rep = kernel_report(kt, nprof, dims, nd, B, traffic if mode == args.conv_mode else None) if args.full else None
         return dt, per_step, loss, rep
 
     results = {m: timed(m) for m in modes}
     ctx.set_conv_mode(args.conv_mode)
     out = None
-    if rank == 0 and "f16x3" in results and not args.no_sustained:
+    if rank == 0 and args.full and "f16x3" in results and not args.no_sustained:
         # What the chip's clock under MFMA load leaves of the spec ceiling, on THIS device in THIS run: the bare f16x3 inner loop
         # (LDS reads + three fp16 MFMA products per accumulate, two waves per SIMD, random data; csrc/mfmaloop.hip) right after the
         # timed steps.  `peak` and `frac` stay priced at the guide's dense peak; the sustained figure is reported beside them.
@@ -713,28 +728,34 @@ def run_workload(args, wl_key, modes, ctx, rank, world, shared_gpu, traffic, tra
                                  note="fp32-accurate TFLOP/s of a bare LDS-read + f16x3 MFMA loop (no staging, no epilogue) on this device after a warm-up under load, "
                                       "same units as `peak`: the chip does not hold 2.4 GHz under MFMA load on random data (MI355X_MICROARCH.md, DVFS give-back); "
                                       "32x32x16 is the instruction the convolution kernels issue, 16x16x32 the shape the chip clocks higher on")
+
+    def moved(m):
+        return f"{DTYPE[tripped[m]]} (the f16x3 range guard moved the context from {m} to {tripped[m]} during the timed steps)"
     if rank == 0:
-        fl_img = step_flops_per_image(dims, nd)[0]
-        dt, per_step, loss, (roofline, kernels, extra) = results[args.conv_mode]
-        if roofline.get("traffic") is not None or traffic_from:
-            roofline["traffic_from"] = traffic_from
-        mode_rows = {}
-        for m, (mdt, mps, mloss, (mroof, _, mextra)) in results.items():
-            mode_rows[m] = dict(images_per_sec=round(GB * args.steps / mdt, 1), ms_per_step=round(mdt / args.steps * 1e3, 4), dtype=DTYPE[m],
-                                step_ms_events=percentiles(mps), last_loss=mloss,
-                                roofline={k: mroof[k] for k in ("kernel", "achieved", "peak", "unit", "frac", "frac_of_fp32_mfma_peak", "avg_launch_ms", "sustained") if k in mroof},
-                                r_convs=mextra["r_convs"], elementwise=mextra["elementwise"])
-            if m in tripped:
-                mode_rows[m]["dtype"] = f"{DTYPE[tripped[m]]} (the f16x3 range guard moved the context from {m} to {tripped[m]} during the timed steps)"
-                mode_rows[m]["range_guard_tripped"] = True
+        dt = results[args.conv_mode][0]
         out = dict(images_per_sec=round(GB * args.steps / dt, 1), ms_per_step=round(dt / args.steps * 1e3, 4),
-                   workload=wl["name"], global_batch=GB, per_gpu_batch=B,
-                   step_ms_events=percentiles(per_step),
-                   step_tflops=round(fl_img * GB * args.steps / dt / 1e12 / world, 2),
-                   step_frac_of_fp32_mfma_peak=round(fl_img * GB * args.steps / dt / 1e12 / world / PEAK_FP32_MFMA_TFLOPS, 4),
-                   last_loss=loss, roofline=roofline, **extra, modes=mode_rows, kernels=kernels, host_reduce=host_reduce)
+                   workload=wl["name"], global_batch=GB, per_gpu_batch=B)
+        if args.full:
+            fl_img = step_flops_per_image(dims, nd)[0]
+            _, per_step, loss, (roofline, kernels, extra) = results[args.conv_mode]
+            if roofline.get("traffic") is not None or traffic_from:
+                roofline["traffic_from"] = traffic_from
+            mode_rows = {}
+            for m, (mdt, mps, mloss, (mroof, _, mextra)) in results.items():
+                mode_rows[m] = dict(images_per_sec=round(GB * args.steps / mdt, 1), ms_per_step=round(mdt / args.steps * 1e3, 4), dtype=DTYPE[m],
+                                    step_ms_events=percentiles(mps), last_loss=mloss,
+                                    roofline={k: mroof[k] for k in ("kernel", "achieved", "peak", "unit", "frac", "frac_of_fp32_mfma_peak", "avg_launch_ms", "sustained") if k in mroof},
+                                    r_convs=mextra["r_convs"], elementwise=mextra["elementwise"])
+                if m in tripped:
+                    mode_rows[m]["dtype"] = moved(m)
+                    mode_rows[m]["range_guard_tripped"] = True
+            out.update(step_ms_events=percentiles(per_step),
+                       step_tflops=round(fl_img * GB * args.steps / dt / 1e12 / world, 2),
+                       step_frac_of_fp32_mfma_peak=round(fl_img * GB * args.steps / dt / 1e12 / world / PEAK_FP32_MFMA_TFLOPS, 4),
+                       last_loss=loss, roofline=roofline, **extra, modes=mode_rows, kernels=kernels)
+        out["host_reduce"] = host_reduce
         if args.conv_mode in tripped:
-            out["range_guard_tripped"] = mode_rows[args.conv_mode]["dtype"]
+            out["range_guard_tripped"] = moved(args.conv_mode)
     trainer.close()
     gnet.close(); rnet.close()
     return out
@@ -755,8 +776,8 @@ def _pick(d, keys):
 
 
 def headline(out, conv_mode="f16x3"):
-    """The compact line: exactly the contract's keys + roofline + cpu_baseline + the strict-precision row, cfg3 and cfg5 summaries
-    (VERDICT round 4, item 1).  Pure function of the full result dict (tests/test_host_logic.py feeds it a canned one)."""
+    """The compact line: exactly the contract's keys, and for a --full result roofline + cpu_baseline + the strict-precision row, cfg3 and
+    cfg5 summaries.  Pure function of the result dict (tests/test_host_logic.py feeds it canned ones)."""
     cfgkeys = ("workload", "global_batch", "per_gpu_batch", "parallelism", "bn")
     line = {k: out.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline")}
     line["dtype"] = out["dtype"] if len(str(out.get("dtype", ""))) <= 100 else _SHORT_DTYPE.get(conv_mode, conv_mode)
@@ -765,6 +786,8 @@ def headline(out, conv_mode="f16x3"):
     line["data"] = out.get("data", "synthetic")
     line["config"] = _pick(out.get("config", {}), cfgkeys)
     line["rccl_ranks"] = out.get("rccl_ranks", 1)
+    if "roofline" not in out:          # a plain run: the headline measurement and nothing else
+        return line
     roof = out.get("roofline") or {}
     line["roofline"] = _pick(roof, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "launches_per_step", "algorithmic_gflop_per_launch"))
     if isinstance(roof.get("sustained"), dict):
@@ -843,16 +866,17 @@ def _stdout_to_stderr():
 
 def emit(out, args):
     out = _finite(out)
-    detail = json.dumps(out, allow_nan=False)
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-        with open(args.detail, "w") as f:
-            f.write(detail + "\n")
-    except OSError as e:
-        print(f"bench.py: could not write {args.detail}: {e}", file=sys.stderr)
-    # (the 23 KB detail is NOT echoed to stderr: a driver that merges the streams and keeps a tail would be back to parsing around it - round 4's failure)
-    print(f"bench.py: full result ({len(detail)} bytes: mode tables, per-kernel tables, notes) written to {args.detail}", file=sys.stderr)
-    sys.stderr.flush()
+    if args.full:                      # a plain run's line is its whole result: no detail file
+        detail = json.dumps(out, allow_nan=False)
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+            with open(args.detail, "w") as f:
+                f.write(detail + "\n")
+        except OSError as e:
+            print(f"bench.py: could not write {args.detail}: {e}", file=sys.stderr)
+        # (the 23 KB detail is NOT echoed to stderr: a driver that merges the streams and keeps a tail would be back to parsing around it - round 4's failure)
+        print(f"bench.py: full result ({len(detail)} bytes: mode tables, per-kernel tables, notes) written to {args.detail}", file=sys.stderr)
+        sys.stderr.flush()
     print(headline_text(out, args.conv_mode))
     sys.stdout.flush()
 
@@ -862,8 +886,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the other arithmetic modes, the cfg3 rider, per-kernel tables and "
+                         "roofline, the cfg5 search and embedding pipeline, the GAN batch, the CPU baselines, and the --detail file")
     ap.add_argument("--workload", default="both", choices=sorted(WORKLOADS) + ["both"],
-                    help="both (default): cfg2 is the headline (BASELINE configs[1], the size north_star's bs256 target is quoted on) and "
+                    help="both (default): cfg2 is the headline (BASELINE configs[1], the size north_star's bs256 target is quoted on) and, with --full, "
                          "cfg3 (configs[2] = the per-GPU shard of configs[3]) rides in the same line as the `cfg3` object")
     ap.add_argument("--init", default="reference", choices=["reference", "synth"], help="R's initial weights: models.create_R's (the reference's initialisation) or synth.init_params")
     ap.add_argument("--seed", type=int, default=1, help="seed of R's initialisation (train_r.lua:18 default 1)")
@@ -877,14 +904,15 @@ def main():
     ap.add_argument("--no-gan", action="store_true", help="skip the GAN-game leg (SURVEY.md 8f rank 4: G + D2, one adversarial batch)")
     ap.add_argument("--conv-mode", default=os.environ.get("GR_CONV_MODE", "f16x3"), choices=list(MODES),
                     help="arithmetic of the headline line (all meet the 1e-4 parity bar; see DESIGN.md)")
-    ap.add_argument("--modes", default=",".join(MODES), help="arithmetic modes timed in this invocation (the headline mode is always run)")
+    ap.add_argument("--modes", default=",".join(MODES), help="arithmetic modes a --full run times (the headline mode is always run)")
     ap.add_argument("--traffic", default="live", choices=["live", "file", "off"],
                     help="roofline.traffic: measured in this run by rocprofv3 --pmc children (N = 1), read from profiles/traffic.json, or omitted")
-    ap.add_argument("--detail", default=DETAIL_FILE, help="file the FULL result (mode tables, per-kernel tables, notes) is written to; stdout carries the compact headline only")
+    ap.add_argument("--detail", default=DETAIL_FILE, help="file a --full run writes its FULL result (mode tables, per-kernel tables, notes) to; stdout carries the compact headline only")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after each timed mode, write what its last timed step computed (R's parameters, gradient, Adam moments, BatchNorm running "
                          "statistics, G's images, R's predictions) as DIR/<workload>_<mode>_<name>.npy, float32; arrays above "
-                         f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample; at most {DUMP_MAX_BYTES // 10 ** 6} MB in all")
+                         f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample; at most {DUMP_MAX_BYTES // 10 ** 6} MB in all; the files of a --full run "
+                         "in a plain run too (every mode and workload is stepped, only the headline reported)")
     ap.add_argument("--quiet-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:
@@ -923,13 +951,14 @@ def main():
         return
 
     head = "cfg2" if args.workload == "both" else args.workload
-    workloads = [head] + (["cfg3"] if args.workload == "both" else [])
+    workloads = [head] + (["cfg3"] if args.workload == "both" and every_mode(args) else [])
+    traffic_src = args.traffic if args.full else "off"     # roofline.traffic belongs to the --full tables
     traffic, traffic_from = {}, {}
     for w in workloads:
         t, tf = None, None
-        if world == 1 and args.traffic == "live":
+        if world == 1 and traffic_src == "live":
             t, tf = measure_traffic(args, w)              # children first: this process has not initialised the GPU yet
-        if t is None and args.traffic != "off":
+        if t is None and traffic_src != "off":
             tfile = os.path.join(ROOT, "profiles", "traffic.json")
             note = tf
             if os.path.exists(tfile):
@@ -965,10 +994,10 @@ def main():
 
     if args.sync_bn:
         ctx.set_tuning("sync_bn", 1)                                          # takes effect with a communicator (N > 1)
-    modes = [args.conv_mode] + [m for m in args.modes.split(",") if m in MODES and m != args.conv_mode]
+    modes = [args.conv_mode] + ([m for m in args.modes.split(",") if m in MODES and m != args.conv_mode] if every_mode(args) else [])
     res = {}
     for w in workloads:
-        # the second workload of a default run is timed in the headline arithmetic only (its other modes: --workload cfg3)
+        # the second workload of a --full run is timed in the headline arithmetic only (its other modes: --full --workload cfg3)
         res[w] = run_workload(args, w, modes if w == head else [args.conv_mode], ctx, rank, world, shared_gpu,
                               traffic[w], traffic_from[w], dist, torch)
 
@@ -1001,26 +1030,27 @@ def main():
                                   roofline_kernel=f32["roofline"]["kernel"], roofline_frac=f32["roofline"]["frac"], roofline_peak=f32["roofline"]["peak"],
                                   r_convs_frac_of_fp32_mfma_peak=f32["r_convs"]["frac_of_fp32_mfma_peak"],
                                   note="the same workload in exact-fp32 arithmetic (modes.f32); the headline `value` runs fp32-accurate f16x3 (22-bit operand splits)")
-        if "cfg3" in res and head != "cfg3":
+        if "cfg3" in res and head != "cfg3" and args.full:
             c3 = res["cfg3"]; c3.pop("host_reduce")
             c3["note"] = ("BASELINE configs[2] (64x64 RGB, noise 100, batch 512 per GPU) = the per-GPU shard of configs[3] (global batch 4096 over 8 GPUs): "
                           "same run, same steps / warmup, headline arithmetic; at n_gpus = 8 this object IS configs[3]")
             out["cfg3"] = c3
-        if world == 1 and not args.no_search:
-            out["search_cfg5"] = search_cfg5(ctx)
-            try:                      # configs[4] as stated: the corpus produced by the device-resident G -> R pipeline, then searched
-                out["search_cfg5"].update(embed_cfg5(ctx, args.embed_rows, with_oracle=not args.no_cpu_baseline, train_steps=args.embed_train_steps))
-            except Exception as e:  # noqa: BLE001
-                out["search_cfg5"]["embed"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_gan:
-            try:                      # a side leg: its failure is reported in the line, it never takes the headline measurement down
-                out["gan_step"] = gan_step(ctx, with_cpu=not args.no_cpu_baseline)
-            except Exception as e:  # noqa: BLE001
-                out["gan_step"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(WORKLOADS["cfg2"]["dims"], WORKLOADS["cfg2"]["nd"], ctx)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:                 # the side legs
+            if world == 1 and not args.no_search:
+                out["search_cfg5"] = search_cfg5(ctx)
+                try:                      # configs[4] as stated: the corpus produced by the device-resident G -> R pipeline, then searched
+                    out["search_cfg5"].update(embed_cfg5(ctx, args.embed_rows, with_oracle=not args.no_cpu_baseline, train_steps=args.embed_train_steps))
+                except Exception as e:  # noqa: BLE001
+                    out["search_cfg5"]["embed"] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not args.no_gan:
+                try:                      # a side leg: its failure is reported in the line, it never takes the headline measurement down
+                    out["gan_step"] = gan_step(ctx, with_cpu=not args.no_cpu_baseline)
+                except Exception as e:  # noqa: BLE001
+                    out["gan_step"] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(WORKLOADS["cfg2"]["dims"], WORKLOADS["cfg2"]["nd"], ctx)
+            else:
+                out["cpu_baseline"] = None
     if world > 1:
         dist.barrier()
         if not shared_gpu:

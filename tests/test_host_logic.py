@@ -356,7 +356,7 @@ def test_sharded_search_eight_ranks_with_ties_across_three_boundaries(oracle):
 
 def test_design_quotes_the_tracked_bench_summary():
     """VERDICT round 5, item 2 (the mis-filed r05 summary: DESIGN quoted 136.4 k img/s while the tracked file held a 3-step run at 50.6 k).  The tracked
-    summary of the round - profiles/r06_bench_default.json, the --detail file of an UNPROFILED `python bench.py` - must be a real run (>= 20 timed steps,
+    summary of the round - profiles/r06_bench_default.json, the --detail file of an UNPROFILED `python bench.py --full` - must be a real run (>= 20 timed steps,
     >= 5 warm-up, the headline workload, the arithmetic the line names), and every number DESIGN.md's current-round table quotes must be the number in that
     file (the table is generated from it by tools/update_design_table.py: equal to the printed precision, not merely within a box-to-box spread)."""
     import json, os, re
@@ -435,6 +435,25 @@ def test_bench_headline_is_compact_strict_json():
     l2 = json.loads(t2)
     assert len(t2) < 4096 and l2["roofline"]["traffic"] is None and l2["search_cfg5"]["embed_error"] == "boom" and len(l2["dtype"]) < 120
     json.dumps(bad, allow_nan=False)                           # the detail file is strict JSON too
+
+
+def test_bench_plain_headline_carries_the_contract_keys_only():
+    """A plain `bench.py` run (no --full) times the headline alone: its result holds the contract's keys and the run's configuration, and its
+    line says exactly that - no side-leg summaries standing empty - with the same values and dtype rule as a --full line."""
+    import copy, json, os, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    full = json.load(open(os.path.join(root, "tests", "golden", "bench_result_canned.json")))
+    contract = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype")
+    plain = {k: copy.deepcopy(full[k]) for k in contract + ("data", "config", "rccl_ranks")}
+    line = json.loads(bench.headline_text(plain))
+    assert set(line) == set(contract) | {"data", "config", "rccl_ranks"}, sorted(line)
+    full_line = json.loads(bench.headline_text(full))
+    for k in contract + ("data", "config", "rccl_ranks"):
+        assert line[k] == full_line[k], k
+    plain["dtype"] = "f32 via bf16x6 (...) (the f16x3 range guard moved the context from f16x3 to bf16x6 during the timed steps)"
+    assert "range guard" in json.loads(bench.headline_text(plain))["dtype"]
 
 
 def test_oracle_act_side_hook_moves_exactly_the_forced_elements():

@@ -6,7 +6,7 @@ V=$1; WL=${2:-cfg3}; N=${3:-2}; F=${4:-.}
 for i in $(seq 1 $N); do
   for arm in A B; do
     if [ $arm = B ]; then export $V; else unset ${V%%=*}; fi
-    python bench.py --workload $WL --modes f16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-search --no-gan --no-sustained --traffic off --detail /tmp/ab_$arm.json > /dev/null 2>&1
+    python bench.py --full --workload $WL --modes f16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-search --no-gan --no-sustained --traffic off --detail /tmp/ab_$arm.json > /dev/null 2>&1
     python - $arm "$F" <<'PY'
 import json, re, sys
 d = json.load(open(f"/tmp/ab_{sys.argv[1]}.json"))

@@ -5,7 +5,7 @@ WL=${1:-cfg3}; N=${2:-2}; F=${3:-.}
 for i in $(seq 1 $N); do
   for arm in A B; do
     if [ $arm = A ]; then cp tools/probe/libganrev_base.so gan-reverser_amd/ganrev/libganrev.so; else cp tools/probe/libganrev_new.so gan-reverser_amd/ganrev/libganrev.so; fi
-    python bench.py --workload $WL --modes f16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-search --no-gan --no-sustained --traffic off --detail /tmp/ab_$arm.json > /dev/null 2>&1
+    python bench.py --full --workload $WL --modes f16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-search --no-gan --no-sustained --traffic off --detail /tmp/ab_$arm.json > /dev/null 2>&1
     python - $arm "$F" <<'PY'
 import json, re, sys
 d = json.load(open(f"/tmp/ab_{sys.argv[1]}.json"))

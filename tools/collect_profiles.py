@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Turn the rocprofv3 outputs a gpurun call left under gpurun_out/ into the committed summaries under profiles/.
+"""Turn the rocprofv3 outputs tools/profile_bench.sh left under $PROF_OUT (default build/profile/) into the committed summaries under profiles/.
 
-  gpurun_out/prof_stats_<workload>/**/_kernel_stats.csv       (rocprofv3 --kernel-trace --stats)   -> profiles/<tag>_<workload>_kernel_stats.csv
-  gpurun_out/prof_fetch_<workload>|prof_write_<workload>/**/_counter_collection.csv (--pmc FETCH_SIZE / WRITE_SIZE, separate passes)
+  $PROF_OUT/prof_stats_<workload>/**/_kernel_stats.csv         (rocprofv3 --kernel-trace --stats)   -> profiles/<tag>_<workload>_kernel_stats.csv
+  $PROF_OUT/prof_fetch_<workload>|prof_write_<workload>/**/_counter_collection.csv (--pmc FETCH_SIZE / WRITE_SIZE, separate passes)
                                                                                        -> profiles/<tag>_hbm_traffic.json
                                                                                        -> profiles/traffic.json (read by bench.py)
 HBM bytes per launch follow MI355X_MICROARCH.md section HBM: FETCH_SIZE and WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE
@@ -19,6 +19,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.environ.get("PROF_OUT", os.path.join(ROOT, "build", "profile"))      # where tools/profile_bench.sh wrote its passes
 
 
 def short(name):
@@ -27,7 +28,7 @@ def short(name):
 
 
 def pmc_avg(d, counter):
-    files = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", d, "**", "*_counter_collection.csv"), recursive=True), key=os.path.getmtime)[-1:]
+    files = sorted(glob.glob(os.path.join(SRC, d, "**", "*_counter_collection.csv"), recursive=True), key=os.path.getmtime)[-1:]
     if not files:
         return {}
     agg = collections.defaultdict(lambda: [0, 0.0])
@@ -45,7 +46,7 @@ def main():
     workload = sys.argv[2] if len(sys.argv) > 2 else "cfg2"
     out = os.path.join(ROOT, "profiles")
     os.makedirs(out, exist_ok=True)
-    stats = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"prof_stats_{workload}", "**", "*_kernel_stats.csv"), recursive=True), key=os.path.getmtime)
+    stats = sorted(glob.glob(os.path.join(SRC, f"prof_stats_{workload}", "**", "*_kernel_stats.csv"), recursive=True), key=os.path.getmtime)
     if stats:
         shutil.copy(stats[-1], os.path.join(out, f"{tag}_{workload}_kernel_stats.csv"))
     fetch, write = pmc_avg(f"prof_fetch_{workload}", "FETCH_SIZE"), pmc_avg(f"prof_write_{workload}", "WRITE_SIZE")
@@ -62,7 +63,7 @@ def main():
     traffic = json.load(open(tpath)) if os.path.exists(tpath) else {}
     traffic[workload] = {k: v["hbm_bytes_corrected"] for k, v in summary.items()}
     json.dump(traffic, open(tpath, "w"), indent=1)
-    p = os.path.join(ROOT, "gpurun_out", f"bench_prof_{workload}.json")      # the FULL result of the profiled run (bench.py --detail)
+    p = os.path.join(SRC, f"bench_prof_{workload}.json")      # the FULL result of the profiled run (bench.py --full --detail)
     if os.path.exists(p):
         shutil.copy(p, os.path.join(out, f"{tag}_{workload}_bench_under_rocprof.json"))
     print("wrote", sorted(os.listdir(out)))

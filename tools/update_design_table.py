@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rewrites the table between <!-- bench-table:begin --> and <!-- bench-table:end --> in DESIGN.md from the tracked bench summary
-(profiles/r06_bench_default.json = the --detail file of an UNPROFILED `python bench.py` at HEAD), so that the numbers DESIGN.md quotes cannot drift from
+(profiles/r06_bench_default.json = the --detail file of an UNPROFILED `python bench.py --full` at HEAD), so that the numbers DESIGN.md quotes cannot drift from
 the file the judge reads.  tests/test_host_logic.py::test_design_quotes_the_tracked_bench_summary checks the two against each other.
    python tools/update_design_table.py [profiles/r06_bench_default.json]"""
 import json, os, re, sys
