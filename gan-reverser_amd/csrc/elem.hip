@@ -6,6 +6,7 @@
 //   nn.SpatialBatchNormalization / nn.BatchNormalization   models.lua:116,123,129,410..437,448
 //   nn.ELU / cudnn.ReLU / nn.Sigmoid / nn.Tanh / nn.LeakyReLU  models.lua:411,117,133,453,18
 //   nn.Dropout / nn.SpatialDropout / nn.SpatialMaxPooling  models.lua:402-405,412,439,422,440
+//   nn.SpatialAveragePooling(2,2,2,2)                      models.lua:71,235,242,249,348-363
 //   nn.MSECriterion                                        train_r.lua:119,147,150
 //   fevalR penalty+clamp and optim.adam                    train_r.lua:153-165,170
 #include "kernels.h"
@@ -35,40 +36,41 @@ __device__ __forceinline__ float post_slope(const PostArgs& a) { return a.act ==
 // branch on it per element - uniform branches, but ~25 of them per float4 and every taken one a fetch bubble.  The three
 // descriptions R's training step consists of (models.lua:409-440: conv-SBN-ELU-Dropout; ...-ELU-MaxPool-Dropout;
 // ...-ELU-SpatialDropout-MaxPool) are instantiated with those fields as compile-time constants: same code, same arithmetic,
-// the switches folded.  CB = 0 is the generic kernel.
+// the switches folded.  CB = 0 is the generic kernel.  Every pooling combo is a max pool (pool = POOL_MAX); average-pooling
+// stages run on CB = 0.
 template <int CB>
 __device__ __forceinline__ void post_specialize(PostArgs& f) {
   if (CB == 1) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_ELEM; f.pool = 0; f.m2.kind = MASK_NONE; }
-  if (CB == 2) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_NONE; f.pool = 1; f.m2.kind = MASK_ELEM; }
-  if (CB == 3) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_SPATIAL; f.pool = 1; f.m2.kind = MASK_NONE; }
+  if (CB == 2) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_NONE; f.pool = POOL_MAX; f.m2.kind = MASK_ELEM; }
+  if (CB == 3) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_SPATIAL; f.pool = POOL_MAX; f.m2.kind = MASK_NONE; }
   // the D network's stages (models.lua:272-337: no BatchNorm; a PReLU closes its stage, dropout / pooling follow element-wise)
   if (CB == 4) { f.act = ACT_PRELU; f.has_bn = 0; f.m1.kind = MASK_NONE; f.pool = 0; f.m2.kind = MASK_NONE; }
-  if (CB == 5) { f.act = ACT_NONE; f.has_bn = 0; f.m1.kind = MASK_SPATIAL; f.pool = 1; f.m2.kind = MASK_NONE; }
-  if (CB == 6) { f.act = ACT_NONE; f.has_bn = 0; f.m1.kind = MASK_NONE; f.pool = 1; f.m2.kind = MASK_NONE; }
+  if (CB == 5) { f.act = ACT_NONE; f.has_bn = 0; f.m1.kind = MASK_SPATIAL; f.pool = POOL_MAX; f.m2.kind = MASK_NONE; }
+  if (CB == 6) { f.act = ACT_NONE; f.has_bn = 0; f.m1.kind = MASK_NONE; f.pool = POOL_MAX; f.m2.kind = MASK_NONE; }
   if (CB == 7) { f.act = ACT_NONE; f.has_bn = 0; f.m1.kind = MASK_SPATIAL; f.pool = 0; f.m2.kind = MASK_NONE; }
   // G in training mode (the GAN game trains it: models.lua:115-133): Linear/conv - BatchNorm - ReLU, and the Sigmoid of its last layer
   if (CB == 8) { f.act = ACT_RELU; f.has_bn = 1; f.m1.kind = MASK_NONE; f.pool = 0; f.m2.kind = MASK_NONE; }
   if (CB == 9) { f.act = ACT_SIGMOID; f.has_bn = 0; f.m1.kind = MASK_NONE; f.pool = 0; f.m2.kind = MASK_NONE; }
   // R in evaluate() mode (apply_r.lua's embedding): the two pooling stages (the other four ride in their convolutions' epilogues);
   // Dropout is the identity there, SpatialDropout a multiplication by 1 - p
-  if (CB == 10) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_NONE; f.pool = 1; f.m2.kind = MASK_NONE; }
-  if (CB == 11) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_SCALE; f.pool = 1; f.m2.kind = MASK_NONE; }
+  if (CB == 10) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_NONE; f.pool = POOL_MAX; f.m2.kind = MASK_NONE; }
+  if (CB == 11) { f.act = ACT_ELU; f.has_bn = 1; f.m1.kind = MASK_SCALE; f.pool = POOL_MAX; f.m2.kind = MASK_NONE; }
 }
 inline int post_combo(const PostArgs& f) {
   if (!f.has_bn && f.m2.kind == MASK_NONE) {
     if (f.act == ACT_PRELU && f.m1.kind == MASK_NONE && !f.pool) return 4;
-    if (f.act == ACT_NONE && f.m1.kind == MASK_SPATIAL && f.pool) return 5;
-    if (f.act == ACT_NONE && f.m1.kind == MASK_NONE && f.pool) return 6;
+    if (f.act == ACT_NONE && f.m1.kind == MASK_SPATIAL && f.pool == POOL_MAX) return 5;
+    if (f.act == ACT_NONE && f.m1.kind == MASK_NONE && f.pool == POOL_MAX) return 6;
     if (f.act == ACT_NONE && f.m1.kind == MASK_SPATIAL && !f.pool) return 7;
     if (f.act == ACT_SIGMOID && f.m1.kind == MASK_NONE && !f.pool) return 9;
   }
   if (f.act == ACT_RELU && f.has_bn && f.m1.kind == MASK_NONE && !f.pool && f.m2.kind == MASK_NONE) return 8;
   if (f.act != ACT_ELU || !f.has_bn) return 0;
   if (f.m1.kind == MASK_ELEM && !f.pool && f.m2.kind == MASK_NONE) return 1;
-  if (f.m1.kind == MASK_NONE && f.pool && f.m2.kind == MASK_ELEM) return 2;
-  if (f.m1.kind == MASK_SPATIAL && f.pool && f.m2.kind == MASK_NONE) return 3;
-  if (f.m1.kind == MASK_NONE && f.pool && f.m2.kind == MASK_NONE) return 10;
-  if (f.m1.kind == MASK_SCALE && f.pool && f.m2.kind == MASK_NONE) return 11;
+  if (f.m1.kind == MASK_NONE && f.pool == POOL_MAX && f.m2.kind == MASK_ELEM) return 2;
+  if (f.m1.kind == MASK_SPATIAL && f.pool == POOL_MAX && f.m2.kind == MASK_NONE) return 3;
+  if (f.m1.kind == MASK_NONE && f.pool == POOL_MAX && f.m2.kind == MASK_NONE) return 10;
+  if (f.m1.kind == MASK_SCALE && f.pool == POOL_MAX && f.m2.kind == MASK_NONE) return 11;
   return 0;
 }
 template <typename F>
@@ -144,15 +146,20 @@ __global__ __launch_bounds__(256) void post_forward_kernel(PostArgs a) {
     float r;
     if (a.pool) {
       const int yo = po / Wo, xo = po - yo * Wo;
-      float best = -INFINITY; int bi = 0;
+      float best = -INFINITY, sum = 0.f; int bi = 0;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const long e = bc * HW + (long)(2 * yo + (t >> 1)) * W + 2 * xo + (t & 1);
         const float v = act_fwd(bn_apply(a, a.y[e], c), a.act, post_slope(a)) * mask_mul(a.m1, e, bc);
         if (v > best) { best = v; bi = t; }
+        sum += v;
       }
-      a.pool_idx[i] = (uint8_t)bi;
-      r = best;
+      if (a.pool == POOL_AVG) {
+        r = sum / 4.f;
+      } else {
+        a.pool_idx[i] = (uint8_t)bi;
+        r = best;
+      }
     } else {
       r = act_fwd(bn_apply(a, a.y[i], c), a.act, post_slope(a)) * mask_mul(a.m1, i, bc);
     }
@@ -234,16 +241,25 @@ __global__ __launch_bounds__(256) void post_forward_vec_kernel(PostArgs a) {
       const float top[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
       const float bot[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
       float o[4]; uint32_t idx = 0;
+      if (a.pool == POOL_AVG) {         // THNN / cunn: sum = 0, the window added in scan order, then / 4 (no index)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float best = -INFINITY; uint32_t bi = 0;      // scan order (0,0) (0,1) (1,0) (1,1); first strictly greater wins
-        if (top[2 * k] > best) { best = top[2 * k]; bi = 0; }
-        if (top[2 * k + 1] > best) { best = top[2 * k + 1]; bi = 1; }
-        if (bot[2 * k] > best) { best = bot[2 * k]; bi = 2; }
-        if (bot[2 * k + 1] > best) { best = bot[2 * k + 1]; bi = 3; }
-        o[k] = best; idx |= bi << (8 * k);
+        for (int k = 0; k < 4; ++k) {
+          float sum = 0.f;
+          sum += top[2 * k]; sum += top[2 * k + 1]; sum += bot[2 * k]; sum += bot[2 * k + 1];
+          o[k] = sum / 4.f;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float best = -INFINITY; uint32_t bi = 0;      // scan order (0,0) (0,1) (1,0) (1,1); first strictly greater wins
+          if (top[2 * k] > best) { best = top[2 * k]; bi = 0; }
+          if (top[2 * k + 1] > best) { best = top[2 * k + 1]; bi = 1; }
+          if (bot[2 * k] > best) { best = bot[2 * k]; bi = 2; }
+          if (bot[2 * k + 1] > best) { best = bot[2 * k + 1]; bi = 3; }
+          o[k] = best; idx |= bi << (8 * k);
+        }
+        *reinterpret_cast<uint32_t*>(a.pool_idx + eo) = idx;
       }
-      *reinterpret_cast<uint32_t*>(a.pool_idx + eo) = idx;
       r = make_float4(o[0], o[1], o[2], o[3]);
     } else {
       r = mul4(bn_act4(a, ld4_maybe_nt(a.y + eo, a.nt != 0), mean, invstd, g, bt), mask4(a.m1, eo, bc));
@@ -308,13 +324,14 @@ __device__ __forceinline__ void t8_emit(const unsigned char* img, int npx, uint4
   }
 }
 // PXT = pixels per tile: 1024, or 256 for planes of 256 output pixels (a 34 KB image for 1024 pixels limits a CU to four
-// workgroups; 16x16 planes need 9 KB and fit eight)
-template <bool POOL, int PXT, int CB>
+// workgroups; 16x16 planes need 9 KB and fit eight).  POOL = the PoolMode, fixed at compile time: the max-pool kernels stay
+// what they were before the average existed (the generic one then spilled 3 more SGPRs)
+template <int POOL, int PXT, int CB>
 __global__ __launch_bounds__(256) void post_forward_g8_kernel(PostArgs a) {
   post_specialize<CB>(a);
   constexpr int RSB = PXT * 2 + 64;                          // bytes per (term, channel) row: 64 (mod 256)
   __shared__ __attribute__((aligned(16))) unsigned char img[16 * RSB];
-  const unsigned H = a.H, W = a.W, Ho = POOL ? H >> 1 : H, Wo = POOL ? W >> 1 : W;
+  const unsigned H = a.H, W = a.W, Ho = POOL != POOL_NONE ? H >> 1 : H, Wo = POOL != POOL_NONE ? W >> 1 : W;
   const unsigned HW = H * W, HWo = Ho * Wo, wq = Wo >> 2, G = (unsigned)a.C >> 3;
   const unsigned npx = HWo < (unsigned)PXT ? HWo : (unsigned)PXT, tiles = HWo / npx, qpt = npx >> 2;   // quads per tile
   const unsigned units = (unsigned)a.B * G * tiles;
@@ -329,7 +346,7 @@ __global__ __launch_bounds__(256) void post_forward_g8_kernel(PostArgs a) {
       if (a.has_bn) { mean = a.mean[c]; invstd = a.invstd[c]; gm = a.gamma[c]; bt = a.beta[c]; }
       const unsigned eo = bc * HWo + within * 4;
       float4 r;
-      if constexpr (POOL) {
+      if constexpr (POOL != POOL_NONE) {
         const unsigned yo = udivp(within, wq), xo = (within - yo * wq) * 4;
         const unsigned e0 = bc * HW + (2 * yo) * W + 2 * xo, e1 = e0 + W;
         const float4 t0 = mul4(bn_act4(a, ld4_maybe_nt(a.y + e0, a.nt != 0), mean, invstd, gm, bt), mask4(a.m1, e0, bc));
@@ -339,16 +356,25 @@ __global__ __launch_bounds__(256) void post_forward_g8_kernel(PostArgs a) {
         const float top[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
         const float bot[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
         float o[4]; uint32_t idx = 0;
+        if constexpr (POOL == POOL_AVG) {         // THNN / cunn: sum = 0, the window added in scan order, then / 4 (no index)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float best = -INFINITY; uint32_t bi = 0;      // scan order (0,0) (0,1) (1,0) (1,1); first strictly greater wins
-          if (top[2 * k] > best) { best = top[2 * k]; bi = 0; }
-          if (top[2 * k + 1] > best) { best = top[2 * k + 1]; bi = 1; }
-          if (bot[2 * k] > best) { best = bot[2 * k]; bi = 2; }
-          if (bot[2 * k + 1] > best) { best = bot[2 * k + 1]; bi = 3; }
-          o[k] = best; idx |= bi << (8 * k);
+          for (int k = 0; k < 4; ++k) {
+            float sum = 0.f;
+            sum += top[2 * k]; sum += top[2 * k + 1]; sum += bot[2 * k]; sum += bot[2 * k + 1];
+            o[k] = sum / 4.f;
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            float best = -INFINITY; uint32_t bi = 0;      // scan order (0,0) (0,1) (1,0) (1,1); first strictly greater wins
+            if (top[2 * k] > best) { best = top[2 * k]; bi = 0; }
+            if (top[2 * k + 1] > best) { best = top[2 * k + 1]; bi = 1; }
+            if (bot[2 * k] > best) { best = bot[2 * k]; bi = 2; }
+            if (bot[2 * k + 1] > best) { best = bot[2 * k + 1]; bi = 3; }
+            o[k] = best; idx |= bi << (8 * k);
+          }
+          *reinterpret_cast<uint32_t*>(a.pool_idx + eo) = idx;
         }
-        *reinterpret_cast<uint32_t*>(a.pool_idx + eo) = idx;
         r = make_float4(o[0], o[1], o[2], o[3]);
       } else {
         r = mul4(bn_act4(a, ld4_maybe_nt(a.y + eo, a.nt != 0), mean, invstd, gm, bt), mask4(a.m1, eo, bc));
@@ -410,8 +436,9 @@ void launch_post_forward(const PostArgs& a0, hipStream_t s) {
     KtScope kt("post_forward_g8_kernel", 0.0, 4.0 * ((double)a.B * a.C * a.H * a.W + (a.out ? 2.0 : 1.0) * (double)n), s);
     if (hwo > 256) blocks *= 4;                                       // 256-pixel tiles: four per T8_PXT step
     if (blocks > 8192) blocks = 8192;
-    if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<true, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
-    else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<false, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
+    if (a.pool == POOL_AVG) hipLaunchKernelGGL((post_forward_g8_kernel<POOL_AVG, 256, 0>), dim3((unsigned)blocks), dim3(256), 0, s, a);     // (no combo pools by the average)
+    else if (a.pool) with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<POOL_MAX, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
+    else with_combo(post_combo(a), [&](auto cb) { hipLaunchKernelGGL((post_forward_g8_kernel<POOL_NONE, 256, decltype(cb)::value>), dim3((unsigned)blocks), dim3(256), 0, s, a); });
     return;
   }
   const bool vec = (a.pool ? (a.W % 8 == 0 && a.H % 2 == 0) : (a.W % 4 == 0)) && (long)a.B * a.C * a.H * a.W < (1l << 32);
@@ -632,7 +659,8 @@ __global__ __launch_bounds__(256) void post_backward_a_kernel(PostBwdArgs a, int
       if (yo < Ho && xo < Wo) {
         const long eo = bc * HWo + (long)yo * Wo + xo;
         const int t = ((yy & 1) << 1) | (xx & 1);
-        if (f.pool_idx[eo] == t) g = a.gout[eo] * mask_mul(f.m2, eo, bc);
+        if (f.pool == POOL_AVG) g = (a.gout[eo] * mask_mul(f.m2, eo, bc)) / 4.f;      // every window element: gradOutput / 4
+        else if (f.pool_idx[eo] == t) g = a.gout[eo] * mask_mul(f.m2, eo, bc);
       }
     } else {
       g = a.gout[e] * mask_mul(f.m2, e, bc);
@@ -654,7 +682,7 @@ __global__ __launch_bounds__(256) void post_backward_a_kernel(PostBwdArgs a, int
 }
 
 // dz (gradient wrt the BatchNorm output, or wrt y without BN) of four consecutive pre-pool elements e .. e+3 of plane bc:
-// gradOutput routed back through mask 2, the pool argmax, mask 1 and the activation.  Pass A sums it, pass B needs it again:
+// gradOutput routed back through mask 2, the pool (argmax, or / 4 for the average), mask 1 and the activation.  Pass A sums it, pass B needs it again:
 // with BatchNorm both passes call this (bit-identical results) and dz is never written to memory - one tensor write and one
 // tensor read less than storing it.
 // The same in two phases for kernels that work on several channels per thread: all loads of a channel first (so that the loads
@@ -668,7 +696,7 @@ __device__ __forceinline__ BwdRaw post_bwd_load4(const PostBwdArgs& a, unsigned 
     const unsigned yy = udivp(i, wq), xx = (i - yy * wq) * 4, eo = obase + (yy >> 1) * Wo + (xx >> 1);
     const float2 go = *reinterpret_cast<const float2*>(a.gout + eo);
     r.g = make_float4(go.x, go.y, 0.f, 0.f);
-    r.id2 = *reinterpret_cast<const uint16_t*>(f.pool_idx + eo);
+    r.id2 = f.pool == POOL_AVG ? 0u : *reinterpret_cast<const uint16_t*>(f.pool_idx + eo);      // (an average pool has no index)
     r.m2w = mask_word(f.m2, eo, bc);                  // eo is even: the bits of eo and eo + 1 sit in one word
     r.t0 = (yy & 1) << 1;
   } else {
@@ -686,10 +714,15 @@ __device__ __forceinline__ float4 post_bwd_dz_of(const PostBwdArgs& a, const Bwd
   if (f.pool) {
     const float4 m2 = mask4_of(f.m2, r.m2w);
     const float m20 = m2.x, m21 = m2.y;
-    g.x = ((r.id2 & 0xff) == r.t0) ? r.g.x * m20 : 0.f;
-    g.y = ((r.id2 & 0xff) == (r.t0 | 1)) ? r.g.x * m20 : 0.f;
-    g.z = ((r.id2 >> 8) == r.t0) ? r.g.y * m21 : 0.f;
-    g.w = ((r.id2 >> 8) == (r.t0 | 1)) ? r.g.y * m21 : 0.f;
+    if (f.pool == POOL_AVG) {
+      const float g0 = (r.g.x * m20) / 4.f, g1 = (r.g.y * m21) / 4.f;
+      g = make_float4(g0, g0, g1, g1);
+    } else {
+      g.x = ((r.id2 & 0xff) == r.t0) ? r.g.x * m20 : 0.f;
+      g.y = ((r.id2 & 0xff) == (r.t0 | 1)) ? r.g.x * m20 : 0.f;
+      g.z = ((r.id2 >> 8) == r.t0) ? r.g.y * m21 : 0.f;
+      g.w = ((r.id2 >> 8) == (r.t0 | 1)) ? r.g.y * m21 : 0.f;
+    }
   } else {
     g = mul4(r.g, mask4_of(f.m2, r.m2w));
   }
@@ -713,13 +746,18 @@ __device__ __forceinline__ float4 post_bwd_dz4(const PostBwdArgs& a, unsigned bc
   if (f.pool) {
     const unsigned yy = udivp(i, wq), xx = (i - yy * wq) * 4, eo = obase + (yy >> 1) * Wo + (xx >> 1);
     const float2 go = *reinterpret_cast<const float2*>(a.gout + eo);
-    const uint32_t id2 = *reinterpret_cast<const uint16_t*>(f.pool_idx + eo);
-    const float m20 = mask_mul(f.m2, eo, bc), m21 = mask_mul(f.m2, eo + 1, bc);
-    const uint32_t t0 = (yy & 1) << 1;
-    g.x = ((id2 & 0xff) == t0) ? go.x * m20 : 0.f;
-    g.y = ((id2 & 0xff) == (t0 | 1)) ? go.x * m20 : 0.f;
-    g.z = ((id2 >> 8) == t0) ? go.y * m21 : 0.f;
-    g.w = ((id2 >> 8) == (t0 | 1)) ? go.y * m21 : 0.f;
+    if (f.pool == POOL_AVG) {
+      const float g0 = (go.x * mask_mul(f.m2, eo, bc)) / 4.f, g1 = (go.y * mask_mul(f.m2, eo + 1, bc)) / 4.f;
+      g = make_float4(g0, g0, g1, g1);
+    } else {
+      const uint32_t id2 = *reinterpret_cast<const uint16_t*>(f.pool_idx + eo);
+      const float m20 = mask_mul(f.m2, eo, bc), m21 = mask_mul(f.m2, eo + 1, bc);
+      const uint32_t t0 = (yy & 1) << 1;
+      g.x = ((id2 & 0xff) == t0) ? go.x * m20 : 0.f;
+      g.y = ((id2 & 0xff) == (t0 | 1)) ? go.x * m20 : 0.f;
+      g.z = ((id2 >> 8) == t0) ? go.y * m21 : 0.f;
+      g.w = ((id2 >> 8) == (t0 | 1)) ? go.y * m21 : 0.f;
+    }
   } else {
     g = mul4(*reinterpret_cast<const float4*>(a.gout + e), mask4(f.m2, e, bc));
   }

@@ -253,6 +253,7 @@ enum Act { ACT_NONE = 0, ACT_ELU = 3, ACT_RELU = 4, ACT_LEAKYRELU = 5, ACT_SIGMO
            ACT_PRELU = 16 /* nn.PReLU() with one shared slope: LeakyReLU whose slope is read from device memory (PostArgs::slope_dev) */ };
 enum MaskKind { MASK_NONE = 0, MASK_ELEM = 1, MASK_SPATIAL = 2, MASK_SCALE = 3 /* evaluate(): x*(1-p) */ };
 struct MaskRef { int kind; const uint32_t* bits; float scale; };
+enum PoolMode { POOL_NONE = 0, POOL_MAX = 1 /* nn.SpatialMaxPooling(2,2) */, POOL_AVG = 2 /* nn.SpatialAveragePooling(2,2,2,2): no index */ };
 
 struct PostArgs {
   const float* y;          // raw main-op output [B,C,H,W]
@@ -263,8 +264,8 @@ struct PostArgs {
   int act; float slope;
   const float* slope_dev;  // ACT_PRELU: the learnable slope (one float in the net's flat parameter vector)
   MaskRef m1;              // applied before the pool, indexed at [B,C,H,W] (ELEM) or [B,C] (SPATIAL)
-  int pool;                // 2x2 max pool, stride 2
-  uint8_t* pool_idx;       // [B,C,Ho,Wo] argmax 0..3
+  int pool;                // PoolMode: none, or a 2x2 pool of stride 2 (max or average)
+  uint8_t* pool_idx;       // [B,C,Ho,Wo] argmax 0..3 (POOL_MAX only; null for POOL_AVG)
   MaskRef m2;              // applied after the pool, indexed at [B,C,Ho,Wo] / [B,C]
   unsigned* amax_out;      // nullable: max|out| is folded into this slot (f16x3 scale of the consuming convolution)
   // operand-ready copy of `out` for the convolution that consumes it (see conv_p16_supported): p16 != null selects the

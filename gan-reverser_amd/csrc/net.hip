@@ -1,7 +1,7 @@
 // net.hip — the C ABI (include/ganrev.h) and the nn.Sequential runtime behind it.
 //
 // A gr_net is the reference's nn.Sequential (models.lua:104-143 G3, models.lua:389-464 R) compiled into
-// STAGES:  [UpSample2] (Conv3x3 | Linear) [BN] [act] [Dropout|SpatialDropout] [MaxPool2] [Dropout]
+// STAGES:  [UpSample2] (Conv3x3 | Linear) [BN] [act] [Dropout|SpatialDropout] [MaxPool2|AvgPool2] [Dropout]
 // Each stage runs as: main MFMA kernel -> (training) BN statistics -> one fused per-channel pipeline kernel.
 // Backward mirrors it (train_r.lua:151): pipeline backward (two passes around the BN reduction) ->
 // weight-gradient kernel -> data-gradient kernel.  All device memory is owned by the net / ctx; there is
@@ -436,7 +436,8 @@ struct Stage {
   int act = ACT_NONE; float slope = 0;
   int ksz = 3;                              // window of the main convolution: 3 (conv.hip kernels) or an odd K convk.hip covers (GR_CONVK)
   int64_t slope_off = -1;                   // nn.PReLU: offset of its one learnable slope in the flat vectors
-  int m1 = -1, m2 = -1; bool pool = false;
+  int m1 = -1, m2 = -1; bool pool = false;     // pool: this stage pools (2x2, stride 2) ...
+  bool avg = false;                          // ... by the average (nn.SpatialAveragePooling: no pool_idx) rather than the maximum
   bool has_post = false;
   int outC = 0, outH = 0, outW = 0;
   float *y = nullptr, *out = nullptr; uint8_t* pool_idx = nullptr;
@@ -548,7 +549,7 @@ extern "C" int gr_net_create(gr_ctx* c, const gr_layer_desc* L, int nl, int in_c
         case GR_BN:
           if (d.a != cc) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: BN expects %d features, got %d", i, d.a, cc); }
           woff[i] = off; off += cc; boff[i] = off; off += cc; break;
-        case GR_MAXPOOL2: h /= 2; w /= 2; break;
+        case GR_MAXPOOL2: case GR_AVGPOOL2: h /= 2; w /= 2; break;     // floor, as THNN: an odd last row / column is dropped
         case GR_UPSAMPLE2: h *= 2; w *= 2; break;
         case GR_VIEW: {
           const int vb = d.b > 0 ? d.b : 1, vc = d.c > 0 ? d.c : 1;
@@ -591,7 +592,7 @@ extern "C" int gr_net_create(gr_ctx* c, const gr_layer_desc* L, int nl, int in_c
         if (d.kind == GR_BN) ph = 0;
         else if (is_act(d.kind)) ph = 1;
         else if (d.kind == GR_DROPOUT || d.kind == GR_SPATIAL_DROPOUT) ph = s.pool ? 4 : 2;
-        else if (d.kind == GR_MAXPOOL2) ph = 3;
+        else if (d.kind == GR_MAXPOOL2 || d.kind == GR_AVGPOOL2) ph = 3;
         else break;
         if (ph <= phase) break;
         // nn.PReLU's slope gradient needs the activation's own input and gradOutput as tensors: the PReLU closes its stage (what
@@ -600,7 +601,7 @@ extern "C" int gr_net_create(gr_ctx* c, const gr_layer_desc* L, int nl, int in_c
         phase = ph; s.has_post = true;
         if (ph == 0) { s.has_bn = true; s.g_off = woff[i]; s.be_off = boff[i]; n->bn_stage.push_back((int)n->st.size()); }
         else if (ph == 1) { s.act = d.kind; s.slope = d.p; if (d.kind == GR_PRELU) { s.slope_off = woff[i]; ++i; break; } }
-        else if (ph == 3) { s.pool = true; h /= 2; w /= 2; }
+        else if (ph == 3) { s.pool = true; s.avg = d.kind == GR_AVGPOOL2; h /= 2; w /= 2; }
         else {
           MaskSlot m; m.layer = i; m.kind = d.kind == GR_DROPOUT ? MASK_ELEM : MASK_SPATIAL; m.p = d.p; m.flags = d.flags;
           m.C = cc; m.H = h; m.W = w;
@@ -785,7 +786,7 @@ static int ensure_batch(gr_net* n, int B) {
       (void)hipFree(s.stat_part); s.stat_part = nullptr;
       HIPCHK(c, hipMalloc((void**)&s.stat_part, sizeof(double) * 2 * (size_t)s.Cout * conv_stat_tiles_max(B, s.H, s.W)));
     }
-    if (s.pool) { (void)hipFree(s.pool_idx); s.pool_idx = nullptr; HIPCHK(c, hipMalloc((void**)&s.pool_idx, (size_t)B * vol3(s.outC, s.outH, s.outW))); }
+    if (s.pool && !s.avg) { (void)hipFree(s.pool_idx); s.pool_idx = nullptr; HIPCHK(c, hipMalloc((void**)&s.pool_idx, (size_t)B * vol3(s.outC, s.outH, s.outW))); }
     if (s.kind == ST_CONV && s.ksz == 3 && !s.up && !s.fullconv && s.Cin % 16 == 0) {       // operand-ready input image (same bytes as the fp32 input)
       (void)hipFree(s.x_p16); s.x_p16 = nullptr; s.x_p16_gen = 0;
       HIPCHK(c, hipMalloc(&s.x_p16, sizeof(float) * (size_t)B * vol3(s.inC, s.inH, s.inW)));
@@ -886,7 +887,7 @@ static PostArgs post_args(gr_net* n, Stage& s, int B) {
   a.act = s.act; a.slope = s.slope; a.slope_dev = s.act == ACT_PRELU ? n->params + s.slope_off : nullptr;
   bool nb;
   a.m1 = mask_ref(n, s.m1, nb); a.m2 = mask_ref(n, s.m2, nb);
-  a.pool = s.pool ? 1 : 0; a.pool_idx = s.pool_idx;
+  a.pool = !s.pool ? POOL_NONE : s.avg ? POOL_AVG : POOL_MAX; a.pool_idx = s.pool_idx;
   a.amax_out = nullptr;
   return a;
 }

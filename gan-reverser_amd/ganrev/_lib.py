@@ -31,6 +31,7 @@ STATUS = {0: "GR_OK", -1: "GR_ERR_INVALID", -2: "GR_ERR_UNSUPPORTED", -3: "GR_ER
 # layer kinds (shared numeric values with the oracle's go_layer)
 CONV3, BN, ELU, RELU, LEAKYRELU, SIGMOID, TANH, DROPOUT, SPATIAL_DROPOUT, MAXPOOL2, UPSAMPLE2, VIEW, LINEAR, FULLCONV3 = range(1, 15)
 CONVK, PRELU = 15, 16       # the D network's extra module types (models.lua:272-337)
+AVGPOOL2 = 17               # nn.SpatialAveragePooling(2,2,2,2) (models.lua:71,235,242,249,348-363)
 DROPOUT_V2, DROPOUT_ALWAYS_ON = 1, 2
 COMM_ID_BYTES = 128
 
@@ -249,6 +250,11 @@ class Context:
         g = np.empty_like(x) if want_grad else None
         self.check(self.lib.gr_mse_host(self.h, _ptr(x), _ptr(t), x.size, int(n_global or x.size), C.byref(loss), _ptr(g)), "gr_mse_host")
         return loss.value, g
+
+    def mse_dev(self, x, t, n, loss_dev, grad_dev=None, n_global=None):
+        """nn.MSECriterion (sizeAverage) on device tensors of n floats: the loss (one double) into loss_dev, gradInput into
+        grad_dev when given; n_global = the element count the mean is taken over (default n)"""
+        self.check(self.lib.gr_mse_dev(self.h, _ptr(x), _ptr(t), int(n), int(n_global or n), _ptr(loss_dev), _ptr(grad_dev)), "gr_mse_dev")
 
     def bce(self, x, t, want_grad=True):
         """nn.BCECriterion (sizeAverage): (loss, gradInput)"""

@@ -1,6 +1,8 @@
 """Mirror of the reference model zoo's live constructors (models.lua): create_G -> create_G3 (models.lua:201-203,
 104-143), create_R -> create_R_default (models.lua:385-387, 389-464) and create_D -> create_D2 (models.lua:209-211, 272-337;
-the discriminator adversarial.lua trains G against - SURVEY.md 8f rank 4).  Same layer lists, same argument meaning."""
+the discriminator adversarial.lua trains G against - SURVEY.md 8f rank 4); create_G_encoder (models.lua:57-102, pretrain_g.lua's
+encoder half) and the two D variants with average pooling, create_D_default and create_D_facegen (models.lua:213-270, 339-383),
+which nothing selects (the reference's create_D returns create_D2).  Same layer lists, same argument meaning."""
 from . import nn
 from .weight_init import w_init
 
@@ -35,6 +37,40 @@ def create_G3(dimensions, noiseDim, cuda=True, seed=0):
     model.add(_CudnnReLU(True))
     model.add(_CudnnSpatialConvolution(128, dimensions[0], 3, 3, 1, 1, 1, 1))
     model.add(nn.Sigmoid())
+    if cuda:
+        model.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))
+        model.cuda()
+    return w_init(model, "heuristic", seed)
+
+
+def create_G_encoder(dimensions, noiseDim, cuda=True, seed=0):
+    """models.lua:57-102: three 3x3 conv - BatchNorm - ReLU blocks, halved by an average pool and two max pools, then
+    Linear - BatchNorm - ReLU - Linear - Tanh down to noiseDim.  Built from cudnn.* like create_G3: the heuristic init only
+    zeroes the convolutions' biases (weight-init.lua:54-72)."""
+    nn.manualSeed(seed)
+    model = nn.Sequential()
+    if cuda:
+        model.add(nn.Copy("torch.FloatTensor", "torch.CudaTensor", True, True))
+    startHeight, startWidth = dimensions[1], dimensions[2]
+    model.add(_CudnnSpatialConvolution(dimensions[0], 16, 3, 3, 1, 1, 1, 1))     # 32x32 -> 16x16  (models.lua:68-71)
+    model.add(nn.SpatialBatchNormalization(16))
+    model.add(_CudnnReLU(True))
+    model.add(nn.SpatialAveragePooling(2, 2, 2, 2))
+    model.add(_CudnnSpatialConvolution(16, 32, 3, 3, 1, 1, 1, 1))                # 16x16 -> 8x8  (models.lua:74-77)
+    model.add(nn.SpatialBatchNormalization(32))
+    model.add(_CudnnReLU(True))
+    model.add(nn.SpatialMaxPooling(2, 2))
+    model.add(_CudnnSpatialConvolution(32, 64, 3, 3, 1, 1, 1, 1))                # 8x8 -> 4x4  (models.lua:80-83)
+    model.add(nn.SpatialBatchNormalization(64))
+    model.add(_CudnnReLU(True))
+    model.add(nn.SpatialMaxPooling(2, 2))
+    height, width = startHeight // 2 // 2 // 2, startWidth // 2 // 2 // 2
+    model.add(nn.View(64 * height * width))
+    model.add(nn.Linear(64 * height * width, 512))
+    model.add(nn.BatchNormalization(512))
+    model.add(_CudnnReLU(True))
+    model.add(nn.Linear(512, noiseDim))
+    model.add(nn.Tanh())
     if cuda:
         model.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))
         model.cuda()
@@ -132,6 +168,63 @@ def create_D2(dimensions, cuda=True, seed=0):
     conv.add(nn.PReLU())
     conv.add(nn.Dropout(0.25))
     conv.add(nn.Linear(256, 1))
+    conv.add(nn.Sigmoid())
+    if cuda:
+        conv.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))
+        conv.cuda()
+    return w_init(conv, "heuristic", seed)
+
+
+def create_D_default(dimensions, cuda=True, seed=0):
+    """models.lua:213-270: five 3x3 convolutions, each closed by a PReLU (one slope); SpatialDropout(0.25) behind all but the
+    first, a 2x2 average pool behind the last three; Linear - PReLU - Dropout(0.5) - Linear - Sigmoid."""
+    nn.manualSeed(seed)
+    conv = nn.Sequential()
+    if cuda:
+        conv.add(nn.Copy("torch.FloatTensor", "torch.CudaTensor", True, True))
+    for cin, cout, drop, pool in [(dimensions[0], 32, False, False), (32, 64, True, False), (64, 128, True, True),
+                                  (128, 256, True, True), (256, 512, True, True)]:
+        conv.add(nn.SpatialConvolution(cin, cout, 3, 3, 1, 1, 1, 1))
+        conv.add(nn.PReLU())
+        if drop:
+            conv.add(nn.SpatialDropout(0.25))
+        if pool:
+            conv.add(nn.SpatialAveragePooling(2, 2, 2, 2))
+    height, width = dimensions[1] // 2 // 2 // 2, dimensions[2] // 2 // 2 // 2
+    conv.add(nn.View(512 * height * width))
+    conv.add(nn.Linear(512 * height * width, 512))
+    conv.add(nn.PReLU())
+    conv.add(nn.Dropout(0.5))
+    conv.add(nn.Linear(512, 1))
+    conv.add(nn.Sigmoid())
+    if cuda:
+        conv.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))
+        conv.cuda()
+    return w_init(conv, "heuristic", seed)
+
+
+def create_D_facegen(dimensions, cuda=True, seed=0):
+    """models.lua:339-383: four conv - PReLU - SpatialDropout(0.2) - average-pool blocks (SpatialConvolution(a, b, 3, 3, 1, 1, 1):
+    padH defaults to padW), then Linear - PReLU - Dropout() twice and Linear - Sigmoid.  nn.PReLU(nil, nil, true) is the
+    one-slope PReLU (nn.PReLU takes only nOutputPlane); nn.Dropout() is p = 0.5."""
+    nn.manualSeed(seed)
+    conv = nn.Sequential()
+    if cuda:
+        conv.add(nn.Copy("torch.FloatTensor", "torch.CudaTensor", True, True))
+    for cin, cout in [(dimensions[0], 64), (64, 128), (128, 256), (256, 512)]:
+        conv.add(nn.SpatialConvolution(cin, cout, 3, 3, 1, 1, 1))
+        conv.add(nn.PReLU())
+        conv.add(nn.SpatialDropout(0.2))
+        conv.add(nn.SpatialAveragePooling(2, 2, 2, 2))
+    flat = 512 * (dimensions[1] // 16) * (dimensions[2] // 16)           # 512 * 0.25^4 * height * width
+    conv.add(nn.View(flat))
+    conv.add(nn.Linear(flat, 512))
+    conv.add(nn.PReLU())
+    conv.add(nn.Dropout())
+    conv.add(nn.Linear(512, 512))
+    conv.add(nn.PReLU())
+    conv.add(nn.Dropout())
+    conv.add(nn.Linear(512, 1))
     conv.add(nn.Sigmoid())
     if cuda:
         conv.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))

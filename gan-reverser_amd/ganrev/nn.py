@@ -790,6 +790,22 @@ class SpatialMaxPooling(Module):
         return [(L.MAXPOOL2, 0, 0, 0, 0.0, 0)], (c, h // 2, w // 2)
 
 
+class SpatialAveragePooling(Module):
+    """nn.SpatialAveragePooling(kW, kH, dW, dH, padW, padH) (models.lua:71,235,242,249,348-363): only (2,2,2,2,0,0) has a
+    kernel; Torch7's defaults (dW = dH = 1, ceil_mode false, count_include_pad true, divide true) are kept for the checkpoint"""
+    TYPENAME = "nn.SpatialAveragePooling"
+
+    def __init__(self, kW, kH, dW=1, dH=1, padW=0, padH=0):
+        super().__init__()
+        if (kW, kH, dW, dH, padW, padH) != (2, 2, 2, 2, 0, 0):
+            raise L.GanrevError("only SpatialAveragePooling(2,2,2,2) is implemented (models.lua:71,235,242,249,348-363)")
+        self.kW, self.kH, self.dW, self.dH, self.padW, self.padH = kW, kH, dW, dH, padW, padH
+
+    def desc(self, dims):
+        c, h, w = dims
+        return [(L.AVGPOOL2, 0, 0, 0, 0.0, 0)], (c, h // 2, w // 2)
+
+
 class SpatialUpSamplingNearest(Module):
     TYPENAME = "nn.SpatialUpSamplingNearest"
 

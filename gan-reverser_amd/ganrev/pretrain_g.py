@@ -1,0 +1,210 @@
+"""Mirror of the reference's pretrain_g.lua: train G as the decoder half of an autoencoder (create_G_encoder -> create_G) under
+nn.MSECriterion, the L1 / L2 penalty, the gradient clamp and optim.adam (pretrain_g.lua:82-206), and save the decoder as
+<save>/g_pretrained_CxHxW_ndN.net - the file train.lua:148-161 (ganrev.train --G_pretrained_dir) starts G from.
+
+    python -m ganrev.pretrain_g --epochs 2 --N_epoch 30 --batchSize 128 --save logs [--data images.npy] [--compat]
+
+Same option names and defaults as pretrain_g.lua:12-35 for what is mirrored.  Training images come from --data (an
+[N x C x H x W] float32 .npy in [0, 1]) or, without it, from train.synthetic_images (the dataset loader is out of scope).
+
+Two loops, as in ganrev.train_r / ganrev.train:
+  fast (default)  - the epoch's images device-resident; per batch forward_dev -> gr_mse_dev -> backward_dev -> gr_adam_step
+                    (penalty, clamp and Adam fused), parameters pulled to the host only before a save;
+  --compat        - the fevalG closure exactly as pretrain_g.lua:148-180 spells it, over optim.adam.
+
+Stated deviations:
+  - pretrain_g.lua:112 stops when `OPT.epochs > EPOCH`: inverted, it breaks at once for any --epochs > 1 and runs forever with
+    -1.  Here --epochs N plays N epochs.
+  - One more save after the last epoch, as ganrev.train does (the reference is stopped by hand).
+"""
+import argparse
+import os
+import time
+
+import numpy as np
+
+from . import _lib as L
+from . import models, nn, optim, t7
+from .train import synthetic_images
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description="pretrain_g.lua options (pretrain_g.lua:12-35)")
+    p.add_argument("--save", default="logs")                       # pretrain_g.lua:13
+    p.add_argument("--saveFreq", type=int, default=30)             # :14
+    p.add_argument("--epochs", type=int, default=1, help="epochs to play (see the stop-test deviation above)")
+    p.add_argument("--batchSize", type=int, default=128)           # :18
+    p.add_argument("--N_epoch", type=int, default=30)              # :19
+    p.add_argument("--G_L1", type=float, default=0.0)              # :20
+    p.add_argument("--G_L2", type=float, default=0.0)              # :21
+    p.add_argument("--G_clamp", type=float, default=5.0)           # :22
+    p.add_argument("--noiseDim", type=int, default=100)            # :26
+    p.add_argument("--seed", type=int, default=1)                  # :29
+    p.add_argument("--colorSpace", default="rgb", choices=["rgb", "y"])     # :30 (yuv / hsl: the dataset loader, out of scope)
+    p.add_argument("--height", type=int, default=32)               # :31
+    p.add_argument("--width", type=int, default=32)                # :32
+    p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
+    p.add_argument("--compat", action="store_true")
+    p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
+    p.add_argument("--quiet", action="store_true")
+    return p.parse_args(argv)
+
+
+def image_dims(OPT):
+    return (1 if OPT.colorSpace == "y" else 3, OPT.height, OPT.width)       # pretrain_g.lua:49-53
+
+
+def checkpoint_name(dims, noiseDim):
+    """pretrain_g.lua:190 / train.lua:148: g_pretrained_CHANNELSxHEIGHTxWIDTH_ndNOISEDIM.net"""
+    return "g_pretrained_%dx%dx%d_nd%d.net" % (dims[0], dims[1], dims[2], noiseDim)
+
+
+def build(dims, noiseDim, seed):
+    """pretrain_g.lua:82-88: G_AUTOENCODER = Sequential(G_ENCODER, G_DECODER).  No nn.Concat: it compiles as one gr_net."""
+    enc = models.create_G_encoder(dims, noiseDim, True, seed)
+    dec = models.create_G(dims, noiseDim, True, seed + 1)
+    ae = nn.Sequential()
+    ae.add(enc)
+    ae.add(dec)
+    ae.training()
+    return ae
+
+
+class DeviceLoop:
+    """The fast loop: one autoencoder step per batch on device tensors (pretrain_g.lua:148-183 without a host round trip)."""
+
+    def __init__(self, ae, dims, B, hyper):
+        self.ae, self.B, self.hyper, self.t = ae, int(B), hyper, 0
+        self.net = ae.device_net(dims)                 # compiled, parameters uploaded, training mode; no forward (no BatchNorm side effect)
+        self.net.adam_reset()
+        self.ctx = self.net.ctx
+        self.n = self.B * int(np.prod(dims))
+        self.images = None
+        self.grad = self.ctx.malloc(4 * self.n)
+        self.loss = self.ctx.malloc(64)
+
+    def load(self, images):
+        """the epoch's TRAIN_DATA, device-resident (pretrain_g.lua:118)"""
+        images = np.ascontiguousarray(images, np.float32)
+        if self.images is not None:
+            self.ctx.free(self.images)
+        self.images = self.ctx.upload(images)
+
+    def batch(self, b, want_loss=False):
+        x = self.images + 4 * self.n * b
+        self.t += 1
+        self.net.zero_grads()                                             # :151
+        out = self.net.forward_dev(x, self.B)                             # :154
+        self.ctx.mse_dev(out, x, self.n, self.loss, self.grad)            # :155,159  (targets = inputs)
+        self.net.backward_dev(x, self.grad, self.B)                       # :160 (no gradInput)
+        self.net.adam_step(self.hyper, self.t)                            # :163-183 penalty, clamp, optim.adam
+        return float(self.ctx.download(self.loss, (1,), np.float64)[0]) if want_loss else None
+
+    def sync_to_host(self):
+        self.ae.pull_params()                                             # parameters and BatchNorm running statistics
+
+    def close(self):
+        for p in (self.images, self.grad, self.loss):
+            if p:
+                self.ctx.free(p)
+        self.images = self.grad = self.loss = None
+
+
+def compat_epoch(OPT, ae, PARAMETERS, GRAD_PARAMETERS, CRITERION, OPTSTATE, TRAIN_DATA, dims):
+    """pretrain_g.lua:133-185 on host tensors"""
+    B = OPT.batchSize
+    for batchIdx in range(1, OPT.N_epoch + 1):
+        batchStart = (batchIdx - 1) * B
+        inputs = np.ascontiguousarray(TRAIN_DATA[batchStart:batchStart + B], np.float32)     # :144-147
+        targets = inputs.copy()
+
+        def fevalG(x):
+            if x is not PARAMETERS:
+                PARAMETERS[...] = x
+            GRAD_PARAMETERS[...] = 0                                      # :151
+            outputs = ae.forward(inputs).copy()                           # :154
+            f = CRITERION.forward(outputs, targets)                       # :155
+            df_do = CRITERION.backward(outputs, targets)                  # :159
+            ae.backward(inputs, df_do)                                    # :160
+            if OPT.G_L1 != 0 or OPT.G_L2 != 0:                            # :163-170
+                f += OPT.G_L1 * np.abs(PARAMETERS).sum() + OPT.G_L2 * float(np.dot(PARAMETERS, PARAMETERS)) / 2
+                GRAD_PARAMETERS[...] += np.sign(PARAMETERS) * np.float32(OPT.G_L1) + PARAMETERS * np.float32(OPT.G_L2)
+            if OPT.G_clamp != 0:                                          # :173-175
+                np.clip(GRAD_PARAMETERS, -OPT.G_clamp, OPT.G_clamp, out=GRAD_PARAMETERS)
+            return f, GRAD_PARAMETERS
+        optim.adam(fevalG, PARAMETERS, OPTSTATE, model=ae)                # :180
+    return CRITERION.output
+
+
+def save(OPT, ae, dims, epoch):
+    """pretrain_g.lua:187-203: torch.save(<save>/g_pretrained_..., {G = G_AUTOENCODER:get(2), opt = OPT, EPOCH = EPOCH + 1})"""
+    filename = os.path.join(OPT.save, checkpoint_name(dims, OPT.noiseDim))
+    os.makedirs(OPT.save or ".", exist_ok=True)
+    if not OPT.quiet:
+        print("<trainer> saving network to %s" % filename)
+    opt = {k: v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}      # colorSpace rgb | y: train_r --G reads it
+    t7.save_checkpoint(filename, G=ae.get(2), opt=opt, EPOCH=epoch + 1)
+    return filename
+
+
+def main(argv=None):
+    OPT = parse(argv)
+    dims = image_dims(OPT)
+    ctx = L.default_context()
+    ctx.set_conv_mode(OPT.conv_mode)
+    ae = build(dims, OPT.noiseDim, OPT.seed)
+    ae._ctx = ctx
+    if not OPT.quiet:
+        print("G autoencoder:")
+        print(ae)
+        print("Number of free parameters in G (total): %d" % ae._param_count())
+    data = np.load(OPT.data).astype(np.float32) if OPT.data else None
+    nLoad = OPT.N_epoch * OPT.batchSize                                   # :117
+    if OPT.compat:
+        CRITERION = nn.MSECriterion()                                     # :94
+        PARAMETERS, GRAD_PARAMETERS = ae.getParameters()                  # :97
+        OPTSTATE = {}                                                     # :100
+        loop = None
+    else:
+        loop = DeviceLoop(ae, dims, OPT.batchSize, L.Hyper(l1=OPT.G_L1, l2=OPT.G_L2, clamp=OPT.G_clamp))
+    EPOCH, last, path, t0 = 1, None, None, time.perf_counter()
+    try:
+        for _ in range(OPT.epochs):                                       # pretrain_g.lua:112's stop test, not inverted (module docstring)
+            if not OPT.quiet:
+                print("<trainer> Epoch %d" % EPOCH)
+            if data is not None:
+                TRAIN_DATA = data[((EPOCH - 1) * nLoad + np.arange(nLoad)) % len(data)]
+            else:
+                TRAIN_DATA = synthetic_images(nLoad, dims, OPT.seed * 7919 + EPOCH * 3)
+            if loop is None:
+                last = compat_epoch(OPT, ae, PARAMETERS, GRAD_PARAMETERS, CRITERION, OPTSTATE, TRAIN_DATA, dims)
+            else:
+                loop.load(TRAIN_DATA)
+                for b in range(OPT.N_epoch):
+                    res = loop.batch(b, want_loss=b == OPT.N_epoch - 1)
+                    if res is not None:
+                        last = res
+            if not OPT.quiet:
+                print("<trainer> last batch loss: %.4f" % last)
+            if EPOCH % OPT.saveFreq == 0:                                 # :187
+                if loop is not None:
+                    loop.sync_to_host()
+                else:
+                    ae.pull_params()
+                path = save(OPT, ae, dims, EPOCH)
+            EPOCH += 1
+        if loop is not None:
+            loop.sync_to_host()
+        else:
+            ae.pull_params()
+        path = save(OPT, ae, dims, EPOCH - 1)                              # deviation: a final save, as ganrev.train
+        if not OPT.quiet:
+            print("<trainer> %.1f images/s" % (OPT.epochs * nLoad / (time.perf_counter() - t0)))
+    finally:
+        if loop is not None:
+            loop.close()
+    return dict(path=path, last_loss=last, model=ae, epoch=EPOCH - 1)
+
+
+if __name__ == "__main__":
+    main()

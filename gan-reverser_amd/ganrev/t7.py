@@ -336,6 +336,10 @@ def to_model(obj):
         return nn.SpatialDropout(f.get("p", 0.5))
     if t in ("nn.SpatialMaxPooling", "cudnn.SpatialMaxPooling"):
         return nn.SpatialMaxPooling(f["kW"], f["kH"], f.get("dW"), f.get("dH"), f.get("padW", 0), f.get("padH", 0))
+    if t in ("nn.SpatialAveragePooling", "cudnn.SpatialAveragePooling"):
+        if f.get("ceil_mode", False) or not f.get("count_include_pad", True) or not f.get("divide", True):
+            raise ValueError(f"{t}: only floor mode, count_include_pad and divide are implemented")
+        return nn.SpatialAveragePooling(f["kW"], f["kH"], f.get("dW", 1), f.get("dH", 1), f.get("padW", 0), f.get("padH", 0))
     if t == "nn.SpatialUpSamplingNearest":
         return nn.SpatialUpSamplingNearest(f["scale_factor"])
     if t == "nn.View":
@@ -381,6 +385,8 @@ def from_model(model):
         f.update(p=model.p, noise=empty)
     elif isinstance(model, nn.SpatialMaxPooling):
         f.update(kW=2, kH=2, dW=2, dH=2, padW=0, padH=0, ceil_mode=False, indices=empty)
+    elif isinstance(model, nn.SpatialAveragePooling):
+        f.update(kW=2, kH=2, dW=2, dH=2, padW=0, padH=0, ceil_mode=False, count_include_pad=True, divide=True)
     elif isinstance(model, nn.SpatialUpSamplingNearest):
         f.update(scale_factor=2, inputSize=np.zeros(4, np.int64), outputSize=np.zeros(4, np.int64))
     elif isinstance(model, nn.View):
@@ -399,7 +405,7 @@ def load_checkpoint(path):
         if isinstance(v, TorchObject) and v.typename == "nn.Sequential":
             try:
                 out[k] = to_model(v)
-            except Exception as e:          # a layer this path has no kernel for (e.g. SpatialAveragePooling of create_D_default): keep the raw tree
+            except Exception as e:          # a layer this path has no kernel for (e.g. a 3x3 SpatialAveragePooling, create_G4's layers): keep the raw tree
                 out[k] = v
                 out.setdefault("_unconverted", {})[k] = str(e)
         else:

@@ -1,6 +1,8 @@
 """Mirror of the reference's train.lua main loop (train.lua:125-257): build or load G and D, then per epoch load N_epoch *
 batchSize / 2 * D_iterations training images (train.lua:214-216), play adversarial.train on them and save
 {D, G, opt, epoch} as a Torch7 checkpoint (train.lua:241-257) - the file train_r.lua:68 and apply_r.lua:62 read G from.
+Without --network, G starts from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (ganrev.pretrain_g) when that file exists and
+--nopretraining is not given (train.lua:148-161).
 
     python -m ganrev.train --epochs 5 --N_epoch 30 --batchSize 32 --save logs [--data images.npy] [--compat]
 
@@ -27,6 +29,8 @@ def parse(argv=None):
     p.add_argument("--save", default="logs")                       # train.lua:13
     p.add_argument("--saveFreq", type=int, default=30)             # train.lua:14
     p.add_argument("--network", default="")                        # train.lua:15: continue from this checkpoint
+    p.add_argument("--G_pretrained_dir", default="logs")            # train.lua:20: where pretrain_g.lua saved G
+    p.add_argument("--nopretraining", action="store_true")          # train.lua:21
     p.add_argument("--batchSize", type=int, default=32)
     p.add_argument("--N_epoch", type=int, default=30)
     p.add_argument("--epochs", type=int, default=1, help="epochs to play (train.lua runs until interrupted)")
@@ -68,6 +72,27 @@ def synthetic_images(n, dims, seed):
     return np.ascontiguousarray(np.broadcast_to(img, (n, c, h, w)), dtype=np.float32)
 
 
+def pretrained_G_path(OPT, dims):
+    """train.lua:148-149: <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net when it exists and --nopretraining is not given, else None"""
+    path = os.path.join(OPT.G_pretrained_dir, "g_pretrained_%dx%dx%d_nd%d.net" % (dims[0], dims[1], dims[2], OPT.noiseDim))
+    return path if not OPT.nopretraining and os.path.isfile(path) else None
+
+
+def create_or_load_G(OPT, dims):
+    """train.lua:148-161: pretrain_g.lua's decoder in training mode, or a fresh create_G"""
+    path = pretrained_G_path(OPT, dims)
+    if path is None:
+        if not OPT.quiet:
+            print("<trainer> Note: Did not find pretrained G")
+        return models.create_G(dims, OPT.noiseDim, True, OPT.seed + 1)
+    if not OPT.quiet:
+        print("<trainer> loading pretrained G...")
+    ck = t7.load_checkpoint(path)
+    if "_unconverted" in ck:
+        raise L.GanrevError(f"{path}: {ck['_unconverted']}")
+    return ck["G"].training()
+
+
 def save(OPT, env, epoch, quiet=True):
     """train.lua:236-257: logs/adversarial.net (the previous file moved to .old), {D, G, opt, epoch}."""
     filename = os.path.join(OPT.save, "adversarial.net")
@@ -95,7 +120,7 @@ def main(argv=None):
         MODEL_D, MODEL_G, epoch0 = ck["D"], ck["G"], int(ck.get("epoch", 0)) + 1      # train.lua:113  EPOCH = tmp.epoch + 1
     else:                                                             # train.lua:143,160
         MODEL_D = models.create_D(dims, True, OPT.seed)
-        MODEL_G = models.create_G(dims, OPT.noiseDim, True, OPT.seed + 1)
+        MODEL_G = create_or_load_G(OPT, dims)
     env = adversarial.make_env(MODEL_G, MODEL_D, dims, **{k: getattr(OPT, k) for k in
                                ("batchSize", "N_epoch", "noiseDim", "noiseMethod", "G_L1", "G_L2", "D_L1", "D_L2", "D_iterations", "G_iterations",
                                 "D_clamp", "G_clamp", "D_optmethod", "G_optmethod", "seed", "D_sgd_lr", "G_sgd_lr", "D_sgd_momentum", "G_sgd_momentum")})

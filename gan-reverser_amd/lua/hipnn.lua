@@ -85,7 +85,7 @@ local function check(rc, what) if rc ~= 0 then error(what .. ': ' .. ffi.string(
 
 -- kind numbers of include/ganrev.h
 local K = {CONV3=1, BN=2, ELU=3, RELU=4, LEAKYRELU=5, SIGMOID=6, TANH=7, DROPOUT=8, SPATIAL_DROPOUT=9,
-           MAXPOOL2=10, UPSAMPLE2=11, VIEW=12, LINEAR=13, FULLCONV3=14, CONVK=15, PRELU=16}
+           MAXPOOL2=10, UPSAMPLE2=11, VIEW=12, LINEAR=13, FULLCONV3=14, CONVK=15, PRELU=16, AVGPOOL2=17}
 
 -- nn module -> descriptor rows, in nn.Sequential order (models.lua:104-143, 389-464)
 local function describe(m, out, leaves)
@@ -112,6 +112,9 @@ local function describe(m, out, leaves)
       d.flags = (m.v2 and 1 or 0) + ((rawget(m, 'evaluate') ~= nil) and 2 or 0)   -- models.lua:404 overrides evaluate
    elseif t == 'nn.SpatialDropout' then d.kind, d.p = K.SPATIAL_DROPOUT, m.p
    elseif t == 'nn.SpatialMaxPooling' then assert(m.kW == 2 and m.kH == 2 and m.dW == 2); d.kind = K.MAXPOOL2
+   elseif t == 'nn.SpatialAveragePooling' or t == 'cudnn.SpatialAveragePooling' then   -- models.lua:71,235,242,249,348-363
+      assert(m.kW == 2 and m.kH == 2 and m.dW == 2 and m.dH == 2 and m.padW == 0 and m.padH == 0 and not m.ceil_mode,
+             'hipnn: only SpatialAveragePooling(2,2,2,2)'); d.kind = K.AVGPOOL2
    elseif t == 'nn.SpatialUpSamplingNearest' then assert(m.scale_factor == 2); d.kind = K.UPSAMPLE2
    elseif t == 'nn.View' then
       d.kind = K.VIEW; d.a = m.size[1]; d.b = m.size:size() > 1 and m.size[2] or 1; d.c = m.size:size() > 2 and m.size[3] or 1
