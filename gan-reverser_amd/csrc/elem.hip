@@ -8,6 +8,7 @@
 //   nn.Dropout / nn.SpatialDropout / nn.SpatialMaxPooling  models.lua:402-405,412,439,422,440
 //   nn.SpatialAveragePooling(2,2,2,2)                      models.lua:71,235,242,249,348-363
 //   nn.MSECriterion                                        train_r.lua:119,147,150
+//   NN_UTILS.switchColorSpace / toRgb / rgbToColorSpace    utils/nn_utils.lua:133-246
 //   fevalR penalty+clamp and optim.adam                    train_r.lua:153-165,170
 #include "kernels.h"
 #include <type_traits>
@@ -1868,6 +1869,134 @@ void launch_zero_regions(const ZeroJobs& jobs, hipStream_t s) {
 void launch_scale_copy(const float* src, float* dst, long n, float scale, hipStream_t s) {
   long blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(scale_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, dst, n, scale);
+}
+
+// ------------------------------------------------------------------ NN_UTILS.switchColorSpace (utils/nn_utils.lua:133-246)
+// toRgb(from) then rgbToColorSpace(to) in ONE launch: the rgb intermediate stays in registers.  Each of the two steps rounds to
+// fp32 where the two-step composition would (this file is compiled with -ffp-contract=off and `/` is the correctly rounded
+// division), so the fused result is bit-identical to from -> rgb followed by rgb -> to.  The per-pixel arithmetic of the yuv and
+// hsl pairs restates Torch's un-vendored `image` rock from memory; rgb -> y is nn_utils.rgb2y's own mixture.
+// max / min are compare-selects, not v_max_f32 / v_min_f32: the result for (+0, -0) is then the one the operation order states.
+struct Px3 { float a, b, c; };
+constexpr float CS_1_3 = 1.0f / 3.0f, CS_1_6 = 1.0f / 6.0f, CS_2_3 = 2.0f / 3.0f;      // rounded to fp32 once
+__device__ __forceinline__ float cs_hue(float p, float q, float t) {
+  if (t < 0.f) t = t + 1.f;
+  if (t > 1.f) t = t - 1.f;
+  if (t < CS_1_6) return p + ((q - p) * 6.f) * t;
+  if (t < 0.5f) return q;
+  if (t < CS_2_3) return p + ((q - p) * (CS_2_3 - t)) * 6.f;
+  return p;
+}
+template <int FROM>
+__device__ __forceinline__ Px3 cs_to_rgb(Px3 x) {
+  if (FROM == CS_Y) return Px3{x.a, x.a, x.a};                          // torch.repeatTensor(images, 1, 3, 1, 1)
+  if (FROM == CS_YUV) {
+    Px3 o;
+    o.a = x.a + 1.13983f * x.c;
+    o.b = (x.a - 0.39465f * x.b) - 0.58060f * x.c;
+    o.c = x.a + 2.03211f * x.b;
+    return o;
+  }
+  if (FROM == CS_HSL) {
+    const float h = x.a, s = x.b, l = x.c;
+    if (s == 0.f) return Px3{l, l, l};
+    const float q = l < 0.5f ? l * (1.f + s) : (l + s) - l * s;
+    const float p = 2.f * l - q;
+    return Px3{cs_hue(p, q, h + CS_1_3), cs_hue(p, q, h), cs_hue(p, q, h - CS_1_3)};
+  }
+  return x;
+}
+template <int TO>
+__device__ __forceinline__ Px3 cs_from_rgb(Px3 x) {
+  const float r = x.a, g = x.b, b = x.c;
+  if (TO == CS_Y) return Px3{((0.f + 0.21f * r) + 0.72f * g) + 0.07f * b, 0.f, 0.f};      // z:add(0.21, r):add(0.72, g):add(0.07, b)
+  if (TO == CS_YUV) {
+    Px3 o;
+    o.a = ((0.f + 0.299f * r) + 0.587f * g) + 0.114f * b;
+    o.b = ((0.f - 0.14713f * r) - 0.28886f * g) + 0.436f * b;
+    o.c = ((0.f + 0.615f * r) - 0.51499f * g) - 0.10001f * b;
+    return o;
+  }
+  if (TO == CS_HSL) {
+    float mx = r > g ? r : g; mx = mx > b ? mx : b;
+    float mn = r < g ? r : g; mn = mn < b ? mn : b;
+    if (mx == mn) return Px3{0.f, 0.f, mx};
+    const float d = mx - mn;
+    const float l = (mx + mn) / 2.f;
+    const float s = l > 0.5f ? d / ((2.f - mx) - mn) : d / (mx + mn);
+    float h;
+    if (mx == r) h = (g - b) / d + (g < b ? 6.f : 0.f);
+    else if (mx == g) h = (b - r) / d + 2.f;
+    else h = (r - g) / d + 4.f;
+    return Px3{h / 6.f, s, l};
+  }
+  return x;
+}
+// scalar form: one thread per pixel, any h * w and any alignment
+template <int FROM, int TO>
+__global__ __launch_bounds__(256) void colorspace_kernel(const float* __restrict__ in, float* __restrict__ out, long npix, long hw) {
+  constexpr int CI = FROM == CS_Y ? 1 : 3, CO = TO == CS_Y ? 1 : 3;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
+    const long n = p / hw, i = p - n * hw;
+    const float* src = in + n * CI * hw + i;
+    Px3 x{src[0], 0.f, 0.f};
+    if (CI == 3) { x.b = src[hw]; x.c = src[2 * hw]; }
+    const Px3 y = cs_from_rgb<TO>(cs_to_rgb<FROM>(x));
+    float* dst = out + n * CO * hw + i;
+    dst[0] = y.a;
+    if (CO == 3) { dst[hw] = y.b; dst[2 * hw] = y.c; }
+  }
+}
+// vector form: one thread per four consecutive pixels of a plane, a 16-byte load / store per plane (h * w % 4 == 0 and both
+// pointers 16-byte aligned: a group never straddles two images and every plane starts on a 16-byte boundary)
+template <int FROM, int TO>
+__global__ __launch_bounds__(256) void colorspace_kernel_v4(const float* __restrict__ in, float* __restrict__ out, long ngroups, long hw4) {
+  constexpr int CI = FROM == CS_Y ? 1 : 3, CO = TO == CS_Y ? 1 : 3;
+  const float4* in4 = reinterpret_cast<const float4*>(in);
+  float4* out4 = reinterpret_cast<float4*>(out);
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < ngroups; p += (long)gridDim.x * blockDim.x) {
+    const long n = p / hw4, i = p - n * hw4;
+    const float4* src = in4 + n * CI * hw4 + i;
+    const float4 xa = src[0];
+    float4 xb = xa, xc = xa;
+    if (CI == 3) { xb = src[hw4]; xc = src[2 * hw4]; }
+    const Px3 y0 = cs_from_rgb<TO>(cs_to_rgb<FROM>(Px3{xa.x, xb.x, xc.x}));
+    const Px3 y1 = cs_from_rgb<TO>(cs_to_rgb<FROM>(Px3{xa.y, xb.y, xc.y}));
+    const Px3 y2 = cs_from_rgb<TO>(cs_to_rgb<FROM>(Px3{xa.z, xb.z, xc.z}));
+    const Px3 y3 = cs_from_rgb<TO>(cs_to_rgb<FROM>(Px3{xa.w, xb.w, xc.w}));
+    float4* dst = out4 + n * CO * hw4 + i;
+    dst[0] = make_float4(y0.a, y1.a, y2.a, y3.a);
+    if (CO == 3) { dst[hw4] = make_float4(y0.b, y1.b, y2.b, y3.b); dst[2 * hw4] = make_float4(y0.c, y1.c, y2.c, y3.c); }
+  }
+}
+template <int FROM, int TO>
+static void colorspace_launch(const float* in, float* out, long batch, long hw, hipStream_t s) {
+  const long npix = batch * hw;
+  const bool v4 = hw % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+  const long work = v4 ? npix / 4 : npix;
+  long blocks = (work + 255) / 256; if (blocks > 2048) blocks = 2048;
+  const int ci = FROM == CS_Y ? 1 : 3, co = TO == CS_Y ? 1 : 3;
+  KtScope kt(v4 ? "colorspace_kernel_v4" : "colorspace_kernel", 0.0, 4.0 * (double)(ci + co) * (double)npix, s);
+  if (v4) hipLaunchKernelGGL((colorspace_kernel_v4<FROM, TO>), dim3((unsigned)blocks), dim3(256), 0, s, in, out, work, hw / 4);
+  else hipLaunchKernelGGL((colorspace_kernel<FROM, TO>), dim3((unsigned)blocks), dim3(256), 0, s, in, out, npix, hw);
+}
+template <int FROM>
+static void colorspace_launch_to(const float* in, int to, float* out, long batch, long hw, hipStream_t s) {
+  switch (to) {
+    case CS_RGB: if (FROM != CS_RGB) colorspace_launch<FROM, CS_RGB>(in, out, batch, hw, s); break;      // rgb -> rgb: the caller copies
+    case CS_Y: colorspace_launch<FROM, CS_Y>(in, out, batch, hw, s); break;
+    case CS_YUV: colorspace_launch<FROM, CS_YUV>(in, out, batch, hw, s); break;
+    default: colorspace_launch<FROM, CS_HSL>(in, out, batch, hw, s); break;
+  }
+}
+void launch_colorspace(const float* in, int from, int to, long batch, long hw, float* out, hipStream_t s) {
+  if (batch <= 0 || hw <= 0) return;
+  switch (from) {
+    case CS_RGB: colorspace_launch_to<CS_RGB>(in, to, out, batch, hw, s); break;
+    case CS_Y: colorspace_launch_to<CS_Y>(in, to, out, batch, hw, s); break;
+    case CS_YUV: colorspace_launch_to<CS_YUV>(in, to, out, batch, hw, s); break;
+    default: colorspace_launch_to<CS_HSL>(in, to, out, batch, hw, s); break;
+  }
 }
 
 }  // namespace gr

@@ -386,6 +386,10 @@ void launch_spread_verdict(unsigned* chmax, int C, unsigned* word, int side, hip
 void launch_pair_spread(const float* a, const float* b, int C, unsigned* word, hipStream_t s);
 void launch_l2_distance_rows(const float* a, const float* b, long n, long d, double* out, hipStream_t s);
 void launch_scale_copy(const float* src, float* dst, long n, float scale, hipStream_t s);
+// NN_UTILS.switchColorSpace (utils/nn_utils.lua:133-246): in [batch x (1|3) x hw] -> out [batch x (1|3) x hw], from / to = GR_CS_*; one launch,
+// none for rgb -> rgb.  A 16-byte form when hw % 4 == 0 and both pointers are 16-byte aligned, a scalar form otherwise.
+enum { CS_RGB = 0, CS_Y = 1, CS_YUV = 2, CS_HSL = 3 };
+void launch_colorspace(const float* in, int from, int to, long batch, long hw, float* out, hipStream_t s);
 // several regions zeroed by ONE launch (each a multiple of 16 bytes, 16-byte aligned): the fills a training step needs - the scale slots of both
 // nets, the gradient vector - were three hipMemsetAsync kernels of ~6 us each at batch 256
 struct ZeroJobs { void* ptr[4]; long n16[4]; int n; };

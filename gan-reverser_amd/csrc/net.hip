@@ -1710,6 +1710,44 @@ extern "C" int gr_add_dev(gr_ctx* c, float* y, const float* x, int64_t n) {
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ NN_UTILS.switchColorSpace (utils/nn_utils.lua:133-246)
+static int colorspace_check(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, const float* out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!in || !out) return fail(c, GR_ERR_INVALID, "gr_colorspace: null pointer");
+  if (from < GR_CS_RGB || from > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_colorspace: unknown color space <from>: %d", from);
+  if (to < GR_CS_RGB || to > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_colorspace: unknown color space <to>: %d", to);
+  if (batch <= 0 || h <= 0 || w <= 0) return fail(c, GR_ERR_INVALID, "gr_colorspace: batch %lld, h %d, w %d must be positive", (long long)batch, h, w);
+  if (in == out && (from == GR_CS_Y) != (to == GR_CS_Y)) return fail(c, GR_ERR_INVALID, "gr_colorspace: in place needs equal plane counts (from %d, to %d)", from, to);
+  return GR_OK;
+}
+extern "C" int gr_colorspace_dev(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, float* out) {
+  int r = colorspace_check(c, in, from, to, batch, h, w, out); if (r) return r;
+  const long hw = (long)h * w;
+  if (from == GR_CS_RGB && to == GR_CS_RGB) {
+    if (in != out) HIPCHK(c, hipMemcpyAsync(out, in, sizeof(float) * 3 * (size_t)batch * hw, hipMemcpyDeviceToDevice, c->stream));
+    return GR_OK;
+  }
+  launch_colorspace(in, from, to, (long)batch, hw, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_colorspace_host(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, float* out) {
+  int r = colorspace_check(c, in, from, to, batch, h, w, out); if (r) return r;
+  const size_t hw = (size_t)h * w, nin = (from == GR_CS_Y ? 1 : 3) * (size_t)batch * hw, nout = (to == GR_CS_Y ? 1 : 3) * (size_t)batch * hw;
+  if (from == GR_CS_RGB && to == GR_CS_RGB) {
+    if (in != out) memmove(out, in, sizeof(float) * nin);
+    return GR_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nin_pad = (nin + 3) & ~(size_t)3;                       // keeps the output 16-byte aligned behind the input
+  r = ensure_ws(c, sizeof(float) * (nin_pad + nout)); if (r) return r;
+  float* din = (float*)c->ws; float* dout = din + nin_pad;
+  HIPCHK(c, hipMemcpyAsync(din, in, sizeof(float) * nin, hipMemcpyHostToDevice, c->stream));
+  launch_colorspace(din, from, to, (long)batch, (long)hw, dout, c->stream); LAUNCHCHK(c);
+  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ optimiser
 static AdamConsts adam_consts(const gr_hyper* h, int t) {
   AdamConsts k{};

@@ -33,6 +33,8 @@ CONV3, BN, ELU, RELU, LEAKYRELU, SIGMOID, TANH, DROPOUT, SPATIAL_DROPOUT, MAXPOO
 CONVK, PRELU = 15, 16       # the D network's extra module types (models.lua:272-337)
 AVGPOOL2 = 17               # nn.SpatialAveragePooling(2,2,2,2) (models.lua:71,235,242,249,348-363)
 DROPOUT_V2, DROPOUT_ALWAYS_ON = 1, 2
+GR_CS_RGB, GR_CS_Y, GR_CS_YUV, GR_CS_HSL = 0, 1, 2, 3      # gr_colorspace_*: the reference's four colour spaces (train.lua:45, dataset.lua:27-33)
+COLOR_SPACES = {"rgb": GR_CS_RGB, "y": GR_CS_Y, "yuv": GR_CS_YUV, "hsl": GR_CS_HSL}
 COMM_ID_BYTES = 128
 
 
@@ -133,6 +135,8 @@ _SIGS = {
     "gr_fill_uniform_dev": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, C.c_uint64]),
     "gr_copy2d_dev": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64]),
     "gr_add_dev": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "gr_colorspace_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P]),
+    "gr_colorspace_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P]),
     "gr_conv3_forward_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gr_conv3_backward_data_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gr_conv3_backward_weight_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -239,6 +243,22 @@ class Context:
 
     def add(self, y, x, n):
         self.check(self.lib.gr_add_dev(self.h, _ptr(y), _ptr(x), int(n)), "gr_add_dev")
+
+    def colorspace_dev(self, in_dev, from_, to, batch, h, w, out_dev):
+        """NN_UTILS.switchColorSpace (utils/nn_utils.lua:133-246) on device tensors [batch x (1|3) x h x w]; from_ / to = GR_CS_*.  One
+        launch on the context's stream, none for rgb -> rgb (a copy when the pointers differ)."""
+        self.check(self.lib.gr_colorspace_dev(self.h, _ptr(in_dev), int(from_), int(to), int(batch), int(h), int(w), _ptr(out_dev)), "gr_colorspace_dev")
+
+    def colorspace(self, images, from_, to):
+        """the same on a host array [batch x (1|3) x h x w] -> a new host array [batch x (1|3) x h x w] (gr_colorspace_host)"""
+        images = f32(images)
+        planes = lambda cs: 1 if int(cs) == GR_CS_Y else 3
+        if images.ndim != 4 or (0 <= int(from_) <= 3 and images.shape[1] != planes(from_)):
+            raise GanrevError(f"colorspace: images {images.shape} are not [batch x {planes(from_)} x h x w]")
+        b, _, h, w = images.shape
+        out = np.empty((b, planes(to) if 0 <= int(to) <= 3 else 3, h, w), np.float32)
+        self.check(self.lib.gr_colorspace_host(self.h, _ptr(images), int(from_), int(to), b, h, w, _ptr(out)), "gr_colorspace_host")
+        return out
 
     def bce_dev(self, x, t, n, loss_dev, grad_dev=None):
         self.check(self.lib.gr_bce_dev(self.h, _ptr(x), _ptr(t), int(n), _ptr(loss_dev), _ptr(grad_dev)), "gr_bce_dev")

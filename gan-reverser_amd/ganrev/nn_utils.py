@@ -1,4 +1,4 @@
-"""Mirror of the two hot-path helpers of utils/nn_utils.lua."""
+"""Mirror of the hot-path helpers of utils/nn_utils.lua and of its colour-space conversions (:133-263, :324-379)."""
 import numpy as np
 
 from . import _lib as L
@@ -108,3 +108,86 @@ def sortImagesByPrediction(model_d, images, ascending, nbMaxOut, batchSize):
     predictions = forwardBatched(model_d, images, batchSize).reshape(len(images), -1)[:, 0]
     order = predictionOrder(predictions, ascending, nbMaxOut)
     return images[order], predictions[order]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Colour spaces (utils/nn_utils.lua:133-263).  Every conversion is one gr_colorspace_* call: a host array goes through
+# gr_colorspace_host and comes back as a host array, a DeviceTensor goes through gr_colorspace_dev and comes back as a DeviceTensor.
+def _cs(name, which):
+    if name not in L.COLOR_SPACES:
+        raise ValueError(f"Unknown color space <{which}>: '{name}'")        # utils/nn_utils.lua:165
+    return L.COLOR_SPACES[name]
+
+
+def _convert(images, from_, to):
+    f, t = _cs(from_, "from"), _cs(to, "to")
+    if f == L.GR_CS_RGB and t == L.GR_CS_RGB:
+        return images                                                     # :148-149, :192-193: the tensor itself
+    planes = 1 if t == L.GR_CS_Y else 3
+    if isinstance(images, DeviceTensor):
+        b, c, h, w = images.shape
+        if c != (1 if f == L.GR_CS_Y else 3):
+            raise ValueError(f"'{from_}' images have {1 if f == L.GR_CS_Y else 3} channel(s), not {c}")
+        out = DeviceTensor(images.ctx, (b, planes, h, w))
+        images.ctx.colorspace_dev(images.ptr, f, t, b, h, w, out.ptr)
+        return out
+    return L.default_context().colorspace(toImageTensor(images), f, t)
+
+
+def toImageTensor(imageList):
+    """utils/nn_utils.lua:269-307 without forceChannel: a list of [C x H x W] images becomes one [N x C x H x W] tensor"""
+    return np.ascontiguousarray(imageList, dtype=np.float32)
+
+
+def toBatch(image):
+    """utils/nn_utils.lua:248-263: a batch of one"""
+    return np.asarray(image)[None]
+
+
+def toRgb(images, from_):
+    """utils/nn_utils.lua:146-167"""
+    return _convert(images, from_, "rgb")
+
+
+def rgbToColorSpace(images, colorSpace):
+    """utils/nn_utils.lua:191-217; an unknown target prints the reference's warning and returns None (:214)"""
+    if colorSpace not in L.COLOR_SPACES:
+        print("[WARNING] unknown color space in rgbToColorSpace: '" + str(colorSpace) + "'")
+        return None
+    return _convert(images, "rgb", colorSpace)
+
+
+def switchColorSpace(images, from_, to):
+    """utils/nn_utils.lua:133-137: toRgb then rgbToColorSpace, as ONE launch (the rgb intermediate is never written; bit-identical to
+    the two calls).  Only rgb -> rgb passes through: y -> y, yuv -> yuv and hsl -> hsl go through rgb, as the reference does."""
+    _cs(from_, "from")
+    if to not in L.COLOR_SPACES:
+        return rgbToColorSpace(images, to)
+    return _convert(images, from_, to)
+
+
+def switchColorSpaceSingle(image, from_, to):
+    """utils/nn_utils.lua:139-144"""
+    images = switchColorSpace(toBatch(image), from_, to)
+    return None if images is None else images[0]
+
+
+def rgb2y(im, threeChannels=False):
+    """utils/nn_utils.lua:221-246: one [3 x H x W] image -> [1 x H x W] (or the plane three times) by 0.21 r + 0.72 g + 0.07 b"""
+    im = np.asarray(im, dtype=np.float32)
+    if im.shape[0] != 3:
+        print("<error> expected 3 channels")                              # :224-227
+        return im
+    z = _convert(toBatch(im), "rgb", "y")[0]
+    return np.repeat(z, 3, axis=0) if threeChannels else z
+
+
+def normalize(data, mean_=None, std_=None):
+    """utils/nn_utils.lua:324-379: in place from [0, 1] to [-1, 1] (x * 2 - 1, clamped); returns the reference's dummy (0.5, 0.5).
+    NORMALIZE is false in every reference script, so this has no kernel: host numpy on a host array or a list of them."""
+    for i in range(len(data)):
+        d = data[i]
+        d *= 2
+        d += -1.0
+        np.clip(d, -1.0, 1.0, out=d)
+    return 0.5, 0.5

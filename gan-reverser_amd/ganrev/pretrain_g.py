@@ -5,7 +5,9 @@ nn.MSECriterion, the L1 / L2 penalty, the gradient clamp and optim.adam (pretrai
     python -m ganrev.pretrain_g --epochs 2 --N_epoch 30 --batchSize 128 --save logs [--data images.npy] [--compat]
 
 Same option names and defaults as pretrain_g.lua:12-35 for what is mirrored.  Training images come from --data (an
-[N x C x H x W] float32 .npy in [0, 1]) or, without it, from train.synthetic_images (the dataset loader is out of scope).
+[N x C x H x W] float32 .npy in [0, 1]) or, without it, from train.synthetic_images (the dataset loader is out of scope).  With
+--colorSpace yuv | hsl the images are rgb and are converted once per epoch load, on the device (nn_utils.rgbToColorSpace, as
+dataset.lua:153 does per image); three-channel --data with --colorSpace y is converted the same way.
 
 Two loops, as in ganrev.train_r / ganrev.train:
   fast (default)  - the epoch's images device-resident; per batch forward_dev -> gr_mse_dev -> backward_dev -> gr_adam_step
@@ -24,7 +26,7 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import models, nn, optim, t7
+from . import models, nn, nn_utils, optim, t7
 from .train import synthetic_images
 
 
@@ -40,7 +42,7 @@ def parse(argv=None):
     p.add_argument("--G_clamp", type=float, default=5.0)           # :22
     p.add_argument("--noiseDim", type=int, default=100)            # :26
     p.add_argument("--seed", type=int, default=1)                  # :29
-    p.add_argument("--colorSpace", default="rgb", choices=["rgb", "y"])     # :30 (yuv / hsl: the dataset loader, out of scope)
+    p.add_argument("--colorSpace", default="rgb", choices=["rgb", "y", "yuv", "hsl"])      # :30 (yuv / hsl / y from rgb images: nn_utils.rgbToColorSpace)
     p.add_argument("--height", type=int, default=32)               # :31
     p.add_argument("--width", type=int, default=32)                # :32
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
@@ -52,6 +54,11 @@ def parse(argv=None):
 
 def image_dims(OPT):
     return (1 if OPT.colorSpace == "y" else 3, OPT.height, OPT.width)       # pretrain_g.lua:49-53
+
+
+def needs_conversion(images, colorSpace):
+    """rgb images (three channels) that --colorSpace yuv | hsl | y asks to see in another space"""
+    return colorSpace != "rgb" and images.shape[1] == 3
 
 
 def checkpoint_name(dims, noiseDim):
@@ -83,12 +90,21 @@ class DeviceLoop:
         self.grad = self.ctx.malloc(4 * self.n)
         self.loss = self.ctx.malloc(64)
 
-    def load(self, images):
-        """the epoch's TRAIN_DATA, device-resident (pretrain_g.lua:118)"""
+    def load(self, images, colorSpace="rgb"):
+        """the epoch's TRAIN_DATA, device-resident (pretrain_g.lua:118); rgb images are converted to colorSpace there (dataset.lua:153)"""
         images = np.ascontiguousarray(images, np.float32)
         if self.images is not None:
             self.ctx.free(self.images)
         self.images = self.ctx.upload(images)
+        if needs_conversion(images, colorSpace):
+            n, _, h, w = images.shape
+            if colorSpace == "y":             # three planes in, one out: a buffer of its own
+                rgb, self.images = self.images, self.ctx.malloc(4 * n * h * w)
+                self.ctx.colorspace_dev(rgb, L.GR_CS_RGB, L.GR_CS_Y, n, h, w, self.images)
+                self.ctx.synchronize()
+                self.ctx.free(rgb)
+            else:                             # yuv / hsl: in place
+                self.ctx.colorspace_dev(self.images, L.GR_CS_RGB, L.COLOR_SPACES[colorSpace], n, h, w, self.images)
 
     def batch(self, b, want_loss=False):
         x = self.images + 4 * self.n * b
@@ -142,7 +158,7 @@ def save(OPT, ae, dims, epoch):
     os.makedirs(OPT.save or ".", exist_ok=True)
     if not OPT.quiet:
         print("<trainer> saving network to %s" % filename)
-    opt = {k: v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}      # colorSpace rgb | y: train_r --G reads it
+    opt = {k: v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}      # colorSpace: train_r --G reads it
     t7.save_checkpoint(filename, G=ae.get(2), opt=opt, EPOCH=epoch + 1)
     return filename
 
@@ -177,9 +193,11 @@ def main(argv=None):
             else:
                 TRAIN_DATA = synthetic_images(nLoad, dims, OPT.seed * 7919 + EPOCH * 3)
             if loop is None:
+                if needs_conversion(TRAIN_DATA, OPT.colorSpace):
+                    TRAIN_DATA = nn_utils.rgbToColorSpace(np.ascontiguousarray(TRAIN_DATA, np.float32), OPT.colorSpace)
                 last = compat_epoch(OPT, ae, PARAMETERS, GRAD_PARAMETERS, CRITERION, OPTSTATE, TRAIN_DATA, dims)
             else:
-                loop.load(TRAIN_DATA)
+                loop.load(TRAIN_DATA, OPT.colorSpace)
                 for b in range(OPT.N_epoch):
                     res = loop.batch(b, want_loss=b == OPT.N_epoch - 1)
                     if res is not None:

@@ -8,7 +8,9 @@ Without --network, G starts from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (
 
 Same option names and defaults as train.lua:12-60 for what is mirrored.  The dataset loader, normalisation, plots / `display`
 and image grids are out of scope: training images come from --data (an [N x C x H x W] float32 .npy
-in [0, 1]) or, without it, from a synthetic generator, which is what makes the loop runnable here.
+in [0, 1]) or, without it, from a synthetic generator, which is what makes the loop runnable here.  --colorSpace takes the
+reference's rgb | yuv | hsl | y (train.lua:45) besides gray (= y, one channel): three-channel rgb images are converted with
+nn_utils.rgbToColorSpace once per epoch load.
 
 Two loops, as in ganrev.train_r:
   fast (default)  - adversarial.DeviceGame: every batch device-resident, parameters pulled to the host only before a save;
@@ -21,7 +23,7 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import adversarial, models, synth, t7
+from . import adversarial, models, nn_utils, synth, t7
 
 
 def parse(argv=None):
@@ -52,7 +54,7 @@ def parse(argv=None):
     p.add_argument("--noiseMethod", default="normal", choices=["normal", "uniform"])
     p.add_argument("--height", type=int, default=32)
     p.add_argument("--width", type=int, default=32)
-    p.add_argument("--colorSpace", default="gray", choices=["gray", "rgb"])
+    p.add_argument("--colorSpace", default="gray", choices=["gray", "rgb", "y", "yuv", "hsl"])      # train.lua:45 rgb|yuv|hsl|y; gray = y
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
@@ -109,7 +111,7 @@ def save(OPT, env, epoch, quiet=True):
 
 def main(argv=None):
     OPT = parse(argv)
-    dims = (3 if OPT.colorSpace == "rgb" else 1, OPT.height, OPT.width)
+    dims = (1 if OPT.colorSpace in ("gray", "y") else 3, OPT.height, OPT.width)
     ctx = L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
     epoch0 = 1
@@ -146,6 +148,9 @@ def main(argv=None):
             TRAIN_DATA = data[idx]
         else:
             TRAIN_DATA = synthetic_images(nbLoad, dims, OPT.seed * 7919 + env.EPOCH * 3)
+        if OPT.colorSpace in ("y", "yuv", "hsl") and TRAIN_DATA.shape[1] == 3:
+            # rgb images seen in another space (dataset.lua:153): one gr_colorspace_host call per epoch load
+            TRAIN_DATA = nn_utils.rgbToColorSpace(np.ascontiguousarray(TRAIN_DATA, np.float32), OPT.colorSpace)
         if game is None:
             adversarial.train(env, TRAIN_DATA, quiet=OPT.quiet)       # train.lua:229
             last = (env.last_losses["D"][-1], env.last_losses["G"][-1])

@@ -53,6 +53,8 @@ int gr_memcpy_h2d(gr_ctx*, void* dst_dev, const void* src_host, int64_t bytes);
 int gr_memcpy_d2h(gr_ctx*, void* dst_host, const void* src_dev, int64_t bytes);
 int gr_fill_normal_dev(gr_ctx*, float* dst_dev, int64_t n, uint64_t seed);
 int gr_fill_uniform_dev(gr_ctx*, float* dst_dev, int64_t n, float lo, float hi, uint64_t seed);
+int gr_colorspace_dev(gr_ctx*, const float* in_dev, int from, int to, int64_t batch, int h, int w, float* out_dev);     /* utils/nn_utils.lua:133-246; 0 rgb, 1 y, 2 yuv, 3 hsl */
+int gr_colorspace_host(gr_ctx*, const float* in_host, int from, int to, int64_t batch, int h, int w, float* out_host);
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);
 float* gr_net_output_dev(gr_net*);
 int gr_net_forward_batched_dev(gr_net*, const float* in_dev, int64_t rows, int batch, float* out_dev);   /* utils/nn_utils.lua:5-33 */

@@ -308,6 +308,18 @@ int gr_fill_uniform_dev(gr_ctx* ctx, float* dst_dev, int64_t n, float lo, float 
 int gr_copy2d_dev(gr_ctx* ctx, float* dst_dev, int64_t dst_pitch, const float* src_dev, int64_t src_pitch, int64_t rows, int64_t cols);
 int gr_add_dev(gr_ctx* ctx, float* y_dev, const float* x_dev, int64_t n);
 
+/* ---- NN_UTILS.switchColorSpace(images, from, to) = rgbToColorSpace(toRgb(images, from), to)  (utils/nn_utils.lua:133-246;
+ * pretrain_with_previous_net.lua:167,182; dataset.lua:153).  NCHW fp32, [batch x planes x h x w]: GR_CS_Y has 1 plane, the others 3.
+ * One launch: the rgb intermediate is never written, and the result is bit-identical to from -> rgb followed by rgb -> to (each step
+ * rounds to fp32 as its own call would).  rgb -> rgb is the only pass-through (no launch; out = a copy of in when the pointers differ);
+ * y -> y, yuv -> yuv and hsl -> hsl DO go through rgb, as the reference does (y -> y yields 0.21y + 0.72y + 0.07y).
+ * rgb -> y is nn_utils.rgb2y's mixture (:221-246), not image.rgb2y.  The yuv and hsl arithmetic restates Torch's `image` rock (DESIGN.md
+ * section 1).  in == out is allowed when both spaces have the same plane count.  A bad from / to, batch, h or w <= 0, a null pointer, or
+ * in == out with different plane counts return GR_ERR_INVALID and leave out untouched. ---- */
+enum { GR_CS_RGB = 0, GR_CS_Y = 1, GR_CS_YUV = 2, GR_CS_HSL = 3 };
+int gr_colorspace_dev(gr_ctx* ctx, const float* in_dev, int from, int to, int64_t batch, int h, int w, float* out_dev);
+int gr_colorspace_host(gr_ctx* ctx, const float* in_host, int from, int to, int64_t batch, int h, int w, float* out_host);
+
 /* ---- single-kernel entry points used by bench.py's roofline leg and by kernel-level parity tests ---- */
 int gr_conv3_forward_dev(gr_ctx* ctx, const float* in_dev, const float* w_dev, const float* bias_dev, float* out_dev,
                          int batch, int cin, int cout, int h, int w, int upsample2);
