@@ -237,6 +237,22 @@ class Context:
     def fill_uniform(self, dptr, n, seed, lo=-1.0, hi=1.0):
         self.check(self.lib.gr_fill_uniform_dev(self.h, _ptr(dptr), int(n), float(lo), float(hi), int(seed)), "gr_fill_uniform_dev")
 
+    def fill_noise(self, dptr, n, method, seed, host=None):
+        """createNoiseInputs (utils/nn_utils.lua:39-51) into a device tensor of n floats: normal(0, 1) or uniform(-1, 1) drawn on the
+        device, or the host array `host` uploaded in their place (parity tests)"""
+        if host is not None:
+            self.upload(np.ascontiguousarray(host, np.float32).reshape(int(n)), dptr)      # reshape: n floats, no more
+        elif method == "uniform":
+            self.fill_uniform(dptr, n, seed, -1.0, 1.0)
+        elif method == "normal":
+            self.fill_normal(dptr, n, seed)
+        else:
+            raise ValueError(f"Unknown noise method '{method}'")   # utils/nn_utils.lua:48
+
+    def read_loss(self, dptr):
+        """the float64 loss word a criterion kernel left at dptr"""
+        return float(self.download(dptr, (1,), np.float64)[0])
+
     def copy2d(self, dst, dst_pitch, src, src_pitch, rows, cols):
         """rows x cols floats between two row-major device matrices (pitches in floats): nn.Concat's join / slice"""
         self.check(self.lib.gr_copy2d_dev(self.h, _ptr(dst), int(dst_pitch), _ptr(src), int(src_pitch), int(rows), int(cols)), "gr_copy2d_dev")

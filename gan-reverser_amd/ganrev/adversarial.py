@@ -15,7 +15,7 @@ import types
 import numpy as np
 
 from . import _lib as L
-from . import nn, nn_utils, optim
+from . import device, nn, nn_utils, optim
 
 Y_GENERATOR = 0          # train.lua:67-68
 Y_NOT_GENERATOR = 1
@@ -41,6 +41,15 @@ def l2(parameters, gradParameters, lossValue, l2weight):
     if l2weight != 0:
         lossValue = lossValue + l2weight * float(np.dot(parameters.astype(np.float64), parameters.astype(np.float64))) / 2
         gradParameters += parameters * np.float32(l2weight)
+    return lossValue
+
+
+def penalise_and_clamp(parameters, gradParameters, lossValue, l1weight, l2weight, clampValue):
+    """adversarial.lua:86-88, and the `penalties (L1 and L2)` / `clamp` lines of every other --compat closure (train_r.lua:153-165,
+    pretrain_g.lua:162-175, pretrain_with_previous_net.lua:196-208,224-236) -> the penalised loss value"""
+    lossValue = l1(parameters, gradParameters, lossValue, l1weight)
+    lossValue = l2(parameters, gradParameters, lossValue, l2weight)
+    clamp(gradParameters, clampValue)
     return lossValue
 
 
@@ -94,9 +103,7 @@ def make_fevalD(env, inputs, targets):
         f = env.CRITERION.forward(outputs, targets.reshape(outputs.shape))      # :80
         df_do = env.CRITERION.backward(outputs, targets.reshape(outputs.shape)) # :83
         env.MODEL_D.backward(inputs, df_do)                                     # :84
-        f = l1(env.PARAMETERS_D, env.GRAD_PARAMETERS_D, f, env.OPT.D_L1)        # :86-88
-        f = l2(env.PARAMETERS_D, env.GRAD_PARAMETERS_D, f, env.OPT.D_L2)
-        clamp(env.GRAD_PARAMETERS_D, env.OPT.D_clamp)
+        f = penalise_and_clamp(env.PARAMETERS_D, env.GRAD_PARAMETERS_D, f, env.OPT.D_L1, env.OPT.D_L2, env.OPT.D_clamp)      # :86-88
         for i in range(outputs.shape[0]):                                       # :91-96
             c = 1 if outputs[i][0] > 0.5 else 0
             env.CONFUSION[c, int(targets[i])] += 1
@@ -117,9 +124,7 @@ def make_fevalG_on_D(env, noiseInputs, targets):
         env.MODEL_D.backward(samples, df_samples)                               # :120
         df_do = env.MODEL_D.gradInput                                           # :121  MODEL_D.modules[1].gradInput
         env.MODEL_G.backward(noiseInputs, df_do)                                # :124
-        f = l1(env.PARAMETERS_G, env.GRAD_PARAMETERS_G, f, env.OPT.G_L1)        # :126-128
-        f = l2(env.PARAMETERS_G, env.GRAD_PARAMETERS_G, f, env.OPT.G_L2)
-        clamp(env.GRAD_PARAMETERS_G, env.OPT.G_clamp)
+        f = penalise_and_clamp(env.PARAMETERS_G, env.GRAD_PARAMETERS_G, f, env.OPT.G_L1, env.OPT.G_L2, env.OPT.G_clamp)      # :126-128
         return f, env.GRAD_PARAMETERS_G
     return fevalG_on_D
 
@@ -178,116 +183,9 @@ def train(env, trainData, quiet=True):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Fast mode: the same game with images, gradients, parameters and the Adam state resident on the GPU (what ganrev.train_r's
-# DeviceTrainer / gr_train_r_step is to train_r.lua:138-170).  The containers stay host code that enqueues work: every compiled
-# part runs through gr_net_forward_dev / gr_net_backward_dev, nn.Concat joins / slices / sums with gr_copy2d_dev / gr_add_dev,
-# nn.BCECriterion is gr_bce_dev, and adversarial.l1 / l2 / clamp + optim.adam are the fused gr_adam_step of each part.  Nothing
-# is copied to the host inside a batch except, on request, the two loss values.
-class _DevGraph:
-    """Device-resident executor of a ganrev model that runs as compiled parts (nn.Sequential.parts(), nn.Concat)."""
-
-    def __init__(self, ctx, model):
-        self.ctx, self.model, self.bufs = ctx, model, {}
-        self.nets = [ch._net for ch, _, _ in model._param_chunks()]
-        self.plan = self._plan(model)
-
-    def _plan(self, node):
-        if isinstance(node, nn.Concat):
-            if node.dimension != 2:
-                raise L.GanrevError("device-resident nn.Concat: only nn.Concat(2) of [batch x features] outputs (models.lua:293)")
-            return ("concat", [self._plan(b) for b in node.modules])
-        if node._is_graph():
-            return ("seq", [self._plan(p) for p in node.parts()])
-        if node._net is None:
-            raise L.GanrevError("compile the model first (one forward)")
-        return ("net", node._net)
-
-    def _buf(self, key, n_floats):
-        cur = self.bufs.get(key)
-        if cur is None or cur[1] < n_floats:
-            if cur is not None:
-                self.ctx.free(cur[0])
-            cur = (self.ctx.malloc(4 * int(n_floats)), int(n_floats))
-            self.bufs[key] = cur
-        return cur[0]
-
-    @staticmethod
-    def _vol(d):
-        return int(d[0]) * int(d[1]) * int(d[2])
-
-    def out_features(self, plan=None):
-        plan = plan or self.plan
-        if plan[0] == "net":
-            return self._vol(plan[1].out_dims)
-        if plan[0] == "seq":
-            return self.out_features(plan[1][-1])
-        return sum(self.out_features(p) for p in plan[1])
-
-    def in_features(self, plan=None):
-        plan = plan or self.plan
-        if plan[0] == "net":
-            return self._vol(plan[1].in_dims)
-        return self.in_features(plan[1][0])
-
-    def forward(self, x_dev, B, plan=None):
-        plan = plan or self.plan
-        self.bufs[(id(plan), "x")] = x_dev
-        if plan[0] == "net":
-            return plan[1].forward_dev(x_dev, B)
-        if plan[0] == "seq":
-            for p in plan[1]:
-                x_dev = self.forward(x_dev, B, p)
-            return x_dev
-        total = self.out_features(plan)
-        cat = self._buf((id(plan), "cat"), B * total)
-        lo = 0
-        for p in plan[1]:
-            o, k = self.forward(x_dev, B, p), self.out_features(p)
-            self.ctx.copy2d(cat + 4 * lo, total, o, k, B, k)
-            lo += k
-        return cat
-
-    def backward(self, g_dev, B, want_gin, plan=None):
-        """gradOutput (device) -> gradInput (device pointer, or None when not wanted); accumulates every part's parameter gradient"""
-        plan = plan or self.plan
-        x_dev = self.bufs[(id(plan), "x")]
-        if plan[0] == "net":
-            gin = self._buf((id(plan), "gin"), B * self._vol(plan[1].in_dims)) if want_gin else None
-            plan[1].backward_dev(x_dev, g_dev, B, gin)
-            return gin
-        if plan[0] == "seq":
-            for i in range(len(plan[1]) - 1, -1, -1):
-                g_dev = self.backward(g_dev, B, want_gin or i > 0, plan[1][i])
-            return g_dev
-        total, lo, acc = self.out_features(plan), 0, None
-        nin = B * self.in_features(plan)
-        for j, p in enumerate(plan[1]):
-            k = self.out_features(p)
-            gs = self._buf((id(plan), "gslice", j), B * k)
-            self.ctx.copy2d(gs, k, g_dev + 4 * lo, total, B, k)
-            gi = self.backward(gs, B, want_gin, p)
-            if want_gin:
-                if acc is None:
-                    acc = gi                      # the first branch's own gradInput buffer holds the sum
-                else:
-                    self.ctx.add(acc, gi, nin)
-            lo += k
-        return acc
-
-    def zero_grads(self):
-        for n in self.nets:
-            n.zero_grads()
-
-    def close(self):
-        for key, v in list(self.bufs.items()):
-            if isinstance(v, tuple):           # (pointer, size): a buffer this executor allocated ("x" entries are borrowed pointers)
-                self.ctx.free(v[0])
-            del self.bufs[key]
-
-    def adam_step(self, hyper, t):
-        for n in self.nets:
-            n.adam_step(hyper, t)
-
-
+# DeviceTrainer / gr_train_r_step is to train_r.lua:138-170).  G and D each run through a device.DeviceModel, nn.BCECriterion is
+# gr_bce_dev, and adversarial.l1 / l2 / clamp + optim.adam are the fused gr_adam_step of each part.  Nothing is copied to the host
+# inside a batch except, on request, the two loss values.
 class DeviceGame:
     """adversarial.lua:139-201 per batch, device-resident.  game = DeviceGame(env); game.batch(real_half_batch) per batch;
     game.sync_to_host() before anything reads env.PARAMETERS_* or the host-side modules again (save, evaluate, compat mode)."""
@@ -297,53 +195,32 @@ class DeviceGame:
         OPT, G, D = env.OPT, env.MODEL_G, env.MODEL_D
         if OPT.D_optmethod != "adam" or OPT.G_optmethod != "adam":
             raise L.GanrevError("DeviceGame: only the default optimizer 'adam' (train.lua:37-38); the other methods run in adversarial.train")
-        self.ctx = G._context()
+        self.ctx = ctx = G._context()
         B = OPT.batchSize
-        # Compile every net with one small forward (parameters uploaded) WITHOUT side effects on the models: the
-        # reference has no such step, so the BatchNorm running statistics a training-mode forward of two samples would write - and
-        # which evaluate()-mode users of G (train_r, apply_r) and the saved checkpoint would then carry - are put back afterwards.
-        img = G.forward(nn_utils.createNoiseInputs(2, OPT.noiseDim, OPT.noiseMethod, seed=1))
-        D.forward(img)
-        self.gnet = G._net
-        self.dg = _DevGraph(self.ctx, D)
-        for model in (G, D):
-            for chunk, _, _ in model._param_chunks():
-                bi = 0
-                for mod in chunk.leaves():
-                    if hasattr(mod, "running_mean"):
-                        chunk._net.set_bn_running(bi, mod.running_mean, mod.running_var)     # the modules still hold the pre-compile values
-                        bi += 1
-        for n in [self.gnet] + self.dg.nets:
-            n.set_training(True)
-            n.adam_reset()
+        device.compile_models(nn_utils.createNoiseInputs(2, OPT.noiseDim, OPT.noiseMethod, seed=1), G, D)
+        self.gg, self.dg = device.DeviceModel(ctx, G), device.DeviceModel(ctx, D)
+        self.gnet = G._net                                  # G's one net by name: not used by the game, read by tools/debug
+        for m in (self.gg, self.dg):
+            m.set_training(True)
+            m.adam_reset()
         self.t = {"D": 0, "G": 0}
         self.npix = int(np.prod(env.IMG_DIMENSIONS))
-        m = self.ctx.malloc
+        self.mem = device.Buffers(ctx)
+        m = self.mem.malloc
         self.inputs, self.targets, self.ones = m(4 * B * self.npix), m(4 * B), m(4 * B)
         self.noise, self.df, self.loss = m(4 * B * OPT.noiseDim), m(4 * B), m(16)
         half = B // 2
-        self.ctx.upload(np.concatenate([np.full(half, Y_NOT_GENERATOR, np.float32), np.full(B - half, Y_GENERATOR, np.float32)]), self.targets)
-        self.ctx.upload(np.full(B, Y_NOT_GENERATOR, np.float32), self.ones)
+        ctx.upload(np.concatenate([np.full(half, Y_NOT_GENERATOR, np.float32), np.full(B - half, Y_GENERATOR, np.float32)]), self.targets)
+        ctx.upload(np.full(B, Y_NOT_GENERATOR, np.float32), self.ones)
         self.hyper_d = L.Hyper(l1=OPT.D_L1, l2=OPT.D_L2, clamp=OPT.D_clamp)
         self.hyper_g = L.Hyper(l1=OPT.G_L1, l2=OPT.G_L2, clamp=OPT.G_clamp)
-        self.noise_counter = 0
+        self.noise_counter = self.batches = 0
 
     def _fill_noise(self, N, host=None):
-        nd = self.env.OPT.noiseDim
-        if host is not None:
-            self.ctx.upload(np.ascontiguousarray(host, np.float32), self.noise)
-            return
-        self.noise_counter += 1
-        seed = self.env.OPT.seed * 100003 + self.noise_counter
-        if self.env.OPT.noiseMethod == "uniform":
-            self.ctx.fill_uniform(self.noise, N * nd, seed)
-        else:
-            self.ctx.fill_normal(self.noise, N * nd, seed)
-
-    def _read_loss(self):
-        return float(self.ctx.download(self.loss, (1,), np.float64)[0])
-
-    GUARD_PERIOD = 64       # batches between two f16x3 range-guard scans of the parameters (gr_range_guard_scan_params)
+        OPT = self.env.OPT
+        if host is None:
+            self.noise_counter += 1
+        self.ctx.fill_noise(self.noise, N * OPT.noiseDim, OPT.noiseMethod, OPT.seed * 100003 + self.noise_counter, host)
 
     def batch(self, real, noise_d=None, noise_g=None, want_loss=False):
         """One batch of adversarial.lua:139-201: OPT.D_iterations updates of D, each on batchSize/2 fresh real images + batchSize/2
@@ -352,45 +229,43 @@ class DeviceGame:
         [D_iterations * batchSize/2 x noiseDim] / [G_iterations * batchSize x noiseDim].  Returns the LAST (loss_D, loss_G)."""
         OPT, B = self.env.OPT, self.env.OPT.batchSize
         half = B // 2
-        ctx = self.ctx
+        ctx, gg, dg = self.ctx, self.gg, self.dg
         # `for k=1,OPT.D_iterations` (adversarial.lua:127,168): 0 iterations run zero times - that phase's net stays frozen
         nD, nG = max(0, int(OPT.D_iterations)), max(0, int(OPT.G_iterations))
         real = np.ascontiguousarray(real, np.float32).reshape(-1, self.npix)
         if real.shape[0] < nD * half:
             raise IndexError("trainData exhausted (adversarial.lua:146 indexes past the loaded examples): "
                              f"{real.shape[0]} images for {nD} D iterations of {half}")
-        self.batches = getattr(self, "batches", 0) + 1
-        if self.ctx.conv_mode() == "f16x3" and (self.batches - 1) % self.GUARD_PERIOD == 0:
-            for n in [self.gnet] + self.dg.nets:      # the *_dev calls below are unguarded: sampled parameter scan, as gr_train_r_step does
-                n.range_guard_scan()
+        self.batches += 1
+        device.range_guard(ctx, self.batches, (gg, dg))
         loss_d = loss_g = None
         for k in range(nD):
             # (1) D on half real, half generated (adversarial.lua:141-157, fevalD :66-100)
             ctx.upload(real[k * half:(k + 1) * half], self.inputs)
             self._fill_noise(half, None if noise_d is None else np.asarray(noise_d).reshape(nD, half, -1)[k])
-            fake = self.gnet.forward_dev(self.noise, half)
+            fake = gg.forward(self.noise, half)
             ctx.copy2d(self.inputs + 4 * half * self.npix, self.npix, fake, self.npix, half, self.npix)
-            self.dg.zero_grads()
-            out = self.dg.forward(self.inputs, B)
+            dg.zero_grads()
+            out = dg.forward(self.inputs, B)
             ctx.bce_dev(out, self.targets, B, self.loss, self.df)
-            self.dg.backward(self.df, B, False)
+            dg.backward(self.df, B, False)
             self.t["D"] += 1
-            self.dg.adam_step(self.hyper_d, self.t["D"])
+            dg.adam_step(self.hyper_d, self.t["D"])
             if want_loss and k == nD - 1:
-                loss_d = self._read_loss()
+                loss_d = ctx.read_loss(self.loss)
         for k in range(nG):
             # (2) G through D (adversarial.lua:178-201, fevalG_on_D :104-133)
             self._fill_noise(B, None if noise_g is None else np.asarray(noise_g).reshape(nG, B, -1)[k])
-            self.gnet.zero_grads()
-            samples = self.gnet.forward_dev(self.noise, B)
-            out = self.dg.forward(samples, B)
+            gg.zero_grads()
+            samples = gg.forward(self.noise, B)
+            out = dg.forward(samples, B)
             ctx.bce_dev(out, self.ones, B, self.loss, self.df)
-            df_do = self.dg.backward(self.df, B, True)
-            self.gnet.backward_dev(self.noise, df_do, B, None)
+            df_do = dg.backward(self.df, B, True)
+            gg.backward(df_do, B, False)
             self.t["G"] += 1
-            self.gnet.adam_step(self.hyper_g, self.t["G"])
+            gg.adam_step(self.hyper_g, self.t["G"])
             if want_loss and k == nG - 1:
-                loss_g = self._read_loss()
+                loss_g = ctx.read_loss(self.loss)
         return loss_d, loss_g
 
     def sync_to_host(self):
@@ -399,7 +274,5 @@ class DeviceGame:
 
     def close(self):
         """Release the device buffers of the game (the nets stay with their models)."""
-        self.dg.close()
-        for p in (self.inputs, self.targets, self.ones, self.noise, self.df, self.loss):
-            self.ctx.free(p)
-        self.inputs = self.targets = self.ones = self.noise = self.df = self.loss = None
+        for m in (self.gg, self.dg, self.mem):
+            m.close()

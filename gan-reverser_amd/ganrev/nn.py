@@ -145,6 +145,10 @@ class Module:
         flat = self._flat[0] if self._flat is not None else self._flat_host()
         if flat.size:
             self._net.set_params(flat)
+        self.push_bn_running()
+
+    def push_bn_running(self):
+        """host BatchNorm running statistics -> device (what a training-mode forward overwrote there: device.compile_models)"""
         bi = 0
         for m in self.leaves():
             if isinstance(m, BatchNormalization):
@@ -281,17 +285,25 @@ class Module:
         return self.gradInput
 
 
-class Sequential(Module):
-    TYPENAME = "nn.Sequential"
+def _over_children(fn):
+    """fn(self, children, ...) states what a container that runs as several compiled parts does with a call: it passes the call on
+    to its children() and hands each its slice of the flat vector.  A plain Sequential has no children in this sense - it compiles
+    to ONE gr_net - and answers as the Module it is."""
+    base = getattr(Module, fn.__name__)
+
+    def method(self, *args):
+        kids = self.children()
+        return base(self, *args) if kids is None else fn(self, kids, *args)
+    method.__name__, method.__doc__ = fn.__name__, fn.__doc__ or base.__doc__
+    return method
+
+
+class _Container(Module):
+    """What nn.Sequential and nn.Concat share: the list `modules` and the protocol over children()."""
 
     def __init__(self):
         super().__init__()
         self.modules = []
-
-    def add(self, m):
-        self.modules.append(m)
-        self._parts = None             # the execution plan of a model with an nn.Concat is rebuilt on the next use
-        return self
 
     def get(self, i):
         return self.modules[i - 1]     # Lua is 1-based
@@ -300,22 +312,89 @@ class Sequential(Module):
         return len(self.modules)
 
     def listModules(self):
-        out = [self]
-        for m in self.modules:
-            out.extend(m.listModules())
-        return out
+        return [self] + [x for m in self.modules for x in m.listModules()]
 
     def leaves(self):
-        out = []
-        for m in self.modules:
-            out.extend(m.leaves())
-        return out
+        return [x for m in self.modules for x in m.leaves()]
+
+    def children(self):
+        """The containers this one runs as (each a Sequential or a Concat), or None when it compiles to one gr_net."""
+        return None
+
+    def _slices(self, kids, lo=0):
+        """(child, lo, hi): each child's slice of this container's flat vector"""
+        for p in kids:
+            k = p._param_count()
+            yield p, lo, lo + k
+            lo += k
+
+    @_over_children
+    def _bind_flat(self, kids, flat, grads):
+        for p, lo, hi in self._slices(kids):
+            p._bind_flat(flat[lo:hi], grads[lo:hi])
+        self._flat = (flat, grads)
+
+    @_over_children
+    def _param_chunks(self, kids, lo=0):
+        return [c for p, plo, _ in self._slices(kids, lo) for c in p._param_chunks(plo)]
+
+    @_over_children
+    def push_params(self, kids):
+        for p in kids:
+            p.push_params()
+
+    @_over_children
+    def push_bn_running(self, kids):
+        for p in kids:
+            p.push_bn_running()
+
+    @_over_children
+    def pull_params(self, kids):
+        for p in kids:
+            p.pull_params()
+
+    @_over_children
+    def zeroGradParameters(self, kids):
+        if self._flat is not None:
+            self._flat[1][...] = 0
+        for p in kids:
+            p.zeroGradParameters()
+
+    def _owner(self, module):
+        """The compiled chunk a leaf module sits in (dropout-noise injection / read-back), or None"""
+        kids = self.children()
+        if kids is None:
+            return self if any(m is module for m in self.leaves()) else None
+        return next((o for o in (p._owner(module) for p in kids) if o is not None), None)
+
+    def setNoise(self, module, keep):
+        Module.setNoise(self._owner(module), module, keep)
+
+    def getNoise(self, module, batch):
+        return Module.getNoise(self._owner(module), module, batch)
+
+    def __repr__(self):
+        lines = [self._head() + " {"]
+        lines += [f"  ({i + 1}): {m!r}" for i, m in enumerate(self.modules)]
+        return "\n".join(lines + ["}"])
+
+
+class Sequential(_Container):
+    TYPENAME = "nn.Sequential"
+
+    def add(self, m):
+        self.modules.append(m)
+        self._parts = None             # the execution plan of a model with an nn.Concat is rebuilt on the next use
+        return self
 
     # ---- a Sequential that holds an nn.Concat (models.lua:293-321, the D network) cannot be one gr_net: it runs as a chain
     # of PARTS - every run of plain modules is compiled into one gr_net (a chunk), a branching container runs its branches.
     # Host arrays travel between the parts, as Torch7 tensors travel between the modules of the reference's containers.
     def _is_graph(self):
         return any(isinstance(m, Concat) or (isinstance(m, Sequential) and m._is_graph()) for m in self.modules)
+
+    def children(self):
+        return self.parts() if self._is_graph() else None
 
     def parts(self):
         if getattr(self, "_parts", None) is None:
@@ -359,79 +438,17 @@ class Sequential(Module):
         self.gradInput = g
         return g
 
-    def _bind_flat(self, flat, grads):
-        if not self._is_graph():
-            return Module._bind_flat(self, flat, grads)
-        off = 0
-        for p in self.parts():
-            k = p._param_count()
-            p._bind_flat(flat[off:off + k], grads[off:off + k])
-            off += k
-        self._flat = (flat, grads)
-
-    def _param_chunks(self, lo=0):
-        if not self._is_graph():
-            return Module._param_chunks(self, lo)
-        out = []
-        for p in self.parts():
-            out.extend(p._param_chunks(lo))
-            lo += p._param_count()
-        return out
-
-    def push_params(self):
-        if not self._is_graph():
-            return Module.push_params(self)
-        for p in self.parts():
-            p.push_params()
-
-    def pull_params(self):
-        if not self._is_graph():
-            return Module.pull_params(self)
-        for p in self.parts():
-            p.pull_params()
-
-    def zeroGradParameters(self):
-        if not self._is_graph():
-            return Module.zeroGradParameters(self)
-        if self._flat is not None:
-            self._flat[1][...] = 0
-        for p in self.parts():
-            p.zeroGradParameters()
-
     def manualSeed(self, seed):
         if not self._is_graph():
             return Module.manualSeed(self, seed)
         for i, (chunk, _, _) in enumerate(self._param_chunks()):
             chunk.manualSeed(int(seed) * 1009 + i)
 
-    def _owner(self, module):
-        """The compiled chunk a leaf module sits in (dropout-noise injection / read-back of a graph model)."""
-        for p in self.parts():
-            if isinstance(p, Concat) or p._is_graph():
-                o = p._owner(module)
-                if o is not None:
-                    return o
-            elif any(m is module for m in p.leaves()):
-                return p
-        return None
-
-    def setNoise(self, module, keep):
-        if not self._is_graph():
-            return Module.setNoise(self, module, keep)
-        self._owner(module).setNoise(module, keep)
-
-    def getNoise(self, module, batch):
-        if not self._is_graph():
-            return Module.getNoise(self, module, batch)
-        return self._owner(module).getNoise(module, batch)
-
-    def __repr__(self):
-        lines = ["nn.Sequential {"]
-        lines += [f"  ({i + 1}): {m!r}" for i, m in enumerate(self.modules)]
-        return "\n".join(lines + ["}"])
+    def _head(self):
+        return "nn.Sequential"
 
 
-class Concat(Module):
+class Concat(_Container):
     """nn.Concat(dimension): every branch gets the same input, the outputs are joined along `dimension` (1-based, the batch
     is dimension 1): the D network's two convolution towers (models.lua:293-321, `nn.Concat(2)` of two [B x 512] feature
     vectors).  backward hands each branch its slice of gradOutput and sums the branches' gradInputs."""
@@ -440,7 +457,6 @@ class Concat(Module):
     def __init__(self, dimension):
         super().__init__()
         self.dimension = int(dimension)
-        self.modules = []
 
     def add(self, m):
         if not isinstance(m, Sequential):
@@ -448,26 +464,11 @@ class Concat(Module):
         self.modules.append(m)
         return self
 
-    def get(self, i):
-        return self.modules[i - 1]
-
-    def size(self):
-        return len(self.modules)
-
-    def listModules(self):
-        out = [self]
-        for m in self.modules:
-            out.extend(m.listModules())
-        return out
-
-    def leaves(self):
-        out = []
-        for m in self.modules:
-            out.extend(m.leaves())
-        return out
-
     def _is_graph(self):
         return True
+
+    def children(self):
+        return self.modules
 
     def forward(self, input):
         x = L.f32(input)
@@ -495,49 +496,8 @@ class Concat(Module):
         self.gradInput = gin
         return gin
 
-    def _bind_flat(self, flat, grads):
-        off = 0
-        for b in self.modules:
-            k = b._param_count()
-            b._bind_flat(flat[off:off + k], grads[off:off + k])
-            off += k
-        self._flat = (flat, grads)
-
-    def _param_chunks(self, lo=0):
-        out = []
-        for b in self.modules:
-            out.extend(b._param_chunks(lo))
-            lo += b._param_count()
-        return out
-
-    def push_params(self):
-        for b in self.modules:
-            b.push_params()
-
-    def pull_params(self):
-        for b in self.modules:
-            b.pull_params()
-
-    def zeroGradParameters(self):
-        if self._flat is not None:
-            self._flat[1][...] = 0
-        for b in self.modules:
-            b.zeroGradParameters()
-
-    def _owner(self, module):
-        for b in self.modules:
-            if b._is_graph():
-                o = b._owner(module)
-                if o is not None:
-                    return o
-            elif any(m is module for m in b.leaves()):
-                return b
-        return None
-
-    def __repr__(self):
-        lines = [f"nn.Concat({self.dimension}) {{"]
-        lines += [f"  ({i + 1}): {m!r}" for i, m in enumerate(self.modules)]
-        return "\n".join(lines + ["}"])
+    def _head(self):
+        return f"nn.Concat({self.dimension})"
 
 
 class Copy(Module):

@@ -62,12 +62,7 @@ def forwardBatchedDev(model, input, batchSize, out=None):
 def createNoiseInputsDev(ctx, N, noiseDim, method="normal", seed=1):
     """utils/nn_utils.lua:39-51 drawn on the GPU (Philox4x32-10; the stream tests/test_gpu_abi_behaviour.py pins)."""
     t = DeviceTensor(ctx, (N, noiseDim))
-    if method == "uniform":
-        ctx.fill_uniform(t.ptr, N * noiseDim, seed)
-    elif method == "normal":
-        ctx.fill_normal(t.ptr, N * noiseDim, seed)
-    else:
-        raise ValueError(f"Unknown noise method '{method}'")   # utils/nn_utils.lua:48
+    ctx.fill_noise(t.ptr, N * noiseDim, method, seed)           # ValueError for an unknown method (utils/nn_utils.lua:48)
     return t
 
 

@@ -160,10 +160,7 @@ class DeviceTrainer:
     def new_noise(self, seed):
         # createNoiseInputs on device (utils/nn_utils.lua:39-51): normal(0, 1) or uniform(-1, 1) - with the uniform method R ends
         # in a Tanh (models.lua:452-454) and can only reach targets in (-1, 1)
-        if self.noise_method == "uniform":
-            self.ctx.fill_uniform(self.noise, self.B * self.nd, seed, -1.0, 1.0)
-        else:
-            self.ctx.fill_normal(self.noise, self.B * self.nd, seed)
+        self.ctx.fill_noise(self.noise, self.B * self.nd, self.noise_method, seed)
 
     def step(self, want_loss=False):
         self.t += 1
@@ -184,7 +181,7 @@ class DeviceTrainer:
         if reduce_grads is not None:
             reduce_grads(r)                                                             # SUM over ranks before the non-linear part
         r.adam_step(self.hyper, self.t)                                                 # :153-170
-        loss = float(self.ctx.download(self.loss_dev, (1,), np.float64)[0])
+        loss = self.ctx.read_loss(self.loss_dev)
         return reduce_scalar(loss) if reduce_scalar is not None else loss
 
 

@@ -5,7 +5,7 @@ nn.MSECriterion, the L1 / L2 penalty, the gradient clamp and optim.adam (pretrai
     python -m ganrev.pretrain_g --epochs 2 --N_epoch 30 --batchSize 128 --save logs [--data images.npy] [--compat]
 
 Same option names and defaults as pretrain_g.lua:12-35 for what is mirrored.  Training images come from --data (an
-[N x C x H x W] float32 .npy in [0, 1]) or, without it, from train.synthetic_images (the dataset loader is out of scope).  With
+[N x C x H x W] float32 .npy in [0, 1]) or, without it, from synth.synthetic_images (the dataset loader is out of scope).  With
 --colorSpace yuv | hsl the images are rgb and are converted once per epoch load, on the device (nn_utils.rgbToColorSpace, as
 dataset.lua:153 does per image); three-channel --data with --colorSpace y is converted the same way.
 
@@ -26,8 +26,9 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import models, nn, nn_utils, optim, t7
-from .train import synthetic_images
+from . import device, models, nn, nn_utils, optim, scripts, t7
+from .adversarial import penalise_and_clamp
+from .synth import synthetic_images
 
 
 def parse(argv=None):
@@ -53,17 +54,12 @@ def parse(argv=None):
 
 
 def image_dims(OPT):
-    return (1 if OPT.colorSpace == "y" else 3, OPT.height, OPT.width)       # pretrain_g.lua:49-53
-
-
-def needs_conversion(images, colorSpace):
-    """rgb images (three channels) that --colorSpace yuv | hsl | y asks to see in another space"""
-    return colorSpace != "rgb" and images.shape[1] == 3
+    return scripts.image_dims(OPT.colorSpace, OPT.height, OPT.width)         # pretrain_g.lua:49-53
 
 
 def checkpoint_name(dims, noiseDim):
     """pretrain_g.lua:190 / train.lua:148: g_pretrained_CHANNELSxHEIGHTxWIDTH_ndNOISEDIM.net"""
-    return "g_pretrained_%dx%dx%d_nd%d.net" % (dims[0], dims[1], dims[2], noiseDim)
+    return "g_pretrained_%s.net" % scripts.geometry(dims, noiseDim)
 
 
 def build(dims, noiseDim, seed):
@@ -82,27 +78,28 @@ class DeviceLoop:
 
     def __init__(self, ae, dims, B, hyper):
         self.ae, self.B, self.hyper, self.t = ae, int(B), hyper, 0
-        self.net = ae.device_net(dims)                 # compiled, parameters uploaded, training mode; no forward (no BatchNorm side effect)
+        self.ctx = ae.device_net(dims).ctx             # compiled, parameters uploaded, training mode; no forward (no BatchNorm side effect)
+        self.net = device.DeviceModel(self.ctx, ae)
         self.net.adam_reset()
-        self.ctx = self.net.ctx
         self.n = self.B * int(np.prod(dims))
+        self.mem = device.Buffers(self.ctx)
         self.images = None
-        self.grad = self.ctx.malloc(4 * self.n)
-        self.loss = self.ctx.malloc(64)
+        self.grad = self.mem.malloc(4 * self.n)
+        self.loss = self.mem.malloc(64)
 
     def load(self, images, colorSpace="rgb"):
         """the epoch's TRAIN_DATA, device-resident (pretrain_g.lua:118); rgb images are converted to colorSpace there (dataset.lua:153)"""
         images = np.ascontiguousarray(images, np.float32)
         if self.images is not None:
-            self.ctx.free(self.images)
-        self.images = self.ctx.upload(images)
-        if needs_conversion(images, colorSpace):
+            self.mem.free(self.images)
+        self.images = self.ctx.upload(images, self.mem.malloc(images.nbytes))
+        if scripts.needs_conversion(images, colorSpace):
             n, _, h, w = images.shape
             if colorSpace == "y":             # three planes in, one out: a buffer of its own
-                rgb, self.images = self.images, self.ctx.malloc(4 * n * h * w)
+                rgb, self.images = self.images, self.mem.malloc(4 * n * h * w)
                 self.ctx.colorspace_dev(rgb, L.GR_CS_RGB, L.GR_CS_Y, n, h, w, self.images)
                 self.ctx.synchronize()
-                self.ctx.free(rgb)
+                self.mem.free(rgb)
             else:                             # yuv / hsl: in place
                 self.ctx.colorspace_dev(self.images, L.GR_CS_RGB, L.COLOR_SPACES[colorSpace], n, h, w, self.images)
 
@@ -110,20 +107,19 @@ class DeviceLoop:
         x = self.images + 4 * self.n * b
         self.t += 1
         self.net.zero_grads()                                             # :151
-        out = self.net.forward_dev(x, self.B)                             # :154
+        out = self.net.forward(x, self.B)                                 # :154
         self.ctx.mse_dev(out, x, self.n, self.loss, self.grad)            # :155,159  (targets = inputs)
-        self.net.backward_dev(x, self.grad, self.B)                       # :160 (no gradInput)
+        self.net.backward(self.grad, self.B, False)                       # :160 (no gradInput)
         self.net.adam_step(self.hyper, self.t)                            # :163-183 penalty, clamp, optim.adam
-        return float(self.ctx.download(self.loss, (1,), np.float64)[0]) if want_loss else None
+        return self.ctx.read_loss(self.loss) if want_loss else None
 
     def sync_to_host(self):
         self.ae.pull_params()                                             # parameters and BatchNorm running statistics
 
     def close(self):
-        for p in (self.images, self.grad, self.loss):
-            if p:
-                self.ctx.free(p)
-        self.images = self.grad = self.loss = None
+        self.net.close()
+        self.mem.close()
+        self.images = None
 
 
 def compat_epoch(OPT, ae, PARAMETERS, GRAD_PARAMETERS, CRITERION, OPTSTATE, TRAIN_DATA, dims):
@@ -142,11 +138,7 @@ def compat_epoch(OPT, ae, PARAMETERS, GRAD_PARAMETERS, CRITERION, OPTSTATE, TRAI
             f = CRITERION.forward(outputs, targets)                       # :155
             df_do = CRITERION.backward(outputs, targets)                  # :159
             ae.backward(inputs, df_do)                                    # :160
-            if OPT.G_L1 != 0 or OPT.G_L2 != 0:                            # :163-170
-                f += OPT.G_L1 * np.abs(PARAMETERS).sum() + OPT.G_L2 * float(np.dot(PARAMETERS, PARAMETERS)) / 2
-                GRAD_PARAMETERS[...] += np.sign(PARAMETERS) * np.float32(OPT.G_L1) + PARAMETERS * np.float32(OPT.G_L2)
-            if OPT.G_clamp != 0:                                          # :173-175
-                np.clip(GRAD_PARAMETERS, -OPT.G_clamp, OPT.G_clamp, out=GRAD_PARAMETERS)
+            f = penalise_and_clamp(PARAMETERS, GRAD_PARAMETERS, f, OPT.G_L1, OPT.G_L2, OPT.G_clamp)      # :163-175
             return f, GRAD_PARAMETERS
         optim.adam(fevalG, PARAMETERS, OPTSTATE, model=ae)                # :180
     return CRITERION.output
@@ -158,8 +150,7 @@ def save(OPT, ae, dims, epoch):
     os.makedirs(OPT.save or ".", exist_ok=True)
     if not OPT.quiet:
         print("<trainer> saving network to %s" % filename)
-    opt = {k: v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}      # colorSpace: train_r --G reads it
-    t7.save_checkpoint(filename, G=ae.get(2), opt=opt, EPOCH=epoch + 1)
+    t7.save_checkpoint(filename, G=ae.get(2), opt=scripts.opt_table(OPT), EPOCH=epoch + 1)      # opt.colorSpace: train_r --G reads it
     return filename
 
 
@@ -193,7 +184,7 @@ def main(argv=None):
             else:
                 TRAIN_DATA = synthetic_images(nLoad, dims, OPT.seed * 7919 + EPOCH * 3)
             if loop is None:
-                if needs_conversion(TRAIN_DATA, OPT.colorSpace):
+                if scripts.needs_conversion(TRAIN_DATA, OPT.colorSpace):
                     TRAIN_DATA = nn_utils.rgbToColorSpace(np.ascontiguousarray(TRAIN_DATA, np.float32), OPT.colorSpace)
                 last = compat_epoch(OPT, ae, PARAMETERS, GRAD_PARAMETERS, CRITERION, OPTSTATE, TRAIN_DATA, dims)
             else:

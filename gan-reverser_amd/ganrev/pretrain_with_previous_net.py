@@ -10,12 +10,12 @@ D's predictions as SOFT targets), each under its L1 / L2 penalty, gradient clamp
 Same option names and defaults as pretrain_with_previous_net.lua:12-37.  --noplot, --window, --aws, --threads and --N_epoch are
 accepted and unused (the reference's `display` UI, thread count and an option its loop never reads).  Real images come from --data
 (an rgb [N x 3 x H x W] float32 .npy in [0, 1], converted to --colorSpace with rgbToColorSpace as dataset.lua:153 does) or, without
-it, from train.synthetic_images; the dataset loader and visualizeProgress (:270-306) are out of scope.
+it, from synth.synthetic_images; the dataset loader and visualizeProgress (:270-306) are out of scope.
 
 Two loops, as in ganrev.pretrain_g:
   fast (default)  - device-resident: gr_fill_*_dev for both noise tensors, gr_copy2d_dev for the shared noise columns and the two
-                    halves of D's input, gr_colorspace_dev for the two conversions, the old and the new D through
-                    adversarial._DevGraph, gr_mse_dev / gr_bce_dev, gr_adam_step (penalty, clamp and Adam fused).  Only the real
+                    halves of D's input, gr_colorspace_dev for the two conversions, the four nets through
+                    device.DeviceModel, gr_mse_dev / gr_bce_dev, gr_adam_step (penalty, clamp and Adam fused).  Only the real
                     half-batch goes up and, on request, two losses come down.
   --compat        - fevalG / fevalD exactly as :185-239 spells them, on host arrays over optim.adam.
 
@@ -34,9 +34,9 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import models, nn, nn_utils, optim, t7
-from .adversarial import _DevGraph
-from .train import synthetic_images
+from . import device, models, nn, nn_utils, optim, scripts, t7
+from .adversarial import penalise_and_clamp
+from .synth import synthetic_images
 
 COLOR_SPACES = ("rgb", "yuv", "hsl", "y")
 
@@ -73,13 +73,12 @@ def parse(argv=None):
     return p.parse_args(argv)
 
 
-def image_dims(colorSpace, height, width):
-    return (1 if colorSpace == "y" else 3, int(height), int(width))          # :59-63
+image_dims = scripts.image_dims                                              # :59-63
 
 
 def checkpoint_name(dims, noiseDim):
     """:262  pretrained_CHANNELSxHEIGHTxWIDTH_ndNOISEDIM.net"""
-    return "pretrained_%dx%dx%d_nd%d.net" % (dims[0], dims[1], dims[2], noiseDim)
+    return "pretrained_%s.net" % scripts.geometry(dims, noiseDim)
 
 
 def previous_options(opt):
@@ -113,28 +112,17 @@ def real_images(OPT, data, i, half):
 
 
 def compile_models(state):
-    """Compile the four networks with one forward of two samples each, WITHOUT side effects on them (as adversarial.DeviceGame does):
-    the BatchNorm running statistics a training-mode forward writes are put back.  Both loops start here, so their Philox dropout
-    streams have seen the same number of forwards."""
+    """Compile the four networks with one forward of two samples each, WITHOUT side effects on them (device.compile_models, as
+    adversarial.DeviceGame does).  Both loops start here, so their Philox dropout streams have seen the same number of forwards."""
     s = state
     s.G_PREV.evaluate(); s.D_PREV.evaluate()                                 # :98-99
     s.G.training(); s.D.training()
-    z = np.zeros((2, s.prev[0]), np.float32)
-    s.D_PREV.forward(s.G_PREV.forward(z))
-    s.D.forward(s.G.forward(np.zeros((2, s.OPT.noiseDim), np.float32)))
-    for model in (s.G, s.D):
-        for chunk, _, _ in model._param_chunks():
-            bi = 0
-            for mod in chunk.leaves():
-                if hasattr(mod, "running_mean"):
-                    chunk._net.set_bn_running(bi, mod.running_mean, mod.running_var)
-                    bi += 1
+    device.compile_models(np.zeros((2, s.prev[0]), np.float32), s.G_PREV, s.D_PREV)
+    device.compile_models(np.zeros((2, s.OPT.noiseDim), np.float32), s.G, s.D)
 
 
 class DeviceDistill:
     """The fast loop: one batch of pretrain_with_previous_net.lua:161-242 on device tensors."""
-
-    GUARD_PERIOD = 64       # batches between two f16x3 range-guard scans of the parameters (as adversarial.DeviceGame)
 
     def __init__(self, state):
         s = self.s = state
@@ -144,14 +132,15 @@ class DeviceDistill:
         self.dims, self.pdims = s.dims, image_dims(s.prev[2], s.prev[3], s.prev[4])
         self.npix, self.pnpix = int(np.prod(self.dims)), int(np.prod(self.pdims))
         self.cs, self.pcs = L.COLOR_SPACES[OPT.colorSpace], L.COLOR_SPACES[s.prev[2]]
-        self.gprev, self.gnet = s.G_PREV._net, s.G._net
-        self.dprev, self.dg = _DevGraph(ctx, s.D_PREV), _DevGraph(ctx, s.D)
-        for n in [self.gprev] + self.dprev.nets:
-            n.set_training(False)
-        for n in [self.gnet] + self.dg.nets:
-            n.set_training(True)
-            n.adam_reset()
-        B, m = self.B, ctx.malloc
+        self.gg_prev, self.gg, self.dg_prev, self.dg = (device.DeviceModel(ctx, m) for m in (s.G_PREV, s.G, s.D_PREV, s.D))
+        self.gprev, self.gnet = s.G_PREV._net, s.G._net       # the two G nets by name: not used by the loop, read by its tests
+        for m in (self.gg_prev, self.dg_prev):
+            m.set_training(False)
+        for m in (self.gg, self.dg):
+            m.set_training(True)
+            m.adam_reset()
+        self.mem = device.Buffers(ctx)
+        B, m = self.B, self.mem.malloc
         self.prev_noise, self.noise = m(4 * B * s.prev[0]), m(4 * B * OPT.noiseDim)
         self.images_by_gprev, self.d_input, self.d_input_prev = m(4 * B * self.npix), m(4 * B * self.npix), m(4 * B * self.pnpix)
         self.real_rgb = m(4 * self.half * 3 * self.dims[1] * self.dims[2])
@@ -159,14 +148,6 @@ class DeviceDistill:
         self.hyper_g = L.Hyper(l1=OPT.G_L1, l2=OPT.G_L2, clamp=OPT.G_clamp)
         self.hyper_d = L.Hyper(l1=OPT.D_L1, l2=OPT.D_L2, clamp=OPT.D_clamp)
         self.t = 0
-
-    def _fill(self, dst, dim, method, seed, host):
-        if host is not None:
-            self.ctx.upload(np.ascontiguousarray(host, np.float32).reshape(self.B, dim), dst)
-        elif method == "uniform":
-            self.ctx.fill_uniform(dst, self.B * dim, seed)
-        else:
-            self.ctx.fill_normal(dst, self.B * dim, seed)
 
     def forward(self, real_rgb, prev_noise=None, noise=None):
         """:151-183: both noise tensors, the four forwards and the two conversions.  real_rgb: [batchSize / 2 x 3 x H x W] host array
@@ -176,24 +157,22 @@ class DeviceDistill:
         OPT, (pnd, pmethod) = s.OPT, s.prev[:2]
         _, H, W = self.dims
         self.t += 1
-        if ctx.conv_mode() == "f16x3" and (self.t - 1) % self.GUARD_PERIOD == 0:
-            for n in [self.gprev, self.gnet] + self.dprev.nets + self.dg.nets:      # the *_dev calls below are unguarded
-                n.range_guard_scan()
+        device.range_guard(ctx, self.t, (self.gg_prev, self.gg, self.dg_prev, self.dg))
         s1, s2 = noise_seeds(OPT.seed, self.t)
-        self._fill(self.prev_noise, pnd, pmethod, s1, prev_noise)                                   # :151
-        self._fill(self.noise, OPT.noiseDim, OPT.noiseMethod, s2, noise)                            # :152
+        ctx.fill_noise(self.prev_noise, B * pnd, pmethod, s1, prev_noise)                           # :151
+        ctx.fill_noise(self.noise, B * OPT.noiseDim, OPT.noiseMethod, s2, noise)                    # :152
         shared = min(OPT.noiseDim, pnd)
         ctx.copy2d(self.noise, OPT.noiseDim, self.prev_noise, pnd, B, shared)                       # :155-159
-        old = self.gprev.forward_dev(self.prev_noise, B)                                            # :166
+        old = self.gg_prev.forward(self.prev_noise, B)                                              # :166
         ctx.colorspace_dev(old, self.pcs, self.cs, B, H, W, self.images_by_gprev)                   # :167 (rgb -> rgb: the :clone())
-        self.gnet.zero_grads()
-        self.images_by_g = self.gnet.forward_dev(self.noise, B)                                     # :168
+        self.gg.zero_grads()
+        self.images_by_g = self.gg.forward(self.noise, B)                                           # :168
         real = np.ascontiguousarray(real_rgb, np.float32).reshape(half, 3 * H * W)
         ctx.upload(real, self.real_rgb)
         ctx.colorspace_dev(self.real_rgb, L.GR_CS_RGB, self.cs, half, H, W, self.d_input)           # dataset.lua:153; :173-176
         ctx.copy2d(self.d_input + 4 * half * self.npix, self.npix, self.images_by_gprev, self.npix, half, self.npix)      # :177-180
         ctx.colorspace_dev(self.d_input, self.cs, self.pcs, B, H, W, self.d_input_prev)             # :182
-        self.preds_by_dprev = self.dprev.forward(self.d_input_prev, B)
+        self.preds_by_dprev = self.dg_prev.forward(self.d_input_prev, B)
         self.dg.zero_grads()
         self.preds_by_d = self.dg.forward(self.d_input, B)                                          # :183
 
@@ -201,13 +180,13 @@ class DeviceDistill:
         """the criterion and backward halves of fevalG (:190-194) and fevalD (:218-222)"""
         ctx, B = self.ctx, self.B
         ctx.mse_dev(self.images_by_g, self.images_by_gprev, B * self.npix, self.loss_g, self.grad_g)
-        self.gnet.backward_dev(self.noise, self.grad_g, B, None)
+        self.gg.backward(self.grad_g, B, False)
         ctx.bce_dev(self.preds_by_d, self.preds_by_dprev, B, self.loss_d, self.df)
         self.dg.backward(self.df, B, False)
 
     def step(self):
         """penalty, clamp (:196-208, :224-236) and optim.adam (:241-242), fused"""
-        self.gnet.adam_step(self.hyper_g, self.t)
+        self.gg.adam_step(self.hyper_g, self.t)
         self.dg.adam_step(self.hyper_d, self.t)
 
     def batch(self, real_rgb, prev_noise=None, noise=None, want_loss=False):
@@ -216,29 +195,15 @@ class DeviceDistill:
         self.step()
         if not want_loss:
             return None
-        rd = lambda p: float(self.ctx.download(p, (1,), np.float64)[0])
-        return rd(self.loss_g), rd(self.loss_d)
+        return self.ctx.read_loss(self.loss_g), self.ctx.read_loss(self.loss_d)
 
     def sync_to_host(self):
         self.s.G.pull_params()
         self.s.D.pull_params()
 
     def close(self):
-        self.dprev.close(); self.dg.close()
-        for p in (self.prev_noise, self.noise, self.images_by_gprev, self.d_input, self.d_input_prev, self.real_rgb, self.grad_g, self.df,
-                  self.loss_g, self.loss_d):
-            self.ctx.free(p)
-
-
-def _penalise_and_clamp(PARAMETERS, GRAD_PARAMETERS, f, l1w, l2w, clampv):
-    """:196-208 / :224-236"""
-    if l1w != 0 or l2w != 0:
-        f += l1w * float(np.abs(PARAMETERS).sum(dtype=np.float64))
-        f += l2w * float(np.dot(PARAMETERS.astype(np.float64), PARAMETERS.astype(np.float64))) / 2
-        GRAD_PARAMETERS[...] += np.sign(PARAMETERS) * np.float32(l1w) + PARAMETERS * np.float32(l2w)
-    if clampv != 0:
-        np.clip(GRAD_PARAMETERS, -clampv, clampv, out=GRAD_PARAMETERS)
-    return f
+        for m in (self.gg_prev, self.gg, self.dg_prev, self.dg, self.mem):
+            m.close()
 
 
 def compat_batch(state, i, real_rgb, prev_noise=None, noise=None):
@@ -273,7 +238,7 @@ def compat_batch(state, i, real_rgb, prev_noise=None, noise=None):
         f = s.CRITERION_G.forward(imagesByG, imagesByGprev)                                         # :190
         df_do = s.CRITERION_G.backward(imagesByG, imagesByGprev)                                    # :193
         s.G.backward(batchNoise, df_do)                                                             # :194
-        return _penalise_and_clamp(s.PARAMETERS_G, s.GRAD_PARAMETERS_G, f, OPT.G_L1, OPT.G_L2, OPT.G_clamp), s.GRAD_PARAMETERS_G
+        return penalise_and_clamp(s.PARAMETERS_G, s.GRAD_PARAMETERS_G, f, OPT.G_L1, OPT.G_L2, OPT.G_clamp), s.GRAD_PARAMETERS_G      # :196-208
 
     def fevalD(x):
         if x is not s.PARAMETERS_D:
@@ -282,7 +247,7 @@ def compat_batch(state, i, real_rgb, prev_noise=None, noise=None):
         f = s.CRITERION_D.forward(predsByD, predsByDprev)                                           # :218
         df_do = s.CRITERION_D.backward(predsByD, predsByDprev)                                      # :221
         s.D.backward(imagesDinput, df_do)                                                           # :222
-        return _penalise_and_clamp(s.PARAMETERS_D, s.GRAD_PARAMETERS_D, f, OPT.D_L1, OPT.D_L2, OPT.D_clamp), s.GRAD_PARAMETERS_D
+        return penalise_and_clamp(s.PARAMETERS_D, s.GRAD_PARAMETERS_D, f, OPT.D_L1, OPT.D_L2, OPT.D_clamp), s.GRAD_PARAMETERS_D      # :224-236
 
     optim.adam(fevalG, s.PARAMETERS_G, s.OPTSTATE["adam"]["G"], model=s.G)                          # :241
     optim.adam(fevalD, s.PARAMETERS_D, s.OPTSTATE["adam"]["D"], model=s.D)                          # :242
@@ -319,8 +284,7 @@ def save(OPT, s):
     os.makedirs(OPT.save or ".", exist_ok=True)
     if not OPT.quiet:
         print("Saving networks...")
-    opt = {k: v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}
-    t7.save_checkpoint(filename, G=s.G, D=s.D, opt=opt)
+    t7.save_checkpoint(filename, G=s.G, D=s.D, opt=scripts.opt_table(OPT))
     return filename
 
 
@@ -330,9 +294,7 @@ def main(argv=None):
     ctx.set_conv_mode(OPT.conv_mode)
     if not OPT.quiet:
         print("<trainer> reloading previously trained network: %s" % OPT.network)
-    ck = t7.load_checkpoint(OPT.network)                                                            # :95
-    if "_unconverted" in ck:
-        raise L.GanrevError(f"{OPT.network}: {ck['_unconverted']}")
+    ck = scripts.load_checkpoint(OPT.network)                                                       # :95
     prev = previous_options(ck["opt"])
     s = setup(OPT, ck["G"], ck["D"], prev)
     if not OPT.quiet:

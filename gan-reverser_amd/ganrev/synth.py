@@ -37,6 +37,16 @@ def bernoulli_keep(shape, seed, p_drop):
     return (uniform01(shape, seed) >= p_drop).astype(np.uint8)
 
 
+def synthetic_images(n, dims, seed):
+    """Stand-in for DATASET.loadRandomImages (dataset.lua, out of scope): smooth blobs in [0, 1], different per call."""
+    c, h, w = dims
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    cy, cx = uniform((n, 1, 1, 1), seed, 0.25 * h, 0.75 * h), uniform((n, 1, 1, 1), seed + 1, 0.25 * w, 0.75 * w)
+    r = uniform((n, 1, 1, 1), seed + 2, 0.1 * h, 0.3 * h)
+    img = np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * r * r)).astype(np.float32)
+    return np.ascontiguousarray(np.broadcast_to(img, (n, c, h, w)), dtype=np.float32)
+
+
 def init_params(model, seed):
     """Realistic weights for parity tests: conv/linear U(-sqrt(1/fan_in), +) (= weight-init heuristic stdv*sqrt(3)),
     biases small non-zero (so bias paths are exercised), BN gamma U(0.5,1.5), beta small, running stats non-trivial."""

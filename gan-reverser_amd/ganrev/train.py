@@ -23,7 +23,8 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import adversarial, models, nn_utils, synth, t7
+from . import adversarial, models, nn_utils, pretrain_g, scripts, t7
+from .synth import synthetic_images          # also the name tests and tools import it by: train.synthetic_images
 
 
 def parse(argv=None):
@@ -64,19 +65,9 @@ def parse(argv=None):
     return p.parse_args(argv)
 
 
-def synthetic_images(n, dims, seed):
-    """Stand-in for DATASET.loadRandomImages (dataset.lua, out of scope): smooth blobs in [0, 1], different per call."""
-    c, h, w = dims
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
-    cy, cx = synth.uniform((n, 1, 1, 1), seed, 0.25 * h, 0.75 * h), synth.uniform((n, 1, 1, 1), seed + 1, 0.25 * w, 0.75 * w)
-    r = synth.uniform((n, 1, 1, 1), seed + 2, 0.1 * h, 0.3 * h)
-    img = np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * r * r)).astype(np.float32)
-    return np.ascontiguousarray(np.broadcast_to(img, (n, c, h, w)), dtype=np.float32)
-
-
 def pretrained_G_path(OPT, dims):
     """train.lua:148-149: <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net when it exists and --nopretraining is not given, else None"""
-    path = os.path.join(OPT.G_pretrained_dir, "g_pretrained_%dx%dx%d_nd%d.net" % (dims[0], dims[1], dims[2], OPT.noiseDim))
+    path = os.path.join(OPT.G_pretrained_dir, pretrain_g.checkpoint_name(dims, OPT.noiseDim))
     return path if not OPT.nopretraining and os.path.isfile(path) else None
 
 
@@ -89,10 +80,7 @@ def create_or_load_G(OPT, dims):
         return models.create_G(dims, OPT.noiseDim, True, OPT.seed + 1)
     if not OPT.quiet:
         print("<trainer> loading pretrained G...")
-    ck = t7.load_checkpoint(path)
-    if "_unconverted" in ck:
-        raise L.GanrevError(f"{path}: {ck['_unconverted']}")
-    return ck["G"].training()
+    return scripts.load_checkpoint(path)["G"].training()
 
 
 def save(OPT, env, epoch, quiet=True):
@@ -104,21 +92,18 @@ def save(OPT, env, epoch, quiet=True):
         os.replace(filename, filename + ".old")
     if not quiet:
         print("<trainer> saving network to %s" % filename)
-    t7.save_checkpoint(filename, D=env.MODEL_D, G=env.MODEL_G, opt={k: v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))},
-                       epoch=epoch)
+    t7.save_checkpoint(filename, D=env.MODEL_D, G=env.MODEL_G, opt=scripts.opt_table(OPT), epoch=epoch)
     return filename
 
 
 def main(argv=None):
     OPT = parse(argv)
-    dims = (1 if OPT.colorSpace in ("gray", "y") else 3, OPT.height, OPT.width)
+    dims = scripts.image_dims(OPT.colorSpace, OPT.height, OPT.width)
     ctx = L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
     epoch0 = 1
     if OPT.network:                                                   # train.lua:125-140
-        ck = t7.load_checkpoint(OPT.network)
-        if "_unconverted" in ck:
-            raise L.GanrevError(f"{OPT.network}: {ck['_unconverted']}")
+        ck = scripts.load_checkpoint(OPT.network)
         MODEL_D, MODEL_G, epoch0 = ck["D"], ck["G"], int(ck.get("epoch", 0)) + 1      # train.lua:113  EPOCH = tmp.epoch + 1
     else:                                                             # train.lua:143,160
         MODEL_D = models.create_D(dims, True, OPT.seed)
@@ -148,7 +133,7 @@ def main(argv=None):
             TRAIN_DATA = data[idx]
         else:
             TRAIN_DATA = synthetic_images(nbLoad, dims, OPT.seed * 7919 + env.EPOCH * 3)
-        if OPT.colorSpace in ("y", "yuv", "hsl") and TRAIN_DATA.shape[1] == 3:
+        if scripts.needs_conversion(TRAIN_DATA, OPT.colorSpace):
             # rgb images seen in another space (dataset.lua:153): one gr_colorspace_host call per epoch load
             TRAIN_DATA = nn_utils.rgbToColorSpace(np.ascontiguousarray(TRAIN_DATA, np.float32), OPT.colorSpace)
         if game is None:

@@ -16,7 +16,8 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import models, nn, nn_utils, optim, synth
+from . import models, nn, nn_utils, optim, scripts, synth
+from .adversarial import penalise_and_clamp
 from .parallel import DeviceTrainer
 
 
@@ -98,7 +99,7 @@ def main(argv=None):
         MODEL_R = models.create_R(dims, OPT.noiseDim, OPT.noiseMethod, OPT.fixer, seed=OPT.seed)   # train_r.lua:106
     MODEL_G._ctx = MODEL_R._ctx = ctx
     losses = []
-    opt_table = {k.rstrip("_"): v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}
+    opt_table = scripts.opt_table(OPT)
 
     def save():
         """train_r.lua:227-235: torch.save(<OPT.save>/r_CxHxW_ndN_<method>[_fixer].net, {R=MODEL_R, opt=OPT}).  An --save that names a
@@ -110,8 +111,7 @@ def main(argv=None):
         if not target.endswith((".net", ".t7", ".npz")):
             import os
             os.makedirs(target, exist_ok=True)
-            target = os.path.join(target, "r_%dx%dx%d_nd%d_%s%s.net" % (dims[0], dims[1], dims[2], OPT.noiseDim, OPT.noiseMethod,
-                                                                        "_fixer" if OPT.fixer else ""))
+            target = os.path.join(target, "r_%s_%s%s.net" % (scripts.geometry(dims, OPT.noiseDim), OPT.noiseMethod, "_fixer" if OPT.fixer else ""))
         if target.endswith(".npz"):
             save_model(target, MODEL_R, opt_table)
         else:
@@ -141,11 +141,7 @@ def main(argv=None):
                 f = CRITERION_R.forward(predsByR, noise)                 # :147
                 df_do = CRITERION_R.backward(predsByR, noise)            # :150
                 MODEL_R.backward(images, df_do)                          # :151
-                if OPT.R_L1 != 0 or OPT.R_L2 != 0:                       # :154-160
-                    f += OPT.R_L1 * np.abs(PARAMETERS_R).sum() + OPT.R_L2 * float(np.dot(PARAMETERS_R, PARAMETERS_R)) / 2
-                    GRAD_PARAMETERS_R[...] += np.sign(PARAMETERS_R) * np.float32(OPT.R_L1) + PARAMETERS_R * np.float32(OPT.R_L2)
-                if OPT.R_clamp != 0:                                     # :163-165
-                    np.clip(GRAD_PARAMETERS_R, -OPT.R_clamp, OPT.R_clamp, out=GRAD_PARAMETERS_R)
+                f = penalise_and_clamp(PARAMETERS_R, GRAD_PARAMETERS_R, f, OPT.R_L1, OPT.R_L2, OPT.R_clamp)      # :154-165
                 return f, GRAD_PARAMETERS_R
             MODEL_R.training()
             optim.adam(fevalR, PARAMETERS_R, state, model=MODEL_R)       # :170

@@ -10,7 +10,7 @@ sys.path[:0] = [os.path.join(ROOT, "gan-reverser_amd"), ROOT]
 import numpy as np
 import ganrev._lib as L
 from ganrev import models, pretrain_with_previous_net as P
-from ganrev.train import synthetic_images
+from ganrev.synth import synthetic_images
 
 ctx = L.default_context(); ctx.set_conv_mode("f16x3")
 res = {"device": ctx.info(), "conversions": [], "distillation": []}

@@ -9,7 +9,7 @@ sys.path[:0] = [os.path.join(ROOT, "gan-reverser_amd"), ROOT]
 import numpy as np
 import ganrev._lib as L
 from ganrev import nn, pretrain_g, synth
-from ganrev.train import synthetic_images
+from ganrev.synth import synthetic_images
 
 ctx = L.default_context(); ctx.set_conv_mode("f16x3")
 res = {"device": ctx.info(), "conv_mode": "f16x3", "autoencoder": [], "pool_kernels": []}
