@@ -390,6 +390,22 @@ void launch_scale_copy(const float* src, float* dst, long n, float scale, hipStr
 // none for rgb -> rgb.  A 16-byte form when hw % 4 == 0 and both pointers are 16-byte aligned, a scalar form otherwise.
 enum { CS_RGB = 0, CS_Y = 1, CS_YUV = 2, CS_HSL = 3 };
 void launch_colorspace(const float* in, int from, int to, long batch, long hw, float* out, hipStream_t s);
+// ---- image grids (render.hip): image.toDisplayTensor over tiles gathered from device-resident image tables, with the decorations of
+// apply_r.lua's pictures (include/ganrev.h, gr_image_grid_dev, states the arithmetic).  GridTile is the per-tile metadata the kernels read
+// from a small device array; GridGeom travels in the kernel arguments.
+struct GridTile { long row[2]; float bg[3]; int inset; };          // row[s] = -1: slot s shows the background
+struct GridGeom {
+  const float* src[2]; const GridTile* tiles;
+  int slots, C, Cout, H, W, from;                                  // from = CS_* or -1 (channels copied as they are)
+  int n_tiles, xmaps, padding, margin, TH, TW, cellH, cellW, GH, GW;
+  float inset_rgb[3], fill, lo, hi;
+};
+constexpr int GRID_RANGE_BLOCKS = 256;                             // upper bound of the (min, max) partial pairs of an auto-range grid
+// parts != null: auto range - image_grid_range_kernel leaves up to GRID_RANGE_BLOCKS (min, max) pairs over every pixel inside a tile in
+// parts [2 x GRID_RANGE_BLOCKS floats], the grid kernel reduces them to lo / hi; null: g.lo / g.hi.  One launch, two with auto range.
+void launch_image_grid(const GridGeom& g, float* parts, float* grid, uint8_t* u8, hipStream_t s);
+// out[p] = (((0 + x[rows[0]][p]) + x[rows[1]][p]) + ...) / n for p < d, rows a device array; n == 0: zeros
+void launch_rows_mean(const float* x, long d, const long* rows_dev, int n, float* out, hipStream_t s);
 // several regions zeroed by ONE launch (each a multiple of 16 bytes, 16-byte aligned): the fills a training step needs - the scale slots of both
 // nets, the gradient vector - were three hipMemsetAsync kernels of ~6 us each at batch 256
 struct ZeroJobs { void* ptr[4]; long n16[4]; int n; };

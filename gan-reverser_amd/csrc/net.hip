@@ -2147,6 +2147,80 @@ extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* 
   return GR_OK;
 }
 
+extern "C" int gr_l2_distance_rows_dev(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
+  if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ensure_ws(c, sizeof(double) * (size_t)n); if (r) return r;
+  double* dout = (double*)c->ws;
+  launch_l2_distance_rows(a, b, n, d, dout, c->stream); LAUNCHCHK(c);
+  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ the pictures of apply_r.lua / sample.lua (render.hip)
+extern "C" int gr_rows_mean_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, int n, float* out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table || !out || (n > 0 && !rows)) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: null pointer");
+  if (n_rows <= 0 || d <= 0 || n < 0) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: n_rows %lld and d %lld must be positive, n %d not negative", (long long)n_rows, (long long)d, n);
+  for (int j = 0; j < n; ++j)
+    if (rows[j] < 0 || rows[j] >= n_rows) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: rows[%d] = %lld is outside [0, %lld)", j, (long long)rows[j], (long long)n_rows);
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ensure_ws(c, sizeof(long) * (size_t)(n > 0 ? n : 1)); if (r) return r;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(c->ws, rows, sizeof(long) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                      // the caller's array is its own again when the call returns
+  }
+  launch_rows_mean(table, (long)d, (const long*)c->ws, n, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_image_grid_dev(gr_ctx* c, const float* const* src, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
+                                 const int64_t* rows, int n_tiles, int nrow, int padding, int margin, const float* bg, const uint8_t* inset,
+                                 const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid, uint8_t* u8) {
+  if (!c) return GR_ERR_INVALID;
+  if (slots != 1 && slots != 2) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: slots %d (1 or 2)", slots);
+  if (!src || !n_rows || !rows) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: null pointer");
+  for (int s = 0; s < slots; ++s)
+    if (!src[s] || n_rows[s] <= 0) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: table %d is null or has no rows", s);
+  if (!grid && !u8) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: both outputs are null");
+  if (from_space < -1 || from_space > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: unknown color space <from>: %d", from_space);
+  if ((channels != 1 && channels != 3) || (from_space >= 0 && channels != (from_space == GR_CS_Y ? 1 : 3)))
+    return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: %d channel(s) with from_space %d", channels, from_space);
+  if (h <= 0 || w <= 0 || n_tiles <= 0 || nrow <= 0 || padding < 0 || padding > 64 || margin < 0 || margin > 1)
+    return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: bad geometry (h %d, w %d, n_tiles %d, nrow %d, padding %d in [0, 64], margin %d in {0, 1})", h, w, n_tiles, nrow, padding, margin);
+  if (inset && !inset_rgb) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: inset flags without inset_rgb");
+  if (!auto_range && !(lo <= hi)) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: display range [%g, %g]", (double)lo, (double)hi);
+  GridGeom g{};
+  g.slots = slots; g.C = channels; g.Cout = from_space >= 0 ? 3 : channels; g.H = h; g.W = w; g.from = from_space;
+  g.n_tiles = n_tiles; g.xmaps = nrow < n_tiles ? nrow : n_tiles; g.padding = padding; g.margin = margin;
+  const int ymaps = (n_tiles + g.xmaps - 1) / g.xmaps;
+  const long TH = (long)h + 2 * margin, TW = (long)slots * w + 2 * margin, GH = (TH + padding) * ymaps, GW = (TW + padding) * g.xmaps;
+  if (GH > (1 << 20) || GW > (1 << 20) || GH * GW > (1L << 28)) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: a %ld x %ld grid is too large", GH, GW);
+  g.TH = (int)TH; g.TW = (int)TW; g.cellH = (int)TH + padding; g.cellW = (int)TW + padding; g.GH = (int)GH; g.GW = (int)GW;
+  std::vector<GridTile> tiles((size_t)n_tiles);
+  for (int t = 0; t < n_tiles; ++t) {
+    GridTile& tl = tiles[t];
+    tl.row[0] = tl.row[1] = -1;
+    for (int s = 0; s < slots; ++s) {
+      const int64_t r = rows[(size_t)t * slots + s];
+      if (r < -1 || r >= n_rows[s]) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: row %lld of tile %d, slot %d is outside [-1, %lld)", (long long)r, t, s, (long long)n_rows[s]);
+      tl.row[s] = (long)r;
+    }
+    for (int k = 0; k < 3; ++k) tl.bg[k] = bg ? bg[(size_t)t * 3 + k] : 0.f;
+    tl.inset = inset ? inset[t] != 0 : 0;
+  }
+  for (int k = 0; k < 3; ++k) g.inset_rgb[k] = inset_rgb ? inset_rgb[k] : 0.f;
+  g.fill = fill; g.lo = lo; g.hi = hi;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t tb = (sizeof(GridTile) * (size_t)n_tiles + 255) & ~(size_t)255;
+  int r = ensure_ws(c, tb + sizeof(float) * 2 * GRID_RANGE_BLOCKS); if (r) return r;
+  HIPCHK(c, hipMemcpyAsync(c->ws, tiles.data(), sizeof(GridTile) * (size_t)n_tiles, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));                        // `tiles` dies with this call
+  g.src[0] = src[0]; g.src[1] = slots == 2 ? src[1] : src[0]; g.tiles = (const GridTile*)c->ws;
+  launch_image_grid(g, auto_range ? (float*)((char*)c->ws + tb) : nullptr, grid, u8, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ sample.lua:130-148 findClosestNeighboursOf (neighbours.hip)
 extern "C" int gr_l2_nearest_dev(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
                                  int64_t* idx_out, double* dist_out) {

@@ -123,6 +123,10 @@ _SIGS = {
     "gr_cosine_topk_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gr_cosine_similarity_host": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_float)]),
     "gr_l2_distance_rows_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "gr_l2_distance_rows_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "gr_image_grid_dev": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    _P, _P, _P, C.c_float, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "gr_rows_mean_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, _P]),
     "gr_l2_nearest_host": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     "gr_l2_nearest_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     "gr_kmeans_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
@@ -177,6 +181,13 @@ def _ptr(a):
 
 def f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def grid_shape(n_tiles, slots, channels, h, w, from_space, nrow, padding=0, margin=0):
+    """(Cout, GH, GW) of gr_image_grid_dev's grid: image.toDisplayTensor's layout, xmaps = min(nrow, n_tiles) tiles per row"""
+    xmaps = max(1, min(int(nrow), int(n_tiles)))
+    ymaps = -(-int(n_tiles) // xmaps)
+    return (3 if from_space >= 0 else int(channels), ymaps * (h + 2 * margin + padding), xmaps * (slots * w + 2 * margin + padding))
 
 
 class Context:
@@ -329,6 +340,38 @@ class Context:
         out = np.empty(n, dtype=np.float64)
         self.check(self.lib.gr_l2_distance_rows_host(self.h, _ptr(a2), _ptr(b2), n, a2.shape[1], _ptr(out)), "gr_l2_distance_rows_host")
         return out
+
+    def l2_distance_rows_dev(self, a_dev, b_dev, n, d):
+        """the same on two device-resident tables [n x d] (gr_l2_distance_rows_dev): same kernel, same bits; the distances come to the host"""
+        out = np.empty(int(n), dtype=np.float64)
+        self.check(self.lib.gr_l2_distance_rows_dev(self.h, _ptr(a_dev), _ptr(b_dev), int(n), int(d), _ptr(out)), "gr_l2_distance_rows_dev")
+        return out
+
+    def rows_mean_dev(self, table_dev, n_rows, d, rows, out_dev):
+        """apply_r.lua:233-243: out_dev [d] = the mean of the listed rows of the device table [n_rows x d], added in list order in fp32 and
+        divided once (gr_rows_mean_dev); zeros for an empty list"""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        self.check(self.lib.gr_rows_mean_dev(self.h, _ptr(table_dev), int(n_rows), int(d), _ptr(rows) if rows.size else None, rows.size, _ptr(out_dev)),
+                   "gr_rows_mean_dev")
+
+    def image_grid_dev(self, srcs, n_rows, channels, h, w, from_space, rows, nrow, padding=0, margin=0, bg=None, inset=None,
+                       inset_rgb=None, fill=1.0, auto_range=False, lo=0.0, hi=1.0, grid_dev=None, u8_dev=None):
+        """gr_image_grid_dev (include/ganrev.h states the layout and the arithmetic): srcs = the device tables of the 1 or 2 slots,
+        n_rows their row counts, rows [n_tiles x slots] int64 (-1: background), bg [n_tiles x 3], inset [n_tiles] flags.
+        -> (Cout, GH, GW) of the grid written to grid_dev (floats, planar) and / or u8_dev (bytes, interleaved)."""
+        slots = len(srcs)
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, max(slots, 1))
+        n_tiles = rows.shape[0]
+        tabs = (_P * max(slots, 1))(*[_ptr(p) for p in srcs])
+        nr = np.ascontiguousarray(n_rows, dtype=np.int64).reshape(-1)
+        bg = None if bg is None else np.ascontiguousarray(bg, dtype=np.float32).reshape(n_tiles, 3)
+        inset = None if inset is None else np.ascontiguousarray(inset, dtype=np.uint8).reshape(n_tiles)
+        inset_rgb = None if inset_rgb is None else np.ascontiguousarray(inset_rgb, dtype=np.float32).reshape(3)
+        rc = self.lib.gr_image_grid_dev(self.h, tabs, _ptr(nr), slots, int(channels), int(h), int(w), int(from_space), _ptr(rows), n_tiles,
+                                        int(nrow), int(padding), int(margin), _ptr(bg), _ptr(inset), _ptr(inset_rgb), float(fill),
+                                        int(bool(auto_range)), float(lo), float(hi), _ptr(grid_dev), _ptr(u8_dev))
+        self.check(rc, "gr_image_grid_dev")
+        return grid_shape(n_tiles, slots, channels, h, w, from_space, nrow, padding, margin)
 
     L2_NEAREST_MAX_Q = 64       # queries per gr_l2_nearest_* call (include/ganrev.h)
 

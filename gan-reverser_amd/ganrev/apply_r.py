@@ -7,15 +7,15 @@
   detectAnomalies              apply_r.lua:355-390   1 - torch.dist(image, fixed image), lowest `threshold` share = anomalies
   createClusterImages          apply_r.lua:197-231   unsup.kmeans on the recovered noise, nearest-centroid pass, per-cluster lists
 
-Everything image-writing (image.toDisplayTensor / image.save / colour conversion) is out of scope: these functions return
-the tensors / index lists the reference would have rendered.
+These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
+frames and fields apply_r.lua draws) come from ganrev.render, on the GPU, and main() writes them with --render.
 """
 import math
 
 import numpy as np
 
 from . import _lib as L
-from .nn_utils import DeviceTensor, forwardBatched
+from .nn_utils import DeviceTensor, forwardBatched, forwardBatchedDev
 
 
 def embed(model_g, model_r, noise, batchSize=32, model_r_fixer=None):
@@ -143,10 +143,71 @@ def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attri
     return centroids, counts, clusters, faces
 
 
+def createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, centroids0=None, seed=1, closest=False):
+    """createClusterImages with the images resident on the GPU (`images` a DeviceTensor [N x C x H x W], `attributes` the small host
+    table [N x nd]): k-means and the assignment as there, the average faces by gr_rows_mean_dev - the cluster's rows added in the
+    cluster's order in fp32 and divided once, as the reference's face:add / face:div (apply_r.lua:233-243).  createClusterImages
+    averages in float64 on the host: the faces may differ from it in the last bits.
+    -> (centroids, counts, clusters, faces) with faces a DeviceTensor [nbClusters x C x H x W] (the caller frees it)."""
+    attributes = np.asarray(attributes, np.float32)
+    N, d = attributes.shape
+    if centroids0 is None:
+        centroids0 = initialCentroids(nbClusters, d, seed)
+    ctx = images.ctx
+    centroids, counts, _ = ctx.kmeans(attributes, nbClusters, nbIterations, centroids0)            # :198
+    label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
+    chw = images.size // images.shape[0]
+    faces = DeviceTensor(ctx, (nbClusters,) + tuple(images.shape[1:]))
+    clusters = []
+    for j in range(nbClusters):
+        rows = np.nonzero(label == j)[0]
+        keep = rows[np.argsort(-sim[rows], kind="stable")][:nbMaxPerCluster]                        # :221-227
+        clusters.append([(int(r), float(sim[r])) for r in keep])
+        ctx.rows_mean_dev(images.ptr, images.shape[0], chw, keep, faces.ptr + 4 * chw * j)          # :233-243 (zeros for an empty cluster)
+    return centroids, counts, clusters, faces
+
+
+def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributesFixer, by_attr, by_pix):
+    """The pictures of apply_r.lua:158-191 from the device-resident tables (`images` [N x C x H x W] and `attributesFixer` [N x nd] as
+    DeviceTensors, `attributes` on the host): cluster_%02d, similar_attributes_%02d / similar_pixelwise_%02d, fixed_pairs,
+    fixed_images_<n>[_unfixed] and anomalies as PNG files out(name).  Only the rows a picture shows are read; nothing but the finished
+    pictures and the per-image distances leaves the GPU.
+    -> what the run's arrays and summary are written from: dict(clusters = createClusterImagesDev's tuple with the faces on the host,
+    fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple)."""
+    from . import render
+    ctx, N = images.ctx, images.shape[0]
+    chw = images.size // N
+    centroids, counts, clusters, faces = createClusterImagesDev(20, 15, 64 + 7, images, attributes, seed=OPT.seed)      # :158-163
+    for j, cl in enumerate(clusters):
+        if cl:                                                                                                          # :249
+            render.cluster_grid(images, [r for r, _ in cl], colorSpace, face_dev=faces.rows(j, j + 1), path=out("cluster_%02d.png" % (j + 1)))
+    faces_host = faces.numpy(); faces.free()
+    if by_attr is not None:                                                                                             # :170-172
+        for i in range(len(by_attr)):
+            render.similar_grid(images, by_attr[i], colorSpace, path=out("similar_attributes_%02d.png" % (i + 1)))
+            render.similar_grid(images, by_pix[i], colorSpace, path=out("similar_pixelwise_%02d.png" % (i + 1)))
+    MODEL_G.evaluate()
+    nbFixed, nbCalc = min(512 + 16, N), min(1024, N)
+    fixed = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbFixed), OPT.batchSize)                                 # :349
+    render.fixed_pairs_grid(images, fixed, min(52, N), colorSpace, path=out("fixed_pairs.png"))                         # :325-342
+    render.fixed_images_grid(images, nbFixed, path=out("fixed_images_%d_unfixed.png" % nbFixed))                        # :345-347
+    render.fixed_images_grid(fixed, nbFixed, path=out("fixed_images_%d.png" % nbFixed))                                 # :350-351
+    fixed_host = fixed.numpy(); fixed.free()
+    fixedCalc = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbCalc), OPT.batchSize)                              # :360-363
+    dist = 1.0 - ctx.l2_distance_rows_dev(images.ptr, fixedCalc.ptr, nbCalc, chw)                                       # :366, scored where the images lie
+    fixedCalc.free()
+    srt = np.sort(dist)
+    below = srt[max(int(math.floor(nbCalc * 0.15)) - 1, 0)]                                                             # :371-372
+    is_anom = dist <= below
+    render.anomalies_grid(images, is_anom[:min(512 + 16, nbCalc)], colorSpace, path=out("anomalies.png"))               # :374-389
+    return dict(clusters=(centroids, counts, clusters, list(faces_host)), fixed=fixed_host, anomalies=(dist, below, is_anom))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
-# apply_r.lua:25-193 main(): the whole analysis as one run.  Image writing (image.toDisplayTensor / image.save, apply_r.lua:136,
-# 233-262, 283-300, 336-352, 374-390) is out of scope: what the reference would have rendered is written as arrays (.npy) and one
-# summary.json under --writeTo.  G / R / R_fixer come from Torch7 checkpoints (ganrev.t7: train.lua:256, train_r.lua:234) or, with
+# apply_r.lua:25-193 main(): the whole analysis as one run.  What the reference computes is written as arrays (.npy) and one
+# summary.json under --writeTo; with --render the pictures it saves (apply_r.lua:137-138, 245-258, 283-298, 325-351, 374-389) are written
+# beside them as PNG, under the reference's names: variations, cluster_%02d, similar_attributes_%02d, similar_pixelwise_%02d, fixed_pairs,
+# fixed_images_528[_unfixed], anomalies (the counts clamp to --nbImages).  G / R / R_fixer come from Torch7 checkpoints (ganrev.t7: train.lua:256, train_r.lua:234) or, with
 # --synthetic, from random-initialised nets of the requested shape (a smoke run: no trained checkpoint exists in this repository).
 def parse(argv=None):
     import argparse
@@ -163,6 +224,7 @@ def parse(argv=None):
     p.add_argument("--host", action="store_true", help="the host-tensor loop (forwardBatched per chunk, as apply_r.lua spells it) instead of the device-resident pipeline")
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
+    p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
     return p.parse_args(argv)
 
 
@@ -177,7 +239,7 @@ def main(argv=None):
     say = (lambda *a: None) if OPT.quiet else print
     if OPT.synthetic:
         c, h, w, nd = (int(v) for v in OPT.synthetic.split("x"))
-        dims, method = (c, h, w), "normal"
+        dims, method, colorSpace = (c, h, w), "normal", "y" if c == 1 else "rgb"
         MODEL_G = models.create_G(dims, nd, seed=OPT.seed); synth.init_params(MODEL_G, OPT.seed)
         MODEL_R = models.create_R(dims, nd, method, False, seed=OPT.seed + 1); synth.init_params(MODEL_R, OPT.seed + 1)
         MODEL_R_FIXER = models.create_R(dims, nd, method, True, seed=OPT.seed + 2); synth.init_params(MODEL_R_FIXER, OPT.seed + 2)
@@ -185,7 +247,7 @@ def main(argv=None):
         from . import t7
         ck = t7.load_checkpoint(OPT.G)                                        # apply_r.lua:62-69
         MODEL_G, o = ck["G"], ck.get("opt", {})
-        nd, method = int(o.get("noiseDim", 32)), o.get("noiseMethod", "normal")
+        nd, method, colorSpace = int(o.get("noiseDim", 32)), o.get("noiseMethod", "normal"), o.get("colorSpace", "rgb")
         dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
         MODEL_R = t7.load_checkpoint(OPT.R)["R"]                              # :92-94
         MODEL_R_FIXER = t7.load_checkpoint(OPT.R_fixer)["R"]                  # :101-103
@@ -204,7 +266,14 @@ def main(argv=None):
     var_noise = np.repeat(noise1, nd * nbSteps, axis=0)
     for i in range(nd):
         var_noise[i * nbSteps:(i + 1) * nbSteps, i] = steps
-    np.save(out("variations.npy"), forwardBatched(MODEL_G, var_noise, OPT.batchSize).reshape((nd, nbSteps) + tuple(dims)))
+    variations = forwardBatched(MODEL_G, var_noise, OPT.batchSize)
+    np.save(out("variations.npy"), variations.reshape((nd, nbSteps) + tuple(dims)))
+    if OPT.render:
+        from . import render
+        dv = DeviceTensor(ctx, variations.shape)
+        ctx.upload(variations, dv.ptr)
+        render.variations_grid(dv, nbSteps, path=out("variations.png"))                                                   # :137-138
+        dv.free()
 
     say("Generating images, converting images to attributes...")             # :141-153
     N = OPT.nbImages
@@ -214,30 +283,38 @@ def main(argv=None):
         noise = dn.numpy(); dn.free()
         images, attributes, attributesFixer = embed(MODEL_G, MODEL_R, noise, OPT.batchSize, MODEL_R_FIXER)
         by_attr, by_pix = createSimilaritySearch(5, 100, images, attributes) if N >= 500 else (None, None)
+        if OPT.render:                                                        # the same pictures from uploaded tables
+            di, df = DeviceTensor(ctx, images.shape), DeviceTensor(ctx, attributesFixer.shape)
+            ctx.upload(images, di.ptr); ctx.upload(attributesFixer, df.ptr)
     else:
         di, da, df = embed_dev(MODEL_G, MODEL_R, dn, OPT.batchSize, MODEL_R_FIXER, keep_images=True, dims=dims)
         by_attr, by_pix = createSimilaritySearchDev(5, 100, da, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
         noise, images, attributes, attributesFixer = dn.numpy(), di.numpy(), da.numpy(), df.numpy()
-        for t in (dn, di, da, df):
+        for t in (dn, da) if OPT.render else (dn, di, da, df):
             t.free()
     ctx.synchronize()
     summary["embed_and_search_seconds"] = round(time.perf_counter() - t0, 4)
+    rendered = None
+    if OPT.render:
+        say("Rendering...")                                                   # from di / df, before they are freed
+        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, attributes, df, by_attr, by_pix)
+        di.free(); df.free()
     np.save(out("attributes.npy"), attributes); np.save(out("attributes_fixer.npy"), attributesFixer)
     if by_attr is not None:
         np.save(out("similar_by_attributes.npy"), by_attr); np.save(out("similar_by_pixels.npy"), by_pix)
 
     say("Clustering...")                                                      # :158-162
-    centroids, counts, clusters, faces = createClusterImages(20, 15, 64 + 7, images, attributes, seed=OPT.seed)
+    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(20, 15, 64 + 7, images, attributes, seed=OPT.seed)
     np.save(out("cluster_centroids.npy"), centroids); np.save(out("cluster_average_faces.npy"), np.stack(faces))
     summary["cluster_sizes"] = [len(c) for c in clusters]; summary["cluster_total_counts"] = [float(v) for v in counts]
 
     say("Fixing faces...")                                                    # :178-181
     nbFixed = min(512 + 16, N)
-    np.save(out("fixed_faces.npy"), fixFaces(nbFixed, MODEL_G, attributesFixer, OPT.batchSize))
+    np.save(out("fixed_faces.npy"), rendered["fixed"] if rendered else fixFaces(nbFixed, MODEL_G, attributesFixer, OPT.batchSize))
 
     say("Detecting anomalies...")                                             # :186-191
     nbCalc = min(1024, N)
-    dist, below, is_anom = detectAnomalies(nbCalc, 0.15, images, MODEL_G, attributesFixer, OPT.batchSize)
+    dist, below, is_anom = rendered["anomalies"] if rendered else detectAnomalies(nbCalc, 0.15, images, MODEL_G, attributesFixer, OPT.batchSize)
     np.save(out("anomaly_distances.npy"), dist)
     summary.update(anomaly_below=float(below), anomalies=int(is_anom.sum()))
     json.dump(summary, open(out("summary.json"), "w"), indent=1)

@@ -4,10 +4,13 @@ each of the 16 best.
 
     python -m ganrev.sample --save logs --network adversarial.net --data images.npy --writeTo samples [--neighbours]
 
-Same option names and defaults as sample.lua:9-24.  Image grids and image files, colour-space conversion and the dataset loader are
-out of scope: the training set comes from --data (an [N x C x H x W] float32 .npy, as in ganrev.train), and each run writes one
-samples_<run>.npz into --writeTo with best, best_pred, worst, worst_pred, random and, with --neighbours, neighbour_idx,
-neighbour_dist and neighbours.  Random choices use numpy's generator seeded by --seed (Torch's generator is not reproduced).
+Same option names and defaults as sample.lua:9-24.  The dataset loader is out of scope: the training set comes from --data (an
+[N x C x H x W] float32 .npy, as in ganrev.train), and each run writes one samples_<run>.npz into --writeTo with best, best_pred,
+worst, worst_pred, random and, with --neighbours, neighbour_idx, neighbour_dist and neighbours.  With --render the run's pictures
+(sample.lua:96-118: random1024, random256, best, worst, random and best_*_neighbours, named <name>_<run>_base) are written beside it
+as PNG - toGrid / toNeighboursGrid (sample.lua:166-185) on the GPU through ganrev.render, display range taken from the picture itself
+as image.toDisplayTensor does without min / max.  trainset_s1 (sample.lua:77-83) needs the dataset loader and is not written.  Random
+choices use numpy's generator seeded by --seed (Torch's generator is not reproduced).
 """
 import argparse
 import os
@@ -35,6 +38,7 @@ def parse(argv=None):
     p.add_argument("--width", type=int, default=32)
     p.add_argument("--dataset", default="NONE", help="(the dataset loader is out of scope: use --data)")
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy: the training set --neighbours searches")
+    p.add_argument("--render", action="store_true", help="also write the run's image grids as PNG files (ganrev.render)")
     return p.parse_args(argv)
 
 
@@ -68,6 +72,19 @@ def findClosestNeighboursOf(ctx, images, table_dev, n, d, k=1):
     return ctx.l2_nearest(None, np.asarray(images, np.float32).reshape(len(images), -1), k, table_dev=table_dev, n=n, d=d)
 
 
+def toGrid(ctx, images, nrow, colorSpace, path=None):
+    """sample.lua:166-168: image.toDisplayTensor{input = toRgb(images), nrow = nrow}, no min / max -> uint8 [GH x GW x 3]; the host
+    images are uploaded, the grid is rendered on the GPU"""
+    from . import render
+    images = np.ascontiguousarray(images, dtype=np.float32)
+    t = nn_utils.DeviceTensor(ctx, images.shape)
+    try:
+        ctx.upload(images, t.ptr)
+        return render.grid(t, np.arange(len(images)), nrow, colorSpace, auto_range=True, path=path)
+    finally:
+        t.free()
+
+
 def main(argv=None):
     opt = parse(argv)
     if opt.gpu < 0:
@@ -92,8 +109,15 @@ def main(argv=None):
             print("Settings:", dims)
         best, best_pred = nn_utils.sortImagesByPrediction(D, images, False, 64, opt.batchSize)
         worst, worst_pred = nn_utils.sortImagesByPrediction(D, images, True, 64, opt.batchSize)
+        if opt.render:                                                # sample.lua:96-97 (drawn before the 64 random ones, as there)
+            name = lambda what: os.path.join(opt.writeTo, "%s_%04d_base.png" % (what, run))
+            toGrid(ctx, images[rng.permutation(len(images))[:256]], 16, opt.colorSpace, name("random256"))
+            toGrid(ctx, images, 32, opt.colorSpace, name("random1024"))
         random = images[rng.choice(len(images), 64, replace=False)]
         out = dict(best=best, best_pred=best_pred, worst=worst, worst_pred=worst_pred, random=random)
+        if opt.render:                                                # sample.lua:107-109
+            for what, imgs in (("best", best), ("worst", worst), ("random", random)):
+                toGrid(ctx, imgs, 8, opt.colorSpace, name(what))
         if opt.neighbours:                                            # sample.lua:115-123
             n, d = len(data), int(np.prod(data.shape[1:]))
             if d != int(np.prod(best.shape[1:])):
@@ -101,6 +125,13 @@ def main(argv=None):
             table_dev = ctx.upload(data)                              # once per run
             try:
                 idx, dist = findClosestNeighboursOf(ctx, best[:16], table_dev, n, d)
+                if opt.render:                                        # sample.lua:118, from the table where it lies
+                    from . import render
+                    bt = nn_utils.DeviceTensor(ctx, best[:16].shape)
+                    ctx.upload(best[:16], bt.ptr)
+                    render.neighbours_grid(bt, np.arange(len(idx)), nn_utils.DeviceTensor(ctx, data.shape, table_dev), idx[:, 0], opt.colorSpace,
+                                           path=os.path.join(opt.writeTo, "best_%04d_neighbours_base.png" % run))
+                    bt.free()
             finally:
                 ctx.free(table_dev)
             out.update(neighbour_idx=idx[:, 0], neighbour_dist=dist[:, 0], neighbours=data[idx[:, 0]])

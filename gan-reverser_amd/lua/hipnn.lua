@@ -55,6 +55,11 @@ int gr_fill_normal_dev(gr_ctx*, float* dst_dev, int64_t n, uint64_t seed);
 int gr_fill_uniform_dev(gr_ctx*, float* dst_dev, int64_t n, float lo, float hi, uint64_t seed);
 int gr_colorspace_dev(gr_ctx*, const float* in_dev, int from, int to, int64_t batch, int h, int w, float* out_dev);     /* utils/nn_utils.lua:133-246; 0 rgb, 1 y, 2 yuv, 3 hsl */
 int gr_colorspace_host(gr_ctx*, const float* in_host, int from, int to, int64_t batch, int h, int w, float* out_host);
+int gr_l2_distance_rows_dev(gr_ctx*, const float* a_dev, const float* b_dev, int64_t n, int64_t d, double* out_host);
+int gr_image_grid_dev(gr_ctx*, const float* const* src_dev, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
+                      const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,
+                      const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid_dev, uint8_t* u8_dev);     /* image.toDisplayTensor + decorations, apply_r.lua / sample.lua */
+int gr_rows_mean_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_host, int n, float* out_dev);   /* apply_r.lua:233-243 */
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);
 float* gr_net_output_dev(gr_net*);
 int gr_net_forward_batched_dev(gr_net*, const float* in_dev, int64_t rows, int batch, float* out_dev);   /* utils/nn_utils.lua:5-33 */

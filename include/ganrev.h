@@ -255,6 +255,44 @@ int gr_search_stats(gr_ctx* ctx, int64_t* reruns);
 
 /* ---- apply_r.lua:355-372 (detectAnomalies): out[i] = torch.dist(a[i], b[i]) = sqrt(sum_j (a_ij - b_ij)^2), rows of length d ---- */
 int gr_l2_distance_rows_host(gr_ctx* ctx, const float* a_host, const float* b_host, int64_t n, int64_t d, double* out_host);
+/* the same kernel on two device-resident tables [n x d] (the images and their fixed versions where embed / G left them); the n distances
+ * come back to the host, the call is synchronous.  Bit-identical to gr_l2_distance_rows_host on the same values. */
+int gr_l2_distance_rows_dev(gr_ctx* ctx, const float* a_dev, const float* b_dev, int64_t n, int64_t d, double* out_host);
+
+/* ---- The pictures apply_r.lua and sample.lua end in, rendered from device-resident image tables (csrc/render.hip) ----
+ *
+ * gr_image_grid_dev = image.toDisplayTensor over tiles gathered from up to two tables, with the reference's decorations (apply_r.lua:137,
+ * 256,286-297,325-341,346-350,375-388; sample.lua:166-185).  Tables are [n_rows[s] x channels x h x w] fp32, channels 1 or 3.
+ *   layout     n_tiles tiles, xmaps = min(nrow, n_tiles) per row, ymaps = ceil(n_tiles / xmaps) rows.  A tile is TH x TW with TH = h + 2 margin,
+ *              TW = slots w + 2 margin; a cell is the tile + padding, the tile sits at offset padding / 2 (integer) in its cell; the grid is
+ *              GH x GW = ymaps (TH + padding) x xmaps (TW + padding).
+ *   tile t     slot s (0 .. slots-1, side by side) shows row rows_host[t slots + s] of src_dev[s]; a row of -1 leaves the tile's background
+ *              bg_host[3t ..] (null: 0), which also paints the margin ring (margin 0 or 1): the blue field of fixed_pairs, the black or red
+ *              frame of anomalies.  inset_host[t] != 0 (null: none) overwrites the outermost pixel ring of every slot image of the tile with
+ *              inset_rgb: the blue frame drawn over the needle of similar_*.
+ *   colour     from_space = GR_CS_*: the slot image goes through the toRgb arithmetic of gr_colorspace_* (same device functions), the grid
+ *              has 3 channels.  from_space = -1: channels copied as they are, the grid has `channels` channels (fixed_images_*, which skip
+ *              toRgb in the reference); backgrounds and inset_rgb then use their first `channels` entries.
+ *   range      every pixel inside a tile - image, margin or empty slot - after conversion and decoration is a value v.  auto_range = 0:
+ *              lo, hi as given (lo <= hi).  auto_range = 1 (toDisplayTensor without min / max, sample.lua:166-168): lo = min v + 0, hi = max v + 0
+ *              over all of them (compare-selects, a NaN never wins; the + 0 makes a zero bound +0), found by a reduction launch.
+ *              out = hi == lo ? 0 : (clamp(v, lo, hi) - lo) / (hi - lo)   - compare-select clamp, two subtractions, one division, fp32.
+ *              Pixels no tile covers (padding, the unfilled end of the last row) get `fill` as it is.
+ *   outputs    grid_dev [Cout x GH x GW] floats and / or u8_dev [GH x GW x Cout] bytes, u8 = (uint8) min(255, max(0, trunc(out * 255 + 0.5)))
+ *              (one multiplication, one addition).  This quantisation is this library's choice: the reference writes lossy JPEG, so no byte
+ *              parity with its files exists or is claimed.
+ * One launch on the ctx stream, two with auto_range; the host arrays are uploaded by the call and are the caller's again when it returns.
+ * GR_ERR_INVALID with a gr_last_error message, and no launch, for: slots outside {1, 2}, a null table, both outputs null, channels / from_space
+ * that do not fit, h, w, n_tiles, nrow < 1, padding outside [0, 64], margin outside {0, 1}, a row outside [-1, n_rows[s]), lo > hi, a grid
+ * beyond 2^28 pixels.
+ *
+ * gr_rows_mean_dev: out_dev[p] = (((0 + x[rows[0]][p]) + x[rows[1]][p]) + ...) / n for p < d - the average face of a cluster as
+ * apply_r.lua:233-243 computes it (face:add per image in list order, one face:div), fp32 throughout; n == 0 writes zeros.  table_dev is
+ * [n_rows x d]; a row outside [0, n_rows) returns GR_ERR_INVALID without a launch. ---- */
+int gr_image_grid_dev(gr_ctx* ctx, const float* const* src_dev, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
+                      const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,
+                      const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid_dev, uint8_t* u8_dev);
+int gr_rows_mean_dev(gr_ctx* ctx, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_host, int n, float* out_dev);
 
 /* ---- sample.lua:130-148 findClosestNeighboursOf: the k nearest table rows of each query by torch.dist ----
  * Contract: for each query q [d] and table row x_j [d] (table [n x d], fp32, contiguous)
