@@ -390,6 +390,22 @@ void launch_scale_copy(const float* src, float* dst, long n, float scale, hipStr
 // none for rgb -> rgb.  A 16-byte form when hw % 4 == 0 and both pointers are 16-byte aligned, a scalar form otherwise.
 enum { CS_RGB = 0, CS_Y = 1, CS_YUV = 2, CS_HSL = 3 };
 void launch_colorspace(const float* in, int from, int to, long batch, long hw, float* out, hipStream_t s);
+// ---- dataset.lua's per-image work (dataset.hip; include/ganrev.h, gr_image_scale_dev / gr_dataset_images_dev, states the arithmetic).
+// ScaleAxis = one pass of image.scale's scaleLinear_rowcol(src_len, dst_len); scale is rounded to fp32 once, on the host.
+enum { SCALE_COPY = 0, SCALE_UP = 1, SCALE_DOWN = 2, SCALE_REPLICATE = 3 };
+struct ScaleAxis { int mode, src_len, dst_len; float scale; };
+constexpr int SCALE_MAX_LEN = 32768;                               // per side: keeps every fp32 index product below 2^15, far from an integer it must not reach
+inline ScaleAxis scale_axis(int src_len, int dst_len) {
+  if (dst_len == src_len) return ScaleAxis{SCALE_COPY, src_len, dst_len, 1.f};
+  if (dst_len < src_len) return ScaleAxis{SCALE_DOWN, src_len, dst_len, (float)src_len / (float)dst_len};
+  if (src_len == 1) return ScaleAxis{SCALE_REPLICATE, src_len, dst_len, 0.f};
+  return ScaleAxis{SCALE_UP, src_len, dst_len, (float)(src_len - 1) / (float)(dst_len - 1)};
+}
+// in [nplanes x sh x sw] -> out [nplanes x dh x dw]; ay = scale_axis(sh, dh), ax = scale_axis(sw, dw).  One launch; 16-byte stores when dw % 4 == 0
+// and out is 16-byte aligned, a scalar form otherwise.
+void launch_image_scale(const float* in, long nplanes, const ScaleAxis& ay, const ScaleAxis& ax, float* out, hipStream_t s);
+// in uint8 [n x sh x sw x sc] (sc 1, 3 or 4) -> out [n x (1|3) x dh x dw] in colour space `to`, normalised to [-1, 1] when normalize != 0.  One launch.
+void launch_dataset_images(const uint8_t* in, long n, int sc, const ScaleAxis& ay, const ScaleAxis& ax, int to, int normalize, float* out, hipStream_t s);
 // ---- image grids (render.hip): image.toDisplayTensor over tiles gathered from device-resident image tables, with the decorations of
 // apply_r.lua's pictures (include/ganrev.h, gr_image_grid_dev, states the arithmetic).  GridTile is the per-tile metadata the kernels read
 // from a small device array; GridGeom travels in the kernel arguments.

@@ -1748,6 +1748,51 @@ extern "C" int gr_colorspace_host(gr_ctx* c, const float* in, int from, int to, 
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ dataset.lua:111-116,149-153: image.scale and the loader's fused path (dataset.hip)
+// GR_SCALE_MAX_ELEMS bounds both tensors of a call: the kernels index with 64-bit integers, the bound keeps every product of the geometry far inside them
+static const int64_t GR_SCALE_MAX_ELEMS = (int64_t)1 << 40;
+static int scale_check(gr_ctx* c, const char* who, const void* in, const void* out, int64_t n, int64_t per_in, int sh, int sw, int dh, int dw, int64_t per_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!in || !out) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);
+  if (n < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1) return fail(c, GR_ERR_INVALID, "%s: n %lld, source %d x %d, target %d x %d must be positive", who, (long long)n, sh, sw, dh, dw);
+  if (sh > SCALE_MAX_LEN || sw > SCALE_MAX_LEN || dh > SCALE_MAX_LEN || dw > SCALE_MAX_LEN)
+    return fail(c, GR_ERR_INVALID, "%s: source %d x %d, target %d x %d: a side is too large (at most %d)", who, sh, sw, dh, dw, SCALE_MAX_LEN);
+  const int64_t ein = per_in * sh * sw, eout = per_out * dh * dw;              // per_* <= 2^31, a side <= 2^15: below 2^61
+  if (n > GR_SCALE_MAX_ELEMS / ein || n > GR_SCALE_MAX_ELEMS / eout) return fail(c, GR_ERR_INVALID, "%s: %lld images are too large a batch (at most 2^40 elements per tensor)", who, (long long)n);
+  return GR_OK;
+}
+extern "C" int gr_image_scale_dev(gr_ctx* c, const float* in, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out) {
+  if (c && planes < 1) return fail(c, GR_ERR_INVALID, "gr_image_scale: planes %d must be positive", planes);
+  int r = scale_check(c, "gr_image_scale", in, out, n, planes, sh, sw, dh, dw, planes); if (r) return r;
+  if (in == out) return fail(c, GR_ERR_INVALID, "gr_image_scale: in place is not supported");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_image_scale(in, (long)n * planes, scale_axis(sh, dh), scale_axis(sw, dw), out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_image_scale_host(gr_ctx* c, const float* in, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out) {
+  if (c && planes < 1) return fail(c, GR_ERR_INVALID, "gr_image_scale: planes %d must be positive", planes);
+  int r = scale_check(c, "gr_image_scale", in, out, n, planes, sh, sw, dh, dw, planes); if (r) return r;
+  if (in == out) return fail(c, GR_ERR_INVALID, "gr_image_scale: in place is not supported");
+  const size_t nin = (size_t)n * planes * sh * sw, nout = (size_t)n * planes * dh * dw;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nin_pad = (nin + 3) & ~(size_t)3;                       // keeps the output 16-byte aligned behind the input
+  r = ensure_ws(c, sizeof(float) * (nin_pad + nout)); if (r) return r;
+  float* din = (float*)c->ws; float* dout = din + nin_pad;
+  HIPCHK(c, hipMemcpyAsync(din, in, sizeof(float) * nin, hipMemcpyHostToDevice, c->stream));
+  launch_image_scale(din, (long)n * planes, scale_axis(sh, dh), scale_axis(sw, dw), dout, c->stream); LAUNCHCHK(c);
+  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GR_OK;
+}
+extern "C" int gr_dataset_images_dev(gr_ctx* c, const uint8_t* in, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize, float* out) {
+  if (c && sc != 1 && sc != 3 && sc != 4) return fail(c, GR_ERR_INVALID, "gr_dataset_images: %d source channels (1, 3 or 4)", sc);
+  if (c && (to_space < GR_CS_RGB || to_space > GR_CS_HSL)) return fail(c, GR_ERR_INVALID, "gr_dataset_images: unknown color space <to>: %d", to_space);
+  int r = scale_check(c, "gr_dataset_images", in, out, n, sc, sh, sw, dh, dw, to_space == GR_CS_Y ? 1 : 3); if (r) return r;
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_dataset_images(in, (long)n, sc, scale_axis(sh, dh), scale_axis(sw, dw), to_space, normalize != 0, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ optimiser
 static AdamConsts adam_consts(const gr_hyper* h, int t) {
   AdamConsts k{};

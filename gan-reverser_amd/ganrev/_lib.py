@@ -141,6 +141,9 @@ _SIGS = {
     "gr_add_dev": (C.c_int, [_P, _P, _P, C.c_int64]),
     "gr_colorspace_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P]),
     "gr_colorspace_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P]),
+    "gr_image_scale_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "gr_image_scale_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "gr_dataset_images_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gr_conv3_forward_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gr_conv3_backward_data_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gr_conv3_backward_weight_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -286,6 +289,28 @@ class Context:
         out = np.empty((b, planes(to) if 0 <= int(to) <= 3 else 3, h, w), np.float32)
         self.check(self.lib.gr_colorspace_host(self.h, _ptr(images), int(from_), int(to), b, h, w, _ptr(out)), "gr_colorspace_host")
         return out
+
+    def image_scale_dev(self, in_dev, n, planes, sh, sw, dh, dw, out_dev):
+        """image.scale(src, dw, dh), bilinear (dataset.lua:112,150), on a device tensor [n x planes x sh x sw] -> out_dev [n x planes x dh x dw].
+        One launch on the context's stream."""
+        self.check(self.lib.gr_image_scale_dev(self.h, _ptr(in_dev), int(n), int(planes), int(sh), int(sw), int(dh), int(dw), _ptr(out_dev)),
+                   "gr_image_scale_dev")
+
+    def image_scale(self, images, dh, dw):
+        """the same on a host array [n x planes x sh x sw] -> a new host array [n x planes x dh x dw] (gr_image_scale_host)"""
+        images = f32(images)
+        if images.ndim != 4:
+            raise GanrevError(f"image_scale: images {images.shape} are not [n x planes x h x w]")
+        n, planes, sh, sw = images.shape
+        out = np.empty((n, planes, max(int(dh), 0), max(int(dw), 0)), np.float32)
+        self.check(self.lib.gr_image_scale_host(self.h, _ptr(images), n, planes, sh, sw, int(dh), int(dw), _ptr(out)), "gr_image_scale_host")
+        return out
+
+    def dataset_images_dev(self, bytes_dev, n, sh, sw, sc, dh, dw, to_space, normalize, out_dev):
+        """dataset.lua:149-153 for n decoded files of one size: uint8 HWC [n x sh x sw x sc] in device memory -> out_dev fp32
+        [n x (1|3) x dh x dw] in colour space to_space (GR_CS_*), normalised to [-1, 1] when `normalize`.  One launch (gr_dataset_images_dev)."""
+        self.check(self.lib.gr_dataset_images_dev(self.h, _ptr(bytes_dev), int(n), int(sh), int(sw), int(sc), int(dh), int(dw), int(to_space),
+                                                  int(bool(normalize)), _ptr(out_dev)), "gr_dataset_images_dev")
 
     def bce_dev(self, x, t, n, loss_dev, grad_dev=None):
         self.check(self.lib.gr_bce_dev(self.h, _ptr(x), _ptr(t), int(n), _ptr(loss_dev), _ptr(grad_dev)), "gr_bce_dev")

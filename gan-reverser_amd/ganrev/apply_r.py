@@ -15,6 +15,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from . import scripts
 from .nn_utils import DeviceTensor, forwardBatched, forwardBatchedDev
 
 
@@ -222,6 +223,7 @@ def parse(argv=None):
     p.add_argument("--nbImages", type=int, default=10000)                     # apply_r.lua:145
     p.add_argument("--synthetic", default="", help="CxHxWxND, e.g. 1x32x32x32: random-initialised G / R / R_fixer instead of checkpoints")
     p.add_argument("--host", action="store_true", help="the host-tensor loop (forwardBatched per chunk, as apply_r.lua spells it) instead of the device-resident pipeline")
+    scripts.add_dataset_options(p)                                            # apply_r.lua:16 --dataset (configured as there, never read)
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
@@ -251,6 +253,7 @@ def main(argv=None):
         dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
         MODEL_R = t7.load_checkpoint(OPT.R)["R"]                              # :92-94
         MODEL_R_FIXER = t7.load_checkpoint(OPT.R_fixer)["R"]                  # :101-103
+    scripts.open_dataset(OPT, colorSpace, dims[1], dims[2])                   # apply_r.lua:83-87
     for m in (MODEL_G, MODEL_R, MODEL_R_FIXER):
         m._ctx = ctx
         m.evaluate()

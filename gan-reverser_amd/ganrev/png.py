@@ -3,8 +3,11 @@
 The reference saves JPEG through Torch's `image` rock (image.save); JPEG is lossy and its encoder is not restated here, so the pictures
 are written as 8-bit PNG instead - lossless, which lets a test read a file back and compare it byte for byte with the grid it came from.
 
-    write_png(path, u8)     u8: uint8 array [H x W x 1] (or [H x W]) -> grayscale, [H x W x 3] -> RGB; filter 0 on every scanline
-    read_png(path)          8-bit grayscale or RGB, non-interlaced, any of the five scanline filters -> uint8 [H x W x 1 | 3]
+    write_png(path, u8)     u8: uint8 array [H x W x 1] (or [H x W]) -> grayscale, [H x W x 3] -> RGB, [H x W x 4] -> RGBA; filter 0 on
+                            every scanline
+    read_png(path)          8-bit grayscale, RGB or RGBA, non-interlaced, any of the five scanline filters -> uint8 [H x W x 1 | 3 | 4]
+
+ganrev.dataset decodes a folder of .png files with read_png (dataset.lua:111,149: image.load); RGBA is there for that.
 """
 import struct
 import zlib
@@ -25,12 +28,12 @@ def encode_png(u8, level=6):
         raise ValueError(f"write_png: uint8 pixels, not {u8.dtype}")
     if u8.ndim == 2:
         u8 = u8[:, :, None]
-    if u8.ndim != 3 or u8.shape[2] not in (1, 3) or u8.shape[0] < 1 or u8.shape[1] < 1:
-        raise ValueError(f"write_png: [H x W x 1] or [H x W x 3], not {u8.shape}")
+    if u8.ndim != 3 or u8.shape[2] not in (1, 3, 4) or u8.shape[0] < 1 or u8.shape[1] < 1:
+        raise ValueError(f"write_png: [H x W x 1], [H x W x 3] or [H x W x 4], not {u8.shape}")
     h, w, c = u8.shape
     raw = np.zeros((h, 1 + w * c), np.uint8)                  # filter byte 0 (None) in front of every scanline
     raw[:, 1:] = u8.reshape(h, w * c)
-    ihdr = struct.pack(">IIBBBBB", w, h, 8, 0 if c == 1 else 2, 0, 0, 0)
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, {1: 0, 3: 2, 4: 6}[c], 0, 0, 0)
     return SIGNATURE + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + chunk(b"IEND", b"")
 
 
@@ -66,9 +69,9 @@ def decode_png(data):
     if ihdr is None:
         raise ValueError("read_png: no IHDR chunk")
     w, h, depth, ctype, comp, flt, interlace = ihdr
-    if depth != 8 or ctype not in (0, 2) or comp != 0 or flt != 0 or interlace != 0:
-        raise ValueError(f"read_png: only 8-bit gray / RGB, non-interlaced (depth {depth}, colour type {ctype}, interlace {interlace})")
-    c = 1 if ctype == 0 else 3
+    if depth != 8 or ctype not in (0, 2, 6) or comp != 0 or flt != 0 or interlace != 0:
+        raise ValueError(f"read_png: only 8-bit gray / RGB / RGBA, non-interlaced (depth {depth}, colour type {ctype}, interlace {interlace})")
+    c = {0: 1, 2: 3, 6: 4}[ctype]
     stride = w * c
     raw = zlib.decompress(b"".join(idat))
     if len(raw) != h * (stride + 1):

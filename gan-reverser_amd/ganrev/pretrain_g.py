@@ -2,10 +2,10 @@
 nn.MSECriterion, the L1 / L2 penalty, the gradient clamp and optim.adam (pretrain_g.lua:82-206), and save the decoder as
 <save>/g_pretrained_CxHxW_ndN.net - the file train.lua:148-161 (ganrev.train --G_pretrained_dir) starts G from.
 
-    python -m ganrev.pretrain_g --epochs 2 --N_epoch 30 --batchSize 128 --save logs [--data images.npy] [--compat]
+    python -m ganrev.pretrain_g --epochs 2 --N_epoch 30 --batchSize 128 --save logs [--dataset DIR | --data images.npy] [--compat]
 
 Same option names and defaults as pretrain_g.lua:12-35 for what is mirrored.  Training images come from --data (an
-[N x C x H x W] float32 .npy in [0, 1]) or, without it, from synth.synthetic_images (the dataset loader is out of scope).  With
+[N x C x H x W] float32 .npy in [0, 1]) or, without it, from synth.synthetic_images, or from --dataset DIR through ganrev.dataset (DATASET.loadRandomImages per epoch, :118).  With
 --colorSpace yuv | hsl the images are rgb and are converted once per epoch load, on the device (nn_utils.rgbToColorSpace, as
 dataset.lua:153 does per image); three-channel --data with --colorSpace y is converted the same way.
 
@@ -47,6 +47,7 @@ def parse(argv=None):
     p.add_argument("--height", type=int, default=32)               # :31
     p.add_argument("--width", type=int, default=32)                # :32
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
+    scripts.add_dataset_options(p)                                 # :15 --dataset
     p.add_argument("--compat", action="store_true")
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
@@ -166,6 +167,7 @@ def main(argv=None):
         print(ae)
         print("Number of free parameters in G (total): %d" % ae._param_count())
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
+    DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width)      # :60-64; rgb: the loops convert to --colorSpace as they do for --data
     nLoad = OPT.N_epoch * OPT.batchSize                                   # :117
     if OPT.compat:
         CRITERION = nn.MSECriterion()                                     # :94
@@ -179,7 +181,9 @@ def main(argv=None):
         for _ in range(OPT.epochs):                                       # pretrain_g.lua:112's stop test, not inverted (module docstring)
             if not OPT.quiet:
                 print("<trainer> Epoch %d" % EPOCH)
-            if data is not None:
+            if DATASET is not None:
+                TRAIN_DATA = scripts.load_random_images(DATASET, nLoad)       # :118
+            elif data is not None:
                 TRAIN_DATA = data[((EPOCH - 1) * nLoad + np.arange(nLoad)) % len(data)]
             else:
                 TRAIN_DATA = synthetic_images(nLoad, dims, OPT.seed * 7919 + EPOCH * 3)

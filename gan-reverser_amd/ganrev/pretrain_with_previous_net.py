@@ -5,12 +5,13 @@ D's predictions as SOFT targets), each under its L1 / L2 penalty, gradient clamp
 <save>/pretrained_CxHxW_ndN.net = {G, D, opt}.
 
     python -m ganrev.pretrain_with_previous_net --network logs/adversarial.net --N_batches 1000 --colorSpace yuv --noiseDim 64 \\
-        --save logs [--data images.npy] [--compat]
+        --save logs [--dataset DIR | --data images.npy] [--compat]
 
 Same option names and defaults as pretrain_with_previous_net.lua:12-37.  --noplot, --window, --aws, --threads and --N_epoch are
 accepted and unused (the reference's `display` UI, thread count and an option its loop never reads).  Real images come from --data
 (an rgb [N x 3 x H x W] float32 .npy in [0, 1], converted to --colorSpace with rgbToColorSpace as dataset.lua:153 does) or, without
-it, from synth.synthetic_images; the dataset loader and visualizeProgress (:270-306) are out of scope.
+it, from synth.synthetic_images, or from --dataset DIR through ganrev.dataset (DATASET.loadRandomImages(batchSize / 2) per batch, :171);
+visualizeProgress (:270-306) is out of scope.
 
 Two loops, as in ganrev.pretrain_g:
   fast (default)  - device-resident: gr_fill_*_dev for both noise tensors, gr_copy2d_dev for the shared noise columns and the two
@@ -67,6 +68,7 @@ def parse(argv=None):
     p.add_argument("--network", default="logs/adversarial.net")    # :34
     p.add_argument("--N_batches", type=int, default=1000)          # :35
     p.add_argument("--data", default="", help="rgb [N x 3 x H x W] float32 .npy of real images in [0, 1]; default: synthetic")      # :36 --dataset
+    scripts.add_dataset_options(p)                                 # :36 --dataset
     p.add_argument("--compat", action="store_true")
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
@@ -104,8 +106,11 @@ def noise_seeds(seed, i):
     return seed * 100003 + 2 * i - 1, seed * 100003 + 2 * i
 
 
-def real_images(OPT, data, i, half):
-    """DATASET.loadRandomImages(batchSize / 2) of batch i (:171), as rgb [half x 3 x H x W]: consecutive images of --data, or synthetic"""
+def real_images(OPT, data, i, half, DATASET=None):
+    """DATASET.loadRandomImages(batchSize / 2) of batch i (:171), as rgb [half x 3 x H x W]: the loader's draw from --dataset,
+    consecutive images of --data, or synthetic"""
+    if DATASET is not None:
+        return scripts.load_random_images(DATASET, half)
     if data is not None:
         return np.ascontiguousarray(data[((i - 1) * half + np.arange(half)) % len(data)], np.float32)
     return synthetic_images(half, (3, OPT.height, OPT.width), OPT.seed * 7919 + i * 3)
@@ -303,12 +308,13 @@ def main(argv=None):
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
     if data is not None and tuple(data.shape[1:]) != (3, OPT.height, OPT.width):
         raise L.GanrevError(f"--data holds {tuple(data.shape[1:])} images, not rgb (3, {OPT.height}, {OPT.width})")
+    DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width)                               # :69-73; rgb: converted with the generated half (:173-176)
     loop = None if OPT.compat else DeviceDistill(s)
     half, last, path, t0 = OPT.batchSize // 2, None, None, time.perf_counter()
     pull = (lambda: (s.G.pull_params(), s.D.pull_params())) if loop is None else loop.sync_to_host
     try:
         for i in range(1, OPT.N_batches + 1):                                                       # :161
-            real = real_images(OPT, data, i, half)
+            real = real_images(OPT, data, i, half, DATASET)
             want = not OPT.quiet or i == OPT.N_batches
             if loop is None:
                 last = compat_batch(s, i, real)

@@ -2,14 +2,15 @@
 best and the 64 worst according to D and 64 random ones, and with --neighbours find the nearest training image (torch.dist) of
 each of the 16 best.
 
-    python -m ganrev.sample --save logs --network adversarial.net --data images.npy --writeTo samples [--neighbours]
+    python -m ganrev.sample --save logs --network adversarial.net --dataset DIR --writeTo samples [--neighbours]
 
-Same option names and defaults as sample.lua:9-24.  The dataset loader is out of scope: the training set comes from --data (an
-[N x C x H x W] float32 .npy, as in ganrev.train), and each run writes one samples_<run>.npz into --writeTo with best, best_pred,
+Same option names and defaults as sample.lua:9-24.  The training set comes from --dataset DIR (ganrev.dataset = dataset.lua; files
+matching --fileExtension; --neighbours searches the device-resident table DATASET.loadImages leaves, sample.lua:132) or from --data
+(an [N x C x H x W] float32 .npy, as in ganrev.train), and each run writes one samples_<run>.npz into --writeTo with best, best_pred,
 worst, worst_pred, random and, with --neighbours, neighbour_idx, neighbour_dist and neighbours.  With --render the run's pictures
 (sample.lua:96-118: random1024, random256, best, worst, random and best_*_neighbours, named <name>_<run>_base) are written beside it
 as PNG - toGrid / toNeighboursGrid (sample.lua:166-185) on the GPU through ganrev.render, display range taken from the picture itself
-as image.toDisplayTensor does without min / max.  trainset_s1 (sample.lua:77-83) needs the dataset loader and is not written.  Random
+as image.toDisplayTensor does without min / max.  trainset_s1 (sample.lua:77-83: 64 random training images) is written with --dataset.  Random
 choices use numpy's generator seeded by --seed (Torch's generator is not reproduced).
 """
 import argparse
@@ -36,7 +37,7 @@ def parse(argv=None):
     p.add_argument("--batchSize", type=int, default=16)
     p.add_argument("--height", type=int, default=32)
     p.add_argument("--width", type=int, default=32)
-    p.add_argument("--dataset", default="NONE", help="(the dataset loader is out of scope: use --data)")
+    scripts.add_dataset_options(p)                                    # sample.lua:19 --dataset
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy: the training set --neighbours searches")
     p.add_argument("--render", action="store_true", help="also write the run's image grids as PNG files (ganrev.render)")
     return p.parse_args(argv)
@@ -92,11 +93,17 @@ def main(argv=None):
     dims = image_dims(opt)
     ctx = L.default_context()
     G, D = loadModels(opt)
-    data = None
+    DATASET = scripts.open_dataset(opt, opt.colorSpace, opt.height, opt.width)      # sample.lua:46-50
+    data = table = None
     if opt.neighbours:
-        if not opt.data:
-            raise SystemExit("--neighbours needs --data (the training set)")
-        data = np.ascontiguousarray(np.load(opt.data), dtype=np.float32)
+        if DATASET is not None:
+            # sample.lua:132 DATASET.loadImages(0, 9999999) - with 1: dataset.lua:100 asserts startAt > 0.  Loaded once, not per call;
+            # the table stays where the loader's kernel left it and gr_l2_nearest_dev searches it there.
+            table = DATASET.loadImages(1, 9999999).data
+        elif opt.data:
+            data = np.ascontiguousarray(np.load(opt.data), dtype=np.float32)
+        else:
+            raise SystemExit("--neighbours needs --dataset or --data (the training set)")
     os.makedirs(opt.writeTo, exist_ok=True)
     rng = np.random.default_rng(opt.seed)
     print("Sampling...")
@@ -109,8 +116,13 @@ def main(argv=None):
             print("Settings:", dims)
         best, best_pred = nn_utils.sortImagesByPrediction(D, images, False, 64, opt.batchSize)
         worst, worst_pred = nn_utils.sortImagesByPrediction(D, images, True, 64, opt.batchSize)
+        name = lambda what: os.path.join(opt.writeTo, "%s_%04d_base.png" % (what, run))
+        if opt.render and DATASET is not None:                        # sample.lua:77-83
+            from . import render
+            train = DATASET.loadRandomImages(64)
+            render.grid(train.images, np.arange(train.size()), 8, opt.colorSpace, auto_range=True, path=name("trainset_s1"))
+            train.free()
         if opt.render:                                                # sample.lua:96-97 (drawn before the 64 random ones, as there)
-            name = lambda what: os.path.join(opt.writeTo, "%s_%04d_base.png" % (what, run))
             toGrid(ctx, images[rng.permutation(len(images))[:256]], 16, opt.colorSpace, name("random256"))
             toGrid(ctx, images, 32, opt.colorSpace, name("random1024"))
         random = images[rng.choice(len(images), 64, replace=False)]
@@ -119,26 +131,32 @@ def main(argv=None):
             for what, imgs in (("best", best), ("worst", worst), ("random", random)):
                 toGrid(ctx, imgs, 8, opt.colorSpace, name(what))
         if opt.neighbours:                                            # sample.lua:115-123
-            n, d = len(data), int(np.prod(data.shape[1:]))
+            shape = data.shape if table is None else table.shape
+            n, d = shape[0], int(np.prod(shape[1:]))
             if d != int(np.prod(best.shape[1:])):
-                raise SystemExit(f"--data rows have {d} values, G's images {int(np.prod(best.shape[1:]))}")
-            table_dev = ctx.upload(data)                              # once per run
+                raise SystemExit(f"the training images have {d} values, G's images {int(np.prod(best.shape[1:]))}")
+            table_dev = ctx.upload(data) if table is None else table.ptr      # --data: once per run
             try:
                 idx, dist = findClosestNeighboursOf(ctx, best[:16], table_dev, n, d)
                 if opt.render:                                        # sample.lua:118, from the table where it lies
                     from . import render
                     bt = nn_utils.DeviceTensor(ctx, best[:16].shape)
                     ctx.upload(best[:16], bt.ptr)
-                    render.neighbours_grid(bt, np.arange(len(idx)), nn_utils.DeviceTensor(ctx, data.shape, table_dev), idx[:, 0], opt.colorSpace,
+                    render.neighbours_grid(bt, np.arange(len(idx)), nn_utils.DeviceTensor(ctx, shape, table_dev), idx[:, 0], opt.colorSpace,
                                            path=os.path.join(opt.writeTo, "best_%04d_neighbours_base.png" % run))
                     bt.free()
+                # the rows found: --data has them on the host; the loader's table gives up just these
+                found = data[idx[:, 0]] if table is None else np.stack([ctx.download(table_dev + 4 * d * int(j), shape[1:]) for j in idx[:, 0]])
             finally:
-                ctx.free(table_dev)
-            out.update(neighbour_idx=idx[:, 0], neighbour_dist=dist[:, 0], neighbours=data[idx[:, 0]])
+                if table is None:
+                    ctx.free(table_dev)
+            out.update(neighbour_idx=idx[:, 0], neighbour_dist=dist[:, 0], neighbours=found)
         path = os.path.join(opt.writeTo, "samples_%04d.npz" % run)
         np.savez(path, **out)
         written.append(path)
         print(f"run {run}/{opt.runs}: {path}")
+    if table is not None:
+        table.free()
     print("Finished.")
     return written
 

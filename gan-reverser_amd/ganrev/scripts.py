@@ -1,5 +1,6 @@
 """What the script modules (train, train_r, pretrain_g, pretrain_with_previous_net, sample) say the same way: image geometry from a
-colour-space name, the CxHxW_ndN part of their checkpoint names, a checkpoint's opt table and loading a checkpoint for good."""
+colour-space name, the CxHxW_ndN part of their checkpoint names, a checkpoint's opt table, loading a checkpoint for good, and the
+--dataset / --fileExtension options with the DATASET.* calls every reference script opens with."""
 from . import _lib as L
 from . import t7
 
@@ -20,8 +21,11 @@ def geometry(dims, noiseDim):
 
 
 def opt_table(OPT):
-    """The scalar options, in the order the parser declares them, as a checkpoint's `opt` (train.lua:256 saves OPT itself)."""
-    return {k.rstrip("_"): v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool))}      # continue_ -> continue
+    """The scalar options, in the order the parser declares them, as a checkpoint's `opt` (train.lua:256 saves OPT itself).
+    dataset and fileExtension are saved only when --dataset names a directory: a run that reads no folder writes the checkpoint it
+    wrote before these options existed, byte for byte."""
+    skip = ("dataset", "fileExtension") if getattr(OPT, "dataset", "NONE") == "NONE" else ()
+    return {k.rstrip("_"): v for k, v in vars(OPT).items() if isinstance(v, (int, float, str, bool)) and k not in skip}      # continue_ -> continue
 
 
 def load_checkpoint(path):
@@ -30,3 +34,39 @@ def load_checkpoint(path):
     if "_unconverted" in ck:
         raise L.GanrevError(f"{path}: {ck['_unconverted']}")
     return ck
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The dataset loader (ganrev.dataset = dataset.lua).  Every reference script has `--dataset` (default "NONE") and opens with
+#   DATASET.setColorSpace(OPT.colorSpace); DATASET.setFileExtension("jpg"); DATASET.setHeight(..); DATASET.setWidth(..); DATASET.setDirs({OPT.dataset})
+# (train.lua:81-85, train_r.lua:93-97, apply_r.lua:83-87, sample.lua:46-50, pretrain_g.lua:60-64, pretrain_with_previous_net.lua:69-73).
+def add_dataset_options(p):
+    p.add_argument("--dataset", default="NONE", help="directory of image files to load with ganrev.dataset (dataset.lua); NONE: --data or synthetic images")
+    p.add_argument("--fileExtension", default="jpg", help="only files whose name ends in this are loaded (the reference hard-codes jpg)")
+
+
+def open_dataset(OPT, colorSpace, height, width):
+    """The five DATASET.set* calls of a script's head when --dataset names a directory -> the configured ganrev.dataset module, else None.
+    The reference asserts OPT.dataset ~= "NONE"; here NONE keeps --data / the synthetic images.  Giving both --data and --dataset is an error.
+    The permutations of loadRandomImages are seeded from --seed."""
+    if OPT.dataset == "NONE":
+        return None
+    if getattr(OPT, "data", ""):
+        raise L.GanrevError("--data and --dataset both given: the images come from one of them")
+    from . import dataset as DATASET
+    DATASET.setColorSpace("y" if colorSpace == "gray" else colorSpace)
+    DATASET.setFileExtension(OPT.fileExtension)
+    DATASET.setHeight(height)
+    DATASET.setWidth(width)
+    DATASET.setDirs([OPT.dataset])
+    DATASET.setSeed(getattr(OPT, "seed", 0))
+    return DATASET
+
+
+def load_random_images(DATASET, count):
+    """DATASET.loadRandomImages(count) as the host array the training loops take (train.lua:216, pretrain_g.lua:118,
+    pretrain_with_previous_net.lua:171); a folder with fewer files than the loop will index is an error here, not an index past the end there"""
+    res = DATASET.loadRandomImages(count, device=False)
+    if res.size() < count:
+        raise L.GanrevError(f"--dataset holds {res.size()} matching files, the loop needs {count}")
+    return res.images

@@ -38,7 +38,7 @@ def bernoulli_keep(shape, seed, p_drop):
 
 
 def synthetic_images(n, dims, seed):
-    """Stand-in for DATASET.loadRandomImages (dataset.lua, out of scope): smooth blobs in [0, 1], different per call."""
+    """Stand-in for DATASET.loadRandomImages (ganrev.dataset) when a script is given neither --dataset nor --data: smooth blobs in [0, 1], different per call."""
     c, h, w = dims
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
     cy, cx = uniform((n, 1, 1, 1), seed, 0.25 * h, 0.75 * h), uniform((n, 1, 1, 1), seed + 1, 0.25 * w, 0.75 * w)

@@ -4,11 +4,12 @@ batchSize / 2 * D_iterations training images (train.lua:214-216), play adversari
 Without --network, G starts from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (ganrev.pretrain_g) when that file exists and
 --nopretraining is not given (train.lua:148-161).
 
-    python -m ganrev.train --epochs 5 --N_epoch 30 --batchSize 32 --save logs [--data images.npy] [--compat]
+    python -m ganrev.train --epochs 5 --N_epoch 30 --batchSize 32 --save logs [--dataset DIR | --data images.npy] [--compat]
 
-Same option names and defaults as train.lua:12-60 for what is mirrored.  The dataset loader, normalisation, plots / `display`
-and image grids are out of scope: training images come from --data (an [N x C x H x W] float32 .npy
-in [0, 1]) or, without it, from a synthetic generator, which is what makes the loop runnable here.  --colorSpace takes the
+Same option names and defaults as train.lua:12-60 for what is mirrored.  Normalisation, plots / `display` and image grids are out
+of scope.  Training images come from --dataset DIR (ganrev.dataset = dataset.lua: DATASET.loadRandomImages per
+epoch, train.lua:216; files matching --fileExtension), from --data (an [N x C x H x W] float32 .npy in [0, 1]) or, without either,
+from a synthetic generator.  --colorSpace takes the
 reference's rgb | yuv | hsl | y (train.lua:45) besides gray (= y, one channel): three-channel rgb images are converted with
 nn_utils.rgbToColorSpace once per epoch load.
 
@@ -59,6 +60,7 @@ def parse(argv=None):
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
+    scripts.add_dataset_options(p)                                   # train.lua:16 --dataset
     p.add_argument("--compat", action="store_true")
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
@@ -113,6 +115,7 @@ def main(argv=None):
                                 "D_clamp", "G_clamp", "D_optmethod", "G_optmethod", "seed", "D_sgd_lr", "G_sgd_lr", "D_sgd_momentum", "G_sgd_momentum")})
     env.EPOCH = epoch0
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
+    DATASET = scripts.open_dataset(OPT, OPT.colorSpace, OPT.height, OPT.width)      # train.lua:81-85
     only_adam = OPT.D_optmethod == "adam" and OPT.G_optmethod == "adam"      # the fused device update is Adam's; the rest are host mirrors
     game = None if (OPT.compat or not only_adam) else adversarial.DeviceGame(env)
     N_epoch = OPT.N_epoch if OPT.N_epoch > 0 else 100                 # adversarial.lua:42-45: N_epoch <= 0 means 100 batches
@@ -128,12 +131,14 @@ def main(argv=None):
     nbLoad = (N_epoch * OPT.batchSize // 2) * D_it
     cursor, last, t0, images = (epoch0 - 1) * nbLoad, None, time.perf_counter(), 0
     for _ in range(OPT.epochs):
-        if data is not None:
+        if DATASET is not None:
+            TRAIN_DATA = scripts.load_random_images(DATASET, nbLoad)   # train.lua:216; already in --colorSpace (dataset.lua:153)
+        elif data is not None:
             idx = (cursor + np.arange(nbLoad)) % len(data); cursor += nbLoad
             TRAIN_DATA = data[idx]
         else:
             TRAIN_DATA = synthetic_images(nbLoad, dims, OPT.seed * 7919 + env.EPOCH * 3)
-        if scripts.needs_conversion(TRAIN_DATA, OPT.colorSpace):
+        if DATASET is None and scripts.needs_conversion(TRAIN_DATA, OPT.colorSpace):
             # rgb images seen in another space (dataset.lua:153): one gr_colorspace_host call per epoch load
             TRAIN_DATA = nn_utils.rgbToColorSpace(np.ascontiguousarray(TRAIN_DATA, np.float32), OPT.colorSpace)
         if game is None:

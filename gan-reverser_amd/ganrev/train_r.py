@@ -57,6 +57,7 @@ def parse(argv=None):
     p.add_argument("--height", type=int, default=32)
     p.add_argument("--width", type=int, default=32)
     p.add_argument("--channels", type=int, default=1)
+    scripts.add_dataset_options(p)                                 # train_r.lua:14 --dataset (configured as there, never read: R learns from G's images)
     p.add_argument("--compat", action="store_true")
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
@@ -86,6 +87,7 @@ def main(argv=None):
         else:
             synth.init_params(MODEL_G, OPT.seed)
     MODEL_G.evaluate()                                                   # train_r.lua:70
+    scripts.open_dataset(OPT, "y" if OPT.channels == 1 else "rgb", OPT.height, OPT.width)      # train_r.lua:93-97
     if OPT.continue_:                                                    # train_r.lua:101-104  MODEL_R = torch.load(OPT.continue).R
         if OPT.continue_.endswith((".net", ".t7")):
             from . import t7

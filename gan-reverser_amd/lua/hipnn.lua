@@ -55,6 +55,10 @@ int gr_fill_normal_dev(gr_ctx*, float* dst_dev, int64_t n, uint64_t seed);
 int gr_fill_uniform_dev(gr_ctx*, float* dst_dev, int64_t n, float lo, float hi, uint64_t seed);
 int gr_colorspace_dev(gr_ctx*, const float* in_dev, int from, int to, int64_t batch, int h, int w, float* out_dev);     /* utils/nn_utils.lua:133-246; 0 rgb, 1 y, 2 yuv, 3 hsl */
 int gr_colorspace_host(gr_ctx*, const float* in_host, int from, int to, int64_t batch, int h, int w, float* out_host);
+int gr_image_scale_dev(gr_ctx*, const float* in_dev, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out_dev);     /* image.scale, bilinear; dataset.lua:112,150 */
+int gr_image_scale_host(gr_ctx*, const float* in_host, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out_host);
+int gr_dataset_images_dev(gr_ctx*, const uint8_t* in_dev, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize,
+                          float* out_dev);     /* decoded bytes -> / 255 -> image.scale -> rgbToColorSpace [-> normalize]; dataset.lua:149-153 */
 int gr_l2_distance_rows_dev(gr_ctx*, const float* a_dev, const float* b_dev, int64_t n, int64_t d, double* out_host);
 int gr_image_grid_dev(gr_ctx*, const float* const* src_dev, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
                       const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,

@@ -358,6 +358,39 @@ enum { GR_CS_RGB = 0, GR_CS_Y = 1, GR_CS_YUV = 2, GR_CS_HSL = 3 };
 int gr_colorspace_dev(gr_ctx* ctx, const float* in_dev, int from, int to, int64_t batch, int h, int w, float* out_dev);
 int gr_colorspace_host(gr_ctx* ctx, const float* in_host, int from, int to, int64_t batch, int h, int w, float* out_host);
 
+/* ---- dataset.lua:99-173: what loadImages / loadRandomImages do to every file after decoding it (csrc/dataset.hip) ----
+ *
+ * gr_image_scale_* = image.scale(src, width, height) in its default bilinear mode on fp32 NCHW [n x planes x sh x sw] -> [n x planes x dh x dw]
+ * (dataset.lua:112,150).  The arithmetic restates the un-vendored `image` rock's scaleBilinear FROM MEMORY and is unpinned, like the yuv / hsl
+ * arithmetic above.  Per plane the row pass runs first - every source row from sw to dw values, each rounded to fp32 -
+ * then the column pass maps every column of that intermediate from sh to dh.  Each pass is scaleLinear_rowcol(src_len, dst_len); all variables
+ * fp32, one IEEE operation per step (no fused multiply-add, `/` correctly rounded), in this order:
+ *   dst_len == src_len   copy
+ *   dst_len >  src_len   src_len == 1 replicates the value; else scale = (float)(src_len - 1) / (float)(dst_len - 1);
+ *                        for di < dst_len - 1:  f = di * scale; i = (long)f; f -= i; dst[di] = (1 - f) * src[i] + f * src[i + 1];
+ *                        dst[dst_len - 1] = src[src_len - 1]
+ *   dst_len <  src_len   (fractional box average) scale = (float)src_len / (float)dst_len; (i0, f0) = (0, 0); for each di:
+ *                        f1 = (di + 1) * scale; i1 = (long)f1; f1 -= i1;  acc = (1 - f0) * src[i0]; n = 1 - f0;
+ *                        for s = i0 + 1 .. i1 - 1: acc += src[s]; n += 1;   if i1 < src_len: acc += f1 * src[i1]; n += f1;
+ *                        dst[di] = acc / n; (i0, f0) = (i1, f1)
+ *                        ((i0, f0) before output di is the split of (float)di * scale: a thread computes its own span in closed form)
+ * One launch; the intermediate is never written.  in == out is not supported.
+ *
+ * gr_dataset_images_dev = the loader's fused path, one launch per batch of decoded files: uint8 interleaved HWC [n x sh x sw x sc] in device
+ * memory -> fp32 NCHW [n x planes(to_space) x dh x dw].  sc = 1 (grey, replicated to three channels), 3, or 4 (alpha dropped): what
+ * image.load(fp, 3, "float") yields (dataset.lua:149).  Per pixel: v = (float)byte / 255.0f (correctly rounded); the two scale passes above;
+ * rgbToColorSpace(to_space) by the device functions of gr_colorspace_*; if normalize != 0, NN_UTILS.normalize as the live code has it
+ * (utils/nn_utils.lua:371-375): v * 2, + (-1), clamp to [-1, 1] by compare-selects.  Bit-identical to the unfused chain bytes -> / 255 planar,
+ * gr_image_scale_dev, gr_colorspace_dev(rgb -> to_space), normalise.
+ *
+ * GR_ERR_INVALID with a gr_last_error message, no launch and `out` untouched for: a null pointer; n, planes, sh, sw, dh or dw < 1; sc outside
+ * {1, 3, 4}; a bad to_space; in == out (gr_image_scale_*).  Limits of the index arithmetic: every side at most 32768 (the fp32 products
+ * di * scale then stay exact enough that no index leaves its row), and at most 2^40 elements in the input and in the output tensor. ---- */
+int gr_image_scale_dev(gr_ctx* ctx, const float* in_dev, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out_dev);
+int gr_image_scale_host(gr_ctx* ctx, const float* in_host, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out_host);
+int gr_dataset_images_dev(gr_ctx* ctx, const uint8_t* in_dev, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize,
+                          float* out_dev);
+
 /* ---- single-kernel entry points used by bench.py's roofline leg and by kernel-level parity tests ---- */
 int gr_conv3_forward_dev(gr_ctx* ctx, const float* in_dev, const float* w_dev, const float* bias_dev, float* out_dev,
                          int batch, int cin, int cout, int h, int w, int upsample2);
