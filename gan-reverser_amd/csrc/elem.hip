@@ -10,6 +10,7 @@
 //   nn.MSECriterion                                        train_r.lua:119,147,150
 //   NN_UTILS.switchColorSpace / toRgb / rgbToColorSpace    utils/nn_utils.lua:133-246
 //   fevalR penalty+clamp and optim.adam                    train_r.lua:153-165,170
+//   fevalD / fevalG_on_D penalty+clamp and optim.sgd | adagrad | adadelta | adamax | rmsprop   adversarial.lua:86-88,126-128,147-161,174-188
 #include "kernels.h"
 #include "colorspace.h"
 #include <type_traits>
@@ -1638,13 +1639,18 @@ void launch_add_inplace(float* y, const float* x, long n, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------ penalty + clamp + Adam, one pass over (theta, g, m, v)
-__device__ __forceinline__ void adam_one(float& th, float& gv, float& mv, float& vv, const AdamConsts& c) {
+// the penalty / clamp lines in front of every update rule (adversarial.lua:8-28,86-88,126-128; train_r.lua:153-165) on one entry: Consts is AdamConsts or OptimConsts
+template <class Consts>
+__device__ __forceinline__ void penalty_clamp_one(const float th, float& gv, const Consts& c) {
   if (c.use_penalty) {
     const float sg = th > 0.f ? 1.f : (th < 0.f ? -1.f : 0.f);
     const float pen = sg * c.l1 + th * c.l2;
     gv = gv + pen;
   }
   if (c.use_clamp) gv = gv < -c.clamp ? -c.clamp : (gv > c.clamp ? c.clamp : gv);
+}
+__device__ __forceinline__ void adam_one(float& th, float& gv, float& mv, float& vv, const AdamConsts& c) {
+  penalty_clamp_one(th, gv, c);
   mv = mv * c.b1 + c.c1 * gv;
   vv = vv * c.b2 + (c.c2 * gv) * gv;
   const float denom = sqrtf(vv) + c.eps;
@@ -1681,6 +1687,96 @@ void launch_penalty_clamp_adam(float* theta, float* g, float* m, float* v, long 
   if (blocks < 1) blocks = 1;
   KtScope kt("penalty_clamp_adam_kernel", 0.0, 32.0 * (double)n, s);   // read theta,g,m,v + write theta,g,m,v
   hipLaunchKernelGGL(penalty_clamp_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, s, theta, g, m, v, n, c, skip);
+}
+
+// ------------------------------------------------------------------ penalty + clamp + sgd | adagrad | adadelta | adamax | rmsprop
+// The optim rock's other five methods (adversarial.lua:147-161,174-188) in the operation order of their float32 mirrors in ganrev/optim.py, one IEEE
+// operation per step.  a / b are the entry's two state slots: sgd dfdx | adagrad paramVariance | adadelta paramVariance, accDelta | adamax m, u |
+// rmsprop m.  gv leaves as the penalised, clamped gradient: sgd's weight decay goes into a copy, as the rock clones dfdx.
+template <int M, bool MOM>
+__device__ __forceinline__ void optim_one(float& th, float& gv, float& a, float& b, const OptimConsts& c) {
+  penalty_clamp_one(th, gv, c);
+  if constexpr (M == OPT_SGD) {
+    float d = gv;
+    if (c.use_wd) d = d + c.wd * th;
+    if constexpr (MOM) {
+      a = c.first ? d : c.mom * a + c.omd * d;
+      d = c.nesterov ? d + c.mom * a : a;
+    }
+    th = th - c.lr * d;
+  } else if constexpr (M == OPT_ADAGRAD) {
+    a = a + gv * gv;
+    th = th - (c.lr * gv) / (sqrtf(a) + 1e-10f);
+  } else if constexpr (M == OPT_ADADELTA) {
+    a = c.rho * a + (c.omr * gv) * gv;
+    const float sd = sqrtf(a + c.eps);
+    const float delta = sqrtf(b + c.eps) / sd * gv;
+    th = th - delta;
+    b = c.rho * b + (c.omr * delta) * delta;
+  } else if constexpr (M == OPT_ADAMAX) {
+    a = c.b1 * a + c.c1 * gv;
+    const float x = c.b2 * b, y = fabsf(gv) + c.eps;      // eps = 1e-38 is an fp32 subnormal: it must survive, or a zero gradient on step 1 divides 0 by 0
+    b = x != x ? x : (y != y ? y : (x > y ? x : y));      // torch.max / np.maximum: a NaN wins
+    th = th - (c.lr * a) / b;
+  } else {
+    static_assert(M == OPT_RMSPROP, "unknown method");
+    a = c.rho * a + (c.omr * gv) * gv;
+    th = th - (c.lr * gv) / (sqrtf(a) + c.eps);
+  }
+}
+// penalty_clamp_adam_kernel's shape: 16-byte accesses, grid-stride, the thread that would own the next vector takes the n % 4 tail, the same skip word.
+// Specialised on the method and on sgd's momentum, so a slot the method does not use is neither read nor written (plain sgd: no state at all).
+template <int M, bool MOM>
+__global__ __launch_bounds__(256) void penalty_clamp_optim_kernel(float* __restrict__ theta, float* __restrict__ g, float* __restrict__ s0,
+                                                                  float* __restrict__ s1, long n, OptimConsts c, const unsigned* __restrict__ skip) {
+  constexpr bool U0 = M != OPT_SGD || MOM, U1 = M == OPT_ADADELTA || M == OPT_ADAMAX;
+  if (skip != nullptr && *skip != 0u) return;
+  const long n4 = n >> 2;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i <= n4; i += (long)gridDim.x * blockDim.x) {
+    if (i < n4) {
+      float4 th = reinterpret_cast<float4*>(theta)[i], gv = reinterpret_cast<float4*>(g)[i];
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+      if constexpr (U0) a = reinterpret_cast<float4*>(s0)[i];
+      if constexpr (U1) b = reinterpret_cast<float4*>(s1)[i];
+      optim_one<M, MOM>(th.x, gv.x, a.x, b.x, c); optim_one<M, MOM>(th.y, gv.y, a.y, b.y, c);
+      optim_one<M, MOM>(th.z, gv.z, a.z, b.z, c); optim_one<M, MOM>(th.w, gv.w, a.w, b.w, c);
+      reinterpret_cast<float4*>(theta)[i] = th; reinterpret_cast<float4*>(g)[i] = gv;
+      if constexpr (U0) reinterpret_cast<float4*>(s0)[i] = a;
+      if constexpr (U1) reinterpret_cast<float4*>(s1)[i] = b;
+    } else {
+      for (long j = n4 << 2; j < n; ++j) {
+        float th = theta[j], gv = g[j], a = 0.f, b = 0.f;
+        if constexpr (U0) a = s0[j];
+        if constexpr (U1) b = s1[j];
+        optim_one<M, MOM>(th, gv, a, b, c);
+        theta[j] = th; g[j] = gv;
+        if constexpr (U0) s0[j] = a;
+        if constexpr (U1) s1[j] = b;
+      }
+    }
+  }
+}
+template <int M, bool MOM>
+static void launch_optim_as(const char* name, double bytes_per_entry, float* theta, float* g, float* s0, float* s1, long n, const OptimConsts& c, hipStream_t s,
+                            const unsigned* skip) {
+  long blocks = ((n >> 2) + 1 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  KtScope kt(name, 0.0, bytes_per_entry * (double)n, s);   // read + write of theta, g and of each slot the method uses
+  hipLaunchKernelGGL((penalty_clamp_optim_kernel<M, MOM>), dim3((unsigned)blocks), dim3(256), 0, s, theta, g, s0, s1, n, c, skip);
+}
+void launch_penalty_clamp_optim(int method, float* theta, float* g, float* s0, float* s1, long n, const OptimConsts& c, hipStream_t s, const unsigned* skip) {
+  switch (method) {
+    case OPT_SGD:
+      if (c.use_mom) launch_optim_as<OPT_SGD, true>("penalty_clamp_sgd_momentum_kernel", 24.0, theta, g, s0, s1, n, c, s, skip);
+      else launch_optim_as<OPT_SGD, false>("penalty_clamp_sgd_kernel", 16.0, theta, g, s0, s1, n, c, s, skip);
+      break;
+    case OPT_ADAGRAD: launch_optim_as<OPT_ADAGRAD, false>("penalty_clamp_adagrad_kernel", 24.0, theta, g, s0, s1, n, c, s, skip); break;
+    case OPT_ADADELTA: launch_optim_as<OPT_ADADELTA, false>("penalty_clamp_adadelta_kernel", 32.0, theta, g, s0, s1, n, c, s, skip); break;
+    case OPT_ADAMAX: launch_optim_as<OPT_ADAMAX, false>("penalty_clamp_adamax_kernel", 32.0, theta, g, s0, s1, n, c, s, skip); break;
+    case OPT_RMSPROP: launch_optim_as<OPT_RMSPROP, false>("penalty_clamp_rmsprop_kernel", 24.0, theta, g, s0, s1, n, c, s, skip); break;
+    default: break;     // gr_optim_step has refused it
+  }
 }
 
 // ------------------------------------------------------------------ counter-based RNG (Philox4x32-10)

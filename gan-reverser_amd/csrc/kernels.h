@@ -360,6 +360,13 @@ void launch_add_inplace(float* y, const float* x, long n, hipStream_t s);       
 void launch_bce(const float* x, const float* t, long n, double* loss_dev, float* grad, hipStream_t s);      // nn.BCECriterion (sizeAverage)
 struct AdamConsts { float b1, b2, c1, c2, eps, step, l1, l2, clamp; int use_penalty, use_clamp; };
 void launch_penalty_clamp_adam(float* theta, float* g, float* m, float* v, long n, const AdamConsts& c, hipStream_t s, const unsigned* skip = nullptr);
+// The optim rock's other five methods (adversarial.lua:147-161,174-188), same fused pass.  method = GR_OPT_* (net.hip asserts the two lists agree).
+// Every scalar is rounded to fp32 once on the host (gr_optim_step); a method reads only its own: sgd lr (= clr), wd, mom, omd (1 - dampening), use_wd,
+// use_mom, nesterov, first (t == 1: the buffer becomes the gradient); adagrad lr (= clr); adadelta rho, omr (1 - rho), eps; adamax b1, c1 (1 - beta1),
+// b2, eps, lr (= lr / (1 - beta1^t)); rmsprop lr, rho (alpha), omr (1 - alpha), eps.
+enum { OPT_SGD = 1, OPT_ADAGRAD = 2, OPT_ADADELTA = 3, OPT_ADAMAX = 4, OPT_RMSPROP = 5 };
+struct OptimConsts { float lr, wd, mom, omd, rho, omr, eps, b1, c1, b2, l1, l2, clamp; int use_wd, use_mom, nesterov, first, use_penalty, use_clamp; };
+void launch_penalty_clamp_optim(int method, float* theta, float* g, float* s0, float* s1, long n, const OptimConsts& c, hipStream_t s, const unsigned* skip = nullptr);
 void launch_gen_mask(uint32_t* words, long n_elems, float p_drop, uint64_t seed, uint64_t counter, uint32_t layer, hipStream_t s);
 // all masks of one forward in one launch (jobs travel in the kernel argument block)
 struct MaskJob { uint32_t* words; long nwords; uint32_t thresh; int half; uint32_t layer; };

@@ -1814,6 +1814,49 @@ extern "C" int gr_adam_step(gr_net* n, const gr_hyper* h, int t) {
   return GR_OK;
 }
 
+// optim.sgd | adagrad | adadelta | adamax | rmsprop (adversarial.lua:147-161,174-188) behind the same penalty / clamp prologue.  The scalars are taken
+// exactly as the float32 mirrors in ganrev/optim.py take them: double arithmetic rounded to fp32 once, except 1 - rho and 1 - alpha, which the mirrors
+// compute as fp32 differences.
+static_assert(GR_OPT_SGD == OPT_SGD && GR_OPT_ADAGRAD == OPT_ADAGRAD && GR_OPT_ADADELTA == OPT_ADADELTA && GR_OPT_ADAMAX == OPT_ADAMAX &&
+              GR_OPT_RMSPROP == OPT_RMSPROP, "ganrev.h and kernels.h number the methods differently");
+static OptimConsts optim_consts(const gr_optim_config* g, int t) {
+  OptimConsts k{};
+  const double clr = g->learningRate / (1.0 + (double)(t - 1) * g->learningRateDecay);      // evalCounter = t - 1 when the rock reads it
+  switch (g->method) {
+    case GR_OPT_SGD:
+      k.lr = (float)clr; k.wd = (float)g->weightDecay; k.mom = (float)g->momentum; k.omd = (float)(1.0 - g->dampening);
+      k.use_wd = g->weightDecay != 0; k.use_mom = g->momentum != 0; k.nesterov = g->nesterov != 0; k.first = t == 1;
+      break;
+    case GR_OPT_ADAGRAD: k.lr = (float)clr; break;
+    case GR_OPT_ADADELTA: k.rho = (float)g->rho; k.omr = 1.0f - k.rho; k.eps = (float)g->eps; break;
+    case GR_OPT_ADAMAX:
+      k.b1 = (float)g->beta1; k.c1 = (float)(1.0 - g->beta1); k.b2 = (float)g->beta2; k.eps = (float)g->epsilon;
+      k.lr = (float)(g->learningRate / (1.0 - std::pow(g->beta1, t)));
+      break;
+    default: k.lr = (float)g->learningRate; k.rho = (float)g->alpha; k.omr = 1.0f - k.rho; k.eps = (float)g->epsilon; break;      // GR_OPT_RMSPROP
+  }
+  k.l1 = (float)g->l1; k.l2 = (float)g->l2; k.clamp = (float)g->clamp;
+  k.use_penalty = (g->l1 != 0 || g->l2 != 0) ? 1 : 0;
+  k.use_clamp = g->clamp != 0 ? 1 : 0;
+  return k;
+}
+extern "C" int gr_optim_step(gr_net* n, const gr_optim_config* g, int t) {
+  if (!n || !g) return GR_ERR_INVALID;
+  gr_ctx* c = n->ctx;
+  if (t < 1) return fail(c, GR_ERR_INVALID, "gr_optim_step: t = %d (1-based count of steps since the reset)", t);
+  if (g->method < GR_OPT_SGD || g->method > GR_OPT_RMSPROP) return fail(c, GR_ERR_INVALID, "gr_optim_step: unknown optimizer method %d", (int)g->method);
+  if (g->method == GR_OPT_SGD && g->nesterov && !(g->momentum > 0 && g->dampening == 0))
+    return fail(c, GR_ERR_INVALID, "gr_optim_step: Nesterov momentum requires a momentum and zero dampening");
+  launch_penalty_clamp_optim(g->method, n->params, n->grads, n->adam_m, n->adam_v, n->n_params, optim_consts(g, t), c->stream, head_fault_dev(c));
+  LAUNCHCHK(c);
+  n->params_version++;
+  return GR_OK;
+}
+// the two state vectors are the ones gr_adam_* names m and v: one storage, whichever method steps the net
+extern "C" int gr_optim_reset(gr_net* n) { return gr_adam_reset(n); }
+extern "C" int gr_optim_get_state(gr_net* n, float* slot0, float* slot1) { return gr_adam_get_state(n, slot0, slot1); }
+extern "C" int gr_optim_set_state(gr_net* n, const float* slot0, const float* slot1) { return gr_adam_set_state(n, slot0, slot1); }
+
 // ------------------------------------------------------------------ data parallelism (RCCL over xGMI)
 static_assert(sizeof(ncclUniqueId) <= GR_COMM_ID_BYTES, "unique id does not fit");
 extern "C" int gr_comm_unique_id(gr_ctx* c, void* id_out) {

@@ -51,6 +51,40 @@ class Hyper(C.Structure):
         super().__init__(lr, beta1, beta2, eps, l1, l2, clamp)
 
 
+GR_OPT_SGD, GR_OPT_ADAGRAD, GR_OPT_ADADELTA, GR_OPT_ADAMAX, GR_OPT_RMSPROP = range(1, 6)      # gr_optim_step: the optim rock's other five methods
+OPT_METHODS = {"sgd": GR_OPT_SGD, "adagrad": GR_OPT_ADAGRAD, "adadelta": GR_OPT_ADADELTA, "adamax": GR_OPT_ADAMAX, "rmsprop": GR_OPT_RMSPROP}
+# which of a net's two state vectors a method uses, under the key the mirror in ganrev/optim.py keeps it (slot 0, slot 1); sgd's only with a momentum
+OPT_STATE_KEYS = {"sgd": ("dfdx", None), "adagrad": ("paramVariance", None), "adadelta": ("paramVariance", "accDelta"), "adamax": ("m", "u"),
+                  "rmsprop": ("m", None)}
+
+
+class OptimConfig(C.Structure):
+    """gr_optim_config: the config table of optim.sgd | adagrad | adadelta | adamax | rmsprop (adversarial.lua:147-161,174-188) + the closure's
+    penalties.  OptimConfig(method, table, l1=, l2=, clamp=) reads the table's keys as the mirror in ganrev/optim.py reads them: a key that is not
+    there takes that METHOD's default (learningRate: sgd, adagrad 1e-3, adamax 2e-3, rmsprop 1e-2; epsilon: adamax 1e-38, rmsprop 1e-8; dampening:
+    the momentum).  State keys in the table (dfdx, evalCounter, m, ...) are not config and are ignored."""
+    _fields_ = [("method", C.c_int32), ("nesterov", C.c_int32), ("learningRate", C.c_double), ("learningRateDecay", C.c_double),
+                ("weightDecay", C.c_double), ("momentum", C.c_double), ("dampening", C.c_double), ("rho", C.c_double), ("eps", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("epsilon", C.c_double), ("alpha", C.c_double),
+                ("l1", C.c_double), ("l2", C.c_double), ("clamp", C.c_double)]
+
+    def __init__(self, method="sgd", config=None, l1=0.0, l2=0.0, clamp=0.0):
+        cfg = dict(config or {})
+        code = OPT_METHODS.get(method, method)       # a name, or a GR_OPT_* number (an unknown one is gr_optim_step's to refuse)
+        if not isinstance(code, int):
+            raise GanrevError(f"Unknown optimizer method '{method}'")
+        mom = cfg.get("momentum", 0.0)
+        super().__init__(code, int(bool(cfg.get("nesterov", False))),
+                         cfg.get("learningRate", {GR_OPT_ADAMAX: 2e-3, GR_OPT_RMSPROP: 1e-2}.get(code, 1e-3)), cfg.get("learningRateDecay", 0.0),
+                         cfg.get("weightDecay", 0.0), mom, cfg.get("dampening", mom), cfg.get("rho", 0.9), cfg.get("eps", 1e-6),
+                         cfg.get("beta1", 0.9), cfg.get("beta2", 0.999), cfg.get("epsilon", 1e-38 if code == GR_OPT_ADAMAX else 1e-8),
+                         cfg.get("alpha", 0.99), l1, l2, clamp)
+
+    def slots(self):
+        """(slot 0 used, slot 1 used) by this configuration"""
+        return (self.method != GR_OPT_SGD or self.momentum != 0, self.method in (GR_OPT_ADADELTA, GR_OPT_ADAMAX))
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _SIGS = {
@@ -98,6 +132,10 @@ _SIGS = {
     "gr_adam_reset": (C.c_int, [_P]),
     "gr_adam_get_state": (C.c_int, [_P, _P, _P]),
     "gr_adam_set_state": (C.c_int, [_P, _P, _P]),
+    "gr_optim_step": (C.c_int, [_P, C.POINTER(OptimConfig), C.c_int]),
+    "gr_optim_reset": (C.c_int, [_P]),
+    "gr_optim_get_state": (C.c_int, [_P, _P, _P]),
+    "gr_optim_set_state": (C.c_int, [_P, _P, _P]),
     "gr_comm_unique_id": (C.c_int, [_P, _P]),
     "gr_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "gr_comm_destroy": (C.c_int, [_P]),
@@ -698,6 +736,24 @@ class Net:
     def set_adam_state(self, m, v):
         m, v = f32(m), f32(v)
         self._c(self.lib.gr_adam_set_state(self.h, _ptr(m), _ptr(v)), "gr_adam_set_state")
+
+    def optim_step(self, config, t):
+        """penalty + clamp + optim.<config.method> on the device (config: OptimConfig); t = 1-based count of steps since optim_reset"""
+        self._c(self.lib.gr_optim_step(self.h, C.byref(config), int(t)), "gr_optim_step")
+
+    def optim_reset(self):
+        self._c(self.lib.gr_optim_reset(self.h), "gr_optim_reset")
+
+    def optim_state(self):
+        """the net's two state vectors (slot 0, slot 1): what they mean is the method's business (OPT_STATE_KEYS)"""
+        a, b = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
+        self._c(self.lib.gr_optim_get_state(self.h, _ptr(a), _ptr(b)), "gr_optim_get_state")
+        return a, b
+
+    def set_optim_state(self, slot0=None, slot1=None):
+        slot0, slot1 = (None if s is None else f32(s) for s in (slot0, slot1))
+        assert all(s is None or s.size == self.n_params for s in (slot0, slot1))
+        self._c(self.lib.gr_optim_set_state(self.h, _ptr(slot0), _ptr(slot1)), "gr_optim_set_state")
 
     def range_guard_scan(self):
         """f16x3 range guard for loops built from the *_dev calls: synchronous scan of this net's weights / BatchNorm scales; True

@@ -131,7 +131,8 @@ def make_fevalG_on_D(env, noiseInputs, targets):
 
 def _optimize(env, which, feval, params, model):
     """adversarial.lua:156-171 / 183-198: the optimiser chosen with --D_optmethod / --G_optmethod on the host flat vectors.  adam (the
-    default) updates through the fused device kernel; the other five are host mirrors of the optim rock (ganrev/optim.py)."""
+    default) updates through the fused device kernel; the other five are host mirrors of the optim rock (ganrev/optim.py) here, in the
+    --compat game - DeviceGame steps them on the device with gr_optim_step."""
     method = getattr(env.OPT, which + "_optmethod")
     if method == "adam":
         return optim.adam(feval, params, env.OPTSTATE["adam"][which], model=model)
@@ -182,10 +183,11 @@ def train(env, trainData, quiet=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Fast mode: the same game with images, gradients, parameters and the Adam state resident on the GPU (what ganrev.train_r's
+# Fast mode: the same game with images, gradients, parameters and the optimiser state resident on the GPU (what ganrev.train_r's
 # DeviceTrainer / gr_train_r_step is to train_r.lua:138-170).  G and D each run through a device.DeviceModel, nn.BCECriterion is
-# gr_bce_dev, and adversarial.l1 / l2 / clamp + optim.adam are the fused gr_adam_step of each part.  Nothing is copied to the host
-# inside a batch except, on request, the two loss values.
+# gr_bce_dev, and adversarial.l1 / l2 / clamp + the optimiser chosen for the net (train.lua:37-38) are one fused launch per part:
+# gr_adam_step for adam, gr_optim_step for sgd, adagrad, adadelta, adamax and rmsprop.  Nothing is copied to the host inside a batch
+# except, on request, the two loss values.
 class DeviceGame:
     """adversarial.lua:139-201 per batch, device-resident.  game = DeviceGame(env); game.batch(real_half_batch) per batch;
     game.sync_to_host() before anything reads env.PARAMETERS_* or the host-side modules again (save, evaluate, compat mode)."""
@@ -193,8 +195,10 @@ class DeviceGame:
     def __init__(self, env):
         self.env = env
         OPT, G, D = env.OPT, env.MODEL_G, env.MODEL_D
-        if OPT.D_optmethod != "adam" or OPT.G_optmethod != "adam":
-            raise L.GanrevError("DeviceGame: only the default optimizer 'adam' (train.lua:37-38); the other methods run in adversarial.train")
+        for which in ("D", "G"):
+            method = getattr(OPT, which + "_optmethod")
+            if method != "adam" and method not in L.OPT_METHODS:
+                raise L.GanrevError(f"Unknown optimizer method '{method}' chosen for {which}.")        # adversarial.lua:170, 197
         self.ctx = ctx = G._context()
         B = OPT.batchSize
         device.compile_models(nn_utils.createNoiseInputs(2, OPT.noiseDim, OPT.noiseMethod, seed=1), G, D)
@@ -202,7 +206,7 @@ class DeviceGame:
         self.gnet = G._net                                  # G's one net by name: not used by the game, read by tools/debug
         for m in (self.gg, self.dg):
             m.set_training(True)
-            m.adam_reset()
+            m.adam_reset()                                  # the two state vectors of every part, whichever method steps it (= optim_reset)
         self.t = {"D": 0, "G": 0}
         self.npix = int(np.prod(env.IMG_DIMENSIONS))
         self.mem = device.Buffers(ctx)
@@ -212,9 +216,25 @@ class DeviceGame:
         half = B // 2
         ctx.upload(np.concatenate([np.full(half, Y_NOT_GENERATOR, np.float32), np.full(B - half, Y_GENERATOR, np.float32)]), self.targets)
         ctx.upload(np.full(B, Y_NOT_GENERATOR, np.float32), self.ones)
-        self.hyper_d = L.Hyper(l1=OPT.D_L1, l2=OPT.D_L2, clamp=OPT.D_clamp)
-        self.hyper_g = L.Hyper(l1=OPT.G_L1, l2=OPT.G_L2, clamp=OPT.G_clamp)
+        self.hyper_d = self._config("D", OPT.D_L1, OPT.D_L2, OPT.D_clamp)
+        self.hyper_g = self._config("G", OPT.G_L1, OPT.G_L2, OPT.G_clamp)
         self.noise_counter = self.batches = 0
+
+    def _config(self, which, l1, l2, clamp):
+        """adversarial.lua:147-161 / 174-188: adam's gr_hyper, or the gr_optim_config of the method chosen for this net, read from the table
+        train.lua:183-193 gives it (OPTSTATE.sgd carries learningRate and momentum; the other tables are empty: the rock's defaults)"""
+        method = getattr(self.env.OPT, which + "_optmethod")
+        if method == "adam":
+            return L.Hyper(l1=l1, l2=l2, clamp=clamp)
+        return L.OptimConfig(method, self.env.OPTSTATE[method][which], l1=l1, l2=l2, clamp=clamp)
+
+    def _step(self, which, model, config):
+        """optim[method](feval, PARAMETERS, OPTSTATE[method][which]) once the closure's gradient is in place: one fused launch per part"""
+        self.t[which] += 1
+        if isinstance(config, L.Hyper):
+            model.adam_step(config, self.t[which])
+        else:
+            model.optim_step(config, self.t[which])
 
     def _fill_noise(self, N, host=None):
         OPT = self.env.OPT
@@ -249,8 +269,7 @@ class DeviceGame:
             out = dg.forward(self.inputs, B)
             ctx.bce_dev(out, self.targets, B, self.loss, self.df)
             dg.backward(self.df, B, False)
-            self.t["D"] += 1
-            dg.adam_step(self.hyper_d, self.t["D"])
+            self._step("D", dg, self.hyper_d)
             if want_loss and k == nD - 1:
                 loss_d = ctx.read_loss(self.loss)
         for k in range(nG):
@@ -262,15 +281,29 @@ class DeviceGame:
             ctx.bce_dev(out, self.ones, B, self.loss, self.df)
             df_do = dg.backward(self.df, B, True)
             gg.backward(df_do, B, False)
-            self.t["G"] += 1
-            gg.adam_step(self.hyper_g, self.t["G"])
+            self._step("G", gg, self.hyper_g)
             if want_loss and k == nG - 1:
                 loss_g = ctx.read_loss(self.loss)
         return loss_d, loss_g
 
     def sync_to_host(self):
+        """Parameters and BatchNorm statistics into the host modules; for a net stepped by one of the five other methods also its state into
+        env.OPTSTATE[method][which] under the keys the mirror in ganrev/optim.py keeps it (dfdx, evalCounter | paramVariance, accDelta | m, u, t), so
+        that adversarial.train continues from it.  (adam's moments stay on the device, as before: optim.adam re-uploads what its table holds.)"""
         self.env.MODEL_D.pull_params()
         self.env.MODEL_G.pull_params()
+        for which, model, config in (("D", self.dg, self.hyper_d), ("G", self.gg, self.hyper_g)):
+            if isinstance(config, L.Hyper) or self.t[which] == 0:
+                continue                                    # a net no step has touched keeps the table train.lua gave it
+            method = getattr(self.env.OPT, which + "_optmethod")
+            state = self.env.OPTSTATE[method][which]
+            for key, used, vec in zip(L.OPT_STATE_KEYS[method], config.slots(), model.optim_state()):
+                if key is not None and used:
+                    state[key] = vec
+            if method == "adamax":
+                state["t"] = self.t[which]
+            elif method != "rmsprop":
+                state["evalCounter"] = self.t[which]
 
     def close(self):
         """Release the device buffers of the game (the nets stay with their models)."""

@@ -5,8 +5,10 @@ base class to inherit from.  (Noise by method and the loss word are ctx.fill_noi
 
 The containers stay host code that enqueues work: every compiled part runs through gr_net_forward_dev / gr_net_backward_dev,
 nn.Concat joins / slices / sums with gr_copy2d_dev / gr_add_dev, penalty + clamp + optim.adam are the fused gr_adam_step of each
-part.  A model that compiles to one gr_net (G, R, the G autoencoder) is the trivial case: one forward_dev, one backward_dev.
+part (gr_optim_step for the other five methods).  A model that compiles to one gr_net (G, R, the G autoencoder) is the trivial case: one forward_dev, one backward_dev.
 """
+import numpy as np
+
 from . import _lib as L
 from . import nn
 
@@ -155,6 +157,23 @@ class DeviceModel:
     def adam_reset(self):
         for n in self.nets:
             n.adam_reset()
+
+    def optim_step(self, config, t):
+        for n in self.nets:
+            n.optim_step(config, t)
+
+    def optim_reset(self):
+        for n in self.nets:
+            n.optim_reset()
+
+    def optim_state(self):
+        """the two state vectors of every part joined in getParameters() order: (slot 0, slot 1) flat host arrays"""
+        chunks = self.model._param_chunks()
+        a, b = (np.zeros(max([hi for _, _, hi in chunks], default=0), np.float32) for _ in range(2))
+        for ch, lo, hi in chunks:
+            if hi > lo:
+                a[lo:hi], b[lo:hi] = ch._net.optim_state()
+        return a, b
 
     def set_training(self, training):
         for n in self.nets:

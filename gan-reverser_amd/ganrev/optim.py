@@ -45,8 +45,9 @@ def adam(opfunc, x, config=None, state=None, model=None):
 # They belong to the un-vendored, un-pinned `optim` luarock, like adam: restated here FROM MEMORY of that package (each function
 # says which defaults and which update it takes), on the host flat vectors exactly as the reference runs them - `optim.*` there
 # are Torch tensor expressions on PARAMETERS_D / PARAMETERS_G, element-wise, with the state kept in the table the caller passes
-# (train.lua:183-193: empty tables, and {learningRate = OPT.X_sgd_lr, momentum = OPT.X_sgd_momentum} for sgd).  adam is the
-# default and the only one with a fused device kernel; these run in float32 numpy (TH float tensors) and serve the --compat game.
+# (train.lua:183-193: empty tables, and {learningRate = OPT.X_sgd_lr, momentum = OPT.X_sgd_momentum} for sgd).  These run in
+# float32 numpy (TH float tensors) and serve the --compat game; they are also the SPECIFICATION of the fused device updates
+# (gr_optim_step, csrc/elem.hip), which repeat their operation order bit for bit (tests/test_gpu_optim.py).
 def _state(config, state):
     config = config if config is not None else {}
     return config, (state if state is not None else config)

@@ -46,7 +46,7 @@ def parse(argv=None):
     p.add_argument("--G_iterations", type=int, default=1)
     p.add_argument("--D_clamp", type=float, default=1.0)
     p.add_argument("--G_clamp", type=float, default=5.0)
-    p.add_argument("--D_optmethod", default="adam", help="sgd|adagrad|adadelta|adamax|adam|rmsprop (anything but adam plays the --compat game)")
+    p.add_argument("--D_optmethod", default="adam", help="sgd|adagrad|adadelta|adamax|adam|rmsprop, each a fused device update (train.lua:37)")
     p.add_argument("--G_optmethod", default="adam")
     p.add_argument("--D_sgd_lr", type=float, default=0.02)
     p.add_argument("--G_sgd_lr", type=float, default=0.02)
@@ -116,12 +116,11 @@ def main(argv=None):
     env.EPOCH = epoch0
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
     DATASET = scripts.open_dataset(OPT, OPT.colorSpace, OPT.height, OPT.width)      # train.lua:81-85
-    only_adam = OPT.D_optmethod == "adam" and OPT.G_optmethod == "adam"      # the fused device update is Adam's; the rest are host mirrors
-    game = None if (OPT.compat or not only_adam) else adversarial.DeviceGame(env)
+    game = None if OPT.compat else adversarial.DeviceGame(env)       # every method of train.lua:37-38 has its fused device update
     N_epoch = OPT.N_epoch if OPT.N_epoch > 0 else 100                 # adversarial.lua:42-45: N_epoch <= 0 means 100 batches
     D_it, G_it = max(0, OPT.D_iterations), max(0, OPT.G_iterations)   # 0 iterations freeze that net (adversarial.lua:127,168 loop zero times)
     # a continued run must not replay the first epochs' noise: the counters start where epoch0 - 1 finished epochs left them
-    # (the reference's Torch RNG is not restored from a checkpoint either; Adam's state restarts empty, as train.lua does)
+    # (the reference's Torch RNG is not restored from a checkpoint either; the optimiser state restarts empty, as train.lua does)
     done = (epoch0 - 1) * N_epoch * (D_it + G_it)
     env.noise_counter = getattr(env, "noise_counter", 0) + done
     if game is not None:

@@ -77,6 +77,12 @@ int gr_l2_nearest_dev(gr_ctx*, const float* table_dev, int64_t n, int64_t d, con
                       int64_t* idx, double* dist);
 int gr_synchronize(gr_ctx*);
 int gr_adam_reset(gr_net*);
+typedef struct { int32_t method, nesterov; double learningRate, learningRateDecay, weightDecay, momentum, dampening, rho, eps, beta1, beta2, epsilon, alpha,
+                 l1, l2, clamp; } gr_optim_config;
+int gr_optim_step(gr_net*, const gr_optim_config*, int t);
+int gr_optim_reset(gr_net*);
+int gr_optim_get_state(gr_net*, float* slot0, float* slot1);
+int gr_optim_set_state(gr_net*, const float* slot0, const float* slot1);
 int gr_train_r_step(gr_net* gnet, gr_net* rnet, const float* noise_dev, int batch, int global_batch,
                     const gr_hyper* h, int t, double* loss_out);
 ]]
@@ -247,6 +253,25 @@ function hipnn.trainer(G, R, batchSize, pen, noiseMethod)
       check(C.gr_train_r_step(G.net, R.net, noise, batchSize, batchSize, h, t, loss), 'gr_train_r_step')
       return loss[0]
    end
+end
+
+-- adversarial.lua:147-161,174-188 with a method other than adam, device-resident: penalty + clamp + optim[method] as ONE launch over the wrapped
+-- net's flat parameters, the gradient its last backward left on the device and the net's two state vectors (slot mapping: include/ganrev.h).
+--   hipnn.optim_reset(MODEL_D)                         -- once, where train.lua:183-193 creates OPTSTATE
+--   hipnn.optim_step(MODEL_D, OPT.D_optmethod, OPTSTATE[OPT.D_optmethod].D, {l1=OPT.D_L1, l2=OPT.D_L2, clamp=OPT.D_clamp}, t)   -- t = 1, 2, ...
+-- config is the rock's table: a key that is absent takes that method's default.  MODEL:pullParams() before anything reads the host storage.
+local OPT_METHODS = {sgd=1, adagrad=2, adadelta=3, adamax=4, rmsprop=5}
+function hipnn.optim_reset(model) check(C.gr_optim_reset(model.net), 'gr_optim_reset') end
+function hipnn.optim_step(model, method, config, pen, t)
+   local code = OPT_METHODS[method]
+   if not code then error(string.format("Unknown optimizer method '%s'", tostring(method))) end
+   config = config or {}; pen = pen or {}
+   local mom = config.momentum or 0
+   local lr = config.learningRate or (code == 4 and 2e-3 or (code == 5 and 1e-2 or 1e-3))
+   local g = ffi.new('gr_optim_config', {code, config.nesterov and 1 or 0, lr, config.learningRateDecay or 0, config.weightDecay or 0, mom,
+                                          config.dampening or mom, config.rho or 0.9, config.eps or 1e-6, config.beta1 or 0.9, config.beta2 or 0.999,
+                                          config.epsilon or (code == 4 and 1e-38 or 1e-8), config.alpha or 0.99, pen.l1 or 0, pen.l2 or 0, pen.clamp or 0})
+   check(C.gr_optim_step(model.net, g, t), 'gr_optim_step')
 end
 
 -- apply_r.lua:396-400 replacement

@@ -143,6 +143,46 @@ int gr_adam_reset(gr_net* net);                             /* OPTSTATE = {adam=
 int gr_adam_get_state(gr_net* net, float* m_host, float* v_host);
 int gr_adam_set_state(gr_net* net, const float* m_host, const float* v_host);
 
+/* ---- the other five choices of --D_optmethod / --G_optmethod (train.lua:37-38), dispatched in adversarial.lua:147-161,174-188: the penalty and
+ * clamp lines of fevalD / fevalG_on_D (adversarial.lua:86-88,126-128) fused with optim.sgd | adagrad | adadelta | adamax | rmsprop, one launch over the
+ * net's flat params, grads and its two state vectors.  The `optim` rock is un-vendored: the update rules are those of the float32 restatements in
+ * ganrev/optim.py, in their operation order, bit for bit (penalties summed as gr_adam_step sums them: g + (sign(x) l1 + x l2)).  The penalised, clamped
+ * gradient is written back to grads (sgd's weightDecay term is not: the rock adds it to a clone).
+ * State: the two vectors are the ones gr_adam_* uses (slot 0 = m, slot 1 = v there).  A method touches only its own slots:
+ *     method     slot 0                      slot 1
+ *     sgd        dfdx (momentum buffer;      -
+ *                untouched at momentum 0)
+ *     adagrad    paramVariance               -
+ *     adadelta   paramVariance               accDelta
+ *     adamax     m                           u
+ *     rmsprop    m                           -
+ * Changing a net's method (adam included) without a reset in between is the caller's error: the new rule would read the old one's state.
+ * Scalars are computed in double and rounded to fp32 once (clr = learningRate / (1 + (t - 1) learningRateDecay), 1 - dampening, 1 - beta1,
+ * learningRate / (1 - beta1^t)); 1 - rho and 1 - alpha are fp32 differences of the rounded values, as the mirrors take them. ---- */
+enum { GR_OPT_SGD = 1, GR_OPT_ADAGRAD = 2, GR_OPT_ADADELTA = 3, GR_OPT_ADAMAX = 4, GR_OPT_RMSPROP = 5 };
+typedef struct {
+  int32_t method;                 /* GR_OPT_* */
+  int32_t nesterov;               /* sgd: needs momentum > 0 and dampening == 0, else GR_ERR_INVALID */
+  double learningRate;            /* rock defaults: sgd, adagrad 1e-3; adamax 2e-3; rmsprop 1e-2 (train.lua:189-190 gives sgd OPT.X_sgd_lr, 0.02); adadelta has none */
+  double learningRateDecay;       /* sgd, adagrad: 0 */
+  double weightDecay;             /* sgd: 0 */
+  double momentum;                /* sgd: 0 (train.lua:189-190: OPT.X_sgd_momentum, 0) */
+  double dampening;               /* sgd: the rock defaults it to the momentum - a plain value here, the caller copies momentum into it */
+  double rho, eps;                /* adadelta: 0.9, 1e-6 */
+  double beta1, beta2;            /* adamax: 0.9, 0.999 */
+  double epsilon;                 /* adamax 1e-38, rmsprop 1e-8 */
+  double alpha;                   /* rmsprop: 0.99 */
+  double l1, l2, clamp;           /* OPT.D_L1 / D_L2 / D_clamp, OPT.G_L1 / G_L2 / G_clamp (train.lua:27-36); 0 = off */
+} gr_optim_config;
+/* one optim.<method>(feval, PARAMETERS, OPTSTATE.<method>.<net>) call after the closure has left its gradient in grads (adversarial.lua:147-161,174-188);
+ * t = 1-based count of steps since the state was reset (sgd, adagrad: evalCounter + 1; adamax: state.t after its increment; at t == 1 sgd's buffer
+ * becomes the gradient).  An unknown method, an invalid nesterov request or t < 1 returns GR_ERR_INVALID and launches nothing.  While the context's
+ * sticky fault word is set (see "fused_head") the step changes nothing, as gr_adam_step. */
+int gr_optim_step(gr_net*, const gr_optim_config* /*config*/, int t);
+int gr_optim_reset(gr_net* net);                            /* OPTSTATE = {sgd = {D = {..}, G = {..}}, adagrad = {D = {}, G = {}}, ...}  train.lua:183-193: both slots zero */
+int gr_optim_get_state(gr_net* net, float* slot0_host, float* slot1_host);       /* either may be null; what train.lua's OPTSTATE tables hold between batches */
+int gr_optim_set_state(gr_net* net, const float* slot0_host, const float* slot1_host);
+
 /* ---- data parallelism (NEW capability required by north_star; the reference is single-GPU, train_r.lua:34,58-62) ---- */
 #define GR_COMM_ID_BYTES 128
 int gr_comm_unique_id(gr_ctx* ctx, void* id_out /*GR_COMM_ID_BYTES, generated on rank 0, shipped by the host to all ranks*/);
