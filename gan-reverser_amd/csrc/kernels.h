@@ -427,6 +427,17 @@ constexpr int GRID_RANGE_BLOCKS = 256;                             // upper boun
 // parts != null: auto range - image_grid_range_kernel leaves up to GRID_RANGE_BLOCKS (min, max) pairs over every pixel inside a tile in
 // parts [2 x GRID_RANGE_BLOCKS floats], the grid kernel reduces them to lo / hi; null: g.lo / g.hi.  One launch, two with auto range.
 void launch_image_grid(const GridGeom& g, float* parts, float* grid, uint8_t* u8, hipStream_t s);
+// ---- the trainers' progress pictures (render.hip): NN_UTILS.imagesToGridTensor (utils/nn_utils.lua:490-548) from a device-resident table;
+// include/ganrev.h, gr_progress_grid_dev, states the layout.  rows: device array of the n_cells rows shown; dig: the epoch's decimal digits,
+// least significant first.
+struct ProgressGeom {
+  const float* src; const long* rows;
+  int C, Cout, H, W, from;                                         // from = CS_* or -1 (channels copied as they are)
+  int n_cells, grid_w, GH, GW, ndig;
+  unsigned char dig[12];
+};
+// vec: four pixels of a row per thread (the caller has checked W % 4 == 0 and the alignment of src, grid and u8), else one.  One launch.
+void launch_progress_grid(const ProgressGeom& g, bool vec, float* grid, uint8_t* u8, hipStream_t s);
 // out[p] = (((0 + x[rows[0]][p]) + x[rows[1]][p]) + ...) / n for p < d, rows a device array; n == 0: zeros
 void launch_rows_mean(const float* x, long d, const long* rows_dev, int n, float* out, hipStream_t s);
 // several regions zeroed by ONE launch (each a multiple of 16 bytes, 16-byte aligned): the fills a training step needs - the scale slots of both

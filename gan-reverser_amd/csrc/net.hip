@@ -746,6 +746,13 @@ extern "C" int gr_net_set_bn_running(gr_net* n, int i, const float* m, const flo
 }
 extern "C" int gr_net_set_training(gr_net* n, int t) { if (!n) return GR_ERR_INVALID; n->training = t != 0; return GR_OK; }
 extern "C" int gr_net_set_seed(gr_net* n, uint64_t seed) { if (!n) return GR_ERR_INVALID; n->seed = seed; n->fwd_counter = 0; return GR_OK; }
+extern "C" int64_t gr_net_get_forward_counter(gr_net* n) { return n ? (int64_t)n->fwd_counter : -1; }
+extern "C" int gr_net_set_forward_counter(gr_net* n, int64_t counter) {
+  if (!n) return GR_ERR_INVALID;
+  if (counter < 0) return fail(n->ctx, GR_ERR_INVALID, "gr_net_set_forward_counter: counter %lld is negative", (long long)counter);
+  n->fwd_counter = (uint64_t)counter;
+  return GR_OK;
+}
 
 static MaskSlot* find_mask(gr_net* n, int layer) { for (auto& m : n->masks) if (m.layer == layer) return &m; return nullptr; }
 static int64_t mask_elems(const MaskSlot& m, int B) { return m.kind == MASK_ELEM ? (int64_t)B * vol3(m.C, m.H, m.W) : (int64_t)B * m.C; }
@@ -2306,6 +2313,43 @@ extern "C" int gr_image_grid_dev(gr_ctx* c, const float* const* src, const int64
   HIPCHK(c, hipStreamSynchronize(c->stream));                        // `tiles` dies with this call
   g.src[0] = src[0]; g.src[1] = slots == 2 ? src[1] : src[0]; g.tiles = (const GridTile*)c->ws;
   launch_image_grid(g, auto_range ? (float*)((char*)c->ws + tb) : nullptr, grid, u8, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ the trainers' progress pictures (render.hip)
+extern "C" int gr_progress_grid_dev(gr_ctx* c, const float* table, int64_t n_rows, int channels, int h, int w, int from_space,
+                                    const int64_t* rows, int n_show, int grid_h, int grid_w, int epoch, float* grid, uint8_t* u8) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: the table is null");
+  if (!grid && !u8) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: both outputs are null");
+  if (from_space < -1 || from_space > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: unknown color space <from>: %d", from_space);
+  if ((channels != 1 && channels != 3) || (from_space >= 0 && channels != (from_space == GR_CS_Y ? 1 : 3)))
+    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: %d channel(s) with from_space %d", channels, from_space);
+  if (n_rows < 1 || h < 1 || w < 1 || grid_h < 1 || grid_w < 1 || n_show < 0)
+    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: bad geometry (n_rows %lld, h %d, w %d, grid %d x %d, n_show %d)", (long long)n_rows, h, w, grid_h, grid_w, n_show);
+  if (epoch < 0) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: epoch %d is negative", epoch);
+  const long GH = (long)grid_h * h + 7, GW = (long)grid_w * w;
+  if (GH > (1 << 20) || GW > (1 << 20) || GH * GW > (1L << 28)) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: a %ld x %ld grid is too large", GH, GW);
+  ProgressGeom g{};
+  for (int e = epoch; g.ndig == 0 || e > 0; e /= 10) g.dig[g.ndig++] = (unsigned char)(e % 10);
+  if (GW - 2 - 6L * g.ndig < 0)
+    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: the %d digit(s) of epoch %d do not fit a grid %ld pixels wide", g.ndig, epoch, GW);
+  const long cells = (long)grid_h * grid_w;
+  g.n_cells = (int)(n_show < cells ? n_show : cells);
+  if (g.n_cells > 0 && !rows) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: rows_host is null");
+  for (int t = 0; t < g.n_cells; ++t)
+    if (rows[t] < 0 || rows[t] >= n_rows) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: rows[%d] = %lld is outside [0, %lld)", t, (long long)rows[t], (long long)n_rows);
+  g.C = channels; g.Cout = from_space >= 0 ? 3 : channels; g.H = h; g.W = w; g.from = from_space;
+  g.grid_w = grid_w; g.GH = (int)GH; g.GW = (int)GW;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ensure_ws(c, sizeof(long) * (size_t)(g.n_cells > 0 ? g.n_cells : 1)); if (r) return r;
+  if (g.n_cells > 0) {
+    HIPCHK(c, hipMemcpyAsync(c->ws, rows, sizeof(long) * (size_t)g.n_cells, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                      // the caller's array is its own again when the call returns
+  }
+  g.src = table; g.rows = (const long*)c->ws;
+  const bool vec = w % 4 == 0 && (uintptr_t)table % 16 == 0 && (uintptr_t)grid % 16 == 0 && (uintptr_t)u8 % 4 == 0;
+  launch_progress_grid(g, vec, grid, u8, c->stream); LAUNCHCHK(c);
   return GR_OK;
 }
 

@@ -16,6 +16,16 @@
 
 namespace gr {
 
+// NN_UTILS.toRgb of one pixel; `from` is uniform over a launch; -1 and CS_RGB copy the channels
+__device__ __forceinline__ Px3 to_rgb_from(int from, Px3 x) {
+  switch (from) {
+    case CS_Y: return cs_to_rgb<CS_Y>(x);
+    case CS_YUV: return cs_to_rgb<CS_YUV>(x);
+    case CS_HSL: return cs_to_rgb<CS_HSL>(x);
+    default: return x;
+  }
+}
+
 // Output pixel (gy, gx) before the display range is applied: false = no tile covers it (it takes `fill`); true = v holds the tile's
 // background (margin, or a slot whose row is -1) or the slot image's pixel, converted to rgb and with the inset frame drawn over it.
 __device__ __forceinline__ bool grid_pixel(const GridGeom& g, int gy, int gx, Px3& v) {
@@ -34,12 +44,7 @@ __device__ __forceinline__ bool grid_pixel(const GridGeom& g, int gy, int gx, Px
   const float* p = g.src[s] + row * g.C * hw + (long)iy * g.W + px;
   Px3 x{p[0], 0.f, 0.f};
   if (g.C == 3) { x.b = p[hw]; x.c = p[2 * hw]; }
-  switch (g.from) {                                   // uniform over the launch; -1 and CS_RGB copy the channels
-    case CS_Y: x = cs_to_rgb<CS_Y>(x); break;
-    case CS_YUV: x = cs_to_rgb<CS_YUV>(x); break;
-    case CS_HSL: x = cs_to_rgb<CS_HSL>(x); break;
-    default: break;
-  }
+  x = to_rgb_from(g.from, x);
   if (tl.inset && (iy == 0 || iy == g.H - 1 || px == 0 || px == g.W - 1)) x = Px3{g.inset_rgb[0], g.inset_rgb[1], g.inset_rgb[2]};
   v = x;
   return true;
@@ -136,6 +141,109 @@ void launch_image_grid(const GridGeom& g, float* parts, float* grid, uint8_t* u8
   }
   KtScope kt("image_grid_kernel", 0.0, 4.0 * g.C * tile_px + (double)npix * g.Cout * ((grid ? 4.0 : 0.0) + (u8 ? 1.0 : 0.0)), s);
   hipLaunchKernelGGL(image_grid_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, g, (const float*)parts, nparts, grid, u8);
+}
+
+// ------------------------------------------------------------------ the trainers' progress pictures (utils/nn_utils.lua:490-548)
+// The ten digits as 3 x 5 blocks, one octal digit per pixel row from the top, the left pixel the high bit: the seven-segment shapes of
+// utils/nn_utils.lua:430-479 ("1" is the right-hand column only, the middle bar of "3" starts in the middle column).
+__constant__ const unsigned short PROGRESS_GLYPH[10] = {075557, 011111, 071747, 071317, 055711, 074717, 074757, 071111, 075757, 075717};
+
+// pixel (gy, gx) of the seven bottom rows: true with v = 0 / 1 when a digit's block covers it (digit p = 1, 2, ... from the right covers
+// columns GW-2-6p .. GW-6p of rows GH-7 .. GH-3)
+__device__ __forceinline__ bool progress_digit(const ProgressGeom& g, int gy, int gx, float& v) {
+  const int r = gy - (g.GH - 7), d = g.GW - gx;          // d = 6p + 2 at the block's left column, 6p at its right
+  const int p = d / 6, k = d - 6 * p;
+  if (r < 0 || r > 4 || p < 1 || p > g.ndig || k > 2) return false;
+  v = (float)((PROGRESS_GLYPH[g.dig[p - 1]] >> (3 * (4 - r) + k)) & 1);
+  return true;
+}
+// the N (1 or 4) pixels (gy, gx ..) of one cell row: cell (gy / H, gx / W); N = 4 asks W % 4 == 0, so that they share the cell
+template <int N>
+__device__ __forceinline__ void progress_pixels(const ProgressGeom& g, int gy, int gx, float (&o)[3][N]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[c][j] = 0.f;
+  if (gy >= g.GH - 7) {                                  // the bottom rows: zeros and the digits
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      float v;
+      if (progress_digit(g, gy, gx + j, v)) o[0][j] = o[1][j] = o[2][j] = v;
+    }
+    return;
+  }
+  const int cy = gy / g.H, cx = gx / g.W, t = cy * g.grid_w + cx;
+  if (t >= g.n_cells) return;
+  const long hw = (long)g.H * g.W;
+  const float* p = g.src + g.rows[t] * g.C * hw + (long)(gy - cy * g.H) * g.W + (gx - cx * g.W);
+  float x[3][N];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (c < g.C) {
+      if constexpr (N == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + c * hw);
+        x[c][0] = q.x; x[c][1] = q.y; x[c][2] = q.z; x[c][3] = q.w;
+      } else {
+        x[c][0] = p[c * hw];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; ++j) x[c][j] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const Px3 v = to_rgb_from(g.from, Px3{x[0][j], x[1][j], x[2][j]});
+    o[0][j] = v.a; o[1][j] = v.b; o[2][j] = v.c;
+  }
+}
+// one thread per N pixels of a grid row, all channels: grid [Cout][GH][GW] floats (the values as they are) and / or u8 [GH][GW][Cout]
+// bytes (display range [0, 1]).  N = 4: one 16-byte store per channel of the grid, the 4 Cout bytes of u8 as Cout words.
+template <int N>
+__global__ __launch_bounds__(256) void progress_grid_kernel(ProgressGeom g, float* __restrict__ grid, uint8_t* __restrict__ u8) {
+  const long npix = (long)g.GH * g.GW;
+  const long p = (blockIdx.x * (long)blockDim.x + threadIdx.x) * N;
+  if (p >= npix) return;
+  const int gy = (int)(p / g.GW), gx = (int)(p - (long)gy * g.GW);
+  float o[3][N];
+  progress_pixels<N>(g, gy, gx, o);
+  if (grid) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (c >= g.Cout) break;
+      if constexpr (N == 4) *reinterpret_cast<float4*>(grid + c * npix + p) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+      else grid[c * npix + p] = o[c][0];
+    }
+  }
+  if (u8) {
+    uint32_t q[3][N];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int j = 0; j < N; ++j) q[c][j] = grid_quantise(grid_display(o[c][j], 0.f, 1.f, 1.f));
+    uint8_t* d = u8 + p * g.Cout;
+    if constexpr (N == 4) {                              // the 4 Cout bytes as they lie in u8: pixel-major, channel-minor
+      uint32_t* w = reinterpret_cast<uint32_t*>(d);
+      if (g.Cout == 1) {
+        w[0] = q[0][0] | (q[0][1] << 8) | (q[0][2] << 16) | (q[0][3] << 24);
+      } else {
+        w[0] = q[0][0] | (q[1][0] << 8) | (q[2][0] << 16) | (q[0][1] << 24);
+        w[1] = q[1][1] | (q[2][1] << 8) | (q[0][2] << 16) | (q[1][2] << 24);
+        w[2] = q[2][2] | (q[0][3] << 8) | (q[1][3] << 16) | (q[2][3] << 24);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (c < g.Cout) d[c] = (uint8_t)q[c][0];
+    }
+  }
+}
+void launch_progress_grid(const ProgressGeom& g, bool vec, float* grid, uint8_t* u8, hipStream_t s) {
+  const long npix = (long)g.GH * g.GW, threads = vec ? npix / 4 : npix;
+  KtScope kt("progress_grid_kernel", 0.0, 4.0 * g.C * (double)g.n_cells * g.H * g.W + (double)npix * g.Cout * ((grid ? 4.0 : 0.0) + (u8 ? 1.0 : 0.0)), s);
+  const dim3 blocks((unsigned)((threads + 255) / 256));
+  if (vec) hipLaunchKernelGGL(progress_grid_kernel<4>, blocks, dim3(256), 0, s, g, grid, u8);
+  else hipLaunchKernelGGL(progress_grid_kernel<1>, blocks, dim3(256), 0, s, g, grid, u8);
 }
 
 // ------------------------------------------------------------------ a cluster's average face (apply_r.lua:233-243)

@@ -112,6 +112,8 @@ _SIGS = {
     "gr_net_set_bn_running": (C.c_int, [_P, C.c_int, _P, _P]),
     "gr_net_set_training": (C.c_int, [_P, C.c_int]),
     "gr_net_set_seed": (C.c_int, [_P, C.c_uint64]),
+    "gr_net_get_forward_counter": (C.c_int64, [_P]),
+    "gr_net_set_forward_counter": (C.c_int, [_P, C.c_int64]),
     "gr_net_mask_size": (C.c_int64, [_P, C.c_int, C.c_int]),
     "gr_net_set_mask": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "gr_net_get_mask": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
@@ -165,6 +167,7 @@ _SIGS = {
     "gr_image_grid_dev": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                     _P, _P, _P, C.c_float, C.c_int, C.c_float, C.c_float, _P, _P]),
     "gr_rows_mean_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, _P]),
+    "gr_progress_grid_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "gr_l2_nearest_host": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     "gr_l2_nearest_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     "gr_kmeans_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
@@ -229,6 +232,11 @@ def grid_shape(n_tiles, slots, channels, h, w, from_space, nrow, padding=0, marg
     xmaps = max(1, min(int(nrow), int(n_tiles)))
     ymaps = -(-int(n_tiles) // xmaps)
     return (3 if from_space >= 0 else int(channels), ymaps * (h + 2 * margin + padding), xmaps * (slots * w + 2 * margin + padding))
+
+
+def progress_grid_shape(channels, h, w, from_space, grid_h, grid_w):
+    """(Cout, GH, GW) of gr_progress_grid_dev's grid: grid_h x grid_w cells and the seven rows that carry the epoch digits"""
+    return (3 if from_space >= 0 else int(channels), int(grid_h) * int(h) + 7, int(grid_w) * int(w))
 
 
 class Context:
@@ -436,6 +444,19 @@ class Context:
         self.check(rc, "gr_image_grid_dev")
         return grid_shape(n_tiles, slots, channels, h, w, from_space, nrow, padding, margin)
 
+    def progress_grid_dev(self, table_dev, n_rows, channels, h, w, from_space, rows, grid_h, grid_w, epoch, grid_dev=None, u8_dev=None,
+                          n_show=None):
+        """gr_progress_grid_dev = NN_UTILS.imagesToGridTensor (include/ganrev.h states the layout): the first grid_h * grid_w of the
+        listed rows of the device table [n_rows x channels x h x w] as cells, the epoch's digits below them.  n_show: len(rows).
+        -> (Cout, GH, GW) of the grid written to grid_dev (floats, planar) and / or u8_dev (bytes, interleaved)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n_show = rows.size if n_show is None else int(n_show)
+        rc = self.lib.gr_progress_grid_dev(self.h, _ptr(table_dev), int(n_rows), int(channels), int(h), int(w), int(from_space),
+                                           _ptr(rows) if rows.size else None, n_show, int(grid_h), int(grid_w), int(epoch),
+                                           _ptr(grid_dev), _ptr(u8_dev))
+        self.check(rc, "gr_progress_grid_dev")
+        return progress_grid_shape(channels, h, w, from_space, grid_h, grid_w)
+
     L2_NEAREST_MAX_Q = 64       # queries per gr_l2_nearest_* call (include/ganrev.h)
 
     def l2_nearest(self, table, queries, k, table_dev=None, n=None, d=None):
@@ -614,6 +635,7 @@ class Net:
         ctx.check(self.lib.gr_net_out_dim(h, C.byref(oc), C.byref(oh), C.byref(ow)), "gr_net_out_dim")
         self.out_dims = (oc.value, oh.value, ow.value)
         self.n_params = int(self.lib.gr_net_param_count(h))
+        self.training = True               # the mode set_training last gave the net (a new gr_net is in training mode)
 
     def close(self):
         if getattr(self, "h", None):
@@ -669,9 +691,17 @@ class Net:
 
     def set_training(self, t):
         self._c(self.lib.gr_net_set_training(self.h, int(bool(t))), "gr_net_set_training")
+        self.training = bool(t)
 
     def set_seed(self, s):
         self._c(self.lib.gr_net_set_seed(self.h, int(s)), "gr_net_set_seed")
+
+    def forward_counter(self):
+        """the Philox forward-call counter (gr_net_get_forward_counter): forwards since set_seed, in either mode"""
+        return int(self.lib.gr_net_get_forward_counter(self.h))
+
+    def set_forward_counter(self, counter):
+        self._c(self.lib.gr_net_set_forward_counter(self.h, int(counter)), "gr_net_set_forward_counter")
 
     def mask_size(self, layer, batch):
         return int(self.lib.gr_net_mask_size(self.h, layer, batch))

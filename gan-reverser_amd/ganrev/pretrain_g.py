@@ -14,6 +14,10 @@ Two loops, as in ganrev.train_r / ganrev.train:
                     (penalty, clamp and Adam fused), parameters pulled to the host only before a save;
   --compat        - the fevalG closure exactly as pretrain_g.lua:148-180 spells it, over optim.adam.
 
+--progress writes visualizeProgress (pretrain_g.lua:216-246) after every epoch from the device-resident autoencoder (ganrev.progress):
+<save>/progress/real_<epoch>.png and decoded_<epoch>.png (the epoch's first 100 images and their encode-decode) and
+<save>/plot_data.json (epoch, loss); the trained parameters are bit for bit those of a run without it.  Refused with --compat.
+
 Stated deviations:
   - pretrain_g.lua:112 stops when `OPT.epochs > EPOCH`: inverted, it breaks at once for any --epochs > 1 and runs forever with
     -1.  Here --epochs N plays N epochs.
@@ -26,7 +30,7 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import device, models, nn, nn_utils, optim, scripts, t7
+from . import device, models, nn, nn_utils, optim, progress, scripts, t7
 from .adversarial import penalise_and_clamp
 from .synth import synthetic_images
 
@@ -49,6 +53,7 @@ def parse(argv=None):
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
     scripts.add_dataset_options(p)                                 # :15 --dataset
     p.add_argument("--compat", action="store_true")
+    scripts.add_progress_option(p)
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
     return p.parse_args(argv)
@@ -94,6 +99,7 @@ class DeviceLoop:
         if self.images is not None:
             self.mem.free(self.images)
         self.images = self.ctx.upload(images, self.mem.malloc(images.nbytes))
+        self.n_images = images.shape[0]
         if scripts.needs_conversion(images, colorSpace):
             n, _, h, w = images.shape
             if colorSpace == "y":             # three planes in, one out: a buffer of its own
@@ -157,6 +163,7 @@ def save(OPT, ae, dims, epoch):
 
 def main(argv=None):
     OPT = parse(argv)
+    scripts.refuse_progress_in_compat(OPT)
     dims = image_dims(OPT)
     ctx = L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
@@ -176,6 +183,7 @@ def main(argv=None):
         loop = None
     else:
         loop = DeviceLoop(ae, dims, OPT.batchSize, L.Hyper(l1=OPT.G_L1, l2=OPT.G_L2, clamp=OPT.G_clamp))
+    pictures = progress.AutoencoderPictures(loop, dims, OPT.colorSpace, OPT.save) if OPT.progress else None
     EPOCH, last, path, t0 = 1, None, None, time.perf_counter()
     try:
         for _ in range(OPT.epochs):                                       # pretrain_g.lua:112's stop test, not inverted (module docstring)
@@ -199,6 +207,8 @@ def main(argv=None):
                         last = res
             if not OPT.quiet:
                 print("<trainer> last batch loss: %.4f" % last)
+            if pictures is not None:
+                pictures.visualize(EPOCH, last)                           # :125-127, after the epoch
             if EPOCH % OPT.saveFreq == 0:                                 # :187
                 if loop is not None:
                     loop.sync_to_host()
@@ -214,9 +224,11 @@ def main(argv=None):
         if not OPT.quiet:
             print("<trainer> %.1f images/s" % (OPT.epochs * nLoad / (time.perf_counter() - t0)))
     finally:
+        if pictures is not None:
+            pictures.close()
         if loop is not None:
             loop.close()
-    return dict(path=path, last_loss=last, model=ae, epoch=EPOCH - 1)
+    return dict(path=path, last_loss=last, model=ae, epoch=EPOCH - 1, pictures=pictures)
 
 
 if __name__ == "__main__":

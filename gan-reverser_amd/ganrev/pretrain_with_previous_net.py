@@ -10,8 +10,10 @@ D's predictions as SOFT targets), each under its L1 / L2 penalty, gradient clamp
 Same option names and defaults as pretrain_with_previous_net.lua:12-37.  --noplot, --window, --aws, --threads and --N_epoch are
 accepted and unused (the reference's `display` UI, thread count and an option its loop never reads).  Real images come from --data
 (an rgb [N x 3 x H x W] float32 .npy in [0, 1], converted to --colorSpace with rgbToColorSpace as dataset.lua:153 does) or, without
-it, from synth.synthetic_images, or from --dataset DIR through ganrev.dataset (DATASET.loadRandomImages(batchSize / 2) per batch, :171);
-visualizeProgress (:270-306) is out of scope.
+it, from synth.synthetic_images, or from --dataset DIR through ganrev.dataset (DATASET.loadRandomImages(batchSize / 2) per batch, :171).
+--progress writes visualizeProgress (:270-306) every 10th batch (:245-247) from the device-resident new G and D (ganrev.progress):
+<save>/progress/images_<batch>.png, good_<batch>.png and bad_<batch>.png; its 50 real images are drawn beside the training stream
+(a --dataset draw with a seed of its own), so the trained parameters are bit for bit those of a run without it.  Refused with --compat.
 
 Two loops, as in ganrev.pretrain_g:
   fast (default)  - device-resident: gr_fill_*_dev for both noise tensors, gr_copy2d_dev for the shared noise columns and the two
@@ -35,7 +37,7 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import device, models, nn, nn_utils, optim, scripts, t7
+from . import device, models, nn, nn_utils, optim, progress, scripts, t7
 from .adversarial import penalise_and_clamp
 from .synth import synthetic_images
 
@@ -70,6 +72,7 @@ def parse(argv=None):
     p.add_argument("--data", default="", help="rgb [N x 3 x H x W] float32 .npy of real images in [0, 1]; default: synthetic")      # :36 --dataset
     scripts.add_dataset_options(p)                                 # :36 --dataset
     p.add_argument("--compat", action="store_true")
+    scripts.add_progress_option(p)
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
     return p.parse_args(argv)
@@ -114,6 +117,16 @@ def real_images(OPT, data, i, half, DATASET=None):
     if data is not None:
         return np.ascontiguousarray(data[((i - 1) * half + np.arange(half)) % len(data)], np.float32)
     return synthetic_images(half, (3, OPT.height, OPT.width), OPT.seed * 7919 + i * 3)
+
+
+def picture_images(OPT, data, i, DATASET=None):
+    """imagesReal = DATASET.loadRandomImages(50) of visualizeProgress(i) (:279), as rgb [50 x 3 x H x W], WITHOUT touching what the
+    batches read: a draw of the loader with a seed of its own (its draw count stays), --data from its end, or synthetic images of another seed"""
+    if DATASET is not None:
+        return DATASET.loadRandomImages(50, seed=[OPT.seed, 0x70726F67, i], device=False).images
+    if data is not None:
+        return np.ascontiguousarray(data[(len(data) - 1 - (i * 50 + np.arange(50))) % len(data)], np.float32)
+    return synthetic_images(50, (3, OPT.height, OPT.width), OPT.seed * 7919 + i * 3 + 1)
 
 
 def compile_models(state):
@@ -295,6 +308,7 @@ def save(OPT, s):
 
 def main(argv=None):
     OPT = parse(argv)
+    scripts.refuse_progress_in_compat(OPT)
     ctx = L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
     if not OPT.quiet:
@@ -310,6 +324,7 @@ def main(argv=None):
         raise L.GanrevError(f"--data holds {tuple(data.shape[1:])} images, not rgb (3, {OPT.height}, {OPT.width})")
     DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width)                               # :69-73; rgb: converted with the generated half (:173-176)
     loop = None if OPT.compat else DeviceDistill(s)
+    pictures = progress.DistillPictures(loop, OPT.save) if OPT.progress else None
     half, last, path, t0 = OPT.batchSize // 2, None, None, time.perf_counter()
     pull = (lambda: (s.G.pull_params(), s.D.pull_params())) if loop is None else loop.sync_to_host
     try:
@@ -322,6 +337,8 @@ def main(argv=None):
                 last = loop.batch(real, want_loss=want) or last
             if not OPT.quiet:
                 print("<batch %d of %d (%.2f%%)> loss G: %.4f, loss D: %.4f" % (i, OPT.N_batches, 100.0 * i / OPT.N_batches, last[0], last[1]))
+            if pictures is not None and i % 10 == 0:                                                # :245-247
+                pictures.visualize(picture_images(OPT, data, i, DATASET), i)
             if i % OPT.saveFreq == 0:                                                               # :249-251
                 pull()
                 path = save(OPT, s)
@@ -330,9 +347,11 @@ def main(argv=None):
         if not OPT.quiet:
             print("<trainer> %.1f images/s" % (OPT.N_batches * OPT.batchSize / (time.perf_counter() - t0)))
     finally:
+        if pictures is not None:
+            pictures.close()
         if loop is not None:
             loop.close()
-    return dict(path=path, last_losses=last, G=s.G, D=s.D, state=s)
+    return dict(path=path, last_losses=last, G=s.G, D=s.D, state=s, pictures=pictures)
 
 
 if __name__ == "__main__":

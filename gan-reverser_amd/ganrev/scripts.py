@@ -45,6 +45,20 @@ def add_dataset_options(p):
     p.add_argument("--fileExtension", default="jpg", help="only files whose name ends in this are loaded (the reference hard-codes jpg)")
 
 
+def add_progress_option(p):
+    """--progress: True when given, None (not False) when absent - opt_table saves scalars, so a run without the option writes the opt table,
+    and with it the checkpoint, it wrote before the option existed"""
+    p.add_argument("--progress", action="store_true", default=None,
+                   help="write the reference's visualizeProgress pictures and plot_data.json under --save (ganrev.progress); off: nothing changes")
+
+
+def refuse_progress_in_compat(OPT):
+    """--progress draws from the device-resident loop's nets where they lie (ganrev.progress); the --compat loops keep their parameters in
+    host vectors that every forward uploads, so they have no such state to look at: the combination is refused, not approximated."""
+    if OPT.progress and OPT.compat:
+        raise L.GanrevError("--progress needs the device-resident loop: it cannot be combined with --compat")
+
+
 def open_dataset(OPT, colorSpace, height, width):
     """The five DATASET.set* calls of a script's head when --dataset names a directory -> the configured ganrev.dataset module, else None.
     The reference asserts OPT.dataset ~= "NONE"; here NONE keeps --data / the synthetic images.  Giving both --data and --dataset is an error.

@@ -6,8 +6,11 @@ Without --network, G starts from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (
 
     python -m ganrev.train --epochs 5 --N_epoch 30 --batchSize 32 --save logs [--dataset DIR | --data images.npy] [--compat]
 
-Same option names and defaults as train.lua:12-60 for what is mirrored.  Normalisation, plots / `display` and image grids are out
-of scope.  Training images come from --dataset DIR (ganrev.dataset = dataset.lua: DATASET.loadRandomImages per
+Same option names and defaults as train.lua:12-60 for what is mirrored.  Normalisation and the `display` UI are out of scope (SURVEY.md
+section 2).  --progress writes visualizeProgress's pictures (train.lua:268-319) per epoch -
+<save>/images, images_good, images_bad, images_train - and <save>/plot_data.json from the device-resident models (ganrev.progress),
+and stores vis_noise_inputs and plot_data in the checkpoint, which --network reuses (train.lua:116,204,256); the trained parameters are
+bit for bit those of a run without it.  It needs the fast loop (refused with --compat).  Training images come from --dataset DIR (ganrev.dataset = dataset.lua: DATASET.loadRandomImages per
 epoch, train.lua:216; files matching --fileExtension), from --data (an [N x C x H x W] float32 .npy in [0, 1]) or, without either,
 from a synthetic generator.  --colorSpace takes the
 reference's rgb | yuv | hsl | y (train.lua:45) besides gray (= y, one channel): three-channel rgb images are converted with
@@ -24,7 +27,7 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import adversarial, models, nn_utils, pretrain_g, scripts, t7
+from . import adversarial, models, nn_utils, pretrain_g, progress, scripts, t7
 from .synth import synthetic_images          # also the name tests and tools import it by: train.synthetic_images
 
 
@@ -62,6 +65,7 @@ def parse(argv=None):
     p.add_argument("--data", default="", help="[N x C x H x W] float32 .npy of training images; default: synthetic")
     scripts.add_dataset_options(p)                                   # train.lua:16 --dataset
     p.add_argument("--compat", action="store_true")
+    scripts.add_progress_option(p)
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
     return p.parse_args(argv)
@@ -85,8 +89,9 @@ def create_or_load_G(OPT, dims):
     return scripts.load_checkpoint(path)["G"].training()
 
 
-def save(OPT, env, epoch, quiet=True):
-    """train.lua:236-257: logs/adversarial.net (the previous file moved to .old), {D, G, opt, epoch}."""
+def save(OPT, env, epoch, quiet=True, pictures=None):
+    """train.lua:236-257: logs/adversarial.net (the previous file moved to .old), {D, G, opt, epoch}; with --progress (pictures)
+    also {plot_data, vis_noise_inputs}, as train.lua:256."""
     filename = os.path.join(OPT.save, "adversarial.net")
     env.MODEL_G.pull_params(); env.MODEL_D.pull_params()             # current BatchNorm running statistics (and parameters) into the modules
     os.makedirs(os.path.dirname(filename) or ".", exist_ok=True)
@@ -94,16 +99,18 @@ def save(OPT, env, epoch, quiet=True):
         os.replace(filename, filename + ".old")
     if not quiet:
         print("<trainer> saving network to %s" % filename)
-    t7.save_checkpoint(filename, D=env.MODEL_D, G=env.MODEL_G, opt=scripts.opt_table(OPT), epoch=epoch)
+    extra = {} if pictures is None else dict(plot_data=pictures.plot_data, vis_noise_inputs=pictures.vis_noise_inputs)
+    t7.save_checkpoint(filename, D=env.MODEL_D, G=env.MODEL_G, opt=scripts.opt_table(OPT), epoch=epoch, **extra)
     return filename
 
 
 def main(argv=None):
     OPT = parse(argv)
+    scripts.refuse_progress_in_compat(OPT)
     dims = scripts.image_dims(OPT.colorSpace, OPT.height, OPT.width)
     ctx = L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
-    epoch0 = 1
+    epoch0, ck = 1, {}
     if OPT.network:                                                   # train.lua:125-140
         ck = scripts.load_checkpoint(OPT.network)
         MODEL_D, MODEL_G, epoch0 = ck["D"], ck["G"], int(ck.get("epoch", 0)) + 1      # train.lua:113  EPOCH = tmp.epoch + 1
@@ -117,6 +124,11 @@ def main(argv=None):
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
     DATASET = scripts.open_dataset(OPT, OPT.colorSpace, OPT.height, OPT.width)      # train.lua:81-85
     game = None if OPT.compat else adversarial.DeviceGame(env)       # every method of train.lua:37-38 has its fused device update
+    pictures = None
+    if OPT.progress:                                                  # train.lua:116,203-204: VIS_NOISE_INPUTS of the checkpoint, or fresh
+        vis, plot = ck.get("vis_noise_inputs"), ck.get("plot_data")
+        pictures = progress.TrainPictures(game, dims, OPT.colorSpace, OPT.save, vis_noise_inputs=vis if isinstance(vis, np.ndarray) else None,
+                                          plot_data=plot if isinstance(plot, list) else None)
     N_epoch = OPT.N_epoch if OPT.N_epoch > 0 else 100                 # adversarial.lua:42-45: N_epoch <= 0 means 100 batches
     D_it, G_it = max(0, OPT.D_iterations), max(0, OPT.G_iterations)   # 0 iterations freeze that net (adversarial.lua:127,168 loop zero times)
     # a continued run must not replay the first epochs' noise: the counters start where epoch0 - 1 finished epochs left them
@@ -140,6 +152,8 @@ def main(argv=None):
         if DATASET is None and scripts.needs_conversion(TRAIN_DATA, OPT.colorSpace):
             # rgb images seen in another space (dataset.lua:153): one gr_colorspace_host call per epoch load
             TRAIN_DATA = nn_utils.rgbToColorSpace(np.ascontiguousarray(TRAIN_DATA, np.float32), OPT.colorSpace)
+        if pictures is not None:
+            pictures.visualize(TRAIN_DATA, env.EPOCH)                 # train.lua:222-224, between the load and the epoch
         if game is None:
             adversarial.train(env, TRAIN_DATA, quiet=OPT.quiet)       # train.lua:229
             last = (env.last_losses["D"][-1], env.last_losses["G"][-1])
@@ -153,17 +167,21 @@ def main(argv=None):
         images += N_epoch * OPT.batchSize * G_it
         if not OPT.quiet:
             print("<trainer> epoch %d: loss D=%.4f G=%.4f" % (env.EPOCH, last[0], last[1]))
+        if pictures is not None:
+            pictures.log(env.EPOCH, last[0], last[1])
         if env.EPOCH % OPT.saveFreq == 0:                             # train.lua:232-234
             if game is not None:
                 game.sync_to_host()
-            save(OPT, env, env.EPOCH, OPT.quiet)
+            save(OPT, env, env.EPOCH, OPT.quiet, pictures)
         env.EPOCH += 1
     if game is not None:
         game.sync_to_host()
-    path = save(OPT, env, env.EPOCH - 1, OPT.quiet)                   # train.lua:209-211 "Last epoch reached."
+    path = save(OPT, env, env.EPOCH - 1, OPT.quiet, pictures)         # train.lua:209-211 "Last epoch reached."
+    if pictures is not None:
+        pictures.close()
     if not OPT.quiet:
         print("<trainer> %.1f generated images/s" % (images / (time.perf_counter() - t0)))
-    return dict(path=path, last_losses=last, epoch=env.EPOCH - 1, env=env)
+    return dict(path=path, last_losses=last, epoch=env.EPOCH - 1, env=env, pictures=pictures)
 
 
 if __name__ == "__main__":

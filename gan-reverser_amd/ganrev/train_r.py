@@ -2,7 +2,10 @@
 
     python -m ganrev.train_r --G g.npz --batchSize 32 --nbBatches 2000 --R_L2 1e-4 --R_clamp 1 --seed 1
 
-Same options and defaults as train_r.lua:12-29 (plots / `display` / `--noplot` are out of scope).  The G "checkpoint" is an
+Same options and defaults as train_r.lua:12-29 (the `display` UI and `--noplot` are out of scope).  --progress writes, from the
+device-resident nets (ganrev.progress), the interleaved pairs image, G(R(image)) of every 25th batch (train_r.lua:207-220) as
+<save>/progress/pairs_<batch>.png and PLOT_DATA (low / avg / high loss per 100 batches, :191-204) as <save>/plot_data.json; --save is
+then a directory.  The trained R is bit for bit that of a run without it.  Refused with --compat.  The G "checkpoint" is an
 .npz written by save_model() below (the reference's .t7 format is Torch7's own serialisation, out of scope); without --G a
 random-initialised create_G3 of the requested shape is used, which is what bench.py measures.
 
@@ -16,7 +19,7 @@ import time
 import numpy as np
 
 from . import _lib as L
-from . import models, nn, nn_utils, optim, scripts, synth
+from . import models, nn, nn_utils, optim, progress, scripts, synth
 from .adversarial import penalise_and_clamp
 from .parallel import DeviceTrainer
 
@@ -59,6 +62,7 @@ def parse(argv=None):
     p.add_argument("--channels", type=int, default=1)
     scripts.add_dataset_options(p)                                 # train_r.lua:14 --dataset (configured as there, never read: R learns from G's images)
     p.add_argument("--compat", action="store_true")
+    scripts.add_progress_option(p)
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
     return p.parse_args(argv)
@@ -66,7 +70,11 @@ def parse(argv=None):
 
 def main(argv=None):
     OPT = parse(argv)
+    scripts.refuse_progress_in_compat(OPT)
+    if OPT.progress and (not OPT.save or str(OPT.save).endswith((".net", ".t7", ".npz"))):
+        raise L.GanrevError("--progress writes its pictures under --save, which must then name a directory")
     dims = (OPT.channels, OPT.height, OPT.width)
+    picture_space = "y" if OPT.channels == 1 else "rgb"
     ctx = L.Context(OPT.gpu) if OPT.gpu != int(__import__("os").environ.get("LOCAL_RANK", "0")) else L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
     if OPT.G and OPT.G.endswith((".net", ".t7")):
@@ -79,6 +87,7 @@ def main(argv=None):
         OPT.noiseDim, OPT.noiseMethod = int(o.get("noiseDim", OPT.noiseDim)), o.get("noiseMethod", OPT.noiseMethod)
         OPT.height, OPT.width = int(o.get("height", OPT.height)), int(o.get("width", OPT.width))
         OPT.channels = 1 if o.get("colorSpace", "rgb") == "y" else 3
+        picture_space = o.get("colorSpace", "rgb")                       # what G paints in: --progress shows it through toRgb (:217)
         dims = (OPT.channels, OPT.height, OPT.width)
     else:
         MODEL_G = models.create_G(dims, OPT.noiseDim, seed=OPT.seed)
@@ -158,6 +167,9 @@ def main(argv=None):
         MODEL_R._net.set_seed(OPT.seed); MODEL_R._net.adam_reset()
         tr = DeviceTrainer(ctx, MODEL_G._net, MODEL_R._net, L.Hyper(l1=OPT.R_L1, l2=OPT.R_L2, clamp=OPT.R_clamp), OPT.batchSize,
                            noise_method=OPT.noiseMethod)
+        pictures = None
+        if OPT.progress:
+            pictures = progress.ReverserPictures(ctx, MODEL_G._net, MODEL_R._net, dims, OPT.noiseDim, OPT.batchSize, picture_space, OPT.save)
         t0 = time.perf_counter()
         nb = 0
         for batchIdx in batches():
@@ -169,6 +181,10 @@ def main(argv=None):
                 print("[batch %d of %d (%.2f%%)] loss R=%.4f" % (batchIdx, OPT.nbBatches, 100 * batchIdx / OPT.nbBatches, loss))
             if batchIdx % OPT.saveFreq == 0:                             # :185-187
                 save()
+            if pictures is not None:
+                pictures.after_batch(batchIdx, loss, tr.noise)           # :189-222
+        if pictures is not None:
+            pictures.close()
         if not OPT.quiet:
             print("<trainer> Last batch reached. %.1f images/s" % (OPT.batchSize * nb / (time.perf_counter() - t0)))
     save()                                                               # :136 "Last batch reached" -> save()

@@ -31,6 +31,7 @@ int gr_net_get_grads(gr_net*, float*);   int gr_net_zero_grads(gr_net*);
 int gr_net_n_bn(gr_net*);
 int gr_net_get_bn_running(gr_net*, int, float*, float*); int gr_net_set_bn_running(gr_net*, int, const float*, const float*);
 int gr_net_set_training(gr_net*, int);   int gr_net_set_seed(gr_net*, uint64_t);
+int64_t gr_net_get_forward_counter(gr_net*);  int gr_net_set_forward_counter(gr_net*, int64_t counter);     /* the Philox forward-call counter: read it, look at the model, set it back */
 int gr_net_forward_host(gr_net*, const float* in_host, int batch, float* out_host);
 int gr_net_backward_host(gr_net*, const float* in_host, const float* gout_host, int batch, float* gin_host);
 int gr_mse_host(gr_ctx*, const float*, const float*, int64_t n, int64_t n_global, double* loss, float* grad);
@@ -64,6 +65,8 @@ int gr_image_grid_dev(gr_ctx*, const float* const* src_dev, const int64_t* n_row
                       const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,
                       const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid_dev, uint8_t* u8_dev);     /* image.toDisplayTensor + decorations, apply_r.lua / sample.lua */
 int gr_rows_mean_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_host, int n, float* out_dev);   /* apply_r.lua:233-243 */
+int gr_progress_grid_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int channels, int h, int w, int from_space,
+                         const int64_t* rows_host, int n_show, int grid_h, int grid_w, int epoch, float* grid_dev, uint8_t* u8_dev);     /* imagesToGridTensor, utils/nn_utils.lua:490-548 */
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);
 float* gr_net_output_dev(gr_net*);
 int gr_net_forward_batched_dev(gr_net*, const float* in_dev, int64_t rows, int batch, float* out_dev);   /* utils/nn_utils.lua:5-33 */

@@ -93,6 +93,12 @@ int gr_net_set_training(gr_net* net, int training);
 /* Dropout noise: production = counter-based Philox keyed (seed, forward-call counter, layer, element)
  * [replaces torch.manualSeed-driven MT19937, train_r.lua:38-39]; tests inject explicit keep flags. */
 int gr_net_set_seed(gr_net* net, uint64_t seed);
+/* The forward-call counter of that key: every gr_net_forward_* adds one, in either mode; gr_net_set_seed restarts it at 0.  Reading it
+ * before a forward that is only an observation (an evaluate() look at the model in the middle of a training run: ganrev/progress.py) and
+ * setting it back afterwards leaves the Dropout masks of every later forward as they would have been without it.  get: -1 for a null
+ * net; set: GR_ERR_INVALID for a null net or a negative counter. */
+int64_t gr_net_get_forward_counter(gr_net* net);
+int gr_net_set_forward_counter(gr_net* net, int64_t counter);
 int64_t gr_net_mask_size(gr_net* net, int layer_index, int batch);       /* elements of that layer's noise tensor */
 int gr_net_set_mask(gr_net* net, int layer_index, const uint8_t* keep_host, int64_t n);  /* used by the NEXT forward only */
 int gr_net_get_mask(gr_net* net, int layer_index, uint8_t* keep_host, int64_t n);        /* noise of the LAST forward */
@@ -333,6 +339,28 @@ int gr_image_grid_dev(gr_ctx* ctx, const float* const* src_dev, const int64_t* n
                       const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,
                       const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid_dev, uint8_t* u8_dev);
 int gr_rows_mean_dev(gr_ctx* ctx, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_host, int n, float* out_dev);
+
+/* ---- The trainers' progress pictures: NN_UTILS.imagesToGridTensor + saveImagesAsGrid (utils/nn_utils.lua:490-548) from a device-resident
+ * table [n_rows x channels x h x w] fp32 (train.lua:312-314; ganrev/progress.py).  Not image.toDisplayTensor: a fixed grid_h x grid_w
+ * grid of cells without padding, seven more pixel rows below them, and the epoch number drawn there.
+ *   layout     the grid is GH x GW = (grid_h h + 7) x (grid_w w) and starts as zeros.  Cell t < min(n_show, grid_h grid_w) shows table row
+ *              rows_host[t]; cells fill row-major, the top-left corner of cell t is ((t / grid_w) h, (t % grid_w) w).  Later cells and the
+ *              seven bottom rows stay 0; entries of rows_host beyond the grid are ignored (and not checked).
+ *   colour     as gr_image_grid_dev: from_space = GR_CS_* sends the tile through the toRgb arithmetic of gr_colorspace_* and the grid has 3
+ *              channels; from_space = -1 copies the channels as they are.
+ *   digits     the decimal digits of epoch, least significant first: digit number p = 1, 2, ... covers rows GH-7 .. GH-3 and columns
+ *              GW-2-6p .. GW-6p (0-based), a 3 x 5 block of 0 / 1 written into every channel after the tiles, its zeros included.  The
+ *              glyphs are the seven-segment shapes of utils/nn_utils.lua:430-479 ("1" is the right-hand column only).
+ *   outputs    grid_dev [Cout x GH x GW] floats, the values as they are (no clamp), and / or u8_dev [GH x GW x Cout] bytes by the
+ *              quantisation rule of gr_image_grid_dev with lo = 0, hi = 1: u8 = (uint8) min(255, max(0, trunc(clamp(v, 0, 1) * 255 + 0.5))),
+ *              a NaN gives 0.
+ * One launch on the ctx stream.  Four pixels of a grid row per thread when w is a multiple of 4 and table_dev / grid_dev are 16-byte,
+ * u8_dev 4-byte aligned (16-byte loads and grid stores, the 4 Cout bytes of u8 as Cout words); one pixel per thread otherwise.
+ * GR_ERR_INVALID with a gr_last_error message, and no launch, for: a null table, both outputs null, channels / from_space that do not
+ * fit, n_rows, h, w, grid_h, grid_w < 1, n_show < 0 (or rows_host null with cells to show), a row outside [0, n_rows) among the rows shown,
+ * epoch < 0, digits that do not fit (GW - 2 - 6 ndigits < 0: the reference raises an index error there), a grid beyond 2^28 pixels. ---- */
+int gr_progress_grid_dev(gr_ctx* ctx, const float* table_dev, int64_t n_rows, int channels, int h, int w, int from_space,
+                         const int64_t* rows_host, int n_show, int grid_h, int grid_w, int epoch, float* grid_dev /*nullable*/, uint8_t* u8_dev /*nullable*/);
 
 /* ---- sample.lua:130-148 findClosestNeighboursOf: the k nearest table rows of each query by torch.dist ----
  * Contract: for each query q [d] and table row x_j [d] (table [n x d], fp32, contiguous)
