@@ -1,4 +1,5 @@
-// net.hip — the C ABI (include/ganrev.h) and the nn.Sequential runtime behind it.
+// net.hip — the context (gr_ctx, ctx.h) and the nn.Sequential runtime behind the net half of the C ABI (include/ganrev.h); the
+// context-level operators, which touch no gr_net, are in ops.hip.
 //
 // A gr_net is the reference's nn.Sequential (models.lua:104-143 G3, models.lua:389-464 R) compiled into
 // STAGES:  [UpSample2] (Conv3x3 | Linear) [BN] [act] [Dropout|SpatialDropout] [MaxPool2|AvgPool2] [Dropout]
@@ -6,74 +7,15 @@
 // Backward mirrors it (train_r.lua:151): pipeline backward (two passes around the BN reduction) ->
 // weight-gradient kernel -> data-gradient kernel.  All device memory is owned by the net / ctx; there is
 // no CPU fallback anywhere in this file.
-#include "../../include/ganrev.h"
-#include "kernels.h"
-#include <rccl/rccl.h>
+#include "ctx.h"
 #include <roctracer/roctx.h>
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
 using namespace gr;
-
-// ------------------------------------------------------------------ context
-struct gr_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  ncclComm_t comm = nullptr;
-  ncclComm_t stat_comm = nullptr;             // synchronised BatchNorm's own communicator (ncclCommSplit of comm): its collectives run on the COMPUTE stream while the gradient
-                                              // buckets run on comm_stream - two streams never share one communicator
-  int nranks = 1, rank = 0;
-  hipStream_t comm_stream = nullptr;          // gradient buckets are reduced here, behind the rest of backward
-  hipEvent_t ev_ready = nullptr, ev_done = nullptr;
-  void* ws = nullptr; size_t ws_bytes = 0;
-  // weight gradients run beside the rest of backward (backward_impl): their own stream, workspace and events
-  hipStream_t side_stream = nullptr; void* ws2 = nullptr; size_t ws2_bytes = 0;
-  hipEvent_t ev_dy_ready = nullptr, ev_wgrad_done[2] = {nullptr, nullptr};
-  // R's head in one launch (gr_train_r_step, elem.hip head_fwd_bwd_kernel): grid-barrier counter (monotonic) and per-workgroup loss partials
-  unsigned* head_bar = nullptr; unsigned head_bar_count = 0; double* head_loss_part = nullptr;
-  bool head_unchecked = false;         // a head kernel has been launched since the sticky fault word (d_loss + 48) was last read: head_fault_check
-  int head_fault_inject = 0;           // gr_set_tuning "head_fault_inject" (test hook): the NEXT head launch waits at its barriers for an arrival count that never comes
-  int cu_count = 0;                    // the grid barrier needs every workgroup of the head kernel resident at once: head_plan refuses devices with fewer CUs than workgroups
-  int fused_head = 1;                  // gr_set_tuning "fused_head" (1 default; 0 = the stage-by-stage path: the A/B control and what every other entry point runs)
-  int side_wgrad = -1;                 // gr_set_tuning "side_wgrad" / GR_SIDE_WGRAD: 1 on, 0 off, -1 (default) by size.  The MFMA kernels take the whole register file of a
-                                       // CU (2 waves x 256 VGPRs per SIMD), so nothing becomes resident beside a weight gradient and only kernel tails overlap.  Round 5,
-                                       // same box, interleaved (profiles/r05_ab_side_wgrad_*.txt): cfg2 1.976 -> 1.998 ms (slower: the tails are a few us and two streams
-                                       // cost an event hand-over per stage), cfg3 12.005 -> 11.875 ms (faster: the slab write + reduction tail of a 0.3 ms launch hides
-                                       // behind the data gradient).  Auto = on for stages of >= 2^26 activations (cfg3's layers; cfg2's have 2^24).  Bit-identical
-                                       // either way.  Per-kernel timing (gr_set_timing 2) forces it off, so that kernel durations are not inflated by overlap.
-  double* d_loss = nullptr;     // device scalar (64-byte block: +0 the loss, +16 the range guard's alarm word, +32 the search's arrival counter, +48 the head kernel's sticky fault word)
-  double* h_loss = nullptr;     // pinned host scalar
-  bool timing = false;
-  int conv_mode = 2;            // 2 = f16x3 split (fp32-accurate, f16 MFMA; default), 1 = bf16x6 split (fp32-accurate, bf16 MFMA), 0 = exact fp32 MFMA
-  unsigned* amax = nullptr;     // 4 scratch slots for the single-kernel entry points (f16x3 scales)
-  hipEvent_t ev[7] = {};
-  std::vector<hipEvent_t> marks;  // gr_event_record slots (bench: per-step times on THIS stream)
-  float times[6] = {0, 0, 0, 0, 0, 0};
-  // f16x3 range guard (kernels.h "range guard"): the alarm word lives behind the loss scalar (d_loss + 16 bytes,
-  // mirrored at h_loss + 16), chmax is the per-channel scratch of the scans
-  int range_guard = 1;                 // 1: on (gr_set_tuning "range_guard")
-  unsigned* guard_chmax = nullptr; size_t guard_chmax_cap = 0;     // (capacity in bytes)
-  long guard_scans = 0, guard_fallbacks = 0;
-  long search_reruns = 0;              // searches whose sample-bound filter overflowed and ran again unfiltered
-  void* pin = nullptr; size_t pin_bytes = 0;   // pinned staging for small results (search)
-  unsigned* search_state = nullptr;    // device words of the small search path (kernels.h SEARCH_STATE_WORDS)
-  unsigned* pin_done = nullptr; unsigned search_seq = 0;   // per-needle completion words of the small search path (pinned, 64 bytes) and the sequence number they carry
-  hipEvent_t ev_guard = nullptr; bool guard_pending = false;   // device-resident trainer: sampled scans, verdict read one call later
-  bool guard_tripped = false;          // ... which found a hostile range: the context stays on bf16x6
-  // synchronised BatchNorm (gr_set_tuning "sync_bn", SURVEY.md 8e optional) and the host-exchange hook that can stand in for RCCL
-  int sync_bn = 0;
-  double* sync_buf = nullptr; size_t sync_cap = 0;     // compact per-channel pairs that travel through the collective
-  gr_exchange_fn xchg = nullptr; void* xchg_user = nullptr;
-  int coll_rc = 0;                     // first failure of a collective issued from inside a kernel launcher (StatSync callbacks)
-};
 
 // ---- per-kernel event timer (gr_set_timing(ctx, 2)) -------------------------------------------------------------
 namespace gr { KernelTimer* g_ktimer = nullptr; }
@@ -126,21 +68,15 @@ struct EventTimer : gr::KernelTimer {
 };
 static EventTimer* g_evtimer = nullptr;
 
-static int fail(gr_ctx* c, int code, const char* fmt, ...) {
+int fail(gr_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
   if (c) c->err = buf;
   return code;
 }
-#define HIPCHK(ctx, call)                                                                             \
-  do { hipError_t e_ = (call); if (e_ != hipSuccess)                                                  \
-      return fail(ctx, GR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define NCCLCHK(ctx, call)                                                                            \
   do { ncclResult_t r_ = (call); if (r_ != ncclSuccess)                                               \
       return fail(ctx, GR_ERR_COMM, "%s failed: %s (%s:%d)", #call, ncclGetErrorString(r_), __FILE__, __LINE__); } while (0)
-#define LAUNCHCHK(ctx)                                                                                \
-  do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess)                                       \
-      return fail(ctx, GR_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 // RCCL reports failures of already-enqueued collectives (a peer that died, a transport error) asynchronously: asked for after
 // every group of collectives this library issues, so that a broken communicator surfaces as GR_ERR_COMM in the call that
@@ -200,20 +136,6 @@ static const StatSync* stat_sync(gr_ctx* c, StatSync& ss, int C, double n_local)
 // roctx range of one phase of gr_train_r_step (shows up in rocprofv3 --marker-trace / the rocprof timeline; a no-op without a tool)
 struct PhaseRange { explicit PhaseRange(const char* name) { roctxRangePushA(name); } ~PhaseRange() { roctxRangePop(); } };
 
-// Device buffers p[0..nbuf) that share the capacity `cap` (bytes) get `bytes` each when they hold less.  The old ones are freed once
-// stream s, the one that may still read them, has drained (a buffer of capacity 0 was never handed to a kernel).  Contents are not kept.
-template <class T> static int grow_dev(gr_ctx* c, T** p, size_t& cap, size_t bytes, hipStream_t s, int nbuf = 1) {
-  if (bytes <= cap) return GR_OK;
-  if (cap) HIPCHK(c, hipStreamSynchronize(s));
-  for (int i = 0; i < nbuf; ++i) { HIPCHK(c, hipFree(p[i])); p[i] = nullptr; }
-  cap = 0;
-  for (int i = 0; i < nbuf; ++i) HIPCHK(c, hipMalloc((void**)&p[i], bytes));
-  cap = bytes;
-  return GR_OK;
-}
-// the workspaces grow past the next MiB boundary
-static size_t past_next_mib(size_t bytes) { return (bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1); }
-static int ensure_ws(gr_ctx* c, size_t bytes) { return bytes <= c->ws_bytes ? GR_OK : grow_dev(c, &c->ws, c->ws_bytes, past_next_mib(bytes), c->stream); }
 // workspace of the side stream (weight gradients running beside the rest of backward)
 static int ensure_ws2(gr_ctx* c, size_t bytes) { return bytes <= c->ws2_bytes ? GR_OK : grow_dev(c, &c->ws2, c->ws2_bytes, past_next_mib(bytes), c->side_stream); }
 
@@ -1659,147 +1581,6 @@ extern "C" int gr_net_backward_host(gr_net* n, const float* in_host, const float
   return GR_OK;
 }
 
-// ------------------------------------------------------------------ criterion
-extern "C" int gr_mse_dev(gr_ctx* c, const float* x, const float* t, int64_t n, int64_t ng, double* loss_dev, float* grad) {
-  if (!c || !x || !t || n <= 0 || ng <= 0) return GR_ERR_INVALID;
-  launch_mse(x, t, n, ng, loss_dev, grad, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-extern "C" int gr_mse_host(gr_ctx* c, const float* x, const float* t, int64_t n, int64_t ng, double* loss, float* grad) {
-  if (!c || !x || !t || n <= 0 || ng <= 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int r = ensure_ws(c, sizeof(float) * 3 * (size_t)n); if (r) return r;
-  float* dx = (float*)c->ws; float* dt = dx + n; float* dg = dt + n;
-  HIPCHK(c, hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dt, t, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-  launch_mse(dx, dt, n, ng, c->d_loss, grad ? dg : nullptr, c->stream); LAUNCHCHK(c);
-  if (grad) HIPCHK(c, hipMemcpyAsync(grad, dg, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_loss, c->d_loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (loss) *loss = *c->h_loss;
-  return GR_OK;
-}
-// nn.BCECriterion (sizeAverage): train.lua:173's CRITERION, used by adversarial.lua (the GAN step's loss; first pieces of SURVEY.md 8f rank 4)
-extern "C" int gr_bce_dev(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss_dev, float* grad) {
-  if (!c || !x || !t || n <= 0) return GR_ERR_INVALID;
-  launch_bce(x, t, n, loss_dev, grad, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-extern "C" int gr_bce_host(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss, float* grad) {
-  if (!c || !x || !t || n <= 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int r = ensure_ws(c, sizeof(float) * 3 * (size_t)n); if (r) return r;
-  float* dx = (float*)c->ws; float* dt = dx + n; float* dg = dt + n;
-  HIPCHK(c, hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dt, t, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-  launch_bce(dx, dt, n, c->d_loss, grad ? dg : nullptr, c->stream); LAUNCHCHK(c);
-  if (grad) HIPCHK(c, hipMemcpyAsync(grad, dg, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_loss, c->d_loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (loss) *loss = *c->h_loss;
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ nn.Concat on device-resident tensors (models.lua:293-321)
-// The container stays on the host (it is a module that calls its children, not an operator); these two move its data
-// without leaving the GPU: rows of one matrix into a column range of another (join the branch outputs / slice gradOutput),
-// and the sum of the branches' gradInputs.
-extern "C" int gr_copy2d_dev(gr_ctx* c, float* dst, int64_t dst_pitch, const float* src, int64_t src_pitch, int64_t rows, int64_t cols) {
-  if (!c || !dst || !src || rows <= 0 || cols <= 0 || dst_pitch < cols || src_pitch < cols) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpy2DAsync(dst, sizeof(float) * (size_t)dst_pitch, src, sizeof(float) * (size_t)src_pitch, sizeof(float) * (size_t)cols, (size_t)rows,
-                             hipMemcpyDeviceToDevice, c->stream));
-  return GR_OK;
-}
-extern "C" int gr_add_dev(gr_ctx* c, float* y, const float* x, int64_t n) {
-  if (!c || !y || !x || n <= 0) return GR_ERR_INVALID;
-  launch_add_inplace(y, x, (long)n, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ NN_UTILS.switchColorSpace (utils/nn_utils.lua:133-246)
-static int colorspace_check(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, const float* out) {
-  if (!c) return GR_ERR_INVALID;
-  if (!in || !out) return fail(c, GR_ERR_INVALID, "gr_colorspace: null pointer");
-  if (from < GR_CS_RGB || from > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_colorspace: unknown color space <from>: %d", from);
-  if (to < GR_CS_RGB || to > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_colorspace: unknown color space <to>: %d", to);
-  if (batch <= 0 || h <= 0 || w <= 0) return fail(c, GR_ERR_INVALID, "gr_colorspace: batch %lld, h %d, w %d must be positive", (long long)batch, h, w);
-  if (in == out && (from == GR_CS_Y) != (to == GR_CS_Y)) return fail(c, GR_ERR_INVALID, "gr_colorspace: in place needs equal plane counts (from %d, to %d)", from, to);
-  return GR_OK;
-}
-extern "C" int gr_colorspace_dev(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, float* out) {
-  int r = colorspace_check(c, in, from, to, batch, h, w, out); if (r) return r;
-  const long hw = (long)h * w;
-  if (from == GR_CS_RGB && to == GR_CS_RGB) {
-    if (in != out) HIPCHK(c, hipMemcpyAsync(out, in, sizeof(float) * 3 * (size_t)batch * hw, hipMemcpyDeviceToDevice, c->stream));
-    return GR_OK;
-  }
-  launch_colorspace(in, from, to, (long)batch, hw, out, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-extern "C" int gr_colorspace_host(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, float* out) {
-  int r = colorspace_check(c, in, from, to, batch, h, w, out); if (r) return r;
-  const size_t hw = (size_t)h * w, nin = (from == GR_CS_Y ? 1 : 3) * (size_t)batch * hw, nout = (to == GR_CS_Y ? 1 : 3) * (size_t)batch * hw;
-  if (from == GR_CS_RGB && to == GR_CS_RGB) {
-    if (in != out) memmove(out, in, sizeof(float) * nin);
-    return GR_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t nin_pad = (nin + 3) & ~(size_t)3;                       // keeps the output 16-byte aligned behind the input
-  r = ensure_ws(c, sizeof(float) * (nin_pad + nout)); if (r) return r;
-  float* din = (float*)c->ws; float* dout = din + nin_pad;
-  HIPCHK(c, hipMemcpyAsync(din, in, sizeof(float) * nin, hipMemcpyHostToDevice, c->stream));
-  launch_colorspace(din, from, to, (long)batch, (long)hw, dout, c->stream); LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ dataset.lua:111-116,149-153: image.scale and the loader's fused path (dataset.hip)
-// GR_SCALE_MAX_ELEMS bounds both tensors of a call: the kernels index with 64-bit integers, the bound keeps every product of the geometry far inside them
-static const int64_t GR_SCALE_MAX_ELEMS = (int64_t)1 << 40;
-static int scale_check(gr_ctx* c, const char* who, const void* in, const void* out, int64_t n, int64_t per_in, int sh, int sw, int dh, int dw, int64_t per_out) {
-  if (!c) return GR_ERR_INVALID;
-  if (!in || !out) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);
-  if (n < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1) return fail(c, GR_ERR_INVALID, "%s: n %lld, source %d x %d, target %d x %d must be positive", who, (long long)n, sh, sw, dh, dw);
-  if (sh > SCALE_MAX_LEN || sw > SCALE_MAX_LEN || dh > SCALE_MAX_LEN || dw > SCALE_MAX_LEN)
-    return fail(c, GR_ERR_INVALID, "%s: source %d x %d, target %d x %d: a side is too large (at most %d)", who, sh, sw, dh, dw, SCALE_MAX_LEN);
-  const int64_t ein = per_in * sh * sw, eout = per_out * dh * dw;              // per_* <= 2^31, a side <= 2^15: below 2^61
-  if (n > GR_SCALE_MAX_ELEMS / ein || n > GR_SCALE_MAX_ELEMS / eout) return fail(c, GR_ERR_INVALID, "%s: %lld images are too large a batch (at most 2^40 elements per tensor)", who, (long long)n);
-  return GR_OK;
-}
-extern "C" int gr_image_scale_dev(gr_ctx* c, const float* in, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out) {
-  if (c && planes < 1) return fail(c, GR_ERR_INVALID, "gr_image_scale: planes %d must be positive", planes);
-  int r = scale_check(c, "gr_image_scale", in, out, n, planes, sh, sw, dh, dw, planes); if (r) return r;
-  if (in == out) return fail(c, GR_ERR_INVALID, "gr_image_scale: in place is not supported");
-  HIPCHK(c, hipSetDevice(c->device));
-  launch_image_scale(in, (long)n * planes, scale_axis(sh, dh), scale_axis(sw, dw), out, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-extern "C" int gr_image_scale_host(gr_ctx* c, const float* in, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out) {
-  if (c && planes < 1) return fail(c, GR_ERR_INVALID, "gr_image_scale: planes %d must be positive", planes);
-  int r = scale_check(c, "gr_image_scale", in, out, n, planes, sh, sw, dh, dw, planes); if (r) return r;
-  if (in == out) return fail(c, GR_ERR_INVALID, "gr_image_scale: in place is not supported");
-  const size_t nin = (size_t)n * planes * sh * sw, nout = (size_t)n * planes * dh * dw;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t nin_pad = (nin + 3) & ~(size_t)3;                       // keeps the output 16-byte aligned behind the input
-  r = ensure_ws(c, sizeof(float) * (nin_pad + nout)); if (r) return r;
-  float* din = (float*)c->ws; float* dout = din + nin_pad;
-  HIPCHK(c, hipMemcpyAsync(din, in, sizeof(float) * nin, hipMemcpyHostToDevice, c->stream));
-  launch_image_scale(din, (long)n * planes, scale_axis(sh, dh), scale_axis(sw, dw), dout, c->stream); LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GR_OK;
-}
-extern "C" int gr_dataset_images_dev(gr_ctx* c, const uint8_t* in, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize, float* out) {
-  if (c && sc != 1 && sc != 3 && sc != 4) return fail(c, GR_ERR_INVALID, "gr_dataset_images: %d source channels (1, 3 or 4)", sc);
-  if (c && (to_space < GR_CS_RGB || to_space > GR_CS_HSL)) return fail(c, GR_ERR_INVALID, "gr_dataset_images: unknown color space <to>: %d", to_space);
-  int r = scale_check(c, "gr_dataset_images", in, out, n, sc, sh, sw, dh, dw, to_space == GR_CS_Y ? 1 : 3); if (r) return r;
-  HIPCHK(c, hipSetDevice(c->device));
-  launch_dataset_images(in, (long)n, sc, scale_axis(sh, dh), scale_axis(sw, dw), to_space, normalize != 0, out, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-
 // ------------------------------------------------------------------ optimiser
 static AdamConsts adam_consts(const gr_hyper* h, int t) {
   AdamConsts k{};
@@ -2072,470 +1853,5 @@ extern "C" int gr_train_r_step(gr_net* g, gr_net* rn, const float* noise_dev, in
     if (tm) for (int i = 0; i < 6; ++i) HIPCHK(c, hipEventElapsedTime(&c->times[i], c->ev[i], c->ev[i + 1]));
     return head_fault_check(c);       // (this call has waited for the stream anyway: a timed-out grid barrier of this or an earlier step surfaces here)
   }
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ search
-extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
-                                  int64_t* idx_out, float* score_out, int accf) {
-  if (!c || !emb || !qrows || !idx_out || N <= 0 || d <= 0 || Q <= 0 || k <= 0) return GR_ERR_INVALID;
-  if (k > N) k = (int)N;
-  for (int q = 0; q < Q; ++q) if (qrows[q] < 0 || qrows[q] >= N) return fail(c, GR_ERR_INVALID, "query row %lld out of range", (long long)qrows[q]);
-  if (k > 1024) return fail(c, GR_ERR_UNSUPPORTED, "k > 1024");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t tail = sizeof(long) * (size_t)Q * (k + 1) + sizeof(float) * (size_t)Q * k + 512;
-  const size_t wsb = cosine_topk_workspace_bytes(N, d, Q, k);
-  int r = ensure_ws(c, wsb + tail); if (r) return r;
-  char* base = (char*)c->ws + ((wsb + 255) & ~(size_t)255);
-  // results [idx | scores | status] are contiguous on the device: ONE copy into pinned memory and one wait per search (three
-  // copies into pageable memory cost about 30 us of the 0.25 ms a cfg5 search takes)
-  long* d_q = (long*)base; long* d_idx = d_q + Q; float* d_sc = (float*)(d_idx + (size_t)Q * k); unsigned* d_status = (unsigned*)(d_sc + (size_t)Q * k);
-  const size_t res_bytes = sizeof(long) * (size_t)Q * k + sizeof(float) * (size_t)Q * k + sizeof(unsigned);
-  if (res_bytes > c->pin_bytes) {
-    if (c->pin) (void)hipHostFree(c->pin);
-    c->pin = nullptr; c->pin_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->pin, res_bytes * 2));
-    c->pin_bytes = res_bytes * 2;
-  }
-  // A handful of needles (the reference's five): their rows travel in the kernel arguments and the kernels write idx | scores | status
-  // straight into the pinned result block (host memory the device can address): no upload, no copy-out - launches, one wait.
-  if (cosine_topk_small_path(N, d, Q, k)) {
-    void* pin_dev = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(&pin_dev, c->pin, 0));
-    char* pd = static_cast<char*>(pin_dev);
-    long* p_idx = reinterpret_cast<long*>(pd); float* p_sc = reinterpret_cast<float*>(pd + sizeof(long) * (size_t)Q * k);
-    unsigned* p_status = reinterpret_cast<unsigned*>(pd + res_bytes - sizeof(unsigned));
-    if (!c->pin_done) { HIPCHK(c, hipHostMalloc((void**)&c->pin_done, 64)); memset(c->pin_done, 0, 64); }
-    void* done_dev = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(&done_dev, c->pin_done, 0));
-    if (++c->search_seq == 0u) c->search_seq = 1u;                                  // never 0: a fresh block reads 0
-    const unsigned seq = c->search_seq;
-    if (!c->search_state) {       // the sample launch's arrival counter and histogram: zero now, left zero by every search
-      HIPCHK(c, hipMalloc((void**)&c->search_state, sizeof(unsigned) * SEARCH_STATE_WORDS));
-      HIPCHK(c, hipMemsetAsync(c->search_state, 0, sizeof(unsigned) * SEARCH_STATE_WORDS, c->stream));
-    }
-    const int lr = launch_cosine_topk(emb, N, d, d_q, Q, k, p_idx, p_sc, accf, c->ws, c->stream, p_status, 0, qrows, c->search_state,
-                                      static_cast<unsigned*>(done_dev), seq);
-    if (lr < 0) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
-    LAUNCHCHK(c);
-    // The selection kernel publishes one completion word per needle behind its results (system-scope release): poll them instead of
-    // synchronising the stream (measured: 1-3 us of a 0.15 ms search).  Bounded: after 20 ms the stream is synchronised after all (a fault
-    // shows up there).
-    bool seen = false;
-    if (lr == 2) {
-      volatile unsigned* dw = c->pin_done;
-      const auto t0 = std::chrono::steady_clock::now();
-      for (unsigned spins = 0;; ++spins) {
-        bool all = true;
-        for (int q = 0; q < Q; ++q) if (dw[q] != seq) { all = false; break; }
-        if (all) { seen = true; break; }
-        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-        __builtin_ia32_pause();
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
-    const char* hres = (const char*)c->pin;
-    unsigned status; memcpy(&status, hres + res_bytes - sizeof(unsigned), sizeof status);
-    if (status == 0) {
-      memcpy(idx_out, hres, sizeof(long) * (size_t)Q * k);
-      if (score_out) memcpy(score_out, hres + sizeof(long) * (size_t)Q * k, sizeof(float) * (size_t)Q * k);
-      return GR_OK;
-    }
-    c->search_reruns++;       // a candidate list overflowed (adversarial row order): the unfiltered search below decides
-  }
-  HIPCHK(c, hipMemcpyAsync(d_q, qrows, sizeof(long) * Q, hipMemcpyHostToDevice, c->stream));
-  const bool small_failed = cosine_topk_small_path(N, d, Q, k);
-  for (int unfiltered = small_failed ? 1 : 0; unfiltered < 2; ++unfiltered) {
-    if (launch_cosine_topk(emb, N, d, d_q, Q, k, d_idx, d_sc, accf, c->ws, c->stream, d_status, unfiltered, qrows)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
-    LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(c->pin, d_idx, res_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const char* h = (const char*)c->pin;
-    unsigned status; memcpy(&status, h + res_bytes - sizeof(unsigned), sizeof status);
-    if (status == 0 || unfiltered) {
-      memcpy(idx_out, h, sizeof(long) * (size_t)Q * k);
-      if (score_out) memcpy(score_out, h + sizeof(long) * (size_t)Q * k, sizeof(float) * (size_t)Q * k);
-      break;
-    }
-    c->search_reruns++;       // 1: the sample-bound filter overflowed (adversarial row order): rerun on every key
-  }
-  return GR_OK;
-}
-extern "C" int gr_cosine_topk_host(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
-                                   int64_t* idx_out, float* score_out, int accf) {
-  if (!c || !emb || N <= 0 || d <= 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  float* dev = nullptr;
-  HIPCHK(c, hipMalloc((void**)&dev, sizeof(float) * (size_t)N * d));
-  hipError_t e = hipMemcpyAsync(dev, emb, sizeof(float) * (size_t)N * d, hipMemcpyHostToDevice, c->stream);
-  int r = e == hipSuccess ? gr_cosine_topk_dev(c, dev, N, d, qrows, Q, k, idx_out, score_out, accf) : fail(c, GR_ERR_HIP, "upload failed");
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(dev);
-  return r;
-}
-extern "C" int gr_cosine_similarity_host(gr_ctx* c, const float* a, const float* b, int d, float* out) {
-  if (!c || !a || !b || !out || d <= 0) return GR_ERR_INVALID;
-  std::vector<float> two((size_t)2 * d);
-  memcpy(two.data(), a, sizeof(float) * d); memcpy(two.data() + d, b, sizeof(float) * d);
-  int64_t q = 0, idx[2]; float sc[2];
-  int r = gr_cosine_topk_host(c, two.data(), 2, d, &q, 1, 2, idx, sc, 0); if (r) return r;
-  *out = idx[0] == 1 ? sc[0] : sc[1];   // score of row 1 against needle row 0
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ apply_r.lua:197-217 clustering of the recovered noise
-extern "C" int gr_kmeans_host(gr_ctx* c, const float* x, int64_t n, int d, int k, int niter, float* cent, float* totalcounts, int32_t* labels) {
-  if (!c || !x || !cent || n <= 0 || d <= 0 || k <= 0 || niter < 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t xb = sizeof(float) * (size_t)n * d, cb = sizeof(float) * (size_t)k * d, wsb = kmeans_workspace_bytes(n, d, k);
-  int r = ensure_ws(c, wsb + xb + cb + sizeof(float) * 3 * (size_t)k + sizeof(int) * (size_t)n + 1024); if (r) return r;
-  char* p = (char*)c->ws + ((wsb + 255) & ~(size_t)255);
-  float* dx = (float*)p; p += xb;
-  float* dc = (float*)p; p += cb;
-  float* dc2 = (float*)p; float* dcnt = dc2 + k; float* dtot = dcnt + k; p += sizeof(float) * 3 * (size_t)k;
-  int* dlab = (int*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-  HIPCHK(c, hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dc, cent, cb, hipMemcpyHostToDevice, c->stream));
-  if (launch_kmeans(dx, n, d, k, niter, dc, dc2, dcnt, dtot, dlab, c->ws, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "kmeans: k <= 32 and d <= 256 only");
-  LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(cent, dc, cb, hipMemcpyDeviceToHost, c->stream));
-  if (totalcounts) HIPCHK(c, hipMemcpyAsync(totalcounts, dtot, sizeof(float) * k, hipMemcpyDeviceToHost, c->stream));
-  if (labels && niter > 0) HIPCHK(c, hipMemcpyAsync(labels, dlab, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GR_OK;
-}
-extern "C" int gr_cosine_assign_host(gr_ctx* c, const float* x, int64_t n, int d, const float* cent, int k, int take_min, int32_t* labels, float* sims) {
-  if (!c || !x || !cent || !labels || !sims || n <= 0 || d <= 0 || k <= 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t xb = sizeof(float) * (size_t)n * d, cb = sizeof(float) * (size_t)k * d;
-  int r = ensure_ws(c, xb + cb + sizeof(float) * (size_t)k + (sizeof(int) + sizeof(float)) * (size_t)n + 1024); if (r) return r;
-  char* p = (char*)c->ws;
-  float* dx = (float*)p; p += xb;
-  float* dc = (float*)p; p += cb;
-  float* dw = (float*)p; p += sizeof(float) * (size_t)k;
-  p = (char*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-  int* dlab = (int*)p; p += sizeof(int) * (size_t)n;
-  float* dsim = (float*)p;
-  HIPCHK(c, hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dc, cent, cb, hipMemcpyHostToDevice, c->stream));
-  if (launch_cosine_assign(dx, n, d, dc, k, take_min, dw, dlab, dsim, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_assign: unsupported size");
-  LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(labels, dlab, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(sims, dsim, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ apply_r.lua:355-372 detectAnomalies' distance
-extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
-  if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t nb = sizeof(float) * (size_t)n * d;
-  int r = ensure_ws(c, 2 * nb + sizeof(double) * (size_t)n + 256); if (r) return r;
-  float* da = (float*)c->ws; float* db = da + (size_t)n * d; double* dout = (double*)((char*)c->ws + ((2 * nb + 255) & ~(size_t)255));
-  HIPCHK(c, hipMemcpyAsync(da, a, nb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db, b, nb, hipMemcpyHostToDevice, c->stream));
-  launch_l2_distance_rows(da, db, n, d, dout, c->stream); LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GR_OK;
-}
-
-extern "C" int gr_l2_distance_rows_dev(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
-  if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int r = ensure_ws(c, sizeof(double) * (size_t)n); if (r) return r;
-  double* dout = (double*)c->ws;
-  launch_l2_distance_rows(a, b, n, d, dout, c->stream); LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ the pictures of apply_r.lua / sample.lua (render.hip)
-extern "C" int gr_rows_mean_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, int n, float* out) {
-  if (!c) return GR_ERR_INVALID;
-  if (!table || !out || (n > 0 && !rows)) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: null pointer");
-  if (n_rows <= 0 || d <= 0 || n < 0) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: n_rows %lld and d %lld must be positive, n %d not negative", (long long)n_rows, (long long)d, n);
-  for (int j = 0; j < n; ++j)
-    if (rows[j] < 0 || rows[j] >= n_rows) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: rows[%d] = %lld is outside [0, %lld)", j, (long long)rows[j], (long long)n_rows);
-  HIPCHK(c, hipSetDevice(c->device));
-  int r = ensure_ws(c, sizeof(long) * (size_t)(n > 0 ? n : 1)); if (r) return r;
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(c->ws, rows, sizeof(long) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                      // the caller's array is its own again when the call returns
-  }
-  launch_rows_mean(table, (long)d, (const long*)c->ws, n, out, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-extern "C" int gr_image_grid_dev(gr_ctx* c, const float* const* src, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
-                                 const int64_t* rows, int n_tiles, int nrow, int padding, int margin, const float* bg, const uint8_t* inset,
-                                 const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid, uint8_t* u8) {
-  if (!c) return GR_ERR_INVALID;
-  if (slots != 1 && slots != 2) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: slots %d (1 or 2)", slots);
-  if (!src || !n_rows || !rows) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: null pointer");
-  for (int s = 0; s < slots; ++s)
-    if (!src[s] || n_rows[s] <= 0) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: table %d is null or has no rows", s);
-  if (!grid && !u8) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: both outputs are null");
-  if (from_space < -1 || from_space > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: unknown color space <from>: %d", from_space);
-  if ((channels != 1 && channels != 3) || (from_space >= 0 && channels != (from_space == GR_CS_Y ? 1 : 3)))
-    return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: %d channel(s) with from_space %d", channels, from_space);
-  if (h <= 0 || w <= 0 || n_tiles <= 0 || nrow <= 0 || padding < 0 || padding > 64 || margin < 0 || margin > 1)
-    return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: bad geometry (h %d, w %d, n_tiles %d, nrow %d, padding %d in [0, 64], margin %d in {0, 1})", h, w, n_tiles, nrow, padding, margin);
-  if (inset && !inset_rgb) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: inset flags without inset_rgb");
-  if (!auto_range && !(lo <= hi)) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: display range [%g, %g]", (double)lo, (double)hi);
-  GridGeom g{};
-  g.slots = slots; g.C = channels; g.Cout = from_space >= 0 ? 3 : channels; g.H = h; g.W = w; g.from = from_space;
-  g.n_tiles = n_tiles; g.xmaps = nrow < n_tiles ? nrow : n_tiles; g.padding = padding; g.margin = margin;
-  const int ymaps = (n_tiles + g.xmaps - 1) / g.xmaps;
-  const long TH = (long)h + 2 * margin, TW = (long)slots * w + 2 * margin, GH = (TH + padding) * ymaps, GW = (TW + padding) * g.xmaps;
-  if (GH > (1 << 20) || GW > (1 << 20) || GH * GW > (1L << 28)) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: a %ld x %ld grid is too large", GH, GW);
-  g.TH = (int)TH; g.TW = (int)TW; g.cellH = (int)TH + padding; g.cellW = (int)TW + padding; g.GH = (int)GH; g.GW = (int)GW;
-  std::vector<GridTile> tiles((size_t)n_tiles);
-  for (int t = 0; t < n_tiles; ++t) {
-    GridTile& tl = tiles[t];
-    tl.row[0] = tl.row[1] = -1;
-    for (int s = 0; s < slots; ++s) {
-      const int64_t r = rows[(size_t)t * slots + s];
-      if (r < -1 || r >= n_rows[s]) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: row %lld of tile %d, slot %d is outside [-1, %lld)", (long long)r, t, s, (long long)n_rows[s]);
-      tl.row[s] = (long)r;
-    }
-    for (int k = 0; k < 3; ++k) tl.bg[k] = bg ? bg[(size_t)t * 3 + k] : 0.f;
-    tl.inset = inset ? inset[t] != 0 : 0;
-  }
-  for (int k = 0; k < 3; ++k) g.inset_rgb[k] = inset_rgb ? inset_rgb[k] : 0.f;
-  g.fill = fill; g.lo = lo; g.hi = hi;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t tb = (sizeof(GridTile) * (size_t)n_tiles + 255) & ~(size_t)255;
-  int r = ensure_ws(c, tb + sizeof(float) * 2 * GRID_RANGE_BLOCKS); if (r) return r;
-  HIPCHK(c, hipMemcpyAsync(c->ws, tiles.data(), sizeof(GridTile) * (size_t)n_tiles, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));                        // `tiles` dies with this call
-  g.src[0] = src[0]; g.src[1] = slots == 2 ? src[1] : src[0]; g.tiles = (const GridTile*)c->ws;
-  launch_image_grid(g, auto_range ? (float*)((char*)c->ws + tb) : nullptr, grid, u8, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ the trainers' progress pictures (render.hip)
-extern "C" int gr_progress_grid_dev(gr_ctx* c, const float* table, int64_t n_rows, int channels, int h, int w, int from_space,
-                                    const int64_t* rows, int n_show, int grid_h, int grid_w, int epoch, float* grid, uint8_t* u8) {
-  if (!c) return GR_ERR_INVALID;
-  if (!table) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: the table is null");
-  if (!grid && !u8) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: both outputs are null");
-  if (from_space < -1 || from_space > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: unknown color space <from>: %d", from_space);
-  if ((channels != 1 && channels != 3) || (from_space >= 0 && channels != (from_space == GR_CS_Y ? 1 : 3)))
-    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: %d channel(s) with from_space %d", channels, from_space);
-  if (n_rows < 1 || h < 1 || w < 1 || grid_h < 1 || grid_w < 1 || n_show < 0)
-    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: bad geometry (n_rows %lld, h %d, w %d, grid %d x %d, n_show %d)", (long long)n_rows, h, w, grid_h, grid_w, n_show);
-  if (epoch < 0) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: epoch %d is negative", epoch);
-  const long GH = (long)grid_h * h + 7, GW = (long)grid_w * w;
-  if (GH > (1 << 20) || GW > (1 << 20) || GH * GW > (1L << 28)) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: a %ld x %ld grid is too large", GH, GW);
-  ProgressGeom g{};
-  for (int e = epoch; g.ndig == 0 || e > 0; e /= 10) g.dig[g.ndig++] = (unsigned char)(e % 10);
-  if (GW - 2 - 6L * g.ndig < 0)
-    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: the %d digit(s) of epoch %d do not fit a grid %ld pixels wide", g.ndig, epoch, GW);
-  const long cells = (long)grid_h * grid_w;
-  g.n_cells = (int)(n_show < cells ? n_show : cells);
-  if (g.n_cells > 0 && !rows) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: rows_host is null");
-  for (int t = 0; t < g.n_cells; ++t)
-    if (rows[t] < 0 || rows[t] >= n_rows) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: rows[%d] = %lld is outside [0, %lld)", t, (long long)rows[t], (long long)n_rows);
-  g.C = channels; g.Cout = from_space >= 0 ? 3 : channels; g.H = h; g.W = w; g.from = from_space;
-  g.grid_w = grid_w; g.GH = (int)GH; g.GW = (int)GW;
-  HIPCHK(c, hipSetDevice(c->device));
-  int r = ensure_ws(c, sizeof(long) * (size_t)(g.n_cells > 0 ? g.n_cells : 1)); if (r) return r;
-  if (g.n_cells > 0) {
-    HIPCHK(c, hipMemcpyAsync(c->ws, rows, sizeof(long) * (size_t)g.n_cells, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                      // the caller's array is its own again when the call returns
-  }
-  g.src = table; g.rows = (const long*)c->ws;
-  const bool vec = w % 4 == 0 && (uintptr_t)table % 16 == 0 && (uintptr_t)grid % 16 == 0 && (uintptr_t)u8 % 4 == 0;
-  launch_progress_grid(g, vec, grid, u8, c->stream); LAUNCHCHK(c);
-  return GR_OK;
-}
-
-// ------------------------------------------------------------------ sample.lua:130-148 findClosestNeighboursOf (neighbours.hip)
-extern "C" int gr_l2_nearest_dev(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
-                                 int64_t* idx_out, double* dist_out) {
-  if (!c) return GR_ERR_INVALID;
-  if (!table || !queries || !idx_out || !dist_out || n <= 0 || d < 1 || d > 65536 || Q < 1 || Q > 64 || k < 1 || k > n)
-    return fail(c, GR_ERR_INVALID, "gr_l2_nearest: bad arguments (n %lld, d %lld, q %d, k %d)", (long long)n, (long long)d, Q, k);
-  if (k > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: k > 128");
-  if (n >= 0xFFFFFFFFll) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: n >= 2^32 - 1");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t wsb = (l2_nearest_workspace_bytes(n, Q) + 255) & ~(size_t)255;
-  const size_t res = sizeof(long) * (size_t)Q * k + sizeof(double) * (size_t)Q * k + sizeof(unsigned) * (size_t)Q;
-  int r = ensure_ws(c, wsb + res + 256); if (r) return r;
-  long* d_idx = (long*)((char*)c->ws + wsb); double* d_dist = (double*)(d_idx + (size_t)Q * k); unsigned* d_status = (unsigned*)(d_dist + (size_t)Q * k);
-  std::vector<char> h(res);
-  for (int exact = l2_nearest_direct(n) ? 1 : 0; exact < 2; ++exact) {
-    if (launch_l2_nearest(table, n, (int)d, queries, Q, k, d_idx, d_dist, d_status, c->ws, exact, c->cu_count, c->stream))
-      return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: unsupported size");
-    LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(h.data(), d_idx, res, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    bool over = false;
-    for (int q = 0; q < Q && !exact; ++q) { unsigned st; memcpy(&st, h.data() + res - sizeof(unsigned) * (size_t)(Q - q), sizeof st); over = over || st != 0u; }
-    if (!over) break;             // (the exact path does not write the status words)
-  }
-  memcpy(idx_out, h.data(), sizeof(long) * (size_t)Q * k);
-  memcpy(dist_out, h.data() + sizeof(long) * (size_t)Q * k, sizeof(double) * (size_t)Q * k);
-  return GR_OK;
-}
-extern "C" int gr_l2_nearest_host(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
-                                  int64_t* idx_out, double* dist_out) {
-  if (!c) return GR_ERR_INVALID;
-  if (!table || !queries || !idx_out || !dist_out || n <= 0 || d < 1 || d > 65536 || Q < 1 || Q > 64 || k < 1 || k > n)
-    return fail(c, GR_ERR_INVALID, "gr_l2_nearest: bad arguments (n %lld, d %lld, q %d, k %d)", (long long)n, (long long)d, Q, k);
-  if (k > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: k > 128");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t tb = sizeof(float) * (size_t)n * d, qb = sizeof(float) * (size_t)Q * d;
-  float* dev = nullptr;
-  HIPCHK(c, hipMalloc((void**)&dev, tb + ((qb + 255) & ~(size_t)255) + 256));
-  float* dq = (float*)((char*)dev + ((tb + 255) & ~(size_t)255));
-  hipError_t e = hipMemcpyAsync(dev, table, tb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dq, queries, qb, hipMemcpyHostToDevice, c->stream);
-  int r = e == hipSuccess ? gr_l2_nearest_dev(c, dev, n, d, dq, Q, k, idx_out, dist_out) : fail(c, GR_ERR_HIP, "upload failed");
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(dev);
-  return r;
-}
-
-// ------------------------------------------------------------------ single-kernel entry points
-static int with_prepped(gr_ctx* c, const float* w, int cin, int cout, bool bwd, float** wt) {
-  const ConvWeightLayout L = bwd ? conv_weight_layout(cout, cin) : conv_weight_layout(cin, cout);
-  HIPCHK(c, hipMalloc((void**)wt, sizeof(float) * L.elems()));
-  launch_conv_weight_prep(w, *wt, cin, cout, bwd, c->stream);
-  LAUNCHCHK(c);
-  return GR_OK;
-}
-// f16x3: the weight maximum goes to c->amax[2]
-static int conv_split_once(gr_ctx* c, const float* w, int cin, int cout, bool bwd, void** ws) {
-  HIPCHK(c, hipMalloc(ws, conv_weight_split_bytes(cin, cout, bwd)));
-  launch_conv_weight_split(w, *ws, cin, cout, bwd, c->stream, c->conv_mode == 2 ? 2 : 3, c->amax + 2 * AMAX_WORDS);
-  LAUNCHCHK(c);
-  return GR_OK;
-}
-extern "C" int gr_conv3_forward_dev(gr_ctx* c, const float* in, const float* w, const float* bias, float* out, int B, int cin, int cout, int h, int wd, int up) {
-  if (!c || !in || !w || !out) return GR_ERR_INVALID;
-  if (c->conv_mode == 2 && up && conv_up2_supported(cin, cout, h, wd)) {
-    // the fused up-sampling layer as four 2x2 convolutions (the path a net takes for such a stage in f16x3 mode)
-    void* wup = nullptr;
-    HIPCHK(c, hipMalloc(&wup, conv_weight_up2_bytes(cin, cout)));
-    launch_conv_weight_up2_split(w, wup, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
-    launch_absmax(in, (long)B * cin * (h / 2) * (wd / 2), c->amax, c->stream);
-    launch_conv3x3_up2_f16x3(in, wup, bias, out, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr);
-    hipError_t e = hipGetLastError(); (void)hipStreamSynchronize(c->stream); (void)hipFree(wup);
-    return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e));
-  }
-  if (c->conv_mode >= 1 && cout > 4) {
-    void* ws = nullptr; int r = conv_split_once(c, w, cin, cout, false, &ws); if (r) return r;
-    if (c->conv_mode == 2) launch_absmax(in, (long)B * cin * (up ? (h / 2) * (wd / 2) : h * wd), c->amax, c->stream);
-    launch_conv3x3_split(in, ws, bias, out, B, cin, cout, h, wd, up != 0, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax, c->amax + 2 * AMAX_WORDS);
-    hipError_t e = hipGetLastError(); (void)hipStreamSynchronize(c->stream); (void)hipFree(ws);
-    return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e));
-  }
-  float* wt = nullptr; int r = with_prepped(c, w, cin, cout, false, &wt); if (r) return r;
-  launch_conv3x3(in, wt, bias, out, B, cin, cout, h, wd, up != 0, c->stream, w);
-  hipError_t e = hipGetLastError(); (void)hipStreamSynchronize(c->stream); (void)hipFree(wt);
-  return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e));
-}
-extern "C" int gr_conv3_backward_data_dev(gr_ctx* c, const float* gout, const float* w, float* gin, int B, int cin, int cout, int h, int wd) {
-  if (!c || !gout || !w || !gin) return GR_ERR_INVALID;
-  if (c->conv_mode >= 1 && cin > 4) {
-    void* ws = nullptr; int r = conv_split_once(c, w, cin, cout, true, &ws); if (r) return r;
-    if (c->conv_mode == 2) launch_absmax(gout, (long)B * cout * h * wd, c->amax + AMAX_WORDS, c->stream);
-    launch_conv3x3_split(gout, ws, nullptr, gin, B, cout, cin, h, wd, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
-    hipError_t e = hipGetLastError(); (void)hipStreamSynchronize(c->stream); (void)hipFree(ws);
-    return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e));
-  }
-  float* wt = nullptr; int r = with_prepped(c, w, cin, cout, true, &wt); if (r) return r;
-  launch_conv3x3(gout, wt, nullptr, gin, B, cout, cin, h, wd, false, c->stream);
-  hipError_t e = hipGetLastError(); (void)hipStreamSynchronize(c->stream); (void)hipFree(wt);
-  return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e));
-}
-extern "C" int gr_conv3_backward_weight_dev(gr_ctx* c, const float* in, const float* gout, float* gw, int B, int cin, int cout, int h, int wd) {
-  if (!c || !in || !gout || !gw) return GR_ERR_INVALID;
-  int r = ensure_ws(c, conv_wgrad_workspace_bytes(B, cin, cout, h, wd, c->conv_mode)); if (r) return r;
-  if (c->conv_mode == 2 && conv_wgrad_is_split(2, cin, wd)) {
-    launch_absmax(in, (long)B * cin * h * wd, c->amax, c->stream);
-    launch_absmax(gout, (long)B * cout * h * wd, c->amax + AMAX_WORDS, c->stream);
-  }
-  launch_conv3x3_wgrad(in, gout, gw, c->ws, B, cin, cout, h, wd, c->stream, c->conv_mode, c->amax, c->amax + AMAX_WORDS);
-  LAUNCHCHK(c);
-  return GR_OK;
-}
-// Sustained rate of the bare f16x3 inner loop (mfmaloop.hip) on this device: `launches` back-to-back launches (>= 0.3 s of them
-// before the timed ones so that the clock settles), HIP events on the ctx stream.  shape 0 = v_mfma_f32_32x32x16_f16 (what the
-// convolution kernels issue), 1 = v_mfma_f32_16x16x32_f16.  tflops_out: fp32-accurate TFLOP/s (f16 MFMA rate / 3 products), the
-// figure comparable with the 833 TFLOP/s ceiling bench.py prices the f16x3 kernels against.
-extern "C" int gr_bench_mfma_loop(gr_ctx* c, int shape, int launches, float* tflops_out) {
-  if (!c || !tflops_out || shape < 0 || shape > 1 || launches < 1) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int r = ensure_ws(c, mfma_loop_workspace_bytes()); if (r) return r;
-  launch_mfma_loop_fill(c->ws, c->stream);
-  const int iters = 200;
-  for (int i = 0; i < 300; ++i) launch_mfma_loop(shape, c->ws, iters, c->stream);     // ~0.35 s of warm-up under load
-  LAUNCHCHK(c);
-  hipEvent_t e0, e1; HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  for (int i = 0; i < launches; ++i) launch_mfma_loop(shape, c->ws, iters, c->stream);
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipEventSynchronize(e1));
-  float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *tflops_out = (float)(mfma_loop_flops(iters) * launches / (ms * 1e-3) / 1e12 / 3.0);
-  return GR_OK;
-}
-extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, int h, int wd, int iters, float* avg_ms) {
-  if (!c || iters < 1 || !avg_ms) return GR_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t nin = (size_t)B * cin * h * wd, nout = (size_t)B * cout * h * wd, nw = (size_t)cin * cout * 9;
-  float *x = nullptr, *y = nullptr, *w = nullptr, *wt = nullptr, *gw = nullptr;
-  HIPCHK(c, hipMalloc((void**)&x, sizeof(float) * nin)); HIPCHK(c, hipMalloc((void**)&y, sizeof(float) * nout));
-  HIPCHK(c, hipMalloc((void**)&w, sizeof(float) * nw)); HIPCHK(c, hipMalloc((void**)&gw, sizeof(float) * nw));
-  launch_fill_normal(x, (long)nin, 11, c->stream); launch_fill_normal(y, (long)nout, 12, c->stream); launch_fill_normal(w, (long)nw, 13, c->stream);
-  (void)hipMemsetAsync(gw, 0, sizeof(float) * nw, c->stream);
-  int r = with_prepped(c, w, cin, cout, which == 1, &wt); if (r) return r;
-  void* wsp = nullptr;
-  const bool split = c->conv_mode >= 1 && which != 2 && (which == 0 ? cout > 4 : cin > 4);
-  const int nterm = c->conv_mode == 2 ? 2 : 3;
-  if (split) { r = conv_split_once(c, w, cin, cout, which == 1, &wsp); if (r) return r; }
-  r = ensure_ws(c, conv_wgrad_workspace_bytes(B, cin, cout, h, wd, c->conv_mode)); if (r) return r;
-  // f16x3 scales: taken once outside the timed loop (in a net the producing kernel tracks them)
-  if (c->conv_mode == 2) { launch_absmax(x, (long)nin, c->amax, c->stream); launch_absmax(y, (long)nout, c->amax + AMAX_WORDS, c->stream); }
-  void* wup = nullptr;
-  if (which == 3) {      // fused up-sampling layer: x is the source plane [B, cin, h/2, wd/2] (a quarter of the buffer), y the output
-    if (c->conv_mode != 2 || !conv_up2_supported(cin, cout, h, wd)) return fail(c, GR_ERR_UNSUPPORTED, "up2 bench needs f16x3 mode and a supported shape");
-    HIPCHK(c, hipMalloc(&wup, conv_weight_up2_bytes(cin, cout)));
-    launch_conv_weight_up2_split(w, wup, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
-  }
-  void* xp16 = nullptr; double* statp = nullptr;
-  if (which == 4 || which == 5) {   // operand-ready forward (5: with the BatchNorm statistics epilogue): x converted once outside the loop
-    if (c->conv_mode != 2 || !conv_p16_supported(B, cin, cout, h, wd)) return fail(c, GR_ERR_UNSUPPORTED, "p16 bench needs f16x3 mode and a supported shape");
-    HIPCHK(c, hipMalloc(&xp16, sizeof(float) * nin));
-    HIPCHK(c, hipMalloc((void**)&statp, sizeof(double) * 2 * cout * conv_stat_tiles_max(B, h, wd)));
-    launch_to_p16(x, xp16, B, cin, h * wd, c->amax, c->stream);
-    r = conv_split_once(c, w, cin, cout, false, &wsp); if (r) return r;
-  }
-  auto run = [&]() {
-    if (which == 4 || which == 5) { int st = 0; launch_conv3x3_p16(xp16, wsp, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr, which == 5 ? statp : nullptr, which == 5 ? &st : nullptr); return; }
-    if (which == 3) { launch_conv3x3_up2_f16x3(x, wup, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr); return; }
-    if (split && which == 0) launch_conv3x3_split(x, wsp, nullptr, y, B, cin, cout, h, wd, false, c->stream, nullptr, nterm, c->amax, c->amax + 2 * AMAX_WORDS);
-    else if (split && which == 1) launch_conv3x3_split(y, wsp, nullptr, x, B, cout, cin, h, wd, false, c->stream, nullptr, nterm, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
-    else if (which == 0) launch_conv3x3(x, wt, nullptr, y, B, cin, cout, h, wd, false, c->stream, w);
-    else if (which == 1) launch_conv3x3(y, wt, nullptr, x, B, cout, cin, h, wd, false, c->stream);
-    else launch_conv3x3_wgrad(x, y, gw, c->ws, B, cin, cout, h, wd, c->stream, c->conv_mode, c->amax, c->amax + AMAX_WORDS);
-  };
-  for (int i = 0; i < 3; ++i) run();
-  hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, c->stream);
-  for (int i = 0; i < iters; ++i) run();
-  (void)hipEventRecord(e1, c->stream);
-  HIPCHK(c, hipEventSynchronize(e1));
-  float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-  *avg_ms = ms / iters;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(x); (void)hipFree(y); (void)hipFree(w); (void)hipFree(wt); (void)hipFree(gw); (void)hipFree(wsp); (void)hipFree(wup); (void)hipFree(xp16); (void)hipFree(statp);
-  LAUNCHCHK(c);
   return GR_OK;
 }

@@ -1,0 +1,598 @@
+// ops.hip — the context-level operators of the C ABI (include/ganrev.h): entry points that take a gr_ctx and no gr_net.  The criteria,
+// the nn.Concat helpers, colour spaces, image.scale and the dataset loader, the searches, k-means, the picture grids and the single-kernel
+// convolution calls.  Host code only: the kernels are in the files kernels.h names.
+#include "ctx.h"
+#include <atomic>
+#include <chrono>
+#include <cstring>
+
+using namespace gr;
+
+#define TRY(call) do { int r_ = (call); if (r_) return r_; } while (0)
+
+// ------------------------------------------------------------------ staging and temporaries
+// One call's share of the context workspace: reserve typed regions (each starts on a 256-byte boundary), grow() once, then ask for
+// pointers.  A kernel that takes c->ws itself as its scratch gets the first region.  Copies go on c->stream; finish() is the one wait.
+template <class T> struct Region { size_t off, count; };
+struct Staging {
+  gr_ctx* c; size_t bytes = 0;
+  explicit Staging(gr_ctx* ctx) : c(ctx) {}
+  template <class T> Region<T> reserve(size_t count) { Region<T> r{bytes, count}; bytes += (sizeof(T) * count + 255) & ~(size_t)255; return r; }
+  int grow() { HIPCHK(c, hipSetDevice(c->device)); return ensure_ws(c, bytes); }
+  template <class T> T* ptr(Region<T> r) const { return reinterpret_cast<T*>(static_cast<char*>(c->ws) + r.off); }
+  template <class T> int upload(Region<T> r, const T* host) { HIPCHK(c, hipMemcpyAsync(ptr(r), host, sizeof(T) * r.count, hipMemcpyHostToDevice, c->stream)); return GR_OK; }
+  template <class T> int download(T* host, Region<T> r) { HIPCHK(c, hipMemcpyAsync(host, ptr(r), sizeof(T) * r.count, hipMemcpyDeviceToHost, c->stream)); return GR_OK; }
+  int finish() { HIPCHK(c, hipStreamSynchronize(c->stream)); return GR_OK; }
+  // a host array that is the caller's own again (or dies) when the call returns
+  template <class T> int upload_now(Region<T> r, const T* host) { TRY(upload(r, host)); return finish(); }
+};
+// A hipMalloc temporary of one call.  It goes on every exit path, once the work enqueued on the context's stream has finished.
+struct DevTemp {
+  gr_ctx* c; void* p = nullptr;
+  explicit DevTemp(gr_ctx* ctx) : c(ctx) {}
+  DevTemp(const DevTemp&) = delete;        // (one owner)
+  ~DevTemp() { if (p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); } }
+  int alloc(size_t nbytes) { HIPCHK(c, hipMalloc(&p, nbytes)); return GR_OK; }
+  template <class T> T* as() const { return static_cast<T*>(p); }
+};
+struct EventTemp {     // a HIP event of one call (a failed create shows in the first call that takes the event)
+  hipEvent_t e = nullptr;
+  EventTemp() { (void)hipEventCreate(&e); }
+  EventTemp(const EventTemp&) = delete;
+  ~EventTemp() { if (e) (void)hipEventDestroy(e); }
+};
+
+// a criterion on host tensors: launch(x, t, loss_dev, grad) runs on staged copies
+template <class Launch> static int criterion_host(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss, float* grad, Launch launch) {
+  Staging s(c);
+  auto dx = s.reserve<float>(n), dt = s.reserve<float>(n), dg = s.reserve<float>(n);
+  TRY(s.grow()); TRY(s.upload(dx, x)); TRY(s.upload(dt, t));
+  launch(s.ptr(dx), s.ptr(dt), c->d_loss, grad ? s.ptr(dg) : nullptr); LAUNCHCHK(c);
+  if (grad) TRY(s.download(grad, dg));
+  HIPCHK(c, hipMemcpyAsync(c->h_loss, c->d_loss, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  TRY(s.finish());
+  if (loss) *loss = *c->h_loss;
+  return GR_OK;
+}
+// one host tensor in, one out: launch(in, out) runs on staged copies (gr_colorspace_host, gr_image_scale_host)
+template <class Launch> static int map_host(gr_ctx* c, const float* in, size_t nin, float* out, size_t nout, Launch launch) {
+  Staging s(c);
+  auto din = s.reserve<float>(nin), dout = s.reserve<float>(nout);
+  TRY(s.grow()); TRY(s.upload(din, in));
+  launch(s.ptr(din), s.ptr(dout)); LAUNCHCHK(c);
+  TRY(s.download(out, dout));
+  return s.finish();
+}
+
+// ------------------------------------------------------------------ criterion
+extern "C" int gr_mse_dev(gr_ctx* c, const float* x, const float* t, int64_t n, int64_t ng, double* loss_dev, float* grad) {
+  if (!c || !x || !t || n <= 0 || ng <= 0) return GR_ERR_INVALID;
+  launch_mse(x, t, n, ng, loss_dev, grad, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_mse_host(gr_ctx* c, const float* x, const float* t, int64_t n, int64_t ng, double* loss, float* grad) {
+  if (!c || !x || !t || n <= 0 || ng <= 0) return GR_ERR_INVALID;
+  return criterion_host(c, x, t, n, loss, grad, [&](const float* dx, const float* dt, double* dl, float* dg) { launch_mse(dx, dt, n, ng, dl, dg, c->stream); });
+}
+// nn.BCECriterion (sizeAverage): train.lua:173's CRITERION, used by adversarial.lua (the GAN step's loss; first pieces of SURVEY.md 8f rank 4)
+extern "C" int gr_bce_dev(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss_dev, float* grad) {
+  if (!c || !x || !t || n <= 0) return GR_ERR_INVALID;
+  launch_bce(x, t, n, loss_dev, grad, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_bce_host(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss, float* grad) {
+  if (!c || !x || !t || n <= 0) return GR_ERR_INVALID;
+  return criterion_host(c, x, t, n, loss, grad, [&](const float* dx, const float* dt, double* dl, float* dg) { launch_bce(dx, dt, n, dl, dg, c->stream); });
+}
+
+// ------------------------------------------------------------------ nn.Concat on device-resident tensors (models.lua:293-321)
+// The container stays on the host (it is a module that calls its children, not an operator); these two move its data
+// without leaving the GPU: rows of one matrix into a column range of another (join the branch outputs / slice gradOutput),
+// and the sum of the branches' gradInputs.
+extern "C" int gr_copy2d_dev(gr_ctx* c, float* dst, int64_t dst_pitch, const float* src, int64_t src_pitch, int64_t rows, int64_t cols) {
+  if (!c || !dst || !src || rows <= 0 || cols <= 0 || dst_pitch < cols || src_pitch < cols) return GR_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpy2DAsync(dst, sizeof(float) * (size_t)dst_pitch, src, sizeof(float) * (size_t)src_pitch, sizeof(float) * (size_t)cols, (size_t)rows,
+                             hipMemcpyDeviceToDevice, c->stream));
+  return GR_OK;
+}
+extern "C" int gr_add_dev(gr_ctx* c, float* y, const float* x, int64_t n) {
+  if (!c || !y || !x || n <= 0) return GR_ERR_INVALID;
+  launch_add_inplace(y, x, (long)n, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ NN_UTILS.switchColorSpace (utils/nn_utils.lua:133-246)
+static int colorspace_check(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, const float* out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!in || !out) return fail(c, GR_ERR_INVALID, "gr_colorspace: null pointer");
+  if (from < GR_CS_RGB || from > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_colorspace: unknown color space <from>: %d", from);
+  if (to < GR_CS_RGB || to > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_colorspace: unknown color space <to>: %d", to);
+  if (batch <= 0 || h <= 0 || w <= 0) return fail(c, GR_ERR_INVALID, "gr_colorspace: batch %lld, h %d, w %d must be positive", (long long)batch, h, w);
+  if (in == out && (from == GR_CS_Y) != (to == GR_CS_Y)) return fail(c, GR_ERR_INVALID, "gr_colorspace: in place needs equal plane counts (from %d, to %d)", from, to);
+  return GR_OK;
+}
+extern "C" int gr_colorspace_dev(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, float* out) {
+  int r = colorspace_check(c, in, from, to, batch, h, w, out); if (r) return r;
+  const long hw = (long)h * w;
+  if (from == GR_CS_RGB && to == GR_CS_RGB) {
+    if (in != out) HIPCHK(c, hipMemcpyAsync(out, in, sizeof(float) * 3 * (size_t)batch * hw, hipMemcpyDeviceToDevice, c->stream));
+    return GR_OK;
+  }
+  launch_colorspace(in, from, to, (long)batch, hw, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_colorspace_host(gr_ctx* c, const float* in, int from, int to, int64_t batch, int h, int w, float* out) {
+  int r = colorspace_check(c, in, from, to, batch, h, w, out); if (r) return r;
+  const size_t hw = (size_t)h * w, nin = (from == GR_CS_Y ? 1 : 3) * (size_t)batch * hw, nout = (to == GR_CS_Y ? 1 : 3) * (size_t)batch * hw;
+  if (from == GR_CS_RGB && to == GR_CS_RGB) {
+    if (in != out) memmove(out, in, sizeof(float) * nin);
+    return GR_OK;
+  }
+  return map_host(c, in, nin, out, nout, [&](const float* din, float* dout) { launch_colorspace(din, from, to, (long)batch, (long)hw, dout, c->stream); });
+}
+
+// ------------------------------------------------------------------ dataset.lua:111-116,149-153: image.scale and the loader's fused path (dataset.hip)
+// GR_SCALE_MAX_ELEMS bounds both tensors of a call: the kernels index with 64-bit integers, the bound keeps every product of the geometry far inside them
+static const int64_t GR_SCALE_MAX_ELEMS = (int64_t)1 << 40;
+static int scale_check(gr_ctx* c, const char* who, const void* in, const void* out, int64_t n, int64_t per_in, int sh, int sw, int dh, int dw, int64_t per_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!in || !out) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);
+  if (n < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1) return fail(c, GR_ERR_INVALID, "%s: n %lld, source %d x %d, target %d x %d must be positive", who, (long long)n, sh, sw, dh, dw);
+  if (sh > SCALE_MAX_LEN || sw > SCALE_MAX_LEN || dh > SCALE_MAX_LEN || dw > SCALE_MAX_LEN)
+    return fail(c, GR_ERR_INVALID, "%s: source %d x %d, target %d x %d: a side is too large (at most %d)", who, sh, sw, dh, dw, SCALE_MAX_LEN);
+  const int64_t ein = per_in * sh * sw, eout = per_out * dh * dw;              // per_* <= 2^31, a side <= 2^15: below 2^61
+  if (n > GR_SCALE_MAX_ELEMS / ein || n > GR_SCALE_MAX_ELEMS / eout) return fail(c, GR_ERR_INVALID, "%s: %lld images are too large a batch (at most 2^40 elements per tensor)", who, (long long)n);
+  return GR_OK;
+}
+extern "C" int gr_image_scale_dev(gr_ctx* c, const float* in, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out) {
+  if (c && planes < 1) return fail(c, GR_ERR_INVALID, "gr_image_scale: planes %d must be positive", planes);
+  int r = scale_check(c, "gr_image_scale", in, out, n, planes, sh, sw, dh, dw, planes); if (r) return r;
+  if (in == out) return fail(c, GR_ERR_INVALID, "gr_image_scale: in place is not supported");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_image_scale(in, (long)n * planes, scale_axis(sh, dh), scale_axis(sw, dw), out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_image_scale_host(gr_ctx* c, const float* in, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out) {
+  if (c && planes < 1) return fail(c, GR_ERR_INVALID, "gr_image_scale: planes %d must be positive", planes);
+  int r = scale_check(c, "gr_image_scale", in, out, n, planes, sh, sw, dh, dw, planes); if (r) return r;
+  if (in == out) return fail(c, GR_ERR_INVALID, "gr_image_scale: in place is not supported");
+  const size_t nin = (size_t)n * planes * sh * sw, nout = (size_t)n * planes * dh * dw;
+  return map_host(c, in, nin, out, nout, [&](const float* din, float* dout) { launch_image_scale(din, (long)n * planes, scale_axis(sh, dh), scale_axis(sw, dw), dout, c->stream); });
+}
+extern "C" int gr_dataset_images_dev(gr_ctx* c, const uint8_t* in, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize, float* out) {
+  if (c && sc != 1 && sc != 3 && sc != 4) return fail(c, GR_ERR_INVALID, "gr_dataset_images: %d source channels (1, 3 or 4)", sc);
+  if (c && (to_space < GR_CS_RGB || to_space > GR_CS_HSL)) return fail(c, GR_ERR_INVALID, "gr_dataset_images: unknown color space <to>: %d", to_space);
+  int r = scale_check(c, "gr_dataset_images", in, out, n, sc, sh, sw, dh, dw, to_space == GR_CS_Y ? 1 : 3); if (r) return r;
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_dataset_images(in, (long)n, sc, scale_axis(sh, dh), scale_axis(sw, dw), to_space, normalize != 0, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ search
+extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
+                                  int64_t* idx_out, float* score_out, int accf) {
+  if (!c || !emb || !qrows || !idx_out || N <= 0 || d <= 0 || Q <= 0 || k <= 0) return GR_ERR_INVALID;
+  if (k > N) k = (int)N;
+  for (int q = 0; q < Q; ++q) if (qrows[q] < 0 || qrows[q] >= N) return fail(c, GR_ERR_INVALID, "query row %lld out of range", (long long)qrows[q]);
+  if (k > 1024) return fail(c, GR_ERR_UNSUPPORTED, "k > 1024");
+  Staging s(c);
+  s.reserve<char>(cosine_topk_workspace_bytes(N, d, Q, k));          // launch_cosine_topk takes c->ws itself: the first region
+  auto tail = s.reserve<char>(sizeof(long) * (size_t)Q * (k + 1) + sizeof(float) * (size_t)Q * k + sizeof(unsigned));
+  TRY(s.grow());
+  char* base = s.ptr(tail);
+  // results [idx | scores | status] are contiguous on the device: ONE copy into pinned memory and one wait per search (three
+  // copies into pageable memory cost about 30 us of the 0.25 ms a cfg5 search takes)
+  long* d_q = (long*)base; long* d_idx = d_q + Q; float* d_sc = (float*)(d_idx + (size_t)Q * k); unsigned* d_status = (unsigned*)(d_sc + (size_t)Q * k);
+  const size_t res_bytes = sizeof(long) * (size_t)Q * k + sizeof(float) * (size_t)Q * k + sizeof(unsigned);
+  if (res_bytes > c->pin_bytes) {
+    if (c->pin) (void)hipHostFree(c->pin);
+    c->pin = nullptr; c->pin_bytes = 0;
+    HIPCHK(c, hipHostMalloc(&c->pin, res_bytes * 2));
+    c->pin_bytes = res_bytes * 2;
+  }
+  // A handful of needles (the reference's five): their rows travel in the kernel arguments and the kernels write idx | scores | status
+  // straight into the pinned result block (host memory the device can address): no upload, no copy-out - launches, one wait.
+  if (cosine_topk_small_path(N, d, Q, k)) {
+    void* pin_dev = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&pin_dev, c->pin, 0));
+    char* pd = static_cast<char*>(pin_dev);
+    long* p_idx = reinterpret_cast<long*>(pd); float* p_sc = reinterpret_cast<float*>(pd + sizeof(long) * (size_t)Q * k);
+    unsigned* p_status = reinterpret_cast<unsigned*>(pd + res_bytes - sizeof(unsigned));
+    if (!c->pin_done) { HIPCHK(c, hipHostMalloc((void**)&c->pin_done, 64)); memset(c->pin_done, 0, 64); }
+    void* done_dev = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&done_dev, c->pin_done, 0));
+    if (++c->search_seq == 0u) c->search_seq = 1u;                                  // never 0: a fresh block reads 0
+    const unsigned seq = c->search_seq;
+    if (!c->search_state) {       // the sample launch's arrival counter and histogram: zero now, left zero by every search
+      HIPCHK(c, hipMalloc((void**)&c->search_state, sizeof(unsigned) * SEARCH_STATE_WORDS));
+      HIPCHK(c, hipMemsetAsync(c->search_state, 0, sizeof(unsigned) * SEARCH_STATE_WORDS, c->stream));
+    }
+    const int lr = launch_cosine_topk(emb, N, d, d_q, Q, k, p_idx, p_sc, accf, c->ws, c->stream, p_status, 0, qrows, c->search_state,
+                                      static_cast<unsigned*>(done_dev), seq);
+    if (lr < 0) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
+    LAUNCHCHK(c);
+    // The selection kernel publishes one completion word per needle behind its results (system-scope release): poll them instead of
+    // synchronising the stream (measured: 1-3 us of a 0.15 ms search).  Bounded: after 20 ms the stream is synchronised after all (a fault
+    // shows up there).
+    bool seen = false;
+    if (lr == 2) {
+      volatile unsigned* dw = c->pin_done;
+      const auto t0 = std::chrono::steady_clock::now();
+      for (unsigned spins = 0;; ++spins) {
+        bool all = true;
+        for (int q = 0; q < Q; ++q) if (dw[q] != seq) { all = false; break; }
+        if (all) { seen = true; break; }
+        if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
+        __builtin_ia32_pause();
+      }
+      std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    if (!seen) HIPCHK(c, hipStreamSynchronize(c->stream));
+    const char* hres = (const char*)c->pin;
+    unsigned status; memcpy(&status, hres + res_bytes - sizeof(unsigned), sizeof status);
+    if (status == 0) {
+      memcpy(idx_out, hres, sizeof(long) * (size_t)Q * k);
+      if (score_out) memcpy(score_out, hres + sizeof(long) * (size_t)Q * k, sizeof(float) * (size_t)Q * k);
+      return GR_OK;
+    }
+    c->search_reruns++;       // a candidate list overflowed (adversarial row order): the unfiltered search below decides
+  }
+  HIPCHK(c, hipMemcpyAsync(d_q, qrows, sizeof(long) * Q, hipMemcpyHostToDevice, c->stream));
+  const bool small_failed = cosine_topk_small_path(N, d, Q, k);
+  for (int unfiltered = small_failed ? 1 : 0; unfiltered < 2; ++unfiltered) {
+    if (launch_cosine_topk(emb, N, d, d_q, Q, k, d_idx, d_sc, accf, c->ws, c->stream, d_status, unfiltered, qrows)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
+    LAUNCHCHK(c);
+    HIPCHK(c, hipMemcpyAsync(c->pin, d_idx, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const char* h = (const char*)c->pin;
+    unsigned status; memcpy(&status, h + res_bytes - sizeof(unsigned), sizeof status);
+    if (status == 0 || unfiltered) {
+      memcpy(idx_out, h, sizeof(long) * (size_t)Q * k);
+      if (score_out) memcpy(score_out, h + sizeof(long) * (size_t)Q * k, sizeof(float) * (size_t)Q * k);
+      break;
+    }
+    c->search_reruns++;       // 1: the sample-bound filter overflowed (adversarial row order): rerun on every key
+  }
+  return GR_OK;
+}
+extern "C" int gr_cosine_topk_host(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
+                                   int64_t* idx_out, float* score_out, int accf) {
+  if (!c || !emb || N <= 0 || d <= 0) return GR_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  DevTemp dev(c);
+  TRY(dev.alloc(sizeof(float) * (size_t)N * d));
+  if (hipMemcpyAsync(dev.p, emb, sizeof(float) * (size_t)N * d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, GR_ERR_HIP, "upload failed");
+  return gr_cosine_topk_dev(c, dev.as<float>(), N, d, qrows, Q, k, idx_out, score_out, accf);
+}
+extern "C" int gr_cosine_similarity_host(gr_ctx* c, const float* a, const float* b, int d, float* out) {
+  if (!c || !a || !b || !out || d <= 0) return GR_ERR_INVALID;
+  std::vector<float> two((size_t)2 * d);
+  memcpy(two.data(), a, sizeof(float) * d); memcpy(two.data() + d, b, sizeof(float) * d);
+  int64_t q = 0, idx[2]; float sc[2];
+  int r = gr_cosine_topk_host(c, two.data(), 2, d, &q, 1, 2, idx, sc, 0); if (r) return r;
+  *out = idx[0] == 1 ? sc[0] : sc[1];   // score of row 1 against needle row 0
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ apply_r.lua:197-217 clustering of the recovered noise
+extern "C" int gr_kmeans_host(gr_ctx* c, const float* x, int64_t n, int d, int k, int niter, float* cent, float* totalcounts, int32_t* labels) {
+  if (!c || !x || !cent || n <= 0 || d <= 0 || k <= 0 || niter < 0) return GR_ERR_INVALID;
+  Staging s(c);
+  auto scratch = s.reserve<char>(kmeans_workspace_bytes(n, d, k));   // launch_kmeans takes c->ws itself: the first region
+  auto dx = s.reserve<float>((size_t)n * d), dc = s.reserve<float>((size_t)k * d), dc2 = s.reserve<float>(k), dcnt = s.reserve<float>(k), dtot = s.reserve<float>(k);
+  auto dlab = s.reserve<int>(n);
+  TRY(s.grow()); TRY(s.upload(dx, x)); TRY(s.upload(dc, cent));
+  if (launch_kmeans(s.ptr(dx), n, d, k, niter, s.ptr(dc), s.ptr(dc2), s.ptr(dcnt), s.ptr(dtot), s.ptr(dlab), s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "kmeans: k <= 32 and d <= 256 only");
+  LAUNCHCHK(c);
+  TRY(s.download(cent, dc));
+  if (totalcounts) TRY(s.download(totalcounts, dtot));
+  if (labels && niter > 0) TRY(s.download(labels, dlab));
+  return s.finish();
+}
+extern "C" int gr_cosine_assign_host(gr_ctx* c, const float* x, int64_t n, int d, const float* cent, int k, int take_min, int32_t* labels, float* sims) {
+  if (!c || !x || !cent || !labels || !sims || n <= 0 || d <= 0 || k <= 0) return GR_ERR_INVALID;
+  Staging s(c);
+  auto dx = s.reserve<float>((size_t)n * d), dc = s.reserve<float>((size_t)k * d), dw = s.reserve<float>(k), dsim = s.reserve<float>(n);
+  auto dlab = s.reserve<int>(n);
+  TRY(s.grow()); TRY(s.upload(dx, x)); TRY(s.upload(dc, cent));
+  if (launch_cosine_assign(s.ptr(dx), n, d, s.ptr(dc), k, take_min, s.ptr(dw), s.ptr(dlab), s.ptr(dsim), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_assign: unsupported size");
+  LAUNCHCHK(c);
+  TRY(s.download(labels, dlab)); TRY(s.download(sims, dsim));
+  return s.finish();
+}
+
+// ------------------------------------------------------------------ apply_r.lua:355-372 detectAnomalies' distance
+extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
+  if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;
+  Staging s(c);
+  auto da = s.reserve<float>((size_t)n * d), db = s.reserve<float>((size_t)n * d);
+  auto dout = s.reserve<double>(n);
+  TRY(s.grow()); TRY(s.upload(da, a)); TRY(s.upload(db, b));
+  launch_l2_distance_rows(s.ptr(da), s.ptr(db), n, d, s.ptr(dout), c->stream); LAUNCHCHK(c);
+  TRY(s.download(out, dout));
+  return s.finish();
+}
+extern "C" int gr_l2_distance_rows_dev(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
+  if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;
+  Staging s(c);
+  auto dout = s.reserve<double>(n);
+  TRY(s.grow());
+  launch_l2_distance_rows(a, b, n, d, s.ptr(dout), c->stream); LAUNCHCHK(c);
+  TRY(s.download(out, dout));
+  return s.finish();
+}
+
+// ------------------------------------------------------------------ the pictures of apply_r.lua / sample.lua (render.hip)
+extern "C" int gr_rows_mean_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, int n, float* out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table || !out || (n > 0 && !rows)) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: null pointer");
+  if (n_rows <= 0 || d <= 0 || n < 0) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: n_rows %lld and d %lld must be positive, n %d not negative", (long long)n_rows, (long long)d, n);
+  for (int j = 0; j < n; ++j)
+    if (rows[j] < 0 || rows[j] >= n_rows) return fail(c, GR_ERR_INVALID, "gr_rows_mean_dev: rows[%d] = %lld is outside [0, %lld)", j, (long long)rows[j], (long long)n_rows);
+  Staging s(c);
+  auto drows = s.reserve<long>(n > 0 ? n : 1);
+  TRY(s.grow());
+  if (n > 0) TRY(s.upload_now(drows, rows));
+  launch_rows_mean(table, (long)d, s.ptr(drows), n, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+// what both picture grids ask of their outputs and source, and of the size of the picture
+static int grid_source_check(gr_ctx* c, const char* who, const void* grid, const void* u8, int channels, int from_space) {
+  if (!grid && !u8) return fail(c, GR_ERR_INVALID, "%s: both outputs are null", who);
+  if (from_space < -1 || from_space > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "%s: unknown color space <from>: %d", who, from_space);
+  if ((channels != 1 && channels != 3) || (from_space >= 0 && channels != (from_space == GR_CS_Y ? 1 : 3)))
+    return fail(c, GR_ERR_INVALID, "%s: %d channel(s) with from_space %d", who, channels, from_space);
+  return GR_OK;
+}
+static int grid_size_check(gr_ctx* c, const char* who, long GH, long GW) {
+  return GH > (1 << 20) || GW > (1 << 20) || GH * GW > (1L << 28) ? fail(c, GR_ERR_INVALID, "%s: a %ld x %ld grid is too large", who, GH, GW) : GR_OK;
+}
+extern "C" int gr_image_grid_dev(gr_ctx* c, const float* const* src, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
+                                 const int64_t* rows, int n_tiles, int nrow, int padding, int margin, const float* bg, const uint8_t* inset,
+                                 const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid, uint8_t* u8) {
+  if (!c) return GR_ERR_INVALID;
+  if (slots != 1 && slots != 2) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: slots %d (1 or 2)", slots);
+  if (!src || !n_rows || !rows) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: null pointer");
+  for (int s = 0; s < slots; ++s)
+    if (!src[s] || n_rows[s] <= 0) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: table %d is null or has no rows", s);
+  TRY(grid_source_check(c, "gr_image_grid_dev", grid, u8, channels, from_space));
+  if (h <= 0 || w <= 0 || n_tiles <= 0 || nrow <= 0 || padding < 0 || padding > 64 || margin < 0 || margin > 1)
+    return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: bad geometry (h %d, w %d, n_tiles %d, nrow %d, padding %d in [0, 64], margin %d in {0, 1})", h, w, n_tiles, nrow, padding, margin);
+  if (inset && !inset_rgb) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: inset flags without inset_rgb");
+  if (!auto_range && !(lo <= hi)) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: display range [%g, %g]", (double)lo, (double)hi);
+  GridGeom g{};
+  g.slots = slots; g.C = channels; g.Cout = from_space >= 0 ? 3 : channels; g.H = h; g.W = w; g.from = from_space;
+  g.n_tiles = n_tiles; g.xmaps = nrow < n_tiles ? nrow : n_tiles; g.padding = padding; g.margin = margin;
+  const int ymaps = (n_tiles + g.xmaps - 1) / g.xmaps;
+  const long TH = (long)h + 2 * margin, TW = (long)slots * w + 2 * margin, GH = (TH + padding) * ymaps, GW = (TW + padding) * g.xmaps;
+  TRY(grid_size_check(c, "gr_image_grid_dev", GH, GW));
+  g.TH = (int)TH; g.TW = (int)TW; g.cellH = (int)TH + padding; g.cellW = (int)TW + padding; g.GH = (int)GH; g.GW = (int)GW;
+  std::vector<GridTile> tiles((size_t)n_tiles);
+  for (int t = 0; t < n_tiles; ++t) {
+    GridTile& tl = tiles[t];
+    tl.row[0] = tl.row[1] = -1;
+    for (int s = 0; s < slots; ++s) {
+      const int64_t r = rows[(size_t)t * slots + s];
+      if (r < -1 || r >= n_rows[s]) return fail(c, GR_ERR_INVALID, "gr_image_grid_dev: row %lld of tile %d, slot %d is outside [-1, %lld)", (long long)r, t, s, (long long)n_rows[s]);
+      tl.row[s] = (long)r;
+    }
+    for (int k = 0; k < 3; ++k) tl.bg[k] = bg ? bg[(size_t)t * 3 + k] : 0.f;
+    tl.inset = inset ? inset[t] != 0 : 0;
+  }
+  for (int k = 0; k < 3; ++k) g.inset_rgb[k] = inset_rgb ? inset_rgb[k] : 0.f;
+  g.fill = fill; g.lo = lo; g.hi = hi;
+  Staging s(c);
+  auto parts = s.reserve<float>(2 * GRID_RANGE_BLOCKS);              // the auto-range blocks: the first region
+  auto dtiles = s.reserve<GridTile>(n_tiles);
+  TRY(s.grow()); TRY(s.upload_now(dtiles, tiles.data()));
+  g.src[0] = src[0]; g.src[1] = slots == 2 ? src[1] : src[0]; g.tiles = s.ptr(dtiles);
+  launch_image_grid(g, auto_range ? s.ptr(parts) : nullptr, grid, u8, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ the trainers' progress pictures (render.hip)
+extern "C" int gr_progress_grid_dev(gr_ctx* c, const float* table, int64_t n_rows, int channels, int h, int w, int from_space,
+                                    const int64_t* rows, int n_show, int grid_h, int grid_w, int epoch, float* grid, uint8_t* u8) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: the table is null");
+  TRY(grid_source_check(c, "gr_progress_grid_dev", grid, u8, channels, from_space));
+  if (n_rows < 1 || h < 1 || w < 1 || grid_h < 1 || grid_w < 1 || n_show < 0)
+    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: bad geometry (n_rows %lld, h %d, w %d, grid %d x %d, n_show %d)", (long long)n_rows, h, w, grid_h, grid_w, n_show);
+  if (epoch < 0) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: epoch %d is negative", epoch);
+  const long GH = (long)grid_h * h + 7, GW = (long)grid_w * w;
+  TRY(grid_size_check(c, "gr_progress_grid_dev", GH, GW));
+  ProgressGeom g{};
+  for (int e = epoch; g.ndig == 0 || e > 0; e /= 10) g.dig[g.ndig++] = (unsigned char)(e % 10);
+  if (GW - 2 - 6L * g.ndig < 0)
+    return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: the %d digit(s) of epoch %d do not fit a grid %ld pixels wide", g.ndig, epoch, GW);
+  const long cells = (long)grid_h * grid_w;
+  g.n_cells = (int)(n_show < cells ? n_show : cells);
+  if (g.n_cells > 0 && !rows) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: rows_host is null");
+  for (int t = 0; t < g.n_cells; ++t)
+    if (rows[t] < 0 || rows[t] >= n_rows) return fail(c, GR_ERR_INVALID, "gr_progress_grid_dev: rows[%d] = %lld is outside [0, %lld)", t, (long long)rows[t], (long long)n_rows);
+  g.C = channels; g.Cout = from_space >= 0 ? 3 : channels; g.H = h; g.W = w; g.from = from_space;
+  g.grid_w = grid_w; g.GH = (int)GH; g.GW = (int)GW;
+  Staging s(c);
+  auto drows = s.reserve<long>(g.n_cells > 0 ? g.n_cells : 1);
+  TRY(s.grow());
+  if (g.n_cells > 0) TRY(s.upload_now(drows, rows));
+  g.src = table; g.rows = s.ptr(drows);
+  const bool vec = w % 4 == 0 && (uintptr_t)table % 16 == 0 && (uintptr_t)grid % 16 == 0 && (uintptr_t)u8 % 4 == 0;
+  launch_progress_grid(g, vec, grid, u8, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ sample.lua:130-148 findClosestNeighboursOf (neighbours.hip)
+static int l2_nearest_check(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k, const int64_t* idx_out, const double* dist_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table || !queries || !idx_out || !dist_out || n <= 0 || d < 1 || d > 65536 || Q < 1 || Q > 64 || k < 1 || k > n)
+    return fail(c, GR_ERR_INVALID, "gr_l2_nearest: bad arguments (n %lld, d %lld, q %d, k %d)", (long long)n, (long long)d, Q, k);
+  if (k > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: k > 128");
+  if (n >= 0xFFFFFFFFll) return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: n >= 2^32 - 1");
+  return GR_OK;
+}
+extern "C" int gr_l2_nearest_dev(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
+                                 int64_t* idx_out, double* dist_out) {
+  TRY(l2_nearest_check(c, table, n, d, queries, Q, k, idx_out, dist_out));
+  Staging s(c);
+  auto scratch = s.reserve<char>(l2_nearest_workspace_bytes(n, Q));     // launch_l2_nearest takes c->ws itself: the first region
+  const size_t res = sizeof(long) * (size_t)Q * k + sizeof(double) * (size_t)Q * k + sizeof(unsigned) * (size_t)Q;
+  auto dres = s.reserve<char>(res);                                     // [idx | dist | status]: one copy back
+  TRY(s.grow());
+  long* d_idx = (long*)s.ptr(dres); double* d_dist = (double*)(d_idx + (size_t)Q * k); unsigned* d_status = (unsigned*)(d_dist + (size_t)Q * k);
+  std::vector<char> h(res);
+  for (int exact = l2_nearest_direct(n) ? 1 : 0; exact < 2; ++exact) {
+    if (launch_l2_nearest(table, n, (int)d, queries, Q, k, d_idx, d_dist, d_status, s.ptr(scratch), exact, c->cu_count, c->stream))
+      return fail(c, GR_ERR_UNSUPPORTED, "gr_l2_nearest: unsupported size");
+    LAUNCHCHK(c);
+    TRY(s.download(h.data(), dres)); TRY(s.finish());
+    bool over = false;
+    for (int q = 0; q < Q && !exact; ++q) { unsigned st; memcpy(&st, h.data() + res - sizeof(unsigned) * (size_t)(Q - q), sizeof st); over = over || st != 0u; }
+    if (!over) break;             // (the exact path does not write the status words)
+  }
+  memcpy(idx_out, h.data(), sizeof(long) * (size_t)Q * k);
+  memcpy(dist_out, h.data() + sizeof(long) * (size_t)Q * k, sizeof(double) * (size_t)Q * k);
+  return GR_OK;
+}
+extern "C" int gr_l2_nearest_host(gr_ctx* c, const float* table, int64_t n, int64_t d, const float* queries, int Q, int k,
+                                  int64_t* idx_out, double* dist_out) {
+  TRY(l2_nearest_check(c, table, n, d, queries, Q, k, idx_out, dist_out));
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t tb = sizeof(float) * (size_t)n * d, qb = sizeof(float) * (size_t)Q * d;
+  DevTemp dt(c), dq(c);
+  TRY(dt.alloc(tb)); TRY(dq.alloc(qb));
+  if (hipMemcpyAsync(dt.p, table, tb, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return fail(c, GR_ERR_HIP, "upload failed");
+  return gr_l2_nearest_dev(c, dt.as<float>(), n, d, dq.as<float>(), Q, k, idx_out, dist_out);
+}
+
+// ------------------------------------------------------------------ single-kernel entry points
+static int with_prepped(gr_ctx* c, const float* w, int cin, int cout, bool bwd, DevTemp& wt) {
+  const ConvWeightLayout L = bwd ? conv_weight_layout(cout, cin) : conv_weight_layout(cin, cout);
+  TRY(wt.alloc(sizeof(float) * L.elems()));
+  launch_conv_weight_prep(w, wt.as<float>(), cin, cout, bwd, c->stream);
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+// f16x3: the weight maximum goes to c->amax[2]
+static int conv_split_once(gr_ctx* c, const float* w, int cin, int cout, bool bwd, DevTemp& ws) {
+  TRY(ws.alloc(conv_weight_split_bytes(cin, cout, bwd)));
+  launch_conv_weight_split(w, ws.p, cin, cout, bwd, c->stream, c->conv_mode == 2 ? 2 : 3, c->amax + 2 * AMAX_WORDS);
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+// how the gr_conv3_* calls end: the launch status is read first, then their weight image goes (DevTemp waits for the stream)
+static int conv_launched(gr_ctx* c) { hipError_t e = hipGetLastError(); return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e)); }
+extern "C" int gr_conv3_forward_dev(gr_ctx* c, const float* in, const float* w, const float* bias, float* out, int B, int cin, int cout, int h, int wd, int up) {
+  if (!c || !in || !w || !out) return GR_ERR_INVALID;
+  DevTemp wt(c);
+  if (c->conv_mode == 2 && up && conv_up2_supported(cin, cout, h, wd)) {
+    // the fused up-sampling layer as four 2x2 convolutions (the path a net takes for such a stage in f16x3 mode)
+    TRY(wt.alloc(conv_weight_up2_bytes(cin, cout)));
+    launch_conv_weight_up2_split(w, wt.p, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
+    launch_absmax(in, (long)B * cin * (h / 2) * (wd / 2), c->amax, c->stream);
+    launch_conv3x3_up2_f16x3(in, wt.p, bias, out, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr);
+  } else if (c->conv_mode >= 1 && cout > 4) {
+    TRY(conv_split_once(c, w, cin, cout, false, wt));
+    if (c->conv_mode == 2) launch_absmax(in, (long)B * cin * (up ? (h / 2) * (wd / 2) : h * wd), c->amax, c->stream);
+    launch_conv3x3_split(in, wt.p, bias, out, B, cin, cout, h, wd, up != 0, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax, c->amax + 2 * AMAX_WORDS);
+  } else {
+    TRY(with_prepped(c, w, cin, cout, false, wt));
+    launch_conv3x3(in, wt.as<float>(), bias, out, B, cin, cout, h, wd, up != 0, c->stream, w);
+  }
+  return conv_launched(c);
+}
+extern "C" int gr_conv3_backward_data_dev(gr_ctx* c, const float* gout, const float* w, float* gin, int B, int cin, int cout, int h, int wd) {
+  if (!c || !gout || !w || !gin) return GR_ERR_INVALID;
+  DevTemp wt(c);
+  if (c->conv_mode >= 1 && cin > 4) {
+    TRY(conv_split_once(c, w, cin, cout, true, wt));
+    if (c->conv_mode == 2) launch_absmax(gout, (long)B * cout * h * wd, c->amax + AMAX_WORDS, c->stream);
+    launch_conv3x3_split(gout, wt.p, nullptr, gin, B, cout, cin, h, wd, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
+  } else {
+    TRY(with_prepped(c, w, cin, cout, true, wt));
+    launch_conv3x3(gout, wt.as<float>(), nullptr, gin, B, cout, cin, h, wd, false, c->stream);
+  }
+  return conv_launched(c);
+}
+extern "C" int gr_conv3_backward_weight_dev(gr_ctx* c, const float* in, const float* gout, float* gw, int B, int cin, int cout, int h, int wd) {
+  if (!c || !in || !gout || !gw) return GR_ERR_INVALID;
+  int r = ensure_ws(c, conv_wgrad_workspace_bytes(B, cin, cout, h, wd, c->conv_mode)); if (r) return r;
+  if (c->conv_mode == 2 && conv_wgrad_is_split(2, cin, wd)) {
+    launch_absmax(in, (long)B * cin * h * wd, c->amax, c->stream);
+    launch_absmax(gout, (long)B * cout * h * wd, c->amax + AMAX_WORDS, c->stream);
+  }
+  launch_conv3x3_wgrad(in, gout, gw, c->ws, B, cin, cout, h, wd, c->stream, c->conv_mode, c->amax, c->amax + AMAX_WORDS);
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+// Sustained rate of the bare f16x3 inner loop (mfmaloop.hip) on this device: `launches` back-to-back launches (>= 0.3 s of them
+// before the timed ones so that the clock settles), HIP events on the ctx stream.  shape 0 = v_mfma_f32_32x32x16_f16 (what the
+// convolution kernels issue), 1 = v_mfma_f32_16x16x32_f16.  tflops_out: fp32-accurate TFLOP/s (f16 MFMA rate / 3 products), the
+// figure comparable with the 833 TFLOP/s ceiling bench.py prices the f16x3 kernels against.
+extern "C" int gr_bench_mfma_loop(gr_ctx* c, int shape, int launches, float* tflops_out) {
+  if (!c || !tflops_out || shape < 0 || shape > 1 || launches < 1) return GR_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ensure_ws(c, mfma_loop_workspace_bytes()); if (r) return r;
+  launch_mfma_loop_fill(c->ws, c->stream);
+  const int iters = 200;
+  for (int i = 0; i < 300; ++i) launch_mfma_loop(shape, c->ws, iters, c->stream);     // ~0.35 s of warm-up under load
+  LAUNCHCHK(c);
+  EventTemp e0, e1;
+  HIPCHK(c, hipEventRecord(e0.e, c->stream));
+  for (int i = 0; i < launches; ++i) launch_mfma_loop(shape, c->ws, iters, c->stream);
+  HIPCHK(c, hipEventRecord(e1.e, c->stream));
+  HIPCHK(c, hipEventSynchronize(e1.e));
+  float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e0.e, e1.e));
+  *tflops_out = (float)(mfma_loop_flops(iters) * launches / (ms * 1e-3) / 1e12 / 3.0);
+  return GR_OK;
+}
+extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, int h, int wd, int iters, float* avg_ms) {
+  if (!c || iters < 1 || !avg_ms) return GR_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nin = (size_t)B * cin * h * wd, nout = (size_t)B * cout * h * wd, nw = (size_t)cin * cout * 9;
+  DevTemp dx(c), dy(c), dw(c), dgw(c), dwt(c), dwsp(c), dwup(c), dxp16(c), dstatp(c);
+  TRY(dx.alloc(sizeof(float) * nin)); TRY(dy.alloc(sizeof(float) * nout)); TRY(dw.alloc(sizeof(float) * nw)); TRY(dgw.alloc(sizeof(float) * nw));
+  float *x = dx.as<float>(), *y = dy.as<float>(), *w = dw.as<float>(), *gw = dgw.as<float>();
+  launch_fill_normal(x, (long)nin, 11, c->stream); launch_fill_normal(y, (long)nout, 12, c->stream); launch_fill_normal(w, (long)nw, 13, c->stream);
+  (void)hipMemsetAsync(gw, 0, sizeof(float) * nw, c->stream);
+  TRY(with_prepped(c, w, cin, cout, which == 1, dwt));
+  const bool split = c->conv_mode >= 1 && which != 2 && (which == 0 ? cout > 4 : cin > 4);
+  const int nterm = c->conv_mode == 2 ? 2 : 3;
+  if (split) TRY(conv_split_once(c, w, cin, cout, which == 1, dwsp));      // (which 4 and 5 launch on this image too: forward orientation, same term count)
+  TRY(ensure_ws(c, conv_wgrad_workspace_bytes(B, cin, cout, h, wd, c->conv_mode)));
+  // f16x3 scales: taken once outside the timed loop (in a net the producing kernel tracks them)
+  if (c->conv_mode == 2) { launch_absmax(x, (long)nin, c->amax, c->stream); launch_absmax(y, (long)nout, c->amax + AMAX_WORDS, c->stream); }
+  if (which == 3) {      // fused up-sampling layer: x is the source plane [B, cin, h/2, wd/2] (a quarter of the buffer), y the output
+    if (c->conv_mode != 2 || !conv_up2_supported(cin, cout, h, wd)) return fail(c, GR_ERR_UNSUPPORTED, "up2 bench needs f16x3 mode and a supported shape");
+    TRY(dwup.alloc(conv_weight_up2_bytes(cin, cout)));
+    launch_conv_weight_up2_split(w, dwup.p, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
+  }
+  if (which == 4 || which == 5) {   // operand-ready forward (5: with the BatchNorm statistics epilogue): x converted once outside the loop
+    if (c->conv_mode != 2 || !conv_p16_supported(B, cin, cout, h, wd)) return fail(c, GR_ERR_UNSUPPORTED, "p16 bench needs f16x3 mode and a supported shape");
+    TRY(dxp16.alloc(sizeof(float) * nin));
+    TRY(dstatp.alloc(sizeof(double) * 2 * cout * conv_stat_tiles_max(B, h, wd)));
+    launch_to_p16(x, dxp16.p, B, cin, h * wd, c->amax, c->stream);
+  }
+  float* wt = dwt.as<float>(); void *wsp = dwsp.p, *wup = dwup.p, *xp16 = dxp16.p; double* statp = dstatp.as<double>();
+  auto run = [&]() {
+    if (which == 4 || which == 5) { int st = 0; launch_conv3x3_p16(xp16, wsp, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr, which == 5 ? statp : nullptr, which == 5 ? &st : nullptr); return; }
+    if (which == 3) { launch_conv3x3_up2_f16x3(x, wup, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr); return; }
+    if (split && which == 0) launch_conv3x3_split(x, wsp, nullptr, y, B, cin, cout, h, wd, false, c->stream, nullptr, nterm, c->amax, c->amax + 2 * AMAX_WORDS);
+    else if (split && which == 1) launch_conv3x3_split(y, wsp, nullptr, x, B, cout, cin, h, wd, false, c->stream, nullptr, nterm, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
+    else if (which == 0) launch_conv3x3(x, wt, nullptr, y, B, cin, cout, h, wd, false, c->stream, w);
+    else if (which == 1) launch_conv3x3(y, wt, nullptr, x, B, cout, cin, h, wd, false, c->stream);
+    else launch_conv3x3_wgrad(x, y, gw, c->ws, B, cin, cout, h, wd, c->stream, c->conv_mode, c->amax, c->amax + AMAX_WORDS);
+  };
+  for (int i = 0; i < 3; ++i) run();
+  EventTemp e0, e1;
+  (void)hipEventRecord(e0.e, c->stream);
+  for (int i = 0; i < iters; ++i) run();
+  (void)hipEventRecord(e1.e, c->stream);
+  HIPCHK(c, hipEventSynchronize(e1.e));
+  float ms = 0; (void)hipEventElapsedTime(&ms, e0.e, e1.e);
+  *avg_ms = ms / iters;
+  LAUNCHCHK(c);
+  return GR_OK;
+}

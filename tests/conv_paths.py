@@ -5,7 +5,7 @@ Used by tests/test_conv_paths_host.py (CPU: the table reaches every leaf, the mi
 emulations of the three arithmetic modes and rejects degraded ones) and tests/test_gpu_conv_paths.py (every case against the bound, and its
 kernel_times() labels against the mirror).
 
-Scope: what gr_conv3_forward_dev, gr_conv3_backward_data_dev and gr_conv3_backward_weight_dev (net.hip) can launch - launch_conv3x3 (fp32
+Scope: what gr_conv3_forward_dev, gr_conv3_backward_data_dev and gr_conv3_backward_weight_dev (ops.hip) can launch - launch_conv3x3 (fp32
 MFMA and few-output VALU kernels), launch_conv3x3_split_n (bf16x6 / f16x3), launch_conv3x3_up2_f16x3 and launch_conv3x3_wgrad.  The kernels
 only a net launches (conv3x3_fewin*, the 5x5 kernels of conv.hip / convk.hip, the operand-ready P16 kernels) are not restated here."""
 import dataclasses
@@ -94,7 +94,7 @@ def split_wide_tiles(N, B, Cout, H, W):
 
 
 def forward_leaves(mode, B, Cin, Cout, H, W, up, stack8=128):
-    """gr_conv3_forward_dev (net.hip): H, W = the output plane (the input is H/2 x W/2 when up)"""
+    """gr_conv3_forward_dev (ops.hip): H, W = the output plane (the input is H/2 x W/2 when up)"""
     m = MODES[mode]
     if m == 2 and up and conv_up2_supported(Cin, Cout, H, W):
         return {up2_leaf(W)}
@@ -104,7 +104,7 @@ def forward_leaves(mode, B, Cin, Cout, H, W, up, stack8=128):
 
 
 def backward_data_leaves(mode, B, Cin, Cout, H, W, stack8=128):
-    """gr_conv3_backward_data_dev (net.hip): the forward kernels with Cin and Cout exchanged, no native weights (no few-output kernel)"""
+    """gr_conv3_backward_data_dev (ops.hip): the forward kernels with Cin and Cout exchanged, no native weights (no few-output kernel)"""
     m = MODES[mode]
     if m >= 1 and Cin > 4:
         return {split_leaf(2 if m == 2 else 3, B, Cin, H, W, False, stack8)}

@@ -50,7 +50,7 @@ def small_path_ok(N, d, Q, k):
 
 
 def search_path(N, d, Q, k):
-    """The path launch_cosine_topk (search.hip:1244) takes on the first try of gr_cosine_topk_dev (net.hip:1945)."""
+    """The path launch_cosine_topk (search.hip:1244) takes on the first try of gr_cosine_topk_dev (ops.hip:173)."""
     k = min(k, N)
     filt = N >= FILTER_MIN_ROWS and k * 8 <= SAMPLE_ROWS and k <= CHUNK // 2                                  # :1258
     if filt and small_path_ok(N, d, Q, k):                                                                    # :1259
