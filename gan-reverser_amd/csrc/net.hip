@@ -108,7 +108,7 @@ static int ensure_stat_comm(gr_ctx* c) {
   if (!c->comm || c->stat_comm || !c->sync_bn) return GR_OK;
   // a split with operations still outstanding on the parent is not supported: gradient buckets / the loss all-reduce of the previous step may be in flight
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->comm_stream) HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+  HIPCHK(c, hipStreamSynchronize(c->comm_stream));
   NCCLCHK(c, ncclCommSplit(c->comm, 0, c->rank, &c->stat_comm, nullptr));
   return GR_OK;
 }
@@ -122,10 +122,10 @@ static const StatSync* stat_sync(gr_ctx* c, StatSync& ss, int C, double n_local)
     // is parked in coll_rc, which every caller of stat_sync returns before it issues anything else.
     if (c->sync_buf) {
       if (hipStreamSynchronize(c->stream) != hipSuccess) { if (!c->coll_rc) c->coll_rc = fail(c, GR_ERR_HIP, "sync-BN: stream synchronise failed before regrowing the statistics buffer"); return nullptr; }
-      (void)hipFree(c->sync_buf); c->sync_buf = nullptr; c->sync_cap = 0;
+      c->mem.drop(c->sync_buf); c->sync_buf = nullptr; c->sync_cap = 0;
     }
     const size_t cap = (size_t)(C > 2048 ? C : 2048) * 2;
-    if (hipMalloc((void**)&c->sync_buf, sizeof(double) * cap) != hipSuccess) { c->sync_buf = nullptr; if (!c->coll_rc) c->coll_rc = fail(c, GR_ERR_HIP, "sync-BN: statistics buffer allocation failed (%zu bytes)", sizeof(double) * cap); return nullptr; }
+    if (c->mem.dev(&c->sync_buf, sizeof(double) * cap) != hipSuccess) { if (!c->coll_rc) c->coll_rc = fail(c, GR_ERR_HIP, "sync-BN: statistics buffer allocation failed (%zu bytes)", sizeof(double) * cap); return nullptr; }
     c->sync_cap = cap;
   }
   ss.sum = statsync_sum; ss.max_u32 = statsync_max; ss.user = c; ss.buf = c->sync_buf;
@@ -137,7 +137,7 @@ static const StatSync* stat_sync(gr_ctx* c, StatSync& ss, int C, double n_local)
 struct PhaseRange { explicit PhaseRange(const char* name) { roctxRangePushA(name); } ~PhaseRange() { roctxRangePop(); } };
 
 // workspace of the side stream (weight gradients running beside the rest of backward)
-static int ensure_ws2(gr_ctx* c, size_t bytes) { return bytes <= c->ws2_bytes ? GR_OK : grow_dev(c, &c->ws2, c->ws2_bytes, past_next_mib(bytes), c->side_stream); }
+static int ensure_ws2(gr_ctx* c, size_t bytes) { return bytes <= c->ws2_bytes ? GR_OK : grow_dev(c, c->mem, &c->ws2, c->ws2_bytes, past_next_mib(bytes), c->side_stream); }
 
 // The head kernel's sticky fault word (elem.hip head_grid_barrier).  Read - one 4-byte copy, only when a head kernel has run since the last look - by every
 // call that synchronises the stream anyway: gr_train_r_step with a loss_out, gr_synchronize, gr_net_get_params / gr_net_get_grads.  Set means: a grid
@@ -162,6 +162,22 @@ static int head_fault_check(gr_ctx* c) {
 
 extern "C" const char* gr_version(void) { return "ganrev-gfx950 0.6 (round 6)"; }
 
+// the streams, events and buffers every context has (the rest are made by the calls that first need them)
+static int ctx_create(gr_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, c->stream.create());
+  HIPCHK(c, c->mem.dev(&c->d_loss, 64)); HIPCHK(c, c->mem.dev(&c->amax, sizeof(unsigned) * 4 * AMAX_WORDS));
+  HIPCHK(c, c->mem.pinned(&c->h_loss, 64));
+  for (auto& e : c->ev) HIPCHK(c, e.create());
+  HIPCHK(c, c->ev_guard.create(hipEventDisableTiming));
+  HIPCHK(c, hipMemsetAsync(c->d_loss, 0, 64, c->stream));
+  memset(c->h_loss, 0, 64);
+  HIPCHK(c, c->comm_stream.create()); HIPCHK(c, c->side_stream.create());
+  HIPCHK(c, c->ev_dy_ready.create(hipEventDisableTiming));
+  for (auto& e : c->ev_wgrad_done) HIPCHK(c, e.create(hipEventDisableTiming));
+  HIPCHK(c, c->ev_ready.create(hipEventDisableTiming)); HIPCHK(c, c->ev_done.create(hipEventDisableTiming));
+  return GR_OK;
+}
 extern "C" int gr_init(int device, gr_ctx** out) {
   if (!out) return GR_ERR_INVALID;
   *out = nullptr;
@@ -174,56 +190,32 @@ extern "C" int gr_init(int device, gr_ctx** out) {
   gr_ctx* c = new gr_ctx();
   c->device = device;
   c->cu_count = p.multiProcessorCount;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&c->d_loss, 64) != hipSuccess || hipMalloc((void**)&c->amax, sizeof(unsigned) * 4 * AMAX_WORDS) != hipSuccess || hipHostMalloc((void**)&c->h_loss, 64) != hipSuccess) {
-    delete c; return GR_ERR_HIP;
-  }
-  for (auto& e : c->ev) (void)hipEventCreate(&e);
-  (void)hipEventCreateWithFlags(&c->ev_guard, hipEventDisableTiming);
-  (void)hipMemsetAsync(c->d_loss, 0, 64, c->stream);
-  memset(c->h_loss, 0, 64);
+  if (ctx_create(c)) { delete c; return GR_ERR_HIP; }      // (its owners take back whatever was made)
   { const char* d = getenv("GR_RANGE_GUARD"); if (d) c->range_guard = atoi(d); }
   { const char* m = getenv("GR_CONV_MODE"); if (m) c->conv_mode = (!strcmp(m, "f32") || !strcmp(m, "0")) ? 0 : ((!strcmp(m, "bf16x6") || !strcmp(m, "1")) ? 1 : 2); }
-  (void)hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking);
-  (void)hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking);
-  (void)hipEventCreateWithFlags(&c->ev_dy_ready, hipEventDisableTiming);
-  for (auto& e : c->ev_wgrad_done) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   { const char* e = getenv("GR_SIDE_WGRAD"); if (e) c->side_wgrad = atoi(e); }
   { const char* e = getenv("GR_FUSED_HEAD"); if (e) c->fused_head = atoi(e) != 0; }
-  (void)hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming);
-  (void)hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming);
   *out = c;
+  return GR_OK;
+}
+
+// Everything that may still read a buffer of this context or of one of its nets has finished.  All three streams: the compute stream joins the
+// weight gradients (side_stream) and the gradient buckets (comm_stream) at the end of a backward that succeeds, but a backward that returns an
+// error part-way has not waited for them, and neither has a loss all-reduce whose step failed after it.
+static int drain(gr_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e0 = hipStreamSynchronize(c->stream), e1 = hipStreamSynchronize(c->comm_stream), e2 = hipStreamSynchronize(c->side_stream);
+  HIPCHK(c, e0); HIPCHK(c, e1); HIPCHK(c, e2);
   return GR_OK;
 }
 
 extern "C" int gr_shutdown(gr_ctx* c) {
   if (!c) return GR_ERR_INVALID;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);      // gradient buckets in flight: before the communicators go
+  (void)drain(c);                                                       // gradient buckets in flight: before the communicators go
   if (c->stat_comm) { ncclCommDestroy(c->stat_comm); c->stat_comm = nullptr; }
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  if (c->ws2) (void)hipFree(c->ws2);
-  if (c->ev_dy_ready) (void)hipEventDestroy(c->ev_dy_ready);
-  if (c->head_bar) (void)hipFree(c->head_bar);
-  if (c->head_loss_part) (void)hipFree(c->head_loss_part);
-  for (auto& e : c->ev_wgrad_done) if (e) (void)hipEventDestroy(e);
-  if (c->guard_chmax) (void)hipFree(c->guard_chmax);
-  if (c->sync_buf) (void)hipFree(c->sync_buf);
-  if (c->pin) (void)hipHostFree(c->pin);
-  if (c->pin_done) (void)hipHostFree(c->pin_done);
-  if (c->search_state) (void)hipFree(c->search_state);
-  if (c->ev_guard) (void)hipEventDestroy(c->ev_guard);
-  (void)hipFree(c->d_loss); (void)hipFree(c->amax); (void)hipHostFree(c->h_loss);
-  for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->marks) if (e) (void)hipEventDestroy(e);
-  if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
-  if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-  if (c->comm_stream) { (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamDestroy(c->comm_stream); }
-  (void)hipStreamDestroy(c->stream);
-  delete c;
+  c->mem.release();
+  delete c;                                                             // the events, then the streams
   return GR_OK;
 }
 extern "C" const char* gr_last_error(gr_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
@@ -317,8 +309,8 @@ extern "C" int gr_kernel_times(gr_ctx* c, char* buf, int buflen) {
 }
 extern "C" int gr_event_record(gr_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= (1 << 16)) return GR_ERR_INVALID;
-  if ((size_t)slot >= c->marks.size()) c->marks.resize((size_t)slot + 1, nullptr);
-  if (!c->marks[slot]) HIPCHK(c, hipEventCreate(&c->marks[slot]));
+  if ((size_t)slot >= c->marks.size()) c->marks.resize((size_t)slot + 1);
+  if (!c->marks[slot]) HIPCHK(c, c->marks[slot].create());
   HIPCHK(c, hipEventRecord(c->marks[slot], c->stream));
   return GR_OK;
 }
@@ -386,14 +378,22 @@ struct Stage {
   bool out_skipped = false;                 // last forward left `out` operand-ready only (the next stage's x_p16): no fp32 copy exists
 };
 
-struct gr_net {
-  gr_ctx* ctx = nullptr;
-  std::vector<gr_layer_desc> layers;
+// what plan_net makes of a layer list: host data only
+struct NetPlan {
   std::vector<Stage> st;
   std::vector<MaskSlot> masks;
   std::vector<int> bn_stage;
-  int inC = 0, inH = 0, inW = 0, outC = 0, outH = 0, outW = 0;
+  int outC = 0, outH = 0, outW = 0;
   int64_t n_params = 0;
+};
+struct gr_net : NetPlan {
+  gr_ctx* ctx = nullptr;
+  // Two owners of the device memory.  mem: what net_alloc sizes at creation (parameters, optimiser state, per-channel arrays, weight images,
+  // scale slots, prep jobs) and the buffers grow_dev sizes on demand (mask bits, mask_stage, up_tmp).  batch: what ensure_batch sizes.  A
+  // pointer that aliases another buffer (y of an element-wise stage, out of a stage without a pipeline) is never allocated, so never owned.
+  DevMem mem, batch;
+  std::vector<gr_layer_desc> layers;
+  int inC = 0, inH = 0, inW = 0;
   float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
   uint64_t params_version = 1;
   bool training = true;
@@ -426,196 +426,177 @@ static bool is_act(int k) { return k == GR_ELU || k == GR_RELU || k == GR_LEAKYR
 
 extern "C" int gr_net_destroy(gr_net* n) {
   if (!n) return GR_ERR_INVALID;
-  gr_ctx* c = n->ctx;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  for (auto& s : n->st) {
-    if (s.kind != ST_ELEM) (void)hipFree(s.y);
-    if (s.has_post) (void)hipFree(s.out);
-    (void)hipFree(s.pool_idx); (void)hipFree(s.wt_fwd); (void)hipFree(s.wt_bwd); (void)hipFree(s.ws_fwd); (void)hipFree(s.ws_up); (void)hipFree(s.ws_bwd);
-    (void)hipFree(s.mean); (void)hipFree(s.invstd); (void)hipFree(s.coef); (void)hipFree(s.partials); (void)hipFree(s.partials_b); (void)hipFree(s.stat_part);
-    (void)hipFree(s.run_mean); (void)hipFree(s.run_var); (void)hipFree(s.x_p16); (void)hipFree(s.wl1);
-  }
-  for (auto& m : n->masks) (void)hipFree(m.bits);
-  (void)hipFree(n->params); (void)hipFree(n->grads); (void)hipFree(n->adam_m); (void)hipFree(n->adam_v);
-  (void)hipFree(n->in_buf); (void)hipFree(n->gout_buf); (void)hipFree(n->dy_buf); (void)hipFree(n->g_buf[0]); (void)hipFree(n->g_buf[1]);
-  (void)hipFree(n->dy_p16); (void)hipFree(n->dy_p16_b); (void)hipFree(n->dy_buf_b); (void)hipFree(n->up_tmp[0]); (void)hipFree(n->up_tmp[1]); (void)hipFree(n->mask_stage); (void)hipFree(n->jobs_dev[0]); (void)hipFree(n->jobs_dev[1]); (void)hipFree(n->jobs_dev[2]); (void)hipFree(n->amax);
+  (void)drain(n->ctx);
   delete n;
+  return GR_OK;
+}
+
+// The layer list as stages, in one walk: parameter offsets in getParameters() order, the shape checks, stages, masks, bn_stage and the
+// output dims.  A function of (layers, input dims) alone; a failure is a code and a message.
+static int plan_net(const gr_layer_desc* L, int nl, int in_c, int in_h, int in_w, NetPlan& pl, std::string& msg) {
+  auto bad = [&](int code, const char* fmt, auto... a) { char buf[512]; snprintf(buf, sizeof buf, fmt, a...); msg = buf; return code; };
+  int cc = in_c, h = in_h, w = in_w; int64_t off = 0, wo = -1, bo = -1;
+  // layer i joins the stage being built: its shape rule and its slice (wo, bo) of the flat parameter vector.  Every shape rule is here and only here.
+  auto take = [&](int i) -> int {
+    const gr_layer_desc& d = L[i];
+    wo = bo = -1;
+    switch (d.kind) {
+      case GR_CONV3: case GR_FULLCONV3: case GR_CONVK: {
+        if (d.a != cc) return bad(GR_ERR_INVALID, "layer %d: conv expects %d input planes, got %d", i, d.a, cc);
+        if (d.kind == GR_CONVK && !convk_supported(d.c)) return bad(GR_ERR_UNSUPPORTED, "layer %d: no kernel for a %dx%d convolution (3x3: GR_CONV3; 5x5: GR_CONVK)", i, d.c, d.c);
+        const int k = d.kind == GR_CONVK ? d.c : 3;
+        wo = off; off += (int64_t)d.a * d.b * k * k; bo = off; off += d.b; cc = d.b; break; }
+      case GR_PRELU: wo = off; off += 1; break;          // nn.PReLU(): weight = Tensor(1)
+      case GR_LINEAR:
+        if (d.a != vol3(cc, h, w)) return bad(GR_ERR_INVALID, "layer %d: linear expects %d inputs, got %lld", i, d.a, (long long)vol3(cc, h, w));
+        wo = off; off += (int64_t)d.a * d.b; bo = off; off += d.b; cc = d.b; h = 1; w = 1; break;
+      case GR_BN:
+        if (d.a != cc) return bad(GR_ERR_INVALID, "layer %d: BN expects %d features, got %d", i, d.a, cc);
+        wo = off; off += cc; bo = off; off += cc; break;
+      case GR_MAXPOOL2: case GR_AVGPOOL2: h /= 2; w /= 2; break;     // floor, as THNN: an odd last row / column is dropped
+      case GR_UPSAMPLE2: h *= 2; w *= 2; break;
+      case GR_VIEW: {
+        const int vb = d.b > 0 ? d.b : 1, vc = d.c > 0 ? d.c : 1;
+        if (vol3(d.a, vb, vc) != vol3(cc, h, w)) return bad(GR_ERR_INVALID, "layer %d: view size mismatch", i);
+        cc = d.a; h = vb; w = vc; break; }
+      case GR_ELU: case GR_RELU: case GR_LEAKYRELU: case GR_SIGMOID: case GR_TANH: case GR_DROPOUT: case GR_SPATIAL_DROPOUT: break;
+      default: return bad(GR_ERR_INVALID, "layer %d: unknown kind %d", i, d.kind);
+    }
+    if (h <= 0 || w <= 0) return bad(GR_ERR_INVALID, "layer %d: empty spatial extent", i);
+    return GR_OK;
+  };
+  int i = 0, r;
+  while (i < nl) {
+    Stage s; s.first = i;
+    while (i < nl && L[i].kind == GR_VIEW) { r = take(i); if (r) return r; ++i; }
+    if (i >= nl) { if (!pl.st.empty()) pl.st.back().last = nl - 1; break; }
+    s.inC = cc; s.inH = h; s.inW = w;
+    if (L[i].kind == GR_UPSAMPLE2) {
+      if (i + 1 >= nl || L[i + 1].kind != GR_CONV3) return bad(GR_ERR_UNSUPPORTED, "layer %d: UpSamplingNearest(2) is only fused in front of a 3x3 convolution", i);
+      r = take(i); if (r) return r;
+      s.up = true; ++i;
+    }
+    const int k = L[i].kind;
+    if (k == GR_CONV3 || k == GR_FULLCONV3 || k == GR_CONVK || k == GR_LINEAR) {
+      r = take(i); if (r) return r;
+      s.kind = k == GR_LINEAR ? ST_LINEAR : ST_CONV; s.fullconv = k == GR_FULLCONV3; s.ksz = k == GR_CONVK ? L[i].c : 3;
+      s.main_layer = i; s.Cin = L[i].a; s.Cout = L[i].b; s.H = h; s.W = w; s.w_off = wo; s.b_off = bo; ++i;
+    } else {
+      s.kind = ST_ELEM; s.Cin = s.Cout = cc; s.H = h; s.W = w;
+    }
+    int phase = -1;
+    while (i < nl) {
+      const gr_layer_desc& d = L[i];
+      int ph;
+      if (d.kind == GR_BN) ph = 0;
+      else if (is_act(d.kind)) ph = 1;
+      else if (d.kind == GR_DROPOUT || d.kind == GR_SPATIAL_DROPOUT) ph = s.pool ? 4 : 2;
+      else if (d.kind == GR_MAXPOOL2 || d.kind == GR_AVGPOOL2) ph = 3;
+      else break;
+      if (ph <= phase) break;
+      // nn.PReLU's slope gradient needs the activation's own input and gradOutput as tensors: the PReLU closes its stage (what
+      // follows it - dropout, pooling - is the next, element-wise stage), and behind a BatchNorm it opens a stage of its own
+      if (d.kind == GR_PRELU && s.has_bn) break;
+      r = take(i); if (r) return r;
+      phase = ph; s.has_post = true;
+      if (ph == 0) { s.has_bn = true; s.g_off = wo; s.be_off = bo; pl.bn_stage.push_back((int)pl.st.size()); }
+      else if (ph == 1) { s.act = d.kind; s.slope = d.p; if (d.kind == GR_PRELU) { s.slope_off = wo; ++i; break; } }
+      else if (ph == 3) { s.pool = true; s.avg = d.kind == GR_AVGPOOL2; }
+      else {
+        MaskSlot m; m.layer = i; m.kind = d.kind == GR_DROPOUT ? MASK_ELEM : MASK_SPATIAL; m.p = d.p; m.flags = d.flags;
+        m.C = cc; m.H = h; m.W = w;
+        if (ph == 2) s.m1 = (int)pl.masks.size(); else s.m2 = (int)pl.masks.size();
+        pl.masks.push_back(m);
+      }
+      ++i;
+    }
+    if (s.kind == ST_ELEM && !s.has_post) {      // layer i was not consumed: an unknown kind (every kind take() knows is placed above), and the walk must not stand still
+      r = take(i); if (r) return r;
+      return bad(GR_ERR_UNSUPPORTED, "layer %d: kind %d cannot start a stage", i, L[i].kind);
+    }
+    s.last = i - 1;
+    s.outC = cc; s.outH = h; s.outW = w;
+    pl.st.push_back(s);
+  }
+  pl.n_params = off; pl.outC = cc; pl.outH = h; pl.outW = w;
+  return GR_OK;
+}
+
+// parameters, optimiser state, per-stage constant-size buffers, scale slots, prep jobs: everything of a net that no batch size changes
+static int net_alloc(gr_net* n) {
+  gr_ctx* c = n->ctx;
+  DevMem& own = n->mem;
+  const size_t pb = sizeof(float) * (size_t)(n->n_params > 0 ? n->n_params : 1);
+  for (float** p : {&n->params, &n->grads, &n->adam_m, &n->adam_v}) HIPCHK(c, own.dev(p, pb));
+  for (float* p : {n->params, n->grads, n->adam_m, n->adam_v}) HIPCHK(c, hipMemsetAsync(p, 0, pb, c->stream));
+  for (auto& s : n->st) {
+    const int C = s.Cout;
+    if (s.has_bn) {
+      HIPCHK(c, own.dev(&s.run_mean, sizeof(float) * C)); HIPCHK(c, own.dev(&s.run_var, sizeof(float) * C));
+      std::vector<float> ones(C, 1.f);
+      HIPCHK(c, hipMemsetAsync(s.run_mean, 0, sizeof(float) * C, c->stream));
+      HIPCHK(c, hipMemcpy(s.run_var, ones.data(), sizeof(float) * C, hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, own.dev(&s.mean, sizeof(float) * C)); HIPCHK(c, own.dev(&s.invstd, sizeof(float) * C)); HIPCHK(c, own.dev(&s.coef, sizeof(float) * 2 * C));
+    HIPCHK(c, own.dev(&s.partials, sizeof(double) * 2 * STAT_SPLITS * C)); HIPCHK(c, own.dev(&s.partials_b, sizeof(double) * PB_SPLITS * C));
+    if (s.kind == ST_CONV && s.ksz == 3) {
+      // Forward reduces over Cin, backward-data over Cout - of a SpatialFullConvolution too, whose forward image is the backward-data image
+      // of the convolution wi -> wo its weight [Cin][Cout][3][3] is native to (Cout -> Cin), and whose backward-data image is that one's forward.
+      HIPCHK(c, own.dev(&s.wt_fwd, sizeof(float) * conv_weight_layout(s.Cin, s.Cout).elems()));
+      HIPCHK(c, own.dev(&s.wt_bwd, sizeof(float) * conv_weight_layout(s.Cout, s.Cin).elems()));
+      const int wi = s.fullconv ? s.Cout : s.Cin, wo = s.fullconv ? s.Cin : s.Cout;
+      HIPCHK(c, own.dev(&s.ws_fwd, conv_weight_split_bytes(wi, wo, s.fullconv))); HIPCHK(c, own.dev(&s.ws_bwd, conv_weight_split_bytes(wi, wo, !s.fullconv)));
+      if (!s.fullconv && s.up && conv_up2_supported(s.Cin, s.Cout, s.H, s.W)) HIPCHK(c, own.dev(&s.ws_up, conv_weight_up2_bytes(s.Cin, s.Cout)));
+      if (!s.up && !s.fullconv) HIPCHK(c, own.dev(&s.wl1, sizeof(float) * s.Cout));
+    }
+    if (s.kind == ST_CONV && s.ksz == 5 && !s.up && conv5x5_split_supported(s.Cin, s.Cout, s.H, s.W)) {
+      HIPCHK(c, own.dev(&s.ws_fwd, conv_weight_split_bytes(s.Cin, s.Cout, false, 5))); HIPCHK(c, own.dev(&s.ws_bwd, conv_weight_split_bytes(s.Cin, s.Cout, true, 5)));
+    }
+    const size_t ye = (size_t)vol3(s.Cout, s.H, s.W), ie = (size_t)vol3(s.inC, s.inH, s.inW);
+    if (ye > n->max_y) n->max_y = ye;
+    if (ie > n->max_in) n->max_in = ie;
+  }
+  const size_t ns = n->st.size();
+  HIPCHK(c, own.dev(&n->amax, sizeof(unsigned) * AMAX_WORDS * AMAX_GROUPS * ns));
+  HIPCHK(c, hipMemset(n->amax, 0, sizeof(unsigned) * AMAX_WORDS * AMAX_GROUPS * ns));
+  for (size_t si = 0; si < ns; ++si) {
+    Stage& s = n->st[si];
+    auto slot = [&](int grp) { return n->amax + AMAX_WORDS * (grp * ns + si); };
+    s.amax_x = slot(AG_X); s.amax_xt = slot(AG_XT); s.amax_y = slot(AG_Y); s.amax_kb = slot(AG_KB); s.amax_dy = slot(AG_DY); s.amax_dz = slot(AG_DZ); s.amax_w = slot(AG_W);
+  }
+  std::vector<PrepJob> jobs[3];        // [0] fp32 k-major images, [1] bf16x6, [2] f16x3 split images
+  for (auto& s : n->st) {
+    if (s.kind != ST_CONV || s.ksz != 3) continue;
+    const int wi = s.fullconv ? s.Cout : s.Cin, wo = s.fullconv ? s.Cin : s.Cout;       // (as above: a full convolution's forward is wi -> wo's backward-data)
+    for (int m = 0; m < 3; ++m) {
+      jobs[m].push_back(make_prep_job(s.w_off, m ? s.ws_fwd : (void*)s.wt_fwd, wi, wo, s.fullconv, m, m == 2 ? s.amax_w : nullptr));
+      jobs[m].push_back(make_prep_job(s.w_off, m ? s.ws_bwd : (void*)s.wt_bwd, wi, wo, !s.fullconv, m, m == 2 ? s.amax_w : nullptr));
+    }
+  }
+  for (auto& s : n->st)          // nn.Linear weights: only their maximum (f16x3 GEMM scales)
+    if (s.kind == ST_LINEAR && (int64_t)s.Cin * s.Cout >= (1 << 20)) jobs[2].push_back(make_prep_job(s.w_off, nullptr, s.Cin, s.Cout, false, 5, s.amax_w));
+  for (int m = 0; m < 3; ++m) {
+    n->njobs[m] = (int)jobs[m].size();
+    if (jobs[m].empty()) continue;
+    HIPCHK(c, own.dev(&n->jobs_dev[m], sizeof(PrepJob) * jobs[m].size()));
+    HIPCHK(c, hipMemcpy(n->jobs_dev[m], jobs[m].data(), sizeof(PrepJob) * jobs[m].size(), hipMemcpyHostToDevice));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return GR_OK;
 }
 
 extern "C" int gr_net_create(gr_ctx* c, const gr_layer_desc* L, int nl, int in_c, int in_h, int in_w, gr_net** out) {
   if (!c || !L || nl <= 0 || !out || in_c <= 0 || in_h <= 0 || in_w <= 0) return fail(c, GR_ERR_INVALID, "gr_net_create: bad arguments");
   *out = nullptr;
+  NetPlan pl; std::string msg;
+  int r = plan_net(L, nl, in_c, in_h, in_w, pl, msg);
+  if (r) return fail(c, r, "%s", msg.c_str());
   HIPCHK(c, hipSetDevice(c->device));
   gr_net* n = new gr_net();
+  static_cast<NetPlan&>(*n) = std::move(pl);
   n->ctx = c; n->layers.assign(L, L + nl); n->inC = in_c; n->inH = in_h; n->inW = in_w;
-  // pass 1: per-layer parameter offsets in getParameters() order + shape check
-  std::vector<int64_t> woff(nl, -1), boff(nl, -1);
-  {
-    int cc = in_c, h = in_h, w = in_w; int64_t off = 0;
-    for (int i = 0; i < nl; ++i) {
-      const gr_layer_desc& d = L[i];
-      switch (d.kind) {
-        case GR_CONV3: case GR_FULLCONV3:
-          if (d.a != cc) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: conv expects %d input planes, got %d", i, d.a, cc); }
-          woff[i] = off; off += (int64_t)d.a * d.b * 9; boff[i] = off; off += d.b; cc = d.b; break;
-        case GR_CONVK:
-          if (d.a != cc) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: conv expects %d input planes, got %d", i, d.a, cc); }
-          if (!convk_supported(d.c)) { delete n; return fail(c, GR_ERR_UNSUPPORTED, "layer %d: no kernel for a %dx%d convolution (3x3: GR_CONV3; 5x5: GR_CONVK)", i, d.c, d.c); }
-          woff[i] = off; off += (int64_t)d.a * d.b * d.c * d.c; boff[i] = off; off += d.b; cc = d.b; break;
-        case GR_PRELU: woff[i] = off; off += 1; break;          // nn.PReLU(): weight = Tensor(1)
-        case GR_LINEAR:
-          if (d.a != vol3(cc, h, w)) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: linear expects %d inputs, got %lld", i, d.a, (long long)vol3(cc, h, w)); }
-          woff[i] = off; off += (int64_t)d.a * d.b; boff[i] = off; off += d.b; cc = d.b; h = 1; w = 1; break;
-        case GR_BN:
-          if (d.a != cc) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: BN expects %d features, got %d", i, d.a, cc); }
-          woff[i] = off; off += cc; boff[i] = off; off += cc; break;
-        case GR_MAXPOOL2: case GR_AVGPOOL2: h /= 2; w /= 2; break;     // floor, as THNN: an odd last row / column is dropped
-        case GR_UPSAMPLE2: h *= 2; w *= 2; break;
-        case GR_VIEW: {
-          const int vb = d.b > 0 ? d.b : 1, vc = d.c > 0 ? d.c : 1;
-          if (vol3(d.a, vb, vc) != vol3(cc, h, w)) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: view size mismatch", i); }
-          cc = d.a; h = vb; w = vc; break; }
-        case GR_ELU: case GR_RELU: case GR_LEAKYRELU: case GR_SIGMOID: case GR_TANH: case GR_DROPOUT: case GR_SPATIAL_DROPOUT: break;
-        default: delete n; return fail(c, GR_ERR_INVALID, "layer %d: unknown kind %d", i, d.kind);
-      }
-      if (h <= 0 || w <= 0) { delete n; return fail(c, GR_ERR_INVALID, "layer %d: empty spatial extent", i); }
-    }
-    n->n_params = off; n->outC = cc; n->outH = h; n->outW = w;
-  }
-  // pass 2: stages
-  {
-    int cc = in_c, h = in_h, w = in_w, i = 0;
-    while (i < nl) {
-      Stage s; s.first = i;
-      while (i < nl && L[i].kind == GR_VIEW) { cc = L[i].a; h = L[i].b > 0 ? L[i].b : 1; w = L[i].c > 0 ? L[i].c : 1; ++i; }
-      if (i >= nl) { if (!n->st.empty()) n->st.back().last = nl - 1; break; }
-      s.inC = cc; s.inH = h; s.inW = w;
-      if (L[i].kind == GR_UPSAMPLE2) {
-        if (i + 1 >= nl || L[i + 1].kind != GR_CONV3) { gr_net_destroy(n); return fail(c, GR_ERR_UNSUPPORTED, "layer %d: UpSamplingNearest(2) is only fused in front of a 3x3 convolution", i); }
-        s.up = true; h *= 2; w *= 2; ++i;
-      }
-      const int k = L[i].kind;
-      if (k == GR_CONVK && s.up) { gr_net_destroy(n); return fail(c, GR_ERR_UNSUPPORTED, "layer %d: UpSamplingNearest(2) is only fused in front of a 3x3 convolution", i); }
-      if (k == GR_CONV3 || k == GR_FULLCONV3 || k == GR_CONVK) {
-        s.kind = ST_CONV; s.fullconv = k == GR_FULLCONV3; s.ksz = k == GR_CONVK ? L[i].c : 3; s.main_layer = i; s.Cin = L[i].a; s.Cout = L[i].b; s.H = h; s.W = w;
-        s.w_off = woff[i]; s.b_off = boff[i]; cc = s.Cout; ++i;
-      } else if (k == GR_LINEAR) {
-        s.kind = ST_LINEAR; s.main_layer = i; s.Cin = L[i].a; s.Cout = L[i].b; s.H = 1; s.W = 1;
-        s.w_off = woff[i]; s.b_off = boff[i]; cc = s.Cout; h = 1; w = 1; ++i;
-      } else {
-        s.kind = ST_ELEM; s.Cin = s.Cout = cc; s.H = h; s.W = w;
-      }
-      int phase = -1;
-      while (i < nl) {
-        const gr_layer_desc& d = L[i];
-        int ph;
-        if (d.kind == GR_BN) ph = 0;
-        else if (is_act(d.kind)) ph = 1;
-        else if (d.kind == GR_DROPOUT || d.kind == GR_SPATIAL_DROPOUT) ph = s.pool ? 4 : 2;
-        else if (d.kind == GR_MAXPOOL2 || d.kind == GR_AVGPOOL2) ph = 3;
-        else break;
-        if (ph <= phase) break;
-        // nn.PReLU's slope gradient needs the activation's own input and gradOutput as tensors: the PReLU closes its stage (what
-        // follows it - dropout, pooling - is the next, element-wise stage), and behind a BatchNorm it opens a stage of its own
-        if (d.kind == GR_PRELU && s.has_bn) break;
-        phase = ph; s.has_post = true;
-        if (ph == 0) { s.has_bn = true; s.g_off = woff[i]; s.be_off = boff[i]; n->bn_stage.push_back((int)n->st.size()); }
-        else if (ph == 1) { s.act = d.kind; s.slope = d.p; if (d.kind == GR_PRELU) { s.slope_off = woff[i]; ++i; break; } }
-        else if (ph == 3) { s.pool = true; s.avg = d.kind == GR_AVGPOOL2; h /= 2; w /= 2; }
-        else {
-          MaskSlot m; m.layer = i; m.kind = d.kind == GR_DROPOUT ? MASK_ELEM : MASK_SPATIAL; m.p = d.p; m.flags = d.flags;
-          m.C = cc; m.H = h; m.W = w;
-          if (ph == 2) s.m1 = (int)n->masks.size(); else s.m2 = (int)n->masks.size();
-          n->masks.push_back(m);
-        }
-        ++i;
-      }
-      s.last = i - 1;
-      s.outC = cc; s.outH = h; s.outW = w;
-      if (s.kind == ST_ELEM && !s.has_post) { gr_net_destroy(n); return fail(c, GR_ERR_UNSUPPORTED, "layer %d: kind %d cannot start a stage", i, L[i].kind); }
-      n->st.push_back(s);
-    }
-  }
-  // allocate parameters, optimiser state, per-stage constant-size buffers
-  const size_t pb = sizeof(float) * (size_t)(n->n_params > 0 ? n->n_params : 1);
-  if (hipMalloc((void**)&n->params, pb) || hipMalloc((void**)&n->grads, pb) || hipMalloc((void**)&n->adam_m, pb) || hipMalloc((void**)&n->adam_v, pb)) {
-    gr_net_destroy(n); return fail(c, GR_ERR_HIP, "parameter allocation failed");
-  }
-  (void)hipMemsetAsync(n->params, 0, pb, c->stream); (void)hipMemsetAsync(n->grads, 0, pb, c->stream);
-  (void)hipMemsetAsync(n->adam_m, 0, pb, c->stream); (void)hipMemsetAsync(n->adam_v, 0, pb, c->stream);
-  for (auto& s : n->st) {
-    const int C = s.Cout;
-    if (s.has_bn) {
-      if (hipMalloc((void**)&s.run_mean, sizeof(float) * C) || hipMalloc((void**)&s.run_var, sizeof(float) * C)) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-      std::vector<float> ones(C, 1.f);
-      (void)hipMemsetAsync(s.run_mean, 0, sizeof(float) * C, c->stream);
-      (void)hipMemcpy(s.run_var, ones.data(), sizeof(float) * C, hipMemcpyHostToDevice);
-    }
-    if (hipMalloc((void**)&s.mean, sizeof(float) * C) || hipMalloc((void**)&s.invstd, sizeof(float) * C) ||
-        hipMalloc((void**)&s.coef, sizeof(float) * 2 * C) || hipMalloc((void**)&s.partials, sizeof(double) * 2 * STAT_SPLITS * C) ||
-        hipMalloc((void**)&s.partials_b, sizeof(double) * PB_SPLITS * C)) {
-      gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed");
-    }
-    if (s.kind == ST_CONV && s.ksz == 3) {
-      // forward reduces over Cin; backward-data reduces over Cout.  (FullConvolution swaps the two roles.)
-      const ConvWeightLayout lf = s.fullconv ? conv_weight_layout(s.Cin, s.Cout) : conv_weight_layout(s.Cin, s.Cout);
-      const ConvWeightLayout lb = conv_weight_layout(s.Cout, s.Cin);
-      if (hipMalloc((void**)&s.wt_fwd, sizeof(float) * lf.elems()) || hipMalloc((void**)&s.wt_bwd, sizeof(float) * lb.elems())) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-      if (!s.fullconv && (hipMalloc(&s.ws_fwd, conv_weight_split_bytes(s.Cin, s.Cout, false)) || hipMalloc(&s.ws_bwd, conv_weight_split_bytes(s.Cin, s.Cout, true)))) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-      // SpatialFullConvolution(Cin -> Cout), weight [Cin][Cout][3][3] = the native weight of a convolution Cout -> Cin: its forward is
-      // that convolution's backward-data, its backward-data that convolution's forward
-      if (s.fullconv && (hipMalloc(&s.ws_fwd, conv_weight_split_bytes(s.Cout, s.Cin, true)) || hipMalloc(&s.ws_bwd, conv_weight_split_bytes(s.Cout, s.Cin, false)))) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-      if (!s.fullconv && s.up && conv_up2_supported(s.Cin, s.Cout, s.H, s.W) && hipMalloc(&s.ws_up, conv_weight_up2_bytes(s.Cin, s.Cout))) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-    }
-    if (s.kind == ST_CONV && s.ksz == 3 && !s.up && !s.fullconv && hipMalloc((void**)&s.wl1, sizeof(float) * s.Cout)) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-    if (s.kind == ST_CONV && s.ksz == 5 && !s.up && conv5x5_split_supported(s.Cin, s.Cout, s.H, s.W) &&
-        (hipMalloc(&s.ws_fwd, conv_weight_split_bytes(s.Cin, s.Cout, false, 5)) || hipMalloc(&s.ws_bwd, conv_weight_split_bytes(s.Cin, s.Cout, true, 5)))) { gr_net_destroy(n); return fail(c, GR_ERR_HIP, "alloc failed"); }
-    const size_t ye = (size_t)vol3(s.Cout, s.H, s.W), ie = (size_t)vol3(s.inC, s.inH, s.inW);
-    if (ye > n->max_y) n->max_y = ye;
-    if (ie > n->max_in) n->max_in = ie;
-  }
-  {
-    std::vector<PrepJob> jf, js, jh;
-    HIPCHK(c, hipMalloc((void**)&n->amax, sizeof(unsigned) * AMAX_WORDS * AMAX_GROUPS * n->st.size()));
-    HIPCHK(c, hipMemset(n->amax, 0, sizeof(unsigned) * AMAX_WORDS * AMAX_GROUPS * n->st.size()));
-    for (size_t si = 0, ns = n->st.size(); si < ns; ++si) {
-      Stage& s = n->st[si];
-      auto slot = [&](int grp) { return n->amax + AMAX_WORDS * (grp * ns + si); };
-      s.amax_x = slot(AG_X); s.amax_xt = slot(AG_XT); s.amax_y = slot(AG_Y); s.amax_kb = slot(AG_KB); s.amax_dy = slot(AG_DY); s.amax_dz = slot(AG_DZ); s.amax_w = slot(AG_W);
-    }
-    for (auto& s : n->st) {
-      if (s.kind != ST_CONV || s.ksz != 3) continue;
-      if (!s.fullconv) {
-        jf.push_back(make_prep_job(s.w_off, s.wt_fwd, s.Cin, s.Cout, false, 0));
-        jf.push_back(make_prep_job(s.w_off, s.wt_bwd, s.Cin, s.Cout, true, 0));
-        js.push_back(make_prep_job(s.w_off, s.ws_fwd, s.Cin, s.Cout, false, 1));
-        js.push_back(make_prep_job(s.w_off, s.ws_bwd, s.Cin, s.Cout, true, 1));
-        jh.push_back(make_prep_job(s.w_off, s.ws_fwd, s.Cin, s.Cout, false, 2, s.amax_w));
-        jh.push_back(make_prep_job(s.w_off, s.ws_bwd, s.Cin, s.Cout, true, 2, s.amax_w));
-      } else {
-        // SpatialFullConvolution weight is [Cin][Cout][3][3]: its forward is the backward-data of a (Cout -> Cin) conv
-        jf.push_back(make_prep_job(s.w_off, s.wt_fwd, s.Cout, s.Cin, true, 0));
-        jf.push_back(make_prep_job(s.w_off, s.wt_bwd, s.Cout, s.Cin, false, 0));
-        js.push_back(make_prep_job(s.w_off, s.ws_fwd, s.Cout, s.Cin, true, 1));
-        js.push_back(make_prep_job(s.w_off, s.ws_bwd, s.Cout, s.Cin, false, 1));
-        jh.push_back(make_prep_job(s.w_off, s.ws_fwd, s.Cout, s.Cin, true, 2, s.amax_w));
-        jh.push_back(make_prep_job(s.w_off, s.ws_bwd, s.Cout, s.Cin, false, 2, s.amax_w));
-      }
-    }
-    for (auto& s : n->st)          // nn.Linear weights: only their maximum (f16x3 GEMM scales)
-      if (s.kind == ST_LINEAR && (int64_t)s.Cin * s.Cout >= (1 << 20)) jh.push_back(make_prep_job(s.w_off, nullptr, s.Cin, s.Cout, false, 5, s.amax_w));
-    for (int m = 0; m < 3; ++m) {
-      std::vector<PrepJob>& v = m == 0 ? jf : (m == 1 ? js : jh);
-      n->njobs[m] = (int)v.size();
-      if (!v.empty()) {
-        HIPCHK(c, hipMalloc((void**)&n->jobs_dev[m], sizeof(PrepJob) * v.size()));
-        HIPCHK(c, hipMemcpy(n->jobs_dev[m], v.data(), sizeof(PrepJob) * v.size(), hipMemcpyHostToDevice));
-      }
-    }
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  r = net_alloc(n);
+  if (r) { gr_net_destroy(n); return r; }      // (*out stays null; the error text is net_alloc's)
   *out = n;
   return GR_OK;
 }
@@ -680,12 +661,12 @@ static MaskSlot* find_mask(gr_net* n, int layer) { for (auto& m : n->masks) if (
 static int64_t mask_elems(const MaskSlot& m, int B) { return m.kind == MASK_ELEM ? (int64_t)B * vol3(m.C, m.H, m.W) : (int64_t)B * m.C; }
 extern "C" int64_t gr_net_mask_size(gr_net* n, int layer, int B) { if (!n) return -1; MaskSlot* m = find_mask(n, layer); return m ? mask_elems(*m, B) : -1; }
 
-static int ensure_mask_bits(gr_net* n, MaskSlot& m, int64_t elems) { return grow_dev(n->ctx, &m.bits, m.bits_cap, sizeof(uint32_t) * ((size_t)((elems + 31) / 32) + 4), n->ctx->stream); }
+static int ensure_mask_bits(gr_net* n, MaskSlot& m, int64_t elems) { return grow_dev(n->ctx, n->mem, &m.bits, m.bits_cap, sizeof(uint32_t) * ((size_t)((elems + 31) / 32) + 4), n->ctx->stream); }
 extern "C" int gr_net_set_mask(gr_net* n, int layer, const uint8_t* keep, int64_t cnt) {
   if (!n || !keep || cnt <= 0) return GR_ERR_INVALID;
   gr_ctx* c = n->ctx; MaskSlot* m = find_mask(n, layer);
   if (!m) return fail(c, GR_ERR_INVALID, "layer %d is not a Dropout / SpatialDropout", layer);
-  int r = grow_dev(c, &n->mask_stage, n->mask_stage_cap, (size_t)cnt, c->stream); if (r) return r;
+  int r = grow_dev(c, n->mem, &n->mask_stage, n->mask_stage_cap, (size_t)cnt, c->stream); if (r) return r;
   r = ensure_mask_bits(n, *m, cnt); if (r) return r;
   HIPCHK(c, hipMemcpyAsync(n->mask_stage, keep, (size_t)cnt, hipMemcpyHostToDevice, c->stream));
   launch_pack_mask(n->mask_stage, m->bits, cnt, c->stream); LAUNCHCHK(c);
@@ -697,41 +678,38 @@ extern "C" int gr_net_get_mask(gr_net* n, int layer, uint8_t* keep, int64_t cnt)
   if (!n || !keep || cnt <= 0) return GR_ERR_INVALID;
   gr_ctx* c = n->ctx; MaskSlot* m = find_mask(n, layer);
   if (!m || !m->bits || cnt > m->n_last) return fail(c, GR_ERR_STATE, "no noise recorded for layer %d", layer);
-  int r = grow_dev(c, &n->mask_stage, n->mask_stage_cap, (size_t)cnt, c->stream); if (r) return r;
+  int r = grow_dev(c, n->mem, &n->mask_stage, n->mask_stage_cap, (size_t)cnt, c->stream); if (r) return r;
   launch_unpack_mask(m->bits, n->mask_stage, cnt, c->stream); LAUNCHCHK(c);
   HIPCHK(c, hipMemcpyAsync(keep, n->mask_stage, (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GR_OK;
 }
 
+// Sizes the per-batch buffers for B samples: drain, release them all, then allocate.  capB names a batch only while every buffer is in place:
+// after a failed allocation it is 0, so the next forward at any size comes back here and a backward is refused (lastB is 0 too).
 static int ensure_batch(gr_net* n, int B) {
   if (B <= n->capB) return GR_OK;
   gr_ctx* c = n->ctx;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int r = drain(c); if (r) return r;
+  n->batch.release();
+  n->capB = n->lastB = 0; n->last_out = nullptr; n->wg_pending[0] = n->wg_pending[1] = false;
+  // every pointer below ends up fresh or null: after the first failure the rest are nulled, not left on released memory
+  hipError_t e = hipSuccess;
+  auto get = [&](auto** p, size_t bytes) { *p = nullptr; if (e == hipSuccess) e = n->batch.dev(p, bytes); };
+  const size_t fB = sizeof(float) * (size_t)B;
   for (auto& s : n->st) {
-    if (s.kind != ST_ELEM) { (void)hipFree(s.y); s.y = nullptr; HIPCHK(c, hipMalloc((void**)&s.y, sizeof(float) * (size_t)B * vol3(s.Cout, s.H, s.W))); }
-    if (s.has_post) { (void)hipFree(s.out); s.out = nullptr; HIPCHK(c, hipMalloc((void**)&s.out, sizeof(float) * (size_t)B * vol3(s.outC, s.outH, s.outW))); }
-    if (s.kind == ST_CONV && s.has_bn && !s.up) {
-      (void)hipFree(s.stat_part); s.stat_part = nullptr;
-      HIPCHK(c, hipMalloc((void**)&s.stat_part, sizeof(double) * 2 * (size_t)s.Cout * conv_stat_tiles_max(B, s.H, s.W)));
-    }
-    if (s.pool && !s.avg) { (void)hipFree(s.pool_idx); s.pool_idx = nullptr; HIPCHK(c, hipMalloc((void**)&s.pool_idx, (size_t)B * vol3(s.outC, s.outH, s.outW))); }
-    if (s.kind == ST_CONV && s.ksz == 3 && !s.up && !s.fullconv && s.Cin % 16 == 0) {       // operand-ready input image (same bytes as the fp32 input)
-      (void)hipFree(s.x_p16); s.x_p16 = nullptr; s.x_p16_gen = 0;
-      HIPCHK(c, hipMalloc(&s.x_p16, sizeof(float) * (size_t)B * vol3(s.inC, s.inH, s.inW)));
-    }
+    s.x_p16_gen = s.kb_gen = 0; s.stat_tiles_last = 0;      // nothing reads a fresh buffer as written
+    s.y = s.out = nullptr;                                  // (where one of them is an alias, the forward sets it)
+    if (s.kind != ST_ELEM) get(&s.y, fB * vol3(s.Cout, s.H, s.W));
+    if (s.has_post) get(&s.out, fB * vol3(s.outC, s.outH, s.outW));
+    if (s.kind == ST_CONV && s.has_bn && !s.up) get(&s.stat_part, sizeof(double) * 2 * (size_t)s.Cout * conv_stat_tiles_max(B, s.H, s.W));
+    if (s.pool && !s.avg) get(&s.pool_idx, (size_t)B * vol3(s.outC, s.outH, s.outW));
+    if (s.kind == ST_CONV && s.ksz == 3 && !s.up && !s.fullconv && s.Cin % 16 == 0) get(&s.x_p16, fB * vol3(s.inC, s.inH, s.inW));      // operand-ready input image (same bytes as the fp32 input)
   }
-  (void)hipFree(n->dy_p16); n->dy_p16 = nullptr; (void)hipFree(n->dy_p16_b); n->dy_p16_b = nullptr; (void)hipFree(n->dy_buf_b); n->dy_buf_b = nullptr;
-  HIPCHK(c, hipMalloc(&n->dy_p16, sizeof(float) * (size_t)B * n->max_y));
-  HIPCHK(c, hipMalloc(&n->dy_p16_b, sizeof(float) * (size_t)B * n->max_y));
-  HIPCHK(c, hipMalloc((void**)&n->dy_buf_b, sizeof(float) * (size_t)B * n->max_y));
-  (void)hipFree(n->in_buf); (void)hipFree(n->gout_buf); (void)hipFree(n->dy_buf); (void)hipFree(n->g_buf[0]); (void)hipFree(n->g_buf[1]);
-  n->in_buf = n->gout_buf = n->dy_buf = n->g_buf[0] = n->g_buf[1] = nullptr;
-  HIPCHK(c, hipMalloc((void**)&n->in_buf, sizeof(float) * (size_t)B * vol3(n->inC, n->inH, n->inW)));
-  HIPCHK(c, hipMalloc((void**)&n->gout_buf, sizeof(float) * (size_t)B * vol3(n->outC, n->outH, n->outW)));
-  HIPCHK(c, hipMalloc((void**)&n->dy_buf, sizeof(float) * (size_t)B * n->max_y));
-  HIPCHK(c, hipMalloc((void**)&n->g_buf[0], sizeof(float) * (size_t)B * n->max_in));
-  HIPCHK(c, hipMalloc((void**)&n->g_buf[1], sizeof(float) * (size_t)B * n->max_in));
+  get(&n->dy_p16, fB * n->max_y); get(&n->dy_p16_b, fB * n->max_y); get(&n->dy_buf_b, fB * n->max_y);
+  get(&n->in_buf, fB * vol3(n->inC, n->inH, n->inW)); get(&n->gout_buf, fB * vol3(n->outC, n->outH, n->outW));
+  get(&n->dy_buf, fB * n->max_y); get(&n->g_buf[0], fB * n->max_in); get(&n->g_buf[1], fB * n->max_in);
+  HIPCHK(c, e);
   n->capB = B;
   return GR_OK;
 }
@@ -864,7 +842,7 @@ static int guard_scan(gr_ctx* c, const float* t, int B, int C, long HW, long sB,
   if (C < 2) return GR_OK;
   const size_t cb = sizeof(unsigned) * (size_t)C;
   if (cb > c->guard_chmax_cap) {      // (the scans leave the per-channel words zero: only a new buffer is cleared)
-    const int r = grow_dev(c, &c->guard_chmax, c->guard_chmax_cap, cb, c->stream); if (r) return r;
+    const int r = grow_dev(c, c->mem, &c->guard_chmax, c->guard_chmax_cap, cb, c->stream); if (r) return r;
     HIPCHK(c, hipMemsetAsync(c->guard_chmax, 0, cb, c->stream));
   }
   launch_channel_absmax(t, B, C, HW, sB, sC, c->guard_chmax, c->stream);
@@ -1403,7 +1381,7 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
   if (s.up) {
     // SpatialUpSamplingNearest(2) + SpatialConvolution backward (adversarial.lua:37-205 trains G through it): the weight
     // gradient needs the up-sampled input, the data gradient is folded back by summing each 2x2 block
-    r = grow_dev(c, n->up_tmp, n->up_cap, sizeof(float) * (size_t)B * vol3(s.Cin, s.H, s.W), c->stream, 2); if (r) return r;
+    r = grow_dev(c, n->mem, n->up_tmp, n->up_cap, sizeof(float) * (size_t)B * vol3(s.Cin, s.H, s.W), c->stream, 2); if (r) return r;
     launch_upsample2(x, n->up_tmp[0], B, s.Cin, s.H, s.W, c->stream);
     r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
     if (f16 && conv_wgrad_is_split(2, s.Cin, s.W)) input_absmax(n, s, x, B, false);
@@ -1428,7 +1406,7 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
   // stage's data gradient and the memory-bound pipeline kernels of the stages after it (they leave the matrix pipe idle).
   // Its own workspace; the dy pair it reads is not rewritten before ev_wgrad_done[dk] (waited for two stages on).
   const bool side_want = c->side_wgrad < 0 ? (int64_t)B * vol3(s.Cout, s.H, s.W) >= ((int64_t)1 << 26) : c->side_wgrad != 0;
-  const bool side = side_want && c->side_stream != nullptr && gr::g_ktimer == nullptr;
+  const bool side = side_want && gr::g_ktimer == nullptr;
   hipStream_t ws_ = side ? c->side_stream : c->stream;
   void* wsp_ = c->ws;
   if (side) {
@@ -1810,7 +1788,7 @@ extern "C" int gr_train_r_step(gr_net* g, gr_net* rn, const float* noise_dev, in
     // fc1's BatchNorm / activation / Dropout, fc2, the criterion (:147,150) and their backward down to fc1's dy: one launch (elem.hip, head_fwd_bwd_kernel)
     if (!c->head_bar) {
       unsigned* bar = nullptr; double* part = nullptr;           // both or neither: a half-made pair would launch the kernel with a null loss_part next time
-      if (hipMalloc((void**)&bar, 256) != hipSuccess || hipMalloc((void**)&part, sizeof(double) * 512) != hipSuccess) { if (bar) (void)hipFree(bar); return fail(c, GR_ERR_HIP, "head kernel: allocation failed"); }
+      if (c->mem.dev(&bar, 256) != hipSuccess || c->mem.dev(&part, sizeof(double) * 512) != hipSuccess) { c->mem.drop(bar); return fail(c, GR_ERR_HIP, "head kernel: allocation failed"); }
       c->head_bar = bar; c->head_loss_part = part;
       HIPCHK(c, hipMemsetAsync(c->head_bar, 0, 256, c->stream));
       c->head_bar_count = 0;

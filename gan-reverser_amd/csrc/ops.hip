@@ -26,21 +26,7 @@ struct Staging {
   // a host array that is the caller's own again (or dies) when the call returns
   template <class T> int upload_now(Region<T> r, const T* host) { TRY(upload(r, host)); return finish(); }
 };
-// A hipMalloc temporary of one call.  It goes on every exit path, once the work enqueued on the context's stream has finished.
-struct DevTemp {
-  gr_ctx* c; void* p = nullptr;
-  explicit DevTemp(gr_ctx* ctx) : c(ctx) {}
-  DevTemp(const DevTemp&) = delete;        // (one owner)
-  ~DevTemp() { if (p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); } }
-  int alloc(size_t nbytes) { HIPCHK(c, hipMalloc(&p, nbytes)); return GR_OK; }
-  template <class T> T* as() const { return static_cast<T*>(p); }
-};
-struct EventTemp {     // a HIP event of one call (a failed create shows in the first call that takes the event)
-  hipEvent_t e = nullptr;
-  EventTemp() { (void)hipEventCreate(&e); }
-  EventTemp(const EventTemp&) = delete;
-  ~EventTemp() { if (e) (void)hipEventDestroy(e); }
-};
+// (a call's hipMalloc temporaries live in a DevMem tmp(c->stream), ctx.h: they go on every exit path, once the work enqueued on the stream has finished)
 
 // a criterion on host tensors: launch(x, t, loss_dev, grad) runs on staged copies
 template <class Launch> static int criterion_host(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss, float* grad, Launch launch) {
@@ -186,9 +172,9 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
   long* d_q = (long*)base; long* d_idx = d_q + Q; float* d_sc = (float*)(d_idx + (size_t)Q * k); unsigned* d_status = (unsigned*)(d_sc + (size_t)Q * k);
   const size_t res_bytes = sizeof(long) * (size_t)Q * k + sizeof(float) * (size_t)Q * k + sizeof(unsigned);
   if (res_bytes > c->pin_bytes) {
-    if (c->pin) (void)hipHostFree(c->pin);
+    c->mem.drop(c->pin);
     c->pin = nullptr; c->pin_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->pin, res_bytes * 2));
+    HIPCHK(c, c->mem.pinned(&c->pin, res_bytes * 2));
     c->pin_bytes = res_bytes * 2;
   }
   // A handful of needles (the reference's five): their rows travel in the kernel arguments and the kernels write idx | scores | status
@@ -199,13 +185,13 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
     char* pd = static_cast<char*>(pin_dev);
     long* p_idx = reinterpret_cast<long*>(pd); float* p_sc = reinterpret_cast<float*>(pd + sizeof(long) * (size_t)Q * k);
     unsigned* p_status = reinterpret_cast<unsigned*>(pd + res_bytes - sizeof(unsigned));
-    if (!c->pin_done) { HIPCHK(c, hipHostMalloc((void**)&c->pin_done, 64)); memset(c->pin_done, 0, 64); }
+    if (!c->pin_done) { HIPCHK(c, c->mem.pinned(&c->pin_done, 64)); memset(c->pin_done, 0, 64); }
     void* done_dev = nullptr;
     HIPCHK(c, hipHostGetDevicePointer(&done_dev, c->pin_done, 0));
     if (++c->search_seq == 0u) c->search_seq = 1u;                                  // never 0: a fresh block reads 0
     const unsigned seq = c->search_seq;
     if (!c->search_state) {       // the sample launch's arrival counter and histogram: zero now, left zero by every search
-      HIPCHK(c, hipMalloc((void**)&c->search_state, sizeof(unsigned) * SEARCH_STATE_WORDS));
+      HIPCHK(c, c->mem.dev(&c->search_state, sizeof(unsigned) * SEARCH_STATE_WORDS));
       HIPCHK(c, hipMemsetAsync(c->search_state, 0, sizeof(unsigned) * SEARCH_STATE_WORDS, c->stream));
     }
     const int lr = launch_cosine_topk(emb, N, d, d_q, Q, k, p_idx, p_sc, accf, c->ws, c->stream, p_status, 0, qrows, c->search_state,
@@ -260,10 +246,10 @@ extern "C" int gr_cosine_topk_host(gr_ctx* c, const float* emb, int64_t N, int d
                                    int64_t* idx_out, float* score_out, int accf) {
   if (!c || !emb || N <= 0 || d <= 0) return GR_ERR_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  DevTemp dev(c);
-  TRY(dev.alloc(sizeof(float) * (size_t)N * d));
-  if (hipMemcpyAsync(dev.p, emb, sizeof(float) * (size_t)N * d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, GR_ERR_HIP, "upload failed");
-  return gr_cosine_topk_dev(c, dev.as<float>(), N, d, qrows, Q, k, idx_out, score_out, accf);
+  DevMem tmp(c->stream); float* dev = nullptr;
+  HIPCHK(c, tmp.dev(&dev, sizeof(float) * (size_t)N * d));
+  if (hipMemcpyAsync(dev, emb, sizeof(float) * (size_t)N * d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, GR_ERR_HIP, "upload failed");
+  return gr_cosine_topk_dev(c, dev, N, d, qrows, Q, k, idx_out, score_out, accf);
 }
 extern "C" int gr_cosine_similarity_host(gr_ctx* c, const float* a, const float* b, int d, float* out) {
   if (!c || !a || !b || !out || d <= 0) return GR_ERR_INVALID;
@@ -460,59 +446,59 @@ extern "C" int gr_l2_nearest_host(gr_ctx* c, const float* table, int64_t n, int6
   TRY(l2_nearest_check(c, table, n, d, queries, Q, k, idx_out, dist_out));
   HIPCHK(c, hipSetDevice(c->device));
   const size_t tb = sizeof(float) * (size_t)n * d, qb = sizeof(float) * (size_t)Q * d;
-  DevTemp dt(c), dq(c);
-  TRY(dt.alloc(tb)); TRY(dq.alloc(qb));
-  if (hipMemcpyAsync(dt.p, table, tb, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+  DevMem tmp(c->stream); float *dt = nullptr, *dq = nullptr;
+  HIPCHK(c, tmp.dev(&dt, tb)); HIPCHK(c, tmp.dev(&dq, qb));
+  if (hipMemcpyAsync(dt, table, tb, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemcpyAsync(dq, queries, qb, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     return fail(c, GR_ERR_HIP, "upload failed");
-  return gr_l2_nearest_dev(c, dt.as<float>(), n, d, dq.as<float>(), Q, k, idx_out, dist_out);
+  return gr_l2_nearest_dev(c, dt, n, d, dq, Q, k, idx_out, dist_out);
 }
 
 // ------------------------------------------------------------------ single-kernel entry points
-static int with_prepped(gr_ctx* c, const float* w, int cin, int cout, bool bwd, DevTemp& wt) {
+static int with_prepped(gr_ctx* c, const float* w, int cin, int cout, bool bwd, DevMem& tmp, float** wt) {
   const ConvWeightLayout L = bwd ? conv_weight_layout(cout, cin) : conv_weight_layout(cin, cout);
-  TRY(wt.alloc(sizeof(float) * L.elems()));
-  launch_conv_weight_prep(w, wt.as<float>(), cin, cout, bwd, c->stream);
+  HIPCHK(c, tmp.dev(wt, sizeof(float) * L.elems()));
+  launch_conv_weight_prep(w, *wt, cin, cout, bwd, c->stream);
   LAUNCHCHK(c);
   return GR_OK;
 }
 // f16x3: the weight maximum goes to c->amax[2]
-static int conv_split_once(gr_ctx* c, const float* w, int cin, int cout, bool bwd, DevTemp& ws) {
-  TRY(ws.alloc(conv_weight_split_bytes(cin, cout, bwd)));
-  launch_conv_weight_split(w, ws.p, cin, cout, bwd, c->stream, c->conv_mode == 2 ? 2 : 3, c->amax + 2 * AMAX_WORDS);
+static int conv_split_once(gr_ctx* c, const float* w, int cin, int cout, bool bwd, DevMem& tmp, void** ws) {
+  HIPCHK(c, tmp.dev(ws, conv_weight_split_bytes(cin, cout, bwd)));
+  launch_conv_weight_split(w, *ws, cin, cout, bwd, c->stream, c->conv_mode == 2 ? 2 : 3, c->amax + 2 * AMAX_WORDS);
   LAUNCHCHK(c);
   return GR_OK;
 }
-// how the gr_conv3_* calls end: the launch status is read first, then their weight image goes (DevTemp waits for the stream)
+// how the gr_conv3_* calls end: the launch status is read first, then their weight image goes (tmp waits for the stream)
 static int conv_launched(gr_ctx* c) { hipError_t e = hipGetLastError(); return e == hipSuccess ? GR_OK : fail(c, GR_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e)); }
 extern "C" int gr_conv3_forward_dev(gr_ctx* c, const float* in, const float* w, const float* bias, float* out, int B, int cin, int cout, int h, int wd, int up) {
   if (!c || !in || !w || !out) return GR_ERR_INVALID;
-  DevTemp wt(c);
+  DevMem tmp(c->stream); void* wt = nullptr; float* wt32 = nullptr;
   if (c->conv_mode == 2 && up && conv_up2_supported(cin, cout, h, wd)) {
     // the fused up-sampling layer as four 2x2 convolutions (the path a net takes for such a stage in f16x3 mode)
-    TRY(wt.alloc(conv_weight_up2_bytes(cin, cout)));
-    launch_conv_weight_up2_split(w, wt.p, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
+    HIPCHK(c, tmp.dev(&wt, conv_weight_up2_bytes(cin, cout)));
+    launch_conv_weight_up2_split(w, wt, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
     launch_absmax(in, (long)B * cin * (h / 2) * (wd / 2), c->amax, c->stream);
-    launch_conv3x3_up2_f16x3(in, wt.p, bias, out, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr);
+    launch_conv3x3_up2_f16x3(in, wt, bias, out, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr);
   } else if (c->conv_mode >= 1 && cout > 4) {
-    TRY(conv_split_once(c, w, cin, cout, false, wt));
+    TRY(conv_split_once(c, w, cin, cout, false, tmp, &wt));
     if (c->conv_mode == 2) launch_absmax(in, (long)B * cin * (up ? (h / 2) * (wd / 2) : h * wd), c->amax, c->stream);
-    launch_conv3x3_split(in, wt.p, bias, out, B, cin, cout, h, wd, up != 0, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax, c->amax + 2 * AMAX_WORDS);
+    launch_conv3x3_split(in, wt, bias, out, B, cin, cout, h, wd, up != 0, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax, c->amax + 2 * AMAX_WORDS);
   } else {
-    TRY(with_prepped(c, w, cin, cout, false, wt));
-    launch_conv3x3(in, wt.as<float>(), bias, out, B, cin, cout, h, wd, up != 0, c->stream, w);
+    TRY(with_prepped(c, w, cin, cout, false, tmp, &wt32));
+    launch_conv3x3(in, wt32, bias, out, B, cin, cout, h, wd, up != 0, c->stream, w);
   }
   return conv_launched(c);
 }
 extern "C" int gr_conv3_backward_data_dev(gr_ctx* c, const float* gout, const float* w, float* gin, int B, int cin, int cout, int h, int wd) {
   if (!c || !gout || !w || !gin) return GR_ERR_INVALID;
-  DevTemp wt(c);
+  DevMem tmp(c->stream); void* wt = nullptr; float* wt32 = nullptr;
   if (c->conv_mode >= 1 && cin > 4) {
-    TRY(conv_split_once(c, w, cin, cout, true, wt));
+    TRY(conv_split_once(c, w, cin, cout, true, tmp, &wt));
     if (c->conv_mode == 2) launch_absmax(gout, (long)B * cout * h * wd, c->amax + AMAX_WORDS, c->stream);
-    launch_conv3x3_split(gout, wt.p, nullptr, gin, B, cout, cin, h, wd, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
+    launch_conv3x3_split(gout, wt, nullptr, gin, B, cout, cin, h, wd, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, c->amax + AMAX_WORDS, c->amax + 2 * AMAX_WORDS);
   } else {
-    TRY(with_prepped(c, w, cin, cout, true, wt));
-    launch_conv3x3(gout, wt.as<float>(), nullptr, gin, B, cout, cin, h, wd, false, c->stream);
+    TRY(with_prepped(c, w, cin, cout, true, tmp, &wt32));
+    launch_conv3x3(gout, wt32, nullptr, gin, B, cout, cin, h, wd, false, c->stream);
   }
   return conv_launched(c);
 }
@@ -539,12 +525,12 @@ extern "C" int gr_bench_mfma_loop(gr_ctx* c, int shape, int launches, float* tfl
   const int iters = 200;
   for (int i = 0; i < 300; ++i) launch_mfma_loop(shape, c->ws, iters, c->stream);     // ~0.35 s of warm-up under load
   LAUNCHCHK(c);
-  EventTemp e0, e1;
-  HIPCHK(c, hipEventRecord(e0.e, c->stream));
+  Event e0, e1; HIPCHK(c, e0.create()); HIPCHK(c, e1.create());
+  HIPCHK(c, hipEventRecord(e0, c->stream));
   for (int i = 0; i < launches; ++i) launch_mfma_loop(shape, c->ws, iters, c->stream);
-  HIPCHK(c, hipEventRecord(e1.e, c->stream));
-  HIPCHK(c, hipEventSynchronize(e1.e));
-  float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e0.e, e1.e));
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipEventSynchronize(e1));
+  float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
   *tflops_out = (float)(mfma_loop_flops(iters) * launches / (ms * 1e-3) / 1e12 / 3.0);
   return GR_OK;
 }
@@ -552,30 +538,29 @@ extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, in
   if (!c || iters < 1 || !avg_ms) return GR_ERR_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t nin = (size_t)B * cin * h * wd, nout = (size_t)B * cout * h * wd, nw = (size_t)cin * cout * 9;
-  DevTemp dx(c), dy(c), dw(c), dgw(c), dwt(c), dwsp(c), dwup(c), dxp16(c), dstatp(c);
-  TRY(dx.alloc(sizeof(float) * nin)); TRY(dy.alloc(sizeof(float) * nout)); TRY(dw.alloc(sizeof(float) * nw)); TRY(dgw.alloc(sizeof(float) * nw));
-  float *x = dx.as<float>(), *y = dy.as<float>(), *w = dw.as<float>(), *gw = dgw.as<float>();
+  DevMem tmp(c->stream);
+  float *x = nullptr, *y = nullptr, *w = nullptr, *gw = nullptr, *wt = nullptr; void *wsp = nullptr, *wup = nullptr, *xp16 = nullptr; double* statp = nullptr;
+  HIPCHK(c, tmp.dev(&x, sizeof(float) * nin)); HIPCHK(c, tmp.dev(&y, sizeof(float) * nout)); HIPCHK(c, tmp.dev(&w, sizeof(float) * nw)); HIPCHK(c, tmp.dev(&gw, sizeof(float) * nw));
   launch_fill_normal(x, (long)nin, 11, c->stream); launch_fill_normal(y, (long)nout, 12, c->stream); launch_fill_normal(w, (long)nw, 13, c->stream);
   (void)hipMemsetAsync(gw, 0, sizeof(float) * nw, c->stream);
-  TRY(with_prepped(c, w, cin, cout, which == 1, dwt));
+  TRY(with_prepped(c, w, cin, cout, which == 1, tmp, &wt));
   const bool split = c->conv_mode >= 1 && which != 2 && (which == 0 ? cout > 4 : cin > 4);
   const int nterm = c->conv_mode == 2 ? 2 : 3;
-  if (split) TRY(conv_split_once(c, w, cin, cout, which == 1, dwsp));      // (which 4 and 5 launch on this image too: forward orientation, same term count)
+  if (split) TRY(conv_split_once(c, w, cin, cout, which == 1, tmp, &wsp));      // (which 4 and 5 launch on this image too: forward orientation, same term count)
   TRY(ensure_ws(c, conv_wgrad_workspace_bytes(B, cin, cout, h, wd, c->conv_mode)));
   // f16x3 scales: taken once outside the timed loop (in a net the producing kernel tracks them)
   if (c->conv_mode == 2) { launch_absmax(x, (long)nin, c->amax, c->stream); launch_absmax(y, (long)nout, c->amax + AMAX_WORDS, c->stream); }
   if (which == 3) {      // fused up-sampling layer: x is the source plane [B, cin, h/2, wd/2] (a quarter of the buffer), y the output
     if (c->conv_mode != 2 || !conv_up2_supported(cin, cout, h, wd)) return fail(c, GR_ERR_UNSUPPORTED, "up2 bench needs f16x3 mode and a supported shape");
-    TRY(dwup.alloc(conv_weight_up2_bytes(cin, cout)));
-    launch_conv_weight_up2_split(w, dwup.p, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
+    HIPCHK(c, tmp.dev(&wup, conv_weight_up2_bytes(cin, cout)));
+    launch_conv_weight_up2_split(w, wup, cin, cout, c->stream, c->amax + 2 * AMAX_WORDS, true);
   }
   if (which == 4 || which == 5) {   // operand-ready forward (5: with the BatchNorm statistics epilogue): x converted once outside the loop
     if (c->conv_mode != 2 || !conv_p16_supported(B, cin, cout, h, wd)) return fail(c, GR_ERR_UNSUPPORTED, "p16 bench needs f16x3 mode and a supported shape");
-    TRY(dxp16.alloc(sizeof(float) * nin));
-    TRY(dstatp.alloc(sizeof(double) * 2 * cout * conv_stat_tiles_max(B, h, wd)));
-    launch_to_p16(x, dxp16.p, B, cin, h * wd, c->amax, c->stream);
+    HIPCHK(c, tmp.dev(&xp16, sizeof(float) * nin));
+    HIPCHK(c, tmp.dev(&statp, sizeof(double) * 2 * cout * conv_stat_tiles_max(B, h, wd)));
+    launch_to_p16(x, xp16, B, cin, h * wd, c->amax, c->stream);
   }
-  float* wt = dwt.as<float>(); void *wsp = dwsp.p, *wup = dwup.p, *xp16 = dxp16.p; double* statp = dstatp.as<double>();
   auto run = [&]() {
     if (which == 4 || which == 5) { int st = 0; launch_conv3x3_p16(xp16, wsp, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr, which == 5 ? statp : nullptr, which == 5 ? &st : nullptr); return; }
     if (which == 3) { launch_conv3x3_up2_f16x3(x, wup, nullptr, y, B, cin, cout, h, wd, c->stream, nullptr, c->amax, c->amax + 2 * AMAX_WORDS, nullptr); return; }
@@ -586,12 +571,12 @@ extern "C" int gr_bench_conv3(gr_ctx* c, int which, int B, int cin, int cout, in
     else launch_conv3x3_wgrad(x, y, gw, c->ws, B, cin, cout, h, wd, c->stream, c->conv_mode, c->amax, c->amax + AMAX_WORDS);
   };
   for (int i = 0; i < 3; ++i) run();
-  EventTemp e0, e1;
-  (void)hipEventRecord(e0.e, c->stream);
+  Event e0, e1; HIPCHK(c, e0.create()); HIPCHK(c, e1.create());
+  (void)hipEventRecord(e0, c->stream);
   for (int i = 0; i < iters; ++i) run();
-  (void)hipEventRecord(e1.e, c->stream);
-  HIPCHK(c, hipEventSynchronize(e1.e));
-  float ms = 0; (void)hipEventElapsedTime(&ms, e0.e, e1.e);
+  (void)hipEventRecord(e1, c->stream);
+  HIPCHK(c, hipEventSynchronize(e1));
+  float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
   *avg_ms = ms / iters;
   LAUNCHCHK(c);
   return GR_OK;
