@@ -237,9 +237,10 @@ __global__ void convk_wgrad_reduce_kernel(const float* __restrict__ part, float*
   gw[e] += s;
 }
 
-bool convk_supported(int K) { return K == 5; }       // the one window size models.lua instantiates besides 3
+bool convk_supported(int K) { return K == 5 || K == 1; }       // the window sizes models.lua instantiates besides 3 (K = 1: conv1x1.hip)
 static int convk_splits(int B) { return B < 64 ? B : 64; }       // x 8 input-channel groups at Cin = 128: two workgroups per CU
 size_t convk_workspace_bytes(int B, int Cin, int Cout, int K) {
+  if (K == 1) return conv1x1_workspace_bytes(B, Cin, Cout);
   size_t img = convk_image_floats(Cin, Cout, K), img_b = convk_image_floats(Cout, Cin, K);
   size_t parts = (size_t)convk_splits(B) * Cin * Cout * K * K;
   size_t m = img > img_b ? img : img_b;
@@ -279,14 +280,17 @@ static void convk_direct(const float* in, const float* w, const float* bias, flo
 
 // out[b,o,y,x] = bias[o] + sum w[o,i,ky,kx] in[b,i,y+ky-P,x+kx-P]        (ws: convk_workspace_bytes)
 void launch_convk_forward(const float* in, const float* w, const float* bias, float* out, void* ws, int B, int Cin, int Cout, int H, int W, int K, hipStream_t s) {
-  if (K == 5) convk_direct<5>(in, w, bias, out, ws, B, Cin, Cout, Cin, Cout, H, W, false, s);
+  if (K == 1) launch_conv1x1_forward(in, w, bias, out, B, Cin, Cout, H * W, s);
+  else if (K == 5) convk_direct<5>(in, w, bias, out, ws, B, Cin, Cout, Cin, Cout, H, W, false, s);
 }
 // gin[b,i,y,x] = sum w[o,i,ky,kx] gout[b,o,y-ky+P,x-kx+P]
 void launch_convk_backward_data(const float* gout, const float* w, float* gin, void* ws, int B, int Cin, int Cout, int H, int W, int K, hipStream_t s) {
-  if (K == 5) convk_direct<5>(gout, w, nullptr, gin, ws, B, Cout, Cin, Cin, Cout, H, W, true, s);
+  if (K == 1) launch_conv1x1_backward_data(gout, w, gin, B, Cin, Cout, H * W, s);
+  else if (K == 5) convk_direct<5>(gout, w, nullptr, gin, ws, B, Cout, Cin, Cin, Cout, H, W, true, s);
 }
 // gw[o,i,ky,kx] += sum_{b,y,x} gout[b,o,y,x] in[b,i,y+ky-P,x+kx-P]
 void launch_convk_backward_weight(const float* in, const float* gout, float* gw, void* ws, int B, int Cin, int Cout, int H, int W, int K, hipStream_t s) {
+  if (K == 1) { launch_conv1x1_backward_weight(in, gout, gw, ws, B, Cin, Cout, H * W, s); return; }
   float* part = static_cast<float*>(ws);
   const int splits = convk_splits(B);
   dim3 grid((Cin + KW_CI - 1) / KW_CI, (Cout + KW_CO - 1) / KW_CO, splits);

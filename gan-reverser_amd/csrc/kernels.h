@@ -335,6 +335,11 @@ size_t convk_workspace_bytes(int B, int Cin, int Cout, int K);
 void launch_convk_forward(const float* in, const float* w /*[Cout][Cin][K][K]*/, const float* bias, float* out, void* ws, int B, int Cin, int Cout, int H, int W, int K, hipStream_t s);
 void launch_convk_backward_data(const float* gout, const float* w, float* gin, void* ws, int B, int Cin, int Cout, int H, int W, int K, hipStream_t s);
 void launch_convk_backward_weight(const float* in, const float* gout, float* gw /*+=*/, void* ws, int B, int Cin, int Cout, int H, int W, int K, hipStream_t s);
+// the 1 x 1 window (conv1x1.hip): batched GEMMs over the pixels of the whole batch on the fp32 MFMA; launch_convk_* dispatch K == 1 here
+size_t conv1x1_workspace_bytes(int B, int Cin, int Cout);
+void launch_conv1x1_forward(const float* in, const float* w /*[Cout][Cin]*/, const float* bias, float* out, int B, int Cin, int Cout, int HW, hipStream_t s);
+void launch_conv1x1_backward_data(const float* gout, const float* w, float* gin, int B, int Cin, int Cout, int HW, hipStream_t s);
+void launch_conv1x1_backward_weight(const float* in, const float* gout, float* gw /*+=*/, void* ws, int B, int Cin, int Cout, int HW, hipStream_t s);
 size_t prelu_grad_workspace_bytes();
 void launch_prelu_grad(const float* g, const float* z, long n, double* part, float* gslope /*+=*/, hipStream_t s);
 

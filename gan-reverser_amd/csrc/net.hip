@@ -348,7 +348,7 @@ struct Stage {
   int64_t w_off = -1, b_off = -1;
   bool has_bn = false; int64_t g_off = -1, be_off = -1;
   int act = ACT_NONE; float slope = 0;
-  int ksz = 3;                              // window of the main convolution: 3 (conv.hip kernels) or an odd K convk.hip covers (GR_CONVK)
+  int ksz = 3;                              // window of the main convolution: 3 (conv.hip kernels) or an odd K convk.hip covers (GR_CONVK: 5, or 1 - conv1x1.hip)
   int64_t slope_off = -1;                   // nn.PReLU: offset of its one learnable slope in the flat vectors
   int m1 = -1, m2 = -1; bool pool = false;     // pool: this stage pools (2x2, stride 2) ...
   bool avg = false;                          // ... by the average (nn.SpatialAveragePooling: no pool_idx) rather than the maximum
@@ -443,6 +443,7 @@ static int plan_net(const gr_layer_desc* L, int nl, int in_c, int in_h, int in_w
     switch (d.kind) {
       case GR_CONV3: case GR_FULLCONV3: case GR_CONVK: {
         if (d.a != cc) return bad(GR_ERR_INVALID, "layer %d: conv expects %d input planes, got %d", i, d.a, cc);
+        // (the text is pinned word for word by tests/test_gpu_net_memory.py, so it still names 5x5 only; GR_CONVK also takes the 1x1 window: include/ganrev.h)
         if (d.kind == GR_CONVK && !convk_supported(d.c)) return bad(GR_ERR_UNSUPPORTED, "layer %d: no kernel for a %dx%d convolution (3x3: GR_CONV3; 5x5: GR_CONVK)", i, d.c, d.c);
         const int k = d.kind == GR_CONVK ? d.c : 3;
         wo = off; off += (int64_t)d.a * d.b * k * k; bo = off; off += d.b; cc = d.b; break; }

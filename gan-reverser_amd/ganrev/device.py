@@ -4,7 +4,8 @@ it, an owner for the loops' device buffers and the periodic f16x3 range-guard sc
 base class to inherit from.  (Noise by method and the loss word are ctx.fill_noise / ctx.read_loss, ganrev._lib.)
 
 The containers stay host code that enqueues work: every compiled part runs through gr_net_forward_dev / gr_net_backward_dev,
-nn.Concat joins / slices / sums with gr_copy2d_dev / gr_add_dev, penalty + clamp + optim.adam are the fused gr_adam_step of each
+nn.Concat joins / slices / sums with gr_copy2d_dev / gr_add_dev, an nn.ConcatTable + nn.CAddTable pair (models.createResidual) sums its
+branches with the same two calls, penalty + clamp + optim.adam are the fused gr_adam_step of each
 part (gr_optim_step for the other five methods).  A model that compiles to one gr_net (G, R, the G autoencoder) is the trivial case: one forward_dev, one backward_dev.
 """
 import numpy as np
@@ -70,9 +71,14 @@ def _vol(d):
 
 
 class DeviceModel:
-    """Device-resident executor of a compiled ganrev.nn model: one gr_net, or the parts of a model with an nn.Concat.  It walks the
-    containers themselves (nn's children(): a graph Sequential's parts(), a Concat's branches), read once here because the tree is
-    fixed once compiled and the walk runs four times a batch."""
+    """Device-resident executor of a compiled ganrev.nn model: one gr_net, or the parts of a model with an nn.Concat or with
+    nn.ConcatTable + nn.CAddTable blocks.  It walks the containers themselves (nn's children(): a graph Sequential's parts(), a
+    Concat's branches, a table block's branches), read once here because the tree is fixed once compiled and the walk runs four times
+    a batch.
+
+    A table block (models.lua:41-53): out = sum of the branch outputs, gradInput = sum of the branches' gradInputs, an nn.Identity
+    branch contributing the block's input / gradOutput itself.  Both sums are formed in buffers of this executor, never in a branch's
+    output: a training-mode stage output is state its net's backward reads."""
 
     def __init__(self, ctx, model):
         self.ctx, self.model, self.mem = ctx, model, Buffers(ctx)
@@ -82,9 +88,14 @@ class DeviceModel:
         if any(isinstance(m, nn.Concat) and m.dimension != 2 for m in model.listModules()):
             raise L.GanrevError("device-resident nn.Concat: only nn.Concat(2) of [batch x features] outputs (models.lua:293)")
         self.kids, self.x = {}, {}          # id(container) -> its children() / the device input of its last forward (borrowed)
+        self.branches = {}                  # id(table block) -> every branch, nn.Identity ones included
         todo = [model]
         for node in todo:
             self.kids[id(node)] = node.children()
+            if isinstance(node, nn._TableSum):
+                self.branches[id(node)] = node.modules[0].branches()
+                if not self.kids[id(node)]:
+                    raise L.GanrevError("device-resident nn.ConcatTable: at least one branch must hold a net")
             todo.extend(self.kids[id(node)] or ())
 
     def out_features(self, node):
@@ -105,6 +116,16 @@ class DeviceModel:
         kids = self.kids[id(node)]
         if kids is None:
             return node._net.forward_dev(x_dev, B)
+        if isinstance(node, nn._TableSum):
+            n = B * self.out_features(node)
+            acc = self.mem.floats((id(node), "sum"), n)
+            for j, b in enumerate(self.branches[id(node)]):
+                o = x_dev if isinstance(b, nn.Identity) else self.forward(x_dev, B, b)
+                if j == 0:
+                    self.ctx.copy2d(acc, n // B, o, n // B, B, n // B)
+                else:
+                    self.ctx.add(acc, o, n)
+            return acc
         if not isinstance(node, nn.Concat):
             for p in kids:
                 x_dev = self.forward(x_dev, B, p)
@@ -127,6 +148,16 @@ class DeviceModel:
             gin = self.mem.floats((id(node), "gin"), B * _vol(node._net.in_dims)) if want_gin else None
             node._net.backward_dev(x_dev, g_dev, B, gin)
             return gin
+        if isinstance(node, nn._TableSum):
+            nin = B * self.in_features(node)
+            acc = self.mem.floats((id(node), "gsum"), nin) if want_gin else None
+            for j, b in enumerate(self.branches[id(node)]):
+                gi = g_dev if isinstance(b, nn.Identity) else self.backward(g_dev, B, want_gin, b)
+                if want_gin and j == 0:
+                    self.ctx.copy2d(acc, nin // B, gi, nin // B, B, nin // B)
+                elif want_gin:
+                    self.ctx.add(acc, gi, nin)
+            return acc
         if not isinstance(node, nn.Concat):
             for i in range(len(kids) - 1, -1, -1):
                 g_dev = self.backward(g_dev, B, want_gin or i > 0, kids[i])

@@ -2,7 +2,8 @@
 104-143), create_R -> create_R_default (models.lua:385-387, 389-464) and create_D -> create_D2 (models.lua:209-211, 272-337;
 the discriminator adversarial.lua trains G against - SURVEY.md 8f rank 4); create_G_encoder (models.lua:57-102, pretrain_g.lua's
 encoder half) and the two D variants with average pooling, create_D_default and create_D_facegen (models.lua:213-270, 339-383),
-which nothing selects (the reference's create_D returns create_D2).  Same layer lists, same argument meaning."""
+which nothing selects (the reference's create_D returns create_D2); createResidual (models.lua:8-55), the residual block the
+reference's author left for edited models.  Same layer lists, same argument meaning."""
 from . import nn
 from .weight_init import w_init
 
@@ -13,6 +14,47 @@ class _CudnnSpatialConvolution(nn.SpatialConvolution):
 
 class _CudnnReLU(nn.ReLU):
     TYPENAME = "cudnn.ReLU"
+
+
+def createResidual(nbInputPlanes, nbInnerPlanes, nbOutputPlanes, activation=None, bn=True):
+    """models.lua:8-55: [1x1 in -> inner] - 3x3 - 3x3 - [1x1 inner -> out], each followed by [BatchNorm and] the activation, summed with
+    the shortcut: the input itself when in = out, else a 1x1 reducer with [BatchNorm and] the activation.  The bracketed 1x1 layers
+    exist only where the plane counts differ.  No seed and no w_init: the reference's function has neither."""
+    if activation is None or activation == "ReLU":
+        def act(): return _CudnnReLU(True)
+    elif activation == "PReLU":
+        def act(): return nn.PReLU()
+    elif activation == "LeakyReLU":
+        def act(): return nn.LeakyReLU(0.333)
+    else:
+        raise ValueError("Unknown activation '%s'" % (activation,))
+    assert bn is True or bn is False
+
+    def block(seq, nin, nout, k):
+        seq.add(_CudnnSpatialConvolution(nin, nout, k, k, 1, 1, k // 2, k // 2))
+        if bn:
+            seq.add(nn.SpatialBatchNormalization(nout))
+        seq.add(act())
+
+    seq = nn.Sequential()
+    inner = nn.Sequential()
+    if nbInputPlanes != nbInnerPlanes:
+        block(inner, nbInputPlanes, nbInnerPlanes, 1)
+    block(inner, nbInnerPlanes, nbInnerPlanes, 3)
+    block(inner, nbInnerPlanes, nbInnerPlanes, 3)
+    if nbInnerPlanes != nbOutputPlanes:
+        block(inner, nbInnerPlanes, nbOutputPlanes, 1)
+    conc = nn.ConcatTable(2)
+    conc.add(inner)
+    if nbInputPlanes == nbOutputPlanes:
+        conc.add(nn.Identity())
+    else:
+        reducer = nn.Sequential()
+        block(reducer, nbInputPlanes, nbOutputPlanes, 1)
+        conc.add(reducer)
+    seq.add(conc)
+    seq.add(nn.CAddTable())
+    return seq
 
 
 def create_G3(dimensions, noiseDim, cuda=True, seed=0):

@@ -390,8 +390,10 @@ class Sequential(_Container):
     # ---- a Sequential that holds an nn.Concat (models.lua:293-321, the D network) cannot be one gr_net: it runs as a chain
     # of PARTS - every run of plain modules is compiled into one gr_net (a chunk), a branching container runs its branches.
     # Host arrays travel between the parts, as Torch7 tensors travel between the modules of the reference's containers.
+    # An nn.ConcatTable followed by its nn.CAddTable (models.lua:41-53, createResidual) is ONE branching part: the table of branch
+    # outputs exists only between the two.
     def _is_graph(self):
-        return any(isinstance(m, Concat) or (isinstance(m, Sequential) and m._is_graph()) for m in self.modules)
+        return any(isinstance(m, (Concat, ConcatTable, CAddTable)) or (isinstance(m, Sequential) and m._is_graph()) for m in self.modules)
 
     def children(self):
         return self.parts() if self._is_graph() else None
@@ -399,8 +401,16 @@ class Sequential(_Container):
     def parts(self):
         if getattr(self, "_parts", None) is None:
             parts, run = [], None
-            for m in self.modules:
-                if isinstance(m, Concat) or (isinstance(m, Sequential) and m._is_graph()):
+            mods = list(self.modules)
+            while mods:
+                m = mods.pop(0)
+                if isinstance(m, CAddTable):
+                    raise L.GanrevError("nn.CAddTable: only directly behind the nn.ConcatTable whose outputs it sums (models.lua:41-53)")
+                if isinstance(m, ConcatTable):
+                    if not mods or not isinstance(mods[0], CAddTable):
+                        raise L.GanrevError("nn.ConcatTable: only with an nn.CAddTable directly behind it (models.lua:41-53)")
+                    m = _TableSum(m, mods.pop(0))
+                if isinstance(m, (Concat, _TableSum)) or (isinstance(m, Sequential) and m._is_graph()):
                     if run is not None:
                         parts.append(run)
                         run = None
@@ -500,6 +510,137 @@ class Concat(_Container):
         return f"nn.Concat({self.dimension})"
 
 
+class Identity(Module):
+    """nn.Identity(): output = input, gradInput = gradOutput (createResidual's shortcut when the plane counts agree, models.lua:44).
+    No layer of a gr_net: inside a plain Sequential it is skipped, as a ConcatTable branch it hands the input through."""
+    TYPENAME = "nn.Identity"
+
+    def leaves(self):
+        return []
+
+    def forward(self, input):
+        self.output = input
+        return input
+
+    updateOutput = forward
+
+    def backward(self, input, gradOutput, scale=1):
+        self.gradInput = gradOutput
+        return gradOutput
+
+
+class ConcatTable(_Container):
+    """nn.ConcatTable(): every branch gets the same input, the output is the list of branch outputs; backward sums the branches'
+    gradInputs (models.lua:41-52).  `modules` holds what was added, as Torch7's does; a branch runs as a Sequential (its own, or
+    one made around a single module), an nn.Identity as itself."""
+    TYPENAME = "nn.ConcatTable"
+
+    def __init__(self, *_ignored):       # models.lua:41 writes nn.ConcatTable(2); Torch7's constructor takes no argument
+        super().__init__()
+        self._runs = {}
+
+    def add(self, m):
+        self.modules.append(m)
+        return self
+
+    def branches(self):
+        """what each entry of `modules` runs as: itself (a Sequential, an Identity) or a Sequential around it"""
+        out = []
+        for m in self.modules:
+            if not isinstance(m, (Sequential, Identity)):
+                if id(m) not in self._runs:
+                    self._runs[id(m)] = Sequential().add(m)
+                m = self._runs[id(m)]
+            out.append(m)
+        return out
+
+    def _is_graph(self):
+        return True
+
+    def children(self):
+        return [b for b in self.branches() if not isinstance(b, Identity)]      # the branches that compile to nets
+
+    def forward(self, input):
+        x = L.f32(input)
+        self.output = [b.forward(x) for b in self.branches()]
+        return self.output
+
+    updateOutput = forward
+
+    def backward(self, input, gradOutput, scale=1):
+        x, gin = L.f32(input), None
+        if len(gradOutput) != len(self.modules):
+            raise L.GanrevError(f"nn.ConcatTable: {len(gradOutput)} gradOutputs for {len(self.modules)} branches")
+        for b, g in zip(self.branches(), gradOutput):
+            gi = b.backward(x, L.f32(g), scale)
+            gin = gi.copy() if gin is None else gin + gi
+        self.gradInput = gin
+        return gin
+
+    def _head(self):
+        return "nn.ConcatTable"
+
+
+class CAddTable(Module):
+    """nn.CAddTable(inplace=false): the sum of a list of equally shaped tensors; the gradient goes unchanged to every entry
+    (models.lua:53)."""
+    TYPENAME = "nn.CAddTable"
+
+    def __init__(self, inplace=False):
+        super().__init__()
+        self.inplace = bool(inplace)
+
+    def leaves(self):
+        return []
+
+    def forward(self, input):
+        if not isinstance(input, (list, tuple)) or not input or any(np.shape(t) != np.shape(input[0]) for t in input):
+            raise L.GanrevError("nn.CAddTable: expects a non-empty list of equally shaped tensors")
+        out = np.array(input[0], dtype=np.float32, copy=True)
+        for t in input[1:]:
+            out += t
+        self.output = out
+        return out
+
+    updateOutput = forward
+
+    def backward(self, input, gradOutput, scale=1):
+        self.gradInput = [gradOutput for _ in input]
+        return self.gradInput
+
+
+class _TableSum(_Container):
+    """An nn.ConcatTable and the nn.CAddTable behind it as one part of a graph Sequential (Sequential.parts): out = sum of the branch
+    outputs, gradInput = sum of the branches' gradInputs.  Not a module of the model's tree: listModules() / leaves() of the model
+    never show it."""
+    TYPENAME = "nn.Sequential"
+
+    def __init__(self, table, add):
+        super().__init__()
+        self.modules = [table, add]
+
+    def _is_graph(self):
+        return True
+
+    def children(self):
+        return self.modules[0].children()
+
+    def forward(self, input):
+        table, add = self.modules
+        self.output = add.forward(table.forward(input))
+        return self.output
+
+    updateOutput = forward
+
+    def backward(self, input, gradOutput, scale=1):
+        table, add = self.modules
+        self.gradInput = table.backward(input, add.backward(table.output, L.f32(gradOutput), scale), scale)
+        return self.gradInput
+
+    def _head(self):
+        return "nn.Sequential"
+
+
 class Copy(Module):
     """nn.Copy(intype, outtype): host<->device crossing of the reference models — a no-op here."""
     TYPENAME = "nn.Copy"
@@ -528,16 +669,17 @@ class _Param(Module):
 
 class SpatialConvolution(_Param):
     """nn.SpatialConvolution(nInputPlane, nOutputPlane, kW, kH, dW, dH, padW, padH) — 3x3 s1 p1 (the one geometry
-    models.lua uses on the G/R path) and 5x5 s1 p2 (the D network's createNxN(128, 64, 5, ..), models.lua:275,297)."""
+    models.lua uses on the G/R path), 5x5 s1 p2 (the D network's createNxN(128, 64, 5, ..), models.lua:275,297) and 1x1 s1 p0
+    (createResidual's pointwise layers, models.lua:25,36,47)."""
     TYPENAME = "nn.SpatialConvolution"
     KIND = L.CONV3
 
     def __init__(self, nInputPlane, nOutputPlane, kW=3, kH=3, dW=1, dH=1, padW=1, padH=None):
         super().__init__()
         padH = padW if padH is None else padH
-        if (kW, kH, dW, dH, padW, padH) not in ((3, 3, 1, 1, 1, 1), (5, 5, 1, 1, 2, 2)) or (kW != 3 and self.KIND != L.CONV3):
-            raise L.GanrevError("only 3x3 stride-1 pad-1 (models.lua:409-436) and 5x5 stride-1 pad-2 (models.lua:297) "
-                                "convolutions have a gfx950 kernel")
+        if (kW, kH, dW, dH, padW, padH) not in ((3, 3, 1, 1, 1, 1), (5, 5, 1, 1, 2, 2), (1, 1, 1, 1, 0, 0)) or (kW != 3 and self.KIND != L.CONV3):
+            raise L.GanrevError("only 3x3 stride-1 pad-1 (models.lua:409-436), 5x5 stride-1 pad-2 (models.lua:297) and 1x1 stride-1 "
+                                "pad-0 (models.lua:25) convolutions have a gfx950 kernel")
         self.nInputPlane, self.nOutputPlane, self.kW, self.kH = nInputPlane, nOutputPlane, kW, kH
         self.weight = np.zeros(self._wshape(), np.float32)
         self.bias = np.zeros(nOutputPlane, np.float32)

@@ -291,6 +291,17 @@ def to_model(obj):
             if sub is not None:
                 cat.add(sub)
         return cat
+    if t == "nn.ConcatTable":                # createResidual's skeleton (models.lua:41-53)
+        tab = nn.ConcatTable()
+        for m in f.get("modules", []):
+            sub = to_model(m)
+            if sub is not None:
+                tab.add(sub)
+        return tab
+    if t == "nn.CAddTable":
+        return nn.CAddTable(bool(f.get("inplace", False)))
+    if t == "nn.Identity":
+        return nn.Identity()
     if t == "nn.PReLU":
         m = nn.PReLU(int(f.get("nOutputPlane", 0)))
         m.weight[...] = np.asarray(f["weight"], np.float32).reshape(m.weight.shape)
@@ -360,8 +371,12 @@ def from_model(model):
         return TorchObject("nn.Sequential", dict(base, modules=[from_model(m) for m in model.modules]))
     if isinstance(model, nn.Concat):
         return TorchObject("nn.Concat", dict(base, dimension=model.dimension, size=storage([]), modules=[from_model(m) for m in model.modules]))
+    if isinstance(model, nn.ConcatTable):        # its output and gradInput are tables
+        return TorchObject("nn.ConcatTable", dict(base, output=[], gradInput=empty, modules=[from_model(m) for m in model.modules]))
     f = dict(base)
-    if isinstance(model, nn.PReLU):
+    if isinstance(model, nn.CAddTable):
+        f.update(inplace=model.inplace, gradInput=[])
+    elif isinstance(model, nn.PReLU):
         f.update(nOutputPlane=0, weight=model.weight, gradWeight=empty, gradWeightBuf=empty, gradWeightBuf2=empty)
     elif isinstance(model, nn.SpatialConvolution):
         pad = (model.kW - 1) // 2

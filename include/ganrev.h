@@ -49,7 +49,7 @@ enum {
   GR_LINEAR = 13,          /* nn.Linear(a=in, b=out)                                             models.lua:115,447,451 */
   GR_FULLCONV3 = 14,       /* nn.SpatialFullConvolution(a,b,3,3,1,1,1,1) (north_star names it; absent from the reference) */
   /* the module types the D network adds (models.lua:272-337 create_D2, trained by adversarial.lua:37-205) */
-  GR_CONVK = 15,           /* nn.SpatialConvolution(a, b, c=K, K, 1, 1, (K-1)/2, (K-1)/2), K = 5           models.lua:275,297 */
+  GR_CONVK = 15,           /* nn.SpatialConvolution(a, b, c=K, K, 1, 1, (K-1)/2, (K-1)/2), K = 5 or 1      models.lua:275,297; 8-55 */
   GR_PRELU = 16,           /* nn.PReLU(): one learnable slope (nOutputPlane 0) in the flat vector; the host mirror starts it at 0.25  models.lua:276 */
   GR_AVGPOOL2 = 17         /* nn.SpatialAveragePooling(2,2,2,2)                                  models.lua:71,235,242,249,348-363 */
 };
