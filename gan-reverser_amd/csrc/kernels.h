@@ -482,6 +482,14 @@ int launch_kmeans(const float* x, long N, int d, int k, int niter, float* cent, 
                   int* labels_out, void* workspace, hipStream_t s);
 int launch_cosine_assign(const float* x, long N, int d, const float* cent, int k, int take_min, float* w32_scratch,
                          int* labels, float* sims, hipStream_t s);
+// apply_r.lua:218-227: per cluster j < k the min(m, members) rows with the largest similarity (descending, ties by ascending row, NaN last) into
+// rows_out / sims_out [k][m] (unused slots -1 / 0), kept_out [k] = rows written, sizes_out [k] = members.  All pointers device.  Returns 1
+// outside k <= 32, m <= 128, 1 <= n < 2^31.
+size_t cluster_members_workspace_bytes(long n, int k);
+int launch_cluster_members(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
+                           void* workspace, hipStream_t s);
+// apply_r.lua:233-243 for every cluster at once: out[j] = launch_rows_mean of rows[j][0 .. kept[j]); entries outside [0, n_rows) are skipped
+void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows, const int* kept, int k, int m, float* out, hipStream_t s);
 
 // mfmaloop.hip: the bare LDS-read + f16x3 MFMA loop (sustained ceiling of the convolution inner loop on this device; diagnostic)
 size_t mfma_loop_workspace_bytes();

@@ -1,4 +1,4 @@
-// kmeans.hip — clustering of the recovered noise vectors: apply_r.lua:197-217.
+// kmeans.hip — clustering of the recovered noise vectors: apply_r.lua:197-243.
 //
 //   createClusterImages (apply_r.lua:197-231) = unsup.kmeans(attributes, nbClusters, nbIterations) followed by a
 //   nearest-centroid pass in which the reference scores every (row, centroid) pair with cosineSimilarity (apply_r.lua:396-400)
@@ -20,6 +20,8 @@
 //   kmeans_update_kernel      partial blocks summed in workgroup order; new centroids, c2, counts
 //   cosine_assign_kernel      thread = row: the k cosine similarities in nn.CosineDistance's exact op order (fp32 products,
 //                             fp64 sequential row sums, fp32 reciprocal / sqrt / multiply) and their arg-min or arg-max
+//   cluster_members_*_kernel  apply_r.lua:218-227: per cluster the m most similar member rows, by a sort of (similarity, row) keys
+//   cluster_faces_kernel      apply_r.lua:233-243: every cluster's average face in one launch
 #include "kernels.h"
 
 namespace gr {
@@ -207,6 +209,152 @@ int launch_cosine_assign(const float* x, long N, int d, const float* cent, int k
   KtScope kt("cosine_assign_kernel", 2.0 * N * d * k, 4.0 * N * d, s);
   hipLaunchKernelGGL(cosine_assign_kernel, dim3((unsigned)((N + KM_ROWS - 1) / KM_ROWS)), dim3(KM_ROWS), 0, s, x, N, d, cent, w32, k, take_min, labels, sims);
   return 0;
+}
+
+// ------------------------------------------------------------------ apply_r.lua:218-227: the nbMaxPerCluster most similar rows of each cluster
+// table.sort(cluster, a[2] > b[2]) and the first m entries, as numpy's stable argsort of -similarity orders them: similarity descending (-0 and
+// +0 are one value), ties by ascending row, NaN after every number.  Every member row gets a 64-bit key, (order-preserving image of
+// -similarity) << 32 | row: keys are distinct, so "the m smallest keys, ascending" is one well-defined list and nothing depends on the order in
+// which threads meet the rows.  cluster_members_partial_kernel: workgroup = (cluster, one of S contiguous row ranges); it keeps the range's m
+// smallest keys in LDS (candidates below the current m-th key are appended by a block prefix sum, the 512-key buffer is sorted and cut to m
+// when it runs full).  cluster_members_merge_kernel: workgroup = cluster, sorts the S lists and writes the result.
+constexpr int CM_MMAX = 128, CM_U = 16, CM_BUF = 512, CM_SMAX = 8;
+constexpr unsigned long long CM_NONE = ~0ull;
+
+__device__ inline unsigned long long cm_key(float sim, long row) {
+  unsigned u = 0xFFFFFFFFu;                                             // NaN: after every number
+  if (sim == sim) {
+    const float f = sim == 0.f ? 0.f : -sim;
+    u = __float_as_uint(f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                     // unsigned order = order of f
+  }
+  return ((unsigned long long)u << 32) | (unsigned long long)row;
+}
+// ascending bitonic sort of buf[0, P) by 256 threads (P a power of two, >= 512); ends with a barrier
+template <int P> __device__ __noinline__ void cm_sort(unsigned long long* buf, int tid) {
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < P / 2; i += 256) {
+        const int a = 2 * i - (i & (stride - 1)), b = a + stride;
+        const unsigned long long ka = buf[a], kb = buf[b];
+        if ((ka > kb) == ((a & size) == 0)) { buf[a] = kb; buf[b] = ka; }
+      }
+    }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void cluster_members_partial_kernel(const int* __restrict__ labels, const float* __restrict__ sims, long n, int m, int S,
+                                                                       unsigned long long* __restrict__ part_keys /*[k][S][CM_MMAX]*/, int* __restrict__ part_cnt /*[k][S]*/) {
+  __shared__ unsigned long long buf[CM_BUF];
+  __shared__ int wsum[2][4];
+  __shared__ int s_members;
+  const int j = blockIdx.x, sp = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long chunk = 256L * CM_U;
+  const long per = ((n + S - 1) / S + chunk - 1) / chunk * chunk;
+  const long lo = sp * per, hi = min(n, lo + per);
+  buf[tid] = CM_NONE; buf[tid + 256] = CM_NONE;
+  if (tid == 0) s_members = 0;
+  int count = 0, members = 0, par = 0;                                  // count: keys in buf (the same number in every thread)
+  unsigned long long thr = CM_NONE;                                     // a key must be below it to matter: the m-th smallest so far, once m are known
+  __syncthreads();
+  for (long base = lo; base < hi; base += chunk) {
+    unsigned long long key[CM_U];
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < CM_U; ++u) {
+      const long row = base + u * 256 + tid;
+      key[u] = CM_NONE;
+      if (row < hi && labels[row] == j) {
+        ++members;
+        const unsigned long long kk = cm_key(sims[row], row);
+        if (kk < thr) { key[u] = kk; any = true; }
+      }
+    }
+    if (!__syncthreads_or(any)) continue;
+#pragma unroll
+    for (int u = 0; u < CM_U; ++u) {
+      const bool f = key[u] < thr;                                      // (CM_NONE is below nothing)
+      const unsigned long long bal = __ballot(f);
+      if (lane == 0) wsum[par][w] = __popcll(bal);
+      __syncthreads();
+      int off = 0, tot = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { const int v = wsum[par][q]; if (q < w) off += v; tot += v; }
+      par ^= 1;
+      if (f) buf[count + off + __popcll(bal & ((1ull << lane) - 1ull))] = key[u];
+      count += tot;
+      if (count > CM_BUF - 256) {                                       // the next 256 rows might not fit: sort, keep the m smallest
+        cm_sort<CM_BUF>(buf, tid);
+        count = min(count, m);
+        if (tid >= count) buf[tid] = CM_NONE;
+        buf[tid + 256] = CM_NONE;
+        __syncthreads();
+        if (count == m) thr = buf[m - 1];
+      }
+    }
+  }
+  cm_sort<CM_BUF>(buf, tid);
+  if (members) atomicAdd(&s_members, members);                          // an integer sum: the same in any order
+  __syncthreads();
+  if (tid < CM_MMAX) part_keys[((long)j * S + sp) * CM_MMAX + tid] = tid < min(count, m) ? buf[tid] : CM_NONE;
+  if (tid == 0) part_cnt[j * S + sp] = s_members;
+}
+
+__global__ __launch_bounds__(256) void cluster_members_merge_kernel(const unsigned long long* __restrict__ part_keys, const int* __restrict__ part_cnt, int S, int m,
+                                                                     const float* __restrict__ sims, long* __restrict__ rows_out, float* __restrict__ sims_out,
+                                                                     int* __restrict__ kept_out, int* __restrict__ sizes_out) {
+  __shared__ unsigned long long buf[CM_SMAX * CM_MMAX];
+  const int j = blockIdx.x, tid = threadIdx.x;
+  for (int e = tid; e < CM_SMAX * CM_MMAX; e += 256) buf[e] = e < S * CM_MMAX ? part_keys[(long)j * S * CM_MMAX + e] : CM_NONE;
+  cm_sort<CM_SMAX * CM_MMAX>(buf, tid);
+  int size = 0;
+  for (int q = 0; q < S; ++q) size += part_cnt[j * S + q];
+  const int kept = min(size, m);
+  for (int e = tid; e < m; e += 256) {
+    const long row = e < kept ? (long)(buf[e] & 0xFFFFFFFFull) : -1;
+    rows_out[(long)j * m + e] = row;
+    sims_out[(long)j * m + e] = e < kept ? sims[row] : 0.f;
+  }
+  if (tid == 0) { kept_out[j] = kept; sizes_out[j] = size; }
+}
+
+static int cluster_members_splits(long n) { return (int)min((long)CM_SMAX, max(1L, n / 65536)); }
+size_t cluster_members_workspace_bytes(long n, int k) {
+  return (sizeof(unsigned long long) * CM_MMAX + sizeof(int)) * (size_t)k * cluster_members_splits(n) + 256;
+}
+int launch_cluster_members(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
+                           void* workspace, hipStream_t s) {
+  if (k < 1 || k > KM_KMAX || m < 1 || m > CM_MMAX || n < 1 || n > 0x7FFFFFFFL) return 1;
+  const int S = cluster_members_splits(n);
+  unsigned long long* part_keys = reinterpret_cast<unsigned long long*>(workspace);
+  int* part_cnt = reinterpret_cast<int*>(part_keys + (size_t)k * S * CM_MMAX);
+  { KtScope kt("cluster_members_partial_kernel", (double)n * k, 8.0 * n * k, s);
+    hipLaunchKernelGGL(cluster_members_partial_kernel, dim3(k, S), dim3(256), 0, s, labels, sims, n, m, S, part_keys, part_cnt); }
+  KtScope kt("cluster_members_merge_kernel", 0.0, 8.0 * k * S * CM_MMAX, s);
+  hipLaunchKernelGGL(cluster_members_merge_kernel, dim3(k), dim3(256), 0, s, part_keys, part_cnt, S, m, sims, rows_out, sims_out, kept_out, sizes_out);
+  return 0;
+}
+
+// ------------------------------------------------------------------ apply_r.lua:233-243: the average faces of all clusters
+// Per cluster rows_mean_kernel's arithmetic (render.hip): the listed rows added in list order in fp32, one division by the list's length.  The
+// lists are device data nobody has looked at: an entry outside [0, n_rows) is skipped (the divisor stays kept[j]).
+__global__ __launch_bounds__(256) void cluster_faces_kernel(const float* __restrict__ x, long n_rows, long d, const long* __restrict__ rows /*[k][m]*/,
+                                                             const int* __restrict__ kept, int m, float* __restrict__ out /*[k][d]*/) {
+  const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const int j = blockIdx.y;
+  if (p >= d) return;
+  const int n = min(max(kept[j], 0), m);
+  float acc = 0.f;
+  for (int i = 0; i < n; ++i) {
+    const long r = rows[(long)j * m + i];
+    if (r >= 0 && r < n_rows) acc = acc + x[r * d + p];
+  }
+  out[(long)j * d + p] = n > 0 ? acc / (float)n : 0.f;
+}
+void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows, const int* kept, int k, int m, float* out, hipStream_t s) {
+  KtScope kt("cluster_faces_kernel", (double)k * m * (double)d, 4.0 * ((double)k * m + k) * (double)d, s);
+  hipLaunchKernelGGL(cluster_faces_kernel, dim3((unsigned)((d + 255) / 256), k), dim3(256), 0, s, x, n_rows, d, rows, kept, m, out);
 }
 
 }  // namespace gr

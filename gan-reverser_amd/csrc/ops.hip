@@ -287,6 +287,51 @@ extern "C" int gr_cosine_assign_host(gr_ctx* c, const float* x, int64_t n, int d
   TRY(s.download(labels, dlab)); TRY(s.download(sims, dsim));
   return s.finish();
 }
+// the same two on device-resident tables, and the steps that follow them (apply_r.lua:218-243): enqueued on c->stream, no wait
+extern "C" int gr_kmeans_dev(gr_ctx* c, const float* x, int64_t n, int d, int k, int niter, float* cent, float* totalcounts, int32_t* labels) {
+  if (!c || !x || !cent || n <= 0 || d <= 0 || k <= 0 || niter < 0) return GR_ERR_INVALID;
+  Staging s(c);
+  auto scratch = s.reserve<char>(kmeans_workspace_bytes(n, d, k));   // launch_kmeans takes c->ws itself: the first region
+  auto dc2 = s.reserve<float>(k), dcnt = s.reserve<float>(k), dtot = s.reserve<float>(k);
+  TRY(s.grow());
+  if (launch_kmeans(x, n, d, k, niter, cent, s.ptr(dc2), s.ptr(dcnt), totalcounts ? totalcounts : s.ptr(dtot), labels, s.ptr(scratch), c->stream))
+    return fail(c, GR_ERR_UNSUPPORTED, "kmeans: k <= 32 and d <= 256 only");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_cosine_assign_dev(gr_ctx* c, const float* x, int64_t n, int d, const float* cent, int k, int take_min, int32_t* labels, float* sims) {
+  if (!c || !x || !cent || !labels || !sims || n <= 0 || d <= 0 || k <= 0) return GR_ERR_INVALID;
+  Staging s(c);
+  auto dw = s.reserve<float>(k);
+  TRY(s.grow());
+  if (launch_cosine_assign(x, n, d, cent, k, take_min, s.ptr(dw), labels, sims, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_assign: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_cluster_members_dev(gr_ctx* c, const int32_t* labels, const float* sims, int64_t n, int k, int m, int64_t* rows_out, float* sims_out,
+                                      int32_t* kept_out, int32_t* sizes_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!labels || !sims || !rows_out || !sims_out || !kept_out || !sizes_out) return fail(c, GR_ERR_INVALID, "gr_cluster_members_dev: null pointer");
+  if (n <= 0 || k <= 0 || m <= 0) return fail(c, GR_ERR_INVALID, "gr_cluster_members_dev: n %lld, k %d, m %d must be positive", (long long)n, k, m);
+  if (n >= ((int64_t)1 << 31) || k > 32 || m > 128)
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_dev: n %lld, k %d, m %d: n < 2^31, k <= 32 and m <= 128 only", (long long)n, k, m);
+  Staging s(c);
+  auto scratch = s.reserve<char>(cluster_members_workspace_bytes(n, k));
+  TRY(s.grow());
+  if (launch_cluster_members(labels, sims, n, k, m, reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, s.ptr(scratch), c->stream))
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_cluster_faces_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, const int32_t* kept, int k, int m, float* out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!table || !rows || !kept || !out) return fail(c, GR_ERR_INVALID, "gr_cluster_faces_dev: null pointer");
+  if (n_rows <= 0 || d <= 0 || k <= 0 || m <= 0 || k > 65535)
+    return fail(c, GR_ERR_INVALID, "gr_cluster_faces_dev: n_rows %lld, d %lld, k %d (at most 65535), m %d must be positive", (long long)n_rows, (long long)d, k, m);
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_cluster_faces(table, (long)n_rows, (long)d, reinterpret_cast<const long*>(rows), kept, k, m, out, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
 
 // ------------------------------------------------------------------ apply_r.lua:355-372 detectAnomalies' distance
 extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {

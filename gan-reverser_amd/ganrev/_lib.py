@@ -172,6 +172,10 @@ _SIGS = {
     "gr_l2_nearest_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P, _P]),
     "gr_kmeans_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gr_cosine_assign_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "gr_kmeans_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gr_cosine_assign_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "gr_cluster_members_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gr_cluster_faces_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P]),
     "gr_malloc": (C.c_int, [_P, C.c_int64, C.POINTER(_P)]),
     "gr_free": (C.c_int, [_P, _P]),
     "gr_memcpy_h2d": (C.c_int, [_P, _P, _P, C.c_int64]),
@@ -505,6 +509,28 @@ class Context:
         self.check(self.lib.gr_cosine_assign_host(self.h, _ptr(x), n, d, _ptr(cent), cent.shape[0], int(take_min), _ptr(lab), _ptr(sim)),
                    "gr_cosine_assign_host")
         return lab, sim
+
+    def kmeans_dev(self, x_dev, n, d, k, niter, cent_dev, totalcounts_dev=None, labels_dev=None):
+        """gr_kmeans_dev: unsup.kmeans on a device table [n x d]; cent_dev [k x d] carries the initial centroids in and the final ones out,
+        totalcounts_dev [k] floats and labels_dev [n] int32 are optional.  Enqueued on the context's stream."""
+        self.check(self.lib.gr_kmeans_dev(self.h, _ptr(x_dev), int(n), int(d), int(k), int(niter), _ptr(cent_dev), _ptr(totalcounts_dev), _ptr(labels_dev)),
+                   "gr_kmeans_dev")
+
+    def cosine_assign_dev(self, x_dev, n, d, cent_dev, k, take_min, labels_dev, sims_dev):
+        """gr_cosine_assign_dev (apply_r.lua:205-217): labels_dev [n] int32 and sims_dev [n] floats for the device table [n x d]"""
+        self.check(self.lib.gr_cosine_assign_dev(self.h, _ptr(x_dev), int(n), int(d), _ptr(cent_dev), int(k), int(bool(take_min)), _ptr(labels_dev),
+                                                 _ptr(sims_dev)), "gr_cosine_assign_dev")
+
+    def cluster_members_dev(self, labels_dev, sims_dev, n, k, m, rows_out_dev, sims_out_dev, kept_out_dev, sizes_out_dev):
+        """gr_cluster_members_dev (apply_r.lua:218-227): per cluster the m most similar member rows -> rows_out_dev int64 [k x m] (-1 fill),
+        sims_out_dev float [k x m] (0 fill), kept_out_dev / sizes_out_dev int32 [k]"""
+        self.check(self.lib.gr_cluster_members_dev(self.h, _ptr(labels_dev), _ptr(sims_dev), int(n), int(k), int(m), _ptr(rows_out_dev), _ptr(sims_out_dev),
+                                                   _ptr(kept_out_dev), _ptr(sizes_out_dev)), "gr_cluster_members_dev")
+
+    def cluster_faces_dev(self, table_dev, n_rows, d, rows_dev, kept_dev, k, m, out_dev):
+        """gr_cluster_faces_dev (apply_r.lua:233-243): out_dev [k x d] = the average faces of all clusters (rows_dev int64 [k x m], kept_dev int32 [k])"""
+        self.check(self.lib.gr_cluster_faces_dev(self.h, _ptr(table_dev), int(n_rows), int(d), _ptr(rows_dev), _ptr(kept_dev), int(k), int(m), _ptr(out_dev)),
+                   "gr_cluster_faces_dev")
 
     # ---- data parallel
     def comm_unique_id(self):

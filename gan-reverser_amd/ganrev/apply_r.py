@@ -117,6 +117,17 @@ def initialCentroids(nbClusters, nDims, seed=1):
     return c / np.linalg.norm(c.astype(np.float64), axis=1, keepdims=True).astype(np.float32)
 
 
+def selectClusterMembers(label, sim, nbClusters, nbMaxPerCluster):
+    """apply_r.lua:218-227 on host arrays: per cluster the rows sorted by similarity descending (table.sort with a[2] > b[2]; ties by row, a NaN
+    last: a stable argsort of -similarity) and the first nbMaxPerCluster of them -> [row index arrays], one per cluster"""
+    keeps = []
+    for j in range(nbClusters):
+        rows = np.nonzero(label == j)[0]
+        order = np.argsort(-sim[rows], kind="stable")                                               # :221 (a[2] > b[2]); ties by row
+        keeps.append(rows[order][:nbMaxPerCluster])                                                 # :223-227
+    return keeps
+
+
 def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, centroids0=None, seed=1, closest=False):
     """apply_r.lua:197-231 without the image writing.  -> (centroids, counts, clusters, averageFaces): clusters[j] is the list
     of (row index, similarity) kept for cluster j, sorted like the reference (similarity descending, first nbMaxPerCluster);
@@ -134,10 +145,7 @@ def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attri
     label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
     clusters, faces = [], []
     images = np.asarray(images, np.float32)
-    for j in range(nbClusters):
-        rows = np.nonzero(label == j)[0]
-        order = np.argsort(-sim[rows], kind="stable")                                               # :221 (a[2] > b[2]); ties by row
-        keep = rows[order][:nbMaxPerCluster]                                                        # :223-227
+    for keep in selectClusterMembers(label, sim, nbClusters, nbMaxPerCluster):                      # :218-227
         clusters.append([(int(r), float(sim[r])) for r in keep])
         faces.append(images[keep].mean(axis=0, dtype=np.float64).astype(np.float32) if len(keep)
                      else np.zeros(images.shape[1:], np.float32))                                   # :233-243
@@ -145,34 +153,58 @@ def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attri
 
 
 def createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, centroids0=None, seed=1, closest=False):
-    """createClusterImages with the images resident on the GPU (`images` a DeviceTensor [N x C x H x W], `attributes` the small host
-    table [N x nd]): k-means and the assignment as there, the average faces by gr_rows_mean_dev - the cluster's rows added in the
-    cluster's order in fp32 and divided once, as the reference's face:add / face:div (apply_r.lua:233-243).  createClusterImages
-    averages in float64 on the host: the faces may differ from it in the last bits.
+    """createClusterImages with the images resident on the GPU (`images` a DeviceTensor [N x C x H x W]; `attributes` [N x nd] the small
+    host table or the DeviceTensor embed_dev wrote): k-means and the assignment as there, the average faces by gr_rows_mean_dev's
+    arithmetic - the cluster's rows added in the cluster's order in fp32 and divided once, as the reference's face:add / face:div
+    (apply_r.lua:233-243).  createClusterImages averages in float64 on the host: the faces may differ from it in the last bits.
+    With a device table nothing of size N crosses the bus: gr_kmeans_dev, gr_cosine_assign_dev, gr_cluster_members_dev and
+    gr_cluster_faces_dev run where the table lies, and the [k x m] lists, the centroids and the counts come back - the same tuple, bit for bit.
     -> (centroids, counts, clusters, faces) with faces a DeviceTensor [nbClusters x C x H x W] (the caller frees it)."""
+    ctx = images.ctx
+    chw = images.size // images.shape[0]
+    faces = DeviceTensor(ctx, (nbClusters,) + tuple(images.shape[1:]))
+    if isinstance(attributes, DeviceTensor):
+        N, k, m = attributes.shape[0], int(nbClusters), int(nbMaxPerCluster)
+        d = attributes.size // N
+        if centroids0 is None:
+            centroids0 = initialCentroids(k, d, seed)
+        cent = ctx.upload(np.ascontiguousarray(centroids0, np.float32).reshape(k, d))
+        sizes = [4 * k, 4 * N, 4 * N, 8 * k * m, 4 * k * m, 4 * k, 4 * k]               # counts, labels, sims, rows, their sims, kept, cluster sizes
+        tot, lab, sim, rows, rsim, kept, csize = bufs = [ctx.malloc(b) for b in sizes]
+        try:
+            ctx.kmeans_dev(attributes.ptr, N, d, k, nbIterations, cent, tot, lab)                   # :198
+            ctx.cosine_assign_dev(attributes.ptr, N, d, cent, k, not closest, lab, sim)             # :205-217
+            ctx.cluster_members_dev(lab, sim, N, k, m, rows, rsim, kept, csize)                     # :218-227
+            ctx.cluster_faces_dev(images.ptr, images.shape[0], chw, rows, kept, k, m, faces.ptr)    # :233-243 (zeros for an empty cluster)
+            centroids, counts = ctx.download(cent, (k, d)), ctx.download(tot, (k,))
+            hrows, hsim, hkept = ctx.download(rows, (k, m), np.int64), ctx.download(rsim, (k, m)), ctx.download(kept, (k,), np.int32)
+        except Exception:
+            faces.free()
+            raise
+        finally:
+            for b in bufs + [cent]:
+                ctx.free(b)
+        clusters = [[(int(r), float(v)) for r, v in zip(hrows[j, :hkept[j]], hsim[j, :hkept[j]])] for j in range(k)]
+        return centroids, counts, clusters, faces
     attributes = np.asarray(attributes, np.float32)
     N, d = attributes.shape
     if centroids0 is None:
         centroids0 = initialCentroids(nbClusters, d, seed)
-    ctx = images.ctx
     centroids, counts, _ = ctx.kmeans(attributes, nbClusters, nbIterations, centroids0)            # :198
     label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
-    chw = images.size // images.shape[0]
-    faces = DeviceTensor(ctx, (nbClusters,) + tuple(images.shape[1:]))
     clusters = []
-    for j in range(nbClusters):
-        rows = np.nonzero(label == j)[0]
-        keep = rows[np.argsort(-sim[rows], kind="stable")][:nbMaxPerCluster]                        # :221-227
+    for j, keep in enumerate(selectClusterMembers(label, sim, nbClusters, nbMaxPerCluster)):        # :218-227
         clusters.append([(int(r), float(sim[r])) for r in keep])
         ctx.rows_mean_dev(images.ptr, images.shape[0], chw, keep, faces.ptr + 4 * chw * j)          # :233-243 (zeros for an empty cluster)
     return centroids, counts, clusters, faces
 
 
-def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributesFixer, by_attr, by_pix):
-    """The pictures of apply_r.lua:158-191 from the device-resident tables (`images` [N x C x H x W] and `attributesFixer` [N x nd] as
-    DeviceTensors, `attributes` on the host): cluster_%02d, similar_attributes_%02d / similar_pixelwise_%02d, fixed_pairs,
-    fixed_images_<n>[_unfixed] and anomalies as PNG files out(name).  Only the rows a picture shows are read; nothing but the finished
-    pictures and the per-image distances leaves the GPU.
+def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colorSpace=None, by_attr=None, by_pix=None):
+    """The analysis of apply_r.lua:158-191 on the device-resident tables (`images` [N x C x H x W] and `attributesFixer` [N x nd] as
+    DeviceTensors, `attributes` [N x nd] a DeviceTensor or the host table): the clusters (createClusterImagesDev), the fixed faces and the
+    anomaly distance.  Only the rows a step needs are read; the image table stays where it is.  With `out` (name -> path) the reference's
+    pictures are written as PNG files on the way (ganrev.render): cluster_%02d, similar_attributes_%02d / similar_pixelwise_%02d,
+    fixed_pairs, fixed_images_<n>[_unfixed] and anomalies; nothing but the finished pictures and the per-image distances leaves the GPU.
     -> what the run's arrays and summary are written from: dict(clusters = createClusterImagesDev's tuple with the faces on the host,
     fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple)."""
     from . import render
@@ -180,28 +212,36 @@ def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributes
     chw = images.size // N
     centroids, counts, clusters, faces = createClusterImagesDev(20, 15, 64 + 7, images, attributes, seed=OPT.seed)      # :158-163
     for j, cl in enumerate(clusters):
-        if cl:                                                                                                          # :249
+        if cl and out:                                                                                                  # :249
             render.cluster_grid(images, [r for r, _ in cl], colorSpace, face_dev=faces.rows(j, j + 1), path=out("cluster_%02d.png" % (j + 1)))
     faces_host = faces.numpy(); faces.free()
-    if by_attr is not None:                                                                                             # :170-172
+    if by_attr is not None and out:                                                                                     # :170-172
         for i in range(len(by_attr)):
             render.similar_grid(images, by_attr[i], colorSpace, path=out("similar_attributes_%02d.png" % (i + 1)))
             render.similar_grid(images, by_pix[i], colorSpace, path=out("similar_pixelwise_%02d.png" % (i + 1)))
     MODEL_G.evaluate()
     nbFixed, nbCalc = min(512 + 16, N), min(1024, N)
     fixed = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbFixed), OPT.batchSize)                                 # :349
-    render.fixed_pairs_grid(images, fixed, min(52, N), colorSpace, path=out("fixed_pairs.png"))                         # :325-342
-    render.fixed_images_grid(images, nbFixed, path=out("fixed_images_%d_unfixed.png" % nbFixed))                        # :345-347
-    render.fixed_images_grid(fixed, nbFixed, path=out("fixed_images_%d.png" % nbFixed))                                 # :350-351
-    fixed_host = fixed.numpy(); fixed.free()
+    if out:
+        render.fixed_pairs_grid(images, fixed, min(52, N), colorSpace, path=out("fixed_pairs.png"))                     # :325-342
+        render.fixed_images_grid(images, nbFixed, path=out("fixed_images_%d_unfixed.png" % nbFixed))                    # :345-347
+        render.fixed_images_grid(fixed, nbFixed, path=out("fixed_images_%d.png" % nbFixed))                             # :350-351
+    fixed_host = np.concatenate([fixed.rows(lo, min(lo + OPT.batchSize, nbFixed)).numpy() for lo in range(0, nbFixed, OPT.batchSize)])
+    fixed.free()                # (one transfer per batch, as every other step here moves batches; the host array is nbFixed images either way)
     fixedCalc = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbCalc), OPT.batchSize)                              # :360-363
     dist = 1.0 - ctx.l2_distance_rows_dev(images.ptr, fixedCalc.ptr, nbCalc, chw)                                       # :366, scored where the images lie
     fixedCalc.free()
     srt = np.sort(dist)
     below = srt[max(int(math.floor(nbCalc * 0.15)) - 1, 0)]                                                             # :371-372
     is_anom = dist <= below
-    render.anomalies_grid(images, is_anom[:min(512 + 16, nbCalc)], colorSpace, path=out("anomalies.png"))               # :374-389
+    if out:
+        render.anomalies_grid(images, is_anom[:min(512 + 16, nbCalc)], colorSpace, path=out("anomalies.png"))           # :374-389
     return dict(clusters=(centroids, counts, clusters, list(faces_host)), fixed=fixed_host, anomalies=(dist, below, is_anom))
+
+
+def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributesFixer, by_attr, by_pix):
+    """analyseDev with the pictures of apply_r.lua:158-191 written as PNG files out(name)."""
+    return analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out, colorSpace, by_attr, by_pix)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -226,8 +266,12 @@ def parse(argv=None):
     scripts.add_dataset_options(p)                                            # apply_r.lua:16 --dataset (configured as there, never read)
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
+    p.add_argument("--resident", action="store_true", help="device-resident pipeline only: analyse the tables where the embedding wrote them; the image table is never copied to the host")
     p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
-    return p.parse_args(argv)
+    OPT = p.parse_args(argv)
+    if OPT.resident and OPT.host:
+        p.error("--resident applies to the device-resident pipeline: not with --host")
+    return OPT
 
 
 def main(argv=None):
@@ -260,7 +304,7 @@ def main(argv=None):
     MODEL_R_FIXER.manualSeed(OPT.seed)
     os.makedirs(OPT.writeTo, exist_ok=True)
     out = lambda name: os.path.join(OPT.writeTo, name)
-    summary = dict(dims=list(dims), noiseDim=nd, noiseMethod=method, nbImages=OPT.nbImages, batchSize=OPT.batchSize, path="host" if OPT.host else "device")
+    summary = dict(dims=list(dims), noiseDim=nd, noiseMethod=method, nbImages=OPT.nbImages, batchSize=OPT.batchSize, path="host" if OPT.host else "device-resident" if OPT.resident else "device")
 
     say("Varying components...")                                              # apply_r.lua:110-136
     nbSteps = 16
@@ -292,16 +336,25 @@ def main(argv=None):
     else:
         di, da, df = embed_dev(MODEL_G, MODEL_R, dn, OPT.batchSize, MODEL_R_FIXER, keep_images=True, dims=dims)
         by_attr, by_pix = createSimilaritySearchDev(5, 100, da, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
-        noise, images, attributes, attributesFixer = dn.numpy(), di.numpy(), da.numpy(), df.numpy()
-        for t in (dn, da) if OPT.render else (dn, di, da, df):
-            t.free()
+        attributes, attributesFixer = da.numpy(), df.numpy()
+        dn.free()
+        if not OPT.resident:
+            images = di.numpy()
+            if not OPT.render:
+                for t in (di, da, df):
+                    t.free()
     ctx.synchronize()
     summary["embed_and_search_seconds"] = round(time.perf_counter() - t0, 4)
     rendered = None
     if OPT.render:
         say("Rendering...")                                                   # from di / df, before they are freed
-        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, attributes, df, by_attr, by_pix)
-        di.free(); df.free()
+        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, attributes if OPT.host else da, df, by_attr, by_pix)
+    elif OPT.resident:
+        say("Analysing on the device...")
+        rendered = analyseDev(OPT, MODEL_G, di, da, df)
+    if rendered:
+        for t in (di, df) if OPT.host else (di, da, df):
+            t.free()
     np.save(out("attributes.npy"), attributes); np.save(out("attributes_fixer.npy"), attributesFixer)
     if by_attr is not None:
         np.save(out("similar_by_attributes.npy"), by_attr); np.save(out("similar_by_pixels.npy"), by_pix)

@@ -65,6 +65,11 @@ int gr_image_grid_dev(gr_ctx*, const float* const* src_dev, const int64_t* n_row
                       const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,
                       const float* inset_rgb, float fill, int auto_range, float lo, float hi, float* grid_dev, uint8_t* u8_dev);     /* image.toDisplayTensor + decorations, apply_r.lua / sample.lua */
 int gr_rows_mean_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_host, int n, float* out_dev);   /* apply_r.lua:233-243 */
+int gr_kmeans_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float* cent_dev, float* totalcounts_dev, int32_t* labels_dev);     /* apply_r.lua:198 */
+int gr_cosine_assign_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const float* cent_dev, int k, int take_min, int32_t* labels_dev, float* sims_dev);     /* apply_r.lua:205-217 */
+int gr_cluster_members_dev(gr_ctx*, const int32_t* labels_dev, const float* sims_dev, int64_t n, int k, int m, int64_t* rows_out_dev, float* sims_out_dev,
+                           int32_t* kept_out_dev, int32_t* sizes_out_dev);     /* apply_r.lua:218-227 */
+int gr_cluster_faces_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_dev, const int32_t* kept_dev, int k, int m, float* out_dev);     /* apply_r.lua:233-243 */
 int gr_progress_grid_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int channels, int h, int w, int from_space,
                          const int64_t* rows_host, int n_show, int grid_h, int grid_w, int epoch, float* grid_dev, uint8_t* u8_dev);     /* imagesToGridTensor, utils/nn_utils.lua:490-548 */
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);

@@ -395,6 +395,30 @@ int gr_kmeans_host(gr_ctx* ctx, const float* x_host, int64_t n, int d, int k, in
                    float* total_counts_out_host, int32_t* labels_out_host);
 int gr_cosine_assign_host(gr_ctx* ctx, const float* x_host, int64_t n, int d, const float* centroids_host, int k, int take_min,
                           int32_t* labels_out_host, float* sims_out_host);
+/* The clustering on the tables gr_embed_dev wrote (apply_r.lua:197-243).  Every pointer marked _dev is device memory; the work is enqueued
+ * on the ctx stream and the calls return without waiting for it; scratch comes from the context.
+ * gr_kmeans_dev (apply_r.lua:198) and gr_cosine_assign_dev (apply_r.lua:205-217) are gr_kmeans_host and gr_cosine_assign_host without the
+ * copies: the same kernels in the same order, the same bits.  cent_dev [k x d]: initial centroids in, final ones out; totalcounts_dev [k]
+ * and labels_dev [n] are nullable (labels_dev is written by the iterations: untouched when niter == 0).  k <= 32, d <= 256, else
+ * GR_ERR_UNSUPPORTED.
+ * gr_cluster_members_dev (apply_r.lua:218-227: table.sort by similarity, the first nbMaxPerCluster entries): for cluster j < k the
+ * min(m, members) rows i with labels_dev[i] == j that have the largest sims_dev[i], ordered by similarity descending (-0 and +0 are equal),
+ * ties by ascending row; a NaN similarity ranks after every number, NaNs among themselves by row - the order of a stable argsort of
+ * -similarity.  rows_out_dev (int64) and sims_out_dev are [k x m]; slots past the rows written hold -1 and 0.  kept_out_dev [k] = rows
+ * written, sizes_out_dev [k] = members of the cluster.  The result is a function of the inputs alone (a sort of distinct keys).
+ * 1 <= n < 2^31, k <= 32, m <= 128, else GR_ERR_UNSUPPORTED with a gr_last_error message; labels outside [0, k) belong to no cluster.
+ * gr_cluster_faces_dev (apply_r.lua:233-243): out_dev [k x d], row j = gr_rows_mean_dev of rows_dev[j][0 .. kept_dev[j]) over table_dev
+ * [n_rows x d] - the fp32 adds in list order, one division by kept_dev[j], bit for bit - all clusters in one launch; zeros for kept_dev[j] == 0.
+ * rows_dev is [k x m] int64; the lists are device data, so an entry outside [0, n_rows) is skipped by the kernel (the divisor stays
+ * kept_dev[j]) where gr_rows_mean_dev refuses it; kept_dev[j] is clamped to [0, m]. */
+int gr_kmeans_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int niter, float* cent_dev, float* totalcounts_dev /*nullable*/,
+                  int32_t* labels_dev /*nullable*/);
+int gr_cosine_assign_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, const float* cent_dev, int k, int take_min, int32_t* labels_dev,
+                         float* sims_dev);
+int gr_cluster_members_dev(gr_ctx* ctx, const int32_t* labels_dev, const float* sims_dev, int64_t n, int k, int m, int64_t* rows_out_dev,
+                           float* sims_out_dev, int32_t* kept_out_dev, int32_t* sizes_out_dev);
+int gr_cluster_faces_dev(gr_ctx* ctx, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_dev, const int32_t* kept_dev, int k, int m,
+                         float* out_dev);
 
 /* ---- device memory helpers for hosts without a tensor library (LuaJIT FFI, ctypes) ---- */
 int gr_malloc(gr_ctx* ctx, int64_t bytes, void** out_dev);
