@@ -612,10 +612,19 @@ def test_operand_ready_kernels_are_selected(ctx):
 
 @pytest.mark.parametrize("B,nin,nmid,nout", [(130, 1030, 1100, 37), (257, 2052, 640, 129), (128, 1024, 1024, 128)])
 def test_large_linear_ragged_shapes_vs_oracle(oracle, conv_mode, B, nin, nmid, nout):
-    """nn.Linear layers big enough for the f16x3 GEMM (>= 2^20 weights) at sizes that are not multiples of anything: partial
-    128-row tiles in M and N, a K tail (1030 = 32 * 32 + 6, not a multiple of 4: scalar tile loads), split-K and unsplit
-    plans, training-mode BatchNormalization after the first layer (models.lua:447-451 pattern), evaluate()-mode epilogue
-    (models.lua:115-117 pattern).  Forward, gradInput and the flat gradient against the oracle."""
+    """Two nn.Linear layers, the first big enough for the f16x3 GEMM (>= 2^20 weights), with training-mode BatchNormalization
+    behind it (models.lua:447-451 pattern).  Forward, gradInput and the flat gradient against the oracle, then an evaluate()-mode
+    forward.  What the three shapes reach according to tests/gemm_paths.py (f16x3 mode; in the other modes every GEMM is the fp32
+    kernel):
+      (130, 1030 -> 1100): forward and data gradient on the 128-tile kernel in 7 splits (forward: scalar tile loads, both store
+        paths into the slab; data gradient: scalar stores, 1030 % 4 != 0), weight gradient on the 128-tile kernel, unsplit;
+      (257, 2052 -> 640): forward in 13 and data gradient in 5 splits on the 128-tile kernel, both store paths; the weight gradient
+        falls back from the 128-tile plan to the 64-tile kernel, unsplit, K = 257;
+      (128, 1024 -> 1024): forward and data gradient on the 128-tile kernel in 8 splits with all-vector slab stores.
+    Every first-layer forward splits, so no shape here runs an unsplit f16x3 forward, and in evaluate() mode the epilogue is
+    refused each time (the stand-alone pipeline kernel runs).  The second layer (nmid -> 37 / 129 / 128 outputs) is below the
+    threshold: fp32 kernel, forward split in 7 / 5 / 8, the 640 -> 129 weight gradient split in 2.  No kernel label is checked
+    here and one tolerance scales with max|ref|; the per-path, per-element checks are tests/test_gpu_gemm_paths.py."""
     from ganrev import nn, synth
     net = nn.Sequential()
     net.add(nn.Linear(nin, nmid)); net.add(nn.BatchNormalization(nmid)); net.add(nn.ReLU())
