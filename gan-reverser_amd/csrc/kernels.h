@@ -343,6 +343,22 @@ void launch_conv1x1_backward_weight(const float* in, const float* gout, float* g
 size_t prelu_grad_workspace_bytes();
 void launch_prelu_grad(const float* g, const float* z, long n, double* part, float* gslope /*+=*/, hipStream_t s);
 
+// ---------------------------------------------------------------- grouped layer kinds (group.hip): exact fp32 in every mode, deterministic
+// GR_GROUPLINEAR: x [B][a], w [b][a/G], y [B][b]; group g maps inputs [g a/G, (g+1) a/G) to outputs [g b/G, (g+1) b/G)
+void launch_grouplinear_forward(const float* x, const float* w, const float* bias, float* y, int B, int a, int b, int G, hipStream_t s);
+void launch_grouplinear_backward_data(const float* gout, const float* w, float* gin, int B, int a, int b, int G, hipStream_t s);
+void launch_grouplinear_backward_weight(const float* x, const float* gout, float* gw /*+=*/, int B, int a, int b, int G, hipStream_t s);
+// GR_GROUPCONV3: w [Cout][Cin/G][3][3]; H x W are the convolution's planes; up: in / gin are [B][Cin][H/2][W/2] (nearest x2 up-sampling indexed in place)
+size_t groupconv3_workspace_bytes(int B, int Cin, int Cout, int G);
+void launch_groupconv3_forward(const float* in, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int G, int H, int W, bool up, hipStream_t s);
+void launch_groupconv3_backward_data(const float* gout, const float* w, float* gin, int B, int Cin, int Cout, int G, int H, int W, bool up, hipStream_t s);
+void launch_groupconv3_backward_weight(const float* in, const float* gout, float* gw /*+=*/, void* ws, int B, int Cin, int Cout, int G, int H, int W, bool up, hipStream_t s);
+// GR_PRELU with ns >= 2 slopes over [B][C][HW]: slope j covers channels [j C/ns, (j+1) C/ns)
+void launch_prelu_multi_forward(const float* x, const float* w, float* y, int B, int C, int HW, int ns, hipStream_t s);
+void launch_prelu_multi_backward(const float* g, const float* x, const float* w, float* gin, int B, int C, int HW, int ns, hipStream_t s);
+size_t prelu_multi_grad_workspace_bytes(int ns);
+void launch_prelu_multi_grad(const float* g, const float* x, int B, int C, int HW, int ns, double* part, float* gw /*+=*/, hipStream_t s);
+
 // ---------------------------------------------------------------- criterion / optimiser / misc
 void launch_mse(const float* x, const float* t, long n, long n_global, double* loss_dev, float* grad, hipStream_t s);
 // R's head in one launch (elem.hip, head_fwd_bwd_kernel): BatchNorm + act + Dropout of the fc1 stage, fc2 [+ Tanh], MSE, and their backward down to fc1's dy

@@ -3,6 +3,8 @@
 //
 // A gr_net is the reference's nn.Sequential (models.lua:104-143 G3, models.lua:389-464 R) compiled into
 // STAGES:  [UpSample2] (Conv3x3 | Linear) [BN] [act] [Dropout|SpatialDropout] [MaxPool2|AvgPool2] [Dropout]
+// (main operators also: the K x K convolution of convk.hip / conv1x1.hip and the grouped Linear / grouped 3x3 convolution of group.hip, which take the
+// generic route - raw output written, statistics by their own pass, fp32 tensors on both sides; an nn.PReLU(n) with n >= 2 slopes is a stage of its own)
 // Each stage runs as: main MFMA kernel -> (training) BN statistics -> one fused per-channel pipeline kernel.
 // Backward mirrors it (train_r.lua:151): pipeline backward (two passes around the BN reduction) ->
 // weight-gradient kernel -> data-gradient kernel.  All device memory is owned by the net / ctx; there is
@@ -331,7 +333,7 @@ extern "C" int gr_fill_normal_dev(gr_ctx* c, float* d, int64_t n, uint64_t seed)
 extern "C" int gr_fill_uniform_dev(gr_ctx* c, float* d, int64_t n, float lo, float hi, uint64_t seed) { if (!c || !d) return GR_ERR_INVALID; launch_fill_uniform(d, n, lo, hi, seed, c->stream); LAUNCHCHK(c); return GR_OK; }
 
 // ------------------------------------------------------------------ net
-enum { ST_CONV = 1, ST_LINEAR = 2, ST_ELEM = 3 };
+enum { ST_CONV = 1, ST_LINEAR = 2, ST_ELEM = 3, ST_GROUPLIN = 4, ST_GROUPCONV = 5 };      // 4, 5: GR_GROUPLINEAR / GR_GROUPCONV3 (group.hip), on the generic route GR_CONVK takes
 
 struct MaskSlot {
   int layer = -1, kind = MASK_NONE; float p = 0; int flags = 0;
@@ -349,7 +351,9 @@ struct Stage {
   bool has_bn = false; int64_t g_off = -1, be_off = -1;
   int act = ACT_NONE; float slope = 0;
   int ksz = 3;                              // window of the main convolution: 3 (conv.hip kernels) or an odd K convk.hip covers (GR_CONVK: 5, or 1 - conv1x1.hip)
-  int64_t slope_off = -1;                   // nn.PReLU: offset of its one learnable slope in the flat vectors
+  int64_t slope_off = -1;                   // nn.PReLU: offset of its one learnable slope (of its nslopes slopes) in the flat vectors
+  int groups = 0;                           // ST_GROUPLIN / ST_GROUPCONV: the number of groups
+  int nslopes = 0;                          // >= 2: this stage is one nn.PReLU(n) and nothing else, run by group.hip's kernels (no pipeline kernel)
   int m1 = -1, m2 = -1; bool pool = false;     // pool: this stage pools (2x2, stride 2) ...
   bool avg = false;                          // ... by the average (nn.SpatialAveragePooling: no pool_idx) rather than the maximum
   bool has_post = false;
@@ -447,7 +451,17 @@ static int plan_net(const gr_layer_desc* L, int nl, int in_c, int in_h, int in_w
         if (d.kind == GR_CONVK && !convk_supported(d.c)) return bad(GR_ERR_UNSUPPORTED, "layer %d: no kernel for a %dx%d convolution (3x3: GR_CONV3; 5x5: GR_CONVK)", i, d.c, d.c);
         const int k = d.kind == GR_CONVK ? d.c : 3;
         wo = off; off += (int64_t)d.a * d.b * k * k; bo = off; off += d.b; cc = d.b; break; }
-      case GR_PRELU: wo = off; off += 1; break;          // nn.PReLU(): weight = Tensor(1)
+      case GR_PRELU:                                     // nn.PReLU(): weight = Tensor(1); nn.PReLU(n), a = n >= 2: weight = Tensor(n)
+        if (d.a >= 2 && cc % d.a) return bad(GR_ERR_INVALID, "layer %d: PReLU with %d slopes does not divide %d channels", i, d.a, cc);
+        wo = off; off += d.a >= 2 ? d.a : 1; break;
+      case GR_GROUPLINEAR:
+        if (d.c < 1 || d.a < 1 || d.b < 1 || d.a % d.c || d.b % d.c) return bad(GR_ERR_INVALID, "layer %d: grouped linear %d -> %d does not divide into %d groups", i, d.a, d.b, d.c);
+        if (d.a != vol3(cc, h, w)) return bad(GR_ERR_INVALID, "layer %d: grouped linear expects %d inputs, got %lld", i, d.a, (long long)vol3(cc, h, w));
+        wo = off; off += (int64_t)d.b * (d.a / d.c); bo = off; off += d.b; cc = d.b; h = 1; w = 1; break;
+      case GR_GROUPCONV3:
+        if (d.c < 1 || d.a < 1 || d.b < 1 || d.a % d.c || d.b % d.c) return bad(GR_ERR_INVALID, "layer %d: grouped conv %d -> %d does not divide into %d groups", i, d.a, d.b, d.c);
+        if (d.a != cc) return bad(GR_ERR_INVALID, "layer %d: grouped conv expects %d input planes, got %d", i, d.a, cc);
+        wo = off; off += (int64_t)d.b * (d.a / d.c) * 9; bo = off; off += d.b; cc = d.b; break;
       case GR_LINEAR:
         if (d.a != vol3(cc, h, w)) return bad(GR_ERR_INVALID, "layer %d: linear expects %d inputs, got %lld", i, d.a, (long long)vol3(cc, h, w));
         wo = off; off += (int64_t)d.a * d.b; bo = off; off += d.b; cc = d.b; h = 1; w = 1; break;
@@ -473,14 +487,23 @@ static int plan_net(const gr_layer_desc* L, int nl, int in_c, int in_h, int in_w
     if (i >= nl) { if (!pl.st.empty()) pl.st.back().last = nl - 1; break; }
     s.inC = cc; s.inH = h; s.inW = w;
     if (L[i].kind == GR_UPSAMPLE2) {
-      if (i + 1 >= nl || L[i + 1].kind != GR_CONV3) return bad(GR_ERR_UNSUPPORTED, "layer %d: UpSamplingNearest(2) is only fused in front of a 3x3 convolution", i);
+      if (i + 1 >= nl || (L[i + 1].kind != GR_CONV3 && L[i + 1].kind != GR_GROUPCONV3)) return bad(GR_ERR_UNSUPPORTED, "layer %d: UpSamplingNearest(2) is only fused in front of a 3x3 convolution", i);
       r = take(i); if (r) return r;
       s.up = true; ++i;
     }
     const int k = L[i].kind;
-    if (k == GR_CONV3 || k == GR_FULLCONV3 || k == GR_CONVK || k == GR_LINEAR) {
+    if (k == GR_PRELU && L[i].a >= 2) {      // nn.PReLU(n): always a stage of its own
       r = take(i); if (r) return r;
-      s.kind = k == GR_LINEAR ? ST_LINEAR : ST_CONV; s.fullconv = k == GR_FULLCONV3; s.ksz = k == GR_CONVK ? L[i].c : 3;
+      s.kind = ST_ELEM; s.Cin = s.Cout = cc; s.H = h; s.W = w; s.nslopes = L[i].a; s.slope_off = wo; s.has_post = true;
+      s.last = i; s.outC = cc; s.outH = h; s.outW = w; ++i;
+      pl.st.push_back(s);
+      continue;
+    }
+    if (k == GR_CONV3 || k == GR_FULLCONV3 || k == GR_CONVK || k == GR_LINEAR || k == GR_GROUPLINEAR || k == GR_GROUPCONV3) {
+      r = take(i); if (r) return r;
+      s.kind = k == GR_LINEAR ? ST_LINEAR : k == GR_GROUPLINEAR ? ST_GROUPLIN : k == GR_GROUPCONV3 ? ST_GROUPCONV : ST_CONV;
+      s.groups = (k == GR_GROUPLINEAR || k == GR_GROUPCONV3) ? L[i].c : 0;
+      s.fullconv = k == GR_FULLCONV3; s.ksz = k == GR_CONVK ? L[i].c : 3;
       s.main_layer = i; s.Cin = L[i].a; s.Cout = L[i].b; s.H = h; s.W = w; s.w_off = wo; s.b_off = bo; ++i;
     } else {
       s.kind = ST_ELEM; s.Cin = s.Cout = cc; s.H = h; s.W = w;
@@ -495,6 +518,7 @@ static int plan_net(const gr_layer_desc* L, int nl, int in_c, int in_h, int in_w
       else if (d.kind == GR_MAXPOOL2 || d.kind == GR_AVGPOOL2) ph = 3;
       else break;
       if (ph <= phase) break;
+      if (d.kind == GR_PRELU && d.a >= 2) break;      // nn.PReLU(n) is the next stage, alone
       // nn.PReLU's slope gradient needs the activation's own input and gradOutput as tensors: the PReLU closes its stage (what
       // follows it - dropout, pooling - is the next, element-wise stage), and behind a BatchNorm it opens a stage of its own
       if (d.kind == GR_PRELU && s.has_bn) break;
@@ -737,8 +761,8 @@ static bool use_bf16x6(gr_net* n, const Stage& s) { return (n->ctx->conv_mode >=
 static int prep_weights(gr_net* n) {
   gr_ctx* c = n->ctx;
   const int mode = c->conv_mode;
-  bool any_full = false;
-  for (auto& s : n->st) any_full |= s.kind == ST_CONV && s.fullconv;
+  bool any_full = false;      // ... or an up-sampling stage of at most 4 input planes, whose data gradient dgrad3 keeps on the fp32 kernel in every mode
+  for (auto& s : n->st) any_full |= s.kind == ST_CONV && s.ksz == 3 && (s.fullconv || (s.up && s.Cin <= 4));
   for (int m = 0; m < 3; ++m) {
     if (!(m == mode || (m == 0 && any_full))) continue;
     if (n->prepped_version[m] == n->params_version) continue;
@@ -1010,6 +1034,15 @@ static bool p16_dy_ok(gr_net* n, const Stage& t) { return t.kind == ST_CONV && t
 // whether THIS forward wrote them is the caller's x_p16_gen / kb_gen test).  The contract between the passes: the forward may drop the
 // fp32 copy of t's input (out_skipped) only when this holds, and the backward then takes this weight gradient.
 static bool p16_wgrad_ok(gr_net* n, const Stage& t, int B) { return p16_dy_ok(n, t) && t.x_p16 && t.stat_part && conv_wgrad_p16_supported(B, t.Cin, t.Cout, t.H, t.W); }
+// The grouped main operators (group.hip): fp32 in every mode, raw output always written, no statistics tiles (the statistics pass runs), no scale
+// slot and no operand-ready tensor on either side (a grouped stage is no f16x3 consumer, so the stage before it hands over fp32)
+static int fwd_group(gr_net* n, Stage& s, const float* x, int B) {
+  gr_ctx* c = n->ctx;
+  s.stat_tiles_last = 0;
+  if (s.kind == ST_GROUPLIN) launch_grouplinear_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, B, s.Cin, s.Cout, s.groups, c->stream);
+  else launch_groupconv3_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
+  return GR_OK;
+}
 // ---- forward steps.  nx: the next stage when it is an f16x3 consumer (its scale slot amax_x is amax_next), else null.
 // K x K convolution (the D network's 5x5 layer): raw output always written, statistics by the pipeline
 static int fwd_convk(gr_net* n, Stage& s, const float* x, int B) {
@@ -1171,7 +1204,14 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
     unsigned* amax_next = nx ? nx->amax_x : nullptr;
     s.x_in = x; s.fused_epilogue = false; s.out_skipped = false;
     bool post_p16 = false;
-    if (s.kind == ST_CONV && s.ksz != 3) r = fwd_convk(n, s, x, B);
+    if (s.nslopes) {       // nn.PReLU(n): its own kernel; what consumes the output takes its maximum itself (input_absmax)
+      launch_prelu_multi_forward(x, n->params + s.slope_off, s.out, B, s.Cout, s.H * s.W, s.nslopes, c->stream);
+      LAUNCHCHK(c);
+      x = s.out;
+      continue;
+    }
+    if (s.kind == ST_GROUPLIN || s.kind == ST_GROUPCONV) r = fwd_group(n, s, x, B);
+    else if (s.kind == ST_CONV && s.ksz != 3) r = fwd_convk(n, s, x, B);
     else if (s.kind == ST_CONV) r = fwd_conv3(n, s, x, B, nx, amax_next, f16, post_p16);
     else if (s.kind == ST_LINEAR) r = fwd_linear(n, s, x, B, nx, amax_next);
     if (r) return r;
@@ -1422,6 +1462,19 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
   if (gx) dgrad3(n, s, dyb, dyp, gx, B, dgrad_p16);
   return GR_OK;
 }
+// grouped main operators: weight gradient (+=) and data gradient, both on the compute stream (no side stream: they are short and exact fp32)
+static int bwd_group(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
+  gr_ctx* c = n->ctx;
+  if (s.kind == ST_GROUPLIN) {
+    launch_grouplinear_backward_weight(x, dyb, n->grads + s.w_off, B, s.Cin, s.Cout, s.groups, c->stream);
+    if (gx) launch_grouplinear_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, c->stream);
+    return GR_OK;
+  }
+  const int r = ensure_ws(c, groupconv3_workspace_bytes(B, s.Cin, s.Cout, s.groups)); if (r) return r;
+  launch_groupconv3_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
+  if (gx) launch_groupconv3_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
+  return GR_OK;
+}
 // nn.Linear: gW[o][i] += sum_b dy[b][o] x[b][i], gx[b][i] = sum_o dy[b][o] W[o][i]
 static int bwd_linear(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
   gr_ctx* c = n->ctx;
@@ -1460,6 +1513,14 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
     const float* x = si == 0 ? in_dev : s.x_in;
     const bool need_gin = si > 0 || gin_dev != nullptr;
     float* gin = (si == 0 && gin_dev) ? gin_dev : n->g_buf[si & 1];
+    if (s.nslopes) {       // nn.PReLU(n): g is its gradOutput, the stage input its input; the slopes' gradients, then gradInput
+      r = ensure_ws(c, prelu_multi_grad_workspace_bytes(s.nslopes)); if (r) return r;
+      launch_prelu_multi_grad(g, x, B, s.Cout, s.H * s.W, s.nslopes, static_cast<double*>(c->ws), n->grads + s.slope_off, c->stream);
+      if (need_gin) launch_prelu_multi_backward(g, x, n->params + s.slope_off, gin, B, s.Cout, s.H * s.W, s.nslopes, c->stream);
+      LAUNCHCHK(c);
+      g = gin;
+      continue;      // (its slopes lie inside the bucket of the stage in front of it: nothing to reduce here)
+    }
     // pipeline backward: g (wrt stage output) -> dy (wrt raw main-op output / ELEM input)
     // dy pair of this stage; the side-stream weight gradient that last read it (two stages ago) must be done before it is rewritten
     const int dk = si & 1;
@@ -1490,7 +1551,8 @@ static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, 
     }
     LAUNCHCHK(c);
     float* const gx = need_gin ? gin : nullptr;
-    if (s.kind == ST_CONV && s.ksz != 3) r = bwd_convk(n, s, x, dyb, gx, B);
+    if (s.kind == ST_GROUPLIN || s.kind == ST_GROUPCONV) r = bwd_group(n, s, x, dyb, gx, B);
+    else if (s.kind == ST_CONV && s.ksz != 3) r = bwd_convk(n, s, x, dyb, gx, B);
     else if (s.kind == ST_CONV) r = bwd_conv3(n, s, x, dyb, dyp, gx, B, dk, dgrad_p16, wgrad_p16);
     else if (s.kind == ST_LINEAR) r = bwd_linear(n, s, x, dyb, gx, B);
     if (r) return r;
@@ -1704,6 +1766,7 @@ static bool head_plan(gr_net* n, int B, HeadLaunch& h) {
   gr_ctx* c = n->ctx;
   const size_t nst = n->st.size();
   if (nst < 3 || !n->training || (c->sync_bn && have_peers(c)) || n->keep_fp32) return false;
+  for (auto& s : n->st) if (s.groups || s.nslopes) return false;      // a net with a grouped kind takes the stage-by-stage path
   Stage& s1 = n->st[nst - 2]; Stage& s2 = n->st[nst - 1];
   if (s1.kind != ST_LINEAR || s2.kind != ST_LINEAR || !s1.has_post || !s1.has_bn || s1.pool || s1.m2 >= 0 || s1.H != 1 || s1.W != 1) return false;
   if (s1.act == ACT_PRELU || s2.has_bn || s2.pool || s2.m1 >= 0 || s2.m2 >= 0 || !(s2.act == ACT_NONE || s2.act == ACT_TANH)) return false;

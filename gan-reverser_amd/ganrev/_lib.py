@@ -32,6 +32,7 @@ STATUS = {0: "GR_OK", -1: "GR_ERR_INVALID", -2: "GR_ERR_UNSUPPORTED", -3: "GR_ER
 CONV3, BN, ELU, RELU, LEAKYRELU, SIGMOID, TANH, DROPOUT, SPATIAL_DROPOUT, MAXPOOL2, UPSAMPLE2, VIEW, LINEAR, FULLCONV3 = range(1, 15)
 CONVK, PRELU = 15, 16       # the D network's extra module types (models.lua:272-337)
 AVGPOOL2 = 17               # nn.SpatialAveragePooling(2,2,2,2) (models.lua:71,235,242,249,348-363)
+GROUPLINEAR, GROUPCONV3 = 18, 19   # the grouped kinds of create_G4's bundle (models.lua:145-194); PRELU with a = n >= 2 is nn.PReLU(n): one slope per C / n channels
 DROPOUT_V2, DROPOUT_ALWAYS_ON = 1, 2
 GR_CS_RGB, GR_CS_Y, GR_CS_YUV, GR_CS_HSL = 0, 1, 2, 3      # gr_colorspace_*: the reference's four colour spaces (train.lua:45, dataset.lua:27-33)
 COLOR_SPACES = {"rgb": GR_CS_RGB, "y": GR_CS_Y, "yuv": GR_CS_YUV, "hsl": GR_CS_HSL}
@@ -647,10 +648,16 @@ def default_context():
 
 
 class Net:
-    """gr_net handle: a compiled nn.Sequential."""
+    """gr_net handle: a compiled nn.Sequential.
 
-    def __init__(self, ctx, descs, in_dims):
+    perm (optional): the net keeps its flat vectors in another order than the module tree's getParameters() - a bundle of nn.Concat
+    branches (ganrev.nn.bundle_plan) is layer-major on the device, branch-major in the tree.  net_flat = tree_flat[perm].  The
+    host <-> device transfers of the flat vectors below are the ONE place that knows: callers see tree order, and everything that
+    consumes the vectors on the device (Adam / the optim rules, penalty, clamp, the gradient all-reduce) is element-wise."""
+
+    def __init__(self, ctx, descs, in_dims, perm=None):
         self.ctx, self.lib = ctx, ctx.lib
+        self.perm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int64)
         arr = (LayerDesc * len(descs))(*[LayerDesc(*d) for d in descs])
         h = _P()
         c, hh, w = in_dims
@@ -661,6 +668,7 @@ class Net:
         ctx.check(self.lib.gr_net_out_dim(h, C.byref(oc), C.byref(oh), C.byref(ow)), "gr_net_out_dim")
         self.out_dims = (oc.value, oh.value, ow.value)
         self.n_params = int(self.lib.gr_net_param_count(h))
+        assert self.perm is None or self.perm.size == self.n_params, (self.perm.size, self.n_params)
         self.training = True               # the mode set_training last gave the net (a new gr_net is in training mode)
 
     def close(self):
@@ -680,23 +688,34 @@ class Net:
     def _c(self, rc, what):
         self.ctx.check(rc, what)
 
+    def _to_net(self, a):
+        """a flat vector in tree order -> the net's order"""
+        return a if self.perm is None or a is None else np.ascontiguousarray(a.reshape(-1)[self.perm])
+
+    def _to_tree(self, a):
+        if self.perm is None:
+            return a
+        out = np.empty_like(a)
+        out[self.perm] = a
+        return out
+
     def get_params(self):
         a = np.empty(self.n_params, dtype=np.float32)
         self._c(self.lib.gr_net_get_params(self.h, _ptr(a)), "gr_net_get_params")
-        return a
+        return self._to_tree(a)
 
     def set_params(self, a):
-        a = f32(a)
+        a = self._to_net(f32(a))
         assert a.size == self.n_params
         self._c(self.lib.gr_net_set_params(self.h, _ptr(a)), "gr_net_set_params")
 
     def get_grads(self):
         a = np.empty(self.n_params, dtype=np.float32)
         self._c(self.lib.gr_net_get_grads(self.h, _ptr(a)), "gr_net_get_grads")
-        return a
+        return self._to_tree(a)
 
     def set_grads(self, a):
-        a = f32(a)
+        a = self._to_net(f32(a))
         self._c(self.lib.gr_net_set_grads(self.h, _ptr(a)), "gr_net_set_grads")
 
     def zero_grads(self):
@@ -787,10 +806,10 @@ class Net:
     def adam_state(self):
         m, v = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
         self._c(self.lib.gr_adam_get_state(self.h, _ptr(m), _ptr(v)), "gr_adam_get_state")
-        return m, v
+        return self._to_tree(m), self._to_tree(v)
 
     def set_adam_state(self, m, v):
-        m, v = f32(m), f32(v)
+        m, v = self._to_net(f32(m)), self._to_net(f32(v))
         self._c(self.lib.gr_adam_set_state(self.h, _ptr(m), _ptr(v)), "gr_adam_set_state")
 
     def optim_step(self, config, t):
@@ -804,10 +823,10 @@ class Net:
         """the net's two state vectors (slot 0, slot 1): what they mean is the method's business (OPT_STATE_KEYS)"""
         a, b = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
         self._c(self.lib.gr_optim_get_state(self.h, _ptr(a), _ptr(b)), "gr_optim_get_state")
-        return a, b
+        return self._to_tree(a), self._to_tree(b)
 
     def set_optim_state(self, slot0=None, slot1=None):
-        slot0, slot1 = (None if s is None else f32(s) for s in (slot0, slot1))
+        slot0, slot1 = (None if s is None else self._to_net(f32(s)) for s in (slot0, slot1))
         assert all(s is None or s.size == self.n_params for s in (slot0, slot1))
         self._c(self.lib.gr_optim_set_state(self.h, _ptr(slot0), _ptr(slot1)), "gr_optim_set_state")
 

@@ -86,7 +86,8 @@ class DeviceModel:
         if any(n is None for n in self.nets):
             raise L.GanrevError("compile the model first (one forward)")
         if any(isinstance(m, nn.Concat) and m.dimension != 2 for m in model.listModules()):
-            raise L.GanrevError("device-resident nn.Concat: only nn.Concat(2) of [batch x features] outputs (models.lua:293)")
+            raise L.GanrevError("device-resident nn.Concat: only nn.Concat(2), the join along the feature / channel dimension "
+                                "(models.lua:155,293)")
         self.kids, self.x = {}, {}          # id(container) -> its children() / the device input of its last forward (borrowed)
         self.branches = {}                  # id(table block) -> every branch, nn.Identity ones included
         todo = [model]
@@ -97,6 +98,21 @@ class DeviceModel:
                 if not self.kids[id(node)]:
                     raise L.GanrevError("device-resident nn.ConcatTable: at least one branch must hold a net")
             todo.extend(self.kids[id(node)] or ())
+        for node in todo:
+            # [B x C x H x W] branch outputs: joining channels in NCHW is joining each sample's features, which is what copy2d does -
+            # as long as every branch has the same H x W (the host nn.Concat refuses the others at its first forward)
+            if isinstance(node, nn.Concat) and len({self.out_dims(b)[1:] for b in self.kids[id(node)]}) > 1:
+                raise L.GanrevError(f"device-resident nn.Concat(2): branch outputs {[self.out_dims(b) for b in self.kids[id(node)]]} do not line up")
+
+    def out_dims(self, node):
+        """per-sample (C, H, W) a node hands on"""
+        kids = self.kids[id(node)]
+        if kids is None:
+            return tuple(int(d) for d in node._net.out_dims)
+        if isinstance(node, nn.Concat):
+            outs = [self.out_dims(b) for b in kids]
+            return (sum(o[0] for o in outs),) + outs[0][1:]
+        return self.out_dims(kids[-1])
 
     def out_features(self, node):
         kids = self.kids[id(node)]

@@ -2,7 +2,8 @@
 104-143), create_R -> create_R_default (models.lua:385-387, 389-464) and create_D -> create_D2 (models.lua:209-211, 272-337;
 the discriminator adversarial.lua trains G against - SURVEY.md 8f rank 4); create_G_encoder (models.lua:57-102, pretrain_g.lua's
 encoder half) and the two D variants with average pooling, create_D_default and create_D_facegen (models.lua:213-270, 339-383),
-which nothing selects (the reference's create_D returns create_D2); createResidual (models.lua:8-55), the residual block the
+which nothing selects (the reference's create_D returns create_D2); create_G4 (models.lua:145-194), the 32-branch generator
+that nothing selects either; createResidual (models.lua:8-55), the residual block the
 reference's author left for edited models.  Same layer lists, same argument meaning."""
 from . import nn
 from .weight_init import w_init
@@ -83,6 +84,44 @@ def create_G3(dimensions, noiseDim, cuda=True, seed=0):
         model.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))
         model.cuda()
     return w_init(model, "heuristic", seed)
+
+
+def create_G4(dimensions, noiseDim, cuda=True, seed=0):
+    """models.lua:145-194: nn.Concat(2) of 32 branches, each Linear(noiseDim, 16) - PReLU - Linear(16, 16*16*16) - BatchNorm - PReLU -
+    Reshape(16, 16, 16) - up-sampling - 3x3 conv 16 -> 16 - BatchNorm - PReLU, joined to 512 x 32 x 32; then a 3x3 conv 512 -> 64 -
+    BatchNorm - PReLU and a 3x3 conv 64 -> channels - Sigmoid.  As in the reference, startHeight / startWidth are computed and not
+    used: the branches are 16 x 16 whatever `dimensions` says, so the output is channels x 32 x 32.  The 32 branches are
+    structurally identical, so the model compiles to ONE grouped gr_net (nn.bundle_plan) and is a plain net to every caller."""
+    nn.manualSeed(seed)
+    model = nn.Sequential()
+    if cuda:
+        model.add(nn.Copy("torch.FloatTensor", "torch.CudaTensor", True, True))
+    startHeight = dimensions[1] // 2 // 2          # models.lua:152-153: computed, used nowhere
+    startWidth = dimensions[2] // 2 // 2
+    concat = nn.Concat(2)
+    for _ in range(32):
+        seq = nn.Sequential()
+        seq.add(nn.Linear(noiseDim, 16))
+        seq.add(nn.PReLU())
+        seq.add(nn.Linear(16, 16 * 16 * 16))
+        seq.add(nn.BatchNormalization(16 * 16 * 16))
+        seq.add(nn.PReLU())
+        seq.add(nn.Reshape(16, 16, 16))
+        seq.add(nn.SpatialUpSamplingNearest(2))
+        seq.add(_CudnnSpatialConvolution(16, 16, 3, 3, 1, 1, 1, 1))
+        seq.add(nn.SpatialBatchNormalization(16))
+        seq.add(nn.PReLU())
+        concat.add(seq)
+    model.add(concat)
+    model.add(_CudnnSpatialConvolution(32 * 16, 64, 3, 3, 1, 1, 1, 1))
+    model.add(nn.SpatialBatchNormalization(64))
+    model.add(nn.PReLU())
+    model.add(_CudnnSpatialConvolution(64, dimensions[0], 3, 3, 1, 1, 1, 1))
+    model.add(nn.Sigmoid())
+    if cuda:
+        model.add(nn.Copy("torch.CudaTensor", "torch.FloatTensor", True, True))
+        model.cuda()
+    return w_init(model, "heuristic", seed)     # top-level modules only: the two tail convolutions get their bias zeroed, no branch is touched
 
 
 def create_G_encoder(dimensions, noiseDim, cuda=True, seed=0):

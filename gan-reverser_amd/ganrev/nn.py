@@ -127,10 +127,18 @@ class Module:
         descs, self._layer_index = self._descs(dims)
         if not descs:
             raise L.GanrevError("empty module")
-        self._net = L.Net(self._context(), descs, dims)
+        self._net = L.Net(self._context(), descs, dims, perm=self._perm(dims))
         self._net_key = dims
         self.push_params()
         return self._net
+
+    def _perm(self, dims):
+        """net_flat = tree_flat[perm] when the compiled net orders its parameters differently from the tree (a bundle), else None"""
+        return None
+
+    def _bn_groups(self):
+        """per BatchNorm layer of the compiled net, the BatchNorm modules whose running statistics it holds, concatenated in this order"""
+        return [[m] for m in self.leaves() if isinstance(m, BatchNormalization)]
 
     def _flat_host(self):
         arrs = [a for m in self.leaves() for a in m.param_arrays()]
@@ -149,11 +157,8 @@ class Module:
 
     def push_bn_running(self):
         """host BatchNorm running statistics -> device (what a training-mode forward overwrote there: device.compile_models)"""
-        bi = 0
-        for m in self.leaves():
-            if isinstance(m, BatchNormalization):
-                self._net.set_bn_running(bi, m.running_mean, m.running_var)
-                bi += 1
+        for bi, mods in enumerate(self._bn_groups()):
+            self._net.set_bn_running(bi, np.concatenate([m.running_mean for m in mods]), np.concatenate([m.running_var for m in mods]))
 
     def pull_params(self):
         """device -> host parameter arrays (+ BN running stats)."""
@@ -170,11 +175,12 @@ class Module:
                     new.append(flat[off:off + a.size].reshape(a.shape).copy())
                     off += a.size
                 m.set_param_arrays(new)
-        bi = 0
-        for m in self.leaves():
-            if isinstance(m, BatchNormalization):
-                m.running_mean, m.running_var = self._net.get_bn_running(bi)
-                bi += 1
+        for bi, mods in enumerate(self._bn_groups()):
+            mean, var = self._net.get_bn_running(bi)
+            lo = 0
+            for m in mods:
+                m.running_mean, m.running_var = mean[lo:lo + m.nFeature].copy(), var[lo:lo + m.nFeature].copy()
+                lo += m.nFeature
 
     def getParameters(self):
         """Flattens every parameter into one storage; module weight/bias become views into it (train_r.lua:122)."""
@@ -392,11 +398,47 @@ class Sequential(_Container):
     # Host arrays travel between the parts, as Torch7 tensors travel between the modules of the reference's containers.
     # An nn.ConcatTable followed by its nn.CAddTable (models.lua:41-53, createResidual) is ONE branching part: the table of branch
     # outputs exists only between the two.
+    def _has_graph(self):
+        return any(isinstance(m, (Concat, ConcatTable, CAddTable)) or (isinstance(m, Sequential) and m._has_graph()) for m in self.modules)
+
     def _is_graph(self):
-        return any(isinstance(m, (Concat, ConcatTable, CAddTable)) or (isinstance(m, Sequential) and m._is_graph()) for m in self.modules)
+        return self._has_graph() and self._bundle() is None
 
     def children(self):
         return self.parts() if self._is_graph() else None
+
+    # ---- the bundle: an nn.Concat(2) of structurally identical branches (models.lua:155-172, create_G4) is one chain of grouped layers over
+    # the concatenated features, so this Sequential compiles - with the modules behind the Concat - to ONE gr_net and is a plain net to every
+    # caller (children() is None).  bundle_plan states the pattern and the translation.  `concat.bundle = False` before the first forward
+    # keeps the parts route (tests, tools/bench_g4.py); not a user knob.
+    def _bundle(self):
+        """the nn.Concat this Sequential compiles as a bundle, or None"""
+        cat = next((m for m in self.modules if isinstance(m, Concat)), None)
+        key = None if cat is None else (id(cat), len(self.modules), len(cat.modules), sum(len(b.modules) for b in cat.modules), getattr(cat, "bundle", True))
+        if getattr(self, "_bundle_key", ()) != key:
+            self._bundle_key, self._bundle_plans = key, {}
+            self._bundle_cat = cat if cat is not None and key[-1] and _bundle_pattern(self) is not None else None
+        return self._bundle_cat
+
+    def _plan(self, dims):
+        dims = tuple(int(d) for d in dims)
+        if dims not in self._bundle_plans:
+            self._bundle_plans[dims] = bundle_plan(self, dims)
+        return self._bundle_plans[dims]
+
+    def _descs(self, dims):
+        if self._bundle() is None:
+            return Module._descs(self, dims)
+        return list(self._plan(dims)[0]), {}          # (no layer index: a bundle holds no Dropout whose noise could be injected)
+
+    def _perm(self, dims):
+        return None if self._bundle() is None else self._plan(dims)[1]
+
+    def _bn_groups(self):
+        if self._bundle() is None:
+            return Module._bn_groups(self)
+        bns = [m for m in self.leaves() if isinstance(m, BatchNormalization)]
+        return [[bns[i] for i in group] for group in self._plan(self._net_key)[2]]
 
     def parts(self):
         if getattr(self, "_parts", None) is None:
@@ -410,7 +452,7 @@ class Sequential(_Container):
                     if not mods or not isinstance(mods[0], CAddTable):
                         raise L.GanrevError("nn.ConcatTable: only with an nn.CAddTable directly behind it (models.lua:41-53)")
                     m = _TableSum(m, mods.pop(0))
-                if isinstance(m, (Concat, _TableSum)) or (isinstance(m, Sequential) and m._is_graph()):
+                if isinstance(m, (Concat, _TableSum)) or (isinstance(m, Sequential) and m._has_graph()):
                     if run is not None:
                         parts.append(run)
                         run = None
@@ -447,6 +489,13 @@ class Sequential(_Container):
             g = p.backward(x, g, scale)
         self.gradInput = g
         return g
+
+    def device_net(self, dims):
+        if self._is_graph():
+            raise L.GanrevError(f"this model runs as {len(self._param_chunks())} nets (it holds an nn.Concat or an nn.ConcatTable): the single-net "
+                                "device-resident paths (forwardBatchedDev, apply_r.embed_dev, train_r's DeviceTrainer) cannot take it - use "
+                                "the host-tensor paths (train_r --compat, apply_r --host) or device.DeviceModel")
+        return Module.device_net(self, dims)
 
     def manualSeed(self, seed):
         if not self._is_graph():
@@ -820,7 +869,8 @@ class LeakyReLU(Module):
 class PReLU(Module):
     """nn.PReLU(nOutputPlane=0): y = x > 0 ? x : w * x with ONE learnable slope w, initial value 0.25 (models.lua:276 and
     every other activation of the D networks).  The slope is a parameter: it sits in getParameters()' flat vector where
-    the module sits in the network."""
+    the module sits in the network.  (The library's GR_PRELU also takes n >= 2 slopes - a bundle's PReLU layers, bundle_plan - but
+    nn.PReLU(n) itself is still refused here: tests/test_host_logic.py pins the refusal.)"""
     TYPENAME = "nn.PReLU"
 
     def __init__(self, nOutputPlane=0):
@@ -933,6 +983,118 @@ class View(Module):
         if int(np.prod(s)) != int(np.prod(dims)):
             raise L.GanrevError(f"nn.View{self.sizes}: input has {int(np.prod(dims))} elements per sample")
         return [(L.VIEW, s[0], s[1], s[2], 0.0, 0)], s
+
+
+class Reshape(View):
+    """nn.Reshape(size1, size2, ...) (models.lua:165, create_G4's branches): on a batched contiguous tensor what nn.View does - the
+    same GR_VIEW layer - under its own class name, which the checkpoint keeps."""
+    TYPENAME = "nn.Reshape"
+
+    def desc(self, dims):
+        s = self.sizes + (1,) * (3 - len(self.sizes))
+        if int(np.prod(s)) != int(np.prod(dims)):
+            raise L.GanrevError(f"nn.Reshape{self.sizes}: input has {int(np.prod(dims))} elements per sample")
+        return [(L.VIEW, s[0], s[1], s[2], 0.0, 0)], s
+
+
+# ---------------------------------------------------------------------------------------------------------------- the bundle
+def _bundle_pattern(model):
+    """The structural half of bundle_plan (no dims): -> (modules behind the Concat, the Concat) when `model` is a Sequential of [an
+    nn.Concat(2) of >= 2 nn.Sequential branches with the same module types and sizes, module by module, the first an nn.Linear, every one
+    of Linear | BatchNormalization | SpatialBatchNormalization | shared-slope PReLU | Reshape / View | SpatialUpSamplingNearest(2) | 3x3
+    stride-1 pad-1 convolution] followed by plain modules only; else None."""
+    if not isinstance(model, Sequential):
+        return None
+    mods = [m for m in model.modules if isinstance(m, _Container) or m.leaves()]          # (nn.Copy and nn.Identity are no layers)
+    if not mods or not isinstance(mods[0], Concat) or any(isinstance(m, (_Container, CAddTable)) for m in mods[1:]):
+        return None
+    cat = mods[0]
+    if cat.dimension != 2 or len(cat.modules) < 2:
+        return None
+
+    def sig(m):
+        if type(m) is Linear:
+            return ("linear",) + m.weight.shape
+        if isinstance(m, BatchNormalization):
+            return ("bn", m.nFeature)
+        if type(m) is PReLU and m.nOutputPlane == 0:
+            return ("prelu",)
+        if isinstance(m, View):
+            return ("view",) + m.sizes
+        if isinstance(m, SpatialUpSamplingNearest):
+            return ("up",)
+        if isinstance(m, SpatialConvolution) and not isinstance(m, SpatialFullConvolution) and m.kW == 3:
+            return ("conv", m.nInputPlane, m.nOutputPlane)
+        return None
+    sigs = []
+    for b in cat.modules:
+        if not isinstance(b, Sequential) or any(isinstance(m, _Container) for m in b.modules):
+            return None
+        sigs.append([sig(m) for m in b.modules if m.leaves()])
+    first = sigs[0]
+    if not first or None in first or first[0][0] != "linear" or any(s != first for s in sigs[1:]):
+        return None
+    return mods[1:], cat
+
+
+def bundle_plan(model, dims):
+    """-> (descs, perm, bn_map) when `model` compiles as a bundle (_bundle_pattern) for per-sample input dims, else None.  Pure: no GPU.
+    With nb branches, per branch position:  first Linear(n, m) -> LINEAR(n, nb m);  later Linear(m, k) -> GROUPLINEAR(nb m, nb k, nb);
+    BN(k) -> BN(nb k);  PReLU() -> PRELU(a = nb);  Reshape(c, h, w) -> VIEW(nb c, h, w);  up-sampling -> UPSAMPLE2;
+    conv(c, c') -> GROUPCONV3(nb c, nb c', nb); then the modules behind the Concat as they are.
+    perm: net_flat = tree_flat[perm] (the tree's getParameters() order is branch-major, the net's layer-major: per layer and parameter
+    tensor, the branches' tensors one after another).  bn_map[i]: the indices, among the tree's BatchNorm modules in tree order, of the
+    modules whose running statistics BatchNorm layer i of the net holds, concatenated."""
+    pat = _bundle_pattern(model)
+    if pat is None or getattr(pat[1], "bundle", True) is False:
+        return None
+    tail, cat = pat
+    dims = tuple(int(d) for d in (dims if len(dims) == 3 else (dims[0], 1, 1)))
+    nb = len(cat.modules)
+    offs, bn_index, off = {}, {}, 0
+    for m in model.leaves():
+        offs[id(m)] = []
+        for a in m.param_arrays():
+            offs[id(m)].append((off, a.size))
+            off += a.size
+        if isinstance(m, BatchNormalization):
+            bn_index[id(m)] = len(bn_index)
+    descs, perm, bn_map = [], [], []
+
+    def place(mods):
+        """the parameter tensors of one layer: per tensor (weight, bias, ...), the modules' ranges one after another"""
+        for q in range(len(offs[id(mods[0])])):
+            for m in mods:
+                lo, n = offs[id(m)][q]
+                perm.append(np.arange(lo, lo + n, dtype=np.int64))
+        if isinstance(mods[0], BatchNormalization):
+            bn_map.append([bn_index[id(m)] for m in mods])
+    branches = [[m for m in b.modules if m.leaves()] for b in cat.modules]
+    d = dims
+    for p, m in enumerate(branches[0]):
+        (kind, a, b, c, pp, flags), = m.desc(d)[0]
+        nd_ = m.desc(d)[1]
+        if type(m) is Linear:
+            descs.append((L.LINEAR, a, nb * b, 0, 0.0, 0) if p == 0 else (L.GROUPLINEAR, nb * a, nb * b, nb, 0.0, 0))
+        elif isinstance(m, BatchNormalization):
+            descs.append((L.BN, nb * a, 0, 0, 0.0, 0))
+        elif type(m) is PReLU:
+            descs.append((L.PRELU, nb, 0, 0, 0.0, 0))
+        elif isinstance(m, View):
+            descs.append((L.VIEW, nb * a, b, c, 0.0, 0))
+        elif isinstance(m, SpatialUpSamplingNearest):
+            descs.append((L.UPSAMPLE2, 0, 0, 0, 0.0, 0))
+        else:
+            descs.append((L.GROUPCONV3, nb * a, nb * b, nb, 0.0, 0))
+        place([br[p] for br in branches])
+        d = nd_
+    d = (nb * d[0],) + tuple(d[1:])
+    for m in tail:
+        for x in m.leaves():
+            ds, d = x.desc(d)
+            descs.extend(ds)
+            place([x])
+    return descs, (np.concatenate(perm) if perm else np.zeros(0, np.int64)), bn_map
 
 
 class MSECriterion:

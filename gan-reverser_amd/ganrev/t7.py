@@ -356,6 +356,10 @@ def to_model(obj):
     if t == "nn.View":
         size = f.get("size")
         return nn.View(*[int(v) for v in np.asarray(size).ravel()])
+    if t == "nn.Reshape":                    # create_G4's branches (models.lua:165)
+        if f.get("batchMode") is False:
+            raise ValueError("nn.Reshape: batchMode = false (the batch folded into the new shape) is not implemented")
+        return nn.Reshape(*[int(v) for v in np.asarray(f.get("size")).ravel()])
     raise ValueError(f"no ganrev counterpart for {t}")
 
 
@@ -404,6 +408,9 @@ def from_model(model):
         f.update(kW=2, kH=2, dW=2, dH=2, padW=0, padH=0, ceil_mode=False, count_include_pad=True, divide=True)
     elif isinstance(model, nn.SpatialUpSamplingNearest):
         f.update(scale_factor=2, inputSize=np.zeros(4, np.int64), outputSize=np.zeros(4, np.int64))
+    elif isinstance(model, nn.Reshape):
+        # nn.Reshape keeps two torch.LongStorages: size, and batchsize = {batch, size...} whose first entry every forward overwrites
+        f.update(size=storage(model.sizes), batchsize=storage((1,) + model.sizes), nelement=int(np.prod(model.sizes)))
     elif isinstance(model, nn.View):
         f.update(size=storage(model.sizes), numElements=int(np.prod(model.sizes)))            # nn.View keeps a torch.LongStorage
     elif isinstance(model, nn.ELU):
@@ -420,7 +427,7 @@ def load_checkpoint(path):
         if isinstance(v, TorchObject) and v.typename == "nn.Sequential":
             try:
                 out[k] = to_model(v)
-            except Exception as e:          # a layer this path has no kernel for (e.g. a 3x3 SpatialAveragePooling, create_G4's layers): keep the raw tree
+            except Exception as e:          # a layer this path has no kernel for (e.g. a 3x3 SpatialAveragePooling): keep the raw tree
                 out[k] = v
                 out.setdefault("_unconverted", {})[k] = str(e)
         else:

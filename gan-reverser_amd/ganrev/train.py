@@ -55,6 +55,8 @@ def parse(argv=None):
     p.add_argument("--G_sgd_lr", type=float, default=0.02)
     p.add_argument("--D_sgd_momentum", type=float, default=0.0)
     p.add_argument("--G_sgd_momentum", type=float, default=0.0)
+    p.add_argument("--G_model", default="create_G3", choices=["create_G3", "create_G4"],
+                   help="the constructor of a fresh G: models.create_G3 (what models.create_G returns) or the 32-branch models.create_G4 (32x32 only)")
     p.add_argument("--noiseDim", type=int, default=100)
     p.add_argument("--noiseMethod", default="normal", choices=["normal", "uniform"])
     p.add_argument("--height", type=int, default=32)
@@ -78,7 +80,10 @@ def pretrained_G_path(OPT, dims):
 
 
 def create_or_load_G(OPT, dims):
-    """train.lua:148-161: pretrain_g.lua's decoder in training mode, or a fresh create_G"""
+    """train.lua:148-161: pretrain_g.lua's decoder in training mode, or a fresh create_G; --G_model create_G4 builds models.create_G4
+    instead (always fresh: pretrain_g trains create_G's decoder only)"""
+    if OPT.G_model == "create_G4":
+        return models.create_G4(dims, OPT.noiseDim, True, OPT.seed + 1)
     path = pretrained_G_path(OPT, dims)
     if path is None:
         if not OPT.quiet:
@@ -108,6 +113,9 @@ def main(argv=None):
     OPT = parse(argv)
     scripts.refuse_progress_in_compat(OPT)
     dims = scripts.image_dims(OPT.colorSpace, OPT.height, OPT.width)
+    if OPT.G_model == "create_G4" and not OPT.network and (OPT.height, OPT.width) != (32, 32):
+        # models.lua:152-153 computes a start size and never uses it: the branches are 16x16 -> 32x32 whatever the options say
+        raise SystemExit("--G_model create_G4 paints 32x32 images only (models.lua:157-183): got --height %d --width %d" % (OPT.height, OPT.width))
     ctx = L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
     epoch0, ck = 1, {}

@@ -162,6 +162,7 @@ def main(argv=None):
             if batchIdx % OPT.saveFreq == 0:                             # :185-187
                 save()
     else:
+        MODEL_G.device_net((OPT.noiseDim,))                              # a G of several nets (models.create_G4) is refused here, by name
         MODEL_G.forward(synth.normal((2, OPT.noiseDim), 1))              # compile both nets
         MODEL_R.training(); MODEL_R.forward(synth.uniform((2,) + dims, 2, 0, 1)); MODEL_R.push_params()
         MODEL_R._net.set_seed(OPT.seed); MODEL_R._net.adam_reset()

@@ -110,7 +110,7 @@ local function check(rc, what) if rc ~= 0 then error(what .. ': ' .. ffi.string(
 
 -- kind numbers of include/ganrev.h
 local K = {CONV3=1, BN=2, ELU=3, RELU=4, LEAKYRELU=5, SIGMOID=6, TANH=7, DROPOUT=8, SPATIAL_DROPOUT=9,
-           MAXPOOL2=10, UPSAMPLE2=11, VIEW=12, LINEAR=13, FULLCONV3=14, CONVK=15, PRELU=16, AVGPOOL2=17}
+           MAXPOOL2=10, UPSAMPLE2=11, VIEW=12, LINEAR=13, FULLCONV3=14, CONVK=15, PRELU=16, AVGPOOL2=17, GROUPLINEAR=18, GROUPCONV3=19}
 
 -- nn module -> descriptor rows, in nn.Sequential order (models.lua:104-143, 389-464)
 local function describe(m, out, leaves)
@@ -128,8 +128,9 @@ local function describe(m, out, leaves)
    elseif t == 'nn.ELU' then d.kind = K.ELU
    elseif t == 'nn.ReLU' or t == 'cudnn.ReLU' then d.kind = K.RELU
    elseif t == 'nn.LeakyReLU' then d.kind, d.p = K.LEAKYRELU, m.negval
-   elseif t == 'nn.PReLU' then       -- models.lua:276: nn.PReLU() = one shared slope, a parameter (weight[1]) in getParameters() order
-      assert(m.nOutputPlane == 0, 'hipnn: only nn.PReLU() with one shared slope'); d.kind = K.PRELU
+   elseif t == 'nn.PReLU' then       -- models.lua:276: nn.PReLU() = one shared slope, a parameter (weight[1]) in getParameters() order;
+      d.kind = K.PRELU               -- GR_PRELU with a = n >= 2 is nn.PReLU(n): n slopes, slope j over channels [j C/n, (j+1) C/n)
+      if m.nOutputPlane >= 2 then d.a = m.nOutputPlane end
    elseif t == 'nn.Sigmoid' or t == 'cudnn.Sigmoid' then d.kind = K.SIGMOID
    elseif t == 'nn.Tanh' or t == 'cudnn.Tanh' then d.kind = K.TANH
    elseif t == 'nn.Dropout' then

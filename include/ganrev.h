@@ -50,8 +50,16 @@ enum {
   GR_FULLCONV3 = 14,       /* nn.SpatialFullConvolution(a,b,3,3,1,1,1,1) (north_star names it; absent from the reference) */
   /* the module types the D network adds (models.lua:272-337 create_D2, trained by adversarial.lua:37-205) */
   GR_CONVK = 15,           /* nn.SpatialConvolution(a, b, c=K, K, 1, 1, (K-1)/2, (K-1)/2), K = 5 or 1      models.lua:275,297; 8-55 */
-  GR_PRELU = 16,           /* nn.PReLU(): one learnable slope (nOutputPlane 0) in the flat vector; the host mirror starts it at 0.25  models.lua:276 */
-  GR_AVGPOOL2 = 17         /* nn.SpatialAveragePooling(2,2,2,2)                                  models.lua:71,235,242,249,348-363 */
+  GR_PRELU = 16,           /* nn.PReLU(): one learnable slope (nOutputPlane 0) in the flat vector; the host mirror starts it at 0.25  models.lua:276.
+                              a = n >= 2: nn.PReLU(n), n slopes in the flat vector, slope j over channels [j C/n, (j+1) C/n) (C % n == 0; n = C is
+                              Torch7's per-plane PReLU); a stage of its own.  a = 0 or 1: the shared slope */
+  GR_AVGPOOL2 = 17,        /* nn.SpatialAveragePooling(2,2,2,2)                                  models.lua:71,235,242,249,348-363 */
+  /* the grouped kinds an nn.Concat(2) of structurally identical branches compiles to (models.lua:145-194 create_G4); exact fp32 in every
+     GR_CONV_MODE, deterministic */
+  GR_GROUPLINEAR = 18,     /* c = G block-diagonal nn.Linear(a/G, b/G) side by side (a % G == b % G == 0): group g reads inputs [g a/G, (g+1) a/G),
+                              writes outputs [g b/G, (g+1) b/G); weight [b][a/G] (the groups' matrices one after another), bias [b]; output (b,1,1) */
+  GR_GROUPCONV3 = 19       /* 3x3 stride-1 pad-1 convolution a -> b planes in c = G groups (a % G == b % G == 0); weight [b][a/G][3][3] (the `groups`
+                              layout of cudnn.SpatialConvolution), bias [b]; may stand behind GR_UPSAMPLE2 like GR_CONV3 */
 };
 #define GR_DROPOUT_V2 1         /* nn.Dropout default: train-time scale 1/(1-p), identity in evaluate() */
 #define GR_DROPOUT_ALWAYS_ON 2  /* the fixer's `drop.evaluate = function() end` (models.lua:402-405) */
