@@ -113,7 +113,7 @@ def pick_seed(og, shape, training):
 # ---------------------------------------------------------------------------------------------------------------- the single kinds
 def torch_reference(descs, dims, params, x, gout):
     """A layer-descriptor list (kind, a, b, c, p, flags) in float64 PyTorch, training mode: the oracle of the grouped kinds alone and of
-    the short chains they are tested in.  Kinds: LINEAR, GROUPLINEAR, CONV3, GROUPCONV3, UPSAMPLE2, BN (batch statistics, eps 1e-5), PRELU
+    the short chains they are tested in.  Kinds: LINEAR, GROUPLINEAR, CONV3, GROUPCONV3, CONVK, UPSAMPLE2, BN (batch statistics, eps 1e-5), PRELU
     (a = n slopes), VIEW, SIGMOID.  params: the flat vector in layer order (weight, bias | gamma, beta | slopes).
     -> dict(out, gin, grads, kink = smallest |PReLU input|, segs = [(layer, name, lo, hi, in front of a BatchNorm)])"""
     import torch
@@ -142,6 +142,9 @@ def torch_reference(descs, dims, params, x, gout):
             G = c if kind == L.GROUPCONV3 else 1
             w, bias = take(b * (a // G) * 9, (b, a // G, 3, 3), i, "weight"), take(b, (b,), i, "bias", nxt_bn)
             h = F.conv2d(h, w, bias, padding=1, groups=G)
+        elif kind == L.CONVK:                   # c = the odd window K (tests/generic_paths.py: 1 and 5), padding (K - 1) / 2
+            w, bias = take(b * a * c * c, (b, a, c, c), i, "weight"), take(b, (b,), i, "bias", nxt_bn)
+            h = F.conv2d(h, w, bias, padding=c // 2)
         elif kind == L.UPSAMPLE2:
             h = h.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
         elif kind == L.BN:
