@@ -7,7 +7,8 @@ kernel_times() labels against the mirror).
 
 Scope: what gr_conv3_forward_dev, gr_conv3_backward_data_dev and gr_conv3_backward_weight_dev (ops.hip) can launch - launch_conv3x3 (fp32
 MFMA and few-output VALU kernels), launch_conv3x3_split_n (bf16x6 / f16x3), launch_conv3x3_up2_f16x3 and launch_conv3x3_wgrad.  The kernels
-only a net launches (conv3x3_fewin*, the 5x5 kernels of conv.hip / convk.hip, the operand-ready P16 kernels) are not restated here."""
+only a net launches (conv3x3_fewin*, the 5x5 kernels of conv.hip / convk.hip) are restated further down as one-stage nets; the operand-ready
+(P16) kernels, which need a producer stage in front of them, have a module of their own: tests/p16_paths.py."""
 import dataclasses
 import math
 import zlib
@@ -434,8 +435,10 @@ def op64(op, a, b, shape):
     return torch.nn.grad.conv2d_weight(a, shape, b, padding=pad)
 
 
-def reference(case, x, w, b, dy, gw0, op=None):
-    """(ref, bound) as float64 numpy arrays for the case's operation (op: one of the three when the case is a net case)"""
+def reference(case, x, w, b, dy, gw0, op=None, a_scale=None, b_scale=None):
+    """(ref, bound) as float64 numpy arrays for the case's operation (op: one of the three when the case is a net case).  a_scale / b_scale:
+    the magnitude the f16x3 kernel scales its first / second operand by (op64's a, b) where that is not the tensor's own maximum - an
+    operand-ready (P16) image is scaled by an a-priori bound of its tensor (tests/p16_paths.py); default: the maximum, as the split kernels take it"""
     import torch
     op = op or case.op
     X, Wt, D = _t(x), _t(w), _t(dy)
@@ -451,8 +454,9 @@ def reference(case, x, w, b, dy, gw0, op=None):
     A = op64(op, a.abs(), bb.abs(), tuple(w.shape))
     bound = C_MODE[case.mode] * A
     if case.mode == "f16x3":
-        M = float(a.abs().max()) * op64(op, torch.ones_like(a), bb.abs(), tuple(w.shape)) \
-            + float(bb.abs().max()) * op64(op, a.abs(), torch.ones_like(bb), tuple(w.shape))
+        sa = float(a.abs().max()) if a_scale is None else float(a_scale)
+        sb = float(bb.abs().max()) if b_scale is None else float(b_scale)
+        M = sa * op64(op, torch.ones_like(a), bb.abs(), tuple(w.shape)) + sb * op64(op, a.abs(), torch.ones_like(bb), tuple(w.shape))
         bound = bound + C16 * M
     if op == "fwd":
         ref = ref + _t(b)[None, :, None, None]
