@@ -6,8 +6,10 @@
 //                   an nn.SpatialUpSamplingNearest(2) the kernels index the half-size input themselves (in[y >> 1][x >> 1]; the data
 //                   gradient sums its 2x2 block): no up-sampled tensor exists
 //   GR_PRELU, n >= 2 slopes: slope j covers channels [j C/n, (j+1) C/n)
-// All of it is fp32 on the vector ALU with fp32 accumulation - exact fp32 in every GR_CONV_MODE, like convk.hip and conv1x1.hip: G4's
-// instances are bound by the bytes they move (512 -> 131072 with 16 inputs per output) or small (16 planes per group), not by arithmetic.
+// All of it is fp32 on the vector ALU with fp32 accumulation - what this file launches is exact fp32 in every GR_CONV_MODE, like convk.hip
+// and conv1x1.hip.  That no longer holds for the GR_GROUPCONV3 stage as a whole: with 16 planes per group on both sides and planes up to
+// 32 x 32 (G4's instance), from group_mfma_min_tiles (image, group) tiles on and outside f32 mode, net.hip takes groupmfma.hip's f16x3 /
+// bf16x6 MFMA launches instead; every other shape, small batches and f32 mode run here.
 // Every reduction runs in a fixed order (per thread, then a fixed tree, then partials in index order by a second launch): no float atomics,
 // two runs give the same bits.  The bias gradients are not computed here: like every stage's, they come from the pipeline backward.
 #include "kernels.h"

@@ -343,7 +343,7 @@ void launch_conv1x1_backward_weight(const float* in, const float* gout, float* g
 size_t prelu_grad_workspace_bytes();
 void launch_prelu_grad(const float* g, const float* z, long n, double* part, float* gslope /*+=*/, hipStream_t s);
 
-// ---------------------------------------------------------------- grouped layer kinds (group.hip): exact fp32 in every mode, deterministic
+// ---------------------------------------------------------------- grouped layer kinds (group.hip): exact fp32 in every mode, deterministic (GR_GROUPCONV3 also: groupmfma.hip)
 // GR_GROUPLINEAR: x [B][a], w [b][a/G], y [B][b]; group g maps inputs [g a/G, (g+1) a/G) to outputs [g b/G, (g+1) b/G)
 void launch_grouplinear_forward(const float* x, const float* w, const float* bias, float* y, int B, int a, int b, int G, hipStream_t s);
 void launch_grouplinear_backward_data(const float* gout, const float* w, float* gin, int B, int a, int b, int G, hipStream_t s);
@@ -353,6 +353,16 @@ size_t groupconv3_workspace_bytes(int B, int Cin, int Cout, int G);
 void launch_groupconv3_forward(const float* in, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int G, int H, int W, bool up, hipStream_t s);
 void launch_groupconv3_backward_data(const float* gout, const float* w, float* gin, int B, int Cin, int Cout, int G, int H, int W, bool up, hipStream_t s);
 void launch_groupconv3_backward_weight(const float* in, const float* gout, float* gw /*+=*/, void* ws, int B, int Cin, int Cout, int G, int H, int W, bool up, hipStream_t s);
+#if defined(__HIPCC__)
+__global__ void group_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw, long n, int splits);   // gw[e] += the splits' partials in split order
+#endif
+// GR_GROUPCONV3 on the f16 / bf16 MFMA (groupmfma.hip): same tensors, results fp32-accurate in the split arithmetic of `mode` (2 = f16x3 with a scale per
+// (image, group) tile, else bf16x6), deterministic.  Supported: 16 planes per group on both sides, H, W <= 32; ws = groupconv3_workspace_bytes
+extern int g_group_mfma_min_tiles;       // gr_set_tuning "group_mfma_min_tiles": (image, group) tiles from which net.hip takes these launches
+bool groupconv3_mfma_supported(int Cin, int Cout, int G, int H, int W, bool up);
+void launch_groupconv3_mfma_forward(const float* in, const float* w, const float* bias, float* out, int B, int G, int H, int W, bool up, int mode, hipStream_t s);
+void launch_groupconv3_mfma_backward_data(const float* gout, const float* w, float* gin, int B, int G, int H, int W, bool up, int mode, hipStream_t s);
+void launch_groupconv3_mfma_backward_weight(const float* in, const float* gout, float* gw /*+=*/, void* ws, int B, int G, int H, int W, bool up, int mode, hipStream_t s);
 // GR_PRELU with ns >= 2 slopes over [B][C][HW]: slope j covers channels [j C/ns, (j+1) C/ns)
 void launch_prelu_multi_forward(const float* x, const float* w, float* y, int B, int C, int HW, int ns, hipStream_t s);
 void launch_prelu_multi_backward(const float* g, const float* x, const float* w, float* gin, int B, int C, int HW, int ns, hipStream_t s);

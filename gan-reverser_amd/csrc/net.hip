@@ -240,6 +240,7 @@ extern "C" int gr_get_conv_mode(gr_ctx* c) { return c ? c->conv_mode : GR_ERR_IN
 extern "C" int gr_set_tuning(gr_ctx* c, const char* key, int value) {
   if (!c || !key) return GR_ERR_INVALID;
   if (!strcmp(key, "p16_min_tiles")) { gr::g_p16_min_tiles = value; return GR_OK; }
+  if (!strcmp(key, "group_mfma_min_tiles")) { gr::g_group_mfma_min_tiles = value; return GR_OK; }   // GR_GROUPCONV3 takes the f16x3 / bf16x6 MFMA launches (groupmfma.hip) from this many (image, group) tiles on (default 512)
   if (!strcmp(key, "stack8_min_wgs")) { gr::g_stack8_min_wgs = value; return GR_OK; }      // four 8x8 images per convolution tile from this many workgroups on (default 128)
   if (!strcmp(key, "eval_p16")) { g_eval_p16 = value; return GR_OK; }           // evaluate()-mode stages hand their output over operand-ready (1, default) or as fp32 (0: the A/B control)
   if (!strcmp(key, "side_wgrad")) { c->side_wgrad = value; return GR_OK; }
@@ -1034,12 +1035,18 @@ static bool p16_dy_ok(gr_net* n, const Stage& t) { return t.kind == ST_CONV && t
 // whether THIS forward wrote them is the caller's x_p16_gen / kb_gen test).  The contract between the passes: the forward may drop the
 // fp32 copy of t's input (out_skipped) only when this holds, and the backward then takes this weight gradient.
 static bool p16_wgrad_ok(gr_net* n, const Stage& t, int B) { return p16_dy_ok(n, t) && t.x_p16 && t.stat_part && conv_wgrad_p16_supported(B, t.Cin, t.Cout, t.H, t.W); }
-// The grouped main operators (group.hip): fp32 in every mode, raw output always written, no statistics tiles (the statistics pass runs), no scale
-// slot and no operand-ready tensor on either side (a grouped stage is no f16x3 consumer, so the stage before it hands over fp32)
+// The grouped main operators (group.hip): raw output always written, no statistics tiles (the statistics pass runs), no scale slot and no
+// operand-ready tensor on either side (a grouped stage is no f16x3 consumer, so the stage before it hands over fp32).  fp32 in every mode, but
+// for the grouped convolution of group_mfma's shape: that one runs in the context's arithmetic (after the range guard has sent the context to
+// bf16x6, in bf16x6) on groupmfma.hip's launches, which scale per (image, group) tile and so neither need nor trip the guard.
+static bool group_mfma(gr_net* n, const Stage& s, int B) {
+  return n->ctx->conv_mode != 0 && s.kind == ST_GROUPCONV && groupconv3_mfma_supported(s.Cin, s.Cout, s.groups, s.H, s.W, s.up) && (long)B * s.groups >= g_group_mfma_min_tiles;
+}
 static int fwd_group(gr_net* n, Stage& s, const float* x, int B) {
   gr_ctx* c = n->ctx;
   s.stat_tiles_last = 0;
   if (s.kind == ST_GROUPLIN) launch_grouplinear_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, B, s.Cin, s.Cout, s.groups, c->stream);
+  else if (group_mfma(n, s, B)) launch_groupconv3_mfma_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
   else launch_groupconv3_forward(x, n->params + s.w_off, n->params + s.b_off, s.y, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
   return GR_OK;
 }
@@ -1462,7 +1469,7 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
   if (gx) dgrad3(n, s, dyb, dyp, gx, B, dgrad_p16);
   return GR_OK;
 }
-// grouped main operators: weight gradient (+=) and data gradient, both on the compute stream (no side stream: they are short and exact fp32)
+// grouped main operators: weight gradient (+=) and data gradient, both on the compute stream (no side stream: they are short)
 static int bwd_group(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
   gr_ctx* c = n->ctx;
   if (s.kind == ST_GROUPLIN) {
@@ -1471,6 +1478,11 @@ static int bwd_group(gr_net* n, Stage& s, const float* x, const float* dyb, floa
     return GR_OK;
   }
   const int r = ensure_ws(c, groupconv3_workspace_bytes(B, s.Cin, s.Cout, s.groups)); if (r) return r;
+  if (group_mfma(n, s, B)) {
+    launch_groupconv3_mfma_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
+    if (gx) launch_groupconv3_mfma_backward_data(dyb, n->params + s.w_off, gx, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
+    return GR_OK;
+  }
   launch_groupconv3_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
   if (gx) launch_groupconv3_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
   return GR_OK;

@@ -238,6 +238,8 @@ int gr_get_conv_mode(gr_ctx* ctx);
  *   "p16_min_tiles"  (default 128, process-wide) smallest tile count at which a 3x3 convolution takes the operand-ready (P16) kernels; tests set 1 to
  *                    exercise that path on small shapes
  *   "stack8_min_wgs" (default 128, process-wide) smallest grid at which 8x8 planes are stacked four to a convolution tile; tests force the path
+ *   "group_mfma_min_tiles" (default 512, process-wide) smallest number of (image, group) tiles, B x G, at which a GR_GROUPCONV3 stage of 16 planes per group
+ *                    and planes up to 32 x 32 takes the f16x3 / bf16x6 MFMA launches (csrc/groupmfma.hip) instead of the fp32 ones; never in f32 mode; tests set 1
  *   "eval_p16"       (default 1) evaluate()-mode stages hand their output to the next convolution operand-ready - see below
  *   "side_wgrad"     (default -1 = by stage size: on from 2^26 activations) R's convolution weight gradients on a second stream beside the rest of backward;
  *                    bit-identical either way (measured: cfg3 -1.1 %, cfg2 +1.1 %: profiles/r05_ab_side_wgrad_*.txt)
