@@ -1124,6 +1124,84 @@ void launch_post_backward(const PostBwdArgs& a0, hipStream_t s, BiasJobs* defer,
   }
 }
 
+// ------------------------------------------------------------------ frozen backward pipeline (evaluate() mode: nn.Module:updateGradInput)
+// In evaluate() a BatchNorm is the per-channel affine map z = ((y - mean_run) * invstd_run) * gamma + beta, so the gradient wrt y needs no
+// batch reduction:  dy = dz * (invstd_run * gamma)[c],  dz = gradOutput routed back through mask 2, the pool, mask 1 and the activation -
+// exactly pass A's dz (post_bwd_dz4 / the scalar kernel's lines, same operations in the same order).  One pass: g and y are read once, dy is
+// written once; no partials, no coef, no parameter gradient.  max|dy| goes to amax_dy for the f16x3 / bf16x6 data-gradient kernels.
+__global__ __launch_bounds__(256) void post_backward_frozen_kernel(PostBwdArgs a) {
+  const PostArgs& f = a.f;
+  const int H = f.H, W = f.W, Ho = f.pool ? H >> 1 : H, Wo = f.pool ? W >> 1 : W;
+  const long HW = (long)H * W, HWo = (long)Ho * Wo;
+  const long n = (long)f.B * f.C * HW;
+  float dmax = 0.f;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+    const long bc = e / HW; const int p = (int)(e - bc * HW);
+    const int c = (int)(bc % f.C);
+    float g;
+    if (f.pool) {
+      const int yy = p / W, xx = p - yy * W, yo = yy >> 1, xo = xx >> 1;
+      g = 0.f;
+      if (yo < Ho && xo < Wo) {
+        const long eo = bc * HWo + (long)yo * Wo + xo;
+        const int t = ((yy & 1) << 1) | (xx & 1);
+        if (f.pool == POOL_AVG) g = (a.gout[eo] * mask_mul(f.m2, eo, bc)) / 4.f;
+        else if (f.pool_idx[eo] == t) g = a.gout[eo] * mask_mul(f.m2, eo, bc);
+      }
+    } else {
+      g = a.gout[e] * mask_mul(f.m2, e, bc);
+    }
+    g = g * mask_mul(f.m1, e, bc);
+    const float z = bn_apply(f, f.y[e], c);
+    float d = act_bwd_z(g, z, f.act, post_slope(f));
+    if (f.has_bn) d = d * (f.invstd[c] * f.gamma[c]);
+    a.dy[e] = d;
+    dmax = fmaxf(dmax, fabsf(d));
+  }
+  if (a.amax_dy) absmax_commit(dmax, a.amax_dy);
+}
+// float4 variant (the shape rule of launch_post_backward's): one thread per four consecutive pre-pool elements of a row
+template <int CB>
+__global__ __launch_bounds__(256) void post_backward_frozen_vec_kernel(PostBwdArgs a) {
+  post_specialize<CB>(a.f);
+  const PostArgs& f = a.f;
+  const unsigned H = f.H, W = f.W, Wo = f.pool ? W >> 1 : W, HW = H * W, HWo = f.pool ? (H >> 1) * Wo : HW;
+  const unsigned q4 = HW >> 2, wq = W >> 2;
+  const unsigned n4 = (unsigned)f.B * f.C * q4;
+  float dmax = 0.f;
+  for (unsigned i4 = blockIdx.x * blockDim.x + threadIdx.x; i4 < n4; i4 += gridDim.x * blockDim.x) {
+    const unsigned bc = udivp(i4, q4), i = i4 - bc * q4, c = bc - udivp(bc, (unsigned)f.C) * (unsigned)f.C;
+    float mean = 0.f, invstd = 1.f, gm = 1.f, bt = 0.f;
+    if (f.has_bn) { mean = f.mean[c]; invstd = f.invstd[c]; gm = f.gamma[c]; bt = f.beta[c]; }
+    const unsigned e = bc * HW + i * 4;
+    float4 yv;
+    float4 d = post_bwd_dz4(a, bc, e, i, bc * HWo, wq, Wo, mean, invstd, gm, bt, yv);
+    if (f.has_bn) { const float k = invstd * gm; d.x = d.x * k; d.y = d.y * k; d.z = d.z * k; d.w = d.w * k; }
+    *reinterpret_cast<float4*>(a.dy + e) = d;
+    dmax = absmax4(dmax, d);
+  }
+  if (a.amax_dy) absmax_commit(dmax, a.amax_dy);
+}
+void launch_post_backward_frozen(const PostBwdArgs& a0, hipStream_t s) {
+  PostBwdArgs a = a0;
+  a.nt = 0;
+  const PostArgs& f = a.f;
+  const double pre = (double)f.B * f.C * f.H * f.W, post = f.pool ? pre / 4 : pre;
+  const bool vec = (f.pool ? (f.W % 8 == 0 && f.H % 2 == 0) : (f.W % 4 == 0)) && f.H * f.W >= 64 && pre < 4.0e9;      // launch_post_backward's rule
+  if (vec) {
+    long blocks = ((long)(pre / 4) + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    KtScope kt("post_backward_frozen_vec_kernel", 0.0, 4.0 * (2.0 * pre + post), s);      // reads g and y, writes dy
+    with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL(post_backward_frozen_vec_kernel<decltype(cb)::value>, dim3((unsigned)blocks), dim3(256), 0, s, a); });
+  } else {
+    long blocks = ((long)pre + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    KtScope kt("post_backward_frozen_kernel", 0.0, 4.0 * (2.0 * pre + post), s);
+    hipLaunchKernelGGL(post_backward_frozen_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  }
+}
+
 // ------------------------------------------------------------------ f16x3 range guard (kernels.h)
 __global__ __launch_bounds__(256) void channel_absmax_kernel(const float* __restrict__ t, int B, long HW, long sB, long sC, unsigned* __restrict__ chmax) {
   const int c = blockIdx.x;
@@ -1202,6 +1280,26 @@ __global__ __launch_bounds__(1024) void mse_kernel(const float* __restrict__ x, 
 }
 void launch_mse(const float* x, const float* t, long n, long n_global, double* loss_dev, float* grad, hipStream_t s) {
   hipLaunchKernelGGL(mse_kernel, dim3(1), dim3(1024), 0, s, x, t, n, 1.0 / (double)n_global, (float)(2.0 / (double)n_global), loss_dev, grad);
+}
+
+// per-row MSE (noise refinement: every row is a problem of its own): loss[i] = sum_j (x_ij - t_ij)^2 / n, grad_ij = 2 (x_ij - t_ij) / n.  One
+// workgroup per row; the squares are added in double in a fixed order (thread-strided, then block_reduce_sum's tree): the bits repeat.
+__global__ __launch_bounds__(256) void mse_rows_kernel(const float* __restrict__ x, const float* __restrict__ t, long n, double inv_n, float norm,
+                                                       float* __restrict__ loss_rows, float* __restrict__ grad) {
+  __shared__ double sh[8];
+  const long base = (long)blockIdx.x * n;
+  double s = 0;
+  for (long j = threadIdx.x; j < n; j += blockDim.x) {
+    const float z = x[base + j] - t[base + j];
+    s += (double)z * (double)z;
+    if (grad) grad[base + j] = norm * z;
+  }
+  s = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) loss_rows[blockIdx.x] = (float)(s * inv_n);
+}
+void launch_mse_rows(const float* x, const float* t, long rows, long n, float* loss_rows, float* grad, hipStream_t s) {
+  KtScope kt("mse_rows_kernel", 3.0 * (double)rows * n, 4.0 * (double)rows * n * (grad ? 3.0 : 2.0), s);
+  hipLaunchKernelGGL(mse_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, x, t, n, 1.0 / (double)n, (float)(2.0 / (double)n), loss_rows, grad);
 }
 
 // ------------------------------------------------------------------ R's head in ONE launch (gr_train_r_step; round 5)
@@ -1687,6 +1785,35 @@ void launch_penalty_clamp_adam(float* theta, float* g, float* m, float* v, long 
   if (blocks < 1) blocks = 1;
   KtScope kt("penalty_clamp_adam_kernel", 0.0, 32.0 * (double)n, s);   // read theta,g,m,v + write theta,g,m,v
   hipLaunchKernelGGL(penalty_clamp_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, s, theta, g, m, v, n, c, skip);
+}
+
+// Row-wise best-keeping + optim.adam on [rows][nd] (a workgroup walks whole rows).  First the look: a row whose loss fell below its best so far
+// stores the loss and copies its CURRENT z (the one the loss was measured at) to best_z.  Then, when update != 0, adam_one on every entry - the
+// operations of penalty_clamp_adam_kernel with no penalty and no gradient clamp - and, when zclamp > 0, z clamped to +-zclamp.
+__global__ __launch_bounds__(256) void adam_rows_kernel(float* __restrict__ z, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int rows, int nd,
+                                                        AdamConsts c, float zclamp, const float* __restrict__ loss_rows, float* __restrict__ best_loss,
+                                                        float* __restrict__ best_z, int update) {
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const bool better = loss_rows[r] < best_loss[r];
+    __syncthreads();                                    // every thread has read best_loss[r] before thread 0 rewrites it
+    if (better && threadIdx.x == 0) best_loss[r] = loss_rows[r];
+    const long base = (long)r * nd;
+    for (int j = threadIdx.x; j < nd; j += blockDim.x) {
+      float th = z[base + j];
+      if (better) best_z[base + j] = th;
+      if (update) {
+        float gv = g[base + j], mv = m[base + j], vv = v[base + j];
+        adam_one(th, gv, mv, vv, c);
+        if (zclamp > 0.f) th = th < -zclamp ? -zclamp : (th > zclamp ? zclamp : th);
+        z[base + j] = th; m[base + j] = mv; v[base + j] = vv;
+      }
+    }
+  }
+}
+void launch_adam_rows(float* z, float* g, float* m, float* v, int rows, int nd, const AdamConsts& c, float zclamp, const float* loss_rows, float* best_loss,
+                      float* best_z, int update, hipStream_t s) {
+  KtScope kt("adam_rows_kernel", 0.0, 4.0 * (double)rows * nd * (update ? 8.0 : 2.0), s);
+  hipLaunchKernelGGL(adam_rows_kernel, dim3((unsigned)(rows < 4096 ? rows : 4096)), dim3(256), 0, s, z, g, m, v, rows, nd, c, zclamp, loss_rows, best_loss, best_z, update);
 }
 
 // ------------------------------------------------------------------ penalty + clamp + sgd | adagrad | adadelta | adamax | rmsprop

@@ -1,6 +1,7 @@
 // kernels.h — internal launch interface between the net runtime (net.hip) and the gfx950 kernels.
 // Not part of the ABI (that is include/ganrev.h).
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -328,6 +329,9 @@ struct BiasJob { const double* partials; float* gbias; int C, splits; };     // 
 struct BiasJobs { BiasJob job[16]; int n; };
 void launch_post_backward(const PostBwdArgs& a, hipStream_t s, BiasJobs* defer = nullptr, const StatSync* sync = nullptr);
 void launch_bias_grad_batch(BiasJobs& jobs, hipStream_t s);    // runs and empties the list
+// evaluate()-mode backward of the pipeline in ONE pass (nn.Module:updateGradInput with a frozen BatchNorm): dy = dz * (invstd * gamma)[c], where
+// mean / invstd are launch_bn_eval_prepare's.  Reads f, gout, dy and amax_dy of the argument block; no partials, no coef, no parameter gradient.
+void launch_post_backward_frozen(const PostBwdArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- K x K convolution (odd K other than 3) and nn.PReLU: convk.hip
 bool convk_supported(int K);
@@ -391,6 +395,19 @@ void launch_add_inplace(float* y, const float* x, long n, hipStream_t s);       
 void launch_bce(const float* x, const float* t, long n, double* loss_dev, float* grad, hipStream_t s);      // nn.BCECriterion (sizeAverage)
 struct AdamConsts { float b1, b2, c1, c2, eps, step, l1, l2, clamp; int use_penalty, use_clamp; };
 void launch_penalty_clamp_adam(float* theta, float* g, float* m, float* v, long n, const AdamConsts& c, hipStream_t s, const unsigned* skip = nullptr);
+// optim.adam's scalars at step t (1-based): the step size in double, rounded to fp32 once; epsilon stays outside the bias correction
+inline AdamConsts adam_consts_plain(double lr, double beta1, double beta2, double eps, int t) {
+  AdamConsts k{};
+  k.b1 = (float)beta1; k.b2 = (float)beta2; k.eps = (float)eps;
+  k.c1 = (float)(1.0 - beta1); k.c2 = (float)(1.0 - beta2);
+  const double bc1 = 1.0 - std::pow(beta1, t), bc2 = 1.0 - std::pow(beta2, t);
+  k.step = (float)(-(lr * std::sqrt(bc2) / bc1));
+  return k;
+}
+// noise refinement (elem.hip): per-row MSE with its gradient (grad nullable), and best-keeping + Adam on [rows][nd] in one launch each
+void launch_mse_rows(const float* x, const float* t, long rows, long n, float* loss_rows, float* grad, hipStream_t s);
+void launch_adam_rows(float* z, float* g, float* m, float* v, int rows, int nd, const AdamConsts& c, float zclamp, const float* loss_rows, float* best_loss,
+                      float* best_z, int update, hipStream_t s);
 // The optim rock's other five methods (adversarial.lua:147-161,174-188), same fused pass.  method = GR_OPT_* (net.hip asserts the two lists agree).
 // Every scalar is rounded to fp32 once on the host (gr_optim_step); a method reads only its own: sgd lr (= clr), wd, mom, omd (1 - dampening), use_wd,
 // use_mom, nesterov, first (t == 1: the buffer becomes the gradient); adagrad lr (= clr); adadelta rho, omr (1 - rho), eps; adamax b1, c1 (1 - beta1),

@@ -423,6 +423,8 @@ struct gr_net : NetPlan {
   bool keep_fp32 = false;            // range-guarded host calls: no lean (operand-ready only) tensors, so a backward can still fall back to bf16x6
   bool last_fwd_fell_back = false;   // the last guarded forward ran on bf16x6: its backward does too
   unsigned guard_sides = 0;           // the largest spreads (bits: activation side | weight side << 16) the last guarded forward measured
+  bool input_grad = false;           // gr_net_set_input_grad: an evaluate()-mode forward keeps what gr_net_backward_input_dev reads (raw y, fp32 outputs, zeroed dy slots)
+  bool last_fwd_input_grad = false;  // the last forward was such a one
 };
 
 enum { AG_X = 0, AG_XT = 1, AG_Y = 2, AG_KB = 3, AG_DY = 4, AG_DZ = 5, AG_W = 6, AMAX_GROUPS = 7 };
@@ -975,8 +977,9 @@ static int forward_begin(gr_net* n, int B) {
   // prep below is about to recompute the weight maxima
   n->w_slots_zeroed = false;
   if (f16) {
-    const bool w_too = n->training && n->prepped_version[2] != n->params_version;
-    const size_t groups = w_too ? AMAX_GROUPS : (n->training ? AG_W : AG_KB);      // x xt y | kb dy dz | w
+    const bool bwd_follows = n->training || n->input_grad;      // (evaluate() with the input-gradient flag: gr_net_backward_input_dev folds max|dy| in)
+    const bool w_too = bwd_follows && n->prepped_version[2] != n->params_version;
+    const size_t groups = w_too ? AMAX_GROUPS : (bwd_follows ? AG_W : AG_KB);      // x xt y | kb dy dz | w
     if ((size_t)prezeroed_groups < groups) HIPCHK(c, hipMemsetAsync(n->amax, 0, sizeof(unsigned) * AMAX_WORDS * nst * groups, c->stream));
     n->dy_slots_zeroed = groups >= (size_t)AG_W;
     n->w_slots_zeroed = groups == (size_t)AMAX_GROUPS;
@@ -1021,7 +1024,7 @@ static void bn_eval_ready(gr_net* n, Stage& s) { if (!s.eval_ready) launch_bn_ev
 // its raw output is never written.  Needs: no pool, no active dropout noise, no PReLU; a Linear also needs a GEMM without split-K.  Fills ep.
 static bool eval_epilogue(gr_net* n, Stage& s, int B, ConvEpilogue& ep) {
   bool nb1 = false, nb2 = false;
-  if (n->training || !s.has_post || s.pool || s.act == ACT_PRELU || mask_ref(n, s.m1, nb1).kind != MASK_NONE || mask_ref(n, s.m2, nb2).kind != MASK_NONE) return false;
+  if (n->training || n->input_grad || !s.has_post || s.pool || s.act == ACT_PRELU || mask_ref(n, s.m1, nb1).kind != MASK_NONE || mask_ref(n, s.m2, nb2).kind != MASK_NONE) return false;
   if (s.kind == ST_LINEAR && !(s.H == 1 && s.W == 1 && gemm_epilogue_possible(B, s.Cout, s.Cin))) return false;
   if (s.has_bn) { bn_eval_ready(n, s); ep.mean = s.mean; ep.invstd = s.invstd; ep.gamma = n->params + s.g_off; ep.beta = n->params + s.be_off; }
   ep.act = s.act; ep.slope = s.slope;
@@ -1082,7 +1085,7 @@ static int fwd_conv3(gr_net* n, Stage& s, const float* x, int B, Stage* nx, unsi
   // too - straight from the conv epilogue (`po`: BatchNorm + activation fused, scale = the weight-norm bound of launch_eval_bound) or, for
   // a stage with a pipeline kernel (pooling), from that kernel (`post_p16`: scale bounded from max|y|, which the conv epilogue measures).
   // Pure functions of the stage's input and parameters: the host-tensor mirror (gr_net_forward_host) computes the same bits.
-  const bool nx_p16 = g_eval_p16 && f16 && !n->training && nx && p16_input_ok(n, *nx, B) && !s.up && !s.fullconv && s.wl1;
+  const bool nx_p16 = g_eval_p16 && f16 && !n->training && !n->input_grad && nx && p16_input_ok(n, *nx, B) && !s.up && !s.fullconv && s.wl1;
   const bool po = nx_p16 && s.fused_epilogue &&
                   (is_fewin ? conv_fewin_p16_out_supported(s.Cout, s.H, s.W) : (in_p16 && conv_p16_out_supported(s.Cout)));
   post_p16 = nx_p16 && !s.fused_epilogue && s.has_post && s.act != ACT_PRELU && post_g8_supported(s.Cout, s.H, s.W, s.pool) && (is_fewin || use_bf16x6(n, s));
@@ -1201,6 +1204,7 @@ static int forward_stages(gr_net* n, const float* in_dev, int B) {
   gr_ctx* c = n->ctx;
   int r = forward_begin(n, B); if (r) return r;
   n->last_fwd_training = n->training;
+  n->last_fwd_input_grad = !n->training && n->input_grad;
   const float* x = in_dev;
   const bool f16 = c->conv_mode == 2;
   const size_t nst = n->st.size();
@@ -1403,14 +1407,18 @@ constexpr int64_t BUCKET_MIN_ELEMS = 1 << 20;
 // ---- backward steps: the main op's gradients from dy (dyb; dyp its operand-ready image).  gx: where the data gradient goes, null when none is wanted.
 // K x K convolution: the data gradient is the same convolution on the transposed + flipped weights (Cout -> Cin); max|dy| was folded into amax_dy
 // by the pipeline backward
+static int dgrad_convk(gr_net* n, Stage& s, const float* dyb, float* gx, int B) {
+  gr_ctx* c = n->ctx;
+  const int r = ensure_ws(c, convk_workspace_bytes(B, s.Cin, s.Cout, s.ksz)); if (r) return r;
+  if (convk_split(n, s) && conv5x5_split_supported(s.Cout, s.Cin, s.H, s.W)) launch_conv5x5_split(dyb, s.ws_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, c->stream, s.amax_dy, s.amax_w);
+  else launch_convk_backward_data(dyb, n->params + s.w_off, gx, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
+  return GR_OK;
+}
 static int bwd_convk(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
   gr_ctx* c = n->ctx;
   const int r = ensure_ws(c, convk_workspace_bytes(B, s.Cin, s.Cout, s.ksz)); if (r) return r;
   launch_convk_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
-  if (!gx) return GR_OK;
-  if (convk_split(n, s) && conv5x5_split_supported(s.Cout, s.Cin, s.H, s.W)) launch_conv5x5_split(dyb, s.ws_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, c->stream, s.amax_dy, s.amax_w);
-  else launch_convk_backward_data(dyb, n->params + s.w_off, gx, c->ws, B, s.Cin, s.Cout, s.H, s.W, s.ksz, c->stream);
-  return GR_OK;
+  return gx ? dgrad_convk(n, s, dyb, gx, B) : GR_OK;
 }
 // 3x3 data gradient = the convolution Cout -> Cin on the backward weight images.  Plain stages: P16 when dy is operand-ready, else split in
 // either split mode.  Up-sampling / full-conv stages take split only above 4 input channels (why the rules differ is not recorded).
@@ -1420,6 +1428,18 @@ static void dgrad3(gr_net* n, Stage& s, const float* dyb, const void* dyp, float
   else if (c->conv_mode >= 1 && ((!s.up && !s.fullconv) || s.Cin > 4))
     launch_conv3x3_split(dyb, s.ws_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, false, c->stream, nullptr, c->conv_mode == 2 ? 2 : 3, s.amax_dy, s.amax_w);
   else launch_conv3x3(dyb, s.wt_bwd, nullptr, gx, B, s.Cout, s.Cin, s.H, s.W, false, c->stream);
+}
+// the data-gradient half of a 3x3 stage: an up-sampling stage's is taken at the up-sampled size and folded back by summing each 2x2 block
+static int dgrad_conv3(gr_net* n, Stage& s, const float* dyb, const void* dyp, float* gx, int B, bool p16) {
+  gr_ctx* c = n->ctx;
+  if (s.up) {
+    const int r = grow_dev(c, n->mem, n->up_tmp, n->up_cap, sizeof(float) * (size_t)B * vol3(s.Cin, s.H, s.W), c->stream, 2); if (r) return r;
+    dgrad3(n, s, dyb, dyp, n->up_tmp[1], B, false);
+    launch_downsum2(n->up_tmp[1], gx, B, s.Cin, s.H / 2, s.W / 2, c->stream);
+    return GR_OK;
+  }
+  dgrad3(n, s, dyb, dyp, gx, B, p16 && !s.fullconv);
+  return GR_OK;
 }
 // 3x3 convolution.  dk: the dy pair (a side-stream weight gradient marks it busy); dgrad_p16 / wgrad_p16: backward_impl's operand-ready choices.
 static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, const void* dyp, float* gx, int B, int dk, bool dgrad_p16, bool wgrad_p16) {
@@ -1434,8 +1454,7 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
     r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
     if (f16 && conv_wgrad_is_split(2, s.Cin, s.W)) input_absmax(n, s, x, B, false);
     launch_conv3x3_wgrad(n->up_tmp[0], dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.H, s.W, c->stream, c->conv_mode, s.amax_x, s.amax_dy);
-    if (gx) { dgrad3(n, s, dyb, dyp, n->up_tmp[1], B, false); launch_downsum2(n->up_tmp[1], gx, B, s.Cin, s.H / 2, s.W / 2, c->stream); }
-    return GR_OK;
+    return gx ? dgrad_conv3(n, s, dyb, dyp, gx, B, false) : GR_OK;
   }
   if (s.fullconv) {
     // nn.SpatialFullConvolution:accGradParameters: gradWeight[i][o] += x[i] (x) gradOutput[o] = the weight gradient of the convolution
@@ -1443,8 +1462,7 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
     r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cout, s.Cin, s.H, s.W, c->conv_mode)); if (r) return r;
     if (f16 && conv_wgrad_is_split(2, s.Cout, s.W)) input_absmax(n, s, x, B, false);
     launch_conv3x3_wgrad(dyb, x, n->grads + s.w_off, c->ws, B, s.Cout, s.Cin, s.H, s.W, c->stream, c->conv_mode, s.amax_dy, s.amax_x);
-    if (gx) dgrad3(n, s, dyb, dyp, gx, B, false);
-    return GR_OK;
+    return gx ? dgrad_conv3(n, s, dyb, dyp, gx, B, false) : GR_OK;
   }
   r = ensure_ws(c, conv_wgrad_workspace_bytes(B, s.Cin, s.Cout, s.H, s.W, c->conv_mode)); if (r) return r;
   // max|dy| was folded into s.amax_dy by the pipeline-backward kernel that wrote dy_buf
@@ -1466,28 +1484,35 @@ static int bwd_conv3(gr_net* n, Stage& s, const float* x, const float* dyb, cons
   if (wgrad_p16) launch_conv3x3_wgrad_p16(s.x_p16, dyp, n->grads + s.w_off, wsp_, B, s.Cin, s.Cout, s.H, s.W, ws_, s.amax_x, s.amax_dy);
   else launch_conv3x3_wgrad(x, dyb, n->grads + s.w_off, wsp_, B, s.Cin, s.Cout, s.H, s.W, ws_, c->conv_mode, s.amax_x, s.amax_dy);
   if (side) { HIPCHK(c, hipEventRecord(c->ev_wgrad_done[dk], c->side_stream)); n->wg_pending[dk] = true; }
-  if (gx) dgrad3(n, s, dyb, dyp, gx, B, dgrad_p16);
-  return GR_OK;
+  return gx ? dgrad_conv3(n, s, dyb, dyp, gx, B, dgrad_p16) : GR_OK;
 }
 // grouped main operators: weight gradient (+=) and data gradient, both on the compute stream (no side stream: they are short)
+static void dgrad_group(gr_net* n, Stage& s, const float* dyb, float* gx, int B) {
+  gr_ctx* c = n->ctx;
+  if (s.kind == ST_GROUPLIN) launch_grouplinear_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, c->stream);
+  else if (group_mfma(n, s, B)) launch_groupconv3_mfma_backward_data(dyb, n->params + s.w_off, gx, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
+  else launch_groupconv3_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
+}
 static int bwd_group(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
   gr_ctx* c = n->ctx;
-  if (s.kind == ST_GROUPLIN) {
-    launch_grouplinear_backward_weight(x, dyb, n->grads + s.w_off, B, s.Cin, s.Cout, s.groups, c->stream);
-    if (gx) launch_grouplinear_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, c->stream);
-    return GR_OK;
+  if (s.kind == ST_GROUPLIN) launch_grouplinear_backward_weight(x, dyb, n->grads + s.w_off, B, s.Cin, s.Cout, s.groups, c->stream);
+  else {
+    const int r = ensure_ws(c, groupconv3_workspace_bytes(B, s.Cin, s.Cout, s.groups)); if (r) return r;
+    if (group_mfma(n, s, B)) launch_groupconv3_mfma_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
+    else launch_groupconv3_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
   }
-  const int r = ensure_ws(c, groupconv3_workspace_bytes(B, s.Cin, s.Cout, s.groups)); if (r) return r;
-  if (group_mfma(n, s, B)) {
-    launch_groupconv3_mfma_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
-    if (gx) launch_groupconv3_mfma_backward_data(dyb, n->params + s.w_off, gx, B, s.groups, s.H, s.W, s.up, c->conv_mode, c->stream);
-    return GR_OK;
-  }
-  launch_groupconv3_backward_weight(x, dyb, n->grads + s.w_off, c->ws, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
-  if (gx) launch_groupconv3_backward_data(dyb, n->params + s.w_off, gx, B, s.Cin, s.Cout, s.groups, s.H, s.W, s.up, c->stream);
+  if (gx) dgrad_group(n, s, dyb, gx, B);
   return GR_OK;
 }
 // nn.Linear: gW[o][i] += sum_b dy[b][o] x[b][i], gx[b][i] = sum_o dy[b][o] W[o][i]
+static int dgrad_linear(gr_net* n, Stage& s, const float* dyb, float* gx, int B) {
+  gr_ctx* c = n->ctx;
+  const int r = ensure_ws(c, gemm_workspace_bytes(B, s.Cin, s.Cout)); if (r) return r;
+  const bool f16g = use_f16_gemm(n, s);
+  launch_gemm(dyb, s.Cout, 1, n->params + s.w_off, 1, s.Cin, gx, s.Cin, nullptr, false, B, s.Cin, s.Cout, c->ws, c->stream,
+              nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_w : nullptr);
+  return GR_OK;
+}
 static int bwd_linear(gr_net* n, Stage& s, const float* x, const float* dyb, float* gx, int B) {
   gr_ctx* c = n->ctx;
   const int r = ensure_ws(c, std::max(gemm_workspace_bytes(s.Cout, s.Cin, B), gemm_workspace_bytes(B, s.Cin, s.Cout))); if (r) return r;
@@ -1495,9 +1520,7 @@ static int bwd_linear(gr_net* n, Stage& s, const float* x, const float* dyb, flo
   if (f16g) input_absmax(n, s, x, B, false);   // (mode switched since the forward)
   launch_gemm(dyb, 1, s.Cout, x, 1, s.Cin, n->grads + s.w_off, s.Cin, nullptr, true, s.Cout, s.Cin, B, c->ws, c->stream,
               nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_x : nullptr);
-  if (gx) launch_gemm(dyb, s.Cout, 1, n->params + s.w_off, 1, s.Cin, gx, s.Cin, nullptr, false, B, s.Cin, s.Cout, c->ws, c->stream,
-                      nullptr, nullptr, f16g ? s.amax_dy : nullptr, f16g ? s.amax_w : nullptr);
-  return GR_OK;
+  return gx ? dgrad_linear(n, s, dyb, gx, B) : GR_OK;
 }
 static int backward_impl(gr_net* n, const float* in_dev, const float* gout_dev, int B, float* gin_dev, bool reduce = false) {
   gr_ctx* c = n->ctx;
@@ -1602,6 +1625,53 @@ extern "C" int gr_net_backward_dev(gr_net* n, const float* in_dev, const float* 
   return backward_impl(n, in_dev, gout_dev, B, gin_dev);
 }
 
+// nn.Module:updateGradInput in evaluate() mode: gradInput alone.  A frozen BatchNorm is a per-channel affine map, so each stage is ONE pipeline
+// kernel (launch_post_backward_frozen) and the data-gradient half of its main operator, on the compute stream; nothing is written to `grads`, to a
+// running statistic or to a mask.  dy stays fp32 (the operand-ready dy needs the bound factor of training-mode statistics).
+static int backward_input_impl(gr_net* n, const float* in_dev, const float* gout_dev, int B, float* gin_dev) {
+  gr_ctx* c = n->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n->training) return fail(c, GR_ERR_STATE, "gr_net_backward_input_dev: the net is in training mode (the input-only backward is evaluate()-mode; gr_net_backward_dev is the training-mode one)");
+  if (n->lastB <= 0 || !n->last_fwd_input_grad)
+    return fail(c, GR_ERR_STATE, "gr_net_backward_input_dev: the last forward was not an evaluate()-mode forward with gr_net_set_input_grad on (it kept no raw stage outputs)");
+  if (B != n->lastB) return fail(c, GR_ERR_STATE, "backward batch %d does not match the last forward (%d)", B, n->lastB);
+  int r = prep_weights(n); if (r) return r;   // no-op unless the arithmetic mode changed since the forward
+  const bool f16 = c->conv_mode == 2;
+  if (f16 && !n->dy_slots_zeroed)
+    HIPCHK(c, hipMemsetAsync(n->amax + AMAX_WORDS * AG_DY * n->st.size(), 0, sizeof(unsigned) * AMAX_WORDS * 2 * n->st.size(), c->stream));
+  n->dy_slots_zeroed = false;
+  for (int k2 = 0; k2 < 2; ++k2) if (n->wg_pending[k2]) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_wgrad_done[k2], 0)); n->wg_pending[k2] = false; }   // (an earlier full backward that failed part-way)
+  const float* g = gout_dev;
+  for (int si = (int)n->st.size() - 1; si >= 0; --si) {
+    Stage& s = n->st[si];
+    const float* x = si == 0 ? in_dev : s.x_in;
+    float* gin = si == 0 ? gin_dev : n->g_buf[si & 1];
+    if (s.nslopes) {
+      launch_prelu_multi_backward(g, x, n->params + s.slope_off, gin, B, s.Cout, s.H * s.W, s.nslopes, c->stream);
+      LAUNCHCHK(c);
+      g = gin;
+      continue;
+    }
+    float* const dyb = n->dy_buf;
+    if (s.has_bn) bn_eval_ready(n, s);
+    launch_post_backward_frozen(post_bwd_args(n, s, B, g, s.kind == ST_ELEM ? gin : dyb), c->stream);
+    LAUNCHCHK(c);
+    if (s.kind == ST_GROUPLIN || s.kind == ST_GROUPCONV) dgrad_group(n, s, dyb, gin, B);
+    else if (s.kind == ST_CONV && s.ksz != 3) r = dgrad_convk(n, s, dyb, gin, B);
+    else if (s.kind == ST_CONV) r = dgrad_conv3(n, s, dyb, nullptr, gin, B, false);
+    else if (s.kind == ST_LINEAR) r = dgrad_linear(n, s, dyb, gin, B);
+    if (r) return r;
+    LAUNCHCHK(c);
+    g = gin;
+  }
+  return GR_OK;
+}
+extern "C" int gr_net_set_input_grad(gr_net* n, int on) { if (!n) return GR_ERR_INVALID; n->input_grad = on != 0; return GR_OK; }
+extern "C" int gr_net_backward_input_dev(gr_net* n, const float* in_dev, const float* gout_dev, int B, float* gin_dev) {
+  if (!n || !in_dev || !gout_dev || !gin_dev || B <= 0) return GR_ERR_INVALID;
+  return backward_input_impl(n, in_dev, gout_dev, B, gin_dev);
+}
+
 extern "C" int gr_net_backward_host(gr_net* n, const float* in_host, const float* gout_host, int B, float* gin_host) {
   if (!n || !in_host || !gout_host || B <= 0) return GR_ERR_INVALID;
   gr_ctx* c = n->ctx;
@@ -1636,11 +1706,7 @@ extern "C" int gr_net_backward_host(gr_net* n, const float* in_host, const float
 
 // ------------------------------------------------------------------ optimiser
 static AdamConsts adam_consts(const gr_hyper* h, int t) {
-  AdamConsts k{};
-  k.b1 = (float)h->beta1; k.b2 = (float)h->beta2; k.eps = (float)h->eps;
-  k.c1 = (float)(1.0 - h->beta1); k.c2 = (float)(1.0 - h->beta2);
-  const double bc1 = 1.0 - std::pow(h->beta1, t), bc2 = 1.0 - std::pow(h->beta2, t);
-  k.step = (float)(-(h->lr * std::sqrt(bc2) / bc1));
+  AdamConsts k = adam_consts_plain(h->lr, h->beta1, h->beta2, h->eps, t);
   k.l1 = (float)h->l1; k.l2 = (float)h->l2; k.clamp = (float)h->clamp;
   k.use_penalty = (h->l1 != 0 || h->l2 != 0) ? 1 : 0;
   k.use_clamp = h->clamp != 0 ? 1 : 0;

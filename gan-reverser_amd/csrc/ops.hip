@@ -60,6 +60,20 @@ extern "C" int gr_mse_host(gr_ctx* c, const float* x, const float* t, int64_t n,
   if (!c || !x || !t || n <= 0 || ng <= 0) return GR_ERR_INVALID;
   return criterion_host(c, x, t, n, loss, grad, [&](const float* dx, const float* dt, double* dl, float* dg) { launch_mse(dx, dt, n, ng, dl, dg, c->stream); });
 }
+// noise refinement: the per-row criterion and the per-row best-keeping + Adam step (kernels in elem.hip)
+extern "C" int gr_mse_rows_dev(gr_ctx* c, const float* x, const float* t, int64_t rows, int64_t n, float* loss_rows, float* grad) {
+  if (!c || !x || !t || !loss_rows || rows <= 0 || n <= 0) return GR_ERR_INVALID;
+  launch_mse_rows(x, t, rows, n, loss_rows, grad, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_adam_rows_step_dev(gr_ctx* c, float* z, float* g, float* m, float* v, int64_t rows, int64_t nd, const gr_adam_hyper* h, int t, float clamp,
+                                     const float* loss_rows, float* best_loss, float* best_z, int update) {
+  if (!c || !z || !loss_rows || !best_loss || !best_z || rows <= 0 || nd <= 0 || rows > INT32_MAX || nd > INT32_MAX || clamp < 0) return GR_ERR_INVALID;
+  if (update && (!g || !m || !v || !h || t < 1)) return GR_ERR_INVALID;
+  const AdamConsts k = update ? adam_consts_plain(h->lr, h->beta1, h->beta2, h->eps, t) : AdamConsts{};
+  launch_adam_rows(z, g, m, v, (int)rows, (int)nd, k, clamp, loss_rows, best_loss, best_z, update ? 1 : 0, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
 // nn.BCECriterion (sizeAverage): train.lua:173's CRITERION, used by adversarial.lua (the GAN step's loss; first pieces of SURVEY.md 8f rank 4)
 extern "C" int gr_bce_dev(gr_ctx* c, const float* x, const float* t, int64_t n, double* loss_dev, float* grad) {
   if (!c || !x || !t || n <= 0) return GR_ERR_INVALID;

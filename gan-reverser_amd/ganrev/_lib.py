@@ -52,6 +52,14 @@ class Hyper(C.Structure):
         super().__init__(lr, beta1, beta2, eps, l1, l2, clamp)
 
 
+class AdamHyper(C.Structure):
+    """gr_adam_hyper: optim.adam's own four scalars (gr_adam_rows_step_dev: no penalty, no gradient clamp)"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+    def __init__(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        super().__init__(lr, beta1, beta2, eps)
+
+
 GR_OPT_SGD, GR_OPT_ADAGRAD, GR_OPT_ADADELTA, GR_OPT_ADAMAX, GR_OPT_RMSPROP = range(1, 6)      # gr_optim_step: the optim rock's other five methods
 OPT_METHODS = {"sgd": GR_OPT_SGD, "adagrad": GR_OPT_ADAGRAD, "adadelta": GR_OPT_ADADELTA, "adamax": GR_OPT_ADAMAX, "rmsprop": GR_OPT_RMSPROP}
 # which of a net's two state vectors a method uses, under the key the mirror in ganrev/optim.py keeps it (slot 0, slot 1); sgd's only with a momentum
@@ -125,6 +133,10 @@ _SIGS = {
     "gr_embed_dev": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int64, C.c_int, _P, C.POINTER(_P)]),
     "gr_net_backward_host": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "gr_net_backward_dev": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "gr_net_set_input_grad": (C.c_int, [_P, C.c_int]),
+    "gr_net_backward_input_dev": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "gr_mse_rows_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "gr_adam_rows_step_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.POINTER(AdamHyper), C.c_int, C.c_float, _P, _P, _P, C.c_int]),
     "gr_net_layer_output": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "gr_net_get_pool_index": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "gr_mse_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), _P]),
@@ -378,6 +390,17 @@ class Context:
         """nn.MSECriterion (sizeAverage) on device tensors of n floats: the loss (one double) into loss_dev, gradInput into
         grad_dev when given; n_global = the element count the mean is taken over (default n)"""
         self.check(self.lib.gr_mse_dev(self.h, _ptr(x), _ptr(t), int(n), int(n_global or n), _ptr(loss_dev), _ptr(grad_dev)), "gr_mse_dev")
+
+    def mse_rows_dev(self, x, t, rows, n, loss_rows_dev, grad_dev=None):
+        """per-row nn.MSECriterion on device tables [rows x n]: loss_rows_dev[i] (float) = mean_j (x_ij - t_ij)^2, grad_dev (when given) its
+        gradient 2 (x - t) / n.  One launch; the bits repeat."""
+        self.check(self.lib.gr_mse_rows_dev(self.h, _ptr(x), _ptr(t), int(rows), int(n), _ptr(loss_rows_dev), _ptr(grad_dev)), "gr_mse_rows_dev")
+
+    def adam_rows_step_dev(self, z, g, m, v, rows, nd, hyper, t, loss_rows, best_loss, best_z, clamp=0.0, update=True):
+        """one launch: rows whose loss_rows fell below best_loss store it and copy their z to best_z; then (update) optim.adam step t on
+        z / g / m / v [rows x nd] (hyper: AdamHyper), z clamped to +-clamp when clamp > 0"""
+        self.check(self.lib.gr_adam_rows_step_dev(self.h, _ptr(z), _ptr(g), _ptr(m), _ptr(v), int(rows), int(nd), C.byref(hyper) if hyper is not None else None,
+                                                  int(t), float(clamp), _ptr(loss_rows), _ptr(best_loss), _ptr(best_z), int(bool(update))), "gr_adam_rows_step_dev")
 
     def bce(self, x, t, want_grad=True):
         """nn.BCECriterion (sizeAverage): (loss, gradInput)"""
@@ -670,6 +693,7 @@ class Net:
         self.n_params = int(self.lib.gr_net_param_count(h))
         assert self.perm is None or self.perm.size == self.n_params, (self.perm.size, self.n_params)
         self.training = True               # the mode set_training last gave the net (a new gr_net is in training mode)
+        self.input_grad = False            # set_input_grad: evaluate()-mode forwards keep what backward_input_dev reads
 
     def close(self):
         if getattr(self, "h", None):
@@ -785,6 +809,15 @@ class Net:
 
     def backward_dev(self, x_dev, gout_dev, batch, gin_dev=None):
         self._c(self.lib.gr_net_backward_dev(self.h, _ptr(x_dev), _ptr(gout_dev), int(batch), _ptr(gin_dev)), "gr_net_backward_dev")
+
+    def set_input_grad(self, on):
+        """evaluate()-mode forwards keep what backward_input_dev reads (gr_net_set_input_grad); off (the default) they are what they always were"""
+        self._c(self.lib.gr_net_set_input_grad(self.h, int(bool(on))), "gr_net_set_input_grad")
+        self.input_grad = bool(on)
+
+    def backward_input_dev(self, x_dev, gout_dev, batch, gin_dev):
+        """nn.Module:updateGradInput in evaluate(): gradInput alone, nothing accumulated (gr_net_backward_input_dev)"""
+        self._c(self.lib.gr_net_backward_input_dev(self.h, _ptr(x_dev), _ptr(gout_dev), int(batch), _ptr(gin_dev)), "gr_net_backward_input_dev")
 
     def layer_output(self, layer, shape):
         a = np.empty(shape, dtype=np.float32)

@@ -268,9 +268,15 @@ def parse(argv=None):
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--resident", action="store_true", help="device-resident pipeline only: analyse the tables where the embedding wrote them; the image table is never copied to the host")
     p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
+    p.add_argument("--refine", type=int, default=0, metavar="STEPS", help="refine the recovered noise through G: STEPS Adam steps per image on the MSE between G(z) and the image, starting at R's estimate (ganrev.refine; 0, the reference's behaviour: R's estimate is final)")
+    p.add_argument("--refine_lr", type=float, default=0.01, help="Adam learning rate of --refine")
     OPT = p.parse_args(argv)
     if OPT.resident and OPT.host:
         p.error("--resident applies to the device-resident pipeline: not with --host")
+    if OPT.refine and OPT.host:
+        p.error("--refine runs on the device-resident tables: not with --host")
+    if OPT.refine < 0:
+        p.error("--refine: a step count")
     return OPT
 
 
@@ -335,6 +341,24 @@ def main(argv=None):
             ctx.upload(images, di.ptr); ctx.upload(attributesFixer, df.ptr)
     else:
         di, da, df = embed_dev(MODEL_G, MODEL_R, dn, OPT.batchSize, MODEL_R_FIXER, keep_images=True, dims=dims)
+        if OPT.refine:
+            # `attributes` only: pulling attributesFixer back to the unfixed image would undo the fix, and the anomaly score needs the
+            # unrefined reconstruction.  The search and the clusters below read the refined table.
+            from . import device, refine
+            say("Refining the recovered noise through G...")
+            dmG = device.DeviceModel(ctx, MODEL_G)
+            try:
+                first, best = refine.refineNoise(ctx, dmG, di.ptr, da.ptr, N, OPT.refine, OPT.batchSize, lr=OPT.refine_lr, clamp=1.0 if method == "uniform" else 0.0)
+            finally:
+                dmG.close()
+            summary["refine"] = dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
+                                     loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
+            if OPT.render:
+                from . import render
+                k = min(52, N)
+                again = forwardBatchedDev(MODEL_G, da.rows(0, k), OPT.batchSize)
+                render.fixed_pairs_grid(di, again, k, colorSpace, path=out("refined_pairs.png"))      # image next to G(refined z)
+                again.free()
         by_attr, by_pix = createSimilaritySearchDev(5, 100, da, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
         attributes, attributesFixer = da.numpy(), df.numpy()
         dn.free()

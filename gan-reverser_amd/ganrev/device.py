@@ -155,20 +155,27 @@ class DeviceModel:
             lo += k
         return cat
 
-    def backward(self, g_dev, B, want_gin, node=None):
-        """gradOutput (device) -> gradInput (device pointer, or None when not wanted); accumulates every part's parameter gradient"""
+    def backward(self, g_dev, B, want_gin, node=None, params=True):
+        """gradOutput (device) -> gradInput (device pointer, or None when not wanted); accumulates every part's parameter gradient.
+        params=False: nn.Module:updateGradInput in evaluate() mode - every part runs gr_net_backward_input_dev (after a forward with
+        set_input_grad on), gradInput alone and no parameter gradient anywhere."""
         node = self.model if node is None else node
         x_dev = self.x[id(node)]
         kids = self.kids[id(node)]
+        if not params and not want_gin:
+            return None                   # nothing else is formed on this route
         if kids is None:
             gin = self.mem.floats((id(node), "gin"), B * _vol(node._net.in_dims)) if want_gin else None
-            node._net.backward_dev(x_dev, g_dev, B, gin)
+            if params:
+                node._net.backward_dev(x_dev, g_dev, B, gin)
+            else:
+                node._net.backward_input_dev(x_dev, g_dev, B, gin)
             return gin
         if isinstance(node, nn._TableSum):
             nin = B * self.in_features(node)
             acc = self.mem.floats((id(node), "gsum"), nin) if want_gin else None
             for j, b in enumerate(self.branches[id(node)]):
-                gi = g_dev if isinstance(b, nn.Identity) else self.backward(g_dev, B, want_gin, b)
+                gi = g_dev if isinstance(b, nn.Identity) else self.backward(g_dev, B, want_gin, b, params)
                 if want_gin and j == 0:
                     self.ctx.copy2d(acc, nin // B, gi, nin // B, B, nin // B)
                 elif want_gin:
@@ -176,7 +183,7 @@ class DeviceModel:
             return acc
         if not isinstance(node, nn.Concat):
             for i in range(len(kids) - 1, -1, -1):
-                g_dev = self.backward(g_dev, B, want_gin or i > 0, kids[i])
+                g_dev = self.backward(g_dev, B, want_gin or i > 0, kids[i], params)
             return g_dev
         total, lo, acc = self.out_features(node), 0, None
         nin = B * self.in_features(node)
@@ -184,7 +191,7 @@ class DeviceModel:
             k = self.out_features(b)
             gs = self.mem.floats((id(node), "gslice", j), B * k)
             self.ctx.copy2d(gs, k, g_dev + 4 * lo, total, B, k)
-            gi = self.backward(gs, B, want_gin, b)
+            gi = self.backward(gs, B, want_gin, b, params)
             if want_gin:
                 if acc is None:
                     acc = gi                      # the first branch's own gradInput buffer holds the sum
@@ -225,6 +232,10 @@ class DeviceModel:
     def set_training(self, training):
         for n in self.nets:
             n.set_training(training)
+
+    def set_input_grad(self, on):
+        for n in self.nets:
+            n.set_input_grad(on)
 
     def range_guard_scan(self):
         for n in self.nets:

@@ -290,6 +290,39 @@ class Module:
             self._flat[1][...] += net.get_grads()  # accGradParameters accumulates into the flat gradient
         return self.gradInput
 
+    def updateGradInput(self, input, gradOutput):
+        """nn.Module:updateGradInput of a compiled model in evaluate(): gradInput alone - a frozen BatchNorm is an affine map, no parameter
+        gradient is formed, no state moves.  The forward behind `input` is run again on the device with the parts' input-gradient flag on
+        (the fused evaluate()-mode forward keeps no raw stage outputs) at the Philox counter of the forward it repeats, so an always-on
+        Dropout draws the same noise; flag and counters are what they were when the call returns."""
+        from . import device
+        x, g = L.f32(input), L.f32(gradOutput)
+        nets = [ch._net for ch, _, _ in self._param_chunks()]
+        if not nets or any(n is None for n in nets):
+            raise L.GanrevError("updateGradInput called before forward")
+        if any(n.training for n in nets):
+            raise L.GanrevError("updateGradInput is the evaluate()-mode input gradient; in training mode use backward")
+        ctx, b = nets[0].ctx, x.shape[0]
+        dm = device.DeviceModel(ctx, self)
+        saved = [(n, n.forward_counter(), getattr(n, "input_grad", False)) for n in nets]
+        xd = gd = None
+        try:
+            xd, gd = ctx.upload(x), ctx.upload(g)
+            for n, counter, _ in saved:
+                n.set_forward_counter(max(counter - 1, 0))
+                n.set_input_grad(True)
+            dm.forward(xd, b)
+            self.gradInput = ctx.download(dm.backward(gd, b, True, params=False), x.shape)
+        finally:
+            for n, counter, flag in saved:
+                n.set_input_grad(flag)
+                n.set_forward_counter(counter)
+            for p in (xd, gd):
+                if p is not None:
+                    ctx.free(p)
+            dm.close()
+        return self.gradInput
+
 
 def _over_children(fn):
     """fn(self, children, ...) states what a container that runs as several compiled parts does with a call: it passes the call on

@@ -37,6 +37,12 @@ int gr_net_backward_host(gr_net*, const float* in_host, const float* gout_host, 
 int gr_mse_host(gr_ctx*, const float*, const float*, int64_t n, int64_t n_global, double* loss, float* grad);
 int gr_bce_host(gr_ctx*, const float*, const float*, int64_t n, double* loss, float* grad);     /* nn.BCECriterion (train.lua:173) */
 int gr_adam_step(gr_net*, const gr_hyper*, int t);
+int gr_net_set_input_grad(gr_net*, int on);      /* evaluate()-mode forwards keep what the input-only backward reads */
+int gr_net_backward_input_dev(gr_net*, const float* in_dev, const float* gout_dev, int batch, float* gin_dev);
+typedef struct { double lr, beta1, beta2, eps; } gr_adam_hyper;
+int gr_mse_rows_dev(gr_ctx*, const float* x_dev, const float* t_dev, int64_t rows, int64_t n, float* loss_rows_dev, float* grad_dev);
+int gr_adam_rows_step_dev(gr_ctx*, float* z, float* g, float* m, float* v, int64_t rows, int64_t nd, const gr_adam_hyper*, int t,
+                          float clamp, const float* loss_rows, float* best_loss, float* best_z, int update);
 int gr_cosine_topk_host(gr_ctx*, const float* emb, int64_t n, int d, const int64_t* rows, int q, int k,
                         int64_t* idx, float* score, int accumulate_in_float);
 int gr_cosine_similarity_host(gr_ctx*, const float* a, const float* b, int d, float* out);

@@ -132,6 +132,14 @@ int gr_embed_dev(gr_net* gnet, gr_net* const* rnets, int n_rnets, const float* n
 /* m:backward(input, gradOutput) -> m.gradInput ; accumulates into the flat gradient  (train_r.lua:151) */
 int gr_net_backward_host(gr_net* net, const float* in_host, const float* grad_out_host, int batch, float* grad_in_host /*nullable*/);
 int gr_net_backward_dev(gr_net* net, const float* in_dev, const float* grad_out_dev, int batch, float* grad_in_dev /*nullable*/);
+/* nn.Module:updateGradInput in evaluate() mode: gradInput alone.  A frozen BatchNorm is a per-channel affine map of the running statistics,
+ * no parameter gradient is formed, and neither the flat gradient nor a running statistic nor a mask is touched; everything runs on the
+ * context's stream.  gr_net_set_input_grad(net, 1) (per net, default 0) makes every evaluate()-mode forward of the net keep what this
+ * backward reads - raw stage outputs and fp32 stage outputs instead of fused epilogues and operand-ready-only hand-overs; with the flag
+ * off the forward is what it always was.  gr_net_backward_input_dev needs the last forward to have been such a forward at the same
+ * batch, and the net still in evaluate() mode: GR_ERR_STATE otherwise, with a message naming what is missing. */
+int gr_net_set_input_grad(gr_net* net, int on);
+int gr_net_backward_input_dev(gr_net* net, const float* in_dev, const float* grad_out_dev, int batch, float* grad_in_dev);
 /* nn.SpatialMaxPooling.indices of the last forward (models.lua:422,440): one byte per output element, 0..3 = position in the
  * 2x2 window in scan order (dy, dx); n must be batch * C * Ho * Wo of that layer */
 int gr_net_get_pool_index(gr_net* net, int layer_index, uint8_t* host, int64_t n);
@@ -153,6 +161,16 @@ typedef struct {
   double l1, l2, clamp;           /* OPT.R_L1 0, OPT.R_L2 1e-4, OPT.R_clamp 1   (train_r.lua:22-24) */
 } gr_hyper;
 int gr_adam_step(gr_net* net, const gr_hyper* h, int t /*1-based step; state.t after increment*/);
+/* ---- noise refinement: row-wise criterion and optimiser on device tables (every row is an optimisation problem of its own) ----
+ * gr_mse_rows_dev: loss[i] = sum_j (x_ij - t_ij)^2 / n (a float per row; the sum in double in a fixed order, so the bits repeat) and, unless
+ * grad_dev is null, grad_ij = 2 (x_ij - t_ij) / n.  One launch.
+ * gr_adam_rows_step_dev, one launch: first, every row whose loss_rows[i] < best_loss[i] stores that loss and copies row i of z to best_z;
+ * then, when update != 0, optim.adam at step t (1-based) on z / g / m / v [rows x nd] exactly as gr_adam_step computes it without penalty and
+ * gradient clamp (step size formed in double, epsilon outside the bias correction), and when clamp > 0, z clamped to [-clamp, clamp]. */
+typedef struct { double lr, beta1, beta2, eps; } gr_adam_hyper;
+int gr_mse_rows_dev(gr_ctx* ctx, const float* x_dev, const float* t_dev, int64_t rows, int64_t n, float* loss_rows_dev, float* grad_dev /*nullable*/);
+int gr_adam_rows_step_dev(gr_ctx* ctx, float* z_dev, float* g_dev, float* m_dev, float* v_dev, int64_t rows, int64_t nd, const gr_adam_hyper* /*hyper*/, int t,
+                          float clamp, const float* loss_rows_dev, float* best_loss_dev, float* best_z_dev, int update);
 int gr_adam_reset(gr_net* net);                             /* OPTSTATE = {adam={R={}}}  train_r.lua:125 */
 int gr_adam_get_state(gr_net* net, float* m_host, float* v_host);
 int gr_adam_set_state(gr_net* net, const float* m_host, const float* v_host);
