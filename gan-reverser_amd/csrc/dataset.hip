@@ -16,7 +16,8 @@
 // Shape: one thread computes PX (1 or 4) adjacent output pixels of every plane.  It walks the vertical source span of its output row and,
 // for each source row of the span, evaluates the row-pass value in registers - the fp32 intermediate of the two-pass algorithm is rounded
 // where the row pass would round it but never written.  Grid-stride loop over a bounded grid, no LDS.  The _v4 forms store 16 bytes per
-// plane and (dataset kernel) read the interleaved bytes as aligned dwords; the scalar forms take any width and any alignment.
+// plane and (dataset kernel) read the interleaved bytes as aligned dwords; the scalar forms take any width and any alignment.  The gather
+// kernel at the end of the file is the dataset kernel over a cache of images of mixed size: one launch for any list of them.
 #include "kernels.h"
 #include "colorspace.h"
 
@@ -154,9 +155,41 @@ __device__ __forceinline__ float normalize_value(float v) {          // utils/nn
   return v > 1.f ? 1.f : v;
 }
 
+// PX adjacent output pixels (row dy, columns gx * PX ...) of the image whose pixels start at pixel `base` of `in`: the two scale passes over
+// load_pixel<SC, DW>, the colour space, the normalise step.  The per-pixel body of both kernels below.
+template <int SC, int TO, int PX, bool DW>
+__device__ __forceinline__ void dataset_pixels(const uint8_t* __restrict__ in, long base, const ScaleAxis& ay, const ScaleAxis& ax, int dy, int gx, int normalize, Px3 (&y)[PX]) {
+  constexpr int NC = SC == 1 ? 1 : 3, CO = TO == CS_Y ? 1 : 3;
+  const ScaleSpan sy = scale_span(ay, dy);
+#pragma unroll
+  for (int j = 0; j < PX; ++j) {
+    const Vals<NC> v = scaled_pixel<NC>(ay, ax, sy, scale_span(ax, gx * PX + j),
+                                        [&](int yy, int xx) { return load_pixel<SC, DW>(in, base + (long)yy * ax.src_len + xx); });
+    Px3 rgb{v.v[0], v.v[0], v.v[0]};                    // grey: the plane three times
+    if constexpr (NC == 3) { rgb.b = v.v[1]; rgb.c = v.v[2]; }
+    y[j] = cs_from_rgb<TO>(rgb);
+    if (normalize) { y[j].a = normalize_value(y[j].a); if (CO == 3) { y[j].b = normalize_value(y[j].b); y[j].c = normalize_value(y[j].c); } }
+  }
+}
+// ... and their store: PX == 4 writes 16 bytes per plane (dst 16-byte aligned), PX == 1 one float
+template <int TO, int PX>
+__device__ __forceinline__ void store_pixels(float* __restrict__ dst, long plane_out, const Px3 (&y)[PX]) {
+  constexpr int CO = TO == CS_Y ? 1 : 3;
+  if constexpr (PX == 4) {
+    *reinterpret_cast<float4*>(dst) = make_float4(y[0].a, y[1].a, y[2].a, y[3].a);
+    if (CO == 3) {
+      *reinterpret_cast<float4*>(dst + plane_out) = make_float4(y[0].b, y[1].b, y[2].b, y[3].b);
+      *reinterpret_cast<float4*>(dst + 2 * plane_out) = make_float4(y[0].c, y[1].c, y[2].c, y[3].c);
+    }
+  } else {
+    dst[0] = y[0].a;
+    if (CO == 3) { dst[plane_out] = y[0].b; dst[2 * plane_out] = y[0].c; }
+  }
+}
+
 template <int SC, int TO, bool V4>
 __global__ __launch_bounds__(256) void dataset_images_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, long n, ScaleAxis ay, ScaleAxis ax, int normalize) {
-  constexpr int PX = V4 ? 4 : 1, NC = SC == 1 ? 1 : 3, CO = TO == CS_Y ? 1 : 3;
+  constexpr int PX = V4 ? 4 : 1, CO = TO == CS_Y ? 1 : 3;
   const int groups = ax.dst_len / PX;
   const long total = n * ay.dst_len * groups;
   const long image_in = (long)ay.src_len * ax.src_len, plane_out = (long)ay.dst_len * ax.dst_len;
@@ -165,29 +198,9 @@ __global__ __launch_bounds__(256) void dataset_images_kernel(const uint8_t* __re
     const int gx = (int)(p - row * groups);
     const long img = row / ay.dst_len;
     const int dy = (int)(row - img * ay.dst_len);
-    const long base = img * image_in;                     // in pixels
-    const ScaleSpan sy = scale_span(ay, dy);
     Px3 y[PX];
-#pragma unroll
-    for (int j = 0; j < PX; ++j) {
-      const Vals<NC> v = scaled_pixel<NC>(ay, ax, sy, scale_span(ax, gx * PX + j),
-                                          [&](int yy, int xx) { return load_pixel<SC, V4>(in, base + (long)yy * ax.src_len + xx); });
-      Px3 rgb{v.v[0], v.v[0], v.v[0]};                    // grey: the plane three times
-      if constexpr (NC == 3) { rgb.b = v.v[1]; rgb.c = v.v[2]; }
-      y[j] = cs_from_rgb<TO>(rgb);
-      if (normalize) { y[j].a = normalize_value(y[j].a); if (CO == 3) { y[j].b = normalize_value(y[j].b); y[j].c = normalize_value(y[j].c); } }
-    }
-    float* dst = out + img * CO * plane_out + (long)dy * ax.dst_len + gx * PX;
-    if constexpr (V4) {
-      *reinterpret_cast<float4*>(dst) = make_float4(y[0].a, y[1].a, y[2].a, y[3].a);
-      if (CO == 3) {
-        *reinterpret_cast<float4*>(dst + plane_out) = make_float4(y[0].b, y[1].b, y[2].b, y[3].b);
-        *reinterpret_cast<float4*>(dst + 2 * plane_out) = make_float4(y[0].c, y[1].c, y[2].c, y[3].c);
-      }
-    } else {
-      dst[0] = y[0].a;
-      if (CO == 3) { dst[plane_out] = y[0].b; dst[2 * plane_out] = y[0].c; }
-    }
+    dataset_pixels<SC, TO, PX, V4>(in, img * image_in, ay, ax, dy, gx, normalize, y);
+    store_pixels<TO, PX>(out + img * CO * plane_out + (long)dy * ax.dst_len + gx * PX, plane_out, y);
   }
 }
 
@@ -218,6 +231,52 @@ void launch_dataset_images(const uint8_t* in, long n, int sc, const ScaleAxis& a
     case 1: dataset_launch_to<1>(in, n, ay, ax, to, normalize, out, s); break;
     case 3: dataset_launch_to<3>(in, n, ay, ax, to, normalize, out, s); break;
     default: dataset_launch_to<4>(in, n, ay, ax, to, normalize, out, s); break;
+  }
+}
+
+// ------------------------------------------------------------------ the same over a cache of decoded files (gr_dataset_cache_load_dev)
+// Row k of out is image recs[idx[k]] at ITS source size and channel count: the record is read once per item, its two ScaleAxis are built by
+// the function the host builds them with (one correctly rounded division each), the channel count is a branch (uniform over a wave wherever a
+// wave stays inside one image: always at dh * dw / PX >= 64 items per image).  Every cached image is read in load_pixel's dword form - the
+// cache places it on a 4-byte boundary, pads it to a dword and keeps a dword of the allocation behind it; V4 here is the store form alone.
+template <int TO, bool V4>
+__global__ __launch_bounds__(256) void dataset_gather_kernel(const CachedImage* __restrict__ recs, const long* __restrict__ idx, float* __restrict__ out, long n, int dh, int dw,
+                                                             int normalize) {
+  constexpr int PX = V4 ? 4 : 1, CO = TO == CS_Y ? 1 : 3;
+  const int groups = dw / PX;
+  const long total = n * dh * groups;
+  const long plane_out = (long)dh * dw;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const long row = p / groups;                          // k * dh + dy
+    const int gx = (int)(p - row * groups);
+    const long k = row / dh;
+    const int dy = (int)(row - k * dh);
+    const CachedImage im = recs[idx[k]];
+    const ScaleAxis ay = scale_axis(im.sh, dh), ax = scale_axis(im.sw, dw);
+    Px3 y[PX];
+    if (im.sc == 3) dataset_pixels<3, TO, PX, true>(im.data, 0, ay, ax, dy, gx, normalize, y);
+    else if (im.sc == 4) dataset_pixels<4, TO, PX, true>(im.data, 0, ay, ax, dy, gx, normalize, y);
+    else dataset_pixels<1, TO, PX, true>(im.data, 0, ay, ax, dy, gx, normalize, y);
+    store_pixels<TO, PX>(out + k * CO * plane_out + (long)dy * dw + gx * PX, plane_out, y);
+  }
+}
+
+template <int TO>
+static void gather_launch(const CachedImage* recs, const long* idx, long n, int dh, int dw, int normalize, float* out, double bytes_in, hipStream_t s) {
+  const long npix = n * dh * dw;
+  const bool v4 = dw % 4 == 0 && ((uintptr_t)out & 15) == 0;      // whole groups of four per output row: every plane row then starts 16-byte aligned when `out` does
+  const long work = v4 ? npix / 4 : npix;
+  long blocks = (work + 255) / 256; if (blocks > 2048) blocks = 2048;
+  KtScope kt(v4 ? "dataset_gather_kernel_v4" : "dataset_gather_kernel", 0.0, bytes_in + 4.0 * (TO == CS_Y ? 1 : 3) * (double)npix, s);
+  if (v4) hipLaunchKernelGGL((dataset_gather_kernel<TO, true>), dim3((unsigned)blocks), dim3(256), 0, s, recs, idx, out, n, dh, dw, normalize);
+  else hipLaunchKernelGGL((dataset_gather_kernel<TO, false>), dim3((unsigned)blocks), dim3(256), 0, s, recs, idx, out, n, dh, dw, normalize);
+}
+void launch_dataset_gather(const CachedImage* recs, const long* idx, long n, int dh, int dw, int to, int normalize, float* out, double bytes_in, hipStream_t s) {
+  switch (to) {
+    case CS_RGB: gather_launch<CS_RGB>(recs, idx, n, dh, dw, normalize, out, bytes_in, s); break;
+    case CS_Y: gather_launch<CS_Y>(recs, idx, n, dh, dw, normalize, out, bytes_in, s); break;
+    case CS_YUV: gather_launch<CS_YUV>(recs, idx, n, dh, dw, normalize, out, bytes_in, s); break;
+    default: gather_launch<CS_HSL>(recs, idx, n, dh, dw, normalize, out, bytes_in, s); break;
   }
 }
 

@@ -446,11 +446,12 @@ void launch_scale_copy(const float* src, float* dst, long n, float scale, hipStr
 enum { CS_RGB = 0, CS_Y = 1, CS_YUV = 2, CS_HSL = 3 };
 void launch_colorspace(const float* in, int from, int to, long batch, long hw, float* out, hipStream_t s);
 // ---- dataset.lua's per-image work (dataset.hip; include/ganrev.h, gr_image_scale_dev / gr_dataset_images_dev, states the arithmetic).
-// ScaleAxis = one pass of image.scale's scaleLinear_rowcol(src_len, dst_len); scale is rounded to fp32 once, on the host.
+// ScaleAxis = one pass of image.scale's scaleLinear_rowcol(src_len, dst_len); scale is one correctly rounded fp32 division of two exact
+// conversions, on the host - or, by the same function, in the gather kernel, whose source sizes differ from image to image.
 enum { SCALE_COPY = 0, SCALE_UP = 1, SCALE_DOWN = 2, SCALE_REPLICATE = 3 };
 struct ScaleAxis { int mode, src_len, dst_len; float scale; };
 constexpr int SCALE_MAX_LEN = 32768;                               // per side: keeps every fp32 index product below 2^15, far from an integer it must not reach
-inline ScaleAxis scale_axis(int src_len, int dst_len) {
+__host__ __device__ inline ScaleAxis scale_axis(int src_len, int dst_len) {
   if (dst_len == src_len) return ScaleAxis{SCALE_COPY, src_len, dst_len, 1.f};
   if (dst_len < src_len) return ScaleAxis{SCALE_DOWN, src_len, dst_len, (float)src_len / (float)dst_len};
   if (src_len == 1) return ScaleAxis{SCALE_REPLICATE, src_len, dst_len, 0.f};
@@ -461,6 +462,12 @@ inline ScaleAxis scale_axis(int src_len, int dst_len) {
 void launch_image_scale(const float* in, long nplanes, const ScaleAxis& ay, const ScaleAxis& ax, float* out, hipStream_t s);
 // in uint8 [n x sh x sw x sc] (sc 1, 3 or 4) -> out [n x (1|3) x dh x dw] in colour space `to`, normalised to [-1, 1] when normalize != 0.  One launch.
 void launch_dataset_images(const uint8_t* in, long n, int sc, const ScaleAxis& ay, const ScaleAxis& ax, int to, int normalize, float* out, hipStream_t s);
+// The same per image over a cache of decoded files of mixed size (gr_dataset_cache_*): row k of out [n x (1|3) x dh x dw] is what
+// launch_dataset_images writes for image recs[idx[k]] alone.  CachedImage = where an image's bytes lie (4-byte aligned, padded to a dword,
+// at least one more dword of the allocation behind them) and its source size.  One launch whatever sizes the list mixes; bytes_in = the
+// bytes of the listed images (the timer's label).  The caller has checked every idx[k] against the record count.
+struct CachedImage { const uint8_t* data; int sh, sw, sc, pad; };
+void launch_dataset_gather(const CachedImage* recs, const long* idx, long n, int dh, int dw, int to, int normalize, float* out, double bytes_in, hipStream_t s);
 // ---- image grids (render.hip): image.toDisplayTensor over tiles gathered from device-resident image tables, with the decorations of
 // apply_r.lua's pictures (include/ganrev.h, gr_image_grid_dev, states the arithmetic).  GridTile is the per-tile metadata the kernels read
 // from a small device array; GridGeom travels in the kernel arguments.

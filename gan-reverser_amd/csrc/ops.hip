@@ -169,6 +169,133 @@ extern "C" int gr_dataset_images_dev(gr_ctx* c, const uint8_t* in, int64_t n, in
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ the decoded files of a dataset, kept on the device (gr_dataset_cache_*)
+// An arena of chunks: an image is uploaded once, behind the last one of the open chunk (on a 4-byte boundary, padded to a dword, the chunk
+// keeps a spare dword at its end), or into a new chunk when it does not fit; bytes that were uploaded never move.  The records (address,
+// size) are kept on the host, where every call validates against them, and mirrored on the device for the gather kernel: the mirror is
+// brought up to date by the first load after an append.  Like a net, the cache has a DevMem of its own and points at its context: it is
+// destroyed before the context is shut down, or left alone after that.
+struct DatasetCache {
+  gr_ctx* ctx = nullptr;
+  DevMem mem;                                             // the chunks, the record mirror, the index buffers
+  size_t chunk_bytes = 0;                                 // what a new chunk gets (an image that needs more gets what it needs)
+  uint8_t* chunk = nullptr; size_t chunk_cap = 0, chunk_used = 0;      // the open chunk
+  std::vector<CachedImage> recs;
+  int64_t bytes = 0;                                      // decoded bytes held (without the padding)
+  CachedImage* d_recs = nullptr; size_t d_recs_bytes = 0, d_recs_n = 0;      // the mirror holds the first d_recs_n records
+  long* d_idx = nullptr; size_t d_idx_bytes = 0;          // a load's index list on the device ...
+  long* h_idx = nullptr; size_t h_idx_count = 0;          // ... and the pinned block it is copied from, free again once ev_idx has passed
+  Event ev_idx;
+};
+static const int64_t GR_DATASET_CHUNK_DEFAULT = (int64_t)64 << 20;
+
+extern "C" int gr_dataset_cache_create(gr_ctx* c, int64_t chunk_bytes, void** out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!out) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_create: null pointer");
+  *out = nullptr;
+  HIPCHK(c, hipSetDevice(c->device));
+  DatasetCache* k = new DatasetCache();
+  k->ctx = c;
+  k->chunk_bytes = (size_t)(chunk_bytes > 0 ? chunk_bytes : GR_DATASET_CHUNK_DEFAULT);
+  const hipError_t e = k->ev_idx.create(hipEventDisableTiming);
+  if (e != hipSuccess) { delete k; return fail(c, GR_ERR_HIP, "gr_dataset_cache_create: %s", hipGetErrorString(e)); }
+  *out = k;
+  return GR_OK;
+}
+extern "C" int gr_dataset_cache_destroy(void* cache) {
+  DatasetCache* k = static_cast<DatasetCache*>(cache);
+  if (!k) return GR_ERR_INVALID;
+  (void)hipSetDevice(k->ctx->device);
+  (void)hipStreamSynchronize(k->ctx->stream);             // the one stream a load is enqueued on
+  delete k;
+  return GR_OK;
+}
+extern "C" int gr_dataset_cache_append(void* cache, const uint8_t* bytes, int sh, int sw, int sc) {
+  DatasetCache* k = static_cast<DatasetCache*>(cache);
+  if (!k) return GR_ERR_INVALID;
+  gr_ctx* c = k->ctx;
+  if (!bytes) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_append: null pointer");
+  if (sc != 1 && sc != 3 && sc != 4) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_append: %d source channels (1, 3 or 4)", sc);
+  if (sh < 1 || sw < 1 || sh > SCALE_MAX_LEN || sw > SCALE_MAX_LEN)
+    return fail(c, GR_ERR_INVALID, "gr_dataset_cache_append: source %d x %d: a side must be in [1, %d]", sh, sw, SCALE_MAX_LEN);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nbytes = (size_t)sh * sw * sc, padded = (nbytes + 3) & ~(size_t)3;      // at most 2^32
+  if (k->chunk_used + padded + 4 > k->chunk_cap) {        // a new chunk; the open one keeps its images (nothing is copied)
+    const size_t cap = padded + 4 > k->chunk_bytes ? padded + 4 : k->chunk_bytes;
+    uint8_t* p = nullptr;
+    const hipError_t e = k->mem.dev(&p, cap);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();                            // (an allocation failure is not sticky: the cache and the context go on)
+      return fail(c, GR_ERR_HIP, "gr_dataset_cache_append: a chunk of %zu bytes: %s (the cache keeps its %zu images)", cap, hipGetErrorString(e), k->recs.size());
+    }
+    HIPCHK(c, hipMemsetAsync(p, 0, cap, c->stream));      // the padding and the spare dword read as zeros
+    k->chunk = p; k->chunk_cap = cap; k->chunk_used = 0;
+  }
+  uint8_t* dst = k->chunk + k->chunk_used;
+  HIPCHK(c, hipMemcpyAsync(dst, bytes, nbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));             // the caller's array is its own again
+  k->chunk_used += padded;
+  k->recs.push_back(CachedImage{dst, sh, sw, sc, 0});
+  k->bytes += (int64_t)nbytes;
+  return GR_OK;
+}
+extern "C" int gr_dataset_cache_size(void* cache, int64_t* n_images, int64_t* bytes) {
+  DatasetCache* k = static_cast<DatasetCache*>(cache);
+  if (!k) return GR_ERR_INVALID;
+  if (n_images) *n_images = (int64_t)k->recs.size();
+  if (bytes) *bytes = k->bytes;
+  return GR_OK;
+}
+extern "C" int gr_dataset_cache_image(void* cache, int64_t i, int* sh, int* sw, int* sc) {
+  DatasetCache* k = static_cast<DatasetCache*>(cache);
+  if (!k) return GR_ERR_INVALID;
+  if (i < 0 || i >= (int64_t)k->recs.size()) return fail(k->ctx, GR_ERR_INVALID, "gr_dataset_cache_image: image %lld is outside [0, %zu)", (long long)i, k->recs.size());
+  const CachedImage& r = k->recs[(size_t)i];
+  if (sh) *sh = r.sh;
+  if (sw) *sw = r.sw;
+  if (sc) *sc = r.sc;
+  return GR_OK;
+}
+extern "C" int gr_dataset_cache_load_dev(void* cache, const int64_t* indices, int64_t n, int dh, int dw, int to_space, int normalize, float* out) {
+  DatasetCache* k = static_cast<DatasetCache*>(cache);
+  if (!k) return GR_ERR_INVALID;
+  gr_ctx* c = k->ctx;
+  if (!indices || !out) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_load: null pointer");
+  if (to_space < GR_CS_RGB || to_space > GR_CS_HSL) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_load: unknown color space <to>: %d", to_space);
+  if (n < 1 || dh < 1 || dw < 1) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_load: n %lld, target %d x %d must be positive", (long long)n, dh, dw);
+  if (dh > SCALE_MAX_LEN || dw > SCALE_MAX_LEN) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_load: target %d x %d: a side is too large (at most %d)", dh, dw, SCALE_MAX_LEN);
+  if (n > GR_SCALE_MAX_ELEMS / ((int64_t)3 * dh * dw)) return fail(c, GR_ERR_INVALID, "gr_dataset_cache_load: %lld images are too large a batch (at most 2^40 elements per tensor)", (long long)n);
+  const int64_t held = (int64_t)k->recs.size();
+  double bytes_in = 0;
+  for (int64_t j = 0; j < n; ++j) {
+    if (indices[j] < 0 || indices[j] >= held)
+      return fail(c, GR_ERR_INVALID, "gr_dataset_cache_load: indices[%lld] = %lld is outside [0, %lld)", (long long)j, (long long)indices[j], (long long)held);
+    const CachedImage& r = k->recs[(size_t)indices[j]];
+    bytes_in += (double)r.sh * r.sw * r.sc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (k->d_recs_n < k->recs.size()) {                      // images were appended since the mirror was written: all records again, then a wait (the vector may grow)
+    TRY(grow_dev(c, k->mem, &k->d_recs, k->d_recs_bytes, past_next_mib(sizeof(CachedImage) * k->recs.size()), c->stream));
+    HIPCHK(c, hipMemcpyAsync(k->d_recs, k->recs.data(), sizeof(CachedImage) * k->recs.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    k->d_recs_n = k->recs.size();
+  }
+  TRY(grow_dev(c, k->mem, &k->d_idx, k->d_idx_bytes, sizeof(long) * (size_t)n, c->stream));
+  // the list travels through a pinned block of the cache's own, so that the copy is asynchronous and the caller's array is its own again on
+  // return; the block is written again only after the previous load's copy has left it (an event that has long passed in a training loop)
+  HIPCHK(c, hipEventSynchronize(k->ev_idx));
+  if ((size_t)n > k->h_idx_count) {
+    k->mem.drop(k->h_idx); k->h_idx = nullptr; k->h_idx_count = 0;
+    HIPCHK(c, k->mem.pinned(&k->h_idx, sizeof(long) * (size_t)n));
+    k->h_idx_count = (size_t)n;
+  }
+  for (int64_t j = 0; j < n; ++j) k->h_idx[j] = (long)indices[j];
+  HIPCHK(c, hipMemcpyAsync(k->d_idx, k->h_idx, sizeof(long) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(k->ev_idx, c->stream));
+  launch_dataset_gather(k->d_recs, k->d_idx, (long)n, dh, dw, to_space, normalize != 0, out, bytes_in, c->stream); LAUNCHCHK(c);
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ search
 extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
                                   int64_t* idx_out, float* score_out, int accf) {

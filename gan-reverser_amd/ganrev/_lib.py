@@ -202,6 +202,12 @@ _SIGS = {
     "gr_image_scale_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gr_image_scale_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gr_dataset_images_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "gr_dataset_cache_create": (C.c_int, [_P, C.c_int64, C.POINTER(_P)]),
+    "gr_dataset_cache_destroy": (C.c_int, [_P]),
+    "gr_dataset_cache_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "gr_dataset_cache_size": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gr_dataset_cache_image": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gr_dataset_cache_load_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gr_conv3_forward_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gr_conv3_backward_data_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gr_conv3_backward_weight_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -880,6 +886,62 @@ class Net:
     def _shape(d):
         c, h, w = d
         return (c,) if (h == 1 and w == 1) else (c, h, w)
+
+
+class DatasetCache:
+    """gr_dataset_cache handle: the decoded files of a dataset in device memory (uint8 HWC at source size), and the one launch that turns any
+    list of them into the fp32 table gr_dataset_images_dev would write image by image.  One owner, like Net: close() (or the finaliser)
+    destroys it while its context is open, never after."""
+
+    def __init__(self, ctx, chunk_bytes=0):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = _P()
+        ctx.check(self.lib.gr_dataset_cache_create(ctx.h, int(chunk_bytes), C.byref(h)), "gr_dataset_cache_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gr_dataset_cache_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and getattr(getattr(self, "ctx", None), "h", None):
+                self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: nothing to report to)
+            pass
+
+    def append(self, image):
+        """one decoded file, uint8 [H x W x 1|3|4] (or [H x W]) -> its number in the cache"""
+        a = np.ascontiguousarray(image, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            raise GanrevError(f"DatasetCache.append: an image is uint8 [H x W x C], not {a.shape}")
+        self.ctx.check(self.lib.gr_dataset_cache_append(self.h, _ptr(a), a.shape[0], a.shape[1], a.shape[2]), "gr_dataset_cache_append")
+        return len(self) - 1
+
+    def size(self):
+        """(images held, their decoded bytes)"""
+        n, b = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.lib.gr_dataset_cache_size(self.h, C.byref(n), C.byref(b)), "gr_dataset_cache_size")
+        return n.value, b.value
+
+    def __len__(self):
+        return self.size()[0]
+
+    def image(self, i):
+        """(sh, sw, sc) of image i: the record kept on the host"""
+        sh, sw, sc = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.lib.gr_dataset_cache_image(self.h, int(i), C.byref(sh), C.byref(sw), C.byref(sc)), "gr_dataset_cache_image")
+        return sh.value, sw.value, sc.value
+
+    def load_dev(self, indices, dh, dw, to_space, normalize, out_dev):
+        """row k of out_dev fp32 [n x (1|3) x dh x dw] = image indices[k], scaled, in colour space to_space (GR_CS_*), normalised to [-1, 1] when
+        `normalize`: one launch on the context's stream (gr_dataset_cache_load_dev)"""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        self.ctx.check(self.lib.gr_dataset_cache_load_dev(self.h, _ptr(idx) if idx.size else None, idx.size, int(dh), int(dw), int(to_space),
+                                                          int(bool(normalize)), _ptr(out_dev)), "gr_dataset_cache_load_dev")
 
 
 def embed_dev(gnet, rnets, noise_dev, rows, batch, attr_out_devs, images_out_dev=None):

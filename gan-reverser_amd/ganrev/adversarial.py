@@ -245,14 +245,18 @@ class DeviceGame:
     def batch(self, real, noise_d=None, noise_g=None, want_loss=False):
         """One batch of adversarial.lua:139-201: OPT.D_iterations updates of D, each on batchSize/2 fresh real images + batchSize/2
         generated ones, then OPT.G_iterations updates of G through D.  real: [D_iterations * batchSize/2 x C x H x W] host array (the
-        one unavoidable upload).  noise_*: host noise to use instead of device-generated noise (parity tests): arrays of
+        one upload), or a nn_utils.DeviceTensor of that shape (a draw from the dataset cache), copied where it lies.  noise_*: host noise to use instead of device-generated noise (parity tests): arrays of
         [D_iterations * batchSize/2 x noiseDim] / [G_iterations * batchSize x noiseDim].  Returns the LAST (loss_D, loss_G)."""
         OPT, B = self.env.OPT, self.env.OPT.batchSize
         half = B // 2
         ctx, gg, dg = self.ctx, self.gg, self.dg
         # `for k=1,OPT.D_iterations` (adversarial.lua:127,168): 0 iterations run zero times - that phase's net stays frozen
         nD, nG = max(0, int(OPT.D_iterations)), max(0, int(OPT.G_iterations))
-        real = np.ascontiguousarray(real, np.float32).reshape(-1, self.npix)
+        on_device = isinstance(real, nn_utils.DeviceTensor)
+        if on_device and real.size != real.shape[0] * self.npix:
+            raise L.GanrevError(f"DeviceGame.batch: device images {real.shape} are not [n x {self.npix} values]")
+        if not on_device:
+            real = np.ascontiguousarray(real, np.float32).reshape(-1, self.npix)
         if real.shape[0] < nD * half:
             raise IndexError("trainData exhausted (adversarial.lua:146 indexes past the loaded examples): "
                              f"{real.shape[0]} images for {nD} D iterations of {half}")
@@ -261,7 +265,10 @@ class DeviceGame:
         loss_d = loss_g = None
         for k in range(nD):
             # (1) D on half real, half generated (adversarial.lua:141-157, fevalD :66-100)
-            ctx.upload(real[k * half:(k + 1) * half], self.inputs)
+            if on_device:
+                ctx.copy2d(self.inputs, self.npix, real.ptr + 4 * k * half * self.npix, self.npix, half, self.npix)
+            else:
+                ctx.upload(real[k * half:(k + 1) * half], self.inputs)
             self._fill_noise(half, None if noise_d is None else np.asarray(noise_d).reshape(nD, half, -1)[k])
             fake = gg.forward(self.noise, half)
             ctx.copy2d(self.inputs + 4 * half * self.npix, self.npix, fake, self.npix, half, self.npix)

@@ -303,7 +303,7 @@ def main(argv=None):
         dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
         MODEL_R = t7.load_checkpoint(OPT.R)["R"]                              # :92-94
         MODEL_R_FIXER = t7.load_checkpoint(OPT.R_fixer)["R"]                  # :101-103
-    scripts.open_dataset(OPT, colorSpace, dims[1], dims[2])                   # apply_r.lua:83-87
+    scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], reads=False)      # apply_r.lua:83-87
     for m in (MODEL_G, MODEL_R, MODEL_R_FIXER):
         m._ctx = ctx
         m.evaluate()

@@ -13,6 +13,11 @@ as bytes and one gr_dataset_images_dev launch per chunk does the rest on the GPU
 image at source size never exists on the host.  A folder of mixed sizes is processed in groups of equal size; each group's images
 are then moved to their places in the result on the device.
 
+DATASET.cache() (the scripts' --cacheDataset) decodes every file ONCE and keeps the bytes on the device as the files store them
+(_lib.DatasetCache); from then on loadImages / loadRandomImages draw the indices they always drew and make one
+gr_dataset_cache_load_dev launch over the drawn images, whatever sizes they mix - the same bits, no decoding, no upload.  The cache holds
+source bytes, so setHeight / setWidth / setColorSpace / setNbChannels keep it; setDirs and setFileExtension change the files and drop it.
+
 Decoders: .png through ganrev.png (8-bit grey / RGB / RGBA); .npy holding uint8 [H x W] or [H x W x 1|3|4] as it is; everything else
 (the reference's jpg) through Pillow when it can be imported.  Without Pillow such a file raises GanrevError naming the file and the
 missing decoder - pixels are never guessed.
@@ -52,6 +57,7 @@ paths = None
 
 CHUNK_BYTES = 64 << 20       # decoded bytes of one size uploaded and converted per launch
 _seed, _draws = 0, 0
+_cache = None                # cache(): the _lib.DatasetCache that holds paths[i] as image i
 
 
 def setColorSpace(colorSpace_):
@@ -66,6 +72,7 @@ def setDirs(dirs_):
     global dirs, paths
     dirs = [dirs_] if isinstance(dirs_, (str, bytes, os.PathLike)) else list(dirs_)
     paths = None
+    uncache()
 
 
 def setFileExtension(fileExtension_):
@@ -73,6 +80,7 @@ def setFileExtension(fileExtension_):
     global fileExtension, paths
     fileExtension = str(fileExtension_)
     paths = None
+    uncache()
 
 
 def setHeight(height_):
@@ -112,6 +120,41 @@ def loadPaths():
             raise L.GanrevError("given directory doesnt contain any files of type: " + fileExtension)      # :88
     paths = files
     return paths
+
+
+def cache(ctx=None, quiet=True):
+    """Decode every file of paths once and keep its bytes on the device: image i of the cache is paths[i].  Later loadImages /
+    loadRandomImages calls are one launch each (module docstring).  -> the number of files.  A cache that exists is replaced."""
+    global _cache
+    uncache()
+    ctx = ctx or L.default_context()
+    if paths is None:
+        loadPaths()
+    if not quiet:
+        print("<dataset> caching %d files" % len(paths))
+    held = L.DatasetCache(ctx)
+    try:
+        for f in paths:
+            held.append(decode(f))
+    except BaseException:
+        held.close()
+        raise
+    _cache = held
+    return len(paths)
+
+
+def uncache():
+    """release the cache (the loads decode their files again)"""
+    global _cache
+    if _cache is not None:
+        held, _cache = _cache, None
+        if getattr(held.ctx, "h", None):
+            held.close()
+
+
+def cached():
+    """whether loads come from the device-resident cache"""
+    return _cache is not None
 
 
 def imageIndices(startAt, count):
@@ -222,27 +265,50 @@ def _convert_group(ctx, arrays, rows, out, to, normalize, planes):
             ctx.free(stage)
 
 
+def _load_decoding(ctx, files, grey_only, normalize, to, planes, out):
+    """the drawn files, decoded now: groups of equal source size, one upload and one launch per group"""
+    groups = {}                                                           # (sh, sw, sc) -> (arrays, rows) waiting for their launch
+    for row, f in enumerate(files):
+        a = decode(f)
+        if grey_only and a.shape[2] != 1:
+            raise L.GanrevError(f"{f}: {a.shape[2]} channels with nbChannels 1 (image.load's colour -> grey conversion is not restated)")
+        arrays, rows = groups.setdefault(a.shape, ([], []))
+        arrays.append(a); rows.append(row)
+        if len(arrays) * a.nbytes >= CHUNK_BYTES:
+            _convert_group(ctx, arrays, rows, out, to, normalize, planes)
+            del groups[a.shape]
+    for arrays, rows in groups.values():
+        _convert_group(ctx, arrays, rows, out, to, normalize, planes)
+
+
+def _load_cached(indices, files, grey_only, normalize, to, out):
+    """the drawn images from the cache: the nbChannels 1 refusal from the host records, then ONE launch"""
+    if grey_only:
+        for i, f in zip(indices, files):
+            sc = _cache.image(int(i))[2]
+            if sc != 1:
+                raise L.GanrevError(f"{f}: {sc} channels with nbChannels 1 (image.load's colour -> grey conversion is not restated)")
+    if len(files):
+        _cache.load_dev(indices, height, width, to, normalize, out.ptr)
+
+
 def _load(indices, grey_only, normalize, device, ctx):
     if height < 1 or width < 1:
         raise L.GanrevError(f"dataset: height {height} and width {width} must be positive")
+    if _cache is not None:
+        if ctx is not None and ctx is not _cache.ctx:
+            raise L.GanrevError("dataset: the cache lives on another context than the one this load names")
+        ctx = _cache.ctx
     ctx = ctx or L.default_context()
     files = [paths[int(i)] for i in indices]
     to = L.COLOR_SPACES[colorSpace]
     planes = 1 if to == L.GR_CS_Y else 3
     out = nn_utils.DeviceTensor(ctx, (len(files), planes, height, width))
-    groups = {}                                                           # (sh, sw, sc) -> (arrays, rows) waiting for their launch
     try:
-        for row, f in enumerate(files):
-            a = decode(f)
-            if grey_only and a.shape[2] != 1:
-                raise L.GanrevError(f"{f}: {a.shape[2]} channels with nbChannels 1 (image.load's colour -> grey conversion is not restated)")
-            arrays, rows = groups.setdefault(a.shape, ([], []))
-            arrays.append(a); rows.append(row)
-            if len(arrays) * a.nbytes >= CHUNK_BYTES:
-                _convert_group(ctx, arrays, rows, out, to, normalize, planes)
-                del groups[a.shape]
-        for arrays, rows in groups.values():
-            _convert_group(ctx, arrays, rows, out, to, normalize, planes)
+        if _cache is not None:
+            _load_cached(indices, files, grey_only, normalize, to, out)
+        else:
+            _load_decoding(ctx, files, grey_only, normalize, to, planes, out)
     except BaseException:
         out.free()
         raise

@@ -47,6 +47,11 @@ class Buffers:
         self.nbytes[p] = int(nbytes)
         return p
 
+    def adopt(self, p, nbytes):
+        """take over a buffer somebody else got from ctx.malloc (a DeviceTensor handed over): freed like the others from now on"""
+        self.nbytes[p] = int(nbytes)
+        return p
+
     def floats(self, key, n):
         """the buffer kept under `key`, grown (never shrunk) to hold n floats"""
         p = self.named.get(key)

@@ -94,11 +94,17 @@ class DeviceLoop:
         self.loss = self.mem.malloc(64)
 
     def load(self, images, colorSpace="rgb"):
-        """the epoch's TRAIN_DATA, device-resident (pretrain_g.lua:118); rgb images are converted to colorSpace there (dataset.lua:153)"""
-        images = np.ascontiguousarray(images, np.float32)
+        """the epoch's TRAIN_DATA, device-resident (pretrain_g.lua:118); rgb images are converted to colorSpace there (dataset.lua:153).
+        images: a host array, uploaded, or the device table a cached dataset leaves (an owned nn_utils.DeviceTensor), which the loop takes
+        over as it is; either way the previous epoch's table is freed"""
         if self.images is not None:
             self.mem.free(self.images)
-        self.images = self.ctx.upload(images, self.mem.malloc(images.nbytes))
+        if isinstance(images, nn_utils.DeviceTensor):
+            assert images.owned and images.ctx is self.ctx
+            self.images, images.owned = self.mem.adopt(images.ptr, 4 * images.size), False
+        else:
+            images = np.ascontiguousarray(images, np.float32)
+            self.images = self.ctx.upload(images, self.mem.malloc(images.nbytes))
         self.n_images = images.shape[0]
         if scripts.needs_conversion(images, colorSpace):
             n, _, h, w = images.shape
@@ -174,7 +180,7 @@ def main(argv=None):
         print(ae)
         print("Number of free parameters in G (total): %d" % ae._param_count())
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
-    DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width)      # :60-64; rgb: the loops convert to --colorSpace as they do for --data
+    DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width, ctx)      # :60-64; rgb: the loops convert to --colorSpace as they do for --data
     nLoad = OPT.N_epoch * OPT.batchSize                                   # :117
     if OPT.compat:
         CRITERION = nn.MSECriterion()                                     # :94

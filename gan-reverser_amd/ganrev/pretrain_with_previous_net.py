@@ -169,8 +169,8 @@ class DeviceDistill:
 
     def forward(self, real_rgb, prev_noise=None, noise=None):
         """:151-183: both noise tensors, the four forwards and the two conversions.  real_rgb: [batchSize / 2 x 3 x H x W] host array
-        (the one upload).  prev_noise / noise: host noise instead of device-drawn noise (parity tests); the shared columns are copied
-        either way."""
+        (the one upload), or a nn_utils.DeviceTensor of that shape (a draw from the dataset cache), copied on the device.
+        prev_noise / noise: host noise instead of device-drawn noise (parity tests); the shared columns are copied either way."""
         s, ctx, B, half = self.s, self.ctx, self.B, self.half
         OPT, (pnd, pmethod) = s.OPT, s.prev[:2]
         _, H, W = self.dims
@@ -185,8 +185,12 @@ class DeviceDistill:
         ctx.colorspace_dev(old, self.pcs, self.cs, B, H, W, self.images_by_gprev)                   # :167 (rgb -> rgb: the :clone())
         self.gg.zero_grads()
         self.images_by_g = self.gg.forward(self.noise, B)                                           # :168
-        real = np.ascontiguousarray(real_rgb, np.float32).reshape(half, 3 * H * W)
-        ctx.upload(real, self.real_rgb)
+        if isinstance(real_rgb, nn_utils.DeviceTensor):
+            if real_rgb.size != half * 3 * H * W:
+                raise L.GanrevError(f"DeviceDistill.forward: device images {real_rgb.shape} are not [{half} x 3 x {H} x {W}]")
+            ctx.copy2d(self.real_rgb, 3 * H * W, real_rgb.ptr, 3 * H * W, half, 3 * H * W)
+        else:
+            ctx.upload(np.ascontiguousarray(real_rgb, np.float32).reshape(half, 3 * H * W), self.real_rgb)
         ctx.colorspace_dev(self.real_rgb, L.GR_CS_RGB, self.cs, half, H, W, self.d_input)           # dataset.lua:153; :173-176
         ctx.copy2d(self.d_input + 4 * half * self.npix, self.npix, self.images_by_gprev, self.npix, half, self.npix)      # :177-180
         ctx.colorspace_dev(self.d_input, self.cs, self.pcs, B, H, W, self.d_input_prev)             # :182
@@ -322,7 +326,7 @@ def main(argv=None):
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
     if data is not None and tuple(data.shape[1:]) != (3, OPT.height, OPT.width):
         raise L.GanrevError(f"--data holds {tuple(data.shape[1:])} images, not rgb (3, {OPT.height}, {OPT.width})")
-    DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width)                               # :69-73; rgb: converted with the generated half (:173-176)
+    DATASET = scripts.open_dataset(OPT, "rgb", OPT.height, OPT.width, ctx)                          # :69-73; rgb: converted with the generated half (:173-176)
     loop = None if OPT.compat else DeviceDistill(s)
     pictures = progress.DistillPictures(loop, OPT.save) if OPT.progress else None
     half, last, path, t0 = OPT.batchSize // 2, None, None, time.perf_counter()
@@ -335,6 +339,8 @@ def main(argv=None):
                 last = compat_batch(s, i, real)
             else:
                 last = loop.batch(real, want_loss=want) or last
+                if isinstance(real, nn_utils.DeviceTensor):
+                    real.free()                                                                     # the batch's draw from the cache
             if not OPT.quiet:
                 print("<batch %d of %d (%.2f%%)> loss G: %.4f, loss D: %.4f" % (i, OPT.N_batches, 100.0 * i / OPT.N_batches, last[0], last[1]))
             if pictures is not None and i % 10 == 0:                                                # :245-247

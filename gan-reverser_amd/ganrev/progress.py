@@ -174,10 +174,15 @@ class TrainPictures:
         self.last = None                                     # what the last call saw: predictions, orders, grids, paths
 
     def visualize(self, TRAIN_DATA, epoch):
-        """the four pictures of epoch `epoch` from the models as they stand; TRAIN_DATA: the epoch's host images (train.lua:216)"""
+        """the four pictures of epoch `epoch` from the models as they stand; TRAIN_DATA: the epoch's images (train.lua:216), a host array
+        or the device table a cached dataset leaves (nn_utils.DeviceTensor)"""
         ctx, OPT, npix, B = self.ctx, self.OPT, self.npix, self.OPT.batchSize
-        n_train = min(50, len(TRAIN_DATA))                                          # train.lua:288 (which indexes past a shorter load)
-        ctx.upload(np.ascontiguousarray(TRAIN_DATA[:n_train], np.float32), self.train)
+        if isinstance(TRAIN_DATA, nn_utils.DeviceTensor):
+            n_train = min(50, TRAIN_DATA.shape[0])
+            ctx.copy2d(self.train, npix, TRAIN_DATA.ptr, npix, n_train, npix)
+        else:
+            n_train = min(50, len(TRAIN_DATA))                                      # train.lua:288 (which indexes past a shorter load)
+            ctx.upload(np.ascontiguousarray(TRAIN_DATA[:n_train], np.float32), self.train)
         ctx.upload(sanity_image(self.dims, OPT.seed, epoch), self.ranked + 4 * npix * (VIS_ROWS - 1))      # :299, in place in the copy
         with observing(self.game.gg, self.game.dg):                                 # :270-271 ... :317-318
             forward_batched(ctx, self.game.gg, self.noise, VIS_ROWS, OPT.noiseDim, B, self.images, npix)       # :291

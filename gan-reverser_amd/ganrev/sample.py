@@ -93,7 +93,7 @@ def main(argv=None):
     dims = image_dims(opt)
     ctx = L.default_context()
     G, D = loadModels(opt)
-    DATASET = scripts.open_dataset(opt, opt.colorSpace, opt.height, opt.width)      # sample.lua:46-50
+    DATASET = scripts.open_dataset(opt, opt.colorSpace, opt.height, opt.width, ctx)      # sample.lua:46-50; --cacheDataset: both loads below come from the cache
     data = table = None
     if opt.neighbours:
         if DATASET is not None:

@@ -43,6 +43,10 @@ def load_checkpoint(path):
 def add_dataset_options(p):
     p.add_argument("--dataset", default="NONE", help="directory of image files to load with ganrev.dataset (dataset.lua); NONE: --data or synthetic images")
     p.add_argument("--fileExtension", default="jpg", help="only files whose name ends in this are loaded (the reference hard-codes jpg)")
+    # True when given, None (not False) when absent, like --progress: a run without it saves the opt table it saved before the option existed
+    p.add_argument("--cacheDataset", action="store_true", default=None,
+                   help="decode every file of --dataset once and keep the bytes on the GPU: each draw is then one launch, same images bit for bit "
+                        "(needs --dataset and the device-resident loop; apply_r and train_r configure the dataset and never read it: they accept and ignore this)")
 
 
 def add_progress_option(p):
@@ -59,10 +63,17 @@ def refuse_progress_in_compat(OPT):
         raise L.GanrevError("--progress needs the device-resident loop: it cannot be combined with --compat")
 
 
-def open_dataset(OPT, colorSpace, height, width):
+def open_dataset(OPT, colorSpace, height, width, ctx=None, reads=True):
     """The five DATASET.set* calls of a script's head when --dataset names a directory -> the configured ganrev.dataset module, else None.
     The reference asserts OPT.dataset ~= "NONE"; here NONE keeps --data / the synthetic images.  Giving both --data and --dataset is an error.
-    The permutations of loadRandomImages are seeded from --seed."""
+    The permutations of loadRandomImages are seeded from --seed.  --cacheDataset: DATASET.cache(ctx) before the first draw (an error without
+    --dataset, and with --compat, whose host loops have no use for a device table); reads=False (apply_r, train_r: the dataset is
+    configured, never read) ignores it."""
+    want_cache = bool(getattr(OPT, "cacheDataset", None)) and reads
+    if want_cache and OPT.dataset == "NONE":
+        raise L.GanrevError("--cacheDataset needs --dataset: there are no files to keep")
+    if want_cache and getattr(OPT, "compat", False):
+        raise L.GanrevError("--cacheDataset needs the device-resident loop: it cannot be combined with --compat")
     if OPT.dataset == "NONE":
         return None
     if getattr(OPT, "data", ""):
@@ -74,13 +85,17 @@ def open_dataset(OPT, colorSpace, height, width):
     DATASET.setWidth(width)
     DATASET.setDirs([OPT.dataset])
     DATASET.setSeed(getattr(OPT, "seed", 0))
+    if want_cache:
+        DATASET.cache(ctx, quiet=getattr(OPT, "quiet", True))
     return DATASET
 
 
 def load_random_images(DATASET, count):
-    """DATASET.loadRandomImages(count) as the host array the training loops take (train.lua:216, pretrain_g.lua:118,
-    pretrain_with_previous_net.lua:171); a folder with fewer files than the loop will index is an error here, not an index past the end there"""
-    res = DATASET.loadRandomImages(count, device=False)
+    """DATASET.loadRandomImages(count) as the training loops take it (train.lua:216, pretrain_g.lua:118, pretrain_with_previous_net.lua:171): a
+    host array, or with a live cache the device table (nn_utils.DeviceTensor) where the one launch left it - the caller frees it.  A folder
+    with fewer files than the loop will index is an error here, not an index past the end there"""
+    res = DATASET.loadRandomImages(count, device=DATASET.cached())
     if res.size() < count:
+        res.free()
         raise L.GanrevError(f"--dataset holds {res.size()} matching files, the loop needs {count}")
     return res.images

@@ -4,7 +4,7 @@ batchSize / 2 * D_iterations training images (train.lua:214-216), play adversari
 Without --network, G starts from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (ganrev.pretrain_g) when that file exists and
 --nopretraining is not given (train.lua:148-161).
 
-    python -m ganrev.train --epochs 5 --N_epoch 30 --batchSize 32 --save logs [--dataset DIR | --data images.npy] [--compat]
+    python -m ganrev.train --epochs 5 --N_epoch 30 --batchSize 32 --save logs [--dataset DIR [--cacheDataset] | --data images.npy] [--compat]
 
 Same option names and defaults as train.lua:12-60 for what is mirrored.  Normalisation and the `display` UI are out of scope (SURVEY.md
 section 2).  --progress writes visualizeProgress's pictures (train.lua:268-319) per epoch -
@@ -130,7 +130,7 @@ def main(argv=None):
                                 "D_clamp", "G_clamp", "D_optmethod", "G_optmethod", "seed", "D_sgd_lr", "G_sgd_lr", "D_sgd_momentum", "G_sgd_momentum")})
     env.EPOCH = epoch0
     data = np.load(OPT.data).astype(np.float32) if OPT.data else None
-    DATASET = scripts.open_dataset(OPT, OPT.colorSpace, OPT.height, OPT.width)      # train.lua:81-85
+    DATASET = scripts.open_dataset(OPT, OPT.colorSpace, OPT.height, OPT.width, ctx)      # train.lua:81-85; --cacheDataset: every file decoded here, once
     game = None if OPT.compat else adversarial.DeviceGame(env)       # every method of train.lua:37-38 has its fused device update
     pictures = None
     if OPT.progress:                                                  # train.lua:116,203-204: VIS_NOISE_INPUTS of the checkpoint, or fresh
@@ -149,9 +149,12 @@ def main(argv=None):
     # batches and indexes past the loaded examples - here the 100 batches get their images
     nbLoad = (N_epoch * OPT.batchSize // 2) * D_it
     cursor, last, t0, images = (epoch0 - 1) * nbLoad, None, time.perf_counter(), 0
+    TRAIN_DATA = None
     for _ in range(OPT.epochs):
+        if isinstance(TRAIN_DATA, nn_utils.DeviceTensor):
+            TRAIN_DATA.free()                                         # the last epoch's draw from the cache
         if DATASET is not None:
-            TRAIN_DATA = scripts.load_random_images(DATASET, nbLoad)   # train.lua:216; already in --colorSpace (dataset.lua:153)
+            TRAIN_DATA = scripts.load_random_images(DATASET, nbLoad)   # train.lua:216; already in --colorSpace (dataset.lua:153); --cacheDataset: a device table
         elif data is not None:
             idx = (cursor + np.arange(nbLoad)) % len(data); cursor += nbLoad
             TRAIN_DATA = data[idx]
@@ -169,7 +172,8 @@ def main(argv=None):
             per = (OPT.batchSize // 2) * D_it                         # real images one batch consumes: batchSize/2 per D iteration (adversarial.lua:139-149)
             for b in range(N_epoch):
                 want = b == N_epoch - 1
-                res = game.batch(TRAIN_DATA[b * per:(b + 1) * per], want_loss=want)
+                on_device = isinstance(TRAIN_DATA, nn_utils.DeviceTensor)
+                res = game.batch(TRAIN_DATA.rows(b * per, (b + 1) * per) if on_device else TRAIN_DATA[b * per:(b + 1) * per], want_loss=want)
                 if want:
                     last = res
         images += N_epoch * OPT.batchSize * G_it
@@ -184,6 +188,8 @@ def main(argv=None):
         env.EPOCH += 1
     if game is not None:
         game.sync_to_host()
+    if isinstance(TRAIN_DATA, nn_utils.DeviceTensor):
+        TRAIN_DATA.free()
     path = save(OPT, env, env.EPOCH - 1, OPT.quiet, pictures)         # train.lua:209-211 "Last epoch reached."
     if pictures is not None:
         pictures.close()

@@ -96,7 +96,7 @@ def main(argv=None):
         else:
             synth.init_params(MODEL_G, OPT.seed)
     MODEL_G.evaluate()                                                   # train_r.lua:70
-    scripts.open_dataset(OPT, "y" if OPT.channels == 1 else "rgb", OPT.height, OPT.width)      # train_r.lua:93-97
+    scripts.open_dataset(OPT, "y" if OPT.channels == 1 else "rgb", OPT.height, OPT.width, reads=False)      # train_r.lua:93-97
     if OPT.continue_:                                                    # train_r.lua:101-104  MODEL_R = torch.load(OPT.continue).R
         if OPT.continue_.endswith((".net", ".t7")):
             from . import t7

@@ -66,6 +66,12 @@ int gr_image_scale_dev(gr_ctx*, const float* in_dev, int64_t n, int planes, int 
 int gr_image_scale_host(gr_ctx*, const float* in_host, int64_t n, int planes, int sh, int sw, int dh, int dw, float* out_host);
 int gr_dataset_images_dev(gr_ctx*, const uint8_t* in_dev, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize,
                           float* out_dev);     /* decoded bytes -> / 255 -> image.scale -> rgbToColorSpace [-> normalize]; dataset.lua:149-153 */
+/* a dataset's decoded files kept on the device: append each file once, then one launch per loadImages / loadRandomImages (same bits) */
+int gr_dataset_cache_create(gr_ctx*, int64_t chunk_bytes, void** cache_out);  int gr_dataset_cache_destroy(void* cache);
+int gr_dataset_cache_append(void* cache, const uint8_t* bytes_host, int sh, int sw, int sc);
+int gr_dataset_cache_size(void* cache, int64_t* n_images, int64_t* bytes);
+int gr_dataset_cache_image(void* cache, int64_t i, int* sh, int* sw, int* sc);
+int gr_dataset_cache_load_dev(void* cache, const int64_t* indices_host, int64_t n, int dh, int dw, int to_space, int normalize, float* out_dev);
 int gr_l2_distance_rows_dev(gr_ctx*, const float* a_dev, const float* b_dev, int64_t n, int64_t d, double* out_host);
 int gr_image_grid_dev(gr_ctx*, const float* const* src_dev, const int64_t* n_rows, int slots, int channels, int h, int w, int from_space,
                       const int64_t* rows_host, int n_tiles, int nrow, int padding, int margin, const float* bg_host, const uint8_t* inset_host,

@@ -511,6 +511,33 @@ int gr_image_scale_host(gr_ctx* ctx, const float* in_host, int64_t n, int planes
 int gr_dataset_images_dev(gr_ctx* ctx, const uint8_t* in_dev, int64_t n, int sh, int sw, int sc, int dh, int dw, int to_space, int normalize,
                           float* out_dev);
 
+/* ---- a dataset's decoded files, kept on the device (csrc/ops.hip, csrc/dataset.hip; ganrev.dataset.cache) ----
+ *
+ * A run draws from the same files epoch after epoch.  The cache holds each file's bytes as the file stores them - uint8, interleaved HWC,
+ * at source size, sc = 1, 3 or 4 channels - and gr_dataset_cache_load_dev turns any list of them into the fp32 table in ONE launch: row k of
+ * out_dev [n x planes(to_space) x dh x dw] is, bit for bit, what gr_dataset_images_dev writes for image indices_host[k] alone (the
+ * arithmetic stated above: / 255, the two scale passes, rows first, rgbToColorSpace, the optional normalise step).  Source size and channel
+ * count vary from image to image inside the launch, an image may be listed several times, and the order is free.
+ *
+ * The handle (`cache`, an opaque pointer) belongs to one context and follows the rule of a gr_net: gr_dataset_cache_destroy waits for the
+ * context's stream and frees what the cache holds; it is called before gr_shutdown of that context, never after.
+ * gr_dataset_cache_create: chunk_bytes <= 0 takes the default (64 MB).  The arena grows by chunks of that size, one device allocation each;
+ * bytes that were uploaded are never copied again, and an image larger than a chunk gets a chunk of its own.
+ * gr_dataset_cache_append uploads one image (the caller's array is its own again on return); its number is the append order, from 0.  A failed
+ * device allocation returns GR_ERR_HIP and the cache stays usable with the images it holds.
+ * gr_dataset_cache_size: the number of images and their decoded bytes.  gr_dataset_cache_image: the record of image i (any out pointer may be null).
+ * gr_dataset_cache_load_dev is enqueued on the context's stream like every operator: it uploads the index list and launches; it waits for the
+ * stream only in the first load after an append, which brings the device copy of the records up to date.
+ *
+ * GR_ERR_INVALID with a gr_last_error message, no launch and `out` untouched for: a null pointer; n < 1; an index outside [0, n_images);
+ * dh or dw < 1; a side above 32768 (source or target); sc outside {1, 3, 4}; a bad to_space; more than 2^40 elements in the table. ---- */
+int gr_dataset_cache_create(gr_ctx* ctx, int64_t chunk_bytes, void** cache_out);
+int gr_dataset_cache_destroy(void* cache);
+int gr_dataset_cache_append(void* cache, const uint8_t* bytes_host, int sh, int sw, int sc);
+int gr_dataset_cache_size(void* cache, int64_t* n_images, int64_t* bytes);
+int gr_dataset_cache_image(void* cache, int64_t i, int* sh, int* sw, int* sc);
+int gr_dataset_cache_load_dev(void* cache, const int64_t* indices_host, int64_t n, int dh, int dw, int to_space, int normalize, float* out_dev);
+
 /* ---- single-kernel entry points used by bench.py's roofline leg and by kernel-level parity tests ---- */
 int gr_conv3_forward_dev(gr_ctx* ctx, const float* in_dev, const float* w_dev, const float* bias_dev, float* out_dev,
                          int batch, int cin, int cout, int h, int w, int upsample2);
