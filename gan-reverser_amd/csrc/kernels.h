@@ -510,7 +510,8 @@ size_t cosine_topk_workspace_bytes(long N, int d, int Q, int k);
 int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_dev, int Q, int k,
                        long* idx_out, float* score_out, int accf, void* workspace, hipStream_t s, unsigned* status_dev = nullptr, int unfiltered = 0,
                        const long* query_rows_host = nullptr, unsigned* arrival_counter = nullptr,    // arrival_counter: SEARCH_STATE_WORDS zeroed device words the caller owns (word 0: the sample launch's arrival counter, words 16..: its histogram bins; both are left at 0 again)
-                       unsigned* done_words = nullptr, unsigned seq = 0);   // small path: done_words[q] (host-visible) receives seq once needle q's results are written; the call then returns 2
+                       unsigned* done_words = nullptr, unsigned seq = 0,    // small path: done_words[q] (host-visible) receives seq once needle q's results are written; the call then returns 2
+                       const float* queries_dev = nullptr);   // non-null: needle q is row q of this device array [Q][d] (a vector from outside the table) and both query_rows are unused
 constexpr int SEARCH_STATE_WORDS = 16 + 8 * 1024;
 bool cosine_topk_small_path(long N, int d, int Q, int k);     // the filtered search takes the fp32-filter path (query rows by value, no device copy of them needed)
 

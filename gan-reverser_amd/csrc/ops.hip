@@ -297,11 +297,12 @@ extern "C" int gr_dataset_cache_load_dev(void* cache, const int64_t* indices, in
 }
 
 // ------------------------------------------------------------------ search
-extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
-                                  int64_t* idx_out, float* score_out, int accf) {
-  if (!c || !emb || !qrows || !idx_out || N <= 0 || d <= 0 || Q <= 0 || k <= 0) return GR_ERR_INVALID;
+// The search behind both needle sources: rows of the table (qrows, host) or vectors of their own (queries_dev [Q][d], device); exactly one is given
+static int cosine_topk_run(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, const float* queries_dev, int Q, int k,
+                           int64_t* idx_out, float* score_out, int accf) {
+  if (!c || !emb || (!qrows && !queries_dev) || !idx_out || N <= 0 || d <= 0 || Q <= 0 || k <= 0) return GR_ERR_INVALID;
   if (k > N) k = (int)N;
-  for (int q = 0; q < Q; ++q) if (qrows[q] < 0 || qrows[q] >= N) return fail(c, GR_ERR_INVALID, "query row %lld out of range", (long long)qrows[q]);
+  if (qrows) for (int q = 0; q < Q; ++q) if (qrows[q] < 0 || qrows[q] >= N) return fail(c, GR_ERR_INVALID, "query row %lld out of range", (long long)qrows[q]);
   if (k > 1024) return fail(c, GR_ERR_UNSUPPORTED, "k > 1024");
   Staging s(c);
   s.reserve<char>(cosine_topk_workspace_bytes(N, d, Q, k));          // launch_cosine_topk takes c->ws itself: the first region
@@ -336,7 +337,7 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
       HIPCHK(c, hipMemsetAsync(c->search_state, 0, sizeof(unsigned) * SEARCH_STATE_WORDS, c->stream));
     }
     const int lr = launch_cosine_topk(emb, N, d, d_q, Q, k, p_idx, p_sc, accf, c->ws, c->stream, p_status, 0, qrows, c->search_state,
-                                      static_cast<unsigned*>(done_dev), seq);
+                                      static_cast<unsigned*>(done_dev), seq, queries_dev);
     if (lr < 0) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
     LAUNCHCHK(c);
     // The selection kernel publishes one completion word per needle behind its results (system-scope release): poll them instead of
@@ -365,10 +366,10 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
     }
     c->search_reruns++;       // a candidate list overflowed (adversarial row order): the unfiltered search below decides
   }
-  HIPCHK(c, hipMemcpyAsync(d_q, qrows, sizeof(long) * Q, hipMemcpyHostToDevice, c->stream));
+  if (qrows) HIPCHK(c, hipMemcpyAsync(d_q, qrows, sizeof(long) * Q, hipMemcpyHostToDevice, c->stream));
   const bool small_failed = cosine_topk_small_path(N, d, Q, k);
   for (int unfiltered = small_failed ? 1 : 0; unfiltered < 2; ++unfiltered) {
-    if (launch_cosine_topk(emb, N, d, d_q, Q, k, d_idx, d_sc, accf, c->ws, c->stream, d_status, unfiltered, qrows)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
+    if (launch_cosine_topk(emb, N, d, d_q, Q, k, d_idx, d_sc, accf, c->ws, c->stream, d_status, unfiltered, qrows, nullptr, nullptr, 0, queries_dev)) return fail(c, GR_ERR_UNSUPPORTED, "cosine_topk: unsupported size");
     LAUNCHCHK(c);
     HIPCHK(c, hipMemcpyAsync(c->pin, d_idx, res_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -383,6 +384,16 @@ extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d,
   }
   return GR_OK;
 }
+extern "C" int gr_cosine_topk_dev(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
+                                  int64_t* idx_out, float* score_out, int accf) {
+  if (!qrows) return GR_ERR_INVALID;
+  return cosine_topk_run(c, emb, N, d, qrows, nullptr, Q, k, idx_out, score_out, accf);
+}
+extern "C" int gr_cosine_topk_queries_dev(gr_ctx* c, const float* emb, int64_t N, int d, const float* queries, int Q, int k,
+                                          int64_t* idx_out, float* score_out, int accf) {
+  if (!queries) return GR_ERR_INVALID;
+  return cosine_topk_run(c, emb, N, d, nullptr, queries, Q, k, idx_out, score_out, accf);
+}
 extern "C" int gr_cosine_topk_host(gr_ctx* c, const float* emb, int64_t N, int d, const int64_t* qrows, int Q, int k,
                                    int64_t* idx_out, float* score_out, int accf) {
   if (!c || !emb || N <= 0 || d <= 0) return GR_ERR_INVALID;
@@ -391,6 +402,17 @@ extern "C" int gr_cosine_topk_host(gr_ctx* c, const float* emb, int64_t N, int d
   HIPCHK(c, tmp.dev(&dev, sizeof(float) * (size_t)N * d));
   if (hipMemcpyAsync(dev, emb, sizeof(float) * (size_t)N * d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, GR_ERR_HIP, "upload failed");
   return gr_cosine_topk_dev(c, dev, N, d, qrows, Q, k, idx_out, score_out, accf);
+}
+extern "C" int gr_cosine_topk_queries_host(gr_ctx* c, const float* emb, int64_t N, int d, const float* queries, int Q, int k,
+                                           int64_t* idx_out, float* score_out, int accf) {
+  if (!c || !emb || !queries || !idx_out || N <= 0 || d <= 0 || Q <= 0 || k <= 0) return GR_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  DevMem tmp(c->stream); float* dev = nullptr; float* qdev = nullptr;
+  HIPCHK(c, tmp.dev(&dev, sizeof(float) * (size_t)N * d));
+  HIPCHK(c, tmp.dev(&qdev, sizeof(float) * (size_t)Q * d));
+  if (hipMemcpyAsync(dev, emb, sizeof(float) * (size_t)N * d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, GR_ERR_HIP, "upload failed");
+  if (hipMemcpyAsync(qdev, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, GR_ERR_HIP, "upload failed");
+  return gr_cosine_topk_queries_dev(c, dev, N, d, qdev, Q, k, idx_out, score_out, accf);
 }
 extern "C" int gr_cosine_similarity_host(gr_ctx* c, const float* a, const float* b, int d, float* out) {
   if (!c || !a || !b || !out || d <= 0) return GR_ERR_INVALID;

@@ -35,7 +35,8 @@ constexpr long FILTER_MIN_ROWS = 1 << 17;   // below this the unfiltered path is
 constexpr int SAMPLE_ROWS = 16384;          // rows scored ahead for the filter bound
 constexpr int SLOT = 32;                    // candidate keys a workgroup (ROWS rows) may keep per needle: expected ROWS * k / SAMPLE_ROWS = 0.8
 
-template <bool ACCF>
+// EXT: needle q is row q of an array of its own (emb = queries [Q][d], rows unused) instead of row rows[q] of the table: same sums, same order
+template <bool ACCF, bool EXT = false>
 __global__ void needle_prep_kernel(const float* __restrict__ emb, int d, const long* __restrict__ rows, int Q,
                                    float* __restrict__ needles, float* __restrict__ w22, unsigned* __restrict__ counts,
                                    unsigned* __restrict__ status) {
@@ -43,7 +44,7 @@ __global__ void needle_prep_kernel(const float* __restrict__ emb, int d, const l
   if (q == 0 && status) *status = 0u;
   if (q >= Q) return;
   if (counts) counts[q] = 0u;
-  const float* a = emb + rows[q] * (long)d;
+  const float* a = emb + (EXT ? (long)q : rows[q]) * (long)d;
   typename std::conditional<ACCF, float, double>::type s = 0;
   for (int i = 0; i < d; ++i) { const float v = a[i]; needles[(long)q * d + i] = v; s += v * v; }
   float w = (float)s;
@@ -339,15 +340,23 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_row_shr(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
 }
-// needles as the MFMA kernel stages them: bf16 rows [Qpad64][KS] (zero columns past d, zero rows past Q), sqrt(w22), tau = +inf past Q
+// a needle the fp16 candidate pass can carry within the proven bound: its squared norm 1 / w22 - 1e-12 lies in [GR_BNRM_MIN, GR_BNRM_MAX] (no element
+// overflows fp16 then: |a_i| <= |a|)
+__device__ __forceinline__ bool batched_needle_ok(float w22q) { const float n2 = 1.f / w22q; return n2 >= GR_BNRM_MIN && n2 <= GR_BNRM_MAX; }
+// needles as the MFMA kernel stages them: bf16 rows [Qpad64][KS] (zero columns past d, zero rows past Q), sqrt(w22), tau = +inf past Q.
+// A needle outside the norm range raises *status HERE (needle_prep_kernel zeroed it earlier on the stream): the call reruns unbatched whatever the passes
+// below make of it.  A row needle outside the range is also a table row, which the rows' guard in cos_mfma_kernel catches; a needle from outside the
+// table has no such cover, and one with elements beyond fp16 (inf in the staged image, inf - inf = NaN dot products that pass no threshold, not even
+// -inf) would otherwise leave EMPTY lists and status 0.
 __global__ void needles_bf16_kernel(const float* __restrict__ needles, const float* __restrict__ w22, int Q, int Qpad, int d, int KS,
-                                    unsigned short* __restrict__ nb16, float* __restrict__ sw22s, float* __restrict__ tau) {
+                                    unsigned short* __restrict__ nb16, float* __restrict__ sw22s, float* __restrict__ tau, unsigned* __restrict__ status) {
   const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (e < (long)Qpad * KS) {
     const int q = (int)(e / KS), c = (int)(e - (long)q * KS);
     nb16[e] = to_bf16((q < Q && c < d) ? needles[(long)q * d + c] : 0.f);
   }
   if (e < Qpad) { sw22s[e] = e < Q ? sqrtf(w22[e]) : 0.f; if (e >= Q) tau[e] = INFINITY; }
+  if (e < Q && status && !batched_needle_ok(w22[e])) *status = 1u;
 }
 
 // MODE 0: rows are i * stride (the sample), scores out[q][i].  MODE 1: every row, candidates >= tau[q].
@@ -626,8 +635,8 @@ __device__ __forceinline__ unsigned kth_of_maxima(unsigned mine, unsigned* list,
   return r;
 }
 // tau[q] from the approximate sample scores [Q][S]
-// (a needle whose squared norm 1 / w22 - 1e-12 lies outside the fp16 pass's range gets -inf: every row passes, every list overflows, the call reruns unbatched)
-__device__ __forceinline__ bool batched_needle_ok(float w22q) { const float n2 = 1.f / w22q; return n2 >= GR_BNRM_MIN && n2 <= GR_BNRM_MAX; }
+// (a needle outside the fp16 pass's norm range - batched_needle_ok, above - gets -inf here; needles_bf16_kernel has raised the status for it already, so the
+//  call reruns unbatched whether or not its lists overflow)
 // ONE wave per needle (four needles per workgroup): the <= 256 sample maxima as orderable bit patterns, four per lane, and the exact k-th largest
 // built bit by bit from the top (res |= bit while at least k patterns are >= the trial value) - no LDS, no block barriers (round 4's 1024-thread
 // bitonic sort of the maxima took 23 us for 1024 needles; removed with the branch that could never launch it, git history)
@@ -711,7 +720,8 @@ __global__ __launch_bounds__(1024) void batched_select_kernel(const float* __res
   }
   __syncthreads();
   const unsigned m = list_n;
-  if (m > (unsigned)CHUNK) { if (tid == 0 && status) *status = 1u; return; }
+  // (fewer than k candidates: the lists cannot hold the top k - the passes above were defeated, e.g. by NaN scores - and the unbatched search decides)
+  if (m > (unsigned)CHUNK || m < (unsigned)k) { if (tid == 0 && status) *status = 1u; return; }
   // exact scores, cos_keys_kernel's arithmetic: fp32 products, sequential sums over the columns, the same w22 / w32 steps
   const float w22q = from_rows ? sh_w22 : w22[q];
   for (unsigned i = tid; i < m; i += 1024) {
@@ -798,13 +808,14 @@ static int approx_wgs(int d, int Q) {        // ONE resident round (up to 8 one-
   return 256 * per_cu;
 }
 struct ApproxArgs {
-  float* needles; float* w22;                    // [Q][d], [Q]: written by workgroup 0 of the sample launch for the selection kernel (exact: needle_prep's arithmetic)
+  const float* needles;                          // [Q][d]: the needles of a search by outside vectors (cos_approx_kernel<..., EXT>); unused by the row-index search
   unsigned* hist; unsigned* counter; float* tau;  // sample: [AQ_MAX][SBINS] histogram of the workgroups' maxima (zero between searches), arrival counter, [Q] thresholds
   unsigned* cand_idx; float* cand_sc; unsigned* counts;   // main pass: [Q][nwg][ASLOT], [Q][nwg]
   unsigned* status;
   int Q, k, accf; float eps2;
 };
-template <int D4, int NQ, int MODE>
+// EXT: the needles are rows 0 .. Q - 1 of a.needles (vectors from outside the table cannot ride in the arguments: 8 x 128 floats) instead of the table's rows qr.rows
+template <int D4, int NQ, int MODE, bool EXT = false>
 __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict__ emb, long N, long stride, SmallQ qr, ApproxArgs a) {
   constexpr int V = (D4 & 1) ? D4 : D4 + 1, d = D4 * 4;      // vectors per LDS row: odd, so that the 16 lanes of a ds_read_b128 group hit 64 distinct banks
   // NB tiles per workgroup in a ring: while one is multiplied, NB - 1 are in flight (APPROX_NB: two; three lost)
@@ -835,10 +846,12 @@ __global__ __launch_bounds__(64) void cos_approx_kernel(const float* __restrict_
 #pragma unroll
   for (int j = 0; j < NB - 1; ++j)
     if (wg + (long)j * nwg < ntiles) request(wg + (long)j * nwg, j);
-  // the needles: every workgroup gathers them itself (Q rows of d floats; rows come in the kernel arguments - no upload, no launch of their own)
+  // the needles: every workgroup gathers them itself, once, in front of the tile loop (Q rows of d floats; rows come in the kernel arguments - no upload, no
+  // launch of their own; EXT: the same Q x d floats from the caller's array)
   for (int e = lane; e < NQ * D4; e += 64) {
     const int q = e / D4, c4 = e - q * D4;
-    nd[e] = *reinterpret_cast<const float4*>(emb + qr.rows[q < Q ? q : 0] * (long)d + 4 * c4);
+    const int qq = q < Q ? q : 0;
+    nd[e] = *reinterpret_cast<const float4*>((EXT ? a.needles + (long)qq * d : emb + qr.rows[qq] * (long)d) + 4 * c4);
   }
   __syncthreads();
   float w22a[NQ];                      // approximate 1 / (|needle|^2 + 1e-12): same arithmetic in every workgroup
@@ -1023,14 +1036,14 @@ constexpr int SSEL_BINS = 2048, SSEL_MAX = 256;
 constexpr int SMALL_K_MAX = 128;      // largest k of the small path (cosine_topk_small_path)
 static_assert(SSEL_MAX / 2 >= SMALL_K_MAX, "small_select_kernel keeps up to SSEL_MAX rows past its cut: twice the small path's k");
 // NT threads (256: the small path's <= 2048 lists per needle; 512: the batched path's N / 256 lists), SLOT entries per list, FROM_ROWS: the needle is row
-// qr.rows[q] of the table and its norm is formed here (small path) / the needle and its 1 / (|a|^2 + 1e-12) come from needle_prep_kernel's arrays (batched);
+// qr.rows[q] of the table / the needle is row q of `needles` (a search by outside vectors); its 1 / (|a|^2 + 1e-12) is formed here either way;
 // lo_scale (nullable): tau[q] * lo_scale[q] is the lower edge of the candidates' scores (the batched path stores tau divided by sqrt(w22)).
 template <bool ACCF, int NT, int SLOT_, bool FROM_ROWS>
 __global__ __launch_bounds__(NT) void small_select_kernel(const float* __restrict__ emb, int d, const unsigned* __restrict__ cand_idx,
                                                          const float* __restrict__ cand_sc, const unsigned* __restrict__ counts, int nwg, int k,
                                                          long* __restrict__ idx, float* __restrict__ score, unsigned* __restrict__ status,
                                                          float margin2, SmallQ qr, const float* __restrict__ tau, unsigned* __restrict__ done, unsigned seq,
-                                                         const float* __restrict__ needles, const float* __restrict__ w22, const float* __restrict__ lo_scale) {
+                                                         const float* __restrict__ needles, const float* __restrict__ lo_scale) {
   typedef typename std::conditional<ACCF, float, double>::type acc_t;
   __shared__ unsigned hist[SSEL_BINS];
   __shared__ __attribute__((aligned(16))) unsigned long long keys[SSEL_MAX];
@@ -1051,8 +1064,7 @@ __global__ __launch_bounds__(NT) void small_select_kernel(const float* __restric
   if (tid == 0) { list_n = 0u; over = 0u; cutbin = 0u; }
   for (int c = tid; c < d; c += NT) ndl[c] = nd[c];
   __syncthreads();
-  if (!FROM_ROWS) { if (tid == NT - 1) sh_w22 = w22[q]; }
-  else if (tid == NT - 1) {                                                 // 1 / (|needle|^2 + 1e-12) in needle_prep_kernel's arithmetic, from the staged copy
+  if (tid == NT - 1) {                                                 // 1 / (|needle|^2 + 1e-12) in needle_prep_kernel's arithmetic, from the staged copy
     acc_t t = 0;                                                    // (read from global memory by this one thread it was 7 dependent rounds: ~10 us)
     for (int i = 0; i < d; ++i) { const float v = ndl[i]; t += v * v; }
     float w = (float)t;
@@ -1183,20 +1195,25 @@ bool cosine_topk_small_path(long N, int d, int Q, int k) {
   return Q >= 1 && Q <= AQ_MAX && (d & 3) == 0 && (d4 == 8 || d4 == 16 || d4 == 25 || d4 == 32) && N >= FILTER_MIN_ROWS && k <= SMALL_K_MAX &&
          (size_t)N * d * 4 < 0x7FFFF000ul;
 }
-template <int D4, int MODE>
+template <int D4, int MODE, bool EXT>
 static void launch_approx_nq(int Q, unsigned grid, hipStream_t s, const float* emb, long N, long stride, const SmallQ& qr, const ApproxArgs& a) {
-  if (Q <= 2) hipLaunchKernelGGL((cos_approx_kernel<D4, 2, MODE>), dim3(grid), dim3(64), 0, s, emb, N, stride, qr, a);
-  else if (Q <= 5) hipLaunchKernelGGL((cos_approx_kernel<D4, 5, MODE>), dim3(grid), dim3(64), 0, s, emb, N, stride, qr, a);
-  else hipLaunchKernelGGL((cos_approx_kernel<D4, 8, MODE>), dim3(grid), dim3(64), 0, s, emb, N, stride, qr, a);
+  if (Q <= 2) hipLaunchKernelGGL((cos_approx_kernel<D4, 2, MODE, EXT>), dim3(grid), dim3(64), 0, s, emb, N, stride, qr, a);
+  else if (Q <= 5) hipLaunchKernelGGL((cos_approx_kernel<D4, 5, MODE, EXT>), dim3(grid), dim3(64), 0, s, emb, N, stride, qr, a);
+  else hipLaunchKernelGGL((cos_approx_kernel<D4, 8, MODE, EXT>), dim3(grid), dim3(64), 0, s, emb, N, stride, qr, a);
+}
+template <int MODE, bool EXT>
+static void launch_approx_d4(int d4, int Q, unsigned grid, hipStream_t s, const float* emb, long N, long stride, const SmallQ& qr, const ApproxArgs& a) {
+  switch (d4) {
+    case 8: launch_approx_nq<8, MODE, EXT>(Q, grid, s, emb, N, stride, qr, a); break;
+    case 16: launch_approx_nq<16, MODE, EXT>(Q, grid, s, emb, N, stride, qr, a); break;
+    case 25: launch_approx_nq<25, MODE, EXT>(Q, grid, s, emb, N, stride, qr, a); break;
+    default: launch_approx_nq<32, MODE, EXT>(Q, grid, s, emb, N, stride, qr, a); break;
+  }
 }
 template <int MODE>
 static void launch_approx(int d4, int Q, unsigned grid, hipStream_t s, const float* emb, long N, long stride, const SmallQ& qr, const ApproxArgs& a) {
-  switch (d4) {
-    case 8: launch_approx_nq<8, MODE>(Q, grid, s, emb, N, stride, qr, a); break;
-    case 16: launch_approx_nq<16, MODE>(Q, grid, s, emb, N, stride, qr, a); break;
-    case 25: launch_approx_nq<25, MODE>(Q, grid, s, emb, N, stride, qr, a); break;
-    default: launch_approx_nq<32, MODE>(Q, grid, s, emb, N, stride, qr, a); break;
-  }
+  if (a.needles) launch_approx_d4<MODE, true>(d4, Q, grid, s, emb, N, stride, qr, a);
+  else launch_approx_d4<MODE, false>(d4, Q, grid, s, emb, N, stride, qr, a);
 }
 
 static long chunks_of(long n) { return (n + CHUNK - 1) / CHUNK; }
@@ -1243,7 +1260,7 @@ static void launch_keys(bool accf, int mode, int nq, unsigned nb, hipStream_t s,
 // status_dev (nullable): receives 0, or 1 when the filtered path dropped candidates (rerun with unfiltered = 1)
 int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_dev, int Q, int k,
                        long* idx_out, float* score_out, int accf, void* workspace, hipStream_t s, unsigned* status_dev, int unfiltered,
-                       const long* query_rows_host, unsigned* arrival_counter, unsigned* done_words, unsigned seq) {
+                       const long* query_rows_host, unsigned* arrival_counter, unsigned* done_words, unsigned seq, const float* queries_dev) {
   if (k > 1024 || k < 1 || k > N || N >= 0xFFFFFFFFl || d < 1 || d > 4096 * 4) return -1;
   // workspace carve: needles [Q][d] | w22 [Q] | counts [Q] | keys A | keys B | keys C
   char* w = reinterpret_cast<char*>(workspace);
@@ -1256,7 +1273,8 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
   unsigned long long* keysB = keysA + (size_t)Q * N;
   unsigned long long* keysC = keysB + (size_t)Q * n1;
   const bool filter = !unfiltered && status_dev && N >= FILTER_MIN_ROWS && k * 8 <= SAMPLE_ROWS && k <= CHUNK / 2;      // (entries + sample + bounds + counts fit the N keys of region A: SLOT * 8 / ROWS + ... < 8 bytes per row)
-  if (filter && query_rows_host && arrival_counter && cosine_topk_small_path(N, d, Q, k)) {
+  // (outside needles are fetched as float4s there: an array that is not 16-byte aligned takes the filter path below)
+  if (filter && (queries_dev ? ((uintptr_t)queries_dev & 15) == 0 : query_rows_host != nullptr) && arrival_counter && cosine_topk_small_path(N, d, Q, k)) {
     // keys A = maxima [Q][256] | tau [8] | arrival counter | candidate rows [Q][wgs][ASLOT] | scores | counts [Q][wgs]
     const long S = SAMPLE_ROWS, stride = N / S;
     const unsigned swg = (unsigned)(S / 64);
@@ -1265,9 +1283,9 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
     const int awgs = approx_wgs(d, Q);
     unsigned* cidx = pad_ + 8; float* csc = reinterpret_cast<float*>(cidx + (size_t)Q * awgs * ASLOT);
     unsigned* wcnt = reinterpret_cast<unsigned*>(csc + (size_t)Q * awgs * ASLOT);
-    SmallQ qr{}; for (int q = 0; q < AQ_MAX; ++q) qr.rows[q] = query_rows_host[q < Q ? q : 0];
+    SmallQ qr{}; if (!queries_dev) for (int q = 0; q < AQ_MAX; ++q) qr.rows[q] = query_rows_host[q < Q ? q : 0];
     ApproxArgs a{};
-    a.needles = needles; a.w22 = w22; a.hist = hist; a.counter = counter; a.tau = tau; a.cand_idx = cidx; a.cand_sc = csc; a.counts = wcnt;
+    a.needles = queries_dev; a.hist = hist; a.counter = counter; a.tau = tau; a.cand_idx = cidx; a.cand_sc = csc; a.counts = wcnt;
     a.status = status_dev; a.Q = Q; a.k = k; a.accf = accf; a.eps2 = 2.f * (float)(2 * d + 16) * 5.9604645e-8f;
     {
       KtScope kt("cos_approx_kernel (sample + bound)", 0.0, 4.0 * S * d, s);
@@ -1278,10 +1296,18 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
       launch_approx<1>(d / 4, Q, (unsigned)awgs, s, emb, N, 1L, qr, a);
     }
     KtScope kt("small_select_kernel", 0.0, 0.0, s);
-    if (accf) hipLaunchKernelGGL((small_select_kernel<true, 256, ASLOT, true>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-    else hipLaunchKernelGGL((small_select_kernel<false, 256, ASLOT, true>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+    if (queries_dev) {      // outside needles: read from the caller's array, their norms formed by the selection kernel as for rows (no launch of their own)
+      if (accf) hipLaunchKernelGGL((small_select_kernel<true, 256, ASLOT, false>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, queries_dev, (const float*)nullptr);
+      else hipLaunchKernelGGL((small_select_kernel<false, 256, ASLOT, false>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, queries_dev, (const float*)nullptr);
+    } else
+    if (accf) hipLaunchKernelGGL((small_select_kernel<true, 256, ASLOT, true>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, (const float*)nullptr, (const float*)nullptr);
+    else hipLaunchKernelGGL((small_select_kernel<false, 256, ASLOT, true>), dim3(Q), dim3(256), 0, s, emb, d, cidx, csc, wcnt, awgs, k, idx_out, score_out, status_dev, a.eps2, qr, tau, done_words, seq, (const float*)nullptr, (const float*)nullptr);
     return done_words ? 2 : 0;        // 2: the needles' completion words will carry `seq`
   }
+  if (queries_dev) {
+    if (accf) hipLaunchKernelGGL((needle_prep_kernel<true, true>), dim3((Q + 63) / 64), dim3(64), 0, s, queries_dev, d, (const long*)nullptr, Q, needles, w22, counts, status_dev);
+    else hipLaunchKernelGGL((needle_prep_kernel<false, true>), dim3((Q + 63) / 64), dim3(64), 0, s, queries_dev, d, (const long*)nullptr, Q, needles, w22, counts, status_dev);
+  } else
   if (accf) hipLaunchKernelGGL(needle_prep_kernel<true>, dim3((Q + 63) / 64), dim3(64), 0, s, emb, d, query_rows_dev, Q, needles, w22, counts, status_dev);
   else hipLaunchKernelGGL(needle_prep_kernel<false>, dim3((Q + 63) / 64), dim3(64), 0, s, emb, d, query_rows_dev, Q, needles, w22, counts, status_dev);
   if (filter && Q >= BATCH_MIN_Q && Q <= BQ_MAX && d <= BD_MAX && k <= 128 && N >= 2 * BSAMPLE_ROWS) {      // (k distinct workgroup maxima must exist: 256 workgroups)
@@ -1300,7 +1326,7 @@ int launch_cosine_topk(const float* emb, long N, int d, const long* query_rows_d
     constexpr int QCAP_MAX = 256, QCAP_MIN = 32;
     int qcap = (int)(((size_t)80 * 1024 - lds0) / (4 * 8)); qcap = qcap > QCAP_MAX ? QCAP_MAX : (qcap < QCAP_MIN ? 0 : qcap & ~31);
     const size_t lds = lds0 + (size_t)4 * 8 * qcap;
-    hipLaunchKernelGGL(needles_bf16_kernel, dim3((unsigned)(((long)Qpad * KS + 255) / 256)), dim3(256), 0, s, needles, w22, Q, Qpad, d, KS, nb16, sw22s, tau);
+    hipLaunchKernelGGL(needles_bf16_kernel, dim3((unsigned)(((long)Qpad * KS + 255) / 256)), dim3(256), 0, s, needles, w22, Q, Qpad, d, KS, nb16, sw22s, tau, status_dev);
 #define GR_MFMA(MODE_, grid_, gy_, N_, stride_, tau_, out_, ci_, cs_, wc_)                                                                  \
     do {                                                                                                                              \
       switch (NK) {                                                                                                                   \

@@ -174,6 +174,8 @@ _SIGS = {
     "gr_kernel_times": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "gr_cosine_topk_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gr_cosine_topk_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "gr_cosine_topk_queries_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "gr_cosine_topk_queries_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gr_cosine_similarity_host": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_float)]),
     "gr_l2_distance_rows_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
     "gr_l2_distance_rows_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
@@ -429,6 +431,34 @@ class Context:
         else:
             rc = self.lib.gr_cosine_topk_dev(self.h, _ptr(emb_dev), n, d, _ptr(q), q.size, k, _ptr(idx), _ptr(sc), int(accumulate_in_float))
         self.check(rc, "gr_cosine_topk")
+        return idx, sc
+
+    def cosine_topk_queries(self, emb, queries, k, accumulate_in_float=False, emb_dev=None, n=None, d=None, queries_dev=None, q=None):
+        """search by example: cosine_topk with needle i = row i of `queries` [q x d], vectors that need not be rows of the table; every row of
+        the table is scored -> (idx int64 [q, k], scores float32 [q, k]).  emb_dev (with n, d): the table is in device memory; queries_dev (with
+        q): so are the needles.  Host needles against a device table are uploaded once; a host table takes host needles."""
+        if emb_dev is None:
+            emb = f32(emb)
+            n, d = emb.shape
+        n, d = int(n), int(d)
+        if queries_dev is None:
+            queries = f32(queries).reshape(-1, d)
+            q = queries.shape[0]
+        elif emb_dev is None:
+            raise GanrevError("cosine_topk_queries: device needles need a device table (emb_dev)")
+        q, k = int(q), min(int(k), n)
+        idx = np.empty((q, max(k, 0)), dtype=np.int64)
+        sc = np.empty((q, max(k, 0)), dtype=np.float32)
+        if emb_dev is None:
+            rc = self.lib.gr_cosine_topk_queries_host(self.h, _ptr(emb), n, d, _ptr(queries), q, k, _ptr(idx), _ptr(sc), int(accumulate_in_float))
+        else:
+            qdev = queries_dev if queries_dev is not None else (self.upload(queries) if q > 0 else None)
+            try:
+                rc = self.lib.gr_cosine_topk_queries_dev(self.h, _ptr(emb_dev), n, d, _ptr(qdev), q, k, _ptr(idx), _ptr(sc), int(accumulate_in_float))
+            finally:
+                if queries_dev is None and qdev is not None:
+                    self.free(qdev)
+        self.check(rc, "gr_cosine_topk_queries")
         return idx, sc
 
     def cosine_similarity(self, a, b):

@@ -71,6 +71,43 @@ def createSimilaritySearchDev(nbSimilarNeedles, nbShowMax, attributes, images=No
     return by_attr, by_pix
 
 
+def embedImagesDev(models_r, images, batchSize=512):
+    """apply_r.lua:152-153 over an image table that is already on the GPU (`images` a DeviceTensor [N x C x H x W]: a --dataset's files, any
+    table that did not come from G): attributes_k = R_k:forward(images) in chunks of batchSize, in evaluate() mode, where embed_dev leaves
+    them.  -> one DeviceTensor [N x nd_k] per model."""
+    ctx = images.ctx
+    outs = []
+    for m in models_r:
+        m.evaluate()
+        net = m.device_net(images.shape[1:])
+        if ctx.conv_mode() == "f16x3":
+            net.range_guard_scan()        # the *_dev calls are not range-guarded (include/ganrev.h): one synchronous scan per net, as in embed_dev
+        outs.append(forwardBatchedDev(m, images, batchSize))
+    return outs
+
+
+def searchByExample(nbShowMax, attributes, needle_attributes, images=None, needle_images=None):
+    """Search by example, the counterpart of createSimilaritySearchDev for needles that are not rows of the corpus: every row of
+    `needle_attributes` [Q x nd] (R over some other images - a photo) against the corpus table `attributes` [N x nd], and - with both image
+    tables - every needle image against the corpus images pixel-wise.  All four are DeviceTensors; nothing but the index lists leaves the
+    GPU (gr_cosine_topk_queries_dev).  -> (idx_by_attributes, idx_by_pixels or None): per needle the min(nbShowMax, N) most similar corpus
+    rows, best first, ties by ascending index; there is no self hit."""
+    N, Q = attributes.shape[0], needle_attributes.shape[0]
+    n = min(nbShowMax, N)
+    ctx = attributes.ctx
+    d = attributes.size // N
+    if needle_attributes.size != Q * d:
+        raise L.GanrevError(f"searchByExample: needles of {needle_attributes.size // max(Q, 1)} attributes against a table of {d}")
+    by_attr, _ = ctx.cosine_topk_queries(None, None, n, emb_dev=attributes.ptr, n=N, d=d, queries_dev=needle_attributes.ptr, q=Q)
+    by_pix = None
+    if images is not None and needle_images is not None:
+        chw = images.size // N
+        if needle_images.size != Q * chw:
+            raise L.GanrevError(f"searchByExample: needle images of {needle_images.size // max(Q, 1)} values against images of {chw}")
+        by_pix, _ = ctx.cosine_topk_queries(None, None, n, emb_dev=images.ptr, n=N, d=chw, queries_dev=needle_images.ptr, q=Q)
+    return by_attr, by_pix
+
+
 def cosineSimilarity(v1, v2):
     """apply_r.lua:396-400."""
     return L.default_context().cosine_similarity(v1, v2)
@@ -263,7 +300,9 @@ def parse(argv=None):
     p.add_argument("--nbImages", type=int, default=10000)                     # apply_r.lua:145
     p.add_argument("--synthetic", default="", help="CxHxWxND, e.g. 1x32x32x32: random-initialised G / R / R_fixer instead of checkpoints")
     p.add_argument("--host", action="store_true", help="the host-tensor loop (forwardBatched per chunk, as apply_r.lua spells it) instead of the device-resident pipeline")
-    scripts.add_dataset_options(p)                                            # apply_r.lua:16 --dataset (configured as there, never read)
+    scripts.add_dataset_options(p)                                            # apply_r.lua:16 --dataset (configured as there; read by --needles / --real only)
+    p.add_argument("--needles", type=int, default=0, metavar="N", help="search by example: the first N files of --dataset (DATASET.loadPaths() order) are embedded with R and searched in the corpus by attributes and by pixels (device-resident pipeline only)")
+    p.add_argument("--real", action="store_true", help="the corpus is the first --nbImages files of --dataset (apply_r.lua:144, commented out there) instead of G(noise) (device-resident pipeline only)")
     p.add_argument("--conv-mode", default="f16x3", choices=["f32", "bf16x6", "f16x3"])
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--resident", action="store_true", help="device-resident pipeline only: analyse the tables where the embedding wrote them; the image table is never copied to the host")
@@ -277,15 +316,30 @@ def parse(argv=None):
         p.error("--refine runs on the device-resident tables: not with --host")
     if OPT.refine < 0:
         p.error("--refine: a step count")
+    if OPT.needles < 0:
+        p.error("--needles: a file count")
+    if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
+        p.error("--needles and --real read their images from --dataset")
+    if (OPT.needles or OPT.real) and OPT.host:
+        p.error("--needles and --real run on the device-resident tables: not with --host")
     return OPT
 
 
 def main(argv=None):
+    OPT = parse(argv)
+    try:
+        return run(OPT)
+    finally:
+        if OPT.needles or OPT.real:                                           # --cacheDataset: the files' bytes go back with the run, however it ends
+            from . import dataset
+            dataset.uncache()
+
+
+def run(OPT):
     import json
     import os
     import time
     from . import models, nn_utils, synth
-    OPT = parse(argv)
     ctx = L.Context(OPT.gpu) if OPT.gpu != int(os.environ.get("LOCAL_RANK", "0")) else L.default_context()
     ctx.set_conv_mode(OPT.conv_mode)
     say = (lambda *a: None) if OPT.quiet else print
@@ -303,7 +357,32 @@ def main(argv=None):
         dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
         MODEL_R = t7.load_checkpoint(OPT.R)["R"]                              # :92-94
         MODEL_R_FIXER = t7.load_checkpoint(OPT.R_fixer)["R"]                  # :101-103
-    scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], reads=False)      # apply_r.lua:83-87
+    reads = bool(OPT.needles or OPT.real)
+    if reads:                                                                 # --cacheDataset then keeps the files on the GPU
+        DATASET = scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], ctx=ctx, reads=True)
+        have = len(DATASET.paths if DATASET.paths is not None else DATASET.loadPaths())      # checked before anything else is allocated
+        for count, what in ((OPT.nbImages if OPT.real else 0, "--nbImages"), (OPT.needles, "--needles")):
+            if have < count:
+                raise L.GanrevError(f"--dataset holds {have} matching files, {what} asks for {count}")
+    else:
+        DATASET = scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], reads=False)      # apply_r.lua:83-87: configured, never read
+
+    def load_first(count):                                                    # apply_r.lua:144 DATASET.loadImages(1, count), on the device
+        res = DATASET.loadImages(1, count, ctx=ctx)
+        if tuple(res.images.shape[1:]) != tuple(dims):
+            shape = res.images.shape[1:]; res.free()
+            raise L.GanrevError(f"--dataset images are {shape} in colour space {colorSpace}, the nets take {tuple(dims)}")
+        return res
+
+    def refine_rows(images_t, z_t):                                           # ganrev.refine over one image table and its recovered noise
+        from . import device, refine
+        dmG = device.DeviceModel(ctx, MODEL_G)
+        try:
+            first, best = refine.refineNoise(ctx, dmG, images_t.ptr, z_t.ptr, z_t.shape[0], OPT.refine, OPT.batchSize, lr=OPT.refine_lr, clamp=1.0 if method == "uniform" else 0.0)
+        finally:
+            dmG.close()
+        return dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
+                    loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
     for m in (MODEL_G, MODEL_R, MODEL_R_FIXER):
         m._ctx = ctx
         m.evaluate()
@@ -331,7 +410,8 @@ def main(argv=None):
     say("Generating images, converting images to attributes...")             # :141-153
     N = OPT.nbImages
     t0 = time.perf_counter()
-    dn = nn_utils.createNoiseInputsDev(ctx, N, nd, method, seed=OPT.seed + 1)      # utils/nn_utils.lua:39-51, drawn on the device (both paths: same noise)
+    # utils/nn_utils.lua:39-51, drawn on the device (both paths: same noise); --real has no use for it
+    dn = None if OPT.real else nn_utils.createNoiseInputsDev(ctx, N, nd, method, seed=OPT.seed + 1)
     if OPT.host:
         noise = dn.numpy(); dn.free()
         images, attributes, attributesFixer = embed(MODEL_G, MODEL_R, noise, OPT.batchSize, MODEL_R_FIXER)
@@ -340,19 +420,18 @@ def main(argv=None):
             di, df = DeviceTensor(ctx, images.shape), DeviceTensor(ctx, attributesFixer.shape)
             ctx.upload(images, di.ptr); ctx.upload(attributesFixer, df.ptr)
     else:
-        di, da, df = embed_dev(MODEL_G, MODEL_R, dn, OPT.batchSize, MODEL_R_FIXER, keep_images=True, dims=dims)
+        if OPT.real:                                                          # :144: the corpus is the dataset's images, not G's
+            say("Loading the first %d images of --dataset..." % N)
+            di = load_first(N).images
+            da, df = embedImagesDev([MODEL_R, MODEL_R_FIXER], di, OPT.batchSize)                      # :152-153
+            summary["corpus"] = "dataset"
+        else:
+            di, da, df = embed_dev(MODEL_G, MODEL_R, dn, OPT.batchSize, MODEL_R_FIXER, keep_images=True, dims=dims)
         if OPT.refine:
             # `attributes` only: pulling attributesFixer back to the unfixed image would undo the fix, and the anomaly score needs the
             # unrefined reconstruction.  The search and the clusters below read the refined table.
-            from . import device, refine
             say("Refining the recovered noise through G...")
-            dmG = device.DeviceModel(ctx, MODEL_G)
-            try:
-                first, best = refine.refineNoise(ctx, dmG, di.ptr, da.ptr, N, OPT.refine, OPT.batchSize, lr=OPT.refine_lr, clamp=1.0 if method == "uniform" else 0.0)
-            finally:
-                dmG.close()
-            summary["refine"] = dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
-                                     loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
+            summary["refine"] = refine_rows(di, da)
             if OPT.render:
                 from . import render
                 k = min(52, N)
@@ -360,8 +439,37 @@ def main(argv=None):
                 render.fixed_pairs_grid(di, again, k, colorSpace, path=out("refined_pairs.png"))      # image next to G(refined z)
                 again.free()
         by_attr, by_pix = createSimilaritySearchDev(5, 100, da, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
+        if OPT.needles:
+            # search by example: the needles are images from outside the corpus - the dataset's first files - embedded like the corpus
+            # (R, then the same refinement against themselves) and searched in the tables where they lie
+            say("Searching the corpus for the first %d images of --dataset..." % OPT.needles)
+            nl = na = None
+            try:
+                nl = load_first(OPT.needles)
+                ni = nl.images
+                (na,) = embedImagesDev([MODEL_R], ni, OPT.batchSize)
+                summary["needles"] = dict(count=OPT.needles, files=[os.path.basename(f) for f in nl.paths])
+                if OPT.refine:
+                    summary["needles"]["refine"] = refine_rows(ni, na)
+                nb_attr, nb_pix = searchByExample(100, da, na, di, ni)
+                np.save(out("needle_by_attributes.npy"), nb_attr); np.save(out("needle_by_pixels.npy"), nb_pix); np.save(out("needle_attributes.npy"), na.numpy())
+                if OPT.render:
+                    from . import render
+                    for i in range(OPT.needles):
+                        render.similar_example_grid(ni, i, di, nb_attr[i], colorSpace, path=out("needle_attributes_%02d.png" % (i + 1)))
+                        render.similar_example_grid(ni, i, di, nb_pix[i], colorSpace, path=out("needle_pixelwise_%02d.png" % (i + 1)))
+            except BaseException:
+                for t in (di, da, df, dn):                                    # the corpus tables go with a failed needle step
+                    if t is not None:
+                        t.free()
+                raise
+            finally:
+                for t in (na, nl):
+                    if t is not None:
+                        t.free()
         attributes, attributesFixer = da.numpy(), df.numpy()
-        dn.free()
+        if dn is not None:
+            dn.free()
         if not OPT.resident:
             images = di.numpy()
             if not OPT.render:

@@ -248,3 +248,29 @@ def sharded_cosine_topk(local_topk, emb_shard, row_offset, needle_rows, k, comm)
         cand_i[q, :len(ii)] = ii - Q + row_offset; cand_s[q, :len(ii)] = ss
     gi, gs = comm.allgather(cand_i), comm.allgather(cand_s)
     return merge_candidates(gi, gs, k)
+
+
+def context_topk_queries(ctx, accumulate_in_float=False):
+    """Context.cosine_topk_queries as sharded_cosine_topk_queries' local search: a host array is searched as it is, a DeviceTensor where it lies"""
+    def fn(emb_shard, needles, k):
+        if hasattr(emb_shard, "ptr"):
+            n = emb_shard.shape[0]
+            return ctx.cosine_topk_queries(None, needles, k, accumulate_in_float, emb_dev=emb_shard.ptr, n=n, d=emb_shard.size // n)
+        return ctx.cosine_topk_queries(emb_shard, needles, k, accumulate_in_float)
+    return fn
+
+
+def sharded_cosine_topk_queries(local_topk_queries, emb_shard, row_offset, needles, k, comm):
+    """sharded_cosine_topk for needle VECTORS [Q x d] (the same on every rank: gather_needles' result, or vectors from outside the corpus)
+    without the concatenation: local_topk_queries(emb_shard, needles, k) -> (idx, scores) is the single-device search by example
+    (Context.cosine_topk_queries), so the shard is searched where it lies - a host array or a DeviceTensor - and is never copied.  A needle
+    that is a corpus row meets itself like any other row: every row of every shard is scored."""
+    n = int(emb_shard.shape[0])
+    needles = np.ascontiguousarray(needles, np.float32)
+    Q = needles.shape[0]
+    cand_i = np.full((Q, k), -1, np.int64); cand_s = np.full((Q, k), -np.inf, np.float32)
+    if n > 0:
+        idx, sc = local_topk_queries(emb_shard, needles, min(k, n))
+        cand_i[:, :idx.shape[1]] = idx + row_offset; cand_s[:, :idx.shape[1]] = sc
+    gi, gs = comm.allgather(cand_i), comm.allgather(cand_s)
+    return merge_candidates(gi, gs, k)

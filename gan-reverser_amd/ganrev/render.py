@@ -95,6 +95,27 @@ def similar_grid(images_dev, rows, from_space="rgb", path=None):
     return grid(images_dev, rows, math.ceil(math.sqrt(len(rows))), from_space, inset=inset, inset_rgb=BLUE, path=path)
 
 
+def similar_example_grid(needle_images_dev, needle_row, images_dev, rows, from_space="rgb", path=None):
+    """similar_grid for a search by example: the needle image - row `needle_row` of ITS table, it is no row of the corpus - in the first cell
+    with the blue frame, then the hits `rows` of the corpus table, best first; nrow = ceil(sqrt(1 + n)).  The 1 + n images are gathered
+    into one sheet on the device (as cluster_grid does with the average face) and drawn by the same launch."""
+    ctx = images_dev.ctx
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    n, d = len(rows), images_dev.size // images_dev.shape[0]
+    if tuple(needle_images_dev.shape[1:]) != tuple(images_dev.shape[1:]):
+        raise ValueError(f"needle images {needle_images_dev.shape[1:]} and corpus images {images_dev.shape[1:]} differ in shape")
+    sheet = DeviceTensor(ctx, (1 + n,) + tuple(images_dev.shape[1:]))
+    try:
+        ctx.copy2d(sheet.ptr, d, needle_images_dev.ptr + 4 * d * int(needle_row), d, 1, d)
+        for j, r in enumerate(rows):
+            ctx.copy2d(sheet.ptr + 4 * d * (1 + j), d, images_dev.ptr + 4 * d * int(r), d, 1, d)
+        inset = np.zeros(1 + n, np.uint8)
+        inset[0] = 1
+        return grid(sheet, np.arange(1 + n), math.ceil(math.sqrt(1 + n)), from_space, inset=inset, inset_rgb=BLUE, path=path)
+    finally:
+        sheet.free()
+
+
 def fixed_pairs_grid(images_dev, fixed_dev, nbPairs, from_space="rgb", path=None):
     """apply_r.lua:325-342: image i and its fixed version side by side on a blue field with a 1-pixel border, 4 pairs per row"""
     i = np.arange(nbPairs, dtype=np.int64)

@@ -46,7 +46,7 @@ def add_dataset_options(p):
     # True when given, None (not False) when absent, like --progress: a run without it saves the opt table it saved before the option existed
     p.add_argument("--cacheDataset", action="store_true", default=None,
                    help="decode every file of --dataset once and keep the bytes on the GPU: each draw is then one launch, same images bit for bit "
-                        "(needs --dataset and the device-resident loop; apply_r and train_r configure the dataset and never read it: they accept and ignore this)")
+                        "(needs --dataset and the device-resident loop; apply_r and train_r configure the dataset and - but for apply_r --needles / --real - never read it: they accept and ignore this)")
 
 
 def add_progress_option(p):
@@ -67,8 +67,8 @@ def open_dataset(OPT, colorSpace, height, width, ctx=None, reads=True):
     """The five DATASET.set* calls of a script's head when --dataset names a directory -> the configured ganrev.dataset module, else None.
     The reference asserts OPT.dataset ~= "NONE"; here NONE keeps --data / the synthetic images.  Giving both --data and --dataset is an error.
     The permutations of loadRandomImages are seeded from --seed.  --cacheDataset: DATASET.cache(ctx) before the first draw (an error without
-    --dataset, and with --compat, whose host loops have no use for a device table); reads=False (apply_r, train_r: the dataset is
-    configured, never read) ignores it."""
+    --dataset, and with --compat, whose host loops have no use for a device table); reads=False (train_r, and apply_r without
+    --needles / --real: the dataset is configured, never read) ignores it."""
     want_cache = bool(getattr(OPT, "cacheDataset", None)) and reads
     if want_cache and OPT.dataset == "NONE":
         raise L.GanrevError("--cacheDataset needs --dataset: there are no files to keep")

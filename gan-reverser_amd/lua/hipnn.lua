@@ -91,6 +91,10 @@ int gr_embed_dev(gr_net* gnet, gr_net* const* rnets, int n_rnets, const float* n
                  float* images_out_dev, float* const* attr_out_dev);                                       /* apply_r.lua:145-153 */
 int gr_cosine_topk_dev(gr_ctx*, const float* emb_dev, int64_t n, int d, const int64_t* rows, int q, int k,
                        int64_t* idx, float* score, int accumulate_in_float);
+int gr_cosine_topk_queries_dev(gr_ctx*, const float* emb_dev, int64_t n, int d, const float* queries_dev, int q, int k,
+                               int64_t* idx, float* score, int accumulate_in_float);
+int gr_cosine_topk_queries_host(gr_ctx*, const float* emb, int64_t n, int d, const float* queries, int q, int k,
+                                int64_t* idx, float* score, int accumulate_in_float);
 int gr_l2_nearest_host(gr_ctx*, const float* table, int64_t n, int64_t d, const float* queries, int q, int k,
                        int64_t* idx, double* dist);                                                        /* sample.lua:130-148 */
 int gr_l2_nearest_dev(gr_ctx*, const float* table_dev, int64_t n, int64_t d, const float* queries_dev, int q, int k,
@@ -318,6 +322,18 @@ function hipnn.cosineTopK(attributes, needles, k)
    local idx = torch.LongTensor(Q, k); local sc = torch.FloatTensor(Q, k)
    check(C.gr_cosine_topk_host(context(), attributes:contiguous():data(), N, d, rows, Q, k,
                                ffi.cast('int64_t*', idx:data()), sc:data(), 0), 'gr_cosine_topk_host')
+   return idx:add(1), sc
+end
+
+-- search by example: the needles are the rows of a FloatTensor [Q x d] of their own (a photo's attributes: MODEL_R:forward(photo)), not rows
+-- of `attributes`; every row of the table is scored.  Same order, same result layout as hipnn.cosineTopK.
+function hipnn.cosineTopKQueries(attributes, queries, k)
+   local N, d, Q = attributes:size(1), attributes:size(2), queries:size(1)
+   assert(queries:size(2) == d, 'hipnn.cosineTopKQueries: needles and table differ in width')
+   k = math.min(k, N)
+   local idx = torch.LongTensor(Q, k); local sc = torch.FloatTensor(Q, k)
+   check(C.gr_cosine_topk_queries_host(context(), attributes:contiguous():data(), N, d, queries:contiguous():data(), Q, k,
+                                       ffi.cast('int64_t*', idx:data()), sc:data(), 0), 'gr_cosine_topk_queries_host')
    return idx:add(1), sc
 end
 

@@ -318,6 +318,15 @@ int gr_cosine_topk_host(gr_ctx* ctx, const float* emb_host, int64_t n, int d, co
                         int64_t* idx_out_host, float* score_out_host, int accumulate_in_float);
 int gr_cosine_topk_dev(gr_ctx* ctx, const float* emb_dev, int64_t n, int d, const int64_t* query_rows_host, int q, int k,
                        int64_t* idx_out_host, float* score_out_host, int accumulate_in_float);
+/* Search by example: the same search with needle q = row q of queries [q x d], vectors that need not be rows of emb.  Every row of emb is
+ * scored (there is no self hit to drop), same order, same k rules (clamped to n; k > 1024: GR_ERR_UNSUPPORTED), same dispatch on (n, d, q, k)
+ * and the same overflow rerun.  A needle that equals a table row bit for bit returns what the row-index search of that row returns, indices
+ * and score bits.  A zero needle scores 0 against every row: rows 0 .. k-1.  A finite needle whose norm the approximate passes cannot carry (zero,
+ * or elements beyond fp16 with 32 or more needles) costs one rerun, not the result.  Non-finite needles are not supported. */
+int gr_cosine_topk_queries_dev(gr_ctx* ctx, const float* emb_dev, int64_t n, int d, const float* queries_dev, int q, int k,
+                               int64_t* idx_out_host, float* score_out_host, int accumulate_in_float);
+int gr_cosine_topk_queries_host(gr_ctx* ctx, const float* emb_host, int64_t n, int d, const float* queries_host, int q, int k,
+                                int64_t* idx_out_host, float* score_out_host, int accumulate_in_float);
 int gr_cosine_similarity_host(gr_ctx* ctx, const float* a_host, const float* b_host, int d, float* out);
 /* Tables of 2^17 rows or more are searched through a bound taken from a strided 16384-row sample (only keys at or above the
  * sample's k-th largest key are kept: same result, bit for bit, without writing n x q keys).  With 32 or more needles (d <= 128)
