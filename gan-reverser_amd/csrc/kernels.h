@@ -539,6 +539,14 @@ int launch_cosine_assign(const float* x, long N, int d, const float* cent, int k
 size_t cluster_members_workspace_bytes(long n, int k);
 int launch_cluster_members(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
                            void* workspace, hipStream_t s);
+// gr_cluster_dev: apply_r.lua:198-227 in one enqueue, 1 <= k <= 4096, d <= 256, 1 <= m <= 128, 1 <= n < 2^31 (returns 1 outside, 2 when the device refuses
+// the wide assignment kernel's LDS).  Below g_cluster_wide_min_k (and while k * d doubles fit kmeans_accumulate_kernel's 60 KB) the three launch_* above,
+// in their order; from it on the wide kernels of kmeans.hip, which reproduce their bits.  c2 / counts / w32 / totalcounts [k] device scratch.
+extern int g_cluster_wide_min_k;         // gr_set_tuning "cluster_wide_min_k" (default 33)
+bool cluster_takes_wide_route(int d, int k);
+size_t cluster_workspace_bytes(long n, int d, int k);
+int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent, int take_min, int m, float* c2, float* counts, float* totalcounts,
+                   float* w32, int* labels, float* sims, long* rows_out, float* sims_out, int* kept_out, int* sizes_out, void* workspace, hipStream_t s);
 // apply_r.lua:233-243 for every cluster at once: out[j] = launch_rows_mean of rows[j][0 .. kept[j]); entries outside [0, n_rows) are skipped
 void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows, const int* kept, int k, int m, float* out, hipStream_t s);
 

@@ -242,6 +242,7 @@ extern "C" int gr_set_tuning(gr_ctx* c, const char* key, int value) {
   if (!strcmp(key, "p16_min_tiles")) { gr::g_p16_min_tiles = value; return GR_OK; }
   if (!strcmp(key, "group_mfma_min_tiles")) { gr::g_group_mfma_min_tiles = value; return GR_OK; }   // GR_GROUPCONV3 takes the f16x3 / bf16x6 MFMA launches (groupmfma.hip) from this many (image, group) tiles on (default 512)
   if (!strcmp(key, "stack8_min_wgs")) { gr::g_stack8_min_wgs = value; return GR_OK; }      // four 8x8 images per convolution tile from this many workgroups on (default 128)
+  if (!strcmp(key, "cluster_wide_min_k")) { gr::g_cluster_wide_min_k = value; return GR_OK; }   // gr_cluster_dev takes the wide kernels (kmeans.hip) from this k on (default 33; tests set 1)
   if (!strcmp(key, "eval_p16")) { g_eval_p16 = value; return GR_OK; }           // evaluate()-mode stages hand their output over operand-ready (1, default) or as fp32 (0: the A/B control)
   if (!strcmp(key, "side_wgrad")) { c->side_wgrad = value; return GR_OK; }
   if (!strcmp(key, "fused_head")) { c->fused_head = value != 0; return GR_OK; }   // gr_train_r_step: R's last two stages + the criterion, forward and backward, in one launch

@@ -486,6 +486,27 @@ extern "C" int gr_cluster_members_dev(gr_ctx* c, const int32_t* labels, const fl
   LAUNCHCHK(c);
   return GR_OK;
 }
+extern "C" int gr_cluster_dev(gr_ctx* c, const float* x, int64_t n, int d, int k, int niter, float* cent, int take_min, int m, float* totalcounts,
+                              int32_t* labels, float* sims, int64_t* rows_out, float* sims_out, int32_t* kept_out, int32_t* sizes_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !cent || !labels || !sims || !rows_out || !sims_out || !kept_out || !sizes_out) return fail(c, GR_ERR_INVALID, "gr_cluster_dev: null pointer");
+  if (n <= 0 || d <= 0 || k <= 0 || m <= 0 || niter < 0)
+    return fail(c, GR_ERR_INVALID, "gr_cluster_dev: n %lld, d %d, k %d, m %d must be positive and niter %d not negative", (long long)n, d, k, m, niter);
+  if (k > 4096) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_dev: k %d: at most 4096 clusters", k);
+  if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_dev: d %d: at most 256 columns", d);
+  if (m > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_dev: m %d: at most 128 rows per cluster", m);
+  if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_dev: n %lld: fewer than 2^31 rows", (long long)n);
+  Staging s(c);
+  auto scratch = s.reserve<char>(cluster_workspace_bytes(n, d, k));
+  auto dc2 = s.reserve<float>(k), dcnt = s.reserve<float>(k), dtot = s.reserve<float>(k), dw = s.reserve<float>(k);
+  TRY(s.grow());
+  const int r = launch_cluster(x, n, d, k, niter, cent, take_min, m, s.ptr(dc2), s.ptr(dcnt), totalcounts ? totalcounts : s.ptr(dtot), s.ptr(dw), labels, sims,
+                               reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, s.ptr(scratch), c->stream);
+  if (r == 2) return fail(c, GR_ERR_HIP, "gr_cluster_dev: the device refuses the assignment kernel's LDS (d %d)", d);
+  if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
 extern "C" int gr_cluster_faces_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, const int32_t* kept, int k, int m, float* out) {
   if (!c) return GR_ERR_INVALID;
   if (!table || !rows || !kept || !out) return fail(c, GR_ERR_INVALID, "gr_cluster_faces_dev: null pointer");

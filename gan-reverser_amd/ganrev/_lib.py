@@ -191,6 +191,7 @@ _SIGS = {
     "gr_cosine_assign_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "gr_cluster_members_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gr_cluster_faces_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P]),
+    "gr_cluster_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gr_malloc": (C.c_int, [_P, C.c_int64, C.POINTER(_P)]),
     "gr_free": (C.c_int, [_P, _P]),
     "gr_memcpy_h2d": (C.c_int, [_P, _P, _P, C.c_int64]),
@@ -586,6 +587,17 @@ class Context:
         sims_out_dev float [k x m] (0 fill), kept_out_dev / sizes_out_dev int32 [k]"""
         self.check(self.lib.gr_cluster_members_dev(self.h, _ptr(labels_dev), _ptr(sims_dev), int(n), int(k), int(m), _ptr(rows_out_dev), _ptr(sims_out_dev),
                                                    _ptr(kept_out_dev), _ptr(sizes_out_dev)), "gr_cluster_members_dev")
+
+    CLUSTER_WIDE_MIN_K = 33          # default of gr_set_tuning "cluster_wide_min_k": gr_cluster_dev's wide kernels from this k on (tests set 1)
+
+    def cluster_dev(self, x_dev, n, d, k, niter, cent_dev, take_min, m, totalcounts_dev, labels_dev, sims_dev, rows_out_dev, sims_out_dev, kept_out_dev,
+                    sizes_out_dev):
+        """gr_cluster_dev (apply_r.lua:198-227 in one enqueue, k <= 4096, d <= 256, m <= 128): k-means from cent_dev [k x d] (final centroids out;
+        totalcounts_dev [k] or None), the cosine assignment into labels_dev int32 / sims_dev [n], and per cluster the m most similar member rows
+        into rows_out_dev int64 / sims_out_dev [k x m] (-1 / 0 fill), kept_out_dev / sizes_out_dev int32 [k]"""
+        self.check(self.lib.gr_cluster_dev(self.h, _ptr(x_dev), int(n), int(d), int(k), int(niter), _ptr(cent_dev), int(bool(take_min)), int(m),
+                                           _ptr(totalcounts_dev), _ptr(labels_dev), _ptr(sims_dev), _ptr(rows_out_dev), _ptr(sims_out_dev),
+                                           _ptr(kept_out_dev), _ptr(sizes_out_dev)), "gr_cluster_dev")
 
     def cluster_faces_dev(self, table_dev, n_rows, d, rows_dev, kept_dev, k, m, out_dev):
         """gr_cluster_faces_dev (apply_r.lua:233-243): out_dev [k x d] = the average faces of all clusters (rows_dev int64 [k x m], kept_dev int32 [k])"""

@@ -165,6 +165,53 @@ def selectClusterMembers(label, sim, nbClusters, nbMaxPerCluster):
     return keeps
 
 
+MAX_CLUSTERS, NARROW_MAX_CLUSTERS, MAX_PER_CLUSTER = 4096, 32, 128      # gr_cluster_dev's limits; the k the three older calls take
+
+
+def checkClusterCount(nbClusters):
+    if not 1 <= int(nbClusters) <= MAX_CLUSTERS:
+        raise L.GanrevError(f"nbClusters {nbClusters}: 1 to {MAX_CLUSTERS} clusters")
+    return int(nbClusters)
+
+
+def clusterTableDev(ctx, table_ptr, N, d, k, nbIterations, m, centroids0, closest, faces_of=None):
+    """apply_r.lua:198-227 on a device table [N x d].  Up to 32 clusters: gr_kmeans_dev, gr_cosine_assign_dev, gr_cluster_members_dev, as ever;
+    above: gr_cluster_dev, one enqueue.  faces_of = (images pointer, rows of that table, values per image, output pointer) adds gr_cluster_faces_dev
+    (apply_r.lua:233-243) while the lists are still on the device.  -> (centroids, counts, clusters)"""
+    cent = ctx.upload(np.ascontiguousarray(centroids0, np.float32).reshape(k, d))
+    sizes = [4 * k, 4 * N, 4 * N, 8 * k * m, 4 * k * m, 4 * k, 4 * k]               # counts, labels, sims, rows, their sims, kept, cluster sizes
+    bufs = [cent]
+    try:
+        for b in sizes:
+            bufs.append(ctx.malloc(b))
+        tot, lab, sim, rows, rsim, kept, csize = bufs[1:]
+        if k <= NARROW_MAX_CLUSTERS:
+            ctx.kmeans_dev(table_ptr, N, d, k, nbIterations, cent, tot, lab)                    # :198
+            ctx.cosine_assign_dev(table_ptr, N, d, cent, k, not closest, lab, sim)              # :205-217
+            ctx.cluster_members_dev(lab, sim, N, k, m, rows, rsim, kept, csize)                 # :218-227
+        else:
+            ctx.cluster_dev(table_ptr, N, d, k, nbIterations, cent, not closest, m, tot, lab, sim, rows, rsim, kept, csize)
+        if faces_of is not None:
+            images_ptr, n_rows, chw, faces_ptr = faces_of
+            ctx.cluster_faces_dev(images_ptr, n_rows, chw, rows, kept, k, m, faces_ptr)         # :233-243 (zeros for an empty cluster)
+        centroids, counts = ctx.download(cent, (k, d)), ctx.download(tot, (k,))
+        hrows, hsim, hkept = ctx.download(rows, (k, m), np.int64), ctx.download(rsim, (k, m)), ctx.download(kept, (k,), np.int32)
+    finally:
+        for b in bufs:
+            ctx.free(b)
+    clusters = [[(int(r), float(v)) for r, v in zip(hrows[j, :hkept[j]], hsim[j, :hkept[j]])] for j in range(k)]
+    return centroids, counts, clusters
+
+
+def clusterHostTable(ctx, attributes, k, nbIterations, m, centroids0, closest, faces_of=None):
+    """clusterTableDev for a host attribute table: uploaded to a temporary buffer first (more than 32 clusters: gr_cluster_dev has no host variant)"""
+    table = ctx.upload(np.ascontiguousarray(attributes, np.float32))
+    try:
+        return clusterTableDev(ctx, table, attributes.shape[0], attributes.shape[1], k, nbIterations, m, centroids0, closest, faces_of)
+    finally:
+        ctx.free(table)
+
+
 def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, centroids0=None, seed=1, closest=False):
     """apply_r.lua:197-231 without the image writing.  -> (centroids, counts, clusters, averageFaces): clusters[j] is the list
     of (row index, similarity) kept for cluster j, sorted like the reference (similarity descending, first nbMaxPerCluster);
@@ -172,12 +219,22 @@ def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attri
     and skips the cluster when saving, :243,:251).
 
     Reference behaviour preserved: a row joins the centroid with the MINIMUM cosine similarity (:207-214 keep `dist <
-    minDist` of a similarity).  closest=True assigns to the most similar centroid instead."""
+    minDist` of a similarity).  closest=True assigns to the most similar centroid instead.
+
+    Up to 4096 clusters.  The reference's 20, and anything up to 32, run as ever; above 32 the attribute table is uploaded and clustered by
+    gr_cluster_dev (lists of at most 128 rows), and the faces are averaged from its lists the same way."""
     attributes = np.asarray(attributes, np.float32)
     N, d = attributes.shape
+    nbClusters = checkClusterCount(nbClusters)
     if centroids0 is None:
         centroids0 = initialCentroids(nbClusters, d, seed)
     ctx = L.default_context()
+    if nbClusters > NARROW_MAX_CLUSTERS:
+        centroids, counts, clusters = clusterHostTable(ctx, attributes, nbClusters, nbIterations, int(nbMaxPerCluster), centroids0, closest)
+        images = np.asarray(images, np.float32)
+        faces = [images[[r for r, _ in cl]].mean(axis=0, dtype=np.float64).astype(np.float32) if cl else np.zeros(images.shape[1:], np.float32)
+                 for cl in clusters]                                                                # :233-243
+        return centroids, counts, clusters, faces
     centroids, counts, _ = ctx.kmeans(attributes, nbClusters, nbIterations, centroids0)            # :198
     label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
     clusters, faces = [], []
@@ -196,32 +253,29 @@ def createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, at
     (apply_r.lua:233-243).  createClusterImages averages in float64 on the host: the faces may differ from it in the last bits.
     With a device table nothing of size N crosses the bus: gr_kmeans_dev, gr_cosine_assign_dev, gr_cluster_members_dev and
     gr_cluster_faces_dev run where the table lies, and the [k x m] lists, the centroids and the counts come back - the same tuple, bit for bit.
+    Up to 4096 clusters: above 32, gr_cluster_dev stands for the first three calls (a host table is uploaded for it), lists of at most 128 rows.
     -> (centroids, counts, clusters, faces) with faces a DeviceTensor [nbClusters x C x H x W] (the caller frees it)."""
     ctx = images.ctx
     chw = images.size // images.shape[0]
-    faces = DeviceTensor(ctx, (nbClusters,) + tuple(images.shape[1:]))
-    if isinstance(attributes, DeviceTensor):
-        N, k, m = attributes.shape[0], int(nbClusters), int(nbMaxPerCluster)
-        d = attributes.size // N
-        if centroids0 is None:
-            centroids0 = initialCentroids(k, d, seed)
-        cent = ctx.upload(np.ascontiguousarray(centroids0, np.float32).reshape(k, d))
-        sizes = [4 * k, 4 * N, 4 * N, 8 * k * m, 4 * k * m, 4 * k, 4 * k]               # counts, labels, sims, rows, their sims, kept, cluster sizes
-        tot, lab, sim, rows, rsim, kept, csize = bufs = [ctx.malloc(b) for b in sizes]
+    k, m = checkClusterCount(nbClusters), int(nbMaxPerCluster)
+    faces = DeviceTensor(ctx, (k,) + tuple(images.shape[1:]))
+    faces_of = (images.ptr, images.shape[0], chw, faces.ptr)
+    if isinstance(attributes, DeviceTensor) or k > NARROW_MAX_CLUSTERS:     # (a host table of more than 32 clusters is uploaded: gr_cluster_dev)
         try:
-            ctx.kmeans_dev(attributes.ptr, N, d, k, nbIterations, cent, tot, lab)                   # :198
-            ctx.cosine_assign_dev(attributes.ptr, N, d, cent, k, not closest, lab, sim)             # :205-217
-            ctx.cluster_members_dev(lab, sim, N, k, m, rows, rsim, kept, csize)                     # :218-227
-            ctx.cluster_faces_dev(images.ptr, images.shape[0], chw, rows, kept, k, m, faces.ptr)    # :233-243 (zeros for an empty cluster)
-            centroids, counts = ctx.download(cent, (k, d)), ctx.download(tot, (k,))
-            hrows, hsim, hkept = ctx.download(rows, (k, m), np.int64), ctx.download(rsim, (k, m)), ctx.download(kept, (k,), np.int32)
+            if isinstance(attributes, DeviceTensor):
+                N = attributes.shape[0]
+                d = attributes.size // N
+                if centroids0 is None:
+                    centroids0 = initialCentroids(k, d, seed)
+                centroids, counts, clusters = clusterTableDev(ctx, attributes.ptr, N, d, k, nbIterations, m, centroids0, closest, faces_of)
+            else:
+                attributes = np.asarray(attributes, np.float32)
+                if centroids0 is None:
+                    centroids0 = initialCentroids(k, attributes.shape[1], seed)
+                centroids, counts, clusters = clusterHostTable(ctx, attributes, k, nbIterations, m, centroids0, closest, faces_of)
         except Exception:
             faces.free()
             raise
-        finally:
-            for b in bufs + [cent]:
-                ctx.free(b)
-        clusters = [[(int(r), float(v)) for r, v in zip(hrows[j, :hkept[j]], hsim[j, :hkept[j]])] for j in range(k)]
         return centroids, counts, clusters, faces
     attributes = np.asarray(attributes, np.float32)
     N, d = attributes.shape
@@ -247,7 +301,8 @@ def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colo
     from . import render
     ctx, N = images.ctx, images.shape[0]
     chw = images.size // N
-    centroids, counts, clusters, faces = createClusterImagesDev(20, 15, 64 + 7, images, attributes, seed=OPT.seed)      # :158-163
+    nbClusters, nbIterations, nbMaxPerCluster, closest = clusterOptions(OPT)                                            # :159-161: 20, 15, 64 + 7
+    centroids, counts, clusters, faces = createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, seed=OPT.seed, closest=closest)      # :158-163
     for j, cl in enumerate(clusters):
         if cl and out:                                                                                                  # :249
             render.cluster_grid(images, [r for r, _ in cl], colorSpace, face_dev=faces.rows(j, j + 1), path=out("cluster_%02d.png" % (j + 1)))
@@ -287,6 +342,11 @@ def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributes
 # beside them as PNG, under the reference's names: variations, cluster_%02d, similar_attributes_%02d, similar_pixelwise_%02d, fixed_pairs,
 # fixed_images_528[_unfixed], anomalies (the counts clamp to --nbImages).  G / R / R_fixer come from Torch7 checkpoints (ganrev.t7: train.lua:256, train_r.lua:234) or, with
 # --synthetic, from random-initialised nets of the requested shape (a smoke run: no trained checkpoint exists in this repository).
+def clusterOptions(OPT):
+    """(nbClusters, nbIterations, nbMaxPerCluster, closest) of a run: the options given, else what apply_r.lua:159-163 hard-codes"""
+    return (getattr(OPT, "nbClusters", 20), getattr(OPT, "nbIterations", 15), getattr(OPT, "nbMaxPerCluster", 64 + 7), bool(getattr(OPT, "closest", False)))
+
+
 def parse(argv=None):
     import argparse
     p = argparse.ArgumentParser(description="apply_r.lua options (apply_r.lua:13-23)")
@@ -309,6 +369,11 @@ def parse(argv=None):
     p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
     p.add_argument("--refine", type=int, default=0, metavar="STEPS", help="refine the recovered noise through G: STEPS Adam steps per image on the MSE between G(z) and the image, starting at R's estimate (ganrev.refine; 0, the reference's behaviour: R's estimate is final)")
     p.add_argument("--refine_lr", type=float, default=0.01, help="Adam learning rate of --refine")
+    # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
+    p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
+    p.add_argument("--nbIterations", type=int, default=argparse.SUPPRESS, help="k-means iterations (default 15, apply_r.lua:160)")
+    p.add_argument("--nbMaxPerCluster", type=int, default=argparse.SUPPRESS, help="rows kept per cluster, the most similar first (default 71 = 64 + 7, apply_r.lua:161; at most 128)")
+    p.add_argument("--closest", action="store_true", default=argparse.SUPPRESS, help="a row joins its most similar centroid instead of the least similar one the reference keeps (apply_r.lua:207-214)")
     OPT = p.parse_args(argv)
     if OPT.resident and OPT.host:
         p.error("--resident applies to the device-resident pipeline: not with --host")
@@ -318,6 +383,13 @@ def parse(argv=None):
         p.error("--refine: a step count")
     if OPT.needles < 0:
         p.error("--needles: a file count")
+    nbClusters, nbIterations, nbMaxPerCluster, _ = clusterOptions(OPT)
+    if not 1 <= nbClusters <= MAX_CLUSTERS:
+        p.error(f"--nbClusters: 1 to {MAX_CLUSTERS}")
+    if nbIterations < 0:
+        p.error("--nbIterations: an iteration count")
+    if not 1 <= nbMaxPerCluster <= MAX_PER_CLUSTER:
+        p.error(f"--nbMaxPerCluster: 1 to {MAX_PER_CLUSTER}")
     if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
         p.error("--needles and --real read their images from --dataset")
     if (OPT.needles or OPT.real) and OPT.host:
@@ -492,9 +564,10 @@ def run(OPT):
         np.save(out("similar_by_attributes.npy"), by_attr); np.save(out("similar_by_pixels.npy"), by_pix)
 
     say("Clustering...")                                                      # :158-162
-    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(20, 15, 64 + 7, images, attributes, seed=OPT.seed)
+    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(*clusterOptions(OPT)[:3], images, attributes, seed=OPT.seed, closest=clusterOptions(OPT)[3])     # (20, 15, 64 + 7 unless asked otherwise)
     np.save(out("cluster_centroids.npy"), centroids); np.save(out("cluster_average_faces.npy"), np.stack(faces))
     summary["cluster_sizes"] = [len(c) for c in clusters]; summary["cluster_total_counts"] = [float(v) for v in counts]
+    summary.update(zip(("nbClusters", "nbIterations", "nbMaxPerCluster", "closest"), clusterOptions(OPT)))
 
     say("Fixing faces...")                                                    # :178-181
     nbFixed = min(512 + 16, N)

@@ -50,7 +50,7 @@ int gr_l2_distance_rows_host(gr_ctx*, const float* a, const float* b, int64_t n,
 int gr_kmeans_host(gr_ctx*, const float* x, int64_t n, int d, int k, int niter, float* centroids_inout, float* total_counts, int32_t* labels);
 int gr_cosine_assign_host(gr_ctx*, const float* x, int64_t n, int d, const float* centroids, int k, int take_min, int32_t* labels, float* sims);
 int gr_set_conv_mode(gr_ctx*, int mode);   /* 0 exact fp32 MFMA, 1 bf16x6, 2 f16x3 (default) */
-int gr_set_tuning(gr_ctx*, const char* key, int value);                    /* "range_guard" 0|1 ... (include/ganrev.h) */
+int gr_set_tuning(gr_ctx*, const char* key, int value);                    /* "range_guard" 0|1, "cluster_wide_min_k" 33 ... (include/ganrev.h) */
 int gr_range_guard_stats(gr_ctx*, int64_t* scans, int64_t* fallbacks);     /* f16x3 passes the range guard sent to bf16x6 */
 int gr_range_guard_scan_params(gr_net* net, int* tripped_out);                  /* synchronous scan of a net's weights / BatchNorm scales (device-pointer loops) */
 int gr_search_stats(gr_ctx*, int64_t* reruns);
@@ -82,6 +82,8 @@ int gr_cosine_assign_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const fl
 int gr_cluster_members_dev(gr_ctx*, const int32_t* labels_dev, const float* sims_dev, int64_t n, int k, int m, int64_t* rows_out_dev, float* sims_out_dev,
                            int32_t* kept_out_dev, int32_t* sizes_out_dev);     /* apply_r.lua:218-227 */
 int gr_cluster_faces_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_dev, const int32_t* kept_dev, int k, int m, float* out_dev);     /* apply_r.lua:233-243 */
+int gr_cluster_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float* cent_dev, int take_min, int m, float* totalcounts_dev,
+                   int32_t* labels_dev, float* sims_dev, int64_t* rows_out_dev, float* sims_out_dev, int32_t* kept_out_dev, int32_t* sizes_out_dev);     /* apply_r.lua:198-227, k <= 4096 */
 int gr_progress_grid_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int channels, int h, int w, int from_space,
                          const int64_t* rows_host, int n_show, int grid_h, int grid_w, int epoch, float* grid_dev, uint8_t* u8_dev);     /* imagesToGridTensor, utils/nn_utils.lua:490-548 */
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);

@@ -258,6 +258,8 @@ int gr_get_conv_mode(gr_ctx* ctx);
  *   "stack8_min_wgs" (default 128, process-wide) smallest grid at which 8x8 planes are stacked four to a convolution tile; tests force the path
  *   "group_mfma_min_tiles" (default 512, process-wide) smallest number of (image, group) tiles, B x G, at which a GR_GROUPCONV3 stage of 16 planes per group
  *                    and planes up to 32 x 32 takes the f16x3 / bf16x6 MFMA launches (csrc/groupmfma.hip) instead of the fp32 ones; never in f32 mode; tests set 1
+ *   "cluster_wide_min_k" (default 33, process-wide) smallest k at which gr_cluster_dev takes its wide kernels (csrc/kmeans.hip) instead of the launches of
+ *                    gr_kmeans_dev / gr_cosine_assign_dev / gr_cluster_members_dev; the two routes give the same bits; tests set 1 to compare them - no user knob
  *   "eval_p16"       (default 1) evaluate()-mode stages hand their output to the next convolution operand-ready - see below
  *   "side_wgrad"     (default -1 = by stage size: on from 2^26 activations) R's convolution weight gradients on a second stream beside the rest of backward;
  *                    bit-identical either way (measured: cfg3 -1.1 %, cfg2 +1.1 %: profiles/r05_ab_side_wgrad_*.txt)
@@ -456,6 +458,24 @@ int gr_cluster_members_dev(gr_ctx* ctx, const int32_t* labels_dev, const float* 
                            float* sims_out_dev, int32_t* kept_out_dev, int32_t* sizes_out_dev);
 int gr_cluster_faces_dev(gr_ctx* ctx, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_dev, const int32_t* kept_dev, int k, int m,
                          float* out_dev);
+/* gr_cluster_dev: apply_r.lua:198-227 in one enqueue on the ctx stream, for any k up to 4096 - gr_kmeans_dev (cent_dev [k x d]: initial centroids in,
+ * final ones out; totalcounts_dev [k] nullable), then gr_cosine_assign_dev on the final centroids (labels_dev / sims_dev [n]: the COSINE assignment,
+ * the k-means labels stay in scratch), then gr_cluster_members_dev of those labels (rows_out_dev / sims_out_dev [k x m], kept_out_dev / sizes_out_dev
+ * [k]).  Semantics, fill values (-1 / 0), tie and NaN rules are the ones stated above for the three calls; the result is a function of the inputs alone.
+ * Limits: 1 <= k <= 4096, d <= 256, 1 <= m <= 128, 1 <= n < 2^31; outside them GR_ERR_UNSUPPORTED with a gr_last_error text that names the value; null
+ * pointers (totalcounts_dev excepted), non-positive n, d, k, m or a negative niter GR_ERR_INVALID.  The context stays usable after either.
+ * Routes.  k < "cluster_wide_min_k" (default 33), while the k x d fp64 member sums fit the 60 KB of LDS gr_kmeans_dev needs: exactly the launches of the
+ * three calls, in their order.  Otherwise the wide kernels, which reproduce those bits wherever both routes apply: per (row, centroid) one sequential
+ * fp32 chain in column order, s = s + c[j][t] * x[i][t], multiply and add rounded separately, v = s - c2[j], label = first maximum over ascending j (a row
+ * whose scores are NaN: label 0); member sums in fp64 - per block of 512 consecutive rows a cluster's rows in row order from +0.0, the blocks' partials in
+ * block order from +0.0, one rounding to fp32, one fp32 division by (float)count; a cluster without a row keeps its centroid and c2.  The rows are grouped
+ * by label with a stable counting sort per 512-row block; the m best members are taken from the index grouped by the cosine labels.  No floating-point
+ * atomics: two runs agree bit for bit.
+ * Scratch comes from the context.  Narrow route: that of the three calls (ceil(n / 512) x k x d doubles).  Wide route: with B = ceil(n / 512) blocks and
+ * S = B x min(k, 512) segment slots, S x d doubles + 2 S + 2 B + 512 B + n ints: O(n) index entries, and at most n x d doubles once k >= 512. */
+int gr_cluster_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int niter, float* cent_dev, int take_min, int m,
+                   float* totalcounts_dev /*nullable*/, int32_t* labels_dev, float* sims_dev, int64_t* rows_out_dev, float* sims_out_dev,
+                   int32_t* kept_out_dev, int32_t* sizes_out_dev);
 
 /* ---- device memory helpers for hosts without a tensor library (LuaJIT FFI, ctypes) ---- */
 int gr_malloc(gr_ctx* ctx, int64_t bytes, void** out_dev);
