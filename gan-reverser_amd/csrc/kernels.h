@@ -550,6 +550,16 @@ int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent,
 // apply_r.lua:233-243 for every cluster at once: out[j] = launch_rows_mean of rows[j][0 .. kept[j]); entries outside [0, n_rows) are skipped
 void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows, const int* kept, int k, int m, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- principal axes of a device table (pca.hip; gr_pca_dev, gr_pca_project_dev)
+// mean [d] / cov [d][d] (nullable) / eigvals [d] doubles, axes [d][d] floats (row = unit axis), info [2] ints (sweeps, converged): all device;
+// workspace from pca_workspace_bytes.  Returns 1 outside 2 <= n < 2^31, 1 <= d <= 256.
+size_t pca_workspace_bytes(long n, int d);
+int launch_pca(const float* x, long n, int d, double* mean, double* cov, double* eigvals, float* axes, int* info, void* workspace, hipStream_t s);
+// out [n][k] = (x - mean) . axes[0 .. k)^T, column a times 1 / sqrt(eigvals[a]) when whiten (0 for eigvals[a] <= 0).  Returns 1 outside
+// 1 <= n < 2^31, 1 <= k <= d <= 256, 2 when the device refuses the kernel's LDS.
+int launch_pca_project(const float* x, long n, int d, const double* mean, const float* axes, const double* eigvals, int k, int whiten, float* out,
+                       hipStream_t s);
+
 // mfmaloop.hip: the bare LDS-read + f16x3 MFMA loop (sustained ceiling of the convolution inner loop on this device; diagnostic)
 size_t mfma_loop_workspace_bytes();
 double mfma_loop_flops(int iters);

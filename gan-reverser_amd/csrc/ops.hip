@@ -517,6 +517,37 @@ extern "C" int gr_cluster_faces_dev(gr_ctx* c, const float* table, int64_t n_row
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ principal axes of a device table (pca.hip)
+extern "C" int gr_pca_dev(gr_ctx* c, const float* x, int64_t n, int d, double* mean, double* cov, double* eigvals, float* axes, int32_t* info) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !mean || !eigvals || !axes || !info) return fail(c, GR_ERR_INVALID, "gr_pca_dev: null pointer");
+  if (n <= 0 || d <= 0) return fail(c, GR_ERR_INVALID, "gr_pca_dev: n %lld and d %d must be positive", (long long)n, d);
+  if (n < 2) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: n %lld: at least 2 rows", (long long)n);
+  if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: n %lld: fewer than 2^31 rows", (long long)n);
+  if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: d %d: at most 256 columns", d);
+  Staging s(c);
+  auto scratch = s.reserve<char>(pca_workspace_bytes(n, d));
+  TRY(s.grow());
+  if (launch_pca(x, n, d, mean, cov, eigvals, axes, info, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_pca_project_dev(gr_ctx* c, const float* x, int64_t n, int d, const double* mean, const float* axes, const double* eigvals, int k, int whiten,
+                                  float* out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !mean || !axes || !out || (whiten && !eigvals)) return fail(c, GR_ERR_INVALID, "gr_pca_project_dev: null pointer");
+  if (n <= 0 || d <= 0 || k <= 0) return fail(c, GR_ERR_INVALID, "gr_pca_project_dev: n %lld, d %d and k %d must be positive", (long long)n, d, k);
+  if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_project_dev: n %lld: fewer than 2^31 rows", (long long)n);
+  if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_project_dev: d %d: at most 256 columns", d);
+  if (k > d) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_project_dev: k %d: at most d = %d axes", k, d);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int r = launch_pca_project(x, n, d, mean, axes, eigvals, k, whiten, out, c->stream);
+  if (r == 2) return fail(c, GR_ERR_HIP, "gr_pca_project_dev: the device refuses the projection kernel's LDS (d %d)", d);
+  if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_project_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ apply_r.lua:355-372 detectAnomalies' distance
 extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
   if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;

@@ -192,6 +192,8 @@ _SIGS = {
     "gr_cluster_members_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gr_cluster_faces_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P]),
     "gr_cluster_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gr_pca_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
+    "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "gr_malloc": (C.c_int, [_P, C.c_int64, C.POINTER(_P)]),
     "gr_free": (C.c_int, [_P, _P]),
     "gr_memcpy_h2d": (C.c_int, [_P, _P, _P, C.c_int64]),
@@ -603,6 +605,21 @@ class Context:
         """gr_cluster_faces_dev (apply_r.lua:233-243): out_dev [k x d] = the average faces of all clusters (rows_dev int64 [k x m], kept_dev int32 [k])"""
         self.check(self.lib.gr_cluster_faces_dev(self.h, _ptr(table_dev), int(n_rows), int(d), _ptr(rows_dev), _ptr(kept_dev), int(k), int(m), _ptr(out_dev)),
                    "gr_cluster_faces_dev")
+
+    PCA_MAX_D = 256                  # gr_pca_dev / gr_pca_project_dev: columns at most (include/ganrev.h)
+
+    def pca_dev(self, x_dev, n, d, mean_dev, cov_dev, eigvals_dev, axes_dev, info_dev):
+        """gr_pca_dev (2 <= n < 2^31, d <= 256): the principal axes of the device table [n x d] -> mean_dev [d] doubles, cov_dev [d x d] doubles
+        or None, eigvals_dev [d] doubles (descending), axes_dev [d x d] floats (row = unit axis), info_dev [2] int32 (sweeps, converged).
+        Enqueued on the context's stream."""
+        self.check(self.lib.gr_pca_dev(self.h, _ptr(x_dev), int(n), int(d), _ptr(mean_dev), _ptr(cov_dev), _ptr(eigvals_dev), _ptr(axes_dev),
+                                       _ptr(info_dev)), "gr_pca_dev")
+
+    def pca_project_dev(self, x_dev, n, d, mean_dev, axes_dev, eigvals_dev, k, whiten, out_dev):
+        """gr_pca_project_dev: out_dev [n x k] = (x - mean) . axes[0 .. k)^T, column a times 1 / sqrt(eigval_a) when whiten (0 for eigval_a <= 0;
+        eigvals_dev may be None otherwise)"""
+        self.check(self.lib.gr_pca_project_dev(self.h, _ptr(x_dev), int(n), int(d), _ptr(mean_dev), _ptr(axes_dev), _ptr(eigvals_dev), int(k),
+                                               int(bool(whiten)), _ptr(out_dev)), "gr_pca_project_dev")
 
     # ---- data parallel
     def comm_unique_id(self):

@@ -290,6 +290,36 @@ def createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, at
     return centroids, counts, clusters, faces
 
 
+def principalAxesOfTable(ctx, attributes, K, whitened=False):
+    """--pca K: the principal axes of the attribute table (ganrev.pca) - a DeviceTensor [N x nd] where gr_embed_dev left it, or the host table,
+    uploaded to a temporary buffer first as clusterHostTable does.  -> (PrincipalAxes, which the caller closes; the [N x K] coordinates along
+    the first K axes on the host, not whitened; the whitened [N x K] table as a DeviceTensor the caller frees, or None)"""
+    from . import pca as P
+    on_device = isinstance(attributes, DeviceTensor)
+    N = attributes.shape[0]
+    d = (attributes.size if on_device else int(np.prod(attributes.shape))) // N
+    table = attributes.ptr if on_device else ctx.upload(np.ascontiguousarray(attributes, np.float32))
+    axes = None
+    try:
+        axes = P.principalAxes(ctx, table, N, d)
+        plain = P.project(ctx, axes, table, N, K, whiten=False)
+        try:
+            coords = plain.numpy()
+        finally:
+            plain.free()
+        white = P.project(ctx, axes, table, N, K, whiten=True) if whitened else None
+        if not on_device:
+            ctx.synchronize()                                                 # the projection reads the temporary table
+        return axes, coords, white
+    except Exception:
+        if axes is not None:
+            axes.close()
+        raise
+    finally:
+        if not on_device:
+            ctx.free(table)
+
+
 def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colorSpace=None, by_attr=None, by_pix=None):
     """The analysis of apply_r.lua:158-191 on the device-resident tables (`images` [N x C x H x W] and `attributesFixer` [N x nd] as
     DeviceTensors, `attributes` [N x nd] a DeviceTensor or the host table): the clusters (createClusterImagesDev), the fixed faces and the
@@ -347,6 +377,11 @@ def clusterOptions(OPT):
     return (getattr(OPT, "nbClusters", 20), getattr(OPT, "nbIterations", 15), getattr(OPT, "nbMaxPerCluster", 64 + 7), bool(getattr(OPT, "closest", False)))
 
 
+def pcaOptions(OPT):
+    """(K, pcaSpace) of a run: --pca K and --pcaSpace when given, else (0, False): off"""
+    return int(getattr(OPT, "pca", 0)), bool(getattr(OPT, "pcaSpace", False))
+
+
 def parse(argv=None):
     import argparse
     p = argparse.ArgumentParser(description="apply_r.lua options (apply_r.lua:13-23)")
@@ -369,6 +404,9 @@ def parse(argv=None):
     p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
     p.add_argument("--refine", type=int, default=0, metavar="STEPS", help="refine the recovered noise through G: STEPS Adam steps per image on the MSE between G(z) and the image, starting at R's estimate (ganrev.refine; 0, the reference's behaviour: R's estimate is final)")
     p.add_argument("--refine_lr", type=float, default=0.01, help="Adam learning rate of --refine")
+    # the principal-axes options: absent from the namespace unless given, like the clustering options below - pcaOptions() supplies "off"
+    p.add_argument("--pca", type=int, default=argparse.SUPPRESS, metavar="K", help="principal axes of the recovered noise (ganrev.pca; K <= noiseDim): writes pca_mean, pca_eigenvalues, pca_axes [K x noiseDim] and pca_projection [nbImages x K] (.npy), and with --render variations_pca.png along the first K axes (0, the reference's behaviour: off)")
+    p.add_argument("--pcaSpace", action="store_true", default=argparse.SUPPRESS, help="with --pca K: the similarity search by attributes and the clustering run on the whitened [nbImages x K] projection instead of the attribute table")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
     p.add_argument("--nbIterations", type=int, default=argparse.SUPPRESS, help="k-means iterations (default 15, apply_r.lua:160)")
@@ -383,6 +421,13 @@ def parse(argv=None):
         p.error("--refine: a step count")
     if OPT.needles < 0:
         p.error("--needles: a file count")
+    nbAxes, pcaSpace = pcaOptions(OPT)
+    if nbAxes < 0:
+        p.error("--pca: an axis count")
+    if pcaSpace and not nbAxes:
+        p.error("--pcaSpace works on the projection: give --pca K")
+    if nbAxes and OPT.synthetic and nbAxes > int(OPT.synthetic.split("x")[3]):
+        p.error(f"--pca {nbAxes}: at most noiseDim = {OPT.synthetic.split('x')[3]} axes")
     nbClusters, nbIterations, nbMaxPerCluster, _ = clusterOptions(OPT)
     if not 1 <= nbClusters <= MAX_CLUSTERS:
         p.error(f"--nbClusters: 1 to {MAX_CLUSTERS}")
@@ -429,8 +474,11 @@ def run(OPT):
         dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
         MODEL_R = t7.load_checkpoint(OPT.R)["R"]                              # :92-94
         MODEL_R_FIXER = t7.load_checkpoint(OPT.R_fixer)["R"]                  # :101-103
+    nbAxes, pcaSpace = pcaOptions(OPT)
+    if nbAxes > nd:
+        raise L.GanrevError(f"--pca {nbAxes}: at most noiseDim = {nd} axes")
     reads = bool(OPT.needles or OPT.real)
-    if reads:                                                                 # --cacheDataset then keeps the files on the GPU
+    if reads:                                                                # --cacheDataset then keeps the files on the GPU
         DATASET = scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], ctx=ctx, reads=True)
         have = len(DATASET.paths if DATASET.paths is not None else DATASET.loadPaths())      # checked before anything else is allocated
         for count, what in ((OPT.nbImages if OPT.real else 0, "--nbImages"), (OPT.needles, "--needles")):
@@ -455,6 +503,35 @@ def run(OPT):
             dmG.close()
         return dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
                     loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
+
+    def pca_step(table):                                                      # --pca K over the attribute table (a DeviceTensor or the host array)
+        from . import pca as P
+        say("Principal axes of the recovered noise...")
+        axes, coords, white = principalAxesOfTable(ctx, table, nbAxes, pcaSpace)
+        try:
+            np.save(out("pca_mean.npy"), axes.mean); np.save(out("pca_eigenvalues.npy"), axes.eigenvalues)
+            np.save(out("pca_axes.npy"), axes.axes[:nbAxes]); np.save(out("pca_projection.npy"), coords)
+            summary["pca"] = dict(k=nbAxes, explained=[float(v) for v in axes.explained[:nbAxes]], sweeps=axes.sweeps, converged=axes.converged,
+                                  space="pca_whitened" if pcaSpace else "attributes")       # the table the search by attributes and the clusters read
+            if OPT.render:                                                    # variations.png's conventions, along the axes instead of the coordinates
+                from . import render
+                dz = DeviceTensor(ctx, (nbAxes * nbSteps, nd))
+                try:
+                    ctx.upload(P.axisVariations(axes, nbAxes, nbSteps, method), dz.ptr)
+                    walked = forwardBatchedDev(MODEL_G, dz, OPT.batchSize)
+                    try:
+                        render.variations_grid(walked, nbSteps, path=out("variations_pca.png"))
+                    finally:
+                        walked.free()
+                finally:
+                    dz.free()
+        except BaseException:
+            if white is not None:
+                white.free()
+            raise
+        finally:
+            axes.close()
+        return white
     for m in (MODEL_G, MODEL_R, MODEL_R_FIXER):
         m._ctx = ctx
         m.evaluate()
@@ -487,7 +564,12 @@ def run(OPT):
     if OPT.host:
         noise = dn.numpy(); dn.free()
         images, attributes, attributesFixer = embed(MODEL_G, MODEL_R, noise, OPT.batchSize, MODEL_R_FIXER)
-        by_attr, by_pix = createSimilaritySearch(5, 100, images, attributes) if N >= 500 else (None, None)
+        dw, space = None, attributes                                          # `space`: the table the search by attributes and the clusters read
+        if nbAxes:
+            white = pca_step(attributes)
+            if white is not None:                                             # --pcaSpace: the whitened projection, on the host like the table it stands for
+                space = white.numpy(); white.free()
+        by_attr, by_pix = createSimilaritySearch(5, 100, images, space) if N >= 500 else (None, None)
         if OPT.render:                                                        # the same pictures from uploaded tables
             di, df = DeviceTensor(ctx, images.shape), DeviceTensor(ctx, attributesFixer.shape)
             ctx.upload(images, di.ptr); ctx.upload(attributesFixer, df.ptr)
@@ -510,7 +592,9 @@ def run(OPT):
                 again = forwardBatchedDev(MODEL_G, da.rows(0, k), OPT.batchSize)
                 render.fixed_pairs_grid(di, again, k, colorSpace, path=out("refined_pairs.png"))      # image next to G(refined z)
                 again.free()
-        by_attr, by_pix = createSimilaritySearchDev(5, 100, da, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
+        dw = pca_step(da) if nbAxes else None                                # after the refinement, on the table it left, like the search and the clusters
+        ds = dw if dw is not None else da                                     # --pcaSpace: both read the whitened projection, d = K
+        by_attr, by_pix = createSimilaritySearchDev(5, 100, ds, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
         if OPT.needles:
             # search by example: the needles are images from outside the corpus - the dataset's first files - embedded like the corpus
             # (R, then the same refinement against themselves) and searched in the tables where they lie
@@ -531,7 +615,7 @@ def run(OPT):
                         render.similar_example_grid(ni, i, di, nb_attr[i], colorSpace, path=out("needle_attributes_%02d.png" % (i + 1)))
                         render.similar_example_grid(ni, i, di, nb_pix[i], colorSpace, path=out("needle_pixelwise_%02d.png" % (i + 1)))
             except BaseException:
-                for t in (di, da, df, dn):                                    # the corpus tables go with a failed needle step
+                for t in (di, da, df, dn, dw):                                # the corpus tables go with a failed needle step
                     if t is not None:
                         t.free()
                 raise
@@ -540,31 +624,35 @@ def run(OPT):
                     if t is not None:
                         t.free()
         attributes, attributesFixer = da.numpy(), df.numpy()
+        space = dw.numpy() if dw is not None else attributes
         if dn is not None:
             dn.free()
         if not OPT.resident:
             images = di.numpy()
             if not OPT.render:
-                for t in (di, da, df):
+                for t in (di, da, df) + ((dw,) if dw is not None else ()):
                     t.free()
+                dw = None
     ctx.synchronize()
     summary["embed_and_search_seconds"] = round(time.perf_counter() - t0, 4)
     rendered = None
     if OPT.render:
         say("Rendering...")                                                   # from di / df, before they are freed
-        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, attributes if OPT.host else da, df, by_attr, by_pix)
+        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, space if OPT.host else ds, df, by_attr, by_pix)
     elif OPT.resident:
         say("Analysing on the device...")
-        rendered = analyseDev(OPT, MODEL_G, di, da, df)
+        rendered = analyseDev(OPT, MODEL_G, di, ds, df)
     if rendered:
         for t in (di, df) if OPT.host else (di, da, df):
             t.free()
+        if dw is not None:
+            dw.free()
     np.save(out("attributes.npy"), attributes); np.save(out("attributes_fixer.npy"), attributesFixer)
     if by_attr is not None:
         np.save(out("similar_by_attributes.npy"), by_attr); np.save(out("similar_by_pixels.npy"), by_pix)
 
     say("Clustering...")                                                      # :158-162
-    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(*clusterOptions(OPT)[:3], images, attributes, seed=OPT.seed, closest=clusterOptions(OPT)[3])     # (20, 15, 64 + 7 unless asked otherwise)
+    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(*clusterOptions(OPT)[:3], images, space, seed=OPT.seed, closest=clusterOptions(OPT)[3])     # (20, 15, 64 + 7 unless asked otherwise)
     np.save(out("cluster_centroids.npy"), centroids); np.save(out("cluster_average_faces.npy"), np.stack(faces))
     summary["cluster_sizes"] = [len(c) for c in clusters]; summary["cluster_total_counts"] = [float(v) for v in counts]
     summary.update(zip(("nbClusters", "nbIterations", "nbMaxPerCluster", "closest"), clusterOptions(OPT)))

@@ -84,6 +84,9 @@ int gr_cluster_members_dev(gr_ctx*, const int32_t* labels_dev, const float* sims
 int gr_cluster_faces_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_dev, const int32_t* kept_dev, int k, int m, float* out_dev);     /* apply_r.lua:233-243 */
 int gr_cluster_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float* cent_dev, int take_min, int m, float* totalcounts_dev,
                    int32_t* labels_dev, float* sims_dev, int64_t* rows_out_dev, float* sims_out_dev, int32_t* kept_out_dev, int32_t* sizes_out_dev);     /* apply_r.lua:198-227, k <= 4096 */
+int gr_pca_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double* mean_dev, double* cov_dev, double* eigvals_dev, float* axes_dev, int32_t* info_dev);     /* principal axes, d <= 256 */
+int gr_pca_project_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const double* mean_dev, const float* axes_dev, const double* eigvals_dev,
+                       int k, int whiten, float* out_dev);
 int gr_progress_grid_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int channels, int h, int w, int from_space,
                          const int64_t* rows_host, int n_show, int grid_h, int grid_w, int epoch, float* grid_dev, uint8_t* u8_dev);     /* imagesToGridTensor, utils/nn_utils.lua:490-548 */
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);

@@ -477,6 +477,41 @@ int gr_cluster_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int
                    float* totalcounts_dev /*nullable*/, int32_t* labels_dev, float* sims_dev, int64_t* rows_out_dev, float* sims_out_dev,
                    int32_t* kept_out_dev, int32_t* sizes_out_dev);
 
+/* ---- principal axes of a device table (csrc/pca.hip; new: the reference has no counterpart) ----
+ * gr_pca_dev: x_dev [n x d] floats -> mean_dev [d] doubles, cov_dev [d x d] doubles (nullable), eigvals_dev [d] doubles (descending),
+ * axes_dev [d x d] floats (row a = unit axis a), info_dev [2] int32 (sweeps used, converged flag).  Every pointer is device memory; the work is
+ * enqueued on the ctx stream and the call returns without waiting for it; scratch comes from the context.  No floating-point atomics: the result
+ * is a function of the inputs alone and does not depend on the device's CU count.
+ * Mean (fp64).  Per block of 512 consecutive rows the rows are added in row order from +0.0; the block partials are added in block order from
+ * +0.0; one division by n.
+ * Covariance, two-pass and centred: C = 1 / (n - 1) sum_r c_r c_r^T with c_rt = (float)((double)x_rt - mean_t), one rounding to fp32.  Per block of
+ * 512 rows and element (i, j) one sequential fp32 chain in row order from +0.0, acc = acc + c_ri * c_rj, multiply and add rounded separately
+ * (chain length L = 512).  P = 128 partial matrices, a constant of the library: with B = ceil(n / 512) blocks, partial p adds the chains of the
+ * blocks floor(p B / P) .. floor((p + 1) B / P) - 1 in block order in fp64 from +0.0 (an empty range leaves +0.0); C_ij = (the partials in order
+ * p = 0 .. P - 1 from +0.0, fp64) / (double)(n - 1).  Elements with i <= j are computed and written to [i][j] and [j][i]: both triangles carry the
+ * same bits.
+ * Eigen-decomposition: cyclic Jacobi in fp64 in ONE workgroup on C, round-robin (circle method) ordering: with m = d + (d & 1) players, round
+ * r = 0 .. m - 2 of a sweep rotates the pairs (m - 1, r) and ((r + k) mod (m - 1), (r - k) mod (m - 1)), k = 1 .. m / 2 - 1, all at once (a pair
+ * with player d, for odd d, has a bye).  Rotation of the pair (p, q) as listed: tau = (a_qq - a_pp) / (2 a_pq), t = sgn(tau) / (|tau| + sqrt(1 + tau^2)) (sgn(0) = 1),
+ * c = 1 / sqrt(1 + t^2), s = t c; a pair whose a_pq is exactly 0 is skipped (a constant column or a diagonal matrix never divides 0 by 0).
+ * Stop: off(A)_F^2 <= tau_stop^2 ||C||_F^2 with tau_stop = 2^-46, tested before every sweep (a diagonal C: 0 sweeps), and after at most 30
+ * sweeps - then info[1] = 0 and the call still returns GR_OK: the caller decides.  Eigenvalues are the diagonal as computed (a rank-deficient
+ * table may give -tiny), ordered descending, ties by ascending column of the final diagonal; axis a is the matching column of V rounded to fp32
+ * and signed so that its largest-magnitude fp32 component, the first one among equals, is positive.
+ * gr_pca_project_dev: out_dev [n x k] floats, out_ra = sum_t c_rt axes[a][t] for a < k: c_rt as above, per (row, axis) one sequential fp32 chain in
+ * column order from +0.0, acc = acc + c_rt * axes[a][t], multiply and add rounded separately.  whiten != 0: column a becomes
+ * (float)((double)acc * (1 / sqrt(eigvals[a]))), and 0 where eigvals[a] <= 0 (or NaN).  eigvals_dev may be null when whiten == 0.  16-byte loads
+ * when x_dev is 16-byte aligned.
+ * Limits: gr_pca_dev 2 <= n < 2^31, 1 <= d <= 256; gr_pca_project_dev 1 <= n < 2^31, 1 <= k <= d <= 256; outside them GR_ERR_UNSUPPORTED with a
+ * gr_last_error text that names the value; null pointers (cov_dev excepted) or non-positive n, d, k GR_ERR_INVALID.  The context stays usable
+ * after either.  A table whose squared covariances overflow fp64 is outside the contract.
+ * Scratch: ceil(n / 512) x d doubles (the mean's block partials) + (P + 2) x d^2 doubles (the partial matrices, A and V): at most 68 MB + n d / 64
+ * bytes, whatever the device. */
+int gr_pca_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, double* mean_dev, double* cov_dev /*nullable*/, double* eigvals_dev, float* axes_dev,
+               int32_t* info_dev);
+int gr_pca_project_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, const double* mean_dev, const float* axes_dev, const double* eigvals_dev /*nullable unless whiten*/,
+                       int k, int whiten, float* out_dev);
+
 /* ---- device memory helpers for hosts without a tensor library (LuaJIT FFI, ctypes) ---- */
 int gr_malloc(gr_ctx* ctx, int64_t bytes, void** out_dev);
 int gr_free(gr_ctx* ctx, void* dev);
