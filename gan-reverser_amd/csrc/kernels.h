@@ -560,6 +560,19 @@ int launch_pca(const float* x, long n, int d, double* mean, double* cov, double*
 int launch_pca_project(const float* x, long n, int d, const double* mean, const float* axes, const double* eigvals, int k, int whiten, float* out,
                        hipStream_t s);
 
+// ---------------------------------------------------------------- exact t-SNE of a device table (tsne.hip; gr_tsne_*_dev, gr_map_cells_dev)
+// Every pointer is device memory.  The launchers return 1 outside their limits (n <= 16384; affinities n >= 4, d >= 1; cells: grid sides 1 .. 1024),
+// launch_tsne_affinities 2 when the device refuses a memset.  One workspace of tsne_iter_workspace_bytes serves gradient, KL and update.
+size_t tsne_affinities_workspace_bytes(int n, int d);
+size_t tsne_iter_workspace_bytes(int n);
+size_t map_cells_workspace_bytes(int cells);
+int launch_tsne_affinities(const float* x, int n, int d, double perplexity, float* p, double* beta /*nullable*/, int* info, void* workspace, hipStream_t s);
+int launch_tsne_gradient(const float* p, const float* y, int n, float exaggeration, float* grad, double* z /*nullable*/, void* workspace, hipStream_t s);
+int launch_tsne_kl(const float* p, const float* y, int n, double* kl, void* workspace, hipStream_t s);
+int launch_tsne_update(float* y, const float* grad, float* inc, float* gains, int n, float eta, float momentum, float min_gain, void* workspace,
+                       hipStream_t s);
+int launch_map_cells(const float* y, long n, int gh, int gw, long* rows_out, int* counts /*nullable*/, void* workspace, hipStream_t s);
+
 // mfmaloop.hip: the bare LDS-read + f16x3 MFMA loop (sustained ceiling of the convolution inner loop on this device; diagnostic)
 size_t mfma_loop_workspace_bytes();
 double mfma_loop_flops(int iters);

@@ -548,6 +548,99 @@ extern "C" int gr_pca_project_dev(gr_ctx* c, const float* x, int64_t n, int d, c
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ exact t-SNE of a device table (tsne.hip)
+static int tsne_n_check(gr_ctx* c, const char* who, int64_t n, int64_t least) {
+  if (n < least) return fail(c, GR_ERR_INVALID, "%s: n %lld: at least %lld rows", who, (long long)n, (long long)least);
+  if (n > GR_TSNE_MAX_N) return fail(c, GR_ERR_UNSUPPORTED, "%s: n %lld: at most GR_TSNE_MAX_N = %d rows", who, (long long)n, GR_TSNE_MAX_N);
+  return GR_OK;
+}
+extern "C" int gr_tsne_affinities_dev(gr_ctx* c, const float* x, int64_t n, int d, double perplexity, float* p, double* beta, int32_t* info) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !p || !info) return fail(c, GR_ERR_INVALID, "gr_tsne_affinities_dev: null pointer");
+  TRY(tsne_n_check(c, "gr_tsne_affinities_dev", n, 4));
+  if (d < 1) return fail(c, GR_ERR_INVALID, "gr_tsne_affinities_dev: d %d must be positive", d);
+  if (!(perplexity >= 1.0 && perplexity <= (double)(n - 1) / 3.0))
+    return fail(c, GR_ERR_INVALID, "gr_tsne_affinities_dev: perplexity %g: 1 to (n - 1) / 3 = %g", perplexity, (double)(n - 1) / 3.0);
+  Staging s(c);
+  auto scratch = s.reserve<char>(tsne_affinities_workspace_bytes((int)n, d));
+  TRY(s.grow());
+  const int r = launch_tsne_affinities(x, (int)n, d, perplexity, p, beta, info, s.ptr(scratch), c->stream);
+  if (r == 2) return fail(c, GR_ERR_HIP, "gr_tsne_affinities_dev: hipMemsetAsync failed");
+  if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_affinities_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_tsne_gradient_dev(gr_ctx* c, const float* p, const float* y, int64_t n, float exaggeration, float* grad, double* z) {
+  if (!c) return GR_ERR_INVALID;
+  if (!p || !y || !grad) return fail(c, GR_ERR_INVALID, "gr_tsne_gradient_dev: null pointer");
+  TRY(tsne_n_check(c, "gr_tsne_gradient_dev", n, 1));
+  Staging s(c);
+  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
+  TRY(s.grow());
+  if (launch_tsne_gradient(p, y, (int)n, exaggeration, grad, z, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_gradient_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_tsne_update_dev(gr_ctx* c, float* y, const float* grad, float* inc, float* gains, int64_t n, float eta, float momentum, float min_gain) {
+  if (!c) return GR_ERR_INVALID;
+  if (!y || !grad || !inc || !gains) return fail(c, GR_ERR_INVALID, "gr_tsne_update_dev: null pointer");
+  TRY(tsne_n_check(c, "gr_tsne_update_dev", n, 1));
+  Staging s(c);
+  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
+  TRY(s.grow());
+  if (launch_tsne_update(y, grad, inc, gains, (int)n, eta, momentum, min_gain, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_update_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_tsne_kl_dev(gr_ctx* c, const float* p, const float* y, int64_t n, double* kl) {
+  if (!c) return GR_ERR_INVALID;
+  if (!p || !y || !kl) return fail(c, GR_ERR_INVALID, "gr_tsne_kl_dev: null pointer");
+  TRY(tsne_n_check(c, "gr_tsne_kl_dev", n, 1));
+  Staging s(c);
+  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
+  TRY(s.grow());
+  if (launch_tsne_kl(p, y, (int)n, kl, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_kl_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_tsne_run_dev(gr_ctx* c, const float* p, int64_t n, const gr_tsne_config* cfg, float* y, float* inc, float* gains, int first_iter, int iters,
+                               double* kl, int kl_every) {
+  if (!c) return GR_ERR_INVALID;
+  if (!p || !cfg || !y || !inc || !gains) return fail(c, GR_ERR_INVALID, "gr_tsne_run_dev: null pointer");
+  TRY(tsne_n_check(c, "gr_tsne_run_dev", n, 1));
+  if (first_iter < 0 || iters < 0 || kl_every < 0) return fail(c, GR_ERR_INVALID, "gr_tsne_run_dev: first_iter %d, iters %d and kl_every %d must not be negative", first_iter, iters, kl_every);
+  if (first_iter > 0x7FFFFFFF - iters) return fail(c, GR_ERR_INVALID, "gr_tsne_run_dev: first_iter %d + iters %d: below 2^31", first_iter, iters);
+  Staging s(c);
+  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
+  auto grad = s.reserve<float>(2 * (size_t)n);
+  TRY(s.grow());
+  for (int t = first_iter; t < first_iter + iters; ++t) {                 // the public gradient and update launches, back to back on the stream
+    const float ex = t < cfg->stop_lying_iter ? cfg->exaggeration : 1.0f, mom = t < cfg->mom_switch_iter ? cfg->momentum0 : cfg->momentum1;
+    if (launch_tsne_gradient(p, y, (int)n, ex, s.ptr(grad), nullptr, s.ptr(scratch), c->stream) ||
+        launch_tsne_update(y, s.ptr(grad), inc, gains, (int)n, cfg->eta, mom, cfg->min_gain, s.ptr(scratch), c->stream))
+      return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_run_dev: unsupported size");
+    if (kl && kl_every && (t + 1) % kl_every == 0 && launch_tsne_kl(p, y, (int)n, kl + ((t + 1) / kl_every - 1), s.ptr(scratch), c->stream))
+      return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_run_dev: unsupported size");
+    LAUNCHCHK(c);
+  }
+  return GR_OK;
+}
+extern "C" int gr_map_cells_dev(gr_ctx* c, const float* y, int64_t n, int grid_h, int grid_w, int64_t* rows_out, int32_t* counts) {
+  if (!c) return GR_ERR_INVALID;
+  if (!y || !rows_out) return fail(c, GR_ERR_INVALID, "gr_map_cells_dev: null pointer");
+  if (n < 1) return fail(c, GR_ERR_INVALID, "gr_map_cells_dev: n %lld must be positive", (long long)n);
+  if (grid_h < 1 || grid_w < 1) return fail(c, GR_ERR_INVALID, "gr_map_cells_dev: grid %d x %d must be positive", grid_h, grid_w);
+  if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_map_cells_dev: n %lld: fewer than 2^31 rows", (long long)n);
+  if (grid_h > 1024 || grid_w > 1024) return fail(c, GR_ERR_UNSUPPORTED, "gr_map_cells_dev: grid %d x %d: at most 1024 cells a side", grid_h, grid_w);
+  Staging s(c);
+  auto scratch = s.reserve<char>(map_cells_workspace_bytes(grid_h * grid_w));
+  TRY(s.grow());
+  if (launch_map_cells(y, (long)n, grid_h, grid_w, reinterpret_cast<long*>(rows_out), counts, s.ptr(scratch), c->stream))
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_map_cells_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ apply_r.lua:355-372 detectAnomalies' distance
 extern "C" int gr_l2_distance_rows_host(gr_ctx* c, const float* a, const float* b, int64_t n, int64_t d, double* out) {
   if (!c || !a || !b || !out || n <= 0 || d <= 0) return GR_ERR_INVALID;

@@ -94,6 +94,15 @@ class OptimConfig(C.Structure):
         return (self.method != GR_OPT_SGD or self.momentum != 0, self.method in (GR_OPT_ADADELTA, GR_OPT_ADAMAX))
 
 
+class TsneConfig(C.Structure):
+    """gr_tsne_config: the schedule of gr_tsne_run_dev (the defaults of van der Maaten's reference code; eta is the caller's)"""
+    _fields_ = [("exaggeration", C.c_float), ("stop_lying_iter", C.c_int32), ("momentum0", C.c_float), ("momentum1", C.c_float),
+                ("mom_switch_iter", C.c_int32), ("eta", C.c_float), ("min_gain", C.c_float)]
+
+    def __init__(self, eta, exaggeration=12.0, stop_lying_iter=250, momentum0=0.5, momentum1=0.8, mom_switch_iter=250, min_gain=0.01):
+        super().__init__(exaggeration, int(stop_lying_iter), momentum0, momentum1, int(mom_switch_iter), eta, min_gain)
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _SIGS = {
@@ -194,6 +203,12 @@ _SIGS = {
     "gr_cluster_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gr_pca_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "gr_tsne_affinities_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P]),
+    "gr_tsne_gradient_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, _P, _P]),
+    "gr_tsne_update_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float]),
+    "gr_tsne_kl_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "gr_tsne_run_dev": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "gr_map_cells_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "gr_malloc": (C.c_int, [_P, C.c_int64, C.POINTER(_P)]),
     "gr_free": (C.c_int, [_P, _P]),
     "gr_memcpy_h2d": (C.c_int, [_P, _P, _P, C.c_int64]),
@@ -620,6 +635,41 @@ class Context:
         eigvals_dev may be None otherwise)"""
         self.check(self.lib.gr_pca_project_dev(self.h, _ptr(x_dev), int(n), int(d), _ptr(mean_dev), _ptr(axes_dev), _ptr(eigvals_dev), int(k),
                                                int(bool(whiten)), _ptr(out_dev)), "gr_pca_project_dev")
+
+    TSNE_MAX_N = 16384               # GR_TSNE_MAX_N: rows of a map at most (include/ganrev.h)
+
+    def tsne_affinities_dev(self, x_dev, n, d, perplexity, p_dev, beta_dev, info_dev):
+        """gr_tsne_affinities_dev (4 <= n <= 16384, 1 <= perplexity <= (n - 1) / 3): the joint probabilities of the device table [n x d] ->
+        p_dev [n x n] floats (symmetric, zero diagonal), beta_dev [n] doubles or None, info_dev [2] int32 (most updates of beta a row needed,
+        rows that hit the cap of 50).  Enqueued on the context's stream."""
+        self.check(self.lib.gr_tsne_affinities_dev(self.h, _ptr(x_dev), int(n), int(d), float(perplexity), _ptr(p_dev), _ptr(beta_dev), _ptr(info_dev)),
+                   "gr_tsne_affinities_dev")
+
+    def tsne_gradient_dev(self, p_dev, y_dev, n, exaggeration, grad_dev, z_dev=None):
+        """gr_tsne_gradient_dev: grad_dev [n x 2] = 4 (e sum_j p w (y_i - y_j) - sum_j w^2 (y_i - y_j) / Z); z_dev [1] double or None"""
+        self.check(self.lib.gr_tsne_gradient_dev(self.h, _ptr(p_dev), _ptr(y_dev), int(n), float(exaggeration), _ptr(grad_dev), _ptr(z_dev)),
+                   "gr_tsne_gradient_dev")
+
+    def tsne_update_dev(self, y_dev, grad_dev, inc_dev, gains_dev, n, eta, momentum, min_gain=0.01):
+        """gr_tsne_update_dev: the delta-bar-delta step on y, inc, gains [n x 2] in place, then y minus its column mean"""
+        self.check(self.lib.gr_tsne_update_dev(self.h, _ptr(y_dev), _ptr(grad_dev), _ptr(inc_dev), _ptr(gains_dev), int(n), float(eta), float(momentum),
+                                               float(min_gain)), "gr_tsne_update_dev")
+
+    def tsne_kl_dev(self, p_dev, y_dev, n, kl_dev):
+        """gr_tsne_kl_dev: kl_dev [1] double = sum_{p > 0} p log(p Z / w)"""
+        self.check(self.lib.gr_tsne_kl_dev(self.h, _ptr(p_dev), _ptr(y_dev), int(n), _ptr(kl_dev)), "gr_tsne_kl_dev")
+
+    def tsne_run_dev(self, p_dev, n, config, y_dev, inc_dev, gains_dev, first_iter, iters, kl_dev=None, kl_every=0):
+        """gr_tsne_run_dev: iterations first_iter .. first_iter + iters - 1 of the schedule in `config` (a TsneConfig) without a host
+        synchronisation; the KL after every iteration t with (t + 1) % kl_every == 0 goes to kl_dev[(t + 1) / kl_every - 1]"""
+        self.check(self.lib.gr_tsne_run_dev(self.h, _ptr(p_dev), int(n), C.byref(config) if config is not None else None, _ptr(y_dev), _ptr(inc_dev),
+                                            _ptr(gains_dev), int(first_iter), int(iters), _ptr(kl_dev), int(kl_every)), "gr_tsne_run_dev")
+
+    def map_cells_dev(self, y_dev, n, grid_h, grid_w, rows_out_dev, counts_dev=None):
+        """gr_map_cells_dev: rows_out_dev [grid_h x grid_w] int64 = the row of y_dev [n x 2] nearest to each cell's centre (-1: empty),
+        counts_dev [grid_h x grid_w] int32 or None"""
+        self.check(self.lib.gr_map_cells_dev(self.h, _ptr(y_dev), int(n), int(grid_h), int(grid_w), _ptr(rows_out_dev), _ptr(counts_dev)),
+                   "gr_map_cells_dev")
 
     # ---- data parallel
     def comm_unique_id(self):

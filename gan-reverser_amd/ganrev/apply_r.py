@@ -382,6 +382,41 @@ def pcaOptions(OPT):
     return int(getattr(OPT, "pca", 0)), bool(getattr(OPT, "pcaSpace", False))
 
 
+MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
+
+
+def mapOptions(OPT):
+    """(rows, perplexity, iterations, grid) of a --map run: the options given, else min(nbImages, 10000), 30, 1000, 32; None without --map"""
+    if not getattr(OPT, "map", False):
+        return None
+    return (int(getattr(OPT, "mapRows", min(OPT.nbImages, 10000))), float(getattr(OPT, "mapPerplexity", 30.0)), int(getattr(OPT, "mapIterations", 1000)),
+            int(getattr(OPT, "mapGrid", 32)))
+
+
+def mapOfTable(ctx, table, M, perplexity, iterations, grid):
+    """--map: the t-SNE map (ganrev.tsne) of the first M rows of the attribute table - a DeviceTensor where gr_embed_dev left it, or the host
+    table, uploaded to a temporary buffer first as principalAxesOfTable does -> (y [M x 2], (iterations, KL values), cell rows [grid x grid],
+    the summary entry)"""
+    from . import tsne as T
+    on_device = isinstance(table, DeviceTensor)
+    N = table.shape[0]
+    d = (table.size if on_device else int(np.prod(table.shape))) // N
+    ptr = table.ptr if on_device else ctx.upload(np.ascontiguousarray(table[:M], np.float32))
+    try:
+        e = T.embed(ctx, ptr, M, d, perplexity=perplexity, iterations=iterations)
+        try:
+            cells = T.mapCells(ctx, e.y_dev, M, grid, grid)
+            entry = dict(rows=M, d=d, perplexity=perplexity, iterations=iterations, grid=grid, eta=e.eta, beta_updates_max=e.tries, beta_capped_rows=e.capped,
+                         kl_first=float(e.kl[0]), kl_last=float(e.kl[-1]), cells_filled=int((cells >= 0).sum()))
+            return e.y, (np.asarray(e.kl_iterations, np.int64), e.kl), cells, entry
+        finally:
+            e.close()
+    finally:
+        if not on_device:
+            ctx.synchronize()
+            ctx.free(ptr)
+
+
 def parse(argv=None):
     import argparse
     p = argparse.ArgumentParser(description="apply_r.lua options (apply_r.lua:13-23)")
@@ -407,6 +442,12 @@ def parse(argv=None):
     # the principal-axes options: absent from the namespace unless given, like the clustering options below - pcaOptions() supplies "off"
     p.add_argument("--pca", type=int, default=argparse.SUPPRESS, metavar="K", help="principal axes of the recovered noise (ganrev.pca; K <= noiseDim): writes pca_mean, pca_eigenvalues, pca_axes [K x noiseDim] and pca_projection [nbImages x K] (.npy), and with --render variations_pca.png along the first K axes (0, the reference's behaviour: off)")
     p.add_argument("--pcaSpace", action="store_true", default=argparse.SUPPRESS, help="with --pca K: the similarity search by attributes and the clustering run on the whitened [nbImages x K] projection instead of the attribute table")
+    # the map options: absent from the namespace unless given - mapOptions() supplies the defaults
+    p.add_argument("--map", action="store_true", default=argparse.SUPPRESS, help="a two-dimensional t-SNE map of the recovered noise, on the device (ganrev.tsne; of the whitened projection with --pcaSpace): writes map_y [mapRows x 2], map_kl and map_cells [mapGrid x mapGrid] (.npy), and with --render map.png, the faces drawn where they land, ringed by cluster")
+    p.add_argument("--mapRows", type=int, default=argparse.SUPPRESS, metavar="M", help=f"with --map: the first M rows are mapped (default min(nbImages, 10000); at most {MAP_MAX_ROWS}: the rows are independent draws, a prefix is a fair sample)")
+    p.add_argument("--mapPerplexity", type=float, default=argparse.SUPPRESS, help="with --map: the perplexity (default 30; at most (mapRows - 1) / 3)")
+    p.add_argument("--mapIterations", type=int, default=argparse.SUPPRESS, help="with --map: gradient iterations (default 1000)")
+    p.add_argument("--mapGrid", type=int, default=argparse.SUPPRESS, metavar="G", help="with --map: map_cells and map.png have G x G cells (default 32)")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
     p.add_argument("--nbIterations", type=int, default=argparse.SUPPRESS, help="k-means iterations (default 15, apply_r.lua:160)")
@@ -428,6 +469,22 @@ def parse(argv=None):
         p.error("--pcaSpace works on the projection: give --pca K")
     if nbAxes and OPT.synthetic and nbAxes > int(OPT.synthetic.split("x")[3]):
         p.error(f"--pca {nbAxes}: at most noiseDim = {OPT.synthetic.split('x')[3]} axes")
+    for name in ("mapRows", "mapPerplexity", "mapIterations", "mapGrid"):
+        if hasattr(OPT, name) and not getattr(OPT, "map", False):
+            p.error(f"--{name} belongs to the map: give --map")
+    mapped = mapOptions(OPT)
+    if mapped:
+        mapRows, mapPerplexity, mapIterations, mapGrid = mapped
+        if mapRows > MAP_MAX_ROWS:
+            p.error(f"--mapRows {mapRows}: at most {MAP_MAX_ROWS} rows (the joint matrix is mapRows x mapRows)")
+        if not 4 <= mapRows <= OPT.nbImages:
+            p.error(f"--mapRows {mapRows}: 4 to nbImages = {OPT.nbImages} rows")
+        if not 1 <= mapPerplexity <= (mapRows - 1) / 3:
+            p.error(f"--mapPerplexity {mapPerplexity:g}: 1 to (mapRows - 1) / 3 = {(mapRows - 1) / 3:g}")
+        if mapIterations < 0:
+            p.error("--mapIterations: an iteration count")
+        if not 1 <= mapGrid <= 1024:
+            p.error("--mapGrid: 1 to 1024 cells a side")
     nbClusters, nbIterations, nbMaxPerCluster, _ = clusterOptions(OPT)
     if not 1 <= nbClusters <= MAX_CLUSTERS:
         p.error(f"--nbClusters: 1 to {MAX_CLUSTERS}")
@@ -532,6 +589,15 @@ def run(OPT):
         finally:
             axes.close()
         return white
+
+    mapped, map_cells = mapOptions(OPT), None
+
+    def map_step(table):                                                      # --map over the table the search and the clusters read
+        say("Mapping the recovered noise...")
+        y, (kl_iterations, kl), cells, entry = mapOfTable(ctx, table, *mapped)
+        np.save(out("map_y.npy"), y); np.save(out("map_kl.npy"), np.stack([kl_iterations.astype(np.float64), kl], axis=1)); np.save(out("map_cells.npy"), cells)
+        summary["map"] = dict(entry, space="pca_whitened" if pcaSpace else "attributes")
+        return cells
     for m in (MODEL_G, MODEL_R, MODEL_R_FIXER):
         m._ctx = ctx
         m.evaluate()
@@ -569,6 +635,8 @@ def run(OPT):
             white = pca_step(attributes)
             if white is not None:                                             # --pcaSpace: the whitened projection, on the host like the table it stands for
                 space = white.numpy(); white.free()
+        if mapped:
+            map_cells = map_step(space)                                       # the host route uploads the table it has, as --pca does
         by_attr, by_pix = createSimilaritySearch(5, 100, images, space) if N >= 500 else (None, None)
         if OPT.render:                                                        # the same pictures from uploaded tables
             di, df = DeviceTensor(ctx, images.shape), DeviceTensor(ctx, attributesFixer.shape)
@@ -594,6 +662,8 @@ def run(OPT):
                 again.free()
         dw = pca_step(da) if nbAxes else None                                # after the refinement, on the table it left, like the search and the clusters
         ds = dw if dw is not None else da                                     # --pcaSpace: both read the whitened projection, d = K
+        if mapped:
+            map_cells = map_step(ds)
         by_attr, by_pix = createSimilaritySearchDev(5, 100, ds, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
         if OPT.needles:
             # search by example: the needles are images from outside the corpus - the dataset's first files - embedded like the corpus
@@ -642,6 +712,16 @@ def run(OPT):
     elif OPT.resident:
         say("Analysing on the device...")
         rendered = analyseDev(OPT, MODEL_G, di, ds, df)
+    if map_cells is not None and OPT.render:
+        # the faces where they land: one grid over the map's cells, from the image table where it lies; each tile's ring takes the colour of
+        # its row's cluster - the assignment of the clustering step (gr_cosine_assign on its final centroids) repeated for the rows shown
+        from . import render
+        shown = map_cells[map_cells >= 0]
+        labels = None
+        if clusterOptions(OPT)[0] <= NARROW_MAX_CLUSTERS:                     # (the palette has 12 colours: finer clusterings keep plain rings)
+            labels = np.full(N, -1, np.int64)
+            labels[shown] = ctx.cosine_assign(space[shown], rendered["clusters"][0], take_min=not clusterOptions(OPT)[3])[0]
+        render.map_grid(di, map_cells, colorSpace, labels=labels, path=out("map.png"))
     if rendered:
         for t in (di, df) if OPT.host else (di, da, df):
             t.free()

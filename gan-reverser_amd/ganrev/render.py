@@ -146,3 +146,32 @@ def neighbours_grid(images_dev, rows, table_dev, neighbour_rows, from_space="rgb
     if len(rows) != len(nb) or len(rows) % 2:
         raise ValueError(f"neighbours_grid: an even number of (image, neighbour) pairs, not {len(rows)} and {len(nb)}")
     return grid((images_dev, table_dev), np.stack([rows, nb], axis=1), len(rows) // 2, from_space, auto_range=True, path=path)
+
+
+# the ring colours of map_grid: cluster label j takes MAP_PALETTE[j % 12] (twelve hues at full saturation, ordered so that neighbours in the
+# list are far apart on the colour wheel); a tile without a label, and an empty cell, keep MAP_FIELD
+MAP_PALETTE = ((1.0, 0.0, 0.0), (0.0, 0.5, 1.0), (0.0, 0.8, 0.0), (1.0, 0.5, 0.0), (0.5, 0.0, 1.0), (0.0, 0.8, 0.8),
+               (1.0, 0.0, 0.5), (0.5, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.8, 0.0), (1.0, 0.0, 1.0), (0.0, 1.0, 0.5))
+MAP_FIELD = (0.0, 0.0, 0.0)
+
+
+def map_colours(cell_rows, labels=None):
+    """bg [cells x 3] of map_grid: MAP_PALETTE[label % 12] for a cell that shows a row with a label >= 0, MAP_FIELD for the others"""
+    rows = np.asarray(cell_rows, dtype=np.int64).reshape(-1)
+    bg = np.tile(np.float32(MAP_FIELD), (len(rows), 1))
+    if labels is not None:
+        labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+        shown = rows >= 0
+        lab = labels[rows[shown]]
+        colours = np.float32(MAP_PALETTE)[lab % len(MAP_PALETTE)]
+        colours[lab < 0] = np.float32(MAP_FIELD)
+        bg[shown] = colours
+    return bg
+
+
+def map_grid(images_dev, cell_rows, from_space="rgb", labels=None, path=None):
+    """The faces drawn where they land on a two-dimensional map (ganrev.tsne.mapCells): cell_rows [grid_h x grid_w] holds the row shown in each
+    cell, -1 for an empty one, which stays MAP_FIELD.  One launch; every tile has a 1-pixel ring, coloured by labels[row] (the cluster of the
+    row: map_colours) when labels are given."""
+    cell_rows = np.asarray(cell_rows, dtype=np.int64)
+    return grid(images_dev, cell_rows.reshape(-1), cell_rows.shape[1], from_space, margin=1, bg=map_colours(cell_rows, labels), path=path)

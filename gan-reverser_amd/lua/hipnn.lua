@@ -87,6 +87,14 @@ int gr_cluster_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int nit
 int gr_pca_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double* mean_dev, double* cov_dev, double* eigvals_dev, float* axes_dev, int32_t* info_dev);     /* principal axes, d <= 256 */
 int gr_pca_project_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const double* mean_dev, const float* axes_dev, const double* eigvals_dev,
                        int k, int whiten, float* out_dev);
+typedef struct { float exaggeration; int32_t stop_lying_iter; float momentum0, momentum1; int32_t mom_switch_iter; float eta, min_gain; } gr_tsne_config;
+int gr_tsne_affinities_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double perplexity, float* p_dev, double* beta_dev, int32_t* info_dev);     /* exact t-SNE, n <= 16384 */
+int gr_tsne_gradient_dev(gr_ctx*, const float* p_dev, const float* y_dev, int64_t n, float exaggeration, float* grad_dev, double* z_dev);
+int gr_tsne_update_dev(gr_ctx*, float* y_dev, const float* grad_dev, float* inc_dev, float* gains_dev, int64_t n, float eta, float momentum, float min_gain);
+int gr_tsne_kl_dev(gr_ctx*, const float* p_dev, const float* y_dev, int64_t n, double* kl_dev);
+int gr_tsne_run_dev(gr_ctx*, const float* p_dev, int64_t n, const gr_tsne_config* /*config*/, float* y_dev, float* inc_dev, float* gains_dev,
+                    int first_iter, int iters, double* kl_dev, int kl_every);
+int gr_map_cells_dev(gr_ctx*, const float* y_dev, int64_t n, int grid_h, int grid_w, int64_t* rows_out_dev, int32_t* counts_dev);
 int gr_progress_grid_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int channels, int h, int w, int from_space,
                          const int64_t* rows_host, int n_show, int grid_h, int grid_w, int epoch, float* grid_dev, uint8_t* u8_dev);     /* imagesToGridTensor, utils/nn_utils.lua:490-548 */
 int gr_net_forward_dev(gr_net*, const float* in_dev, int batch, float* out_dev);

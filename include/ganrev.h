@@ -512,6 +512,66 @@ int gr_pca_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, double* mean_d
 int gr_pca_project_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, const double* mean_dev, const float* axes_dev, const double* eigvals_dev /*nullable unless whiten*/,
                        int k, int whiten, float* out_dev);
 
+/* ---- exact (dense) t-SNE of a device table (csrc/tsne.hip; new: the reference has no counterpart) ----
+ * A two-dimensional, neighbour-preserving map of up to GR_TSNE_MAX_N rows: the joint matrix is n x n floats (1 GiB at the cap).  Barnes-Hut,
+ * FFT interpolation and sparse affinities are out of scope.  Every pointer is device memory; the work is enqueued on the ctx stream and the calls
+ * return without waiting for it; scratch comes from the context.  No floating-point atomics, nothing depends on the CU count: two runs give the
+ * same bits.
+ * gr_tsne_affinities_dev: x_dev [n x d] floats -> p_dev [n x n] floats, beta_dev [n] doubles (nullable), info_dev [2] int32 (the largest number
+ * of updates of beta any row needed; the rows that still missed the tolerance after 50).
+ *   D_ij = sum_k t_k^2 with t_k = (double)x_ik - (double)x_jk (exact), fp64, in column order from +0.0, multiply and add rounded separately; never
+ *   the |x|^2 + |y|^2 - 2xy form.  m_i = min_{j != i} D_ij, r_j = D_ij - m_i.
+ *   Per row the bisection of van der Maaten's reference code on beta, fp64: beta = 1; S = sum_{j != i} e_j and T = sum_{j != i} r_j e_j with
+ *   e_j = exp(-beta r_j); H = log(S) + beta T / S; stop when |H - log(perplexity)| <= 1e-5 or after 50 updates; H too large: the lower side is
+ *   beta, beta <- beta * 2 while the upper side is unbounded, else the midpoint; H too small: the mirror image with beta / 2.  Order of S and T:
+ *   thread t of 1024 adds its columns j = t, t + 1024, ... in that order from +0.0, then the tree t += t + o, o = 512 .. 1.
+ *   c_ij = (float)(e_j / S), c_ii = 0; p_ij = p_ji = (float)(((double)c_ij + (double)c_ji) / (double)(2 n)): symmetric bit for bit, zero diagonal.
+ *   Scratch: n d floats (the table transposed).
+ * gr_tsne_gradient_dev: p_dev, y_dev [n x 2] floats -> grad_dev [n x 2] floats, z_dev [1] double (nullable).  fp32, each operation rounded:
+ *   dx = y_i0 - y_j0, dy = y_i1 - y_j1, w_ij = 1 / (1 + (dx dx + dy dy)).  fp64 from there: A_i = sum_j ((double)p_ij w) (dx, dy),
+ *   B_i = sum_j (w w) (dx, dy), Z_i = sum_{j != i} w; Z = sum_i Z_i; g_i = (float)(4 (e A_i - B_i / Z)).  One pass reads P once.  Order of a row's
+ *   sums: a workgroup of 256 threads owns 8 consecutive rows; thread t adds its columns j = t, t + 256, ... in that order from +0.0; within a wave
+ *   v += v[lane + o] for o = 32, 16, 8, 4, 2, 1; then ((wave 0 + wave 1) + wave 2) + wave 3.  Order of Z: thread t of 256 adds Z_t, Z_(t + 256), ...
+ *   from +0.0, then the tree t += t + o, o = 128 .. 1.  Scratch: 5 n doubles.
+ * gr_tsne_update_dev: the delta-bar-delta rule of the reference implementation, elementwise fp32, each operation rounded, over y, inc, gains
+ *   [n x 2]: sign(v) = 1, -1 or 0 (for +-0); gains = sign(g) == sign(inc) ? gains * 0.8f : gains + 0.2f; gains = min_gain where it is below;
+ *   inc = momentum * inc - (eta * gains) * g; y = y + inc.  Then the column mean, fp64: per block of 512 consecutive rows the rows in row order
+ *   from +0.0, the block partials in block order from +0.0, one division by n; y = (float)((double)y - mean).
+ * gr_tsne_kl_dev: kl_dev [1] double = sum_{p_ij > 0} p_ij log(p_ij Z / w_ij), computed as sum_i K_i + log(Z) sum_i P_i with
+ *   K_i = sum_{p_ij > 0} (double)p_ij (log((double)p_ij) - log((double)w_ij)), P_i = sum_j p_ij, Z as above; w in fp32 as above, the rest fp64, the
+ *   orders of the gradient.  p_dev is the joint matrix as gr_tsne_affinities_dev wrote it (no exaggeration).
+ * gr_tsne_run_dev: iterations t = first_iter .. first_iter + iters - 1 on the stream without a host synchronisation, each the launches of
+ *   gr_tsne_gradient_dev with e = (t < stop_lying_iter ? exaggeration : 1) and gr_tsne_update_dev with (t < mom_switch_iter ? momentum0 :
+ *   momentum1), eta and min_gain: the same bits as those calls.  kl_every > 0 and kl_dev given: after every iteration t with (t + 1) % kl_every
+ *   == 0 the KL of gr_tsne_kl_dev goes to kl_dev[(t + 1) / kl_every - 1], so kl_dev holds (first_iter + iters) / kl_every doubles.
+ * gr_map_cells_dev: y_dev [n x 2] floats -> rows_out_dev [grid_h x grid_w] int64, the row nearest to each cell's centre (ties: the lower row;
+ *   an empty cell: -1), counts_dev [grid_h x grid_w] int32 (nullable) the rows per cell.  Bounding box lo, hi per axis by compare-selects; axis 0
+ *   runs along grid_w, axis 1 along grid_h, cell index = cell_1 * grid_w + cell_0.  fp32, each operation rounded: cell = min(G - 1,
+ *   (int)(((v - lo) / (hi - lo)) * (float)G)), 0 when hi == lo; centre = lo + ((float)cell + 0.5f) * ((hi - lo) / (float)G); distance =
+ *   da da + db db.  One 64-bit unsigned integer atomicMin per row on the key (distance bits << 32 | row): order-independent.  Scratch: 8 bytes per
+ *   cell.
+ * Limits: null pointers (the nullable ones excepted), n < 4 (affinities; n < 1 elsewhere), d < 1, a perplexity outside [1, (n - 1) / 3], a grid
+ * side < 1 or negative iteration counts: GR_ERR_INVALID.  n > GR_TSNE_MAX_N (gr_map_cells_dev: n >= 2^31, a grid side > 1024):
+ * GR_ERR_UNSUPPORTED with a gr_last_error text that names the value.  Nothing is launched and no output is touched in either case; the context
+ * stays usable. */
+#define GR_TSNE_MAX_N 16384
+typedef struct {
+  float exaggeration;        /* the factor on P during the early iterations (12) */
+  int32_t stop_lying_iter;   /* iterations t < stop_lying_iter run exaggerated (250) */
+  float momentum0, momentum1; /* before and from mom_switch_iter (0.5, 0.8) */
+  int32_t mom_switch_iter;   /* (250) */
+  float eta, min_gain;       /* learning rate; floor of the gains (0.01) */
+} gr_tsne_config;
+int gr_tsne_affinities_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, double perplexity, float* p_dev, double* beta_dev /*nullable*/,
+                           int32_t* info_dev);
+int gr_tsne_gradient_dev(gr_ctx* ctx, const float* p_dev, const float* y_dev, int64_t n, float exaggeration, float* grad_dev, double* z_dev /*nullable*/);
+int gr_tsne_update_dev(gr_ctx* ctx, float* y_dev, const float* grad_dev, float* inc_dev, float* gains_dev, int64_t n, float eta, float momentum,
+                       float min_gain);
+int gr_tsne_kl_dev(gr_ctx* ctx, const float* p_dev, const float* y_dev, int64_t n, double* kl_dev);
+int gr_tsne_run_dev(gr_ctx* ctx, const float* p_dev, int64_t n, const gr_tsne_config* /*config*/, float* y_dev, float* inc_dev, float* gains_dev,
+                    int first_iter, int iters, double* kl_dev /*nullable*/, int kl_every);
+int gr_map_cells_dev(gr_ctx* ctx, const float* y_dev, int64_t n, int grid_h, int grid_w, int64_t* rows_out_dev, int32_t* counts_dev /*nullable*/);
+
 /* ---- device memory helpers for hosts without a tensor library (LuaJIT FFI, ctypes) ---- */
 int gr_malloc(gr_ctx* ctx, int64_t bytes, void** out_dev);
 int gr_free(gr_ctx* ctx, void* dev);
