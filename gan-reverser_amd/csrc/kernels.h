@@ -547,6 +547,11 @@ bool cluster_takes_wide_route(int d, int k);
 size_t cluster_workspace_bytes(long n, int d, int k);
 int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent, int take_min, int m, float* c2, float* counts, float* totalcounts,
                    float* w32, int* labels, float* sims, long* rows_out, float* sims_out, int* kept_out, int* sizes_out, void* workspace, hipStream_t s);
+// gr_cluster_members_wide_dev: launch_cluster_members' lists by the wide route's grouping and selection kernels (the helper launch_cluster uses), for
+// 1 <= k <= 4096, 1 <= m <= 128, 1 <= n < 2^31 (returns 1 outside).
+size_t cluster_members_wide_workspace_bytes(long n, int k);
+int launch_cluster_members_wide(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
+                                void* workspace, hipStream_t s);
 // apply_r.lua:233-243 for every cluster at once: out[j] = launch_rows_mean of rows[j][0 .. kept[j]); entries outside [0, n_rows) are skipped
 void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows, const int* kept, int k, int m, float* out, hipStream_t s);
 
@@ -559,6 +564,14 @@ int launch_pca(const float* x, long n, int d, double* mean, double* cov, double*
 // 1 <= n < 2^31, 1 <= k <= d <= 256, 2 when the device refuses the kernel's LDS.
 int launch_pca_project(const float* x, long n, int d, const double* mean, const float* axes, const double* eigvals, int k, int whiten, float* out,
                        hipStream_t s);
+
+// ---------------------------------------------------------------- diagonal Gaussian mixture of a device table (mixture.hip; gr_mixture_dev)
+// niter x (E-step, M-step), then one E-step: w [k], mu / vars [k][d] floats in and out, loglik [niter + 1] doubles, labels / post / rowll [n] nullable:
+// all device; workspace from mixture_workspace_bytes.  Returns 1 outside 1 <= n < 2^31, 1 <= d, k <= 256, niter >= 0, var_floor > 0, and 2 when the
+// device refuses the kernels' LDS.
+size_t mixture_workspace_bytes(long n, int d, int k);
+int launch_mixture(const float* x, long n, int d, int k, int niter, float var_floor, float* w, float* mu, float* vars, double* loglik, int* labels,
+                   float* post, float* rowll, void* workspace, hipStream_t s);
 
 // ---------------------------------------------------------------- exact t-SNE of a device table (tsne.hip; gr_tsne_*_dev, gr_map_cells_dev)
 // Every pointer is device memory.  The launchers return 1 outside their limits (n <= 16384; affinities n >= 4, d >= 1; cells: grid sides 1 .. 1024),

@@ -752,9 +752,45 @@ size_t cluster_workspace_bytes(long n, int d, int k) {
   const size_t nblk = (size_t)((n + KM_RPB - 1) / KM_RPB), slots = nblk * wide_segs(k);
   return sizeof(double) * slots * d + sizeof(int) * (2 * slots + 2 * nblk + nblk * KM_RPB + (size_t)n) + 8 * a;
 }
-static int wide_group(const int* labels, long n, int k, int* order, int* seg_label, int* seg_start, int* nseg, int* nvalid, hipStream_t s) {
+// The wide route's member lists, shared by launch_cluster and gr_cluster_members_wide_dev (a mixture's labels and posteriors): the labels are grouped
+// block by block (wide_group_kernel), then every cluster walks its segments (cluster_members_wide_kernel).  The index: three ints per segment slot,
+// two per block, one per row of the padded table.
+struct WideIndex { int *seg_label, *seg_start, *nseg, *nvalid, *order; };
+static size_t wide_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
+static WideIndex wide_index_carve(char*& ws, long n, int k) {
+  const size_t nblk = (size_t)((n + KM_RPB - 1) / KM_RPB), slots = nblk * wide_segs(k);
+  auto take = [&](size_t bytes) { char* p = ws; ws += wide_align(bytes); return reinterpret_cast<int*>(p); };
+  WideIndex ix;
+  ix.seg_label = take(sizeof(int) * slots);
+  ix.seg_start = take(sizeof(int) * slots);
+  ix.nseg = take(sizeof(int) * nblk);
+  ix.nvalid = take(sizeof(int) * nblk);
+  ix.order = take(sizeof(int) * nblk * KM_RPB);
+  return ix;
+}
+static int wide_group(const int* labels, long n, int k, const WideIndex& ix, hipStream_t s) {
   KtScope kt("wide_group_kernel", 0.0, 8.0 * n, s);
-  hipLaunchKernelGGL(wide_group_kernel, dim3((unsigned)((n + KM_RPB - 1) / KM_RPB)), dim3(256), 0, s, labels, n, k, wide_segs(k), order, seg_label, seg_start, nseg, nvalid);
+  hipLaunchKernelGGL(wide_group_kernel, dim3((unsigned)((n + KM_RPB - 1) / KM_RPB)), dim3(256), 0, s, labels, n, k, wide_segs(k), ix.order, ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid);
+  return 0;
+}
+static void wide_members(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
+                         const WideIndex& ix, hipStream_t s) {
+  wide_group(labels, n, k, ix, s);
+  KtScope kt("cluster_members_wide_kernel", 0.0, 12.0 * n, s);
+  hipLaunchKernelGGL(cluster_members_wide_kernel, dim3(k), dim3(256), 0, s, ix.order, wide_segs(k), ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid,
+                     (n + KM_RPB - 1) / KM_RPB, sims, m, rows_out, sims_out, kept_out, sizes_out);
+}
+size_t cluster_members_wide_workspace_bytes(long n, int k) {
+  const size_t nblk = (size_t)((n + KM_RPB - 1) / KM_RPB), slots = nblk * wide_segs(k);
+  return sizeof(int) * (2 * slots + 2 * nblk + nblk * KM_RPB) + 8 * 256;
+}
+// launch_cluster_members' lists for any k <= 4096 by the wide route's kernels.  Returns 1 outside 1 <= k <= 4096, 1 <= m <= 128, 1 <= n < 2^31.
+int launch_cluster_members_wide(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
+                                void* workspace, hipStream_t s) {
+  if (k < 1 || k > KW_KMAX || m < 1 || m > CM_MMAX || n < 1 || n > 0x7FFFFFFFL) return 1;
+  char* ws = static_cast<char*>(workspace);
+  const WideIndex ix = wide_index_carve(ws, n, k);
+  wide_members(labels, sims, n, k, m, rows_out, sims_out, kept_out, sizes_out, ix, s);
   return 0;
 }
 // apply_r.lua:198-227 in one enqueue; c2 / counts / w32 [k] scratch, totalcounts [k]; workspace from cluster_workspace_bytes.  Returns 1 outside
@@ -775,11 +811,7 @@ int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent,
   const size_t slots = (size_t)nblk * segs;
   auto take = [&](size_t bytes) { char* p = ws; ws += (bytes + a - 1) / a * a; return p; };
   double* part = reinterpret_cast<double*>(take(sizeof(double) * slots * d));
-  int* seg_label = reinterpret_cast<int*>(take(sizeof(int) * slots));
-  int* seg_start = reinterpret_cast<int*>(take(sizeof(int) * slots));
-  int* nseg = reinterpret_cast<int*>(take(sizeof(int) * nblk));
-  int* nvalid = reinterpret_cast<int*>(take(sizeof(int) * nblk));
-  int* order = reinterpret_cast<int*>(take(sizeof(int) * (size_t)nblk * KM_RPB));
+  const WideIndex ix = wide_index_carve(ws, n, k);
   int* klab = reinterpret_cast<int*>(take(sizeof(int) * (size_t)n));
   const size_t lds = sizeof(float) * KW_TR * (size_t)(d | 1);
   if (lds > 48 * 1024)                                                   // (per device; a host-side setting, cheap to repeat)
@@ -790,18 +822,16 @@ int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent,
   for (int it = 0; it < niter; ++it) {
     { KtScope kt("kmeans_assign_wide_kernel", 2.0 * n * d * k, 4.0 * n * d, s);
       hipLaunchKernelGGL(kmeans_assign_wide_kernel, dim3((unsigned)((n + KW_TR - 1) / KW_TR)), dim3(256), lds, s, x, n, d, cent, c2, k, klab); }
-    wide_group(klab, n, k, order, seg_label, seg_start, nseg, nvalid, s);
+    wide_group(klab, n, k, ix, s);
     { KtScope kt("wide_segment_sum_kernel", (double)n * d, 4.0 * n * d, s);
-      hipLaunchKernelGGL(wide_segment_sum_kernel, dim3((unsigned)nblk), dim3(256), 0, s, x, d, segs, order, seg_start, nseg, nvalid, part); }
+      hipLaunchKernelGGL(wide_segment_sum_kernel, dim3((unsigned)nblk), dim3(256), 0, s, x, d, segs, ix.order, ix.seg_start, ix.nseg, ix.nvalid, part); }
     KtScope kt("kmeans_update_wide_kernel", 0.0, 8.0 * n * d, s);
-    hipLaunchKernelGGL(kmeans_update_wide_kernel, dim3(k), dim3(256), 0, s, part, segs, seg_label, seg_start, nseg, nvalid, nblk, k, d, cent, c2, counts, totalcounts);
+    hipLaunchKernelGGL(kmeans_update_wide_kernel, dim3(k), dim3(256), 0, s, part, segs, ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid, nblk, k, d, cent, c2, counts, totalcounts);
   }
   hipLaunchKernelGGL(cosine_centroid_prep_kernel, dim3((k + 63) / 64), dim3(64), 0, s, cent, k, d, w32);
   { KtScope kt("cosine_assign_wide_kernel", 2.0 * n * d * k, 4.0 * n * d, s);
     hipLaunchKernelGGL(cosine_assign_wide_kernel, dim3((unsigned)((n + KW_TR - 1) / KW_TR)), dim3(256), lds, s, x, n, d, cent, w32, k, take_min, labels, sims); }
-  wide_group(labels, n, k, order, seg_label, seg_start, nseg, nvalid, s);
-  KtScope kt("cluster_members_wide_kernel", 0.0, 12.0 * n, s);
-  hipLaunchKernelGGL(cluster_members_wide_kernel, dim3(k), dim3(256), 0, s, order, segs, seg_label, seg_start, nseg, nvalid, nblk, sims, m, rows_out, sims_out, kept_out, sizes_out);
+  wide_members(labels, sims, n, k, m, rows_out, sims_out, kept_out, sizes_out, ix, s);
   return 0;
 }
 

@@ -507,6 +507,22 @@ extern "C" int gr_cluster_dev(gr_ctx* c, const float* x, int64_t n, int d, int k
   LAUNCHCHK(c);
   return GR_OK;
 }
+extern "C" int gr_cluster_members_wide_dev(gr_ctx* c, const int32_t* labels, const float* sims, int64_t n, int k, int m, int64_t* rows_out, float* sims_out,
+                                           int32_t* kept_out, int32_t* sizes_out) {
+  if (!c) return GR_ERR_INVALID;
+  if (!labels || !sims || !rows_out || !sims_out || !kept_out || !sizes_out) return fail(c, GR_ERR_INVALID, "gr_cluster_members_wide_dev: null pointer");
+  if (n <= 0 || k <= 0 || m <= 0) return fail(c, GR_ERR_INVALID, "gr_cluster_members_wide_dev: n %lld, k %d, m %d must be positive", (long long)n, k, m);
+  if (k > 4096) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: k %d: at most 4096 clusters", k);
+  if (m > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: m %d: at most 128 rows per cluster", m);
+  if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: n %lld: fewer than 2^31 rows", (long long)n);
+  Staging s(c);
+  auto scratch = s.reserve<char>(cluster_members_wide_workspace_bytes(n, k));
+  TRY(s.grow());
+  if (launch_cluster_members_wide(labels, sims, n, k, m, reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, s.ptr(scratch), c->stream))
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
 extern "C" int gr_cluster_faces_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, const int32_t* kept, int k, int m, float* out) {
   if (!c) return GR_ERR_INVALID;
   if (!table || !rows || !kept || !out) return fail(c, GR_ERR_INVALID, "gr_cluster_faces_dev: null pointer");
@@ -544,6 +560,27 @@ extern "C" int gr_pca_project_dev(gr_ctx* c, const float* x, int64_t n, int d, c
   const int r = launch_pca_project(x, n, d, mean, axes, eigvals, k, whiten, out, c->stream);
   if (r == 2) return fail(c, GR_ERR_HIP, "gr_pca_project_dev: the device refuses the projection kernel's LDS (d %d)", d);
   if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_project_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+
+// ------------------------------------------------------------------ diagonal Gaussian mixture of a device table (mixture.hip)
+extern "C" int gr_mixture_dev(gr_ctx* c, const float* x, int64_t n, int d, int k, int niter, float var_floor, float* weights, float* means, float* vars,
+                              double* loglik, int32_t* labels, float* post, float* rowll) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !weights || !means || !vars || !loglik) return fail(c, GR_ERR_INVALID, "gr_mixture_dev: null pointer");
+  if (n <= 0 || d <= 0 || k <= 0) return fail(c, GR_ERR_INVALID, "gr_mixture_dev: n %lld, d %d and k %d must be positive", (long long)n, d, k);
+  if (niter < 0) return fail(c, GR_ERR_INVALID, "gr_mixture_dev: niter %d: an iteration count", niter);
+  if (!(var_floor > 0.f)) return fail(c, GR_ERR_INVALID, "gr_mixture_dev: var_floor %g must be positive", (double)var_floor);
+  if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: n %lld: fewer than 2^31 rows", (long long)n);
+  if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: d %d: at most 256 columns", d);
+  if (k > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: k %d: at most 256 components", k);
+  Staging s(c);
+  auto scratch = s.reserve<char>(mixture_workspace_bytes(n, d, k));
+  TRY(s.grow());
+  const int r = launch_mixture(x, n, d, k, niter, var_floor, weights, means, vars, loglik, labels, post, rowll, s.ptr(scratch), c->stream);
+  if (r == 2) return fail(c, GR_ERR_HIP, "gr_mixture_dev: the device refuses the kernels' LDS (d %d)", d);
+  if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: unsupported size");
   LAUNCHCHK(c);
   return GR_OK;
 }

@@ -201,7 +201,9 @@ _SIGS = {
     "gr_cluster_members_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gr_cluster_faces_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P]),
     "gr_cluster_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gr_cluster_members_wide_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gr_pca_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
+    "gr_mixture_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "gr_tsne_affinities_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P]),
     "gr_tsne_gradient_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, _P, _P]),
@@ -620,6 +622,21 @@ class Context:
         """gr_cluster_faces_dev (apply_r.lua:233-243): out_dev [k x d] = the average faces of all clusters (rows_dev int64 [k x m], kept_dev int32 [k])"""
         self.check(self.lib.gr_cluster_faces_dev(self.h, _ptr(table_dev), int(n_rows), int(d), _ptr(rows_dev), _ptr(kept_dev), int(k), int(m), _ptr(out_dev)),
                    "gr_cluster_faces_dev")
+
+    def cluster_members_wide_dev(self, labels_dev, sims_dev, n, k, m, rows_out_dev, sims_out_dev, kept_out_dev, sizes_out_dev):
+        """gr_cluster_members_wide_dev: cluster_members_dev's lists for any k <= 4096, by the kernels of gr_cluster_dev's wide route; sims_dev is
+        any per-row score (a mixture's posteriors)"""
+        self.check(self.lib.gr_cluster_members_wide_dev(self.h, _ptr(labels_dev), _ptr(sims_dev), int(n), int(k), int(m), _ptr(rows_out_dev),
+                                                        _ptr(sims_out_dev), _ptr(kept_out_dev), _ptr(sizes_out_dev)), "gr_cluster_members_wide_dev")
+
+    MIXTURE_MAX_D = MIXTURE_MAX_K = 256     # gr_mixture_dev: columns and components at most (include/ganrev.h)
+
+    def mixture_dev(self, x_dev, n, d, k, niter, var_floor, weights_dev, means_dev, vars_dev, loglik_dev, labels_dev=None, post_dev=None, rowll_dev=None):
+        """gr_mixture_dev (1 <= n < 2^31, d <= 256, k <= 256): niter EM iterations of a diagonal Gaussian mixture on the device table [n x d] from
+        weights_dev [k], means_dev / vars_dev [k x d] floats (fitted parameters out), then one E-step: loglik_dev [niter + 1] doubles, labels_dev
+        int32 / post_dev / rowll_dev [n] floats (each may be None).  niter = 0 scores rows under the given parameters.  Enqueued; no host wait."""
+        self.check(self.lib.gr_mixture_dev(self.h, _ptr(x_dev), int(n), int(d), int(k), int(niter), float(var_floor), _ptr(weights_dev), _ptr(means_dev),
+                                           _ptr(vars_dev), _ptr(loglik_dev), _ptr(labels_dev), _ptr(post_dev), _ptr(rowll_dev)), "gr_mixture_dev")
 
     PCA_MAX_D = 256                  # gr_pca_dev / gr_pca_project_dev: columns at most (include/ganrev.h)
 

@@ -320,14 +320,15 @@ def principalAxesOfTable(ctx, attributes, K, whitened=False):
             ctx.free(table)
 
 
-def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colorSpace=None, by_attr=None, by_pix=None):
+def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colorSpace=None, by_attr=None, by_pix=None, mixture=None):
     """The analysis of apply_r.lua:158-191 on the device-resident tables (`images` [N x C x H x W] and `attributesFixer` [N x nd] as
     DeviceTensors, `attributes` [N x nd] a DeviceTensor or the host table): the clusters (createClusterImagesDev), the fixed faces and the
     anomaly distance.  Only the rows a step needs are read; the image table stays where it is.  With `out` (name -> path) the reference's
     pictures are written as PNG files on the way (ganrev.render): cluster_%02d, similar_attributes_%02d / similar_pixelwise_%02d,
     fixed_pairs, fixed_images_<n>[_unfixed] and anomalies; nothing but the finished pictures and the per-image distances leaves the GPU.
     -> what the run's arrays and summary are written from: dict(clusters = createClusterImagesDev's tuple with the faces on the host,
-    fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple)."""
+    fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple).  mixture: --mixture's step, called with the final
+    centroids while the tables are still where they are."""
     from . import render
     ctx, N = images.ctx, images.shape[0]
     chw = images.size // N
@@ -358,12 +359,14 @@ def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colo
     is_anom = dist <= below
     if out:
         render.anomalies_grid(images, is_anom[:min(512 + 16, nbCalc)], colorSpace, path=out("anomalies.png"))           # :374-389
+    if mixture is not None:
+        mixture(attributes, centroids, images)
     return dict(clusters=(centroids, counts, clusters, list(faces_host)), fixed=fixed_host, anomalies=(dist, below, is_anom))
 
 
-def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributesFixer, by_attr, by_pix):
+def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributesFixer, by_attr, by_pix, mixture=None):
     """analyseDev with the pictures of apply_r.lua:158-191 written as PNG files out(name)."""
-    return analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out, colorSpace, by_attr, by_pix)
+    return analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out, colorSpace, by_attr, by_pix, mixture)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -380,6 +383,40 @@ def clusterOptions(OPT):
 def pcaOptions(OPT):
     """(K, pcaSpace) of a run: --pca K and --pcaSpace when given, else (0, False): off"""
     return int(getattr(OPT, "pca", 0)), bool(getattr(OPT, "pcaSpace", False))
+
+
+def mixtureOptions(OPT):
+    """EM iterations of a --mixture run; None without --mixture"""
+    return int(OPT.mixture) if hasattr(OPT, "mixture") else None
+
+
+MAX_COMPONENTS = L.Context.MIXTURE_MAX_K     # gr_mixture_dev's limit
+
+
+def mixtureOfTable(ctx, table, centroids, iterations, column_variances=None, needle_rows=None):
+    """--mixture ITER: a diagonal Gaussian mixture (ganrev.mixture) fitted to the table the clustering read - a DeviceTensor, or the host table,
+    uploaded to a temporary buffer first as clusterHostTable does - by ITER EM iterations from the clustering's final centroids; then every row,
+    and every needle row [Q x d] if given, scored under it -> (Mixture, (labels, posterior, row log-likelihood), the needles' triple or None)"""
+    from . import mixture as MX
+    on_device = isinstance(table, DeviceTensor)
+    N = table.shape[0]
+    d = (table.size if on_device else int(np.prod(table.shape))) // N
+    ptr = table.ptr if on_device else ctx.upload(np.ascontiguousarray(table, np.float32))
+    try:
+        fitted = MX.fit(ctx, ptr, N, d, centroids, iterations, column_variances=column_variances)
+        rows = MX.score(ctx, fitted, ptr, N)
+        needles = None
+        if needle_rows is not None:
+            q = ctx.upload(np.ascontiguousarray(needle_rows, np.float32))
+            try:
+                needles = MX.score(ctx, fitted, q, len(needle_rows))
+            finally:
+                ctx.free(q)
+        return fitted, rows, needles
+    finally:
+        if not on_device:
+            ctx.synchronize()
+            ctx.free(ptr)
 
 
 MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
@@ -448,6 +485,7 @@ def parse(argv=None):
     p.add_argument("--mapPerplexity", type=float, default=argparse.SUPPRESS, help="with --map: the perplexity (default 30; at most (mapRows - 1) / 3)")
     p.add_argument("--mapIterations", type=int, default=argparse.SUPPRESS, help="with --map: gradient iterations (default 1000)")
     p.add_argument("--mapGrid", type=int, default=argparse.SUPPRESS, metavar="G", help="with --map: map_cells and map.png have G x G cells (default 32)")
+    p.add_argument("--mixture", type=int, default=argparse.SUPPRESS, metavar="ITER", help="a diagonal Gaussian mixture of the recovered noise, on the device (ganrev.mixture): ITER EM iterations from the clustering's final centroids, --nbClusters components (at most 256), in the table the clustering read; writes mixture_weights, mixture_means, mixture_variances, mixture_loglik [ITER + 1], mixture_labels, mixture_posterior, mixture_row_loglik (.npy), with --render mixture_%%02d.png and mixture_outliers.png, with --needles needle_mixture.npy")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
     p.add_argument("--nbIterations", type=int, default=argparse.SUPPRESS, help="k-means iterations (default 15, apply_r.lua:160)")
@@ -492,6 +530,14 @@ def parse(argv=None):
         p.error("--nbIterations: an iteration count")
     if not 1 <= nbMaxPerCluster <= MAX_PER_CLUSTER:
         p.error(f"--nbMaxPerCluster: 1 to {MAX_PER_CLUSTER}")
+    mixIter = mixtureOptions(OPT)
+    if mixIter is not None:
+        if OPT.host:
+            p.error("--mixture runs on the device-resident tables: not with --host")
+        if mixIter < 0:
+            p.error("--mixture: an iteration count")
+        if nbClusters > MAX_COMPONENTS:
+            p.error(f"--mixture: --nbClusters {nbClusters}: at most {MAX_COMPONENTS} components")
     if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
         p.error("--needles and --real read their images from --dataset")
     if (OPT.needles or OPT.real) and OPT.host:
@@ -561,11 +607,15 @@ def run(OPT):
         return dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
                     loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
 
+    mixIter, mix = mixtureOptions(OPT), {}                                  # mix: what the steps before the mixture leave for it
+
     def pca_step(table):                                                      # --pca K over the attribute table (a DeviceTensor or the host array)
         from . import pca as P
         say("Principal axes of the recovered noise...")
         axes, coords, white = principalAxesOfTable(ctx, table, nbAxes, pcaSpace)
         try:
+            if mixIter is not None:                                           # the mixture reuses the covariance diagonal, and projects the needles
+                mix["pca"] = (axes.mean, axes.axes, axes.eigenvalues, np.diag(axes.covariance()).copy())
             np.save(out("pca_mean.npy"), axes.mean); np.save(out("pca_eigenvalues.npy"), axes.eigenvalues)
             np.save(out("pca_axes.npy"), axes.axes[:nbAxes]); np.save(out("pca_projection.npy"), coords)
             summary["pca"] = dict(k=nbAxes, explained=[float(v) for v in axes.explained[:nbAxes]], sweeps=axes.sweeps, converged=axes.converged,
@@ -589,6 +639,43 @@ def run(OPT):
         finally:
             axes.close()
         return white
+
+    def needles_in_space(na):                                                 # the needles' rows in the table the mixture is fitted in
+        if not pcaSpace:
+            return na.numpy()
+        mean, axes, lam, _ = mix["pca"]
+        bufs = [ctx.upload(np.ascontiguousarray(a)) for a in (mean, axes, lam)]
+        white = DeviceTensor(ctx, (na.shape[0], nbAxes))
+        try:
+            ctx.pca_project_dev(na.ptr, na.shape[0], nd, bufs[0], bufs[1], bufs[2], nbAxes, True, white.ptr)
+            return white.numpy()
+        finally:
+            white.free()
+            for b in bufs:
+                ctx.free(b)
+
+    def mixture_step(table, centroids, images=None):                          # --mixture ITER, after the clustering, in the table it read
+        say("Fitting a Gaussian mixture to the recovered noise...")
+        reuse = mix["pca"][3] if "pca" in mix and not pcaSpace else None      # (the whitened projection is another table: its variances are its own)
+        fitted, (labels, post, rowll), needles = mixtureOfTable(ctx, table, centroids, mixIter, reuse, mix.get("needles"))
+        for name, a in (("weights", fitted.weights), ("means", fitted.means), ("variances", fitted.variances), ("loglik", fitted.loglik),
+                        ("labels", labels), ("posterior", post), ("row_loglik", rowll)):
+            np.save(out("mixture_%s.npy" % name), a)
+        summary["mixture"] = dict(iterations=mixIter, k=fitted.k, var_floor=fitted.var_floor, loglik=[float(v) for v in fitted.loglik],
+                                  weights=[float(v) for v in fitted.weights], sizes=[int(v) for v in np.bincount(labels, minlength=fitted.k)],
+                                  row_loglik_min=float(rowll.min()), row_loglik_median=float(np.median(rowll)),
+                                  space="pca_whitened" if pcaSpace else "attributes")
+        if needles is not None:
+            np.save(out("needle_mixture.npy"), np.stack([needles[0].astype(np.float64), needles[1].astype(np.float64), needles[2].astype(np.float64)], axis=1))
+        if OPT.render and images is not None:
+            from . import mixture as MX
+            from . import render
+            for j, cl in enumerate(MX.members(ctx, labels, post, fitted.k, clusterOptions(OPT)[2])):
+                if cl:                                                        # the average face first, then the rows of highest posterior
+                    render.cluster_grid(images, [r for r, _ in cl], colorSpace, path=out("mixture_%02d.png" % (j + 1)))
+            shown = min(512 + 16, N, 1024)                                    # as many rows as anomalies.png shows
+            worst = np.argsort(rowll, kind="stable")[:shown]                  # lowest row log-likelihood first
+            render.grid(images, worst, int(math.floor(math.sqrt(shown))), colorSpace, path=out("mixture_outliers.png"))
 
     mapped, map_cells = mapOptions(OPT), None
 
@@ -677,6 +764,8 @@ def run(OPT):
                 summary["needles"] = dict(count=OPT.needles, files=[os.path.basename(f) for f in nl.paths])
                 if OPT.refine:
                     summary["needles"]["refine"] = refine_rows(ni, na)
+                if mixIter is not None:
+                    mix["needles"] = needles_in_space(na)
                 nb_attr, nb_pix = searchByExample(100, da, na, di, ni)
                 np.save(out("needle_by_attributes.npy"), nb_attr); np.save(out("needle_by_pixels.npy"), nb_pix); np.save(out("needle_attributes.npy"), na.numpy())
                 if OPT.render:
@@ -708,10 +797,10 @@ def run(OPT):
     rendered = None
     if OPT.render:
         say("Rendering...")                                                   # from di / df, before they are freed
-        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, space if OPT.host else ds, df, by_attr, by_pix)
+        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, space if OPT.host else ds, df, by_attr, by_pix, **({} if mixIter is None else dict(mixture=mixture_step)))
     elif OPT.resident:
         say("Analysing on the device...")
-        rendered = analyseDev(OPT, MODEL_G, di, ds, df)
+        rendered = analyseDev(OPT, MODEL_G, di, ds, df, **({} if mixIter is None else dict(mixture=mixture_step)))
     if map_cells is not None and OPT.render:
         # the faces where they land: one grid over the map's cells, from the image table where it lies; each tile's ring takes the colour of
         # its row's cluster - the assignment of the clustering step (gr_cosine_assign on its final centroids) repeated for the rows shown
@@ -736,6 +825,8 @@ def run(OPT):
     np.save(out("cluster_centroids.npy"), centroids); np.save(out("cluster_average_faces.npy"), np.stack(faces))
     summary["cluster_sizes"] = [len(c) for c in clusters]; summary["cluster_total_counts"] = [float(v) for v in counts]
     summary.update(zip(("nbClusters", "nbIterations", "nbMaxPerCluster", "closest"), clusterOptions(OPT)))
+    if mixIter is not None and not rendered:                                  # neither --resident nor --render: the host copy of the table is uploaded
+        mixture_step(space, centroids)
 
     say("Fixing faces...")                                                    # :178-181
     nbFixed = min(512 + 16, N)

@@ -84,9 +84,13 @@ int gr_cluster_members_dev(gr_ctx*, const int32_t* labels_dev, const float* sims
 int gr_cluster_faces_dev(gr_ctx*, const float* table_dev, int64_t n_rows, int64_t d, const int64_t* rows_dev, const int32_t* kept_dev, int k, int m, float* out_dev);     /* apply_r.lua:233-243 */
 int gr_cluster_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float* cent_dev, int take_min, int m, float* totalcounts_dev,
                    int32_t* labels_dev, float* sims_dev, int64_t* rows_out_dev, float* sims_out_dev, int32_t* kept_out_dev, int32_t* sizes_out_dev);     /* apply_r.lua:198-227, k <= 4096 */
+int gr_cluster_members_wide_dev(gr_ctx*, const int32_t* labels_dev, const float* sims_dev, int64_t n, int k, int m, int64_t* rows_out_dev, float* sims_out_dev,
+                                int32_t* kept_out_dev, int32_t* sizes_out_dev);     /* the same lists, k <= 4096 */
 int gr_pca_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double* mean_dev, double* cov_dev, double* eigvals_dev, float* axes_dev, int32_t* info_dev);     /* principal axes, d <= 256 */
 int gr_pca_project_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const double* mean_dev, const float* axes_dev, const double* eigvals_dev,
                        int k, int whiten, float* out_dev);
+int gr_mixture_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float var_floor, float* weights_dev, float* means_dev, float* vars_dev,
+                   double* loglik_dev, int32_t* labels_dev, float* post_dev, float* rowll_dev);     /* diagonal Gaussian mixture by EM, d, k <= 256 */
 typedef struct { float exaggeration; int32_t stop_lying_iter; float momentum0, momentum1; int32_t mom_switch_iter; float eta, min_gain; } gr_tsne_config;
 int gr_tsne_affinities_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double perplexity, float* p_dev, double* beta_dev, int32_t* info_dev);     /* exact t-SNE, n <= 16384 */
 int gr_tsne_gradient_dev(gr_ctx*, const float* p_dev, const float* y_dev, int64_t n, float exaggeration, float* grad_dev, double* z_dev);

@@ -477,6 +477,14 @@ int gr_cluster_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int
                    float* totalcounts_dev /*nullable*/, int32_t* labels_dev, float* sims_dev, int64_t* rows_out_dev, float* sims_out_dev,
                    int32_t* kept_out_dev, int32_t* sizes_out_dev);
 
+/* gr_cluster_members_wide_dev: gr_cluster_members_dev's lists - the same rule, fill values, tie and NaN order - for any k up to 4096, by the grouping and
+ * member-selection kernels of gr_cluster_dev's wide route (one helper serves both).  sims_dev is any per-row score: a mixture's posteriors rank a
+ * component's rows the way similarities rank a cluster's.  Limits: 1 <= k <= 4096, 1 <= m <= 128, 1 <= n < 2^31; outside them GR_ERR_UNSUPPORTED with
+ * a gr_last_error text that names the value; null pointers or non-positive n, k, m GR_ERR_INVALID.  Scratch: the index of gr_cluster_dev's wide route,
+ * 2 S + 2 B + 512 B ints. */
+int gr_cluster_members_wide_dev(gr_ctx* ctx, const int32_t* labels_dev, const float* sims_dev, int64_t n, int k, int m, int64_t* rows_out_dev,
+                                float* sims_out_dev, int32_t* kept_out_dev, int32_t* sizes_out_dev);
+
 /* ---- principal axes of a device table (csrc/pca.hip; new: the reference has no counterpart) ----
  * gr_pca_dev: x_dev [n x d] floats -> mean_dev [d] doubles, cov_dev [d x d] doubles (nullable), eigvals_dev [d] doubles (descending),
  * axes_dev [d x d] floats (row a = unit axis a), info_dev [2] int32 (sweeps used, converged flag).  Every pointer is device memory; the work is
@@ -511,6 +519,37 @@ int gr_pca_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, double* mean_d
                int32_t* info_dev);
 int gr_pca_project_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, const double* mean_dev, const float* axes_dev, const double* eigvals_dev /*nullable unless whiten*/,
                        int k, int whiten, float* out_dev);
+
+/* ---- diagonal-covariance Gaussian mixture of a device table, fitted by EM (csrc/mixture.hip; new: the reference has no counterpart) ----
+ * gr_mixture_dev: x_dev [n x d] floats; weights_dev [k], means_dev [k x d], vars_dev [k x d] floats, the initial parameters in, the fitted ones out;
+ * loglik_dev [niter + 1] doubles; labels_dev (int32), post_dev, rowll_dev [n] nullable.  Every pointer is device memory; the work is enqueued on the
+ * ctx stream and the call returns without waiting for it; scratch comes from the context.  For t = 0 .. niter - 1 an E-step under the current
+ * parameters, which writes loglik[t], then an M-step; one last E-step under the final parameters writes loglik[niter] and the per-row outputs.
+ * niter = 0 scores rows under given parameters, which come back bit for bit.
+ * Everything past the loads is fp64, every operation rounded on its own (no fused multiply-add); exp and log are the device library's.
+ * Log-density.  Once per E-step and component: h_jt = 0.5 / var_jt; c_j = log(w_j) - 0.5 (d log(2 pi) + S_j), S_j the log(var_jt) added in column order
+ * from +0.0.  Per (row, component) one chain in column order from +0.0: dl = x_it - mu_jt, e = dl dl, q = q + e h_jt; l_ij = c_j - q.  A component
+ * with w_j = 0 has l = -inf: it is dead and adds nothing.
+ * Row log-likelihood.  The components form 4 contiguous ranges of ceil(k / 4).  Within a range, in ascending j, the running pair (m, s) from (-inf, 0):
+ * l > m: s = s exp(m - l) + 1, m = l, label = j; otherwise, for l > -inf, s = s + exp(l - m).  M = the largest m, the lowest range among equals:
+ * labels = its label, the first maximum of l_ij over ascending j; S = the s_g exp(m_g - M) added in range order from +0.0; L_i = M + log(S);
+ * post = (float)exp(M - L_i), the responsibility at the label; rowll = (float)L_i.  loglik[t]: per block of 512 consecutive rows the L_i in row order
+ * from +0.0, the block partials in block order from +0.0, one division by n.
+ * M-step.  r_ij = exp(l_ij - L_i), l_ij by the chain above, 0 where l_ij = -inf.  Per block of 512 rows and (j, t) three chains in row order from +0.0:
+ * a1 = a1 + r x; dl = x - mu_jt, e = dl dl, a2 = a2 + r e; an = an + r.  P = 128 partial sets, a constant of the library: with B = ceil(n / 512) blocks,
+ * set p adds the chains of the blocks floor(p B / P) .. floor((p + 1) B / P) - 1 in block order from +0.0; S1, S2, N = the sets in order from +0.0.
+ * N_j >= 1: mu' = S1 / N; dm = mu' - mu; var' = S2 / N - dm dm - the second moment about the old mean, never sum r x^2 - mu^2 - and var_floor where
+ * that is not above it; both rounded to float once.  N_j < 1, less than one row's worth of responsibility: the mean and the variances stay, bit for
+ * bit.  w' = (float)(N / n) either way.
+ * No floating-point atomics, nothing depends on the CU count or on the order in which workgroups finish: two runs give the same bits, and niter = 3
+ * gives the bits of three calls with niter = 1.
+ * Limits: 1 <= n < 2^31, 1 <= d <= 256, 1 <= k <= 256; outside them GR_ERR_UNSUPPORTED with a gr_last_error text that names the value; null required
+ * pointers, non-positive n, d, k, a negative niter or a var_floor that is not > 0: GR_ERR_INVALID.  The context stays usable after either.  A table or
+ * parameters with non-finite elements, or weights that are all 0, are outside the contract (the call still returns).
+ * Scratch: n + ceil(n / 512) + k + k d + P k (2 d + 1) doubles: 8 n bytes plus at most 135 MB, whatever the device. */
+int gr_mixture_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int niter, float var_floor, float* weights_dev /*[k] in/out*/,
+                   float* means_dev /*[k x d] in/out*/, float* vars_dev /*[k x d] in/out*/, double* loglik_dev /*[niter + 1]*/,
+                   int32_t* labels_dev /*[n] nullable*/, float* post_dev /*[n] nullable*/, float* rowll_dev /*[n] nullable*/);
 
 /* ---- exact (dense) t-SNE of a device table (csrc/tsne.hip; new: the reference has no counterpart) ----
  * A two-dimensional, neighbour-preserving map of up to GR_TSNE_MAX_N rows: the joint matrix is n x n floats (1 GiB at the cap).  Barnes-Hut,
