@@ -193,6 +193,22 @@ __device__ __forceinline__ uint32_t mask_word(const MaskRef& m, unsigned e, unsi
   if (m.kind == MASK_SPATIAL) return ((m.bits[bc >> 5] >> (bc & 31)) & 1u) ? 0xFu : 0u;
   return 0xFu;
 }
+// mask_word in two halves for kernels that issue a batch of loads before they use any: the fetch (the word as it lies in memory) and
+// the integer work on it (mask_word = mask_word_finish(mask_word_raw, mask_word_shift)).  A shift that sits between the loads of
+// two groups makes the second group's requests wait for the first group's word.
+__device__ __forceinline__ uint32_t mask_word_raw(const MaskRef& m, unsigned e, unsigned bc) {
+  if (m.kind == MASK_ELEM) return m.bits[e >> 5];
+  if (m.kind == MASK_SPATIAL) return m.bits[bc >> 5];
+  return 0u;
+}
+__device__ __forceinline__ uint32_t mask_word_shift(const MaskRef& m, unsigned e, unsigned bc) {
+  return m.kind == MASK_ELEM ? (e & 31) : m.kind == MASK_SPATIAL ? (bc & 31) : 0u;
+}
+__device__ __forceinline__ uint32_t mask_word_finish(const MaskRef& m, uint32_t raw, uint32_t sh) {
+  if (m.kind == MASK_ELEM) return raw >> sh;
+  if (m.kind == MASK_SPATIAL) return ((raw >> sh) & 1u) ? 0xFu : 0u;
+  return 0xFu;
+}
 __device__ __forceinline__ float4 mask4_of(const MaskRef& m, uint32_t w) {
   if (m.kind == MASK_NONE) return make_float4(1.f, 1.f, 1.f, 1.f);
   if (m.kind == MASK_SCALE) return make_float4(m.scale, m.scale, m.scale, m.scale);
@@ -690,7 +706,8 @@ __global__ __launch_bounds__(256) void post_backward_a_kernel(PostBwdArgs a, int
 // tensor read less than storing it.
 // The same in two phases for kernels that work on several channels per thread: all loads of a channel first (so that the loads
 // of eight channels are in flight together), the arithmetic afterwards.  Same operations in the same order as post_bwd_dz4.
-struct BwdRaw { float4 g, y; uint32_t id2, m2w, m1w, t0; };
+// m2w / m1w: the mask words as fetched; t0: bit 1 = the row's parity in its pool window, bits 8-12 / 16-20 = the shifts of m1w / m2w
+struct BwdRaw { float4 g, y; uint32_t m2w, m1w, t0; uint16_t id2; };      // (id2 as loaded: widening it is work on a loaded value, too)
 
 __device__ __forceinline__ BwdRaw post_bwd_load4(const PostBwdArgs& a, unsigned bc, unsigned e, unsigned i, unsigned obase, unsigned wq, unsigned Wo) {
   const PostArgs& f = a.f;
@@ -699,20 +716,25 @@ __device__ __forceinline__ BwdRaw post_bwd_load4(const PostBwdArgs& a, unsigned 
     const unsigned yy = udivp(i, wq), xx = (i - yy * wq) * 4, eo = obase + (yy >> 1) * Wo + (xx >> 1);
     const float2 go = *reinterpret_cast<const float2*>(a.gout + eo);
     r.g = make_float4(go.x, go.y, 0.f, 0.f);
-    r.id2 = f.pool == POOL_AVG ? 0u : *reinterpret_cast<const uint16_t*>(f.pool_idx + eo);      // (an average pool has no index)
-    r.m2w = mask_word(f.m2, eo, bc);                  // eo is even: the bits of eo and eo + 1 sit in one word
-    r.t0 = (yy & 1) << 1;
+    r.id2 = f.pool == POOL_AVG ? (uint16_t)0 : *reinterpret_cast<const uint16_t*>(f.pool_idx + eo);      // (an average pool has no index)
+    r.m2w = mask_word_raw(f.m2, eo, bc);              // eo is even: the bits of eo and eo + 1 sit in one word
+    r.t0 = (yy & 1) << 1 | mask_word_shift(f.m2, eo, bc) << 16;
   } else {
     r.g = ld4_maybe_nt(a.gout + e, a.nt != 0);
-    r.id2 = 0; r.t0 = 0;
-    r.m2w = mask_word(f.m2, e, bc);
+    r.id2 = 0; r.t0 = mask_word_shift(f.m2, e, bc) << 16;
+    r.m2w = mask_word_raw(f.m2, e, bc);
   }
-  r.m1w = mask_word(f.m1, e, bc);
+  r.m1w = mask_word_raw(f.m1, e, bc);
+  r.t0 |= mask_word_shift(f.m1, e, bc) << 8;
   r.y = ld4_maybe_nt(f.y + e, a.nt != 0);
   return r;
 }
-__device__ __forceinline__ float4 post_bwd_dz_of(const PostBwdArgs& a, const BwdRaw& r, float mean, float invstd, float gm, float bt) {
+__device__ __forceinline__ float4 post_bwd_dz_of(const PostBwdArgs& a, const BwdRaw& r0, float mean, float invstd, float gm, float bt) {
   const PostArgs& f = a.f;
+  BwdRaw r = r0;
+  r.m1w = mask_word_finish(f.m1, r0.m1w, (r0.t0 >> 8) & 31u);
+  r.m2w = mask_word_finish(f.m2, r0.m2w, (r0.t0 >> 16) & 31u);
+  r.t0 = r0.t0 & 2u;
   float4 g;
   if (f.pool) {
     const float4 m2 = mask4_of(f.m2, r.m2w);
@@ -778,7 +800,9 @@ __device__ __forceinline__ float4 post_bwd_dz4(const PostBwdArgs& a, unsigned bc
 }
 
 // float4 variants of pass A / pass B: block (c, split) walks its images, threads take consecutive pre-pool float4s.
-template <int CB>
+// ONE: the launcher found that a block's batch slice is a single round (tot <= 1024 groups: cfg2) - no second buffer set, which the
+// multi-round body keeps allocated whether it is used or not (108-114 registers, 4 waves per SIMD).
+template <int CB, bool ONE>
 __global__ __launch_bounds__(256) void post_backward_a_vec_kernel(PostBwdArgs a, int splits) {
   __shared__ double sh[8];
   post_specialize<CB>(a.f);
@@ -799,7 +823,7 @@ __global__ __launch_bounds__(256) void post_backward_a_vec_kernel(PostBwdArgs a,
     // A block owns several rounds of 1024 groups whenever its batch slice holds more than 4096 elements per channel (cfg3: 8 images of 64 x 64 = 8 rounds;
     // cfg2: one round); round k + 1 is requested before round k is worked on.  (Making blocks longer at
     // cfg2 measured no gain: profiles/r05_ab_passa_prefetch_cfg2.txt - the second buffer set is for the naturally long blocks.)
-    BwdRaw r[4], rn[4]; unsigned ee[4], een[4];
+    BwdRaw r[4]; unsigned ee[4];
     auto request = [&](unsigned j0, BwdRaw* rr, unsigned* e_) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -812,27 +836,35 @@ __global__ __launch_bounds__(256) void post_backward_a_vec_kernel(PostBwdArgs a,
         }
       }
     };
+    // the four elements of a group are added in fp32 (pairwise), the groups in fp64: 2 conversions + 2 fp64 adds per
+    // group instead of 20 fp64-class instructions (half rate on gfx950, and these kernels are VALU-bound); the partial's
+    // rounding is 2 ulp of a 4-term sum, far inside the 1e-4 bar
+    auto add = [&](const BwdRaw& ru, unsigned e) {
+      const float4 dz = post_bwd_dz_of(a, ru, mean, invstd, gm, bt);
+      const float4 yv = ru.y;
+      if (!f.has_bn) *reinterpret_cast<float4*>(a.dy + e) = dz;     // with BatchNorm pass B recomputes dz: nothing stored here
+      dmax = absmax4(dmax, dz);
+      s += (double)((dz.x + dz.y) + (dz.z + dz.w));
+      q += (double)(((yv.x - mean) * dz.x + (yv.y - mean) * dz.y) + ((yv.z - mean) * dz.z + (yv.w - mean) * dz.w));
+    };
     if (threadIdx.x < tot) request(threadIdx.x, r, ee);
-    for (unsigned j0 = threadIdx.x; j0 < tot; j0 += 1024) {
-      const bool more = j0 + 1024 < tot;
-      if (more) request(j0 + 1024, rn, een);
+    if constexpr (ONE) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (j0 + 256u * u < tot) {
-          const float4 dz = post_bwd_dz_of(a, r[u], mean, invstd, gm, bt);
-          const float4 yv = r[u].y;
-          if (!f.has_bn) *reinterpret_cast<float4*>(a.dy + ee[u]) = dz;     // with BatchNorm pass B recomputes dz: nothing stored here
-          dmax = absmax4(dmax, dz);
-          // the four elements of a group are added in fp32 (pairwise), the groups in fp64: 2 conversions + 2 fp64 adds per
-          // group instead of 20 fp64-class instructions (half rate on gfx950, and these kernels are VALU-bound); the partial's
-          // rounding is 2 ulp of a 4-term sum, far inside the 1e-4 bar
-          s += (double)((dz.x + dz.y) + (dz.z + dz.w));
-          q += (double)(((yv.x - mean) * dz.x + (yv.y - mean) * dz.y) + ((yv.z - mean) * dz.z + (yv.w - mean) * dz.w));
+      for (int u = 0; u < 4; ++u)
+        if (threadIdx.x + 256u * u < tot) add(r[u], ee[u]);
+    } else {
+      BwdRaw rn[4]; unsigned een[4];
+      for (unsigned j0 = threadIdx.x; j0 < tot; j0 += 1024) {
+        const bool more = j0 + 1024 < tot;
+        if (more) request(j0 + 1024, rn, een);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (j0 + 256u * u < tot) add(r[u], ee[u]);
         }
-      }
-      if (more) {
+        if (more) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) { r[u] = rn[u]; ee[u] = een[u]; }
+          for (int u = 0; u < 4; ++u) { r[u] = rn[u]; ee[u] = een[u]; }
+        }
       }
     }
   }
@@ -896,6 +928,13 @@ __global__ __launch_bounds__(256) void post_backward_b_vec_kernel(PostBwdArgs a,
   if (threadIdx.x == 0) a.partials_b[(long)c * PB_SPLITS + sp] = s;
 }
 
+// __shfl_down(v, off, width) of a double with the caller's own lane number (same lanes, same halves: the same sum)
+__device__ __forceinline__ double shfl_down_f64(double v, unsigned lane, unsigned off, unsigned width) {
+  const unsigned src = ((lane & (width - 1)) + off >= width ? lane : lane + off) << 2;
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute((int)src, (int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_ds_bpermute((int)src, (int)(unsigned)(b >> 32));
+  return __builtin_bit_cast(double, (unsigned long long)hi << 32 | lo);
+}
 // Operand-ready pass B: block (8-channel group, batch slice), light threads (one channel x 4 consecutive pre-pool pixels) and
 // the LDS transpose of the forward kernel (t8_pack / t8_emit).  Writes dy as the data- / weight-gradient convolutions' image
 // dy_p16[b][g][term][pixel], scaled by the power of two of the bound K * max|dz| (K from the forward's statistics, max|dz| from
@@ -939,55 +978,63 @@ __global__ __launch_bounds__(256) void post_backward_b_g8_kernel(PostBwdArgs a, 
   const float sc = pow2f(f16_scale_exp(__float_as_uint(bound)));
   const unsigned H = f.H, W = f.W, Wo = f.pool ? W >> 1 : W, HW = H * W, HWo = f.pool ? (H >> 1) * Wo : HW, wq = W >> 2;
   const unsigned G = (unsigned)f.C >> 3;
-  const unsigned npx = HW < (unsigned)PXT ? HW : (unsigned)PXT, tiles = HW / npx, qpt = npx >> 2;
+  // Every tile has PXT pixels (post_g8_supported, backward: whole 256-pixel tiles), so a thread's quads per tile are a compile-time
+  // fact: KQ = 2 at PXT = 256.  (A run-time count kept a four-deep batch whose upper half is never loaded alive in the register
+  // allocation: 66-72 registers, 7 blocks per CU; the grid is 8 or 16 blocks per CU, i.e. 1.14 / 2.29 residency rounds.)
+  constexpr unsigned QPT = PXT >> 2, KQ = QPT / 32;
+  static_assert(PXT % 128 == 0 && KQ >= 1, "a tile is whole rounds of 32 quads per channel");
+  const unsigned tiles = HW / (unsigned)PXT;
   const int per = (f.B + slices - 1) / slices, b0 = sp * per, b1 = min(f.B, b0 + per);      // blockIdx.y = one of `slices` batch slices (finer than pass A's splits)
   uint4* p16 = reinterpret_cast<uint4*>(a.dy_p16);
   const unsigned jc = threadIdx.x >> 5, q0 = threadIdx.x & 31;      // this thread's channel of the group and its first quad
   const float mean = par[jc][0], invstd = par[jc][1], w = par[jc][2], bt = par[jc][3], gm = par[jc][4], kk = par[jc][5];
   double csum = 0.0;
-  for (int b = b0; b < b1; ++b)
+  for (int b = b0; b < b1; ++b) {
+    const unsigned bcj = (unsigned)b * f.C + 8 * g + jc;
+    // a SpatialDropout word belongs to the plane: fetched once per image (per tile it kept its address and bit alive: 3 registers)
+    const uint32_t m1_plane = mask_word_raw(f.m1, 0, bcj);
     for (unsigned tile = 0; tile < tiles; ++tile) {
-      const unsigned bcj = (unsigned)b * f.C + 8 * g + jc;
-      // thread -> (channel jc = tid / 32, quads (tid & 31) + 32 k): a thread stays on ONE channel, so its bias-gradient sum is a
-      // single register (an array indexed by a task slot went to scratch memory); four quads at a time: their loads (gradOutput,
-      // y, masks, argmax) are in flight together, then the arithmetic.  qpt is a multiple of 64.
-      for (unsigned k0 = 0; k0 < qpt / 32; k0 += 4) {
-        BwdRaw raw[4];
+      // thread -> (channel jc = tid / 32, quads (tid & 31) + 32 u): a thread stays on ONE channel, so its bias-gradient sum is a
+      // single register (an array indexed by a task slot went to scratch memory); the tile's KQ quads at a time: their loads
+      // (gradOutput, y, masks, argmax) are in flight together, then the arithmetic.
+      BwdRaw raw[KQ];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned qi = q0 + 32 * (k0 + u), i = tile * qpt + qi;
-          if (k0 + u < qpt / 32) {
-            raw[u] = post_bwd_load4(a, bcj, bcj * HW + i * 4, i, bcj * HWo, wq, Wo);
-          }
-        }
+      for (unsigned u = 0; u < KQ; ++u) {
+        const unsigned i = tile * QPT + q0 + 32 * u;
+        raw[u] = post_bwd_load4(a, bcj, bcj * HW + i * 4, i, bcj * HWo, wq, Wo);
+        if (f.m1.kind == MASK_SPATIAL) raw[u].m1w = m1_plane;
+      }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned qi = q0 + 32 * (k0 + u), i = tile * qpt + qi;
-          if (k0 + u < qpt / 32) {
-            const float4 yv = raw[u].y;
-            const float4 dz = post_bwd_dz_of(a, raw[u], mean, invstd, w, bt);                 // as pass A computed it
-            float4 d;
-            d.x = ((dz.x - gm) - (yv.x - mean) * kk) * invstd * w; d.y = ((dz.y - gm) - (yv.y - mean) * kk) * invstd * w;
-            d.z = ((dz.z - gm) - (yv.z - mean) * kk) * invstd * w; d.w = ((dz.w - gm) - (yv.w - mean) * kk) * invstd * w;
-            if (a.dy) store4(a.dy + (size_t)bcj * HW + 4 * (size_t)i, d, f.nt_st != 0);     // (null: both gradient kernels take the operand-ready image)
-            csum += (double)((d.x + d.y) + (d.z + d.w));
-            uint2 hi, lo;
-            t8_pack(d, sc, hi, lo);
-            *reinterpret_cast<uint2*>(img + (size_t)jc * RSB + qi * 8) = hi;
-            *reinterpret_cast<uint2*>(img + (size_t)(8 + jc) * RSB + qi * 8) = lo;
-          }
-        }
+      for (unsigned u = 0; u < KQ; ++u) {
+        const unsigned qi = q0 + 32 * u, i = tile * QPT + qi;
+        const float4 yv = raw[u].y;
+        const float4 dz = post_bwd_dz_of(a, raw[u], mean, invstd, w, bt);                 // as pass A computed it
+        float4 d;
+        d.x = ((dz.x - gm) - (yv.x - mean) * kk) * invstd * w; d.y = ((dz.y - gm) - (yv.y - mean) * kk) * invstd * w;
+        d.z = ((dz.z - gm) - (yv.z - mean) * kk) * invstd * w; d.w = ((dz.w - gm) - (yv.w - mean) * kk) * invstd * w;
+        if (a.dy) store4(a.dy + (size_t)bcj * HW + 4 * (size_t)i, d, f.nt_st != 0);     // (null: both gradient kernels take the operand-ready image)
+        csum += (double)((d.x + d.y) + (d.z + d.w));
+        uint2 hi, lo;
+        t8_pack(d, sc, hi, lo);
+        *reinterpret_cast<uint2*>(img + (size_t)jc * RSB + qi * 8) = hi;
+        *reinterpret_cast<uint2*>(img + (size_t)(8 + jc) * RSB + qi * 8) = lo;
       }
       __syncthreads();
-      t8_emit<RSB>(img, (int)npx, p16 + ((size_t)b * G + g) * 2 * HW + (size_t)tile * npx, HW, f.nt_st != 0);
+      t8_emit<RSB>(img, PXT, p16 + ((size_t)b * G + g) * 2 * HW + (size_t)tile * PXT, HW, f.nt_st != 0);
       __syncthreads();
     }
-  // bias gradient: per-channel sums of dy = the 32 threads of a channel (one half-wave), added in a fixed shuffle tree
+  }
+  // bias gradient: per-channel sums of dy = the 32 threads of a channel (one half-wave), added in a fixed shuffle tree.  The
+  // thread's indices are derived again, behind an opaque move: the lane number, tid / 32 and 8 g + tid kept alive across the tile
+  // loop for these few lines cost four registers there - the difference between seven and eight resident blocks.
+  unsigned t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  const unsigned lane = t & 63;
 #pragma unroll
-  for (int off = 16; off > 0; off >>= 1) csum += __shfl_down(csum, off, 32);
-  if (q0 == 0) chsum[jc] = csum;
+  for (unsigned off = 16; off > 0; off >>= 1) csum += shfl_down_f64(csum, lane, off, 32);
+  if ((t & 31) == 0) chsum[t >> 5] = csum;
   __syncthreads();
-  if (threadIdx.x < 8) a.partials_b[(long)(8 * g + threadIdx.x) * PB_SPLITS + sp] = chsum[threadIdx.x];
+  if (t < 8) a.partials_b[(long)(8 * g + t) * PB_SPLITS + sp] = chsum[t];
 }
 
 __global__ void post_backward_finalize_kernel(PostBwdArgs a, int splits, double n) {
@@ -1072,7 +1119,9 @@ void launch_post_backward(const PostBwdArgs& a0, hipStream_t s, BiasJobs* defer,
   if (vec) {
     splits = batch_splits(n, f.B);
     KtScope kt("post_backward_a_vec_kernel", 0.0, 4.0 * ((f.has_bn ? 1.0 : 2.0) * pre + post), s);   // with BN: dz is not stored
-    with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL(post_backward_a_vec_kernel<decltype(cb)::value>, dim3(f.C, splits), dim3(256), 0, s, a, splits); });
+    const long per = (f.B + splits - 1) / splits;                     // images per block: a single round of 1024 float4 groups, or several
+    if (per * (f.H * f.W / 4) <= 1024) with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_a_vec_kernel<decltype(cb)::value, true>), dim3(f.C, splits), dim3(256), 0, s, a, splits); });
+    else with_combo(post_combo(f), [&](auto cb) { hipLaunchKernelGGL((post_backward_a_vec_kernel<decltype(cb)::value, false>), dim3(f.C, splits), dim3(256), 0, s, a, splits); });
   } else {
     KtScope kt("post_backward_a_kernel", 0.0, 4.0 * (2.0 * pre + post), s);
     hipLaunchKernelGGL(post_backward_a_kernel, dim3(f.C, splits), dim3(256), 0, s, a, splits);
