@@ -573,6 +573,13 @@ size_t mixture_workspace_bytes(long n, int d, int k);
 int launch_mixture(const float* x, long n, int d, int k, int niter, float var_floor, float* w, float* mu, float* vars, double* loglik, int* labels,
                    float* post, float* rowll, void* workspace, hipStream_t s);
 
+// ---------------------------------------------------------------- the sampling layer of a VAE (vae.hip; gr_vae_sample_dev, gr_vae_sample_backward_dev)
+// h [B x 2 nd] = (mu | logvar), eps (nullable: 0) / z / gz [B x nd], gh [B x 2 nd], kl_rows [B] floats and kl 1 double nullable: all device; workspace
+// from vae_workspace_bytes, read only when kl is given; c = kl_weight / B.  Both return 1 outside 1 <= B < 2^31, 1 <= nd <= 256.
+size_t vae_workspace_bytes(long B);
+int launch_vae_sample(const float* h, const float* eps, long B, int nd, float* z, float* kl_rows, double* kl, void* workspace, hipStream_t s);
+int launch_vae_sample_backward(const float* h, const float* eps, const float* gz, long B, int nd, double c, float* gh, hipStream_t s);
+
 // ---------------------------------------------------------------- exact t-SNE of a device table (tsne.hip; gr_tsne_*_dev, gr_map_cells_dev)
 // Every pointer is device memory.  The launchers return 1 outside their limits (n <= 16384; affinities n >= 4, d >= 1; cells: grid sides 1 .. 1024),
 // launch_tsne_affinities 2 when the device refuses a memset.  One workspace of tsne_iter_workspace_bytes serves gradient, KL and update.

@@ -585,6 +585,65 @@ extern "C" int gr_mixture_dev(gr_ctx* c, const float* x, int64_t n, int d, int k
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ the sampling layer of a VAE (vae.hip)
+static int vae_check(gr_ctx* c, const char* who, bool null_ptr, int64_t B, int nd) {
+  if (null_ptr) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);
+  if (B <= 0 || nd <= 0) return fail(c, GR_ERR_INVALID, "%s: B %lld and nd %d must be positive", who, (long long)B, nd);
+  if (nd > 256) return fail(c, GR_ERR_UNSUPPORTED, "%s: nd %d: at most 256 latent dimensions", who, nd);
+  if (B >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "%s: B %lld: fewer than 2^31 rows", who, (long long)B);
+  return GR_OK;
+}
+extern "C" int gr_vae_sample_dev(gr_ctx* c, const float* h, const float* eps, int64_t B, int nd, float* z, float* kl_rows, double* kl) {
+  if (!c) return GR_ERR_INVALID;
+  TRY(vae_check(c, "gr_vae_sample_dev", !h || !z, B, nd));
+  Staging s(c);
+  auto scratch = s.reserve<char>(kl ? vae_workspace_bytes(B) : 0);
+  if (kl) TRY(s.grow());
+  if (launch_vae_sample(h, eps, B, nd, z, kl_rows, kl, kl ? s.ptr(scratch) : nullptr, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_vae_sample_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_vae_sample_backward_dev(gr_ctx* c, const float* h, const float* eps, const float* gz, int64_t B, int nd, double kl_weight, float* gh) {
+  if (!c) return GR_ERR_INVALID;
+  TRY(vae_check(c, "gr_vae_sample_backward_dev", !h || !gz || !gh, B, nd));
+  if (launch_vae_sample_backward(h, eps, gz, B, nd, kl_weight / (double)B, gh, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_vae_sample_backward_dev: unsupported size");
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+// the same kernels on staged copies of host tensors
+extern "C" int gr_vae_sample_host(gr_ctx* c, const float* h, const float* eps, int64_t B, int nd, float* z, float* kl_rows, double* kl) {
+  if (!c) return GR_ERR_INVALID;
+  TRY(vae_check(c, "gr_vae_sample_host", !h || !z, B, nd));
+  const size_t n = (size_t)B * nd;
+  Staging s(c);
+  auto scratch = s.reserve<char>(vae_workspace_bytes(B));
+  auto dh = s.reserve<float>(2 * n), de = s.reserve<float>(n), dz = s.reserve<float>(n), dr = s.reserve<float>((size_t)B);
+  auto dk = s.reserve<double>(1);
+  TRY(s.grow()); TRY(s.upload(dh, h));
+  if (eps) TRY(s.upload(de, eps));
+  if (launch_vae_sample(s.ptr(dh), eps ? s.ptr(de) : nullptr, B, nd, s.ptr(dz), kl_rows ? s.ptr(dr) : nullptr, kl ? s.ptr(dk) : nullptr, s.ptr(scratch), c->stream))
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_vae_sample_host: unsupported size");
+  LAUNCHCHK(c);
+  TRY(s.download(z, dz));
+  if (kl_rows) TRY(s.download(kl_rows, dr));
+  if (kl) TRY(s.download(kl, dk));
+  return s.finish();
+}
+extern "C" int gr_vae_sample_backward_host(gr_ctx* c, const float* h, const float* eps, const float* gz, int64_t B, int nd, double kl_weight, float* gh) {
+  if (!c) return GR_ERR_INVALID;
+  TRY(vae_check(c, "gr_vae_sample_backward_host", !h || !gz || !gh, B, nd));
+  const size_t n = (size_t)B * nd;
+  Staging s(c);
+  auto dh = s.reserve<float>(2 * n), de = s.reserve<float>(n), dg = s.reserve<float>(n), dout = s.reserve<float>(2 * n);
+  TRY(s.grow()); TRY(s.upload(dh, h)); TRY(s.upload(dg, gz));
+  if (eps) TRY(s.upload(de, eps));
+  if (launch_vae_sample_backward(s.ptr(dh), eps ? s.ptr(de) : nullptr, s.ptr(dg), B, nd, kl_weight / (double)B, s.ptr(dout), c->stream))
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_vae_sample_backward_host: unsupported size");
+  LAUNCHCHK(c);
+  TRY(s.download(gh, dout));
+  return s.finish();
+}
+
 // ------------------------------------------------------------------ exact t-SNE of a device table (tsne.hip)
 static int tsne_n_check(gr_ctx* c, const char* who, int64_t n, int64_t least) {
   if (n < least) return fail(c, GR_ERR_INVALID, "%s: n %lld: at least %lld rows", who, (long long)n, (long long)least);

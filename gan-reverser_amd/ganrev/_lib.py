@@ -205,6 +205,10 @@ _SIGS = {
     "gr_pca_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
     "gr_mixture_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "gr_vae_sample_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "gr_vae_sample_backward_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
+    "gr_vae_sample_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "gr_vae_sample_backward_host": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
     "gr_tsne_affinities_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P]),
     "gr_tsne_gradient_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, _P, _P]),
     "gr_tsne_update_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float]),
@@ -637,6 +641,53 @@ class Context:
         int32 / post_dev / rowll_dev [n] floats (each may be None).  niter = 0 scores rows under the given parameters.  Enqueued; no host wait."""
         self.check(self.lib.gr_mixture_dev(self.h, _ptr(x_dev), int(n), int(d), int(k), int(niter), float(var_floor), _ptr(weights_dev), _ptr(means_dev),
                                            _ptr(vars_dev), _ptr(loglik_dev), _ptr(labels_dev), _ptr(post_dev), _ptr(rowll_dev)), "gr_mixture_dev")
+
+    VAE_MAX_ND = 256                 # gr_vae_sample_*: latent dimensions at most (include/ganrev.h GR_VAE_MAX_ND)
+
+    def vae_sample_dev(self, h_dev, eps_dev, B, nd, z_dev, kl_rows_dev=None, kl_dev=None):
+        """gr_vae_sample_dev (1 <= B < 2^31, nd <= 256): h_dev [B x 2 nd] = (mu | logvar), eps_dev [B x nd] or None (eps = 0) ->
+        z_dev [B x nd] = mu + exp(logvar / 2) eps, kl_rows_dev [B] floats and kl_dev, one double, their mean (each may be None).  Enqueued; no host wait."""
+        self.check(self.lib.gr_vae_sample_dev(self.h, _ptr(h_dev), _ptr(eps_dev), int(B), int(nd), _ptr(z_dev), _ptr(kl_rows_dev), _ptr(kl_dev)),
+                   "gr_vae_sample_dev")
+
+    def vae_sample_backward_dev(self, h_dev, eps_dev, gz_dev, B, nd, kl_weight, gh_dev):
+        """gr_vae_sample_backward_dev: gh_dev [B x 2 nd] = the gradient of recon + kl_weight mean_i KL_i with respect to h, from gz_dev = d recon / d z.
+        Enqueued; no host wait."""
+        self.check(self.lib.gr_vae_sample_backward_dev(self.h, _ptr(h_dev), _ptr(eps_dev), _ptr(gz_dev), int(B), int(nd), float(kl_weight), _ptr(gh_dev)),
+                   "gr_vae_sample_backward_dev")
+
+    def vae_sample_host(self, h, eps=None, want_kl=True):
+        """gr_vae_sample_host on host arrays: h [B x 2 nd], eps [B x nd] or None -> (z, kl_rows, kl); the last two None without want_kl.  The bits of
+        vae_sample_dev."""
+        h = f32(h)
+        if h.ndim != 2 or h.shape[1] % 2:
+            raise GanrevError(f"vae_sample_host: h {h.shape} is not [B x 2 nd]")
+        B, nd = h.shape[0], h.shape[1] // 2
+        if eps is not None:
+            eps = f32(eps)
+            if eps.shape != (B, nd):
+                raise GanrevError(f"vae_sample_host: eps {eps.shape} is not [{B} x {nd}]")
+        z = np.empty((B, nd), np.float32)
+        rows = np.empty(B, np.float32) if want_kl else None
+        kl = np.empty(1, np.float64) if want_kl else None
+        self.check(self.lib.gr_vae_sample_host(self.h, _ptr(h), _ptr(eps), B, nd, _ptr(z), _ptr(rows), _ptr(kl)),
+                   "gr_vae_sample_host")
+        return z, rows, (float(kl[0]) if want_kl else None)
+
+    def vae_sample_backward_host(self, h, eps, gz, kl_weight):
+        """gr_vae_sample_backward_host on host arrays -> gh [B x 2 nd].  The bits of vae_sample_backward_dev."""
+        h, gz = f32(h), f32(gz)
+        if h.ndim != 2 or h.shape[1] % 2 or gz.shape != (h.shape[0], h.shape[1] // 2):
+            raise GanrevError(f"vae_sample_backward_host: h {h.shape} / gz {gz.shape} are not [B x 2 nd] / [B x nd]")
+        B, nd = gz.shape
+        if eps is not None:
+            eps = f32(eps)
+            if eps.shape != (B, nd):
+                raise GanrevError(f"vae_sample_backward_host: eps {eps.shape} is not [{B} x {nd}]")
+        gh = np.empty((B, 2 * nd), np.float32)
+        self.check(self.lib.gr_vae_sample_backward_host(self.h, _ptr(h), _ptr(eps), _ptr(gz), B, nd, float(kl_weight), _ptr(gh)),
+                   "gr_vae_sample_backward_host")
+        return gh
 
     PCA_MAX_D = 256                  # gr_pca_dev / gr_pca_project_dev: columns at most (include/ganrev.h)
 

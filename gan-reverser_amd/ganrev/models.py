@@ -158,6 +158,15 @@ def create_G_encoder(dimensions, noiseDim, cuda=True, seed=0):
     return w_init(model, "heuristic", seed)
 
 
+def create_VAE_encoder(dimensions, noiseDim, cuda=True, seed=0):
+    """The reference has no counterpart: models.lua holds no variational model (its README only asks to compare with one).  This is
+    create_G_encoder's trunk, unchanged, under the head a VAE needs: nn.Linear(512, 2 noiseDim) with no
+    nn.Tanh behind it - columns 0 .. noiseDim - 1 of the output are the mean, the rest the log-variance (ganrev.vae, gr_vae_sample_dev)."""
+    model = create_G_encoder(dimensions, 2 * noiseDim, cuda, seed)
+    model.modules = [m for m in model.modules if not isinstance(m, nn.Tanh)]
+    return model
+
+
 def create_G(dimensions, noiseDim, cuda=True, seed=0):
     return create_G3(dimensions, noiseDim, cuda, seed)        # models.lua:201-203
 

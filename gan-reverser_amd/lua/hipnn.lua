@@ -91,6 +91,10 @@ int gr_pca_project_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const doub
                        int k, int whiten, float* out_dev);
 int gr_mixture_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float var_floor, float* weights_dev, float* means_dev, float* vars_dev,
                    double* loglik_dev, int32_t* labels_dev, float* post_dev, float* rowll_dev);     /* diagonal Gaussian mixture by EM, d, k <= 256 */
+int gr_vae_sample_dev(gr_ctx*, const float* h_dev, const float* eps_dev, int64_t B, int nd, float* z_dev, float* kl_rows_dev, double* kl_dev);     /* a VAE's sampling layer, nd <= 256 */
+int gr_vae_sample_backward_dev(gr_ctx*, const float* h_dev, const float* eps_dev, const float* gz_dev, int64_t B, int nd, double kl_weight, float* gh_dev);
+int gr_vae_sample_host(gr_ctx*, const float* h, const float* eps, int64_t B, int nd, float* z, float* kl_rows, double* kl);
+int gr_vae_sample_backward_host(gr_ctx*, const float* h, const float* eps, const float* gz, int64_t B, int nd, double kl_weight, float* gh);
 typedef struct { float exaggeration; int32_t stop_lying_iter; float momentum0, momentum1; int32_t mom_switch_iter; float eta, min_gain; } gr_tsne_config;
 int gr_tsne_affinities_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double perplexity, float* p_dev, double* beta_dev, int32_t* info_dev);     /* exact t-SNE, n <= 16384 */
 int gr_tsne_gradient_dev(gr_ctx*, const float* p_dev, const float* y_dev, int64_t n, float exaggeration, float* grad_dev, double* z_dev);

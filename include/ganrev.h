@@ -551,6 +551,34 @@ int gr_mixture_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int
                    float* means_dev /*[k x d] in/out*/, float* vars_dev /*[k x d] in/out*/, double* loglik_dev /*[niter + 1]*/,
                    int32_t* labels_dev /*[n] nullable*/, float* post_dev /*[n] nullable*/, float* rowll_dev /*[n] nullable*/);
 
+/* ---- the sampling layer of a variational autoencoder (csrc/vae.hip; new: the reference has no counterpart) ----
+ * The layer between an encoder whose head emits a mean and a log-variance and a decoder: the reparameterisation z = mu + exp(logvar / 2) eps, its KL
+ * term against the unit Gaussian, and the backward of both.  h [B x 2 nd] floats: columns 0 .. nd - 1 of a row hold mu, columns nd .. 2 nd - 1 hold
+ * logvar; eps, z and gz are [B x nd], gh is [B x 2 nd].  A null eps is eps = 0 (z = mu: the encoder's mean, with the KL of the row as a score).
+ * The _dev calls take device pointers, enqueue on the ctx stream and return without waiting; the _host calls take host pointers, stage them, run
+ * the same kernels and wait: the same bits.
+ * Everything past the loads is fp64, every operation rounded on its own (no fused multiply-add); exp is the device library's.
+ * Forward.  s = exp(0.5 lv); se = s eps; z = (float)(mu + se).  Element KL: mm = mu mu, ss = s s, a = mm + ss, b = a - 1, d = b - lv, k = 0.5 d.
+ * kl_rows[i] = (float)K_i, K_i the k of row i added in column order from +0.0.  kl[0], the mean over rows: per block of 512 consecutive rows the K_i
+ * (fp64, not the rounded kl_rows) in row order from +0.0, the block partials in block order from +0.0, one division by B.
+ * Backward, for the loss recon + kl_weight mean_i K_i, gz = d recon / d z.  c = kl_weight / B, one fp64 division; s as in forward;
+ * gmu = (float)(gz + c mu); glv = (float)((gz eps) (0.5 s) + c (0.5 (s s - 1))); gh = (gmu | glv) in h's layout.
+ * No floating-point atomics, nothing depends on the CU count: two runs give the same bits.  16-byte loads and stores are used when nd % 4 == 0 and
+ * every pointer is 16-byte aligned, scalar ones otherwise: the same bits either way.
+ * Limits: 1 <= nd <= 256 (GR_VAE_MAX_ND), 1 <= B < 2^31; outside them GR_ERR_UNSUPPORTED with a gr_last_error text that names the value; null required
+ * pointers or non-positive B, nd: GR_ERR_INVALID.  Nothing is launched in either case and the context stays usable.  Finite inputs with
+ * |logvar| <= 80 are the contract; beyond that the call still returns.
+ * Scratch (only when kl is asked for): B + ceil(B / 512) doubles from the context. */
+#define GR_VAE_MAX_ND 256
+int gr_vae_sample_dev(gr_ctx* ctx, const float* h_dev, const float* eps_dev /*nullable: eps = 0*/, int64_t B, int nd, float* z_dev,
+                      float* kl_rows_dev /*[B] nullable*/, double* kl_dev /*1 double, nullable*/);
+int gr_vae_sample_backward_dev(gr_ctx* ctx, const float* h_dev, const float* eps_dev /*nullable: eps = 0*/, const float* gz_dev, int64_t B, int nd,
+                               double kl_weight, float* gh_dev /*[B x 2 nd]*/);
+int gr_vae_sample_host(gr_ctx* ctx, const float* h, const float* eps /*nullable*/, int64_t B, int nd, float* z, float* kl_rows /*nullable*/,
+                       double* kl /*nullable*/);
+int gr_vae_sample_backward_host(gr_ctx* ctx, const float* h, const float* eps /*nullable*/, const float* gz, int64_t B, int nd, double kl_weight,
+                                float* gh);
+
 /* ---- exact (dense) t-SNE of a device table (csrc/tsne.hip; new: the reference has no counterpart) ----
  * A two-dimensional, neighbour-preserving map of up to GR_TSNE_MAX_N rows: the joint matrix is n x n floats (1 GiB at the cap).  Barnes-Hut,
  * FFT interpolation and sparse affinities are out of scope.  Every pointer is device memory; the work is enqueued on the ctx stream and the calls
