@@ -580,6 +580,15 @@ size_t vae_workspace_bytes(long B);
 int launch_vae_sample(const float* h, const float* eps, long B, int nd, float* z, float* kl_rows, double* kl, void* workspace, hipStream_t s);
 int launch_vae_sample_backward(const float* h, const float* eps, const float* gz, long B, int nd, double c, float* gh, hipStream_t s);
 
+// ---------------------------------------------------------------- SSIM and MSE per image (quality.hip; gr_ssim_dev)
+// a, b [n x channels x h x w], ssim_rows [n], mse_rows [n] nullable, mean 1 double nullable: all device; workspace from ssim_workspace_bytes, read only
+// when mean is given.  sigma <= 0: the uniform window.  Returns 1 outside the limits of ssim_args_ok or for a data_range that is not > 0, and 2 when
+// the device refuses the kernel's LDS.
+bool ssim_args_ok(long n, int channels, int h, int w, int win);
+size_t ssim_workspace_bytes(long n);
+int launch_ssim(const float* a, const float* b, long n, int channels, int h, int w, int win, double sigma, double data_range, float* ssim_rows, float* mse_rows,
+                double* mean, void* workspace, hipStream_t s);
+
 // ---------------------------------------------------------------- exact t-SNE of a device table (tsne.hip; gr_tsne_*_dev, gr_map_cells_dev)
 // Every pointer is device memory.  The launchers return 1 outside their limits (n <= 16384; affinities n >= 4, d >= 1; cells: grid sides 1 .. 1024),
 // launch_tsne_affinities 2 when the device refuses a memset.  One workspace of tsne_iter_workspace_bytes serves gradient, KL and update.

@@ -644,6 +644,51 @@ extern "C" int gr_vae_sample_backward_host(gr_ctx* c, const float* h, const floa
   return s.finish();
 }
 
+// ------------------------------------------------------------------ SSIM and MSE per image (quality.hip)
+static int ssim_check(gr_ctx* c, const char* who, bool null_ptr, int64_t n, int channels, int h, int w, int win, double data_range) {
+  if (null_ptr) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);
+  if (n <= 0 || n >= ((int64_t)1 << 31) || channels <= 0) return fail(c, GR_ERR_INVALID, "%s: n %lld (1 .. 2^31 - 1) and channels %d must be positive", who, (long long)n, channels);
+  if (win < 3 || win > GR_SSIM_MAX_WIN || !(win & 1)) return fail(c, GR_ERR_INVALID, "%s: win %d: an odd window of 3 .. %d", who, win, GR_SSIM_MAX_WIN);
+  if (h < win || w < win || h > GR_SSIM_MAX_HW || w > GR_SSIM_MAX_HW)
+    return fail(c, GR_ERR_INVALID, "%s: h %d, w %d: images of win = %d .. %d pixels a side", who, h, w, win, GR_SSIM_MAX_HW);
+  if (!(data_range > 0)) return fail(c, GR_ERR_INVALID, "%s: data_range %g must be positive", who, data_range);
+  return ssim_args_ok((long)n, channels, h, w, win) ? GR_OK : fail(c, GR_ERR_INVALID, "%s: unsupported size", who);
+}
+static int ssim_launch_status(gr_ctx* c, const char* who, int r) {
+  if (r == 2) return fail(c, GR_ERR_HIP, "%s: the device refuses the kernel's LDS", who);
+  if (r) return fail(c, GR_ERR_INVALID, "%s: unsupported size", who);
+  LAUNCHCHK(c);
+  return GR_OK;
+}
+extern "C" int gr_ssim_dev(gr_ctx* c, const float* a, const float* b, int64_t n, int channels, int h, int w, int win, double sigma, double data_range,
+                           float* ssim_rows, float* mse_rows, double* mean) {
+  if (!c) return GR_ERR_INVALID;
+  TRY(ssim_check(c, "gr_ssim_dev", !a || !b || !ssim_rows, n, channels, h, w, win, data_range));
+  Staging s(c);
+  auto scratch = s.reserve<char>(mean ? ssim_workspace_bytes((long)n) : 0);
+  if (mean) TRY(s.grow());
+  return ssim_launch_status(c, "gr_ssim_dev", launch_ssim(a, b, (long)n, channels, h, w, win, sigma, data_range, ssim_rows, mse_rows, mean,
+                                                          mean ? s.ptr(scratch) : nullptr, c->stream));
+}
+// the same kernels on staged copies of host tensors
+extern "C" int gr_ssim_host(gr_ctx* c, const float* a, const float* b, int64_t n, int channels, int h, int w, int win, double sigma, double data_range,
+                            float* ssim_rows, float* mse_rows, double* mean) {
+  if (!c) return GR_ERR_INVALID;
+  TRY(ssim_check(c, "gr_ssim_host", !a || !b || !ssim_rows, n, channels, h, w, win, data_range));
+  const size_t elems = (size_t)n * channels * h * w;
+  Staging s(c);
+  auto scratch = s.reserve<char>(ssim_workspace_bytes((long)n));
+  auto da = s.reserve<float>(elems), db = s.reserve<float>(elems), ds = s.reserve<float>((size_t)n), dm = s.reserve<float>((size_t)n);
+  auto dq = s.reserve<double>(1);
+  TRY(s.grow()); TRY(s.upload(da, a)); TRY(s.upload(db, b));
+  TRY(ssim_launch_status(c, "gr_ssim_host", launch_ssim(s.ptr(da), s.ptr(db), (long)n, channels, h, w, win, sigma, data_range, s.ptr(ds),
+                                                        mse_rows ? s.ptr(dm) : nullptr, mean ? s.ptr(dq) : nullptr, s.ptr(scratch), c->stream)));
+  TRY(s.download(ssim_rows, ds));
+  if (mse_rows) TRY(s.download(mse_rows, dm));
+  if (mean) TRY(s.download(mean, dq));
+  return s.finish();
+}
+
 // ------------------------------------------------------------------ exact t-SNE of a device table (tsne.hip)
 static int tsne_n_check(gr_ctx* c, const char* who, int64_t n, int64_t least) {
   if (n < least) return fail(c, GR_ERR_INVALID, "%s: n %lld: at least %lld rows", who, (long long)n, (long long)least);

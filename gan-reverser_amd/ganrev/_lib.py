@@ -209,6 +209,8 @@ _SIGS = {
     "gr_vae_sample_backward_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
     "gr_vae_sample_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gr_vae_sample_backward_host": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
+    "gr_ssim_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P]),
+    "gr_ssim_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P]),
     "gr_tsne_affinities_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P]),
     "gr_tsne_gradient_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, _P, _P]),
     "gr_tsne_update_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float]),
@@ -286,6 +288,22 @@ def grid_shape(n_tiles, slots, channels, h, w, from_space, nrow, padding=0, marg
 def progress_grid_shape(channels, h, w, from_space, grid_h, grid_w):
     """(Cout, GH, GW) of gr_progress_grid_dev's grid: grid_h x grid_w cells and the seven rows that carry the epoch digits"""
     return (3 if from_space >= 0 else int(channels), int(grid_h) * int(h) + 7, int(grid_w) * int(w))
+
+
+SSIM_MAX_WIN, SSIM_MAX_HW = 11, 128      # gr_ssim_*: window and image side at most (include/ganrev.h GR_SSIM_MAX_WIN, GR_SSIM_MAX_HW)
+
+
+def ssim_check_args(n, channels, h, w, win, data_range):
+    """the limits of gr_ssim_dev, checked before the library is asked (needs no GPU): raises GanrevError naming the value"""
+    n, channels, h, w, win = int(n), int(channels), int(h), int(w), int(win)
+    if not (1 <= n < 2 ** 31) or channels < 1:
+        raise GanrevError(f"ssim: n {n} (1 .. 2^31 - 1) and channels {channels} must be positive")
+    if win < 3 or win > SSIM_MAX_WIN or win % 2 == 0:
+        raise GanrevError(f"ssim: win {win}: an odd window of 3 .. {SSIM_MAX_WIN}")
+    if min(h, w) < win or max(h, w) > SSIM_MAX_HW:
+        raise GanrevError(f"ssim: h {h}, w {w}: images of win = {win} .. {SSIM_MAX_HW} pixels a side")
+    if not float(data_range) > 0:
+        raise GanrevError(f"ssim: data_range {data_range} must be positive")
 
 
 class Context:
@@ -688,6 +706,28 @@ class Context:
         self.check(self.lib.gr_vae_sample_backward_host(self.h, _ptr(h), _ptr(eps), _ptr(gz), B, nd, float(kl_weight), _ptr(gh)),
                    "gr_vae_sample_backward_host")
         return gh
+
+    def ssim_dev(self, a_dev, b_dev, n, channels, h, w, ssim_rows_dev, mse_rows_dev=None, ssim_mean_dev=None, win=11, sigma=1.5, data_range=1.0):
+        """gr_ssim_dev: a_dev, b_dev [n x channels x h x w] floats -> ssim_rows_dev [n] floats, the structural similarity index per image over the valid
+        positions of a win x win Gaussian window (sigma <= 0: uniform); mse_rows_dev [n] floats and ssim_mean_dev, one double (each may be None).
+        win odd, 3 .. 11, <= min(h, w); h, w <= 128.  Enqueued; no host wait."""
+        ssim_check_args(n, channels, h, w, win, data_range)
+        self.check(self.lib.gr_ssim_dev(self.h, _ptr(a_dev), _ptr(b_dev), int(n), int(channels), int(h), int(w), int(win), float(sigma), float(data_range),
+                                        _ptr(ssim_rows_dev), _ptr(mse_rows_dev), _ptr(ssim_mean_dev)), "gr_ssim_dev")
+
+    def ssim_host(self, a, b, win=11, sigma=1.5, data_range=1.0, want_mse=True, want_mean=True):
+        """gr_ssim_host on host arrays [n x channels x h x w] -> (ssim_rows, mse_rows, mean); mse_rows / mean None when not wanted.  The bits of ssim_dev."""
+        a, b = f32(a), f32(b)
+        if a.ndim != 4 or a.shape != b.shape:
+            raise GanrevError(f"ssim_host: a {a.shape} / b {b.shape} are not two tables [n x channels x h x w] of one shape")
+        n, ch, h, w = a.shape
+        ssim_check_args(n, ch, h, w, win, data_range)
+        rows = np.empty(n, np.float32)
+        mse = np.empty(n, np.float32) if want_mse else None
+        mean = np.empty(1, np.float64) if want_mean else None
+        self.check(self.lib.gr_ssim_host(self.h, _ptr(a), _ptr(b), n, ch, h, w, int(win), float(sigma), float(data_range), _ptr(rows), _ptr(mse), _ptr(mean)),
+                   "gr_ssim_host")
+        return rows, mse, (float(mean[0]) if want_mean else None)
 
     PCA_MAX_D = 256                  # gr_pca_dev / gr_pca_project_dev: columns at most (include/ganrev.h)
 

@@ -5,6 +5,7 @@
   cosineSimilarity             apply_r.lua:396-400
   fixFaces                     apply_r.lua:324-352   noise -> G -> image -> R_fixer -> noise -> G -> image
   detectAnomalies              apply_r.lua:355-390   1 - torch.dist(image, fixed image), lowest `threshold` share = anomalies
+                                                     (--anomalyMetric ssim: the structural similarity of the two instead, ganrev.quality)
   createClusterImages          apply_r.lua:197-231   unsup.kmeans on the recovered noise, nearest-centroid pass, per-cluster lists
 
 These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
@@ -144,6 +145,19 @@ def detectAnomalies(nbImagesCalculations, threshold, images, model_g, attributes
     srt = np.sort(dist)                                                     # table.sort(distancesForSort)
     anomalyBelow = srt[max(int(math.floor(n * threshold)) - 1, 0)]          # distancesForSort[floor(#*threshold)]  (1-based)
     return dist, anomalyBelow, dist <= anomalyBelow
+
+
+def lowestShare(score, threshold):
+    """apply_r.lua:368-372 on any per-image score: (anomalyBelow, isAnomaly) - the floor(n * threshold)-th lowest value (1-based, at least the
+    first) and every row at or below it"""
+    srt = np.sort(score)                                                    # table.sort(distancesForSort)
+    below = srt[max(int(math.floor(len(srt) * threshold)) - 1, 0)]          # distancesForSort[floor(#*threshold)]  (1-based)
+    return below, score <= below
+
+
+def anomalyMetric(OPT):
+    """--anomalyMetric of a run: dist, the reference's 1 - torch.dist, unless asked otherwise"""
+    return getattr(OPT, "anomalyMetric", "dist")
 
 
 def initialCentroids(nbClusters, nDims, seed=1):
@@ -328,7 +342,9 @@ def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colo
     fixed_pairs, fixed_images_<n>[_unfixed] and anomalies; nothing but the finished pictures and the per-image distances leaves the GPU.
     -> what the run's arrays and summary are written from: dict(clusters = createClusterImagesDev's tuple with the faces on the host,
     fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple).  mixture: --mixture's step, called with the final
-    centroids while the tables are still where they are."""
+    centroids while the tables are still where they are.  --anomalyMetric ssim: the same rows are also scored with quality.ssim(images, fixed
+    images) where they lie, the lowest 15 % of THAT score are the anomalies (anomalies = (ssim, below, flags)), and the distances come back
+    beside them as `distances`."""
     from . import render
     ctx, N = images.ctx, images.shape[0]
     chw = images.size // N
@@ -352,16 +368,20 @@ def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colo
     fixed_host = np.concatenate([fixed.rows(lo, min(lo + OPT.batchSize, nbFixed)).numpy() for lo in range(0, nbFixed, OPT.batchSize)])
     fixed.free()                # (one transfer per batch, as every other step here moves batches; the host array is nbFixed images either way)
     fixedCalc = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbCalc), OPT.batchSize)                              # :360-363
-    dist = 1.0 - ctx.l2_distance_rows_dev(images.ptr, fixedCalc.ptr, nbCalc, chw)                                       # :366, scored where the images lie
-    fixedCalc.free()
-    srt = np.sort(dist)
-    below = srt[max(int(math.floor(nbCalc * 0.15)) - 1, 0)]                                                             # :371-372
-    is_anom = dist <= below
+    try:
+        dist = 1.0 - ctx.l2_distance_rows_dev(images.ptr, fixedCalc.ptr, nbCalc, chw)                                   # :366, scored where the images lie
+        score = dist
+        if anomalyMetric(OPT) == "ssim":
+            from . import quality
+            score, _, _ = quality.ssim(images.rows(0, nbCalc), fixedCalc)
+    finally:
+        fixedCalc.free()
+    below, is_anom = lowestShare(score, 0.15)                                                                           # :371-372
     if out:
         render.anomalies_grid(images, is_anom[:min(512 + 16, nbCalc)], colorSpace, path=out("anomalies.png"))           # :374-389
     if mixture is not None:
         mixture(attributes, centroids, images)
-    return dict(clusters=(centroids, counts, clusters, list(faces_host)), fixed=fixed_host, anomalies=(dist, below, is_anom))
+    return dict(clusters=(centroids, counts, clusters, list(faces_host)), fixed=fixed_host, anomalies=(score, below, is_anom), distances=dist)
 
 
 def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributesFixer, by_attr, by_pix, mixture=None):
@@ -474,6 +494,8 @@ def parse(argv=None):
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--resident", action="store_true", help="device-resident pipeline only: analyse the tables where the embedding wrote them; the image table is never copied to the host")
     p.add_argument("--render", action="store_true", help="also write the reference's pictures as PNG files (ganrev.render; colour space: the checkpoint's, y / rgb for 1- / 3-channel --synthetic nets)")
+    # absent from the namespace unless given: anomalyMetric() supplies dist, and a run without the option writes the summary it wrote before it existed
+    p.add_argument("--anomalyMetric", choices=["dist", "ssim"], default=argparse.SUPPRESS, help="the per-image score whose lowest 15 %% are the anomalies: dist, the reference's 1 - torch.dist(image, fixed image) (default), or ssim, the structural similarity of the two (ganrev.quality, 11 x 11 Gaussian window: images of 11 .. 128 pixels a side), scored where the tables lie: needs --resident or --render; writes anomaly_ssim.npy beside anomaly_distances.npy")
     p.add_argument("--refine", type=int, default=0, metavar="STEPS", help="refine the recovered noise through G: STEPS Adam steps per image on the MSE between G(z) and the image, starting at R's estimate (ganrev.refine; 0, the reference's behaviour: R's estimate is final)")
     p.add_argument("--refine_lr", type=float, default=0.01, help="Adam learning rate of --refine")
     # the principal-axes options: absent from the namespace unless given, like the clustering options below - pcaOptions() supplies "off"
@@ -498,6 +520,15 @@ def parse(argv=None):
         p.error("--refine runs on the device-resident tables: not with --host")
     if OPT.refine < 0:
         p.error("--refine: a step count")
+    if anomalyMetric(OPT) == "ssim":
+        if OPT.host:
+            p.error("--anomalyMetric ssim scores the device-resident tables: not with --host")
+        if not (OPT.resident or OPT.render):
+            p.error("--anomalyMetric ssim scores the tables where they lie: give --resident (or --render)")
+        if OPT.synthetic:
+            _, sh, sw, _ = (int(v) for v in OPT.synthetic.split("x"))
+            if min(sh, sw) < 11 or max(sh, sw) > L.SSIM_MAX_HW:
+                p.error(f"--anomalyMetric ssim: images of 11 .. {L.SSIM_MAX_HW} pixels a side")
     if OPT.needles < 0:
         p.error("--needles: a file count")
     nbAxes, pcaSpace = pcaOptions(OPT)
@@ -580,6 +611,8 @@ def run(OPT):
     nbAxes, pcaSpace = pcaOptions(OPT)
     if nbAxes > nd:
         raise L.GanrevError(f"--pca {nbAxes}: at most noiseDim = {nd} axes")
+    if anomalyMetric(OPT) == "ssim":
+        L.ssim_check_args(min(1024, OPT.nbImages), dims[0], dims[1], dims[2], 11, 1.0)      # before anything is allocated
     reads = bool(OPT.needles or OPT.real)
     if reads:                                                                # --cacheDataset then keeps the files on the GPU
         DATASET = scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], ctx=ctx, reads=True)
@@ -835,8 +868,13 @@ def run(OPT):
     say("Detecting anomalies...")                                             # :186-191
     nbCalc = min(1024, N)
     dist, below, is_anom = rendered["anomalies"] if rendered else detectAnomalies(nbCalc, 0.15, images, MODEL_G, attributesFixer, OPT.batchSize)
+    if anomalyMetric(OPT) == "ssim":                                          # (parse: only where analyseDev ran) the score is the SSIM, the distances beside it
+        np.save(out("anomaly_ssim.npy"), dist)
+        dist = rendered["distances"]
     np.save(out("anomaly_distances.npy"), dist)
     summary.update(anomaly_below=float(below), anomalies=int(is_anom.sum()))
+    if hasattr(OPT, "anomalyMetric"):
+        summary["anomaly_metric"] = OPT.anomalyMetric
     json.dump(summary, open(out("summary.json"), "w"), indent=1)
     say("<apply_r> results in", OPT.writeTo, summary)
     return summary

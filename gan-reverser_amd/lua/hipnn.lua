@@ -95,6 +95,8 @@ int gr_vae_sample_dev(gr_ctx*, const float* h_dev, const float* eps_dev, int64_t
 int gr_vae_sample_backward_dev(gr_ctx*, const float* h_dev, const float* eps_dev, const float* gz_dev, int64_t B, int nd, double kl_weight, float* gh_dev);
 int gr_vae_sample_host(gr_ctx*, const float* h, const float* eps, int64_t B, int nd, float* z, float* kl_rows, double* kl);
 int gr_vae_sample_backward_host(gr_ctx*, const float* h, const float* eps, const float* gz, int64_t B, int nd, double kl_weight, float* gh);
+int gr_ssim_dev(gr_ctx*, const float* a_dev, const float* b_dev, int64_t n, int channels, int h, int w, int win, double sigma, double data_range, float* ssim_rows_dev, float* mse_rows_dev, double* ssim_mean_dev);     /* SSIM and MSE per image, h, w <= 128 */
+int gr_ssim_host(gr_ctx*, const float* a, const float* b, int64_t n, int channels, int h, int w, int win, double sigma, double data_range, float* ssim_rows, float* mse_rows, double* ssim_mean);
 typedef struct { float exaggeration; int32_t stop_lying_iter; float momentum0, momentum1; int32_t mom_switch_iter; float eta, min_gain; } gr_tsne_config;
 int gr_tsne_affinities_dev(gr_ctx*, const float* x_dev, int64_t n, int d, double perplexity, float* p_dev, double* beta_dev, int32_t* info_dev);     /* exact t-SNE, n <= 16384 */
 int gr_tsne_gradient_dev(gr_ctx*, const float* p_dev, const float* y_dev, int64_t n, float exaggeration, float* grad_dev, double* z_dev);

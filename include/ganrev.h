@@ -579,6 +579,40 @@ int gr_vae_sample_host(gr_ctx* ctx, const float* h, const float* eps /*nullable*
 int gr_vae_sample_backward_host(gr_ctx* ctx, const float* h, const float* eps /*nullable*/, const float* gz, int64_t B, int nd, double kl_weight,
                                 float* gh);
 
+/* ---- image-to-image scores: the structural similarity index and the mean squared error (csrc/quality.hip; new: the reference has no counterpart) ----
+ * gr_ssim_dev: a_dev, b_dev [n x channels x h x w] floats -> ssim_rows_dev [n] floats, the SSIM of Wang et al. 2004 per image over the valid window
+ * positions (no padding); mse_rows_dev [n] floats (nullable), the mean squared error per image from the same pass; ssim_mean_dev (1 double, nullable), the
+ * mean of the per-image SSIM.  Every pointer is device memory; the work is enqueued on the ctx stream and the call returns without waiting for it;
+ * scratch comes from the context.  gr_ssim_host takes host pointers, stages them once, runs the same kernels and waits: the same bits.
+ * Everything past the loads is fp64, every operation rounded on its own (no fused multiply-add): var = sum w x^2 - mu^2 cancels, and fp32 window sums
+ * lose 4.5e-5 of the index on a flat bright image.  With x = a, y = b (a float enters by an exact conversion, a product of two floats is exact):
+ * Window.  sigma > 0: e[i] = exp(-(d d) / (2 (sigma sigma))), d = i - (win - 1) / 2, i = 0 .. win - 1, the host's exp; E = the e[i] added in index order
+ * from +0.0; g[i] = e[i] / E.  sigma <= 0: the uniform window g[i] = 1 / win.  The 2-D window is g (x) g, applied as two 1-D passes.
+ * Constants.  C1 = k1 k1, k1 = 0.01 data_range; C2 = k2 k2, k2 = 0.03 data_range.
+ * Horizontal.  Per channel, input row i and valid column c (ow = w - win + 1 of them), five chains over t = 0 .. win - 1 from +0.0:
+ * H = H + g[t] q[i][c + t], for q = x, y, x x, y y, x y.
+ * Vertical.  Per valid position (r, c) (oh = h - win + 1 rows), five chains over t from +0.0: V = V + g[t] H[r + t][c], giving mx, my, sxx, syy, sxy.
+ * Position.  mxx = mx mx, myy = my my, mxy = mx my; vx = sxx - mxx, vy = syy - myy, cxy = sxy - mxy; n1 = 2 mxy + C1, n2 = 2 cxy + C2,
+ * d1 = (mxx + myy) + C1, d2 = (vx + vy) + C2; S = (n1 n2) / (d1 d2).  The x and y chains are the same instruction sequence and every operation that
+ * mixes them is commutative: swapping a and b gives the same bits, and a == b gives n1 == d1 and n2 == d2 bit for bit, so S == 1.0 exactly.
+ * Image.  R_r = the S of row r added in column order from +0.0; P_ch = the R_r of channel ch in row order from +0.0; Q = the P_ch in channel order
+ * from +0.0; q = Q / (channels oh ow), one division; ssim_rows[i] = (float)q.  mse_rows[i] is formed the same way over every pixel: e = d d, d = x - y;
+ * rows of e in column order, the rows in row order, the channels in channel order, one division by channels h w, one rounding to float.
+ * Mean.  ssim_mean[0]: per block of 512 consecutive images the q (fp64, not the rounded ssim_rows) in image order from +0.0, the block partials in
+ * block order from +0.0, one division by n.
+ * No floating-point atomics, nothing depends on the CU count or on how many rows of an image the kernel holds at a time: two runs give the same bits.
+ * 16-byte loads are used when w % 4 == 0 and both tables are 16-byte aligned, scalar ones otherwise: the same bits either way.
+ * Limits: win odd, 3 <= win <= GR_SSIM_MAX_WIN (11), win <= min(h, w), h, w <= GR_SSIM_MAX_HW (128), channels >= 1, 1 <= n < 2^31, data_range > 0 (a NaN is
+ * refused too); anything else, and a null a, b or ssim_rows, is GR_ERR_INVALID with a gr_last_error text that names the value, before any launch; the
+ * context stays usable.  Non-finite pixels are outside the contract (the call still returns).  a and b may be the same table.
+ * Scratch (only when ssim_mean is asked for): n + ceil(n / 512) doubles from the context. */
+#define GR_SSIM_MAX_WIN 11
+#define GR_SSIM_MAX_HW 128
+int gr_ssim_dev(gr_ctx* ctx, const float* a_dev, const float* b_dev, int64_t n, int channels, int h, int w, int win, double sigma, double data_range,
+                float* ssim_rows_dev /*[n]*/, float* mse_rows_dev /*[n] nullable*/, double* ssim_mean_dev /*1 double, nullable*/);
+int gr_ssim_host(gr_ctx* ctx, const float* a, const float* b, int64_t n, int channels, int h, int w, int win, double sigma, double data_range,
+                 float* ssim_rows /*[n]*/, float* mse_rows /*[n] nullable*/, double* ssim_mean /*nullable*/);
+
 /* ---- exact (dense) t-SNE of a device table (csrc/tsne.hip; new: the reference has no counterpart) ----
  * A two-dimensional, neighbour-preserving map of up to GR_TSNE_MAX_N rows: the joint matrix is n x n floats (1 GiB at the cap).  Barnes-Hut,
  * FFT interpolation and sparse affinities are out of scope.  Every pointer is device memory; the work is enqueued on the ctx stream and the calls
