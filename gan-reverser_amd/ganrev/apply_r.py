@@ -7,17 +7,33 @@
   detectAnomalies              apply_r.lua:355-390   1 - torch.dist(image, fixed image), lowest `threshold` share = anomalies
                                                      (--anomalyMetric ssim: the structural similarity of the two instead, ganrev.quality)
   createClusterImages          apply_r.lua:197-231   unsup.kmeans on the recovered noise, nearest-centroid pass, per-cluster lists
+  main, run                    apply_r.lua:25-193    the whole analysis as one run (parse: its options, apply_r.lua:13-23)
+
+  embed_dev, embedImagesDev    apply_r.lua:145-153   the same where the tables stay on the GPU: G(noise), or R over an image table (--real, --needles)
+  createSimilaritySearchDev    apply_r.lua:265-318   ... the needle rows searched where the embeddings were written
+  searchByExample              -                     ... needles from outside the corpus (--needles)
+  createClusterImagesDev       apply_r.lua:197-243   ... clusters and average faces; its parts: checkClusterCount, initialCentroids,
+                                                     selectClusterMembers, clusterTableDev, clusterHostTable
+  analyseDev, renderAnalysis   apply_r.lua:158-191   ... clusters, fixed faces and anomalies (--resident), with the pictures (--render)
+  lowestShare, anomalyMetric   apply_r.lua:368-372   the anomaly rule on any per-image score
+  principalAxesOfTable, mapOfTable, mixtureOfTable   --pca, --map, --mixture: ganrev.pca, ganrev.tsne, ganrev.mixture over the attribute table
+  clusterOptions, pcaOptions, mapOptions, mixtureOptions   what a run's options say about each, with the defaults
 
 These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
 frames and fields apply_r.lua draws) come from ganrev.render, on the GPU, and main() writes them with --render.
 """
+import contextlib
+import functools
+import json
 import math
+import os
+import time
 
 import numpy as np
 
 from . import _lib as L
-from . import scripts
-from .nn_utils import DeviceTensor, forwardBatched, forwardBatchedDev
+from . import render, scripts
+from .nn_utils import DeviceScope, DeviceTensor, createNoiseInputs, createNoiseInputsDev, deviceTable, forwardBatched, forwardBatchedDev
 
 
 def embed(model_g, model_r, noise, batchSize=32, model_r_fixer=None):
@@ -142,9 +158,7 @@ def detectAnomalies(nbImagesCalculations, threshold, images, model_g, attributes
     model_g.evaluate()
     fixed = forwardBatched(model_g, attributesFixer[:n], batchSize)
     dist = 1.0 - L.default_context().l2_distance_rows(images[:n], fixed)
-    srt = np.sort(dist)                                                     # table.sort(distancesForSort)
-    anomalyBelow = srt[max(int(math.floor(n * threshold)) - 1, 0)]          # distancesForSort[floor(#*threshold)]  (1-based)
-    return dist, anomalyBelow, dist <= anomalyBelow
+    return (dist,) + lowestShare(dist, threshold)                           # :368-372
 
 
 def lowestShare(score, threshold):
@@ -192,13 +206,10 @@ def clusterTableDev(ctx, table_ptr, N, d, k, nbIterations, m, centroids0, closes
     """apply_r.lua:198-227 on a device table [N x d].  Up to 32 clusters: gr_kmeans_dev, gr_cosine_assign_dev, gr_cluster_members_dev, as ever;
     above: gr_cluster_dev, one enqueue.  faces_of = (images pointer, rows of that table, values per image, output pointer) adds gr_cluster_faces_dev
     (apply_r.lua:233-243) while the lists are still on the device.  -> (centroids, counts, clusters)"""
-    cent = ctx.upload(np.ascontiguousarray(centroids0, np.float32).reshape(k, d))
     sizes = [4 * k, 4 * N, 4 * N, 8 * k * m, 4 * k * m, 4 * k, 4 * k]               # counts, labels, sims, rows, their sims, kept, cluster sizes
-    bufs = [cent]
-    try:
-        for b in sizes:
-            bufs.append(ctx.malloc(b))
-        tot, lab, sim, rows, rsim, kept, csize = bufs[1:]
+    with DeviceScope(ctx) as bufs:
+        cent = bufs.upload(np.ascontiguousarray(centroids0, np.float32).reshape(k, d))
+        tot, lab, sim, rows, rsim, kept, csize = [bufs.malloc(b) for b in sizes]
         if k <= NARROW_MAX_CLUSTERS:
             ctx.kmeans_dev(table_ptr, N, d, k, nbIterations, cent, tot, lab)                    # :198
             ctx.cosine_assign_dev(table_ptr, N, d, cent, k, not closest, lab, sim)              # :205-217
@@ -210,20 +221,31 @@ def clusterTableDev(ctx, table_ptr, N, d, k, nbIterations, m, centroids0, closes
             ctx.cluster_faces_dev(images_ptr, n_rows, chw, rows, kept, k, m, faces_ptr)         # :233-243 (zeros for an empty cluster)
         centroids, counts = ctx.download(cent, (k, d)), ctx.download(tot, (k,))
         hrows, hsim, hkept = ctx.download(rows, (k, m), np.int64), ctx.download(rsim, (k, m)), ctx.download(kept, (k,), np.int32)
-    finally:
-        for b in bufs:
-            ctx.free(b)
     clusters = [[(int(r), float(v)) for r, v in zip(hrows[j, :hkept[j]], hsim[j, :hkept[j]])] for j in range(k)]
     return centroids, counts, clusters
 
 
 def clusterHostTable(ctx, attributes, k, nbIterations, m, centroids0, closest, faces_of=None):
     """clusterTableDev for a host attribute table: uploaded to a temporary buffer first (more than 32 clusters: gr_cluster_dev has no host variant)"""
-    table = ctx.upload(np.ascontiguousarray(attributes, np.float32))
-    try:
-        return clusterTableDev(ctx, table, attributes.shape[0], attributes.shape[1], k, nbIterations, m, centroids0, closest, faces_of)
-    finally:
-        ctx.free(table)
+    with deviceTable(ctx, attributes) as (table, N, d):
+        return clusterTableDev(ctx, table, N, d, k, nbIterations, m, centroids0, closest, faces_of)
+
+
+def clusterHostRoute(ctx, attributes, k, nbIterations, m, centroids0, closest):
+    """apply_r.lua:198-227 for a host table of up to 32 clusters -> (centroids, counts, label, sim, [kept row index arrays])"""
+    centroids, counts, _ = ctx.kmeans(attributes, k, nbIterations, centroids0)                     # :198
+    label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
+    return centroids, counts, label, sim, selectClusterMembers(label, sim, k, m)                    # :218-227
+
+
+def clusterInputs(nbClusters, nbMaxPerCluster, attributes, centroids0, seed):
+    """-> (k, m, the attribute table - a DeviceTensor as it is, anything else as a float32 array -, the initial centroids: drawn unless given)"""
+    k = checkClusterCount(nbClusters)
+    if not isinstance(attributes, DeviceTensor):
+        attributes = np.asarray(attributes, np.float32)
+    if centroids0 is None:
+        centroids0 = initialCentroids(k, attributes.size // attributes.shape[0], seed)
+    return k, int(nbMaxPerCluster), attributes, centroids0
 
 
 def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, centroids0=None, seed=1, closest=False):
@@ -237,26 +259,16 @@ def createClusterImages(nbClusters, nbIterations, nbMaxPerCluster, images, attri
 
     Up to 4096 clusters.  The reference's 20, and anything up to 32, run as ever; above 32 the attribute table is uploaded and clustered by
     gr_cluster_dev (lists of at most 128 rows), and the faces are averaged from its lists the same way."""
-    attributes = np.asarray(attributes, np.float32)
-    N, d = attributes.shape
-    nbClusters = checkClusterCount(nbClusters)
-    if centroids0 is None:
-        centroids0 = initialCentroids(nbClusters, d, seed)
+    k, m, attributes, centroids0 = clusterInputs(nbClusters, nbMaxPerCluster, attributes, centroids0, seed)
     ctx = L.default_context()
-    if nbClusters > NARROW_MAX_CLUSTERS:
-        centroids, counts, clusters = clusterHostTable(ctx, attributes, nbClusters, nbIterations, int(nbMaxPerCluster), centroids0, closest)
-        images = np.asarray(images, np.float32)
-        faces = [images[[r for r, _ in cl]].mean(axis=0, dtype=np.float64).astype(np.float32) if cl else np.zeros(images.shape[1:], np.float32)
-                 for cl in clusters]                                                                # :233-243
-        return centroids, counts, clusters, faces
-    centroids, counts, _ = ctx.kmeans(attributes, nbClusters, nbIterations, centroids0)            # :198
-    label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
-    clusters, faces = [], []
+    if k > NARROW_MAX_CLUSTERS:
+        centroids, counts, clusters = clusterHostTable(ctx, attributes, k, nbIterations, m, centroids0, closest)
+    else:
+        centroids, counts, _, sim, keeps = clusterHostRoute(ctx, attributes, k, nbIterations, m, centroids0, closest)
+        clusters = [[(int(r), float(sim[r])) for r in keep] for keep in keeps]
     images = np.asarray(images, np.float32)
-    for keep in selectClusterMembers(label, sim, nbClusters, nbMaxPerCluster):                      # :218-227
-        clusters.append([(int(r), float(sim[r])) for r in keep])
-        faces.append(images[keep].mean(axis=0, dtype=np.float64).astype(np.float32) if len(keep)
-                     else np.zeros(images.shape[1:], np.float32))                                   # :233-243
+    faces = [images[[r for r, _ in cl]].mean(axis=0, dtype=np.float64).astype(np.float32) if cl else np.zeros(images.shape[1:], np.float32)
+             for cl in clusters]                                                                    # :233-243
     return centroids, counts, clusters, faces
 
 
@@ -271,36 +283,20 @@ def createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, at
     -> (centroids, counts, clusters, faces) with faces a DeviceTensor [nbClusters x C x H x W] (the caller frees it)."""
     ctx = images.ctx
     chw = images.size // images.shape[0]
-    k, m = checkClusterCount(nbClusters), int(nbMaxPerCluster)
+    k, m, attributes, centroids0 = clusterInputs(nbClusters, nbMaxPerCluster, attributes, centroids0, seed)
     faces = DeviceTensor(ctx, (k,) + tuple(images.shape[1:]))
-    faces_of = (images.ptr, images.shape[0], chw, faces.ptr)
-    if isinstance(attributes, DeviceTensor) or k > NARROW_MAX_CLUSTERS:     # (a host table of more than 32 clusters is uploaded: gr_cluster_dev)
-        try:
-            if isinstance(attributes, DeviceTensor):
-                N = attributes.shape[0]
-                d = attributes.size // N
-                if centroids0 is None:
-                    centroids0 = initialCentroids(k, d, seed)
-                centroids, counts, clusters = clusterTableDev(ctx, attributes.ptr, N, d, k, nbIterations, m, centroids0, closest, faces_of)
-            else:
-                attributes = np.asarray(attributes, np.float32)
-                if centroids0 is None:
-                    centroids0 = initialCentroids(k, attributes.shape[1], seed)
-                centroids, counts, clusters = clusterHostTable(ctx, attributes, k, nbIterations, m, centroids0, closest, faces_of)
-        except Exception:
-            faces.free()
-            raise
-        return centroids, counts, clusters, faces
-    attributes = np.asarray(attributes, np.float32)
-    N, d = attributes.shape
-    if centroids0 is None:
-        centroids0 = initialCentroids(nbClusters, d, seed)
-    centroids, counts, _ = ctx.kmeans(attributes, nbClusters, nbIterations, centroids0)            # :198
-    label, sim = ctx.cosine_assign(attributes, centroids, take_min=not closest)                     # :205-217
-    clusters = []
-    for j, keep in enumerate(selectClusterMembers(label, sim, nbClusters, nbMaxPerCluster)):        # :218-227
-        clusters.append([(int(r), float(sim[r])) for r in keep])
-        ctx.rows_mean_dev(images.ptr, images.shape[0], chw, keep, faces.ptr + 4 * chw * j)          # :233-243 (zeros for an empty cluster)
+    try:
+        if isinstance(attributes, DeviceTensor) or k > NARROW_MAX_CLUSTERS: # (a host table of more than 32 clusters is uploaded: gr_cluster_dev)
+            with deviceTable(ctx, attributes) as (table, N, d):
+                centroids, counts, clusters = clusterTableDev(ctx, table, N, d, k, nbIterations, m, centroids0, closest, (images.ptr, images.shape[0], chw, faces.ptr))
+        else:
+            centroids, counts, _, sim, keeps = clusterHostRoute(ctx, attributes, k, nbIterations, m, centroids0, closest)
+            clusters = [[(int(r), float(sim[r])) for r in keep] for keep in keeps]
+            for j, keep in enumerate(keeps):
+                ctx.rows_mean_dev(images.ptr, images.shape[0], chw, keep, faces.ptr + 4 * chw * j)      # :233-243 (zeros for an empty cluster)
+    except Exception:
+        faces.free()
+        raise
     return centroids, counts, clusters, faces
 
 
@@ -309,29 +305,15 @@ def principalAxesOfTable(ctx, attributes, K, whitened=False):
     uploaded to a temporary buffer first as clusterHostTable does.  -> (PrincipalAxes, which the caller closes; the [N x K] coordinates along
     the first K axes on the host, not whitened; the whitened [N x K] table as a DeviceTensor the caller frees, or None)"""
     from . import pca as P
-    on_device = isinstance(attributes, DeviceTensor)
-    N = attributes.shape[0]
-    d = (attributes.size if on_device else int(np.prod(attributes.shape))) // N
-    table = attributes.ptr if on_device else ctx.upload(np.ascontiguousarray(attributes, np.float32))
-    axes = None
-    try:
+    with deviceTable(ctx, attributes) as (table, N, d):
         axes = P.principalAxes(ctx, table, N, d)
-        plain = P.project(ctx, axes, table, N, K, whiten=False)
         try:
-            coords = plain.numpy()
-        finally:
-            plain.free()
-        white = P.project(ctx, axes, table, N, K, whiten=True) if whitened else None
-        if not on_device:
-            ctx.synchronize()                                                 # the projection reads the temporary table
-        return axes, coords, white
-    except Exception:
-        if axes is not None:
+            with P.project(ctx, axes, table, N, K, whiten=False) as plain:
+                coords = plain.numpy()
+            return axes, coords, P.project(ctx, axes, table, N, K, whiten=True) if whitened else None
+        except Exception:
             axes.close()
-        raise
-    finally:
-        if not on_device:
-            ctx.free(table)
+            raise
 
 
 def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colorSpace=None, by_attr=None, by_pix=None, mixture=None):
@@ -345,37 +327,34 @@ def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colo
     centroids while the tables are still where they are.  --anomalyMetric ssim: the same rows are also scored with quality.ssim(images, fixed
     images) where they lie, the lowest 15 % of THAT score are the anomalies (anomalies = (ssim, below, flags)), and the distances come back
     beside them as `distances`."""
-    from . import render
     ctx, N = images.ctx, images.shape[0]
     chw = images.size // N
     nbClusters, nbIterations, nbMaxPerCluster, closest = clusterOptions(OPT)                                            # :159-161: 20, 15, 64 + 7
     centroids, counts, clusters, faces = createClusterImagesDev(nbClusters, nbIterations, nbMaxPerCluster, images, attributes, seed=OPT.seed, closest=closest)      # :158-163
-    for j, cl in enumerate(clusters):
-        if cl and out:                                                                                                  # :249
-            render.cluster_grid(images, [r for r, _ in cl], colorSpace, face_dev=faces.rows(j, j + 1), path=out("cluster_%02d.png" % (j + 1)))
-    faces_host = faces.numpy(); faces.free()
+    with faces:
+        for j, cl in enumerate(clusters):
+            if cl and out:                                                                                              # :249
+                render.cluster_grid(images, [r for r, _ in cl], colorSpace, face_dev=faces.rows(j, j + 1), path=out("cluster_%02d.png" % (j + 1)))
+        faces_host = faces.numpy()
     if by_attr is not None and out:                                                                                     # :170-172
         for i in range(len(by_attr)):
             render.similar_grid(images, by_attr[i], colorSpace, path=out("similar_attributes_%02d.png" % (i + 1)))
             render.similar_grid(images, by_pix[i], colorSpace, path=out("similar_pixelwise_%02d.png" % (i + 1)))
     MODEL_G.evaluate()
     nbFixed, nbCalc = min(512 + 16, N), min(1024, N)
-    fixed = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbFixed), OPT.batchSize)                                 # :349
-    if out:
-        render.fixed_pairs_grid(images, fixed, min(52, N), colorSpace, path=out("fixed_pairs.png"))                     # :325-342
-        render.fixed_images_grid(images, nbFixed, path=out("fixed_images_%d_unfixed.png" % nbFixed))                    # :345-347
-        render.fixed_images_grid(fixed, nbFixed, path=out("fixed_images_%d.png" % nbFixed))                             # :350-351
-    fixed_host = np.concatenate([fixed.rows(lo, min(lo + OPT.batchSize, nbFixed)).numpy() for lo in range(0, nbFixed, OPT.batchSize)])
-    fixed.free()                # (one transfer per batch, as every other step here moves batches; the host array is nbFixed images either way)
-    fixedCalc = forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbCalc), OPT.batchSize)                              # :360-363
-    try:
+    with forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbFixed), OPT.batchSize) as fixed:                          # :349
+        if out:
+            render.fixed_pairs_grid(images, fixed, min(52, N), colorSpace, path=out("fixed_pairs.png"))                 # :325-342
+            render.fixed_images_grid(images, nbFixed, path=out("fixed_images_%d_unfixed.png" % nbFixed))                # :345-347
+            render.fixed_images_grid(fixed, nbFixed, path=out("fixed_images_%d.png" % nbFixed))                         # :350-351
+        # (one transfer per batch, as every other step here moves batches; the host array is nbFixed images either way)
+        fixed_host = np.concatenate([fixed.rows(lo, min(lo + OPT.batchSize, nbFixed)).numpy() for lo in range(0, nbFixed, OPT.batchSize)])
+    with forwardBatchedDev(MODEL_G, attributesFixer.rows(0, nbCalc), OPT.batchSize) as fixedCalc:                       # :360-363
         dist = 1.0 - ctx.l2_distance_rows_dev(images.ptr, fixedCalc.ptr, nbCalc, chw)                                   # :366, scored where the images lie
         score = dist
         if anomalyMetric(OPT) == "ssim":
             from . import quality
             score, _, _ = quality.ssim(images.rows(0, nbCalc), fixedCalc)
-    finally:
-        fixedCalc.free()
     below, is_anom = lowestShare(score, 0.15)                                                                           # :371-372
     if out:
         render.anomalies_grid(images, is_anom[:min(512 + 16, nbCalc)], colorSpace, path=out("anomalies.png"))           # :374-389
@@ -389,12 +368,6 @@ def renderAnalysis(OPT, out, colorSpace, MODEL_G, images, attributes, attributes
     return analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out, colorSpace, by_attr, by_pix, mixture)
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# apply_r.lua:25-193 main(): the whole analysis as one run.  What the reference computes is written as arrays (.npy) and one
-# summary.json under --writeTo; with --render the pictures it saves (apply_r.lua:137-138, 245-258, 283-298, 325-351, 374-389) are written
-# beside them as PNG, under the reference's names: variations, cluster_%02d, similar_attributes_%02d, similar_pixelwise_%02d, fixed_pairs,
-# fixed_images_528[_unfixed], anomalies (the counts clamp to --nbImages).  G / R / R_fixer come from Torch7 checkpoints (ganrev.t7: train.lua:256, train_r.lua:234) or, with
-# --synthetic, from random-initialised nets of the requested shape (a smoke run: no trained checkpoint exists in this repository).
 def clusterOptions(OPT):
     """(nbClusters, nbIterations, nbMaxPerCluster, closest) of a run: the options given, else what apply_r.lua:159-163 hard-codes"""
     return (getattr(OPT, "nbClusters", 20), getattr(OPT, "nbIterations", 15), getattr(OPT, "nbMaxPerCluster", 64 + 7), bool(getattr(OPT, "closest", False)))
@@ -418,25 +391,14 @@ def mixtureOfTable(ctx, table, centroids, iterations, column_variances=None, nee
     uploaded to a temporary buffer first as clusterHostTable does - by ITER EM iterations from the clustering's final centroids; then every row,
     and every needle row [Q x d] if given, scored under it -> (Mixture, (labels, posterior, row log-likelihood), the needles' triple or None)"""
     from . import mixture as MX
-    on_device = isinstance(table, DeviceTensor)
-    N = table.shape[0]
-    d = (table.size if on_device else int(np.prod(table.shape))) // N
-    ptr = table.ptr if on_device else ctx.upload(np.ascontiguousarray(table, np.float32))
-    try:
+    with deviceTable(ctx, table) as (ptr, N, d):
         fitted = MX.fit(ctx, ptr, N, d, centroids, iterations, column_variances=column_variances)
         rows = MX.score(ctx, fitted, ptr, N)
         needles = None
         if needle_rows is not None:
-            q = ctx.upload(np.ascontiguousarray(needle_rows, np.float32))
-            try:
-                needles = MX.score(ctx, fitted, q, len(needle_rows))
-            finally:
-                ctx.free(q)
+            with deviceTable(ctx, needle_rows) as (q, Q, _):
+                needles = MX.score(ctx, fitted, q, Q)
         return fitted, rows, needles
-    finally:
-        if not on_device:
-            ctx.synchronize()
-            ctx.free(ptr)
 
 
 MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
@@ -455,23 +417,11 @@ def mapOfTable(ctx, table, M, perplexity, iterations, grid):
     table, uploaded to a temporary buffer first as principalAxesOfTable does -> (y [M x 2], (iterations, KL values), cell rows [grid x grid],
     the summary entry)"""
     from . import tsne as T
-    on_device = isinstance(table, DeviceTensor)
-    N = table.shape[0]
-    d = (table.size if on_device else int(np.prod(table.shape))) // N
-    ptr = table.ptr if on_device else ctx.upload(np.ascontiguousarray(table[:M], np.float32))
-    try:
-        e = T.embed(ctx, ptr, M, d, perplexity=perplexity, iterations=iterations)
-        try:
-            cells = T.mapCells(ctx, e.y_dev, M, grid, grid)
-            entry = dict(rows=M, d=d, perplexity=perplexity, iterations=iterations, grid=grid, eta=e.eta, beta_updates_max=e.tries, beta_capped_rows=e.capped,
-                         kl_first=float(e.kl[0]), kl_last=float(e.kl[-1]), cells_filled=int((cells >= 0).sum()))
-            return e.y, (np.asarray(e.kl_iterations, np.int64), e.kl), cells, entry
-        finally:
-            e.close()
-    finally:
-        if not on_device:
-            ctx.synchronize()
-            ctx.free(ptr)
+    with deviceTable(ctx, table, rows=M) as (ptr, _, d), contextlib.closing(T.embed(ctx, ptr, M, d, perplexity=perplexity, iterations=iterations)) as e:
+        cells = T.mapCells(ctx, e.y_dev, M, grid, grid)
+        entry = dict(rows=M, d=d, perplexity=perplexity, iterations=iterations, grid=grid, eta=e.eta, beta_updates_max=e.tries, beta_capped_rows=e.capped,
+                     kl_first=float(e.kl[0]), kl_last=float(e.kl[-1]), cells_filled=int((cells >= 0).sum()))
+        return e.y, (np.asarray(e.kl_iterations, np.int64), e.kl), cells, entry
 
 
 def parse(argv=None):
@@ -586,288 +536,332 @@ def main(argv=None):
             dataset.uncache()
 
 
-def run(OPT):
-    import json
-    import os
-    import time
-    from . import models, nn_utils, synth
-    ctx = L.Context(OPT.gpu) if OPT.gpu != int(os.environ.get("LOCAL_RANK", "0")) else L.default_context()
-    ctx.set_conv_mode(OPT.conv_mode)
-    say = (lambda *a: None) if OPT.quiet else print
+class Run:
+    """What the steps of one run share.  run() calls the steps in the reference's order; a step reads what the steps before it left here and
+    leaves its own part.  Device tables are allocated in `tables` and go with it."""
+
+    def __init__(self, OPT, ctx, MODEL_G, MODEL_R, MODEL_R_FIXER, dims, nd, method, colorSpace):
+        self.OPT, self.ctx, self.say = OPT, ctx, (lambda *a: None) if OPT.quiet else print
+        self.MODEL_G, self.MODEL_R, self.MODEL_R_FIXER = MODEL_G, MODEL_R, MODEL_R_FIXER
+        self.dims, self.nd, self.method, self.colorSpace, self.nbSteps = tuple(dims), nd, method, colorSpace, 16
+        self.summary = dict(dims=list(dims), noiseDim=nd, noiseMethod=method, nbImages=OPT.nbImages, batchSize=OPT.batchSize,
+                            path="host" if OPT.host else "device-resident" if OPT.resident else "device")
+        self.tables = DeviceScope(ctx)                                        # owns every device table named below
+        self.DATASET = None
+        self.dn = self.di = self.da = self.df = None                          # the corpus on the device: noise, images, attributes, attributesFixer
+        self.images = self.attributes = self.attributesFixer = None           # ... and on the host (the images: not with --resident)
+        # the table the search by attributes, the clusters, the map and the mixture read - the attributes, with --pcaSpace their whitened
+        # projection: a DeviceTensor on the device routes, the host array with --host; space_host: its copy for the steps that run on the host
+        self.space = self.space_host = None
+        self.spaceName = "pca_whitened" if pcaOptions(OPT)[1] else "attributes"
+        self.by_attr = self.by_pix = self.map_cells = self.rendered = None
+        self.pca = self.needle_rows = None                                    # what the steps before the mixture leave for it
+
+    def out(self, name):
+        return os.path.join(self.OPT.writeTo, name)
+
+
+def loadModels(OPT):
+    """apply_r.lua:62-103 -> (G, R, R_fixer, dims, noiseDim, noiseMethod, colorSpace)"""
     if OPT.synthetic:
+        from . import models, synth
         c, h, w, nd = (int(v) for v in OPT.synthetic.split("x"))
         dims, method, colorSpace = (c, h, w), "normal", "y" if c == 1 else "rgb"
         MODEL_G = models.create_G(dims, nd, seed=OPT.seed); synth.init_params(MODEL_G, OPT.seed)
         MODEL_R = models.create_R(dims, nd, method, False, seed=OPT.seed + 1); synth.init_params(MODEL_R, OPT.seed + 1)
         MODEL_R_FIXER = models.create_R(dims, nd, method, True, seed=OPT.seed + 2); synth.init_params(MODEL_R_FIXER, OPT.seed + 2)
-    else:
-        from . import t7
-        ck = t7.load_checkpoint(OPT.G)                                        # apply_r.lua:62-69
-        MODEL_G, o = ck["G"], ck.get("opt", {})
-        nd, method, colorSpace = int(o.get("noiseDim", 32)), o.get("noiseMethod", "normal"), o.get("colorSpace", "rgb")
-        dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
-        MODEL_R = t7.load_checkpoint(OPT.R)["R"]                              # :92-94
-        MODEL_R_FIXER = t7.load_checkpoint(OPT.R_fixer)["R"]                  # :101-103
-    nbAxes, pcaSpace = pcaOptions(OPT)
-    if nbAxes > nd:
-        raise L.GanrevError(f"--pca {nbAxes}: at most noiseDim = {nd} axes")
-    if anomalyMetric(OPT) == "ssim":
-        L.ssim_check_args(min(1024, OPT.nbImages), dims[0], dims[1], dims[2], 11, 1.0)      # before anything is allocated
-    reads = bool(OPT.needles or OPT.real)
-    if reads:                                                                # --cacheDataset then keeps the files on the GPU
-        DATASET = scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], ctx=ctx, reads=True)
-        have = len(DATASET.paths if DATASET.paths is not None else DATASET.loadPaths())      # checked before anything else is allocated
-        for count, what in ((OPT.nbImages if OPT.real else 0, "--nbImages"), (OPT.needles, "--needles")):
-            if have < count:
-                raise L.GanrevError(f"--dataset holds {have} matching files, {what} asks for {count}")
-    else:
-        DATASET = scripts.open_dataset(OPT, colorSpace, dims[1], dims[2], reads=False)      # apply_r.lua:83-87: configured, never read
+        return MODEL_G, MODEL_R, MODEL_R_FIXER, dims, nd, method, colorSpace
+    from . import t7
+    ck = t7.load_checkpoint(OPT.G)                                            # apply_r.lua:62-69
+    MODEL_G, o = ck["G"], ck.get("opt", {})
+    nd, method, colorSpace = int(o.get("noiseDim", 32)), o.get("noiseMethod", "normal"), o.get("colorSpace", "rgb")
+    dims = (1 if o.get("colorSpace", "rgb") == "y" else 3, int(o.get("height", 32)), int(o.get("width", 32)))
+    return MODEL_G, t7.load_checkpoint(OPT.R)["R"], t7.load_checkpoint(OPT.R_fixer)["R"], dims, nd, method, colorSpace      # :92-94, :101-103
 
-    def load_first(count):                                                    # apply_r.lua:144 DATASET.loadImages(1, count), on the device
-        res = DATASET.loadImages(1, count, ctx=ctx)
-        if tuple(res.images.shape[1:]) != tuple(dims):
-            shape = res.images.shape[1:]; res.free()
-            raise L.GanrevError(f"--dataset images are {shape} in colour space {colorSpace}, the nets take {tuple(dims)}")
-        return res
 
-    def refine_rows(images_t, z_t):                                           # ganrev.refine over one image table and its recovered noise
-        from . import device, refine
-        dmG = device.DeviceModel(ctx, MODEL_G)
-        try:
-            first, best = refine.refineNoise(ctx, dmG, images_t.ptr, z_t.ptr, z_t.shape[0], OPT.refine, OPT.batchSize, lr=OPT.refine_lr, clamp=1.0 if method == "uniform" else 0.0)
-        finally:
-            dmG.close()
-        return dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
-                    loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
+def checkOptions(S):
+    """what parse() could not check without the models; before anything is allocated"""
+    if pcaOptions(S.OPT)[0] > S.nd:
+        raise L.GanrevError(f"--pca {pcaOptions(S.OPT)[0]}: at most noiseDim = {S.nd} axes")
+    if anomalyMetric(S.OPT) == "ssim":
+        L.ssim_check_args(min(1024, S.OPT.nbImages), S.dims[0], S.dims[1], S.dims[2], 11, 1.0)
 
-    mixIter, mix = mixtureOptions(OPT), {}                                  # mix: what the steps before the mixture leave for it
 
-    def pca_step(table):                                                      # --pca K over the attribute table (a DeviceTensor or the host array)
-        from . import pca as P
-        say("Principal axes of the recovered noise...")
-        axes, coords, white = principalAxesOfTable(ctx, table, nbAxes, pcaSpace)
-        try:
-            if mixIter is not None:                                           # the mixture reuses the covariance diagonal, and projects the needles
-                mix["pca"] = (axes.mean, axes.axes, axes.eigenvalues, np.diag(axes.covariance()).copy())
-            np.save(out("pca_mean.npy"), axes.mean); np.save(out("pca_eigenvalues.npy"), axes.eigenvalues)
-            np.save(out("pca_axes.npy"), axes.axes[:nbAxes]); np.save(out("pca_projection.npy"), coords)
-            summary["pca"] = dict(k=nbAxes, explained=[float(v) for v in axes.explained[:nbAxes]], sweeps=axes.sweeps, converged=axes.converged,
-                                  space="pca_whitened" if pcaSpace else "attributes")       # the table the search by attributes and the clusters read
-            if OPT.render:                                                    # variations.png's conventions, along the axes instead of the coordinates
-                from . import render
-                dz = DeviceTensor(ctx, (nbAxes * nbSteps, nd))
-                try:
-                    ctx.upload(P.axisVariations(axes, nbAxes, nbSteps, method), dz.ptr)
-                    walked = forwardBatchedDev(MODEL_G, dz, OPT.batchSize)
-                    try:
-                        render.variations_grid(walked, nbSteps, path=out("variations_pca.png"))
-                    finally:
-                        walked.free()
-                finally:
-                    dz.free()
-        except BaseException:
-            if white is not None:
-                white.free()
-            raise
-        finally:
-            axes.close()
-        return white
+def openDataset(S):
+    """apply_r.lua:83-87: configured, and never read unless --needles / --real do (--cacheDataset then keeps the files on the GPU); they find
+    out here, before anything else is allocated, whether it holds enough files"""
+    OPT = S.OPT
+    if not (OPT.needles or OPT.real):
+        return scripts.open_dataset(OPT, S.colorSpace, S.dims[1], S.dims[2], reads=False)
+    DATASET = scripts.open_dataset(OPT, S.colorSpace, S.dims[1], S.dims[2], ctx=S.ctx, reads=True)
+    have = len(DATASET.paths if DATASET.paths is not None else DATASET.loadPaths())
+    for count, what in ((OPT.nbImages if OPT.real else 0, "--nbImages"), (OPT.needles, "--needles")):
+        if have < count:
+            raise L.GanrevError(f"--dataset holds {have} matching files, {what} asks for {count}")
+    return DATASET
 
-    def needles_in_space(na):                                                 # the needles' rows in the table the mixture is fitted in
-        if not pcaSpace:
-            return na.numpy()
-        mean, axes, lam, _ = mix["pca"]
-        bufs = [ctx.upload(np.ascontiguousarray(a)) for a in (mean, axes, lam)]
-        white = DeviceTensor(ctx, (na.shape[0], nbAxes))
-        try:
-            ctx.pca_project_dev(na.ptr, na.shape[0], nd, bufs[0], bufs[1], bufs[2], nbAxes, True, white.ptr)
-            return white.numpy()
-        finally:
-            white.free()
-            for b in bufs:
-                ctx.free(b)
 
-    def mixture_step(table, centroids, images=None):                          # --mixture ITER, after the clustering, in the table it read
-        say("Fitting a Gaussian mixture to the recovered noise...")
-        reuse = mix["pca"][3] if "pca" in mix and not pcaSpace else None      # (the whitened projection is another table: its variances are its own)
-        fitted, (labels, post, rowll), needles = mixtureOfTable(ctx, table, centroids, mixIter, reuse, mix.get("needles"))
-        for name, a in (("weights", fitted.weights), ("means", fitted.means), ("variances", fitted.variances), ("loglik", fitted.loglik),
-                        ("labels", labels), ("posterior", post), ("row_loglik", rowll)):
-            np.save(out("mixture_%s.npy" % name), a)
-        summary["mixture"] = dict(iterations=mixIter, k=fitted.k, var_floor=fitted.var_floor, loglik=[float(v) for v in fitted.loglik],
-                                  weights=[float(v) for v in fitted.weights], sizes=[int(v) for v in np.bincount(labels, minlength=fitted.k)],
-                                  row_loglik_min=float(rowll.min()), row_loglik_median=float(np.median(rowll)),
-                                  space="pca_whitened" if pcaSpace else "attributes")
-        if needles is not None:
-            np.save(out("needle_mixture.npy"), np.stack([needles[0].astype(np.float64), needles[1].astype(np.float64), needles[2].astype(np.float64)], axis=1))
-        if OPT.render and images is not None:
-            from . import mixture as MX
-            from . import render
-            for j, cl in enumerate(MX.members(ctx, labels, post, fitted.k, clusterOptions(OPT)[2])):
-                if cl:                                                        # the average face first, then the rows of highest posterior
-                    render.cluster_grid(images, [r for r, _ in cl], colorSpace, path=out("mixture_%02d.png" % (j + 1)))
-            shown = min(512 + 16, N, 1024)                                    # as many rows as anomalies.png shows
-            worst = np.argsort(rowll, kind="stable")[:shown]                  # lowest row log-likelihood first
-            render.grid(images, worst, int(math.floor(math.sqrt(shown))), colorSpace, path=out("mixture_outliers.png"))
+def loadFirst(S, scope, count):
+    """apply_r.lua:144 DATASET.loadImages(1, count), on the device; `scope` owns the table"""
+    res = S.DATASET.loadImages(1, count, ctx=S.ctx)
+    scope.adopt(res.images)
+    if tuple(res.images.shape[1:]) != S.dims:
+        raise L.GanrevError(f"--dataset images are {res.images.shape[1:]} in colour space {S.colorSpace}, the nets take {S.dims}")
+    return res
 
-    mapped, map_cells = mapOptions(OPT), None
 
-    def map_step(table):                                                      # --map over the table the search and the clusters read
-        say("Mapping the recovered noise...")
-        y, (kl_iterations, kl), cells, entry = mapOfTable(ctx, table, *mapped)
-        np.save(out("map_y.npy"), y); np.save(out("map_kl.npy"), np.stack([kl_iterations.astype(np.float64), kl], axis=1)); np.save(out("map_cells.npy"), cells)
-        summary["map"] = dict(entry, space="pca_whitened" if pcaSpace else "attributes")
-        return cells
-    for m in (MODEL_G, MODEL_R, MODEL_R_FIXER):
-        m._ctx = ctx
-        m.evaluate()
-    MODEL_R_FIXER.manualSeed(OPT.seed)
-    os.makedirs(OPT.writeTo, exist_ok=True)
-    out = lambda name: os.path.join(OPT.writeTo, name)
-    summary = dict(dims=list(dims), noiseDim=nd, noiseMethod=method, nbImages=OPT.nbImages, batchSize=OPT.batchSize, path="host" if OPT.host else "device-resident" if OPT.resident else "device")
-
-    say("Varying components...")                                              # apply_r.lua:110-136
-    nbSteps = 16
-    steps = np.linspace(-1, 1, nbSteps) if method == "uniform" else np.linspace(-3, 3, nbSteps)
-    noise1 = nn_utils.createNoiseInputs(1, nd, method, seed=OPT.seed)
+def variationsStep(S):
+    """apply_r.lua:110-138: one noise row, each component walked over its range in turn"""
+    OPT, nd, nbSteps = S.OPT, S.nd, S.nbSteps
+    S.say("Varying components...")
+    steps = np.linspace(-1, 1, nbSteps) if S.method == "uniform" else np.linspace(-3, 3, nbSteps)
+    noise1 = createNoiseInputs(1, nd, S.method, seed=OPT.seed)
     var_noise = np.repeat(noise1, nd * nbSteps, axis=0)
     for i in range(nd):
         var_noise[i * nbSteps:(i + 1) * nbSteps, i] = steps
-    variations = forwardBatched(MODEL_G, var_noise, OPT.batchSize)
-    np.save(out("variations.npy"), variations.reshape((nd, nbSteps) + tuple(dims)))
+    variations = forwardBatched(S.MODEL_G, var_noise, OPT.batchSize)
+    np.save(S.out("variations.npy"), variations.reshape((nd, nbSteps) + S.dims))
     if OPT.render:
-        from . import render
-        dv = DeviceTensor(ctx, variations.shape)
-        ctx.upload(variations, dv.ptr)
-        render.variations_grid(dv, nbSteps, path=out("variations.png"))                                                   # :137-138
-        dv.free()
+        with DeviceTensor(S.ctx, variations.shape) as dv:
+            S.ctx.upload(variations, dv.ptr)
+            render.variations_grid(dv, nbSteps, path=S.out("variations.png"))                                             # :137-138
 
-    say("Generating images, converting images to attributes...")             # :141-153
-    N = OPT.nbImages
-    t0 = time.perf_counter()
-    # utils/nn_utils.lua:39-51, drawn on the device (both paths: same noise); --real has no use for it
-    dn = None if OPT.real else nn_utils.createNoiseInputsDev(ctx, N, nd, method, seed=OPT.seed + 1)
+
+def buildCorpus(S):
+    """apply_r.lua:141-153: the images and what R and R_fixer recover from them, from one of three sources - G(noise) forwarded chunk by chunk
+    through host tensors (--host: images, attributes, attributesFixer), G(noise) by gr_embed_dev, or the first --nbImages files of --dataset
+    (--real, :144, commented out there); the last two leave di, da, df on the device"""
+    OPT, N, adopt = S.OPT, S.OPT.nbImages, S.tables.adopt
+    S.say("Generating images, converting images to attributes...")
+    if OPT.real:
+        S.say("Loading the first %d images of --dataset..." % N)
+        S.di = loadFirst(S, S.tables, N).images
+        S.da, S.df = (adopt(t) for t in embedImagesDev([S.MODEL_R, S.MODEL_R_FIXER], S.di, OPT.batchSize))                # :152-153
+        S.summary["corpus"] = "dataset"
+        return
+    noise = createNoiseInputsDev(S.ctx, N, S.nd, S.method, seed=OPT.seed + 1)      # utils/nn_utils.lua:39-51, drawn on the device (both paths: same noise)
     if OPT.host:
-        noise = dn.numpy(); dn.free()
-        images, attributes, attributesFixer = embed(MODEL_G, MODEL_R, noise, OPT.batchSize, MODEL_R_FIXER)
-        dw, space = None, attributes                                          # `space`: the table the search by attributes and the clusters read
-        if nbAxes:
-            white = pca_step(attributes)
-            if white is not None:                                             # --pcaSpace: the whitened projection, on the host like the table it stands for
-                space = white.numpy(); white.free()
-        if mapped:
-            map_cells = map_step(space)                                       # the host route uploads the table it has, as --pca does
-        by_attr, by_pix = createSimilaritySearch(5, 100, images, space) if N >= 500 else (None, None)
-        if OPT.render:                                                        # the same pictures from uploaded tables
-            di, df = DeviceTensor(ctx, images.shape), DeviceTensor(ctx, attributesFixer.shape)
-            ctx.upload(images, di.ptr); ctx.upload(attributesFixer, df.ptr)
+        with noise:
+            noise = noise.numpy()
+        S.images, S.attributes, S.attributesFixer = embed(S.MODEL_G, S.MODEL_R, noise, OPT.batchSize, S.MODEL_R_FIXER)
     else:
-        if OPT.real:                                                          # :144: the corpus is the dataset's images, not G's
-            say("Loading the first %d images of --dataset..." % N)
-            di = load_first(N).images
-            da, df = embedImagesDev([MODEL_R, MODEL_R_FIXER], di, OPT.batchSize)                      # :152-153
-            summary["corpus"] = "dataset"
-        else:
-            di, da, df = embed_dev(MODEL_G, MODEL_R, dn, OPT.batchSize, MODEL_R_FIXER, keep_images=True, dims=dims)
-        if OPT.refine:
-            # `attributes` only: pulling attributesFixer back to the unfixed image would undo the fix, and the anomaly score needs the
-            # unrefined reconstruction.  The search and the clusters below read the refined table.
-            say("Refining the recovered noise through G...")
-            summary["refine"] = refine_rows(di, da)
-            if OPT.render:
-                from . import render
-                k = min(52, N)
-                again = forwardBatchedDev(MODEL_G, da.rows(0, k), OPT.batchSize)
-                render.fixed_pairs_grid(di, again, k, colorSpace, path=out("refined_pairs.png"))      # image next to G(refined z)
-                again.free()
-        dw = pca_step(da) if nbAxes else None                                # after the refinement, on the table it left, like the search and the clusters
-        ds = dw if dw is not None else da                                     # --pcaSpace: both read the whitened projection, d = K
-        if mapped:
-            map_cells = map_step(ds)
-        by_attr, by_pix = createSimilaritySearchDev(5, 100, ds, di) if N >= 500 else (None, None)     # :170-172 on the tables where they were written
-        if OPT.needles:
-            # search by example: the needles are images from outside the corpus - the dataset's first files - embedded like the corpus
-            # (R, then the same refinement against themselves) and searched in the tables where they lie
-            say("Searching the corpus for the first %d images of --dataset..." % OPT.needles)
-            nl = na = None
-            try:
-                nl = load_first(OPT.needles)
-                ni = nl.images
-                (na,) = embedImagesDev([MODEL_R], ni, OPT.batchSize)
-                summary["needles"] = dict(count=OPT.needles, files=[os.path.basename(f) for f in nl.paths])
-                if OPT.refine:
-                    summary["needles"]["refine"] = refine_rows(ni, na)
-                if mixIter is not None:
-                    mix["needles"] = needles_in_space(na)
-                nb_attr, nb_pix = searchByExample(100, da, na, di, ni)
-                np.save(out("needle_by_attributes.npy"), nb_attr); np.save(out("needle_by_pixels.npy"), nb_pix); np.save(out("needle_attributes.npy"), na.numpy())
-                if OPT.render:
-                    from . import render
-                    for i in range(OPT.needles):
-                        render.similar_example_grid(ni, i, di, nb_attr[i], colorSpace, path=out("needle_attributes_%02d.png" % (i + 1)))
-                        render.similar_example_grid(ni, i, di, nb_pix[i], colorSpace, path=out("needle_pixelwise_%02d.png" % (i + 1)))
-            except BaseException:
-                for t in (di, da, df, dn, dw):                                # the corpus tables go with a failed needle step
-                    if t is not None:
-                        t.free()
-                raise
-            finally:
-                for t in (na, nl):
-                    if t is not None:
-                        t.free()
-        attributes, attributesFixer = da.numpy(), df.numpy()
-        space = dw.numpy() if dw is not None else attributes
-        if dn is not None:
-            dn.free()
-        if not OPT.resident:
-            images = di.numpy()
-            if not OPT.render:
-                for t in (di, da, df) + ((dw,) if dw is not None else ()):
-                    t.free()
-                dw = None
-    ctx.synchronize()
-    summary["embed_and_search_seconds"] = round(time.perf_counter() - t0, 4)
-    rendered = None
+        S.dn = adopt(noise)
+        S.di, S.da, S.df = (adopt(t) for t in embed_dev(S.MODEL_G, S.MODEL_R, S.dn, OPT.batchSize, S.MODEL_R_FIXER, keep_images=True, dims=S.dims))
+
+
+def refineRows(S, images_t, z_t):
+    """ganrev.refine over one image table and its recovered noise, in place -> the summary's entry"""
+    from . import device, refine
+    OPT = S.OPT
+    with contextlib.closing(device.DeviceModel(S.ctx, S.MODEL_G)) as dmG:
+        first, best = refine.refineNoise(S.ctx, dmG, images_t.ptr, z_t.ptr, z_t.shape[0], OPT.refine, OPT.batchSize, lr=OPT.refine_lr,
+                                         clamp=1.0 if S.method == "uniform" else 0.0)
+    return dict(steps=OPT.refine, lr=OPT.refine_lr, loss_before_mean=float(first.mean(dtype=np.float64)),
+                loss_after_mean=float(best.mean(dtype=np.float64)), rows_improved=int((best < first).sum()))
+
+
+def refineStep(S):
+    """--refine STEPS.  `attributes` only: pulling attributesFixer back to the unfixed image would undo the fix, and the anomaly score needs the
+    unrefined reconstruction.  The steps after this one read the refined table."""
+    OPT = S.OPT
+    S.say("Refining the recovered noise through G...")
+    S.summary["refine"] = refineRows(S, S.di, S.da)
     if OPT.render:
-        say("Rendering...")                                                   # from di / df, before they are freed
-        rendered = renderAnalysis(OPT, out, colorSpace, MODEL_G, di, space if OPT.host else ds, df, by_attr, by_pix, **({} if mixIter is None else dict(mixture=mixture_step)))
-    elif OPT.resident:
-        say("Analysing on the device...")
-        rendered = analyseDev(OPT, MODEL_G, di, ds, df, **({} if mixIter is None else dict(mixture=mixture_step)))
-    if map_cells is not None and OPT.render:
-        # the faces where they land: one grid over the map's cells, from the image table where it lies; each tile's ring takes the colour of
-        # its row's cluster - the assignment of the clustering step (gr_cosine_assign on its final centroids) repeated for the rows shown
-        from . import render
-        shown = map_cells[map_cells >= 0]
-        labels = None
-        if clusterOptions(OPT)[0] <= NARROW_MAX_CLUSTERS:                     # (the palette has 12 colours: finer clusterings keep plain rings)
-            labels = np.full(N, -1, np.int64)
-            labels[shown] = ctx.cosine_assign(space[shown], rendered["clusters"][0], take_min=not clusterOptions(OPT)[3])[0]
-        render.map_grid(di, map_cells, colorSpace, labels=labels, path=out("map.png"))
-    if rendered:
-        for t in (di, df) if OPT.host else (di, da, df):
-            t.free()
-        if dw is not None:
-            dw.free()
-    np.save(out("attributes.npy"), attributes); np.save(out("attributes_fixer.npy"), attributesFixer)
-    if by_attr is not None:
-        np.save(out("similar_by_attributes.npy"), by_attr); np.save(out("similar_by_pixels.npy"), by_pix)
+        k = min(52, OPT.nbImages)
+        with forwardBatchedDev(S.MODEL_G, S.da.rows(0, k), OPT.batchSize) as again:
+            render.fixed_pairs_grid(S.di, again, k, S.colorSpace, path=S.out("refined_pairs.png"))                        # image next to G(refined z)
+
+
+def pcaStep(S):
+    """--pca K over the attribute table, where it lies -> with --pcaSpace the whitened projection, lying where that table lies (a DeviceTensor,
+    on the host with --host); else None"""
+    from . import pca as P
+    OPT, ctx, out, nbSteps = S.OPT, S.ctx, S.out, S.nbSteps
+    nbAxes, pcaSpace = pcaOptions(OPT)
+    S.say("Principal axes of the recovered noise...")
+    axes, coords, white = principalAxesOfTable(ctx, S.attributes if OPT.host else S.da, nbAxes, pcaSpace)
+    if white is not None:
+        S.tables.adopt(white)
+    with contextlib.closing(axes):
+        if mixtureOptions(OPT) is not None:                                   # the mixture reuses the covariance diagonal, and projects the needles
+            S.pca = (axes.mean, axes.axes, axes.eigenvalues, np.diag(axes.covariance()).copy())
+        np.save(out("pca_mean.npy"), axes.mean); np.save(out("pca_eigenvalues.npy"), axes.eigenvalues)
+        np.save(out("pca_axes.npy"), axes.axes[:nbAxes]); np.save(out("pca_projection.npy"), coords)
+        S.summary["pca"] = dict(k=nbAxes, explained=[float(v) for v in axes.explained[:nbAxes]], sweeps=axes.sweeps, converged=axes.converged, space=S.spaceName)
+        if OPT.render:                                                        # variations.png's conventions, along the axes instead of the coordinates
+            with DeviceTensor(ctx, (nbAxes * nbSteps, S.nd)) as dz:
+                ctx.upload(P.axisVariations(axes, nbAxes, nbSteps, S.method), dz.ptr)
+                with forwardBatchedDev(S.MODEL_G, dz, OPT.batchSize) as walked:
+                    render.variations_grid(walked, nbSteps, path=out("variations_pca.png"))
+    if white is None or not OPT.host:
+        return white
+    host = white.numpy()                                                      # on the host like the table it stands for
+    S.tables.release(white)
+    return host
+
+
+def mapStep(S):
+    """--map over the table the search and the clusters read (the host route uploads the table it has, as --pca does)"""
+    S.say("Mapping the recovered noise...")
+    y, (kl_iterations, kl), S.map_cells, entry = mapOfTable(S.ctx, S.space, *mapOptions(S.OPT))
+    np.save(S.out("map_y.npy"), y); np.save(S.out("map_kl.npy"), np.stack([kl_iterations.astype(np.float64), kl], axis=1)); np.save(S.out("map_cells.npy"), S.map_cells)
+    S.summary["map"] = dict(entry, space=S.spaceName)
+
+
+def needlesInSpace(S, na):
+    """the needles' rows in the table the mixture is fitted in"""
+    nbAxes, pcaSpace = pcaOptions(S.OPT)
+    if not pcaSpace:
+        return na.numpy()
+    with DeviceScope(S.ctx) as own:
+        mean, axes, lam = (own.upload(np.ascontiguousarray(a)) for a in S.pca[:3])
+        white = own.tensor((na.shape[0], nbAxes))
+        S.ctx.pca_project_dev(na.ptr, na.shape[0], S.nd, mean, axes, lam, nbAxes, True, white.ptr)
+        return white.numpy()
+
+
+def needlesStep(S):
+    """--needles N, search by example: the needles are images from outside the corpus - the dataset's first files - embedded like the corpus
+    (R, then the same refinement against themselves) and searched in the tables where they lie"""
+    OPT, out = S.OPT, S.out
+    S.say("Searching the corpus for the first %d images of --dataset..." % OPT.needles)
+    with DeviceScope(S.ctx) as own:                                           # the needles' tables go with the step
+        nl = loadFirst(S, own, OPT.needles)
+        ni = nl.images
+        (na,) = (own.adopt(t) for t in embedImagesDev([S.MODEL_R], ni, OPT.batchSize))
+        S.summary["needles"] = dict(count=OPT.needles, files=[os.path.basename(f) for f in nl.paths])
+        if OPT.refine:
+            S.summary["needles"]["refine"] = refineRows(S, ni, na)
+        if mixtureOptions(OPT) is not None:
+            S.needle_rows = needlesInSpace(S, na)
+        nb_attr, nb_pix = searchByExample(100, S.da, na, S.di, ni)
+        np.save(out("needle_by_attributes.npy"), nb_attr); np.save(out("needle_by_pixels.npy"), nb_pix); np.save(out("needle_attributes.npy"), na.numpy())
+        if OPT.render:
+            for i in range(OPT.needles):
+                render.similar_example_grid(ni, i, S.di, nb_attr[i], S.colorSpace, path=out("needle_attributes_%02d.png" % (i + 1)))
+                render.similar_example_grid(ni, i, S.di, nb_pix[i], S.colorSpace, path=out("needle_pixelwise_%02d.png" % (i + 1)))
+
+
+def tablesForAnalysis(S):
+    """Every table where the rest of the run reads it.  --host: with --render the same pictures come from uploaded tables.  The device routes:
+    the small tables come to the host for the files, the noise has done its work, and unless the analysis runs on the device (--resident,
+    --render) the images come too and every device table goes here, before the host-side analysis, not at the end of it."""
+    OPT, T = S.OPT, S.tables
+    if OPT.host:
+        S.space_host = S.space
+        if OPT.render:
+            S.di, S.df = T.tensor(S.images.shape), T.tensor(S.attributesFixer.shape)
+            S.ctx.upload(S.images, S.di.ptr); S.ctx.upload(S.attributesFixer, S.df.ptr)
+        return
+    S.attributes, S.attributesFixer = S.da.numpy(), S.df.numpy()
+    S.space_host = S.attributes if S.space is S.da else S.space.numpy()
+    T.release(S.dn)
+    if not OPT.resident:
+        S.images = S.di.numpy()
+        if not OPT.render:
+            T.close()
+
+
+def mapPicture(S):
+    """map.png, the faces where they land: one grid over the map's cells, from the image table where it lies; each tile's ring takes the colour
+    of its row's cluster - the assignment of the clustering step (gr_cosine_assign on its final centroids) repeated for the rows shown"""
+    nbClusters, _, _, closest = clusterOptions(S.OPT)
+    shown = S.map_cells[S.map_cells >= 0]
+    labels = None
+    if nbClusters <= NARROW_MAX_CLUSTERS:                                     # (the palette has 12 colours: finer clusterings keep plain rings)
+        labels = np.full(S.OPT.nbImages, -1, np.int64)
+        labels[shown] = S.ctx.cosine_assign(S.space_host[shown], S.rendered["clusters"][0], take_min=not closest)[0]
+    render.map_grid(S.di, S.map_cells, S.colorSpace, labels=labels, path=S.out("map.png"))
+
+
+def mixtureStep(S, table, centroids, images=None):
+    """--mixture ITER, after the clustering, in the table it read"""
+    OPT, out, mixIter = S.OPT, S.out, mixtureOptions(S.OPT)
+    S.say("Fitting a Gaussian mixture to the recovered noise...")
+    reuse = S.pca[3] if S.pca is not None and not pcaOptions(OPT)[1] else None    # (the whitened projection is another table: its variances are its own)
+    fitted, (labels, post, rowll), needles = mixtureOfTable(S.ctx, table, centroids, mixIter, reuse, S.needle_rows)
+    for name, a in (("weights", fitted.weights), ("means", fitted.means), ("variances", fitted.variances), ("loglik", fitted.loglik),
+                    ("labels", labels), ("posterior", post), ("row_loglik", rowll)):
+        np.save(out("mixture_%s.npy" % name), a)
+    S.summary["mixture"] = dict(iterations=mixIter, k=fitted.k, var_floor=fitted.var_floor, loglik=[float(v) for v in fitted.loglik],
+                                weights=[float(v) for v in fitted.weights], sizes=[int(v) for v in np.bincount(labels, minlength=fitted.k)],
+                                row_loglik_min=float(rowll.min()), row_loglik_median=float(np.median(rowll)), space=S.spaceName)
+    if needles is not None:
+        np.save(out("needle_mixture.npy"), np.stack([needles[0].astype(np.float64), needles[1].astype(np.float64), needles[2].astype(np.float64)], axis=1))
+    if OPT.render and images is not None:
+        from . import mixture as MX
+        for j, cl in enumerate(MX.members(S.ctx, labels, post, fitted.k, clusterOptions(OPT)[2])):
+            if cl:                                                            # the average face first, then the rows of highest posterior
+                render.cluster_grid(images, [r for r, _ in cl], S.colorSpace, path=out("mixture_%02d.png" % (j + 1)))
+        shown = min(512 + 16, OPT.nbImages, 1024)                             # as many rows as anomalies.png shows
+        worst = np.argsort(rowll, kind="stable")[:shown]                      # lowest row log-likelihood first
+        render.grid(images, worst, int(math.floor(math.sqrt(shown))), S.colorSpace, path=out("mixture_outliers.png"))
+
+
+# apply_r.lua:25-193 main(): the whole analysis as one run.  What the reference computes is written as arrays (.npy) and one
+# summary.json under --writeTo; with --render the pictures it saves (apply_r.lua:137-138, 245-258, 283-298, 325-351, 374-389) are written
+# beside them as PNG, under the reference's names: variations, cluster_%02d, similar_attributes_%02d, similar_pixelwise_%02d, fixed_pairs,
+# fixed_images_528[_unfixed], anomalies (the counts clamp to --nbImages).  G / R / R_fixer come from Torch7 checkpoints (ganrev.t7: train.lua:256, train_r.lua:234) or, with
+# --synthetic, from random-initialised nets of the requested shape (a smoke run: no trained checkpoint exists in this repository).
+def run(OPT):
+    ctx = L.Context(OPT.gpu) if OPT.gpu != int(os.environ.get("LOCAL_RANK", "0")) else L.default_context()
+    ctx.set_conv_mode(OPT.conv_mode)
+    S = Run(OPT, ctx, *loadModels(OPT))                                       # apply_r.lua:62-103
+    checkOptions(S)
+    S.DATASET = openDataset(S)                                                # :83-87
+    for m in (S.MODEL_G, S.MODEL_R, S.MODEL_R_FIXER):
+        m._ctx = ctx
+        m.evaluate()
+    S.MODEL_R_FIXER.manualSeed(OPT.seed)
+    os.makedirs(OPT.writeTo, exist_ok=True)
+    out, say, summary, N = S.out, S.say, S.summary, OPT.nbImages
+    mixIter = mixtureOptions(OPT)
+    mixture = {} if mixIter is None else dict(mixture=functools.partial(mixtureStep, S))    # analyseDev calls it while the tables are where they are
+    with S.tables:
+        variationsStep(S)                                                     # :110-138
+        t0 = time.perf_counter()
+        buildCorpus(S)                                                        # :141-153
+        if OPT.refine:
+            refineStep(S)
+        white = pcaStep(S) if pcaOptions(OPT)[0] else None                    # after the refinement, on the table it left, like the search and the clusters
+        S.space = white if white is not None else S.attributes if OPT.host else S.da     # --pcaSpace: d = K
+        if mapOptions(OPT):
+            mapStep(S)
+        if N >= 500:                                                          # :170-172, on the tables where they were written
+            S.by_attr, S.by_pix = createSimilaritySearch(5, 100, S.images, S.space) if OPT.host else createSimilaritySearchDev(5, 100, S.space, S.di)
+        if OPT.needles:
+            needlesStep(S)
+        tablesForAnalysis(S)
+        ctx.synchronize()
+        summary["embed_and_search_seconds"] = round(time.perf_counter() - t0, 4)
+        if OPT.render:
+            say("Rendering...")
+            S.rendered = renderAnalysis(OPT, out, S.colorSpace, S.MODEL_G, S.di, S.space, S.df, S.by_attr, S.by_pix, **mixture)
+        elif OPT.resident:
+            say("Analysing on the device...")
+            S.rendered = analyseDev(OPT, S.MODEL_G, S.di, S.space, S.df, **mixture)
+        if S.map_cells is not None and OPT.render:
+            mapPicture(S)
+    rendered = S.rendered                                                     # the device tables are gone: the rest is host arrays and files
+    np.save(out("attributes.npy"), S.attributes); np.save(out("attributes_fixer.npy"), S.attributesFixer)
+    if S.by_attr is not None:
+        np.save(out("similar_by_attributes.npy"), S.by_attr); np.save(out("similar_by_pixels.npy"), S.by_pix)
 
     say("Clustering...")                                                      # :158-162
-    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(*clusterOptions(OPT)[:3], images, space, seed=OPT.seed, closest=clusterOptions(OPT)[3])     # (20, 15, 64 + 7 unless asked otherwise)
+    centroids, counts, clusters, faces = rendered["clusters"] if rendered else createClusterImages(*clusterOptions(OPT)[:3], S.images, S.space_host, seed=OPT.seed, closest=clusterOptions(OPT)[3])     # (20, 15, 64 + 7 unless asked otherwise)
     np.save(out("cluster_centroids.npy"), centroids); np.save(out("cluster_average_faces.npy"), np.stack(faces))
     summary["cluster_sizes"] = [len(c) for c in clusters]; summary["cluster_total_counts"] = [float(v) for v in counts]
     summary.update(zip(("nbClusters", "nbIterations", "nbMaxPerCluster", "closest"), clusterOptions(OPT)))
     if mixIter is not None and not rendered:                                  # neither --resident nor --render: the host copy of the table is uploaded
-        mixture_step(space, centroids)
+        mixtureStep(S, S.space_host, centroids)
 
     say("Fixing faces...")                                                    # :178-181
     nbFixed = min(512 + 16, N)
-    np.save(out("fixed_faces.npy"), rendered["fixed"] if rendered else fixFaces(nbFixed, MODEL_G, attributesFixer, OPT.batchSize))
+    np.save(out("fixed_faces.npy"), rendered["fixed"] if rendered else fixFaces(nbFixed, S.MODEL_G, S.attributesFixer, OPT.batchSize))
 
     say("Detecting anomalies...")                                             # :186-191
     nbCalc = min(1024, N)
-    dist, below, is_anom = rendered["anomalies"] if rendered else detectAnomalies(nbCalc, 0.15, images, MODEL_G, attributesFixer, OPT.batchSize)
+    dist, below, is_anom = rendered["anomalies"] if rendered else detectAnomalies(nbCalc, 0.15, S.images, S.MODEL_G, S.attributesFixer, OPT.batchSize)
     if anomalyMetric(OPT) == "ssim":                                          # (parse: only where analyseDev ran) the score is the SSIM, the distances beside it
         np.save(out("anomaly_ssim.npy"), dist)
         dist = rendered["distances"]

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib as L
 from . import quality, scripts
-from .nn_utils import DeviceTensor, createNoiseInputsDev, forwardBatchedDev
+from .nn_utils import DeviceScope, DeviceTensor, createNoiseInputsDev, forwardBatchedDev
 
 NB_EXTREMES = 16
 
@@ -120,14 +120,11 @@ def compare_grid(images, recon_a, recon_b, rows, from_space="rgb", path=None):
     from . import render
     ctx = images.ctx
     d = images.size // images.shape[0]
-    sheet = DeviceTensor(ctx, (3 * len(rows),) + tuple(images.shape[1:]))
-    try:
+    with DeviceTensor(ctx, (3 * len(rows),) + tuple(images.shape[1:])) as sheet:
         for j, r in enumerate(rows):
             for s, t in enumerate((images, recon_a, recon_b)):
                 ctx.copy2d(sheet.ptr + 4 * d * (3 * j + s), d, t.ptr + 4 * d * int(r), d, 1, d)
         return render.grid(sheet, np.arange(3 * len(rows)), 12, from_space, path=path)
-    finally:
-        sheet.free()
 
 
 def main(argv=None):
@@ -168,24 +165,19 @@ def run(OPT):
 
     say("Own samples: x = G(z), x^ = G(R(x))...")
     for key, (G, R, nd) in pairs.items():
-        z = createNoiseInputsDev(ctx, N, nd, "normal", seed=OPT.seed + 1)
-        x = xhat = None
-        try:
-            x = forwardBatchedDev(G, z, OPT.batchSize)
-            xhat = quality.reconstruct(G, R, x, OPT.batchSize)
-            score("own", key, x, xhat)
-        finally:
-            for t in (z, x, xhat):
-                if t is not None:
-                    t.free()
+        with DeviceScope(ctx) as own:
+            z = own.adopt(createNoiseInputsDev(ctx, N, nd, "normal", seed=OPT.seed + 1))
+            x = own.adopt(forwardBatchedDev(G, z, OPT.batchSize))
+            score("own", key, x, own.adopt(quality.reconstruct(G, R, x, OPT.batchSize)))
 
     say("Real images: x^ = G(R(x))...")
-    x, corpus = real_images(OPT, ctx, dims, colorSpace)
-    summary["real"] = dict(corpus=corpus)
     recon, scores = {}, {}
-    try:
+    with DeviceScope(ctx) as own:
+        x, corpus = real_images(OPT, ctx, dims, colorSpace)
+        own.adopt(x)
+        summary["real"] = dict(corpus=corpus)
         for key, (G, R, _) in pairs.items():
-            recon[key] = quality.reconstruct(G, R, x, OPT.batchSize)
+            recon[key] = own.adopt(quality.reconstruct(G, R, x, OPT.batchSize))
             scores[key] = score("real", key, x, recon[key])
         summary["real"]["a_wins_ssim"] = a_wins_share(scores["a"][0], scores["b"][0])
         summary["real"]["a_wins_mse"] = a_wins_share(-scores["a"][1].astype(np.float64), -scores["b"][1].astype(np.float64))     # a lower error wins
@@ -193,9 +185,6 @@ def run(OPT):
             best, worst = extreme_rows(scores["a"][0], scores["b"][0])
             compare_grid(x, recon["a"], recon["b"], best + worst, colorSpace, path=out("compare_real.png"))
             summary["real"]["rendered_rows"] = best + worst
-    finally:
-        for t in [x] + list(recon.values()):
-            t.free()
     json.dump(summary, open(out("summary.json"), "w"), indent=1)
     say("<compare> results in", OPT.out, summary)
     return summary

@@ -1,4 +1,6 @@
 """Mirror of the hot-path helpers of utils/nn_utils.lua and of its colour-space conversions (:133-263, :324-379)."""
+import contextlib
+
 import numpy as np
 
 from . import _lib as L
@@ -22,7 +24,7 @@ def forwardBatched(model, input, batchSize):
 
 class DeviceTensor:
     """A row-major fp32 tensor in GPU memory (what a torch.CudaTensor is to the reference's scripts): pointer + shape, nothing else.
-    .numpy() copies it to the host; .free() releases it."""
+    .numpy() copies it to the host; .free() releases it, and so does leaving a `with` block over it."""
 
     def __init__(self, ctx, shape, ptr=None):
         self.ctx, self.shape = ctx, tuple(int(s) for s in shape)
@@ -43,6 +45,64 @@ class DeviceTensor:
         if self.owned and self.ptr is not None:
             self.ctx.free(self.ptr)
         self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+class DeviceScope(contextlib.ExitStack):
+    """Owner of the device memory of one run or one step: a context manager that hands out DeviceTensors (tensor) and raw buffers (malloc,
+    upload), adopts what was made elsewhere - a DeviceTensor, a pointer from ctx.malloc, anything with free() or close() - and on exit, however
+    the block ends, releases what it still holds in reverse order.  release(t) does it early; each thing is released once."""
+
+    def __init__(self, ctx):
+        super().__init__()
+        self.ctx, self.held = ctx, []
+
+    def adopt(self, t):
+        self.held.append(t)
+        self.callback(self.release, t)
+        return t
+
+    def tensor(self, shape):
+        return self.adopt(DeviceTensor(self.ctx, shape))
+
+    def malloc(self, nbytes):
+        return self.adopt(self.ctx.malloc(nbytes))
+
+    def upload(self, arr):
+        return self.adopt(self.ctx.upload(arr))
+
+    def release(self, t):
+        if t not in self.held:
+            return
+        self.held.remove(t)
+        if isinstance(t, int):
+            self.ctx.free(t)
+        else:
+            (t.free if hasattr(t, "free") else t.close)()
+
+
+@contextlib.contextmanager
+def deviceTable(ctx, table, rows=None):
+    """A table [N x d] on the device, for the length of a block -> (pointer, N, d): a DeviceTensor as it lies; a host array uploaded to a temporary
+    buffer, which is freed after the block once the context has synchronised (what the block enqueued may still read it).  rows=M: the first M rows."""
+    if isinstance(table, DeviceTensor):
+        N = table.shape[0]
+        yield table.ptr, N if rows is None else rows, table.size // N
+        return
+    table = np.ascontiguousarray(table if rows is None else table[:rows], np.float32)
+    ptr = ctx.upload(table)
+    try:
+        yield ptr, table.shape[0], table.size // table.shape[0]
+    finally:
+        try:
+            ctx.synchronize()
+        finally:
+            ctx.free(ptr)
 
 
 def forwardBatchedDev(model, input, batchSize, out=None):

@@ -78,12 +78,9 @@ def toGrid(ctx, images, nrow, colorSpace, path=None):
     images are uploaded, the grid is rendered on the GPU"""
     from . import render
     images = np.ascontiguousarray(images, dtype=np.float32)
-    t = nn_utils.DeviceTensor(ctx, images.shape)
-    try:
+    with nn_utils.DeviceTensor(ctx, images.shape) as t:
         ctx.upload(images, t.ptr)
         return render.grid(t, np.arange(len(images)), nrow, colorSpace, auto_range=True, path=path)
-    finally:
-        t.free()
 
 
 def main(argv=None):
@@ -140,11 +137,10 @@ def main(argv=None):
                 idx, dist = findClosestNeighboursOf(ctx, best[:16], table_dev, n, d)
                 if opt.render:                                        # sample.lua:118, from the table where it lies
                     from . import render
-                    bt = nn_utils.DeviceTensor(ctx, best[:16].shape)
-                    ctx.upload(best[:16], bt.ptr)
-                    render.neighbours_grid(bt, np.arange(len(idx)), nn_utils.DeviceTensor(ctx, shape, table_dev), idx[:, 0], opt.colorSpace,
-                                           path=os.path.join(opt.writeTo, "best_%04d_neighbours_base.png" % run))
-                    bt.free()
+                    with nn_utils.DeviceTensor(ctx, best[:16].shape) as bt:
+                        ctx.upload(best[:16], bt.ptr)
+                        render.neighbours_grid(bt, np.arange(len(idx)), nn_utils.DeviceTensor(ctx, shape, table_dev), idx[:, 0], opt.colorSpace,
+                                               path=os.path.join(opt.writeTo, "best_%04d_neighbours_base.png" % run))
                 # the rows found: --data has them on the host; the loader's table gives up just these
                 found = data[idx[:, 0]] if table is None else np.stack([ctx.download(table_dev + 4 * d * int(j), shape[1:]) for j in idx[:, 0]])
             finally:
