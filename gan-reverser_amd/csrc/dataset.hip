@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void image_scale_kernel(const float* __restric
 }
 
 void launch_image_scale(const float* in, long nplanes, const ScaleAxis& ay, const ScaleAxis& ax, float* out, hipStream_t s) {
-  const bool v4 = ax.dst_len % 4 == 0 && ((uintptr_t)out & 15) == 0;
+  const bool v4 = ax.dst_len % 4 == 0 && aligned16(out);
   const long npix = nplanes * ay.dst_len * ax.dst_len;
   const long work = v4 ? npix / 4 : npix;
   long blocks = (work + 255) / 256; if (blocks > 2048) blocks = 2048;
@@ -210,7 +210,7 @@ static void dataset_launch(const uint8_t* in, long n, const ScaleAxis& ay, const
   const long npix = n * ay.dst_len * ax.dst_len;
   // 16-byte stores need whole groups of four per output row (then every plane row starts 16-byte aligned when `out` does); dword reads of the
   // bytes need `in` dword aligned and a tensor that ends on a dword boundary
-  const bool v4 = ax.dst_len % 4 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)in & 3) == 0 && ((long)bytes_in & 3) == 0;
+  const bool v4 = ax.dst_len % 4 == 0 && aligned16(out) && ((uintptr_t)in & 3) == 0 && ((long)bytes_in & 3) == 0;
   const long work = v4 ? npix / 4 : npix;
   long blocks = (work + 255) / 256; if (blocks > 2048) blocks = 2048;
   KtScope kt(v4 ? "dataset_images_kernel_v4" : "dataset_images_kernel", 0.0, bytes_in + 4.0 * (TO == CS_Y ? 1 : 3) * (double)npix, s);
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void dataset_gather_kernel(const CachedImage* 
 template <int TO>
 static void gather_launch(const CachedImage* recs, const long* idx, long n, int dh, int dw, int normalize, float* out, double bytes_in, hipStream_t s) {
   const long npix = n * dh * dw;
-  const bool v4 = dw % 4 == 0 && ((uintptr_t)out & 15) == 0;      // whole groups of four per output row: every plane row then starts 16-byte aligned when `out` does
+  const bool v4 = dw % 4 == 0 && aligned16(out);      // whole groups of four per output row: every plane row then starts 16-byte aligned when `out` does
   const long work = v4 ? npix / 4 : npix;
   long blocks = (work + 255) / 256; if (blocks > 2048) blocks = 2048;
   KtScope kt(v4 ? "dataset_gather_kernel_v4" : "dataset_gather_kernel", 0.0, bytes_in + 4.0 * (TO == CS_Y ? 1 : 3) * (double)npix, s);

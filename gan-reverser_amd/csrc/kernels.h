@@ -18,6 +18,14 @@ namespace gr {
 constexpr int CONV_CK = 8;  // input channels per LDS chunk (k = tap*8 + ci_local)
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // the launchers' test for 16-byte loads and stores
+
+// ---------------------------------------------------------------- the row-order chain of the analysis kernels
+// The reduction convention include/ganrev.h states for k-means, PCA, t-SNE, the mixture, the VAE layer and SSIM, and tests/*_paths.py restate:
+// per block of ROWS_PER_BLOCK consecutive rows the values in row order from +0.0, the block partials in block order from +0.0, one division.
+// The constant, the device pieces (ordered_sum8, stage_rows, block_tree_sum, below) and the mean of n doubles (chain.hip) are stated here once.
+constexpr int ROWS_PER_BLOCK = 512;
+constexpr long row_blocks(long n) { return (n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK; }
 
 // ---------------------------------------------------------------- optional per-kernel HIP-event timing (bench / roofline leg)
 // When a timer is installed every launch_* brackets its kernel with two events ON THE LAUNCH STREAM and reports the
@@ -90,6 +98,61 @@ __device__ __forceinline__ float wave_sum(float v) {
   v = half_wave_sum(v);
   v += dpp_take<0x143, 0xC>(v);     // row_bcast31 into rows 2 and 3: lane 31 holds the sum of the first half-wave
   return v;
+}
+// v[0], v[stride], .. v[(count - 1) stride] added in that order from +0.0: eight loads in flight, then the adds in order (the joins of the chain)
+__device__ __forceinline__ double ordered_sum8(const double* __restrict__ v, long count, long stride) {
+  double s = 0.0;
+  for (long b = 0; b < count; b += 8) {
+    double t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = b + u < count ? v[(b + u) * stride] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (b + u < count) s = s + t[u];
+  }
+  return s;
+}
+// Rows r0 .. r0 + nr of x [.][d] into xs [TR][ld] (ld odd: the lanes of a wave read distinct banks), element (r, c) as f(value, c), the rows past nr
+// zero; by 256 threads.  The rows are one contiguous stretch of x, read 16 bytes per lane where it starts aligned; a scalar tail ends it.
+struct StageAsIs { __device__ float operator()(float v, int) const { return v; } };
+template <int TR, int UNROLL = 4, class F = StageAsIs>
+__device__ __forceinline__ void stage_rows(const float* __restrict__ x, long r0, int nr, int d, int ld, float* xs, int tid, F f = F()) {
+  const float* src = x + r0 * d;
+  const int total = nr * d;
+  const int total4 = (reinterpret_cast<size_t>(src) & 15) == 0 ? total & ~3 : 0;
+#pragma unroll UNROLL
+  for (int e = tid * 4; e < total4; e += 1024) {
+    const float4 v = *reinterpret_cast<const float4*>(src + e);
+    const float vv[4] = {v.x, v.y, v.z, v.w};
+    int r = e / d, c = e - r * d;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xs[r * ld + c] = f(vv[u], c);
+      if (++c == d) { c = 0; ++r; }
+    }
+  }
+  for (int e = total4 + tid; e < TR * d; e += 256) {
+    const int r = e / d, c = e - r * d;
+    xs[r * ld + c] = e < total ? f(src[e], c) : 0.f;
+  }
+}
+// The sums of NV values per thread over the NT threads of a workgroup in a fixed fp64 tree (t += t + o, o = NT / 2 .. 1); every thread gets them.
+// red [NV][NT] is LDS; the leading barrier lets the call before still read it.  One barrier sequence carries all NV values.
+template <int NT, int NV>
+__device__ __forceinline__ void block_tree_sum(double (&v)[NV], double* red, int tid) {
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < NV; ++u) red[u * NT + tid] = v[u];
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+#pragma unroll
+      for (int u = 0; u < NV; ++u) red[u * NT + tid] += red[u * NT + tid + o];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int u = 0; u < NV; ++u) v[u] = red[u * NT];
 }
 // f16x3 operand handling shared by the convolution and GEMM kernels (see conv.hip for the arithmetic)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -525,6 +588,14 @@ double l2_filter_eps(int d, bool vec);   // relative bound |S~ - S| <= eps S of 
 int launch_l2_nearest(const float* x, long n, int d, const float* qs, int Q, int k, long* idx_out, double* dist_out, unsigned* status,
                       void* workspace, int exact, int num_cus, hipStream_t s);
 
+// ---------------------------------------------------------------- the mean of n doubles by the row-order chain (chain.hip)
+// out[0] = ((the rows of each block of ROWS_PER_BLOCK in row order from +0.0), the block partials in block order from +0.0) / n.  rows [n], part
+// [row_blocks(n)], out: device; a caller's scratch for rows and part is chain_mean_doubles(n) doubles.  One launch when n <= ROWS_PER_BLOCK, else two,
+// inside one KtScope named `timer`.
+inline size_t chain_mean_doubles(long n) { return (size_t)n + (size_t)row_blocks(n); }
+inline size_t chain_mean_workspace_bytes(long n) { return sizeof(double) * chain_mean_doubles(n) + 256; }
+void launch_chain_mean(const double* rows, long n, double* part, double* out, const char* timer, hipStream_t s);
+
 // ---------------------------------------------------------------- k-means + nearest-centroid pass (apply_r.lua:197-217)
 size_t kmeans_workspace_bytes(long N, int d, int k);
 // all pointers device; cent [k][d] holds the initial centroids on entry and the final ones on return; returns 1 when the
@@ -575,17 +646,15 @@ int launch_mixture(const float* x, long n, int d, int k, int niter, float var_fl
 
 // ---------------------------------------------------------------- the sampling layer of a VAE (vae.hip; gr_vae_sample_dev, gr_vae_sample_backward_dev)
 // h [B x 2 nd] = (mu | logvar), eps (nullable: 0) / z / gz [B x nd], gh [B x 2 nd], kl_rows [B] floats and kl 1 double nullable: all device; workspace
-// from vae_workspace_bytes, read only when kl is given; c = kl_weight / B.  Both return 1 outside 1 <= B < 2^31, 1 <= nd <= 256.
-size_t vae_workspace_bytes(long B);
+// of chain_mean_workspace_bytes(B), read only when kl is given; c = kl_weight / B.  Both return 1 outside 1 <= B < 2^31, 1 <= nd <= 256.
 int launch_vae_sample(const float* h, const float* eps, long B, int nd, float* z, float* kl_rows, double* kl, void* workspace, hipStream_t s);
 int launch_vae_sample_backward(const float* h, const float* eps, const float* gz, long B, int nd, double c, float* gh, hipStream_t s);
 
 // ---------------------------------------------------------------- SSIM and MSE per image (quality.hip; gr_ssim_dev)
-// a, b [n x channels x h x w], ssim_rows [n], mse_rows [n] nullable, mean 1 double nullable: all device; workspace from ssim_workspace_bytes, read only
+// a, b [n x channels x h x w], ssim_rows [n], mse_rows [n] nullable, mean 1 double nullable: all device; workspace of chain_mean_workspace_bytes(n), read only
 // when mean is given.  sigma <= 0: the uniform window.  Returns 1 outside the limits of ssim_args_ok or for a data_range that is not > 0, and 2 when
 // the device refuses the kernel's LDS.
 bool ssim_args_ok(long n, int channels, int h, int w, int win);
-size_t ssim_workspace_bytes(long n);
 int launch_ssim(const float* a, const float* b, long n, int channels, int h, int w, int win, double sigma, double data_range, float* ssim_rows, float* mse_rows,
                 double* mean, void* workspace, hipStream_t s);
 

@@ -15,7 +15,7 @@
 //
 // Kernels (all HBM-bound: one pass over x[N][d] each):
 //   kmeans_assign_kernel      thread = row, 256 rows x 32 columns staged through LDS per step, centroids via the scalar cache
-//   kmeans_accumulate_kernel  workgroup = 512 consecutive rows, thread = column: fp64 sums per (cluster, column) in LDS, in row
+//   kmeans_accumulate_kernel  workgroup = ROWS_PER_BLOCK consecutive rows, thread = column: fp64 sums per (cluster, column) in LDS, in row
 //                             order (deterministic), one partial block per workgroup
 //   kmeans_update_kernel      partial blocks summed in workgroup order; new centroids, c2, counts
 //   cosine_assign_kernel      thread = row: the k cosine similarities in nn.CosineDistance's exact op order (fp32 products,
@@ -27,7 +27,7 @@
 
 namespace gr {
 
-constexpr int KM_ROWS = 256, KM_DC = 32, KM_KMAX = 32, KM_RPB = 512;
+constexpr int KM_ROWS = 256, KM_DC = 32, KM_KMAX = 32;
 
 __global__ __launch_bounds__(KM_ROWS) void kmeans_assign_kernel(const float* __restrict__ x, long N, int d, const float* __restrict__ cent,
                                                                  const float* __restrict__ c2, int k, int* __restrict__ labels) {
@@ -65,10 +65,10 @@ __global__ __launch_bounds__(KM_ROWS) void kmeans_assign_kernel(const float* __r
 __global__ __launch_bounds__(256) void kmeans_accumulate_kernel(const float* __restrict__ x, long N, int d, const int* __restrict__ labels, int k,
                                                                  double* __restrict__ part_sum /*[nblk][k][d]*/, int* __restrict__ part_cnt /*[nblk][k]*/) {
   extern __shared__ double acc[];                      // [k][d]
-  __shared__ int lab[KM_RPB];
+  __shared__ int lab[ROWS_PER_BLOCK];
   const int tid = threadIdx.x;
-  const long r0 = (long)blockIdx.x * KM_RPB;
-  const int nr = (int)min((long)KM_RPB, N - r0);
+  const long r0 = (long)blockIdx.x * ROWS_PER_BLOCK;
+  const int nr = (int)min((long)ROWS_PER_BLOCK, N - r0);
   for (int e = tid; e < k * d; e += 256) acc[e] = 0.0;
   for (int e = tid; e < nr; e += 256) lab[e] = labels[r0 + e];
   __syncthreads();
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(KM_ROWS) void cosine_assign_kernel(const float* __r
 }
 
 size_t kmeans_workspace_bytes(long N, int d, int k) {
-  const long nblk = (N + KM_RPB - 1) / KM_RPB;
+  const long nblk = row_blocks(N);
   return sizeof(double) * (size_t)nblk * k * d + sizeof(int) * (size_t)nblk * k + sizeof(int) * (size_t)N + 1024;
 }
 
@@ -186,7 +186,7 @@ size_t kmeans_workspace_bytes(long N, int d, int k) {
 int launch_kmeans(const float* x, long N, int d, int k, int niter, float* cent, float* c2, float* counts, float* totalcounts,
                   int* labels_out /*nullable: labels of the last iteration*/, void* workspace, hipStream_t s) {
   if (k > KM_KMAX || (size_t)k * d * sizeof(double) > 60 * 1024 || d > 256) return 1;
-  const long nblk = (N + KM_RPB - 1) / KM_RPB;
+  const long nblk = row_blocks(N);
   double* part_sum = reinterpret_cast<double*>(workspace);
   int* part_cnt = reinterpret_cast<int*>(part_sum + (size_t)nblk * k * d);
   int* labels = labels_out ? labels_out : part_cnt + (size_t)nblk * k;
@@ -361,7 +361,7 @@ void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows,
 // ------------------------------------------------------------------ gr_cluster_dev: the whole of apply_r.lua:198-227, any k <= 4096
 // Narrow route (k < g_cluster_wide_min_k and k * d doubles within the accumulate kernel's 60 KB of LDS): launch_kmeans, launch_cosine_assign,
 // launch_cluster_members as they stand.  Wide route: the kernels below, which reproduce the narrow ones' bits for every k both take -
-//   kmeans_assign_wide_kernel  workgroup = 128 rows held in LDS for the whole call, centroid tiles of KW_KT = 128 visited in ascending j and staged
+//   kmeans_assign_wide_kernel  workgroup = 128 rows held in LDS for the whole call (stage_rows, kernels.h), centroid tiles of KW_KT = 128 visited in ascending j and staged
 //                              32 columns at a time; thread = 4 rows x 16 centroids (a half-wave shares its 16 centroids, its 32 lanes hold the
 //                              rows: about 8 (rows + centroids) LDS cycles against 2 rows x centroids VALU cycles per column and CU; 2 x 16 measured
 //                              2.2x the unfused VALU floor at k = 4096, 4 x 16 1.9x: DESIGN section 4), every (row, centroid) pair one sequential fp32 chain in column
@@ -376,30 +376,7 @@ void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows,
 //   cluster_members_wide_kernel  workgroup = cluster: walks its segments of the index grouped by the cosine labels and keeps the m smallest
 //                              cm_key keys as cluster_members_partial_kernel does (a set of distinct keys, sorted: independent of the visiting order)
 int g_cluster_wide_min_k = 33;          // gr_set_tuning "cluster_wide_min_k": the wide route from this k on (tests set 1 to compare the routes)
-constexpr int KW_TR = 128, KW_RT = 4, KW_KT = 128, KW_DC = 32, KW_CLD = 132, KW_KMAX = 4096, KW_SEGMAX = KM_RPB;   // rows: 32 lanes x KW_RT; centroids of a tile: 4 waves x 2 half-waves x 16
-
-// rows r0 .. r0 + nr of x into xs [KW_TR][ld] (the rows past nr zero): the block is one contiguous stretch of x, read 16 bytes per lane where its
-// start is 16-byte aligned
-__device__ __forceinline__ void wide_stage_rows(const float* __restrict__ x, long r0, int nr, int d, int ld, float* xs, int tid) {
-  const float* src = x + r0 * d;
-  const int total = nr * d;
-  const int total4 = (reinterpret_cast<size_t>(src) & 15) == 0 ? total & ~3 : 0;
-#pragma unroll 4
-  for (int e = tid * 4; e < total4; e += 1024) {
-    const float4 v = *reinterpret_cast<const float4*>(src + e);
-    const float vv[4] = {v.x, v.y, v.z, v.w};
-    int r = e / d, c = e - r * d;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xs[r * ld + c] = vv[u];
-      if (++c == d) { c = 0; ++r; }
-    }
-  }
-  for (int e = total4 + tid; e < KW_TR * d; e += 256) {
-    const int r = e / d, c = e - r * d;
-    xs[r * ld + c] = e < total ? src[e] : 0.f;
-  }
-}
+constexpr int KW_TR = 128, KW_RT = 4, KW_KT = 128, KW_DC = 32, KW_CLD = 132, KW_KMAX = 4096, KW_SEGMAX = ROWS_PER_BLOCK;   // rows: 32 lanes x KW_RT; centroids of a tile: 4 waves x 2 half-waves x 16
 
 __global__ __launch_bounds__(256) void kmeans_assign_wide_kernel(const float* __restrict__ x, long N, int d, const float* __restrict__ cent,
                                                                   const float* __restrict__ c2, int k, int* __restrict__ labels) {
@@ -412,7 +389,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_wide_kernel(const float* __
   const int ld = d | 1;
   const long r0 = (long)blockIdx.x * KW_TR;
   const int nr = (int)min((long)KW_TR, N - r0);
-  wide_stage_rows(x, r0, nr, d, ld, xs, tid);
+  stage_rows<KW_TR>(x, r0, nr, d, ld, xs, tid);
   float best[KW_RT];
   int bi[KW_RT];
   bool first_nan[KW_RT];
@@ -494,7 +471,7 @@ __global__ __launch_bounds__(256) void cosine_assign_wide_kernel(const float* __
   const int ld = d | 1;
   const long r0 = (long)blockIdx.x * KW_TR;
   const int nr = (int)min((long)KW_TR, N - r0);
-  wide_stage_rows(x, r0, nr, d, ld, xs, tid);
+  stage_rows<KW_TR>(x, r0, nr, d, ld, xs, tid);
   const float none = take_min ? INFINITY : -INFINITY;
   float best[KW_RT];
   int bi[KW_RT];
@@ -574,35 +551,35 @@ __global__ __launch_bounds__(256) void cosine_assign_wide_kernel(const float* __
 // first position in the block's order), nseg [block], nvalid [block] = rows with a label in [0, k)
 __global__ __launch_bounds__(256) void wide_group_kernel(const int* __restrict__ labels, long N, int k, int segs, int* __restrict__ order,
                                                           int* __restrict__ seg_label, int* __restrict__ seg_start, int* __restrict__ nseg, int* __restrict__ nvalid) {
-  __shared__ unsigned long long buf[KM_RPB];
-  __shared__ int scan[2][KM_RPB];
+  __shared__ unsigned long long buf[ROWS_PER_BLOCK];
+  __shared__ int scan[2][ROWS_PER_BLOCK];
   const int tid = threadIdx.x, b = blockIdx.x;
-  const long r0 = (long)b * KM_RPB;
-  const int nr = (int)min((long)KM_RPB, N - r0);
-  for (int i = tid; i < KM_RPB; i += 256) {
+  const long r0 = (long)b * ROWS_PER_BLOCK;
+  const int nr = (int)min((long)ROWS_PER_BLOCK, N - r0);
+  for (int i = tid; i < ROWS_PER_BLOCK; i += 256) {
     const int lab = i < nr ? labels[r0 + i] : -1;
     buf[i] = (lab >= 0 && lab < k) ? ((unsigned long long)lab << 32) | (unsigned)i : CM_NONE;
   }
-  cm_sort<KM_RPB>(buf, tid);
-  for (int i = tid; i < KM_RPB; i += 256) {
+  cm_sort<ROWS_PER_BLOCK>(buf, tid);
+  for (int i = tid; i < ROWS_PER_BLOCK; i += 256) {
     const unsigned long long key = buf[i];
     scan[0][i] = key != CM_NONE && (i == 0 || (buf[i - 1] >> 32) != (key >> 32));
   }
   int cur = 0;
-  for (int off = 1; off < KM_RPB; off <<= 1) {                          // inclusive scan of the segment heads
+  for (int off = 1; off < ROWS_PER_BLOCK; off <<= 1) {                  // inclusive scan of the segment heads
     __syncthreads();
-    for (int i = tid; i < KM_RPB; i += 256) scan[cur ^ 1][i] = scan[cur][i] + (i >= off ? scan[cur][i - off] : 0);
+    for (int i = tid; i < ROWS_PER_BLOCK; i += 256) scan[cur ^ 1][i] = scan[cur][i] + (i >= off ? scan[cur][i - off] : 0);
     cur ^= 1;
   }
   __syncthreads();
   if (tid == 0 && buf[0] == CM_NONE) { nseg[b] = 0; nvalid[b] = 0; }
-  for (int i = tid; i < KM_RPB; i += 256) {
+  for (int i = tid; i < ROWS_PER_BLOCK; i += 256) {
     const unsigned long long key = buf[i];
     if (key == CM_NONE) continue;
     const int s = scan[cur][i] - 1;
     order[r0 + i] = (int)(r0 + (long)(key & 0xFFFFFFFFull));
     if (i == 0 || (buf[i - 1] >> 32) != (key >> 32)) { seg_label[(long)b * segs + s] = (int)(key >> 32); seg_start[(long)b * segs + s] = i; }
-    if (i == KM_RPB - 1 || buf[i + 1] == CM_NONE) { nseg[b] = s + 1; nvalid[b] = i + 1; }
+    if (i == ROWS_PER_BLOCK - 1 || buf[i + 1] == CM_NONE) { nseg[b] = s + 1; nvalid[b] = i + 1; }
   }
 }
 
@@ -610,7 +587,7 @@ __global__ __launch_bounds__(256) void wide_segment_sum_kernel(const float* __re
                                                                 const int* __restrict__ seg_start, const int* __restrict__ nseg, const int* __restrict__ nvalid,
                                                                 double* __restrict__ part /*[block][segs][d]*/) {
   const int b = blockIdx.x, ns = nseg[b], nv = nvalid[b];
-  const long r0 = (long)b * KM_RPB;
+  const long r0 = (long)b * ROWS_PER_BLOCK;
   for (int e = threadIdx.x; e < ns * d; e += 256) {
     const int sg = e / d, t = e - sg * d;
     const int st = seg_start[(long)b * segs + sg], en = sg + 1 < ns ? seg_start[(long)b * segs + sg + 1] : nv;
@@ -647,7 +624,7 @@ __device__ __noinline__ int wide_find_segments(int j, long b0, long nblk, int se
   for (int q = 0; q < 4; ++q) { const int v = wsum[q]; if (q < w) off += v; tot += v; }
   if (slot >= 0) {
     const int p = off + __popcll(bal & ((1ull << lane) - 1ull));
-    l_seg[p] = b * segs + slot; l_pos[p] = (int)(b * KM_RPB) + start; l_len[p] = len;
+    l_seg[p] = b * segs + slot; l_pos[p] = (int)(b * ROWS_PER_BLOCK) + start; l_len[p] = len;
   }
   __syncthreads();
   return tot;
@@ -749,8 +726,8 @@ size_t cluster_workspace_bytes(long n, int d, int k) {
   const size_t a = 256;
   if (!cluster_takes_wide_route(d, k))
     return ((kmeans_workspace_bytes(n, d, k) + a - 1) / a + (cluster_members_workspace_bytes(n, k) + a - 1) / a) * a;
-  const size_t nblk = (size_t)((n + KM_RPB - 1) / KM_RPB), slots = nblk * wide_segs(k);
-  return sizeof(double) * slots * d + sizeof(int) * (2 * slots + 2 * nblk + nblk * KM_RPB + (size_t)n) + 8 * a;
+  const size_t nblk = (size_t)row_blocks(n), slots = nblk * wide_segs(k);
+  return sizeof(double) * slots * d + sizeof(int) * (2 * slots + 2 * nblk + nblk * ROWS_PER_BLOCK + (size_t)n) + 8 * a;
 }
 // The wide route's member lists, shared by launch_cluster and gr_cluster_members_wide_dev (a mixture's labels and posteriors): the labels are grouped
 // block by block (wide_group_kernel), then every cluster walks its segments (cluster_members_wide_kernel).  The index: three ints per segment slot,
@@ -758,19 +735,19 @@ size_t cluster_workspace_bytes(long n, int d, int k) {
 struct WideIndex { int *seg_label, *seg_start, *nseg, *nvalid, *order; };
 static size_t wide_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
 static WideIndex wide_index_carve(char*& ws, long n, int k) {
-  const size_t nblk = (size_t)((n + KM_RPB - 1) / KM_RPB), slots = nblk * wide_segs(k);
+  const size_t nblk = (size_t)row_blocks(n), slots = nblk * wide_segs(k);
   auto take = [&](size_t bytes) { char* p = ws; ws += wide_align(bytes); return reinterpret_cast<int*>(p); };
   WideIndex ix;
   ix.seg_label = take(sizeof(int) * slots);
   ix.seg_start = take(sizeof(int) * slots);
   ix.nseg = take(sizeof(int) * nblk);
   ix.nvalid = take(sizeof(int) * nblk);
-  ix.order = take(sizeof(int) * nblk * KM_RPB);
+  ix.order = take(sizeof(int) * nblk * ROWS_PER_BLOCK);
   return ix;
 }
 static int wide_group(const int* labels, long n, int k, const WideIndex& ix, hipStream_t s) {
   KtScope kt("wide_group_kernel", 0.0, 8.0 * n, s);
-  hipLaunchKernelGGL(wide_group_kernel, dim3((unsigned)((n + KM_RPB - 1) / KM_RPB)), dim3(256), 0, s, labels, n, k, wide_segs(k), ix.order, ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid);
+  hipLaunchKernelGGL(wide_group_kernel, dim3((unsigned)row_blocks(n)), dim3(256), 0, s, labels, n, k, wide_segs(k), ix.order, ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid);
   return 0;
 }
 static void wide_members(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
@@ -778,11 +755,11 @@ static void wide_members(const int* labels, const float* sims, long n, int k, in
   wide_group(labels, n, k, ix, s);
   KtScope kt("cluster_members_wide_kernel", 0.0, 12.0 * n, s);
   hipLaunchKernelGGL(cluster_members_wide_kernel, dim3(k), dim3(256), 0, s, ix.order, wide_segs(k), ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid,
-                     (n + KM_RPB - 1) / KM_RPB, sims, m, rows_out, sims_out, kept_out, sizes_out);
+                     row_blocks(n), sims, m, rows_out, sims_out, kept_out, sizes_out);
 }
 size_t cluster_members_wide_workspace_bytes(long n, int k) {
-  const size_t nblk = (size_t)((n + KM_RPB - 1) / KM_RPB), slots = nblk * wide_segs(k);
-  return sizeof(int) * (2 * slots + 2 * nblk + nblk * KM_RPB) + 8 * 256;
+  const size_t nblk = (size_t)row_blocks(n), slots = nblk * wide_segs(k);
+  return sizeof(int) * (2 * slots + 2 * nblk + nblk * ROWS_PER_BLOCK) + 8 * 256;
 }
 // launch_cluster_members' lists for any k <= 4096 by the wide route's kernels.  Returns 1 outside 1 <= k <= 4096, 1 <= m <= 128, 1 <= n < 2^31.
 int launch_cluster_members_wide(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
@@ -806,7 +783,7 @@ int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent,
     if (launch_cosine_assign(x, n, d, cent, k, take_min, w32, labels, sims, s)) return 1;
     return launch_cluster_members(labels, sims, n, k, m, rows_out, sims_out, kept_out, sizes_out, ws_members, s);
   }
-  const long nblk = (n + KM_RPB - 1) / KM_RPB;
+  const long nblk = row_blocks(n);
   const int segs = wide_segs(k);
   const size_t slots = (size_t)nblk * segs;
   auto take = [&](size_t bytes) { char* p = ws; ws += (bytes + a - 1) / a * a; return p; };

@@ -24,7 +24,7 @@
 // Kernels:
 //   mix_prep_kernel          thread = component
 //   mix_estep_kernel         workgroup = 64 rows held in LDS, wave = one of the 4 component ranges (means and h through the scalar cache), lane = row
-//   mix_loglik_*_kernel      block partials of L, then their join
+//   (chain.hip, launch_chain_mean)  loglik[it] from the L_i
 //   mix_mstep_kernel         workgroup = (8 components, one of the MX_P block ranges); per stage of 64 rows: r for the 64 x 8 pairs (lane = row,
 //                            wave = 2 components) into LDS, then thread = (column, JPT of the 8 components) adds the stage's rows in row order.
 //                            JPT = 8, 4, 2, 1 for d <= 256, 128, 64, 32, so that narrow tables still fill the workgroup
@@ -35,7 +35,6 @@
 
 namespace gr {
 
-constexpr int MX_RPB = 512;             // rows per block: the unit of the row-order chains
 constexpr int MX_P = 128;               // partial sets of the M-step sums: a constant of the library (tests/mixture_paths.py restates it)
 constexpr int MX_TR = 64;               // rows per LDS stage
 constexpr int MX_JT = 8;                // components per M-step workgroup
@@ -52,27 +51,6 @@ __global__ void mix_prep_kernel(const float* __restrict__ w, const float* __rest
     hinv[(long)j * d + t] = 0.5 / v;
   }
   cst[j] = log((double)w[j]) - 0.5 * ((double)d * MX_LOG_2PI + s);
-}
-
-// rows r0 .. r0 + nr of x into xs [MX_TR][ld] (the rows past nr zero): one contiguous stretch of x, read 16 bytes per lane where it starts aligned
-__device__ __forceinline__ void mix_stage_rows(const float* __restrict__ x, long r0, int nr, int d, int ld, float* xs, int tid) {
-  const float* src = x + r0 * d;
-  const int total = nr * d;
-  const int total4 = (reinterpret_cast<size_t>(src) & 15) == 0 ? total & ~3 : 0;
-  for (int e = tid * 4; e < total4; e += 1024) {
-    const float4 v = *reinterpret_cast<const float4*>(src + e);
-    const float vv[4] = {v.x, v.y, v.z, v.w};
-    int r = e / d, c = e - r * d;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xs[r * ld + c] = vv[u];
-      if (++c == d) { c = 0; ++r; }
-    }
-  }
-  for (int e = total4 + tid; e < MX_TR * d; e += 256) {
-    const int r = e / d, c = e - r * d;
-    xs[r * ld + c] = e < total ? src[e] : 0.f;
-  }
 }
 
 // l_ij: the chain of the file header.  mj, hj and c are wave-uniform.
@@ -97,7 +75,7 @@ __global__ __launch_bounds__(256) void mix_estep_kernel(const float* __restrict_
   const int ld = d | 1;
   const long r0 = (long)blockIdx.x * MX_TR;
   const int nr = (int)min((long)MX_TR, n - r0);
-  mix_stage_rows(x, r0, nr, d, ld, xs, tid);
+  stage_rows<MX_TR, 1>(x, r0, nr, d, ld, xs, tid);
   __syncthreads();
   const int kq = (k + 3) / 4, j_lo = w * kq, j_hi = min(k, j_lo + kq);
   const float* xr = xs + r * ld;
@@ -126,33 +104,6 @@ __global__ __launch_bounds__(256) void mix_estep_kernel(const float* __restrict_
   }
 }
 
-__global__ __launch_bounds__(64) void mix_loglik_block_kernel(const double* __restrict__ rowl, long n, double* __restrict__ part) {
-  __shared__ double v[MX_RPB];
-  const long r0 = (long)blockIdx.x * MX_RPB;
-  const int nr = (int)min((long)MX_RPB, n - r0);
-  for (int e = threadIdx.x; e < nr; e += 64) v[e] = rowl[r0 + e];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int e = 0; e < nr; ++e) s += v[e];
-    part[blockIdx.x] = s;
-  }
-}
-
-__global__ void mix_loglik_join_kernel(const double* __restrict__ part, long nblk, long n, double* __restrict__ out) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double s = 0.0;
-  for (long b = 0; b < nblk; b += 8) {                 // eight loads in flight, then the adds in block order
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = b + u < nblk ? part[b + u] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b + u < nblk) s += v[u];
-  }
-  *out = s / (double)n;
-}
-
 // part: s1 [MX_P][k][d], then s2 [MX_P][k][d], then sn [MX_P][k]
 template <int JPT>
 __global__ __launch_bounds__(256) void mix_mstep_kernel(const float* __restrict__ x, long n, int d, int k, const float* __restrict__ mu,
@@ -163,7 +114,7 @@ __global__ __launch_bounds__(256) void mix_mstep_kernel(const float* __restrict_
   constexpr int G = MX_JT / JPT, W = 256 / G;                           // thread = (column t < W, group g of JPT components)
   const int tid = threadIdx.x, j0 = blockIdx.x * MX_JT, p = blockIdx.y;
   const int ld = d | 1;
-  const long nblk = (n + MX_RPB - 1) / MX_RPB;
+  const long nblk = row_blocks(n);
   const long b_lo = p * nblk / MX_P, b_hi = (p + 1) * nblk / MX_P;     // contiguous, uneven ranges; empty ones when nblk < MX_P
   const int r1 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);    // the role in the r pass: row r1, components 2 w and 2 w + 1 of the tile
   const int t = tid % W, g = tid / W;
@@ -179,12 +130,12 @@ __global__ __launch_bounds__(256) void mix_mstep_kernel(const float* __restrict_
     double a1[JPT], a2[JPT], an[JPT];                                   // a block begins: its chains start from +0
 #pragma unroll
     for (int u = 0; u < JPT; ++u) a1[u] = a2[u] = an[u] = 0.0;
-    for (int st = 0; st < MX_RPB / MX_TR; ++st) {
-      const long row0 = b * MX_RPB + (long)st * MX_TR;
+    for (int st = 0; st < ROWS_PER_BLOCK / MX_TR; ++st) {
+      const long row0 = b * ROWS_PER_BLOCK + (long)st * MX_TR;
       if (row0 >= n) break;                                             // (the same in every thread)
       const int nr = (int)min((long)MX_TR, n - row0);
       __syncthreads();                                                  // the stage before this one has been read
-      mix_stage_rows(x, row0, nr, d, ld, xs, tid);
+      stage_rows<MX_TR, 1>(x, row0, nr, d, ld, xs, tid);
       __syncthreads();
       const double Li = r1 < nr ? rowl[row0 + r1] : 0.0;
 #pragma unroll
@@ -253,19 +204,17 @@ __global__ __launch_bounds__(256) void mix_update_kernel(const double* __restric
 // ------------------------------------------------------------------ launcher
 // doubles: c [k], h [k][d], L [n], the block partials of L [ceil(n / 512)], the MX_P partial sets [MX_P][k][2 d + 1]
 size_t mixture_workspace_bytes(long n, int d, int k) {
-  const size_t nblk = (size_t)((n + MX_RPB - 1) / MX_RPB);
-  return sizeof(double) * ((size_t)k + (size_t)k * d + (size_t)n + nblk + (size_t)MX_P * k * (2 * (size_t)d + 1)) + 1024;
+  return sizeof(double) * ((size_t)k + (size_t)k * d + chain_mean_doubles(n) + (size_t)MX_P * k * (2 * (size_t)d + 1)) + 1024;
 }
 
 int launch_mixture(const float* x, long n, int d, int k, int niter, float var_floor, float* w, float* mu, float* vars, double* loglik, int* labels,
                    float* post, float* rowll, void* workspace, hipStream_t s) {
   if (n < 1 || n > 0x7FFFFFFFL || d < 1 || d > MX_MAX || k < 1 || k > MX_MAX || niter < 0 || !(var_floor > 0.f)) return 1;
-  const long nblk = (n + MX_RPB - 1) / MX_RPB;
   double* cst = reinterpret_cast<double*>(workspace);
   double* hinv = cst + k;
   double* rowl = hinv + (size_t)k * d;
   double* llpart = rowl + (size_t)n;
-  double* part = llpart + nblk;
+  double* part = llpart + row_blocks(n);
   const int jpt = d > 128 ? 8 : d > 64 ? 4 : d > 32 ? 2 : 1;
   const void* mstep = jpt == 8 ? reinterpret_cast<const void*>(mix_mstep_kernel<8>) : jpt == 4 ? reinterpret_cast<const void*>(mix_mstep_kernel<4>)
                     : jpt == 2 ? reinterpret_cast<const void*>(mix_mstep_kernel<2>) : reinterpret_cast<const void*>(mix_mstep_kernel<1>);
@@ -280,9 +229,7 @@ int launch_mixture(const float* x, long n, int d, int k, int niter, float var_fl
     { KtScope kt("mix_estep_kernel", 4.0 * n * d * k, 4.0 * n * d + 8.0 * n, s);
       hipLaunchKernelGGL(mix_estep_kernel, dim3(egrid), dim3(256), lds, s, x, n, d, k, mu, hinv, cst, rowl, last ? labels : nullptr, last ? post : nullptr,
                          last ? rowll : nullptr); }
-    KtScope kt("mix_loglik_kernels", (double)n, 8.0 * n, s);
-    hipLaunchKernelGGL(mix_loglik_block_kernel, dim3((unsigned)nblk), dim3(64), 0, s, rowl, n, llpart);
-    hipLaunchKernelGGL(mix_loglik_join_kernel, dim3(1), dim3(64), 0, s, llpart, nblk, n, loglik + it);
+    launch_chain_mean(rowl, n, llpart, loglik + it, "mix_loglik_kernels", s);
   };
   const dim3 mgrid((k + MX_JT - 1) / MX_JT, MX_P);
   for (int it = 0; it < niter; ++it) {

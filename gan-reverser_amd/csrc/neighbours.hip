@@ -309,7 +309,7 @@ bool l2_nearest_direct(long n) { return n <= L2_DIRECT_ROWS; }
 int launch_l2_nearest(const float* x, long n, int d, const float* qs, int Q, int k, long* idx_out, double* dist_out, unsigned* status,
                       void* workspace, int exact, int num_cus, hipStream_t s) {
   if (n < 1 || n >= 0xFFFFFFFFl || d < 1 || d > 65536 || Q < 1 || k < 1 || k > 128 || k > n) return -1;
-  const bool vec = (d & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)qs & 15) == 0;
+  const bool vec = (d & 3) == 0 && aligned16(x) && aligned16(qs);
   if (exact) {
     unsigned long long* ekeys = reinterpret_cast<unsigned long long*>(workspace);
     {

@@ -49,6 +49,19 @@ template <class Launch> static int map_host(gr_ctx* c, const float* in, size_t n
   TRY(s.download(out, dout));
   return s.finish();
 }
+// a device entry point that is "scratch, launch, map the status": launch(scratch) gets `bytes` of the context workspace and returns its launcher's
+// status; 1 (any other non-zero) and 2 become the caller's own code and text - a format of at most one int, which a text without one ignores
+struct LaunchError { int code; const char* fmt; int arg; };
+template <class Launch> static int scratch_launch(gr_ctx* c, size_t bytes, Launch launch, LaunchError on1, LaunchError on2 = {0, nullptr, 0}) {
+  Staging s(c);
+  auto scratch = s.reserve<char>(bytes);
+  TRY(s.grow());
+  const int r = launch(static_cast<void*>(s.ptr(scratch)));
+  if (r == 2 && on2.fmt) return fail(c, on2.code, on2.fmt, on2.arg);
+  if (r) return fail(c, on1.code, on1.fmt, on1.arg);
+  LAUNCHCHK(c);
+  return GR_OK;
+}
 
 // ------------------------------------------------------------------ criterion
 extern "C" int gr_mse_dev(gr_ctx* c, const float* x, const float* t, int64_t n, int64_t ng, double* loss_dev, float* grad) {
@@ -478,13 +491,9 @@ extern "C" int gr_cluster_members_dev(gr_ctx* c, const int32_t* labels, const fl
   if (n <= 0 || k <= 0 || m <= 0) return fail(c, GR_ERR_INVALID, "gr_cluster_members_dev: n %lld, k %d, m %d must be positive", (long long)n, k, m);
   if (n >= ((int64_t)1 << 31) || k > 32 || m > 128)
     return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_dev: n %lld, k %d, m %d: n < 2^31, k <= 32 and m <= 128 only", (long long)n, k, m);
-  Staging s(c);
-  auto scratch = s.reserve<char>(cluster_members_workspace_bytes(n, k));
-  TRY(s.grow());
-  if (launch_cluster_members(labels, sims, n, k, m, reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, s.ptr(scratch), c->stream))
-    return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, cluster_members_workspace_bytes(n, k), [&](void* ws) {
+    return launch_cluster_members(labels, sims, n, k, m, reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_cluster_members_dev: unsupported size", 0});
 }
 extern "C" int gr_cluster_dev(gr_ctx* c, const float* x, int64_t n, int d, int k, int niter, float* cent, int take_min, int m, float* totalcounts,
                               int32_t* labels, float* sims, int64_t* rows_out, float* sims_out, int32_t* kept_out, int32_t* sizes_out) {
@@ -515,13 +524,9 @@ extern "C" int gr_cluster_members_wide_dev(gr_ctx* c, const int32_t* labels, con
   if (k > 4096) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: k %d: at most 4096 clusters", k);
   if (m > 128) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: m %d: at most 128 rows per cluster", m);
   if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: n %lld: fewer than 2^31 rows", (long long)n);
-  Staging s(c);
-  auto scratch = s.reserve<char>(cluster_members_wide_workspace_bytes(n, k));
-  TRY(s.grow());
-  if (launch_cluster_members_wide(labels, sims, n, k, m, reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, s.ptr(scratch), c->stream))
-    return fail(c, GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, cluster_members_wide_workspace_bytes(n, k), [&](void* ws) {
+    return launch_cluster_members_wide(labels, sims, n, k, m, reinterpret_cast<long*>(rows_out), sims_out, kept_out, sizes_out, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_cluster_members_wide_dev: unsupported size", 0});
 }
 extern "C" int gr_cluster_faces_dev(gr_ctx* c, const float* table, int64_t n_rows, int64_t d, const int64_t* rows, const int32_t* kept, int k, int m, float* out) {
   if (!c) return GR_ERR_INVALID;
@@ -541,12 +546,8 @@ extern "C" int gr_pca_dev(gr_ctx* c, const float* x, int64_t n, int d, double* m
   if (n < 2) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: n %lld: at least 2 rows", (long long)n);
   if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: n %lld: fewer than 2^31 rows", (long long)n);
   if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: d %d: at most 256 columns", d);
-  Staging s(c);
-  auto scratch = s.reserve<char>(pca_workspace_bytes(n, d));
-  TRY(s.grow());
-  if (launch_pca(x, n, d, mean, cov, eigvals, axes, info, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_pca_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, pca_workspace_bytes(n, d), [&](void* ws) { return launch_pca(x, n, d, mean, cov, eigvals, axes, info, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_pca_dev: unsupported size", 0});
 }
 extern "C" int gr_pca_project_dev(gr_ctx* c, const float* x, int64_t n, int d, const double* mean, const float* axes, const double* eigvals, int k, int whiten,
                                   float* out) {
@@ -575,14 +576,9 @@ extern "C" int gr_mixture_dev(gr_ctx* c, const float* x, int64_t n, int d, int k
   if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: n %lld: fewer than 2^31 rows", (long long)n);
   if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: d %d: at most 256 columns", d);
   if (k > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: k %d: at most 256 components", k);
-  Staging s(c);
-  auto scratch = s.reserve<char>(mixture_workspace_bytes(n, d, k));
-  TRY(s.grow());
-  const int r = launch_mixture(x, n, d, k, niter, var_floor, weights, means, vars, loglik, labels, post, rowll, s.ptr(scratch), c->stream);
-  if (r == 2) return fail(c, GR_ERR_HIP, "gr_mixture_dev: the device refuses the kernels' LDS (d %d)", d);
-  if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_mixture_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, mixture_workspace_bytes(n, d, k), [&](void* ws) {
+    return launch_mixture(x, n, d, k, niter, var_floor, weights, means, vars, loglik, labels, post, rowll, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_mixture_dev: unsupported size", 0}, {GR_ERR_HIP, "gr_mixture_dev: the device refuses the kernels' LDS (d %d)", d});
 }
 
 // ------------------------------------------------------------------ the sampling layer of a VAE (vae.hip)
@@ -597,7 +593,7 @@ extern "C" int gr_vae_sample_dev(gr_ctx* c, const float* h, const float* eps, in
   if (!c) return GR_ERR_INVALID;
   TRY(vae_check(c, "gr_vae_sample_dev", !h || !z, B, nd));
   Staging s(c);
-  auto scratch = s.reserve<char>(kl ? vae_workspace_bytes(B) : 0);
+  auto scratch = s.reserve<char>(kl ? chain_mean_workspace_bytes(B) : 0);
   if (kl) TRY(s.grow());
   if (launch_vae_sample(h, eps, B, nd, z, kl_rows, kl, kl ? s.ptr(scratch) : nullptr, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_vae_sample_dev: unsupported size");
   LAUNCHCHK(c);
@@ -616,7 +612,7 @@ extern "C" int gr_vae_sample_host(gr_ctx* c, const float* h, const float* eps, i
   TRY(vae_check(c, "gr_vae_sample_host", !h || !z, B, nd));
   const size_t n = (size_t)B * nd;
   Staging s(c);
-  auto scratch = s.reserve<char>(vae_workspace_bytes(B));
+  auto scratch = s.reserve<char>(chain_mean_workspace_bytes(B));
   auto dh = s.reserve<float>(2 * n), de = s.reserve<float>(n), dz = s.reserve<float>(n), dr = s.reserve<float>((size_t)B);
   auto dk = s.reserve<double>(1);
   TRY(s.grow()); TRY(s.upload(dh, h));
@@ -665,7 +661,7 @@ extern "C" int gr_ssim_dev(gr_ctx* c, const float* a, const float* b, int64_t n,
   if (!c) return GR_ERR_INVALID;
   TRY(ssim_check(c, "gr_ssim_dev", !a || !b || !ssim_rows, n, channels, h, w, win, data_range));
   Staging s(c);
-  auto scratch = s.reserve<char>(mean ? ssim_workspace_bytes((long)n) : 0);
+  auto scratch = s.reserve<char>(mean ? chain_mean_workspace_bytes((long)n) : 0);
   if (mean) TRY(s.grow());
   return ssim_launch_status(c, "gr_ssim_dev", launch_ssim(a, b, (long)n, channels, h, w, win, sigma, data_range, ssim_rows, mse_rows, mean,
                                                           mean ? s.ptr(scratch) : nullptr, c->stream));
@@ -677,7 +673,7 @@ extern "C" int gr_ssim_host(gr_ctx* c, const float* a, const float* b, int64_t n
   TRY(ssim_check(c, "gr_ssim_host", !a || !b || !ssim_rows, n, channels, h, w, win, data_range));
   const size_t elems = (size_t)n * channels * h * w;
   Staging s(c);
-  auto scratch = s.reserve<char>(ssim_workspace_bytes((long)n));
+  auto scratch = s.reserve<char>(chain_mean_workspace_bytes((long)n));
   auto da = s.reserve<float>(elems), db = s.reserve<float>(elems), ds = s.reserve<float>((size_t)n), dm = s.reserve<float>((size_t)n);
   auto dq = s.reserve<double>(1);
   TRY(s.grow()); TRY(s.upload(da, a)); TRY(s.upload(db, b));
@@ -702,47 +698,30 @@ extern "C" int gr_tsne_affinities_dev(gr_ctx* c, const float* x, int64_t n, int 
   if (d < 1) return fail(c, GR_ERR_INVALID, "gr_tsne_affinities_dev: d %d must be positive", d);
   if (!(perplexity >= 1.0 && perplexity <= (double)(n - 1) / 3.0))
     return fail(c, GR_ERR_INVALID, "gr_tsne_affinities_dev: perplexity %g: 1 to (n - 1) / 3 = %g", perplexity, (double)(n - 1) / 3.0);
-  Staging s(c);
-  auto scratch = s.reserve<char>(tsne_affinities_workspace_bytes((int)n, d));
-  TRY(s.grow());
-  const int r = launch_tsne_affinities(x, (int)n, d, perplexity, p, beta, info, s.ptr(scratch), c->stream);
-  if (r == 2) return fail(c, GR_ERR_HIP, "gr_tsne_affinities_dev: hipMemsetAsync failed");
-  if (r) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_affinities_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, tsne_affinities_workspace_bytes((int)n, d), [&](void* ws) {
+    return launch_tsne_affinities(x, (int)n, d, perplexity, p, beta, info, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_tsne_affinities_dev: unsupported size", 0}, {GR_ERR_HIP, "gr_tsne_affinities_dev: hipMemsetAsync failed", 0});
 }
 extern "C" int gr_tsne_gradient_dev(gr_ctx* c, const float* p, const float* y, int64_t n, float exaggeration, float* grad, double* z) {
   if (!c) return GR_ERR_INVALID;
   if (!p || !y || !grad) return fail(c, GR_ERR_INVALID, "gr_tsne_gradient_dev: null pointer");
   TRY(tsne_n_check(c, "gr_tsne_gradient_dev", n, 1));
-  Staging s(c);
-  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
-  TRY(s.grow());
-  if (launch_tsne_gradient(p, y, (int)n, exaggeration, grad, z, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_gradient_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, tsne_iter_workspace_bytes((int)n), [&](void* ws) { return launch_tsne_gradient(p, y, (int)n, exaggeration, grad, z, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_tsne_gradient_dev: unsupported size", 0});
 }
 extern "C" int gr_tsne_update_dev(gr_ctx* c, float* y, const float* grad, float* inc, float* gains, int64_t n, float eta, float momentum, float min_gain) {
   if (!c) return GR_ERR_INVALID;
   if (!y || !grad || !inc || !gains) return fail(c, GR_ERR_INVALID, "gr_tsne_update_dev: null pointer");
   TRY(tsne_n_check(c, "gr_tsne_update_dev", n, 1));
-  Staging s(c);
-  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
-  TRY(s.grow());
-  if (launch_tsne_update(y, grad, inc, gains, (int)n, eta, momentum, min_gain, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_update_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, tsne_iter_workspace_bytes((int)n), [&](void* ws) { return launch_tsne_update(y, grad, inc, gains, (int)n, eta, momentum, min_gain, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_tsne_update_dev: unsupported size", 0});
 }
 extern "C" int gr_tsne_kl_dev(gr_ctx* c, const float* p, const float* y, int64_t n, double* kl) {
   if (!c) return GR_ERR_INVALID;
   if (!p || !y || !kl) return fail(c, GR_ERR_INVALID, "gr_tsne_kl_dev: null pointer");
   TRY(tsne_n_check(c, "gr_tsne_kl_dev", n, 1));
-  Staging s(c);
-  auto scratch = s.reserve<char>(tsne_iter_workspace_bytes((int)n));
-  TRY(s.grow());
-  if (launch_tsne_kl(p, y, (int)n, kl, s.ptr(scratch), c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_tsne_kl_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, tsne_iter_workspace_bytes((int)n), [&](void* ws) { return launch_tsne_kl(p, y, (int)n, kl, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_tsne_kl_dev: unsupported size", 0});
 }
 extern "C" int gr_tsne_run_dev(gr_ctx* c, const float* p, int64_t n, const gr_tsne_config* cfg, float* y, float* inc, float* gains, int first_iter, int iters,
                                double* kl, int kl_every) {
@@ -773,13 +752,9 @@ extern "C" int gr_map_cells_dev(gr_ctx* c, const float* y, int64_t n, int grid_h
   if (grid_h < 1 || grid_w < 1) return fail(c, GR_ERR_INVALID, "gr_map_cells_dev: grid %d x %d must be positive", grid_h, grid_w);
   if (n >= ((int64_t)1 << 31)) return fail(c, GR_ERR_UNSUPPORTED, "gr_map_cells_dev: n %lld: fewer than 2^31 rows", (long long)n);
   if (grid_h > 1024 || grid_w > 1024) return fail(c, GR_ERR_UNSUPPORTED, "gr_map_cells_dev: grid %d x %d: at most 1024 cells a side", grid_h, grid_w);
-  Staging s(c);
-  auto scratch = s.reserve<char>(map_cells_workspace_bytes(grid_h * grid_w));
-  TRY(s.grow());
-  if (launch_map_cells(y, (long)n, grid_h, grid_w, reinterpret_cast<long*>(rows_out), counts, s.ptr(scratch), c->stream))
-    return fail(c, GR_ERR_UNSUPPORTED, "gr_map_cells_dev: unsupported size");
-  LAUNCHCHK(c);
-  return GR_OK;
+  return scratch_launch(c, map_cells_workspace_bytes(grid_h * grid_w), [&](void* ws) {
+    return launch_map_cells(y, (long)n, grid_h, grid_w, reinterpret_cast<long*>(rows_out), counts, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_map_cells_dev: unsupported size", 0});
 }
 
 // ------------------------------------------------------------------ apply_r.lua:355-372 detectAnomalies' distance

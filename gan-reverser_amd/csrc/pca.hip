@@ -7,20 +7,19 @@
 // Kernels:
 //   pca_mean_kernel       workgroup = max(1, 256 / d) blocks of 512 consecutive rows, thread = (block, column): the block's rows added in row
 //                         order in fp64 -> one partial per block
-//   pca_mean_join_kernel  thread = column: the block partials in block order from +0.0, one division by n
+//   pca_mean_join_kernel  thread = column: the block partials in block order from +0.0 (ordered_sum8, kernels.h), one division by n
 //   pca_cov_kernel        workgroup = (64 x 64 tile of C with tile row <= tile column, one of PCA_P contiguous ranges of 512-row blocks); the
 //                         centred rows c = (float)((double)x - mean) go through LDS 64 at a time; thread = 4 x 4 elements, each one sequential
 //                         fp32 chain over the block's rows (acc = acc + c_i * c_j), added to the thread's fp64 sums when the block ends
 //   pca_cov_join_kernel   element (i <= j): the PCA_P partials in order from +0.0, one division by n - 1, written to [i][j] and [j][i]
 //   pca_jacobi_kernel     ONE workgroup of 1024 threads: cyclic Jacobi in fp64 with the round-robin ordering - floor(d / 2) disjoint rotations
 //                         between two workgroup barriers; A and V^T live in context scratch (512 KB each at d = 256: L2)
-//   pca_project_kernel    workgroup = 128 centred rows held in LDS, axis tiles of 128 staged 32 columns at a time (kmeans_assign_wide_kernel's
+//   pca_project_kernel    workgroup = 128 centred rows held in LDS (stage_rows, kernels.h), axis tiles of 128 staged 32 columns at a time (kmeans_assign_wide_kernel's
 //                         shape): thread = 4 rows x 16 axes, every (row, axis) one sequential fp32 chain in column order
 #include "kernels.h"
 
 namespace gr {
 
-constexpr int PCA_RPB = 512;            // rows per block: the unit of the fp32 chains and of the fp64 joins
 constexpr int PCA_P = 128;              // partial covariance matrices: a constant of the library (tests/pca_paths.py restates it)
 constexpr int PCA_T = 64, PCA_KC = 64;  // tile of C per workgroup; rows per LDS stage
 constexpr int PCA_DMAX = 256;
@@ -33,8 +32,8 @@ __global__ __launch_bounds__(256) void pca_mean_kernel(const float* __restrict__
   const int per = max(1, 256 / d), sub = threadIdx.x / d, t = threadIdx.x - sub * d;      // a workgroup takes as many blocks as its threads hold columns
   const long blk = (long)blockIdx.x * per + sub;
   if (sub >= per || blk >= nblk) return;
-  const long r0 = blk * PCA_RPB;
-  const int nr = (int)min((long)PCA_RPB, n - r0);
+  const long r0 = blk * ROWS_PER_BLOCK;
+  const int nr = (int)min((long)ROWS_PER_BLOCK, n - r0);
   const float* src = x + r0 * d + t;
   double s = 0.0;
   for (int r = 0; r < nr; r += 8) {                    // eight loads in flight, then the adds in row order
@@ -51,16 +50,7 @@ __global__ __launch_bounds__(256) void pca_mean_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void pca_mean_join_kernel(const double* __restrict__ part, long nblk, long n, int d, double* __restrict__ mean) {
   const int t = threadIdx.x;
   if (t >= d) return;
-  double s = 0.0;
-  for (long b = 0; b < nblk; b += 8) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = b + u < nblk ? part[(b + u) * d + t] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b + u < nblk) s += v[u];
-  }
-  mean[t] = s / (double)n;
+  mean[t] = ordered_sum8(part + t, nblk, d) / (double)n;
 }
 
 __global__ __launch_bounds__(256) void pca_cov_kernel(const float* __restrict__ x, long n, int d, const double* __restrict__ mean, int ntile,
@@ -71,7 +61,7 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(const float* __restrict__ 
   int ti = 0, rem = blockIdx.x;
   while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
   const int tj = ti + rem;
-  const long nblk = (n + PCA_RPB - 1) / PCA_RPB;
+  const long nblk = row_blocks(n);
   const long b_lo = p * nblk / PCA_P, b_hi = (p + 1) * nblk / PCA_P;      // contiguous, uneven ranges; empty ones when nblk < PCA_P
   const int c = tid & 63, rs = tid >> 6;                                   // this thread stages column c of rows rs, rs + 4, ...
   const int ca = ti * PCA_T + c, cb = tj * PCA_T + c;
@@ -82,11 +72,11 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(const float* __restrict__ 
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) sum[a][b] = 0.0;
-  // The range's rows in stages of PCA_KC; a block is PCA_RPB / PCA_KC stages (only the table's last block may have fewer).  The raw values of
+  // The range's rows in stages of PCA_KC; a block is ROWS_PER_BLOCK / PCA_KC stages (only the table's last block may have fewer).  The raw values of
   // stage s + 1 are fetched into registers while stage s is multiplied.
-  const long row_lo = b_lo * PCA_RPB, row_hi = min(b_hi * PCA_RPB, n);
+  const long row_lo = b_lo * ROWS_PER_BLOCK, row_hi = min(b_hi * ROWS_PER_BLOCK, n);
   const long nstage = row_hi > row_lo ? (row_hi - row_lo + PCA_KC - 1) / PCA_KC : 0;
-  constexpr int SPB = PCA_RPB / PCA_KC, NU = PCA_KC / 4;
+  constexpr int SPB = ROWS_PER_BLOCK / PCA_KC, NU = PCA_KC / 4;
   float va[NU], vb[NU], acc[4][4];
   auto fetch = [&](long s) {
     const long base = row_lo + s * PCA_KC + rs;
@@ -158,16 +148,11 @@ __global__ __launch_bounds__(256) void pca_cov_join_kernel(const double* __restr
   if (cov) { cov[i * d + j] = v; cov[j * d + i] = v; }
 }
 
-// the sum of one value per thread in a fixed tree; every thread gets it.  Starts with a barrier (red may still be read from the call before).
+// block_tree_sum of one value per thread, out of line: the Jacobi kernel calls it twice and keeps its registers for the rotations
 __device__ __noinline__ double pca_block_sum(double v, double* red, int tid) {
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int o = PCA_JT / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
+  double a[1] = {v};
+  block_tree_sum<PCA_JT, 1>(a, red, tid);
+  return a[0];
 }
 
 // a [d][d] symmetric in (both triangles the same bits; destroyed), vt [d][d] scratch (row = eigenvector).  Round r of a sweep pairs the m = d + (d & 1)
@@ -339,26 +324,7 @@ __global__ __launch_bounds__(256) void pca_project_kernel(const float* __restric
   const int nr = (int)min((long)PJ_TR, n - r0);
   if (tid < d) ms[tid] = mean[tid];
   __syncthreads();
-  {                                                                     // the block is one contiguous stretch of x: 16 bytes per lane where it starts aligned
-    const float* src = x + r0 * d;
-    const int total = nr * d;
-    const int total4 = (reinterpret_cast<size_t>(src) & 15) == 0 ? total & ~3 : 0;
-#pragma unroll 4
-    for (int e = tid * 4; e < total4; e += 1024) {
-      const float4 v = *reinterpret_cast<const float4*>(src + e);
-      const float vv[4] = {v.x, v.y, v.z, v.w};
-      int r = e / d, c = e - r * d;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xs[r * ld + c] = (float)((double)vv[u] - ms[c]);
-        if (++c == d) { c = 0; ++r; }
-      }
-    }
-    for (int e = total4 + tid; e < PJ_TR * d; e += 256) {
-      const int r = e / d, c = e - r * d;
-      xs[r * ld + c] = e < total ? (float)((double)src[e] - ms[c]) : 0.f;
-    }
-  }
+  stage_rows<PJ_TR>(x, r0, nr, d, ld, xs, tid, [&](float v, int c) { return (float)((double)v - ms[c]); });      // centred on the way in
   for (int j0 = 0; j0 < k; j0 += PJ_AT) {
     float acc[PJ_RT][16];
 #pragma unroll
@@ -408,13 +374,13 @@ __global__ __launch_bounds__(256) void pca_project_kernel(const float* __restric
 // ------------------------------------------------------------------ launchers
 // block partials of the mean [ceil(n / 512)][d], the PCA_P partial matrices, A and V^T: all doubles
 size_t pca_workspace_bytes(long n, int d) {
-  const size_t nblk = (size_t)((n + PCA_RPB - 1) / PCA_RPB);
+  const size_t nblk = (size_t)row_blocks(n);
   return sizeof(double) * (nblk * d + (size_t)PCA_P * d * d + 2 * (size_t)d * d) + 1024;
 }
 
 int launch_pca(const float* x, long n, int d, double* mean, double* cov, double* eigvals, float* axes, int* info, void* workspace, hipStream_t s) {
   if (n < 2 || n > 0x7FFFFFFFL || d < 1 || d > PCA_DMAX) return 1;
-  const long nblk = (n + PCA_RPB - 1) / PCA_RPB;
+  const long nblk = row_blocks(n);
   double* part_mean = reinterpret_cast<double*>(workspace);
   double* part_cov = part_mean + (size_t)nblk * d;
   double* a = part_cov + (size_t)PCA_P * d * d;

@@ -25,13 +25,12 @@
 //                            shared) and leaves S in LDS at an odd pitch, where thread = row adds its row.  A strip holds as many rows as the LDS
 //                            budget admits (ssim_plan); strips overlap by win - 1 rows, whose horizontal pass is repeated.  The sums R_r wait in LDS
 //                            until the channel is done, so no result depends on the strip height.
-//   ssim_mean_block_kernel / _join   block partials of q, then their join (one launch when n <= 512)
+//   (chain.hip, launch_chain_mean)   mean[0] from the q
 // Roughly 4 win (h ow + oh ow) 5 fp64 operations per channel against 8 h w bytes read: compute- and LDS-bound, not bandwidth-bound.
 #include "kernels.h"
 
 namespace gr {
 
-constexpr int SQ_RPB = 512;                   // images per block: the unit of the mean's chain (the library's reduction convention)
 constexpr int SQ_MAX_HW = 128;                // h and w at most
 constexpr int SQ_MAX_WIN = 11;
 constexpr size_t SQ_LDS_SMALL = 64 * 1024, SQ_LDS_LARGE = 144 * 1024;      // the budget of a strip: the larger one only where the smaller gives short strips
@@ -185,45 +184,11 @@ __global__ __launch_bounds__(256) void ssim_image_kernel(const float* __restrict
   }
 }
 
-// part[b] = the q of block b in image order from +0.0; with one block (mean non-null) the mean itself: 0.0 + part[0] is part[0], bit for bit
-__global__ __launch_bounds__(64) void ssim_mean_block_kernel(const double* __restrict__ rowq, long n, double* __restrict__ part, double* __restrict__ mean) {
-  __shared__ double v[SQ_RPB];
-  const long r0 = (long)blockIdx.x * SQ_RPB;
-  const int nr = (int)min((long)SQ_RPB, n - r0);
-  for (int e = threadIdx.x; e < nr; e += 64) v[e] = rowq[r0 + e];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int e = 0; e < nr; ++e) s = s + v[e];
-    if (mean) *mean = s / (double)n;
-    else part[blockIdx.x] = s;
-  }
-}
-
-__global__ void ssim_mean_join_kernel(const double* __restrict__ part, long nblk, long n, double* __restrict__ mean) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double s = 0.0;
-  for (long b = 0; b < nblk; b += 8) {                 // eight loads in flight, then the adds in block order
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = b + u < nblk ? part[b + u] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b + u < nblk) s = s + v[u];
-  }
-  *mean = s / (double)n;
-}
-
 // ------------------------------------------------------------------ launchers
-static bool sq_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
-
 bool ssim_args_ok(long n, int channels, int h, int w, int win) {
   return n >= 1 && n <= 0x7FFFFFFFL && channels >= 1 && win >= 3 && win <= SQ_MAX_WIN && (win & 1) && h >= win && w >= win &&
          h <= SQ_MAX_HW && w <= SQ_MAX_HW;
 }
-
-// doubles: q [n], the block partials [ceil(n / 512)]
-size_t ssim_workspace_bytes(long n) { return sizeof(double) * ((size_t)n + (size_t)((n + SQ_RPB - 1) / SQ_RPB)) + 256; }
 
 template <int WIN>
 static int ssim_launch_image(const float* a, const float* b, long n, int C, int h, int w, const SsimPlan& p, int vec, const SsimWindow& g, double c1, double c2,
@@ -258,7 +223,7 @@ int launch_ssim(const float* a, const float* b, long n, int channels, int h, int
   const double c1 = k1 * k1, c2 = k2 * k2;
   const SsimPlan p = ssim_plan(h, w, win);
   if (p.rows < win || p.bytes > SQ_LDS_LARGE) return 1;
-  const int vec = w % 4 == 0 && sq_aligned16(a) && sq_aligned16(b);
+  const int vec = w % 4 == 0 && aligned16(a) && aligned16(b);
   double* rowq = mean ? reinterpret_cast<double*>(workspace) : nullptr;
   int r;
   switch (win) {
@@ -268,13 +233,8 @@ int launch_ssim(const float* a, const float* b, long n, int channels, int h, int
     case 9: r = ssim_launch_image<9>(a, b, n, channels, h, w, p, vec, g, c1, c2, ssim_rows, mse_rows, rowq, s); break;
     default: r = ssim_launch_image<11>(a, b, n, channels, h, w, p, vec, g, c1, c2, ssim_rows, mse_rows, rowq, s); break;
   }
-  if (r || !mean) return r;
-  const long nblk = (n + SQ_RPB - 1) / SQ_RPB;
-  double* part = rowq + (size_t)n;
-  KtScope kt("ssim_mean_kernels", (double)n, 8.0 * n, s);
-  hipLaunchKernelGGL(ssim_mean_block_kernel, dim3((unsigned)nblk), dim3(64), 0, s, rowq, n, part, nblk == 1 ? mean : nullptr);
-  if (nblk > 1) hipLaunchKernelGGL(ssim_mean_join_kernel, dim3(1), dim3(64), 0, s, part, nblk, n, mean);
-  return 0;
+  if (!r && mean) launch_chain_mean(rowq, n, rowq + (size_t)n, mean, "ssim_mean_kernels", s);      // workspace: q [n], then the block partials
+  return r;
 }
 
 }  // namespace gr

@@ -8,7 +8,8 @@
 // Kernels:
 //   tsne_transpose_kernel  x [n][d] -> xt [d][n] in scratch, so that the distance loop below reads along a row of xt
 //   tsne_cond_kernel       workgroup = row i, 1024 threads, thread t = the columns j = t + 1024 u (u < 16): D_ij in fp64 in registers, the
-//                          bisection on beta with two block sums per step, p_j|i -> p [i][j] (fp32), beta, info (integer atomics)
+//                          bisection on beta with two block sums per step (block_tree_sum, kernels.h: one barrier sequence for both),
+//                          p_j|i -> p [i][j] (fp32), beta, info (integer atomics)
 //   tsne_symm_kernel       workgroup = the 32 x 32 tile (bi, bj), bi <= bj, and its mirror, through LDS: both entries of a pair from one thread
 //   tsne_pass_kernel<KL>   workgroup = 8 consecutive rows of P, 256 threads, thread t = the columns j = t + 256 m of all 8 rows (y_j is loaded
 //                          once for them); fp32 up to w, fp64 after; per row and sum: lane chain, wave tree, the 4 waves in order
@@ -26,7 +27,6 @@ constexpr int TS_MAX_N = TS_CT * TS_CU;
 constexpr int TS_MAX_TRIES = 50;                // updates of beta at most
 constexpr double TS_TOL = 1e-5;                 // |H - log(perplexity)| at which the search stops
 constexpr int TS_R = 8, TS_PT = 256;            // rows of P per workgroup, threads
-constexpr int TS_RPB = 512;                     // rows per block of the column mean (pca.hip's PCA_RPB)
 
 __global__ __launch_bounds__(256) void tsne_transpose_kernel(const float* __restrict__ x, int n, int d, float* __restrict__ xt) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -35,21 +35,9 @@ __global__ __launch_bounds__(256) void tsne_transpose_kernel(const float* __rest
   xt[e] = x[j * d + k];
 }
 
-// the sums of two values per thread in a fixed tree (t += t + o, o = 512 .. 1); every thread gets them
-__device__ __forceinline__ void tsne_block_sum2(double& a, double& b, double* ra, double* rb, int tid) {
-  __syncthreads();
-  ra[tid] = a; rb[tid] = b;
-  __syncthreads();
-  for (int o = TS_CT / 2; o > 0; o >>= 1) {
-    if (tid < o) { ra[tid] += ra[tid + o]; rb[tid] += rb[tid + o]; }
-    __syncthreads();
-  }
-  a = ra[0]; b = rb[0];
-}
-
 __global__ __launch_bounds__(TS_CT) void tsne_cond_kernel(const float* __restrict__ x, const float* __restrict__ xt, int n, int d, double logu,
                                                            float* __restrict__ p, double* __restrict__ beta_out, int* __restrict__ info) {
-  __shared__ double ra[TS_CT], rb[TS_CT];
+  __shared__ double ra[2 * TS_CT];                                       // the two planes of block_tree_sum; the first also carries the minimum
   const int i = blockIdx.x, tid = threadIdx.x;
   const float* xi = x + (size_t)i * d;
   double D[TS_CU];
@@ -85,13 +73,14 @@ __global__ __launch_bounds__(TS_CT) void tsne_cond_kernel(const float* __restric
   bool has_min = false, has_max = false, capped = false;
   int tries = 0;
   for (;;) {
-    double s = 0.0, sd = 0.0;
+    double v[2] = {0.0, 0.0};                                            // (s, sd)
 #pragma unroll
     for (int u = 0; u < TS_CU; ++u) {
       const int j = tid + u * TS_CT;
-      if (j < n && j != i) { const double e = exp(-beta * D[u]); s = s + e; sd = sd + D[u] * e; }
+      if (j < n && j != i) { const double e = exp(-beta * D[u]); v[0] = v[0] + e; v[1] = v[1] + D[u] * e; }
     }
-    tsne_block_sum2(s, sd, ra, rb, tid);
+    block_tree_sum<TS_CT, 2>(v, ra, tid);
+    const double s = v[0], sd = v[1];
     S = s;
     const double diff = (log(s) + beta * sd / s) - logu;
     if (fabs(diff) <= TS_TOL) break;
@@ -212,19 +201,12 @@ template <int KL> __global__ __launch_bounds__(TS_PT) void tsne_pass_kernel(cons
   }
 }
 
-// column `col` of rows [n][stride], every thread gets it: thread t adds the rows t, t + 256, ... in that order from +0.0, then the tree
-// t += t + o, o = 128 .. 1
+// column `col` of rows [n][stride], every thread gets it: thread t adds the rows t, t + 256, ... in that order from +0.0, then block_tree_sum
 __device__ __forceinline__ double tsne_column_sum(const double* __restrict__ rows, int n, int stride, int col, double* red, int tid) {
-  double s = 0.0;
-  for (int i = tid; i < n; i += 256) s = s + rows[(size_t)i * stride + col];
-  __syncthreads();
-  red[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
+  double s[1] = {0.0};
+  for (int i = tid; i < n; i += 256) s[0] = s[0] + rows[(size_t)i * stride + col];
+  block_tree_sum<256, 1>(s, red, tid);
+  return s[0];
 }
 
 // g_ic = (float)(4 (e A_ic - B_ic / Z)), fp64
@@ -253,12 +235,12 @@ __global__ __launch_bounds__(256) void tsne_kl_join_kernel(const double* __restr
 
 __device__ __forceinline__ int tsne_sign(float v) { return v > 0.f ? 1 : v < 0.f ? -1 : 0; }      // +-0 (and NaN): 0
 
-__global__ __launch_bounds__(2 * TS_RPB) void tsne_update_kernel(float* __restrict__ y, const float* __restrict__ grad, float* __restrict__ inc,
+__global__ __launch_bounds__(2 * ROWS_PER_BLOCK) void tsne_update_kernel(float* __restrict__ y, const float* __restrict__ grad, float* __restrict__ inc,
                                                                   float* __restrict__ gains, int n, float eta, float momentum, float min_gain,
                                                                   double* __restrict__ part /*[blocks][2]*/) {
-  __shared__ double ys[2 * TS_RPB];
+  __shared__ double ys[2 * ROWS_PER_BLOCK];
   const int tid = threadIdx.x;
-  const long e = (long)blockIdx.x * 2 * TS_RPB + tid;
+  const long e = (long)blockIdx.x * 2 * ROWS_PER_BLOCK + tid;
   double v = 0.0;
   if (e < 2L * n) {
     const float g = grad[e], u = inc[e];
@@ -276,7 +258,7 @@ __global__ __launch_bounds__(2 * TS_RPB) void tsne_update_kernel(float* __restri
   if (tid < 2) {                                                         // the block's rows in row order (rows past the table add +0.0: no change)
     double s = 0.0;
 #pragma unroll 8
-    for (int r = 0; r < TS_RPB; ++r) s = s + ys[2 * r + tid];
+    for (int r = 0; r < ROWS_PER_BLOCK; ++r) s = s + ys[2 * r + tid];
     part[2 * blockIdx.x + tid] = s;
   }
 }
@@ -353,7 +335,7 @@ __global__ __launch_bounds__(256) void cells_unpack_kernel(const unsigned long l
 
 // ------------------------------------------------------------------ launchers
 size_t tsne_affinities_workspace_bytes(int n, int d) { return sizeof(float) * (size_t)n * d + 256; }
-size_t tsne_iter_workspace_bytes(int n) { return sizeof(double) * ((size_t)n * 5 + 2 * (size_t)((n + TS_RPB - 1) / TS_RPB)) + 512; }
+size_t tsne_iter_workspace_bytes(int n) { return sizeof(double) * ((size_t)n * 5 + 2 * (size_t)row_blocks(n)) + 512; }
 size_t map_cells_workspace_bytes(int cells) { return 8 * (size_t)cells + 256; }
 
 int launch_tsne_affinities(const float* x, int n, int d, double perplexity, float* p, double* beta, int* info, void* workspace, hipStream_t s) {
@@ -392,9 +374,9 @@ int launch_tsne_update(float* y, const float* grad, float* inc, float* gains, in
                        hipStream_t s) {
   if (n < 1 || n > TS_MAX_N) return 1;
   double* part = reinterpret_cast<double*>(workspace) + (size_t)n * 5;      // behind the gradient's row sums: one workspace serves an iteration
-  const int nblk = (n + TS_RPB - 1) / TS_RPB;
+  const int nblk = (int)row_blocks(n);
   KtScope kt("tsne_update_kernel", 0.0, 40.0 * n, s);
-  hipLaunchKernelGGL(tsne_update_kernel, dim3(nblk), dim3(2 * TS_RPB), 0, s, y, grad, inc, gains, n, eta, momentum, min_gain, part);
+  hipLaunchKernelGGL(tsne_update_kernel, dim3(nblk), dim3(2 * ROWS_PER_BLOCK), 0, s, y, grad, inc, gains, n, eta, momentum, min_gain, part);
   hipLaunchKernelGGL(tsne_centre_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, s, y, n, part, nblk);
   return 0;
 }

@@ -19,7 +19,7 @@
 // Kernels:
 //   vae_sample_kernel<VEC>            workgroup = VS_TR rows; thread = one element (VEC: four, 16-byte loads and stores); the element KLs go to LDS, then
 //                                     thread = row adds its row in column order.  The chain is serial by contract: a shuffle tree would change the bits
-//   vae_kl_block_kernel / _join       block partials of K, then their join (one launch when B <= 512)
+//   (chain.hip, launch_chain_mean)    kl[0] from the K_i
 //   vae_sample_backward_kernel<VEC>   thread = one element (VEC: four), grid-stride
 // This is a bandwidth-bound layer: 12 nd B bytes in, 4 nd B out, forward; 16 nd B in, 8 nd B out, backward.
 #include "kernels.h"
@@ -27,7 +27,6 @@
 namespace gr {
 
 constexpr int VS_TR = 8;                // rows per workgroup of the forward kernel
-constexpr int VS_RPB = 512;             // rows per block: the unit of the row-order chain (the library's reduction convention)
 constexpr int VS_MAX = 256;             // nd at most
 
 __device__ __forceinline__ void vs_forward_elem(float mu_f, float lv_f, float ep_f, float& z, double& k) {
@@ -90,35 +89,6 @@ __global__ __launch_bounds__(256) void vae_sample_kernel(const float* __restrict
   }
 }
 
-// part[b] = the K_i of block b in row order from +0.0; with one block (mean non-null) the mean itself: 0.0 + part[0] is part[0], bit for bit
-__global__ __launch_bounds__(64) void vae_kl_block_kernel(const double* __restrict__ rowkl, long B, double* __restrict__ part, double* __restrict__ mean) {
-  __shared__ double v[VS_RPB];
-  const long r0 = (long)blockIdx.x * VS_RPB;
-  const int nr = (int)min((long)VS_RPB, B - r0);
-  for (int e = threadIdx.x; e < nr; e += 64) v[e] = rowkl[r0 + e];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int e = 0; e < nr; ++e) s = s + v[e];
-    if (mean) *mean = s / (double)B;
-    else part[blockIdx.x] = s;
-  }
-}
-
-__global__ void vae_kl_join_kernel(const double* __restrict__ part, long nblk, long B, double* __restrict__ mean) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double s = 0.0;
-  for (long b = 0; b < nblk; b += 8) {                 // eight loads in flight, then the adds in block order
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = b + u < nblk ? part[b + u] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b + u < nblk) s = s + v[u];
-  }
-  *mean = s / (double)B;
-}
-
 __device__ __forceinline__ void vs_backward_elem(float mu_f, float lv_f, float ep_f, float gz_f, double c, float& gmu, float& glv) {
   const double mu = (double)mu_f, lv = (double)lv_f, ep = (double)ep_f, gz = (double)gz_f;
   const double s = exp(0.5 * lv);
@@ -164,31 +134,21 @@ __global__ __launch_bounds__(256) void vae_sample_backward_kernel(const float* _
 }
 
 // ------------------------------------------------------------------ launchers
-static bool vs_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
-
-// doubles: K [B], the block partials [ceil(B / 512)]
-size_t vae_workspace_bytes(long B) { return sizeof(double) * ((size_t)B + (size_t)((B + VS_RPB - 1) / VS_RPB)) + 256; }
-
 int launch_vae_sample(const float* h, const float* eps, long B, int nd, float* z, float* kl_rows, double* kl, void* workspace, hipStream_t s) {
   if (B < 1 || B > 0x7FFFFFFFL || nd < 1 || nd > VS_MAX) return 1;
   double* rowkl = kl ? reinterpret_cast<double*>(workspace) : nullptr;
-  const bool vec = nd % 4 == 0 && vs_aligned16(h) && vs_aligned16(z) && (!eps || vs_aligned16(eps));
+  const bool vec = nd % 4 == 0 && aligned16(h) && aligned16(z) && (!eps || aligned16(eps));
   const unsigned grid = (unsigned)((B + VS_TR - 1) / VS_TR);
   { KtScope kt("vae_sample_kernel", 12.0 * B * nd, 16.0 * B * nd, s);
     if (vec) hipLaunchKernelGGL(vae_sample_kernel<true>, dim3(grid), dim3(256), 0, s, h, eps, B, nd, z, kl_rows, rowkl);
     else hipLaunchKernelGGL(vae_sample_kernel<false>, dim3(grid), dim3(256), 0, s, h, eps, B, nd, z, kl_rows, rowkl); }
-  if (!kl) return 0;
-  const long nblk = (B + VS_RPB - 1) / VS_RPB;
-  double* part = rowkl + (size_t)B;
-  KtScope kt("vae_kl_kernels", (double)B, 8.0 * B, s);
-  hipLaunchKernelGGL(vae_kl_block_kernel, dim3((unsigned)nblk), dim3(64), 0, s, rowkl, B, part, nblk == 1 ? kl : nullptr);
-  if (nblk > 1) hipLaunchKernelGGL(vae_kl_join_kernel, dim3(1), dim3(64), 0, s, part, nblk, B, kl);
+  if (kl) launch_chain_mean(rowkl, B, rowkl + (size_t)B, kl, "vae_kl_kernels", s);      // workspace: K [B], then the block partials
   return 0;
 }
 
 int launch_vae_sample_backward(const float* h, const float* eps, const float* gz, long B, int nd, double c, float* gh, hipStream_t s) {
   if (B < 1 || B > 0x7FFFFFFFL || nd < 1 || nd > VS_MAX) return 1;
-  const bool vec = nd % 4 == 0 && vs_aligned16(h) && vs_aligned16(gz) && vs_aligned16(gh) && (!eps || vs_aligned16(eps));
+  const bool vec = nd % 4 == 0 && aligned16(h) && aligned16(gz) && aligned16(gh) && (!eps || aligned16(eps));
   const long items = B * (vec ? nd >> 2 : nd);
   const long blocks = (items + 255) / 256;
   const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);

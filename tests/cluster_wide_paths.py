@@ -7,7 +7,7 @@ WIDE_MIN_K = 33              # kmeans.hip g_cluster_wide_min_k, gr_set_tuning "c
 NARROW_MAX_K = 32            # kmeans.hip KM_KMAX: the registers of kmeans_assign_kernel
 NARROW_LDS_BYTES = 60 * 1024  # launch_kmeans: k x d doubles of kmeans_accumulate_kernel
 MAX_K, MAX_D, MAX_M = 4096, 256, 128
-ROWS_PER_BLOCK = 512         # kmeans.hip KM_RPB
+ROWS_PER_BLOCK = 512         # kernels.h ROWS_PER_BLOCK
 CENTROID_TILE = 128          # kmeans.hip KW_KT: centroids staged per tile of kmeans_assign_wide_kernel
 CENTROIDS_PER_THREAD = 16    # a half-wave's share of the tile
 ROWS_PER_WORKGROUP = 128     # kmeans.hip KW_TR

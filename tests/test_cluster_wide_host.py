@@ -19,7 +19,8 @@ def test_route_rule_and_constants_match_the_sources():
     km = source("gan-reverser_amd", "csrc", "kmeans.hip")
     assert f"int g_cluster_wide_min_k = {cw.WIDE_MIN_K};" in km
     consts = dict(re.findall(r"\b(K[MW]_[A-Z]+) = (\d+)", km))
-    assert int(consts["KM_KMAX"]) == cw.NARROW_MAX_K and int(consts["KM_RPB"]) == cw.ROWS_PER_BLOCK
+    rpb = re.search(r"constexpr int ROWS_PER_BLOCK = (\d+)", source("gan-reverser_amd", "csrc", "kernels.h")).group(1)      # the one constant of every family
+    assert int(consts["KM_KMAX"]) == cw.NARROW_MAX_K and int(rpb) == cw.ROWS_PER_BLOCK and "KW_SEGMAX = ROWS_PER_BLOCK" in km
     assert int(consts["KW_KT"]) == cw.CENTROID_TILE and int(consts["KW_TR"]) == cw.ROWS_PER_WORKGROUP and int(consts["KW_KMAX"]) == cw.MAX_K
     assert cw.CENTROID_TILE == 8 * cw.CENTROIDS_PER_THREAD
     assert "return k >= g_cluster_wide_min_k || k > KM_KMAX || (size_t)k * d * sizeof(double) > 60 * 1024;" in km

@@ -67,6 +67,14 @@ def test_one_e_step_and_one_m_step(ctx, n, d, k):
     both_steps(ctx, n, d, k)
 
 
+@pytest.mark.parametrize("n", [1, 4096, 4097])
+def test_loglik_at_the_edges_of_its_chain(ctx, n):
+    """one row, eight block partials exactly, a ninth (512 and 513 rows are in ROW_SHAPES): the closing E-step alone against the oracle"""
+    x, w, mu, var, floor = case(n, 1, 1)
+    e = mixture_dev(ctx, x, w, mu, var, 0, floor)
+    check_e_step(dict(rowll=e["rowll"], labels=e["labels"], post=e["post"], loglik=float(e["loglik"][0])), x, w, mu, var, f"({n}, 1, 1)")
+
+
 def test_table_pointer_offset_by_four_bytes(ctx):
     both_steps(ctx, 700, 100, 3, misalign=True)
     x, w, mu, var, floor = case(700, 100, 3)

@@ -53,7 +53,10 @@ def ssim_dev(ctx, a, b, win=11, sigma=1.5, data_range=1.0, misalign=False, want=
 
 
 # ------------------------------------------------------------------ 1. the kernel against the oracle
-@pytest.mark.parametrize("shape", so.SHAPES, ids=str)
+MEAN_EDGES = [(n, 1, 3, 3, 3) for n in (512, 4096, 4097)]      # the mean's chain: one full block, eight partials exactly, a ninth (1 and 513 images are in SHAPES)
+
+
+@pytest.mark.parametrize("shape", so.SHAPES + MEAN_EDGES, ids=str)
 def test_ssim_matches_the_oracle_within_the_derived_bounds(ctx, shape):
     for kind in so.KINDS:
         a, b, _, _ = so.case(kind, shape)

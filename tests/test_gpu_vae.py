@@ -54,7 +54,10 @@ def backward_dev(ctx, h, eps, gz, kl_weight, misalign=False):
 
 
 # ------------------------------------------------------------------ 1. the kernels against the oracle
-@pytest.mark.parametrize("B,nd", SHAPES)
+MEAN_EDGES = [(512, 1), (4096, 1), (4097, 1)]         # kl's chain: one full block, eight partials exactly, a ninth (1 and 513 rows are in SHAPES)
+
+
+@pytest.mark.parametrize("B,nd", SHAPES + MEAN_EDGES)
 def test_sampling_layer_matches_the_oracle_within_the_derived_bounds(ctx, B, nd):
     h, eps, gz = case(B, nd)
     name = f"({B}, {nd})"

@@ -106,6 +106,7 @@ def test_the_header_and_the_bindings_declare_the_new_symbols():
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in L.EXPORTED_SYMBOLS and name + "(" in lua
     assert hasattr(L.Context, "pca_dev") and hasattr(L.Context, "pca_project_dev")
     src = open(os.path.join(ROOT, "gan-reverser_amd", "csrc", "pca.hip")).read()
-    for name, value in (("PCA_RPB", pp.RPB), ("PCA_P", pp.P), ("PCA_SWEEP_CAP", pp.SWEEP_CAP), ("PCA_DMAX", pp.MAX_D)):
-        assert re.search(r"constexpr int " + name + r" = (\d+)", src).group(1) == str(value)      # pca_paths restates the library's constants
+    shared = open(os.path.join(ROOT, "gan-reverser_amd", "csrc", "kernels.h")).read()         # ROWS_PER_BLOCK: the one constant of every family
+    for text, name, value in ((shared, "ROWS_PER_BLOCK", pp.RPB), (src, "PCA_P", pp.P), (src, "PCA_SWEEP_CAP", pp.SWEEP_CAP), (src, "PCA_DMAX", pp.MAX_D)):
+        assert re.search(r"constexpr int " + name + r" = (\d+)", text).group(1) == str(value)     # pca_paths restates the library's constants
     assert "PCA_TAU2 = 0x1p-92" in src and pp.TAU ** 2 == 2.0 ** -92

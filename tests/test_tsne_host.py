@@ -162,8 +162,9 @@ def test_the_header_and_the_bindings_declare_the_new_symbols():
         assert hasattr(L.Context, name[3:])
     assert re.search(r"#define GR_TSNE_MAX_N (\d+)", hdr).group(1) == str(tp.MAX_N) == str(L.Context.TSNE_MAX_N)
     src = open(os.path.join(ROOT, "gan-reverser_amd", "csrc", "tsne.hip")).read()
-    for name, value in (("TS_RPB", tp.RPB), ("TS_MAX_TRIES", to.MAX_TRIES)):
-        assert re.search(r"constexpr int " + name + r" = (\d+)", src).group(1) == str(value)      # the restatements keep the library's constants
+    shared = open(os.path.join(ROOT, "gan-reverser_amd", "csrc", "kernels.h")).read()         # ROWS_PER_BLOCK: the one constant of every family
+    for text, name, value in ((shared, "ROWS_PER_BLOCK", tp.RPB), (src, "TS_MAX_TRIES", to.MAX_TRIES)):
+        assert re.search(r"constexpr int " + name + r" = (\d+)", text).group(1) == str(value)     # the restatements keep the library's constants
     assert "TS_TOL = 1e-5" in src and to.TOL == 1e-5
     fields = [f for f, _ in L.TsneConfig._fields_]
     struct = re.search(r"typedef struct \{([^}]*)\}\s*gr_tsne_config", hdr).group(1)

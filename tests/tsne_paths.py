@@ -8,7 +8,7 @@ import tsne_oracle as to
 
 U, V = 2.0 ** -24, 2.0 ** -53
 TINY = 2.0 ** -149                       # the spacing of float32 below 2^-126: a value stored there is within TINY, not within u of itself
-RPB = 512                                # rows per block of the column mean (TS_RPB)
+RPB = 512                                # rows per block of the column mean (kernels.h ROWS_PER_BLOCK)
 MAX_N = 16384
 
 

@@ -11,7 +11,6 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FP_OFF = {"elem", "search", "kmeans", "pca", "mixture", "tsne", "neighbours", "render", "dataset"}     # Makefile: EXTRA_* = -ffp-contract=off
 
 
 def main():
@@ -27,8 +26,9 @@ def main():
     inc = os.path.normpath(os.path.join(src, "..", "..", "include"))
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + inc,
            "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(src, name), "-o", os.devnull]
-    if stem in FP_OFF:
-        cmd.insert(5, "-ffp-contract=off")
+    extra = re.search(r"^EXTRA_" + re.escape(stem) + r"\s*=\s*(.*)$", open(os.path.join(src, "Makefile")).read(), re.M)     # the per-file flags of that checkout
+    if extra:
+        cmd[5:5] = extra.group(1).split()
     err = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, check=True).stderr
     rows, cur = [], None
     for line in err.splitlines():
