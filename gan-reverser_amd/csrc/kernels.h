@@ -623,6 +623,15 @@ int launch_cluster(const float* x, long n, int d, int k, int niter, float* cent,
 size_t cluster_members_wide_workspace_bytes(long n, int k);
 int launch_cluster_members_wide(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
                                 void* workspace, hipStream_t s);
+// The wide route's index of a labelling, for the callers outside kmeans.hip (silhouette.hip): wide_group_kernel sorts every block of 512 rows by
+// (label, row) - order [blocks x 512], the rows with a label in [0, k) first - and lists the block's segments: seg_label / seg_start [block][segs]
+// (ascending labels, first position in the block's order), nseg / nvalid [block].  wide_index_carve takes wide_index_bytes(n, k) from ws and moves
+// ws past them; 1 <= k <= 4096, 1 <= n < 2^31.
+struct WideIndex { int *seg_label, *seg_start, *nseg, *nvalid, *order; };
+int wide_index_segs(int k);
+size_t wide_index_bytes(long n, int k);
+WideIndex wide_index_carve(char*& ws, long n, int k);
+int wide_group(const int* labels, long n, int k, const WideIndex& ix, hipStream_t s);
 // apply_r.lua:233-243 for every cluster at once: out[j] = launch_rows_mean of rows[j][0 .. kept[j]); entries outside [0, n_rows) are skipped
 void launch_cluster_faces(const float* x, long n_rows, long d, const long* rows, const int* kept, int k, int m, float* out, hipStream_t s);
 
@@ -643,6 +652,14 @@ int launch_pca_project(const float* x, long n, int d, const double* mean, const 
 size_t mixture_workspace_bytes(long n, int d, int k);
 int launch_mixture(const float* x, long n, int d, int k, int niter, float var_floor, float* w, float* mu, float* vars, double* loglik, int* labels,
                    float* post, float* rowll, void* workspace, hipStream_t s);
+
+// ---------------------------------------------------------------- silhouette coefficients of a labelled device table (silhouette.hip; gr_silhouette_dev)
+// x [n x d] floats, labels [n]; s [n], a / b / nearest [n] nullable, cluster_mean [k], sizes [k], mean 1 double: all device; workspace from
+// silhouette_workspace_bytes.  metric 0 euclidean, 1 cosine.  Returns 1 outside 2 <= n <= SIL_MAX_N, 1 <= d <= 256, 1 <= k <= 4096, metric 0 / 1.
+constexpr long SIL_MAX_N = 262144;
+size_t silhouette_workspace_bytes(long n, int k);
+int launch_silhouette(const float* x, long n, int d, const int* labels, int k, int metric, double* s_out, double* a_out, double* b_out, int* nearest,
+                      double* cluster_mean, int* sizes, double* mean, void* workspace, hipStream_t s);
 
 // ---------------------------------------------------------------- the sampling layer of a VAE (vae.hip; gr_vae_sample_dev, gr_vae_sample_backward_dev)
 // h [B x 2 nd] = (mu | logvar), eps (nullable: 0) / z / gz [B x nd], gh [B x 2 nd], kl_rows [B] floats and kl 1 double nullable: all device; workspace

@@ -732,9 +732,9 @@ size_t cluster_workspace_bytes(long n, int d, int k) {
 // The wide route's member lists, shared by launch_cluster and gr_cluster_members_wide_dev (a mixture's labels and posteriors): the labels are grouped
 // block by block (wide_group_kernel), then every cluster walks its segments (cluster_members_wide_kernel).  The index: three ints per segment slot,
 // two per block, one per row of the padded table.
-struct WideIndex { int *seg_label, *seg_start, *nseg, *nvalid, *order; };
 static size_t wide_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
-static WideIndex wide_index_carve(char*& ws, long n, int k) {
+int wide_index_segs(int k) { return wide_segs(k); }
+WideIndex wide_index_carve(char*& ws, long n, int k) {
   const size_t nblk = (size_t)row_blocks(n), slots = nblk * wide_segs(k);
   auto take = [&](size_t bytes) { char* p = ws; ws += wide_align(bytes); return reinterpret_cast<int*>(p); };
   WideIndex ix;
@@ -745,7 +745,7 @@ static WideIndex wide_index_carve(char*& ws, long n, int k) {
   ix.order = take(sizeof(int) * nblk * ROWS_PER_BLOCK);
   return ix;
 }
-static int wide_group(const int* labels, long n, int k, const WideIndex& ix, hipStream_t s) {
+int wide_group(const int* labels, long n, int k, const WideIndex& ix, hipStream_t s) {
   KtScope kt("wide_group_kernel", 0.0, 8.0 * n, s);
   hipLaunchKernelGGL(wide_group_kernel, dim3((unsigned)row_blocks(n)), dim3(256), 0, s, labels, n, k, wide_segs(k), ix.order, ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid);
   return 0;
@@ -757,10 +757,11 @@ static void wide_members(const int* labels, const float* sims, long n, int k, in
   hipLaunchKernelGGL(cluster_members_wide_kernel, dim3(k), dim3(256), 0, s, ix.order, wide_segs(k), ix.seg_label, ix.seg_start, ix.nseg, ix.nvalid,
                      row_blocks(n), sims, m, rows_out, sims_out, kept_out, sizes_out);
 }
-size_t cluster_members_wide_workspace_bytes(long n, int k) {
+size_t wide_index_bytes(long n, int k) {
   const size_t nblk = (size_t)row_blocks(n), slots = nblk * wide_segs(k);
   return sizeof(int) * (2 * slots + 2 * nblk + nblk * ROWS_PER_BLOCK) + 8 * 256;
 }
+size_t cluster_members_wide_workspace_bytes(long n, int k) { return wide_index_bytes(n, k); }
 // launch_cluster_members' lists for any k <= 4096 by the wide route's kernels.  Returns 1 outside 1 <= k <= 4096, 1 <= m <= 128, 1 <= n < 2^31.
 int launch_cluster_members_wide(const int* labels, const float* sims, long n, int k, int m, long* rows_out, float* sims_out, int* kept_out, int* sizes_out,
                                 void* workspace, hipStream_t s) {

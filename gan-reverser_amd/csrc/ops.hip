@@ -580,6 +580,21 @@ extern "C" int gr_mixture_dev(gr_ctx* c, const float* x, int64_t n, int d, int k
     return launch_mixture(x, n, d, k, niter, var_floor, weights, means, vars, loglik, labels, post, rowll, ws, c->stream);
   }, {GR_ERR_UNSUPPORTED, "gr_mixture_dev: unsupported size", 0}, {GR_ERR_HIP, "gr_mixture_dev: the device refuses the kernels' LDS (d %d)", d});
 }
+// ------------------------------------------------------------------ silhouette coefficients of a labelled device table (silhouette.hip)
+extern "C" int gr_silhouette_dev(gr_ctx* c, const float* x, int64_t n, int d, const int32_t* labels, int k, int metric, double* sv, double* a, double* b,
+                                 int32_t* nearest, double* cluster_mean, int32_t* sizes, double* mean) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !labels || !sv || !cluster_mean || !sizes || !mean) return fail(c, GR_ERR_INVALID, "gr_silhouette_dev: null pointer");
+  if (n <= 0 || d <= 0 || k <= 0) return fail(c, GR_ERR_INVALID, "gr_silhouette_dev: n %lld, d %d and k %d must be positive", (long long)n, d, k);
+  if (metric != 0 && metric != 1) return fail(c, GR_ERR_INVALID, "gr_silhouette_dev: metric %d: 0 (euclidean) or 1 (cosine)", metric);
+  if (n < 2 || n > GR_SILHOUETTE_MAX_N)
+    return fail(c, GR_ERR_UNSUPPORTED, "gr_silhouette_dev: n %lld: between 2 and %d rows", (long long)n, GR_SILHOUETTE_MAX_N);
+  if (d > 256) return fail(c, GR_ERR_UNSUPPORTED, "gr_silhouette_dev: d %d: at most 256 columns", d);
+  if (k > 4096) return fail(c, GR_ERR_UNSUPPORTED, "gr_silhouette_dev: k %d: at most 4096 clusters", k);
+  return scratch_launch(c, silhouette_workspace_bytes(n, k), [&](void* ws) {
+    return launch_silhouette(x, n, d, labels, k, metric, sv, a, b, nearest, cluster_mean, sizes, mean, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_silhouette_dev: unsupported size", 0});
+}
 
 // ------------------------------------------------------------------ the sampling layer of a VAE (vae.hip)
 static int vae_check(gr_ctx* c, const char* who, bool null_ptr, int64_t B, int nd) {

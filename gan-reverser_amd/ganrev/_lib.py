@@ -204,6 +204,7 @@ _SIGS = {
     "gr_cluster_members_wide_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gr_pca_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
     "gr_mixture_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "gr_silhouette_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "gr_vae_sample_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gr_vae_sample_backward_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
@@ -659,6 +660,20 @@ class Context:
         int32 / post_dev / rowll_dev [n] floats (each may be None).  niter = 0 scores rows under the given parameters.  Enqueued; no host wait."""
         self.check(self.lib.gr_mixture_dev(self.h, _ptr(x_dev), int(n), int(d), int(k), int(niter), float(var_floor), _ptr(weights_dev), _ptr(means_dev),
                                            _ptr(vars_dev), _ptr(loglik_dev), _ptr(labels_dev), _ptr(post_dev), _ptr(rowll_dev)), "gr_mixture_dev")
+
+    SILHOUETTE_MAX_N, SILHOUETTE_MAX_D, SILHOUETTE_MAX_K = 262144, 256, 4096     # gr_silhouette_dev's limits (include/ganrev.h GR_SILHOUETTE_MAX_N)
+    SILHOUETTE_METRICS = {"euclidean": 0, "cosine": 1}
+
+    def silhouette_dev(self, x_dev, n, d, labels_dev, k, metric, s_dev, cluster_mean_dev, sizes_dev, mean_dev, a_dev=None, b_dev=None, nearest_dev=None):
+        """gr_silhouette_dev (2 <= n <= 262144, d <= 256, k <= 4096): the silhouette coefficients of the device table [n x d] under labels_dev [n]
+        int32 (a label outside [0, k): no cluster); metric "euclidean" / "cosine" (or 0 / 1) -> s_dev [n] doubles, cluster_mean_dev [k] doubles,
+        sizes_dev [k] int32, mean_dev 1 double; a_dev / b_dev [n] doubles and nearest_dev [n] int32 may be None.  Enqueued; no host wait."""
+        if isinstance(metric, str):
+            if metric not in self.SILHOUETTE_METRICS:
+                raise GanrevError(f"silhouette: metric {metric!r}: one of {sorted(self.SILHOUETTE_METRICS)}")
+            metric = self.SILHOUETTE_METRICS[metric]
+        self.check(self.lib.gr_silhouette_dev(self.h, _ptr(x_dev), int(n), int(d), _ptr(labels_dev), int(k), int(metric), _ptr(s_dev), _ptr(a_dev),
+                                              _ptr(b_dev), _ptr(nearest_dev), _ptr(cluster_mean_dev), _ptr(sizes_dev), _ptr(mean_dev)), "gr_silhouette_dev")
 
     VAE_MAX_ND = 256                 # gr_vae_sample_*: latent dimensions at most (include/ganrev.h GR_VAE_MAX_ND)
 

@@ -17,13 +17,13 @@
   analyseDev, renderAnalysis   apply_r.lua:158-191   ... clusters, fixed faces and anomalies (--resident), with the pictures (--render)
   lowestShare, anomalyMetric   apply_r.lua:368-372   the anomaly rule on any per-image score
   principalAxesOfTable, mapOfTable, mixtureOfTable   --pca, --map, --mixture: ganrev.pca, ganrev.tsne, ganrev.mixture over the attribute table
-  clusterOptions, pcaOptions, mapOptions, mixtureOptions   what a run's options say about each, with the defaults
+  silhouetteStep, silhouetteSweep                    --silhouette, --silhouetteSweep: ganrev.silhouette over the labellings of that table
+  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions   what a run's options say about each, with the defaults
 
 These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
 frames and fields apply_r.lua draws) come from ganrev.render, on the GPU, and main() writes them with --render.
 """
 import contextlib
-import functools
 import json
 import math
 import os
@@ -202,10 +202,11 @@ def checkClusterCount(nbClusters):
     return int(nbClusters)
 
 
-def clusterTableDev(ctx, table_ptr, N, d, k, nbIterations, m, centroids0, closest, faces_of=None):
+def clusterTableDev(ctx, table_ptr, N, d, k, nbIterations, m, centroids0, closest, faces_of=None, labels_into=None):
     """apply_r.lua:198-227 on a device table [N x d].  Up to 32 clusters: gr_kmeans_dev, gr_cosine_assign_dev, gr_cluster_members_dev, as ever;
     above: gr_cluster_dev, one enqueue.  faces_of = (images pointer, rows of that table, values per image, output pointer) adds gr_cluster_faces_dev
-    (apply_r.lua:233-243) while the lists are still on the device.  -> (centroids, counts, clusters)"""
+    (apply_r.lua:233-243) while the lists are still on the device.  labels_into: a list that receives the [N] int32 labels of the cosine
+    assignment (:205-217), which no list keeps beyond the m best rows of a cluster.  -> (centroids, counts, clusters)"""
     sizes = [4 * k, 4 * N, 4 * N, 8 * k * m, 4 * k * m, 4 * k, 4 * k]               # counts, labels, sims, rows, their sims, kept, cluster sizes
     with DeviceScope(ctx) as bufs:
         cent = bufs.upload(np.ascontiguousarray(centroids0, np.float32).reshape(k, d))
@@ -221,6 +222,8 @@ def clusterTableDev(ctx, table_ptr, N, d, k, nbIterations, m, centroids0, closes
             ctx.cluster_faces_dev(images_ptr, n_rows, chw, rows, kept, k, m, faces_ptr)         # :233-243 (zeros for an empty cluster)
         centroids, counts = ctx.download(cent, (k, d)), ctx.download(tot, (k,))
         hrows, hsim, hkept = ctx.download(rows, (k, m), np.int64), ctx.download(rsim, (k, m)), ctx.download(kept, (k,), np.int32)
+        if labels_into is not None:
+            labels_into.append(ctx.download(lab, (N,), np.int32))
     clusters = [[(int(r), float(v)) for r, v in zip(hrows[j, :hkept[j]], hsim[j, :hkept[j]])] for j in range(k)]
     return centroids, counts, clusters
 
@@ -323,8 +326,8 @@ def analyseDev(OPT, MODEL_G, images, attributes, attributesFixer, out=None, colo
     pictures are written as PNG files on the way (ganrev.render): cluster_%02d, similar_attributes_%02d / similar_pixelwise_%02d,
     fixed_pairs, fixed_images_<n>[_unfixed] and anomalies; nothing but the finished pictures and the per-image distances leaves the GPU.
     -> what the run's arrays and summary are written from: dict(clusters = createClusterImagesDev's tuple with the faces on the host,
-    fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple).  mixture: --mixture's step, called with the final
-    centroids while the tables are still where they are.  --anomalyMetric ssim: the same rows are also scored with quality.ssim(images, fixed
+    fixed = the fixed images [nbFixed x C x H x W], anomalies = detectAnomalies' tuple).  mixture: the steps that follow the clustering in its
+    table (--mixture, --silhouette), called with the final centroids while the tables are still where they are.  --anomalyMetric ssim: the same rows are also scored with quality.ssim(images, fixed
     images) where they lie, the lowest 15 % of THAT score are the anomalies (anomalies = (ssim, below, flags)), and the distances come back
     beside them as `distances`."""
     ctx, N = images.ctx, images.shape[0]
@@ -401,6 +404,26 @@ def mixtureOfTable(ctx, table, centroids, iterations, column_variances=None, nee
         return fitted, rows, needles
 
 
+SILHOUETTE_MAX_ROWS = L.Context.SILHOUETTE_MAX_N     # gr_silhouette_dev's limit (GR_SILHOUETTE_MAX_N)
+SILHOUETTE_METRICS = ("euclidean", "cosine")
+
+
+def silhouetteOptions(OPT):
+    """(rows, [the K of --silhouetteSweep]) of a run with --silhouette or --silhouetteSweep: the first `rows` rows are scored, the option given,
+    else min(nbImages, 100000); None without either"""
+    if not (getattr(OPT, "silhouette", False) or hasattr(OPT, "silhouetteSweep")):
+        return None
+    sweep = [int(v) for v in OPT.silhouetteSweep.split(",")] if hasattr(OPT, "silhouetteSweep") else []
+    return int(getattr(OPT, "silhouetteRows", min(OPT.nbImages, 100000))), sweep
+
+
+def silhouetteOfLabels(ctx, table, rows, labels, k):
+    """ganrev.silhouette of the first `rows` rows of a device table (pointer, N, d) under labels [N] (later rows are nobody's member), in both
+    metrics -> {metric: Silhouette}"""
+    from . import silhouette as SIL
+    return {metric: SIL.score(ctx, table, labels[:rows], k, metric, rows=rows) for metric in SILHOUETTE_METRICS}
+
+
 MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
 
 
@@ -457,6 +480,10 @@ def parse(argv=None):
     p.add_argument("--mapPerplexity", type=float, default=argparse.SUPPRESS, help="with --map: the perplexity (default 30; at most (mapRows - 1) / 3)")
     p.add_argument("--mapIterations", type=int, default=argparse.SUPPRESS, help="with --map: gradient iterations (default 1000)")
     p.add_argument("--mapGrid", type=int, default=argparse.SUPPRESS, metavar="G", help="with --map: map_cells and map.png have G x G cells (default 32)")
+    # the silhouette options: absent from the namespace unless given - silhouetteOptions() supplies the defaults
+    p.add_argument("--silhouette", action="store_true", default=argparse.SUPPRESS, help="silhouette coefficients of the clustering, on the device (ganrev.silhouette), in the table the clustering read: the cosine-assignment labels, and with --mixture the mixture's, each under the euclidean and the cosine distance; writes silhouette_{clusters,mixture}_{euclidean,cosine}.npy, silhouette_clusters_labels.npy and the means per labelling, metric and cluster into summary.json")
+    p.add_argument("--silhouetteRows", type=int, default=argparse.SUPPRESS, metavar="M", help=f"with --silhouette / --silhouetteSweep: the first M rows are scored, later rows are nobody's member (default min(nbImages, 100000); at most {SILHOUETTE_MAX_ROWS}: every pair of rows is visited, the rows are independent draws, a prefix is a fair sample)")
+    p.add_argument("--silhouetteSweep", default=argparse.SUPPRESS, metavar="K1,K2,...", help="which --nbClusters: the clustering is run again for each K (same seed, --nbIterations and --closest; no faces, no pictures) and scored; writes silhouette_sweep.json: K, the mean silhouette under both distances, the number of empty clusters")
     p.add_argument("--mixture", type=int, default=argparse.SUPPRESS, metavar="ITER", help="a diagonal Gaussian mixture of the recovered noise, on the device (ganrev.mixture): ITER EM iterations from the clustering's final centroids, --nbClusters components (at most 256), in the table the clustering read; writes mixture_weights, mixture_means, mixture_variances, mixture_loglik [ITER + 1], mixture_labels, mixture_posterior, mixture_row_loglik (.npy), with --render mixture_%%02d.png and mixture_outliers.png, with --needles needle_mixture.npy")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
@@ -519,6 +546,22 @@ def parse(argv=None):
             p.error("--mixture: an iteration count")
         if nbClusters > MAX_COMPONENTS:
             p.error(f"--mixture: --nbClusters {nbClusters}: at most {MAX_COMPONENTS} components")
+    if hasattr(OPT, "silhouetteSweep"):
+        for v in OPT.silhouetteSweep.split(","):
+            if not v.strip().isdigit():
+                p.error(f"--silhouetteSweep {OPT.silhouetteSweep}: cluster counts separated by commas")
+            if not 1 <= int(v) <= MAX_CLUSTERS:
+                p.error(f"--silhouetteSweep: {int(v)}: 1 to {MAX_CLUSTERS} clusters")
+    scored = silhouetteOptions(OPT)
+    if hasattr(OPT, "silhouetteRows") and scored is None:
+        p.error("--silhouetteRows belongs to the silhouette: give --silhouette or --silhouetteSweep")
+    if scored is not None:
+        if OPT.host:
+            p.error("--silhouette and --silhouetteSweep run on the device-resident tables: not with --host")
+        if scored[0] > SILHOUETTE_MAX_ROWS:
+            p.error(f"--silhouetteRows {scored[0]}: at most {SILHOUETTE_MAX_ROWS} rows (every pair of rows is visited)")
+        if not 2 <= scored[0] <= OPT.nbImages:
+            p.error(f"--silhouetteRows {scored[0]}: 2 to nbImages = {OPT.nbImages} rows")
     if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
         p.error("--needles and --real read their images from --dataset")
     if (OPT.needles or OPT.real) and OPT.host:
@@ -556,6 +599,7 @@ class Run:
         self.spaceName = "pca_whitened" if pcaOptions(OPT)[1] else "attributes"
         self.by_attr = self.by_pix = self.map_cells = self.rendered = None
         self.pca = self.needle_rows = None                                    # what the steps before the mixture leave for it
+        self.mixture_labels = None                                            # ... and the mixture for the silhouette
 
     def out(self, name):
         return os.path.join(self.OPT.writeTo, name)
@@ -780,6 +824,7 @@ def mixtureStep(S, table, centroids, images=None):
     S.say("Fitting a Gaussian mixture to the recovered noise...")
     reuse = S.pca[3] if S.pca is not None and not pcaOptions(OPT)[1] else None    # (the whitened projection is another table: its variances are its own)
     fitted, (labels, post, rowll), needles = mixtureOfTable(S.ctx, table, centroids, mixIter, reuse, S.needle_rows)
+    S.mixture_labels = labels
     for name, a in (("weights", fitted.weights), ("means", fitted.means), ("variances", fitted.variances), ("loglik", fitted.loglik),
                     ("labels", labels), ("posterior", post), ("row_loglik", rowll)):
         np.save(out("mixture_%s.npy" % name), a)
@@ -796,6 +841,56 @@ def mixtureStep(S, table, centroids, images=None):
         shown = min(512 + 16, OPT.nbImages, 1024)                             # as many rows as anomalies.png shows
         worst = np.argsort(rowll, kind="stable")[:shown]                      # lowest row log-likelihood first
         render.grid(images, worst, int(math.floor(math.sqrt(shown))), S.colorSpace, path=out("mixture_outliers.png"))
+
+
+def silhouetteStep(S, table, centroids, images=None):
+    """--silhouette and --silhouetteSweep, after the clustering (and the mixture), in the table they read.  The clustering's labels are the cosine
+    assignment to its final centroids (apply_r.lua:205-217): clusterTableDev from those centroids with no k-means iteration hands them back."""
+    OPT, ctx, out = S.OPT, S.ctx, S.out
+    rows, sweep = silhouetteOptions(OPT)
+    k, nbIterations, m, closest = clusterOptions(OPT)
+    with deviceTable(ctx, table) as (ptr, N, d):
+        if getattr(OPT, "silhouette", False):
+            S.say("Scoring the clusterings (silhouette)...")
+            got = []
+            clusterTableDev(ctx, ptr, N, d, k, 0, m, centroids, closest, labels_into=got)
+            np.save(out("silhouette_clusters_labels.npy"), got[0])
+            entry = dict(rows=rows, space=S.spaceName)
+            for name, labels in (("clusters", got[0]), ("mixture", S.mixture_labels)):
+                if labels is None:
+                    continue
+                entry[name] = {}
+                for metric, sc in silhouetteOfLabels(ctx, (ptr, N, d), rows, labels, k).items():
+                    np.save(out("silhouette_%s_%s.npy" % (name, metric)), sc.values)
+                    entry[name][metric] = sc.summary()
+                    S.say("<apply_r> silhouette of the %s, %s distance, %d rows in %s: mean %.4f" % (name, metric, rows, S.spaceName, sc.mean))
+            S.summary["silhouette"] = entry
+        if sweep:
+            S.say("Sweeping the number of clusters (silhouette)...")
+            found = []
+            for K in sweep:
+                got = []
+                clusterTableDev(ctx, ptr, N, d, K, nbIterations, m, initialCentroids(K, d, OPT.seed), closest, labels_into=got)
+                scores = silhouetteOfLabels(ctx, (ptr, N, d), rows, got[0], K)
+                found.append(dict(K=K, mean_euclidean=scores["euclidean"].mean, mean_cosine=scores["cosine"].mean,
+                                  empty_clusters=int((scores["cosine"].sizes == 0).sum())))
+                S.say("<apply_r> silhouette sweep: K %d: mean %.4f (euclidean), %.4f (cosine), %d empty clusters"
+                      % (K, found[-1]["mean_euclidean"], found[-1]["mean_cosine"], found[-1]["empty_clusters"]))
+            json.dump(dict(rows=rows, space=S.spaceName, nbIterations=nbIterations, closest=closest, seed=OPT.seed, sweep=found),
+                      open(out("silhouette_sweep.json"), "w"), indent=1)
+
+
+def afterClustering(S):
+    """the steps that follow the clustering in its table - the mixture, then the silhouette, which scores the mixture's labels too - as one call
+    (table, centroids, images=None); None when the run asks for neither"""
+    steps = [mixtureStep] * (mixtureOptions(S.OPT) is not None) + [silhouetteStep] * (silhouetteOptions(S.OPT) is not None)
+    if not steps:
+        return None
+
+    def run_steps(table, centroids, images=None):
+        for step in steps:
+            step(S, table, centroids, images)
+    return run_steps
 
 
 # apply_r.lua:25-193 main(): the whole analysis as one run.  What the reference computes is written as arrays (.npy) and one
@@ -815,8 +910,8 @@ def run(OPT):
     S.MODEL_R_FIXER.manualSeed(OPT.seed)
     os.makedirs(OPT.writeTo, exist_ok=True)
     out, say, summary, N = S.out, S.say, S.summary, OPT.nbImages
-    mixIter = mixtureOptions(OPT)
-    mixture = {} if mixIter is None else dict(mixture=functools.partial(mixtureStep, S))    # analyseDev calls it while the tables are where they are
+    after = afterClustering(S)
+    mixture = {} if after is None else dict(mixture=after)                    # analyseDev calls it while the tables are where they are
     with S.tables:
         variationsStep(S)                                                     # :110-138
         t0 = time.perf_counter()
@@ -852,8 +947,8 @@ def run(OPT):
     np.save(out("cluster_centroids.npy"), centroids); np.save(out("cluster_average_faces.npy"), np.stack(faces))
     summary["cluster_sizes"] = [len(c) for c in clusters]; summary["cluster_total_counts"] = [float(v) for v in counts]
     summary.update(zip(("nbClusters", "nbIterations", "nbMaxPerCluster", "closest"), clusterOptions(OPT)))
-    if mixIter is not None and not rendered:                                  # neither --resident nor --render: the host copy of the table is uploaded
-        mixtureStep(S, S.space_host, centroids)
+    if after is not None and not rendered:                                    # neither --resident nor --render: the host copy of the table is uploaded
+        after(S.space_host, centroids)
 
     say("Fixing faces...")                                                    # :178-181
     nbFixed = min(512 + 16, N)

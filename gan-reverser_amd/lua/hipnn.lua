@@ -91,6 +91,8 @@ int gr_pca_project_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const doub
                        int k, int whiten, float* out_dev);
 int gr_mixture_dev(gr_ctx*, const float* x_dev, int64_t n, int d, int k, int niter, float var_floor, float* weights_dev, float* means_dev, float* vars_dev,
                    double* loglik_dev, int32_t* labels_dev, float* post_dev, float* rowll_dev);     /* diagonal Gaussian mixture by EM, d, k <= 256 */
+int gr_silhouette_dev(gr_ctx*, const float* x_dev, int64_t n, int d, const int32_t* labels_dev, int k, int metric, double* s_dev, double* a_dev, double* b_dev,
+                      int32_t* nearest_dev, double* cluster_mean_dev, int32_t* sizes_dev, double* mean_dev);     /* silhouette coefficients, 0 euclidean / 1 cosine, n <= 262144 */
 int gr_vae_sample_dev(gr_ctx*, const float* h_dev, const float* eps_dev, int64_t B, int nd, float* z_dev, float* kl_rows_dev, double* kl_dev);     /* a VAE's sampling layer, nd <= 256 */
 int gr_vae_sample_backward_dev(gr_ctx*, const float* h_dev, const float* eps_dev, const float* gz_dev, int64_t B, int nd, double kl_weight, float* gh_dev);
 int gr_vae_sample_host(gr_ctx*, const float* h, const float* eps, int64_t B, int nd, float* z, float* kl_rows, double* kl);

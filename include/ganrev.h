@@ -551,6 +551,34 @@ int gr_mixture_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int
                    float* means_dev /*[k x d] in/out*/, float* vars_dev /*[k x d] in/out*/, double* loglik_dev /*[niter + 1]*/,
                    int32_t* labels_dev /*[n] nullable*/, float* post_dev /*[n] nullable*/, float* rowll_dev /*[n] nullable*/);
 
+/* ---- silhouette coefficients of a labelled device table (csrc/silhouette.hip; new: the reference has no counterpart) ----
+ * gr_silhouette_dev: x_dev [n x d] floats, labels_dev [n] int32; s_dev [n], a_dev, b_dev [n] doubles and nearest_dev [n] int32 (the last three nullable),
+ * cluster_mean_dev [k] doubles, sizes_dev [k] int32, mean_dev 1 double.  metric 0: euclidean distance, 1: cosine distance.  Every pointer is device
+ * memory; the work is enqueued on the ctx stream and the call returns without waiting for it; scratch comes from the context.
+ * Everything past the loads is fp64, every operation rounded on its own (no fused multiply-add); sqrt is the device library's (correctly rounded).
+ * Pair distance, euclidean.  t = x_it - x_jt, D = D + t t in column order from +0.0, dist = sqrt(D) - never |x_i|^2 + |x_j|^2 - 2 x_i . x_j, which
+ * loses near-duplicate rows and can go negative under the root.
+ * Pair distance, cosine.  p = p + x_it x_jt in column order from +0.0; q_i = sqrt(Q_i), Q_i = Q_i + x_it x_it by the same chain, once per row;
+ * c = p / (q_i q_j), and 0 where either norm is 0; dist = 1 - c, and 0 where that is not above 0.
+ * Per (row i, cluster c): the dist of the members j of c, without i itself, added in ascending row order in one chain from +0.0.  A label outside
+ * [0, k) belongs to no cluster, as in gr_cluster_members_dev: such a row is nobody's member and its own outputs are s = a = b = 0, nearest = -1.
+ * Per row: a = sum_own / (size_own - 1), and 0 for size_own = 1.  b = the smallest sum_c / size_c over the non-empty clusters c != own, nearest = that
+ * c, the first minimum over ascending c; without another member b = 0 and nearest = -1.  s = (b - a) / max(a, b); s = 0 where size_own = 1, where
+ * max(a, b) = 0, or where no other cluster has a member.
+ * Summaries: sizes[c] = the members of c.  cluster_mean[c] = the members' s added in ascending row order from +0.0, divided by sizes[c]; 0 for an
+ * empty cluster.  mean: per block of 512 consecutive rows the s_i in row order from +0.0, the block partials in block order from +0.0, one division
+ * by n (rows without a cluster count as 0).
+ * No floating-point atomics, nothing depends on the CU count or on the order in which workgroups finish: two runs give the same bits.
+ * Limits: 2 <= n <= GR_SILHOUETTE_MAX_N (the pair work is n^2 d), 1 <= d <= 256, 1 <= k <= 4096; outside them GR_ERR_UNSUPPORTED with a gr_last_error
+ * text that names the value; null required pointers, non-positive n, d, k or an unknown metric: GR_ERR_INVALID.  The context stays usable after
+ * either.  Non-finite elements are outside the contract.
+ * Scratch, with B = ceil(n / 512) blocks and S = B x min(k, 512) segment slots: 2 S + 2 B + 512 B + k B + k + 1 + n ints (the grouped index) and
+ * n + B doubles (the norms and the mean's partials): at most 13 MB + 12 n bytes, whatever the device. */
+#define GR_SILHOUETTE_MAX_N 262144
+int gr_silhouette_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, const int32_t* labels_dev, int k, int metric /*0 euclidean, 1 cosine*/,
+                      double* s_dev /*[n]*/, double* a_dev /*[n] nullable*/, double* b_dev /*[n] nullable*/, int32_t* nearest_dev /*[n] nullable*/,
+                      double* cluster_mean_dev /*[k]*/, int32_t* sizes_dev /*[k]*/, double* mean_dev /*[1]*/);
+
 /* ---- the sampling layer of a variational autoencoder (csrc/vae.hip; new: the reference has no counterpart) ----
  * The layer between an encoder whose head emits a mean and a log-variance and a decoder: the reparameterisation z = mu + exp(logvar / 2) eps, its KL
  * term against the unit Gaussian, and the backward of both.  h [B x 2 nd] floats: columns 0 .. nd - 1 of a row hold mu, columns nd .. 2 nd - 1 hold
