@@ -661,6 +661,18 @@ size_t silhouette_workspace_bytes(long n, int k);
 int launch_silhouette(const float* x, long n, int d, const int* labels, int k, int metric, double* s_out, double* a_out, double* b_out, int* nearest,
                       double* cluster_mean, int* sizes, double* mean, void* workspace, hipStream_t s);
 
+// ---------------------------------------------------------------- the k-nearest-neighbour graph of a device table (knn.hip; gr_knn_dev, gr_lof_dev, gr_knn_overlap_dev)
+// x [n x d] floats; idx [n x k] ints, dist [n x k] doubles: row i's k nearest rows j != i by (dist, j) ascending, silhouette.hip's pair distances; lrd
+// (nullable) / lof [n] doubles; count [n] ints, mean 1 double: all device; workspaces from the *_workspace_bytes beside each.  metric 0 euclidean, 1
+// cosine.  All return 1 outside 2 <= n <= KNN_MAX_N, 1 <= k <= min(n - 1, 128), and launch_knn outside 1 <= d <= 256, metric 0 / 1 too.
+constexpr long KNN_MAX_N = SIL_MAX_N;
+size_t knn_workspace_bytes(long n);
+int launch_knn(const float* x, long n, int d, int k, int metric, int* idx_out, double* dist_out, void* workspace, hipStream_t s);
+size_t lof_workspace_bytes(long n);
+int launch_lof(const int* idx, const double* dist, long n, int k, double* lrd, double* lof, void* workspace, hipStream_t s);
+size_t knn_overlap_workspace_bytes(long n);
+int launch_knn_overlap(const int* a, const int* b, long n, int k, int* count, double* mean, void* workspace, hipStream_t s);
+
 // ---------------------------------------------------------------- the sampling layer of a VAE (vae.hip; gr_vae_sample_dev, gr_vae_sample_backward_dev)
 // h [B x 2 nd] = (mu | logvar), eps (nullable: 0) / z / gz [B x nd], gh [B x 2 nd], kl_rows [B] floats and kl 1 double nullable: all device; workspace
 // of chain_mean_workspace_bytes(B), read only when kl is given; c = kl_weight / B.  Both return 1 outside 1 <= B < 2^31, 1 <= nd <= 256.

@@ -596,6 +596,39 @@ extern "C" int gr_silhouette_dev(gr_ctx* c, const float* x, int64_t n, int d, co
   }, {GR_ERR_UNSUPPORTED, "gr_silhouette_dev: unsupported size", 0});
 }
 
+// ------------------------------------------------------------------ the k-nearest-neighbour graph of a device table (knn.hip)
+static int knn_graph_check(gr_ctx* c, const char* who, int64_t n, int k) {
+  if (n <= 0 || k <= 0) return fail(c, GR_ERR_INVALID, "%s: n %lld and k %d must be positive", who, (long long)n, k);
+  if (n < 2 || n > GR_KNN_MAX_N) return fail(c, GR_ERR_UNSUPPORTED, "%s: n %lld: between 2 and %d rows", who, (long long)n, GR_KNN_MAX_N);
+  if (k > GR_KNN_MAX_K) return fail(c, GR_ERR_UNSUPPORTED, "%s: k %d: at most %d neighbours", who, k, GR_KNN_MAX_K);
+  if (k > n - 1) return fail(c, GR_ERR_UNSUPPORTED, "%s: k %d: at most n - 1 = %lld neighbours (a row is not its own)", who, k, (long long)(n - 1));
+  return GR_OK;
+}
+extern "C" int gr_knn_dev(gr_ctx* c, const float* x, int64_t n, int d, int k, int metric, int32_t* idx, double* dist) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !idx || !dist) return fail(c, GR_ERR_INVALID, "gr_knn_dev: null pointer");
+  if (d <= 0) return fail(c, GR_ERR_INVALID, "gr_knn_dev: d %d must be positive", d);
+  if (metric != 0 && metric != 1) return fail(c, GR_ERR_INVALID, "gr_knn_dev: metric %d: 0 (euclidean) or 1 (cosine)", metric);
+  TRY(knn_graph_check(c, "gr_knn_dev", n, k));
+  if (d > GR_KNN_MAX_D) return fail(c, GR_ERR_UNSUPPORTED, "gr_knn_dev: d %d: at most %d columns", d, GR_KNN_MAX_D);
+  return scratch_launch(c, knn_workspace_bytes(n), [&](void* ws) { return launch_knn(x, n, d, k, metric, idx, dist, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_knn_dev: unsupported size", 0});
+}
+extern "C" int gr_lof_dev(gr_ctx* c, const int32_t* idx, const double* dist, int64_t n, int k, double* lrd, double* lof) {
+  if (!c) return GR_ERR_INVALID;
+  if (!idx || !dist || !lof) return fail(c, GR_ERR_INVALID, "gr_lof_dev: null pointer");
+  TRY(knn_graph_check(c, "gr_lof_dev", n, k));
+  return scratch_launch(c, lof_workspace_bytes(n), [&](void* ws) { return launch_lof(idx, dist, n, k, lrd, lof, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_lof_dev: unsupported size", 0});
+}
+extern "C" int gr_knn_overlap_dev(gr_ctx* c, const int32_t* idx_a, const int32_t* idx_b, int64_t n, int k, int32_t* count, double* mean) {
+  if (!c) return GR_ERR_INVALID;
+  if (!idx_a || !idx_b || !count || !mean) return fail(c, GR_ERR_INVALID, "gr_knn_overlap_dev: null pointer");
+  TRY(knn_graph_check(c, "gr_knn_overlap_dev", n, k));
+  return scratch_launch(c, knn_overlap_workspace_bytes(n), [&](void* ws) { return launch_knn_overlap(idx_a, idx_b, n, k, count, mean, ws, c->stream); },
+                        {GR_ERR_UNSUPPORTED, "gr_knn_overlap_dev: unsupported size", 0});
+}
+
 // ------------------------------------------------------------------ the sampling layer of a VAE (vae.hip)
 static int vae_check(gr_ctx* c, const char* who, bool null_ptr, int64_t B, int nd) {
   if (null_ptr) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);

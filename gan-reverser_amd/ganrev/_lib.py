@@ -205,6 +205,9 @@ _SIGS = {
     "gr_pca_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
     "gr_mixture_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "gr_silhouette_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gr_knn_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "gr_lof_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "gr_knn_overlap_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "gr_vae_sample_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gr_vae_sample_backward_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
@@ -674,6 +677,29 @@ class Context:
             metric = self.SILHOUETTE_METRICS[metric]
         self.check(self.lib.gr_silhouette_dev(self.h, _ptr(x_dev), int(n), int(d), _ptr(labels_dev), int(k), int(metric), _ptr(s_dev), _ptr(a_dev),
                                               _ptr(b_dev), _ptr(nearest_dev), _ptr(cluster_mean_dev), _ptr(sizes_dev), _ptr(mean_dev)), "gr_silhouette_dev")
+
+    KNN_MAX_N, KNN_MAX_D, KNN_MAX_K = 262144, 256, 128      # gr_knn_dev's limits (include/ganrev.h GR_KNN_MAX_N, GR_KNN_MAX_D, GR_KNN_MAX_K)
+    KNN_METRICS = {"euclidean": 0, "cosine": 1}
+
+    def knn_dev(self, x_dev, n, d, k, metric, idx_dev, dist_dev):
+        """gr_knn_dev (2 <= n <= 262144, d <= 256, k <= min(n - 1, 128)): the k nearest rows j != i of every row i of the device table [n x d], by
+        (distance, j) ascending; metric "euclidean" / "cosine" (or 0 / 1) -> idx_dev [n x k] int32, dist_dev [n x k] doubles.  Enqueued; no host
+        wait."""
+        if isinstance(metric, str):
+            if metric not in self.KNN_METRICS:
+                raise GanrevError(f"knn: metric {metric!r}: one of {sorted(self.KNN_METRICS)}")
+            metric = self.KNN_METRICS[metric]
+        self.check(self.lib.gr_knn_dev(self.h, _ptr(x_dev), int(n), int(d), int(k), int(metric), _ptr(idx_dev), _ptr(dist_dev)), "gr_knn_dev")
+
+    def lof_dev(self, idx_dev, dist_dev, n, k, lof_dev, lrd_dev=None):
+        """gr_lof_dev: the local outlier factors of a graph as knn_dev leaves it -> lof_dev [n] doubles, and the local reachability densities
+        into lrd_dev [n] doubles unless None.  Enqueued; no host wait."""
+        self.check(self.lib.gr_lof_dev(self.h, _ptr(idx_dev), _ptr(dist_dev), int(n), int(k), _ptr(lrd_dev), _ptr(lof_dev)), "gr_lof_dev")
+
+    def knn_overlap_dev(self, idx_a_dev, idx_b_dev, n, k, count_dev, mean_dev):
+        """gr_knn_overlap_dev: two graphs over the same n rows with the same k -> count_dev [n] int32, how many entries of a's row i are in b's row
+        i, and mean_dev 1 double, the mean of count / k.  Enqueued; no host wait."""
+        self.check(self.lib.gr_knn_overlap_dev(self.h, _ptr(idx_a_dev), _ptr(idx_b_dev), int(n), int(k), _ptr(count_dev), _ptr(mean_dev)), "gr_knn_overlap_dev")
 
     VAE_MAX_ND = 256                 # gr_vae_sample_*: latent dimensions at most (include/ganrev.h GR_VAE_MAX_ND)
 

@@ -18,7 +18,9 @@
   lowestShare, anomalyMetric   apply_r.lua:368-372   the anomaly rule on any per-image score
   principalAxesOfTable, mapOfTable, mixtureOfTable   --pca, --map, --mixture: ganrev.pca, ganrev.tsne, ganrev.mixture over the attribute table
   silhouetteStep, silhouetteSweep                    --silhouette, --silhouetteSweep: ganrev.silhouette over the labellings of that table
-  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions   what a run's options say about each, with the defaults
+  outlierStep, mapNeighboursKept                     --outliers, --mapNeighbours: ganrev.knn, the neighbour graph of that table - outlier factors, and
+                                                     how much of every row's neighbourhood the map (the whitened projection) kept
+  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions, outlierOptions, mapNeighbourOptions   what a run's options say about each, with the defaults
 
 These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
 frames and fields apply_r.lua draws) come from ganrev.render, on the GPU, and main() writes them with --render.
@@ -424,6 +426,36 @@ def silhouetteOfLabels(ctx, table, rows, labels, k):
     return {metric: SIL.score(ctx, table, labels[:rows], k, metric, rows=rows) for metric in SILHOUETTE_METRICS}
 
 
+OUTLIER_MAX_ROWS, OUTLIER_MAX_K = L.Context.KNN_MAX_N, L.Context.KNN_MAX_K     # gr_knn_dev's limits (GR_KNN_MAX_N, GR_KNN_MAX_K)
+OUTLIER_METRICS = ("cosine", "euclidean")
+
+
+def outlierMetric(OPT):
+    """--outlierMetric: the distance of the neighbour graphs; cosine, the search's geometry, unless asked otherwise"""
+    return getattr(OPT, "outlierMetric", "cosine")
+
+
+def outlierOptions(OPT):
+    """(K, rows, metric) of a run with --outliers K: the graph of the first `rows` rows, the option given, else min(nbImages, 100000); None
+    without --outliers"""
+    if not hasattr(OPT, "outliers"):
+        return None
+    return int(OPT.outliers), int(getattr(OPT, "outlierRows", min(OPT.nbImages, 100000))), outlierMetric(OPT)
+
+
+def mapNeighbourOptions(OPT):
+    """(K, metric of the table's graph) of a run with --mapNeighbours K; None without it"""
+    return (int(OPT.mapNeighbours), outlierMetric(OPT)) if hasattr(OPT, "mapNeighbours") else None
+
+
+def mapNeighboursKept(ctx, table, y, M, K, metric):
+    """--mapNeighbours K: the graph of the first M rows of the table the map was made from against the graph of the map y [M x 2] (euclidean: the
+    picture's own geometry) -> (kept [M] int32: how many of a row's K nearest rows in the table are among its K nearest in the map, the mean share)"""
+    from . import knn as KNN
+    with KNN.graph(ctx, table, K, metric, rows=M, keep=True) as there, KNN.graph(ctx, y, K, "euclidean", keep=True) as here:
+        return KNN.overlap(ctx, there, here)
+
+
 MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
 
 
@@ -484,6 +516,11 @@ def parse(argv=None):
     p.add_argument("--silhouette", action="store_true", default=argparse.SUPPRESS, help="silhouette coefficients of the clustering, on the device (ganrev.silhouette), in the table the clustering read: the cosine-assignment labels, and with --mixture the mixture's, each under the euclidean and the cosine distance; writes silhouette_{clusters,mixture}_{euclidean,cosine}.npy, silhouette_clusters_labels.npy and the means per labelling, metric and cluster into summary.json")
     p.add_argument("--silhouetteRows", type=int, default=argparse.SUPPRESS, metavar="M", help=f"with --silhouette / --silhouetteSweep: the first M rows are scored, later rows are nobody's member (default min(nbImages, 100000); at most {SILHOUETTE_MAX_ROWS}: every pair of rows is visited, the rows are independent draws, a prefix is a fair sample)")
     p.add_argument("--silhouetteSweep", default=argparse.SUPPRESS, metavar="K1,K2,...", help="which --nbClusters: the clustering is run again for each K (same seed, --nbIterations and --closest; no faces, no pictures) and scored; writes silhouette_sweep.json: K, the mean silhouette under both distances, the number of empty clusters")
+    # the neighbour-graph options: absent from the namespace unless given - outlierOptions() and mapNeighbourOptions() supply the defaults
+    p.add_argument("--outliers", type=int, default=argparse.SUPPRESS, metavar="K", help=f"local outlier factors of the recovered noise, on the device (ganrev.knn): every row's K nearest rows (at most {OUTLIER_MAX_K}) in the table the clustering read, and from them the rows that lie in a sparser neighbourhood than their neighbours do; writes knn_idx, knn_dist [outlierRows x K], outlier_lof and outlier_lrd (.npy), with --render outliers_lof.png, the highest factor first; with --pca K2 --pcaSpace also the share of every row's neighbours in the attribute table that the whitened projection kept (kept_by_pca in summary.json)")
+    p.add_argument("--outlierRows", type=int, default=argparse.SUPPRESS, metavar="M", help=f"with --outliers: the graph of the first M rows (default min(nbImages, 100000); at most {OUTLIER_MAX_ROWS}: every pair of rows is visited, the rows are independent draws, a prefix is a fair sample)")
+    p.add_argument("--outlierMetric", choices=list(OUTLIER_METRICS), default=argparse.SUPPRESS, help="with --outliers / --mapNeighbours: the distance of the table's neighbour graph (default cosine, the search's geometry)")
+    p.add_argument("--mapNeighbours", type=int, default=argparse.SUPPRESS, metavar="K", help=f"with --map: how many of every mapped row's K nearest rows in the table (at most {OUTLIER_MAX_K}) are still among its K nearest in the map (ganrev.knn); writes map_neighbours_kept.npy [mapRows] and the mean share into summary.json")
     p.add_argument("--mixture", type=int, default=argparse.SUPPRESS, metavar="ITER", help="a diagonal Gaussian mixture of the recovered noise, on the device (ganrev.mixture): ITER EM iterations from the clustering's final centroids, --nbClusters components (at most 256), in the table the clustering read; writes mixture_weights, mixture_means, mixture_variances, mixture_loglik [ITER + 1], mixture_labels, mixture_posterior, mixture_row_loglik (.npy), with --render mixture_%%02d.png and mixture_outliers.png, with --needles needle_mixture.npy")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
@@ -562,6 +599,30 @@ def parse(argv=None):
             p.error(f"--silhouetteRows {scored[0]}: at most {SILHOUETTE_MAX_ROWS} rows (every pair of rows is visited)")
         if not 2 <= scored[0] <= OPT.nbImages:
             p.error(f"--silhouetteRows {scored[0]}: 2 to nbImages = {OPT.nbImages} rows")
+    graphed = outlierOptions(OPT)
+    if hasattr(OPT, "outlierRows") and graphed is None:
+        p.error("--outlierRows belongs to the outlier factors: give --outliers K")
+    if hasattr(OPT, "outlierMetric") and graphed is None and not hasattr(OPT, "mapNeighbours"):
+        p.error("--outlierMetric belongs to the neighbour graphs: give --outliers K or --mapNeighbours K")
+    if graphed is not None:
+        nbNear, nearRows, _ = graphed
+        if OPT.host:
+            p.error("--outliers runs on the device-resident tables: not with --host")
+        if nearRows > OUTLIER_MAX_ROWS:
+            p.error(f"--outlierRows {nearRows}: at most {OUTLIER_MAX_ROWS} rows (every pair of rows is visited)")
+        if not 2 <= nearRows <= OPT.nbImages:
+            p.error(f"--outlierRows {nearRows}: 2 to nbImages = {OPT.nbImages} rows")
+        if not 1 <= nbNear <= OUTLIER_MAX_K:
+            p.error(f"--outliers {nbNear}: 1 to {OUTLIER_MAX_K} neighbours")
+        if nbNear > nearRows - 1:
+            p.error(f"--outliers {nbNear}: at most rows - 1 = {nearRows - 1} neighbours (a row is not its own)")
+    if hasattr(OPT, "mapNeighbours"):
+        if not mapped:
+            p.error("--mapNeighbours belongs to the map: give --map")
+        if not 1 <= OPT.mapNeighbours <= OUTLIER_MAX_K:
+            p.error(f"--mapNeighbours {OPT.mapNeighbours}: 1 to {OUTLIER_MAX_K} neighbours")
+        if OPT.mapNeighbours > mapped[0] - 1:
+            p.error(f"--mapNeighbours {OPT.mapNeighbours}: at most mapRows - 1 = {mapped[0] - 1} neighbours (a row is not its own)")
     if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
         p.error("--needles and --real read their images from --dataset")
     if (OPT.needles or OPT.real) and OPT.host:
@@ -750,6 +811,12 @@ def mapStep(S):
     y, (kl_iterations, kl), S.map_cells, entry = mapOfTable(S.ctx, S.space, *mapOptions(S.OPT))
     np.save(S.out("map_y.npy"), y); np.save(S.out("map_kl.npy"), np.stack([kl_iterations.astype(np.float64), kl], axis=1)); np.save(S.out("map_cells.npy"), S.map_cells)
     S.summary["map"] = dict(entry, space=S.spaceName)
+    if mapNeighbourOptions(S.OPT):
+        K, metric = mapNeighbourOptions(S.OPT)
+        kept, share = mapNeighboursKept(S.ctx, S.space, y, len(y), K, metric)
+        np.save(S.out("map_neighbours_kept.npy"), kept)
+        S.summary["map"]["neighbours"] = dict(k=K, metric=metric, mean_share_kept=share)
+        S.say("<apply_r> the map keeps %.1f %% of every row's %d nearest rows (%s distance in %s)" % (100 * share, K, metric, S.spaceName))
 
 
 def needlesInSpace(S, na):
@@ -880,10 +947,39 @@ def silhouetteStep(S, table, centroids, images=None):
                       open(out("silhouette_sweep.json"), "w"), indent=1)
 
 
+def outlierStep(S, table, centroids, images=None):
+    """--outliers K, after the clustering, in the table it read: the neighbour graph of the first rows is built once, stays on the device and is
+    scored there.  With --pcaSpace the attribute table's graph of the same rows is built beside it: the share of its neighbours that the
+    whitened projection kept."""
+    from . import knn as KNN
+    OPT, ctx, out = S.OPT, S.ctx, S.out
+    k, rows, metric = outlierOptions(OPT)
+    S.say("Neighbour graph and local outlier factors...")
+    with KNN.graph(ctx, table, k, metric, rows=rows, keep=True) as g:
+        lof, lrd = KNN.lof(ctx, g)
+        host = g.numpy()
+        entry = dict(k=k, rows=rows, metric=metric, space=S.spaceName, lof_max=float(lof.max()), lof_median=float(np.median(lof)),
+                     lof_p99=float(np.percentile(lof, 99)))
+        if pcaOptions(OPT)[1]:
+            attributes = S.da if S.da is not None and S.da.ptr is not None else S.attributes
+            with KNN.graph(ctx, attributes, k, metric, rows=rows, keep=True) as before:
+                entry["kept_by_pca"] = KNN.overlap(ctx, before, g)[1]
+    np.save(out("knn_idx.npy"), host.idx); np.save(out("knn_dist.npy"), host.dist)
+    np.save(out("outlier_lof.npy"), lof); np.save(out("outlier_lrd.npy"), lrd)
+    S.summary["outliers"] = entry
+    S.say("<apply_r> local outlier factor, %d neighbours, %s distance, %d rows in %s: median %.4f, 99th percentile %.4f, max %.4f"
+          % (k, metric, rows, S.spaceName, entry["lof_median"], entry["lof_p99"], entry["lof_max"]))
+    if OPT.render and images is not None:
+        shown = min(512 + 16, OPT.nbImages, 1024, rows)                       # as many rows as mixture_outliers.png shows
+        worst = np.argsort(-lof, kind="stable")[:shown]                       # highest factor first
+        render.grid(images, worst, int(math.floor(math.sqrt(shown))), S.colorSpace, path=out("outliers_lof.png"))
+
+
 def afterClustering(S):
-    """the steps that follow the clustering in its table - the mixture, then the silhouette, which scores the mixture's labels too - as one call
-    (table, centroids, images=None); None when the run asks for neither"""
-    steps = [mixtureStep] * (mixtureOptions(S.OPT) is not None) + [silhouetteStep] * (silhouetteOptions(S.OPT) is not None)
+    """the steps that follow the clustering in its table - the mixture, then the silhouette, which scores the mixture's labels too, then the
+    outlier factors - as one call (table, centroids, images=None); None when the run asks for none of them"""
+    steps = ([mixtureStep] * (mixtureOptions(S.OPT) is not None) + [silhouetteStep] * (silhouetteOptions(S.OPT) is not None)
+             + [outlierStep] * (outlierOptions(S.OPT) is not None))
     if not steps:
         return None
 

@@ -579,6 +579,41 @@ int gr_silhouette_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, const i
                       double* s_dev /*[n]*/, double* a_dev /*[n] nullable*/, double* b_dev /*[n] nullable*/, int32_t* nearest_dev /*[n] nullable*/,
                       double* cluster_mean_dev /*[k]*/, int32_t* sizes_dev /*[k]*/, double* mean_dev /*[1]*/);
 
+/* ---- the k-nearest-neighbour graph of a device table, and what is read off it (csrc/knn.hip; new: the reference has no counterpart) ----
+ * gr_knn_dev: x_dev [n x d] floats; idx_dev [n x k] int32 and dist_dev [n x k] doubles receive, for every row i, the k rows j != i of smallest
+ * distance and those distances, ordered by (distance ascending, j ascending).  metric 0: euclidean distance, 1: cosine distance.  Every pointer is
+ * device memory; the work is enqueued on the ctx stream and the call returns without waiting for it; scratch comes from the context.  The graph stays
+ * on the device: gr_lof_dev and gr_knn_overlap_dev read it where it lies.
+ * Everything past the loads is fp64, every operation rounded on its own (no fused multiply-add); sqrt is the device library's (correctly rounded).
+ * The pair distances are gr_silhouette_dev's, operation for operation and bit for bit:
+ * Pair distance, euclidean.  t = x_it - x_jt, D = D + t t in column order from +0.0, dist = sqrt(D) - never |x_i|^2 + |x_j|^2 - 2 x_i . x_j.
+ * Pair distance, cosine.  p = p + x_it x_jt in column order from +0.0; q_i = sqrt(Q_i), Q_i = Q_i + x_it x_it by the same chain, once per row;
+ * c = p / (q_i q_j), and 0 where either norm is 0; dist = 1 - c, and 0 where that is not above 0.
+ * Selection.  Row i itself never appears in its list; a duplicate of row i does, at distance 0.  Among equal distances the lower row index comes
+ * first, inside the list and at its end: of two rows that tie for the k-th place the lower one is kept.
+ * Cost.  All n^2 pairs are visited (the symmetry dist_ij = dist_ji is not used).  The lists cost about k ln(n / k) insertions per row for rows in
+ * random order; a table sorted so that every later row is nearer to some row costs that row n k list moves.
+ * gr_lof_dev: the local outlier factor of every row of a graph as gr_knn_dev leaves it (idx_dev, dist_dev [n x k]); lrd_dev (nullable) and lof_dev
+ * [n] doubles.  kdist_j = dist[j][k - 1]; reach(i, j) = max(kdist_j, dist[i][p]) for the p-th neighbour j of i; m_i = (the k reach values added in
+ * list order from +0.0) / k; lrd_i = 1 / (m_i + 1e-10) - the constant keeps a row among k or more exact duplicates finite; lof_i = ((the
+ * neighbours' lrd added in list order from +0.0) / k) / lrd_i.  Indices outside [0, n) are outside the contract.
+ * gr_knn_overlap_dev: idx_a_dev, idx_b_dev [n x k]: two graphs over the same n rows with the same k.  count_dev [n] int32: how many entries of row i
+ * of a occur in row i of b.  mean_dev 1 double: the values count_i / k (one division each), per block of 512 consecutive rows in row order from
+ * +0.0, the block partials in block order from +0.0, one division by n.
+ * No floating-point atomics, no grid barrier, nothing depends on the CU count or on the order in which workgroups finish: two runs give the same bits.
+ * Limits: 2 <= n <= GR_KNN_MAX_N (the pair work is n^2 d in fp64), 1 <= d <= GR_KNN_MAX_D, 1 <= k <= min(n - 1, GR_KNN_MAX_K); outside them
+ * GR_ERR_UNSUPPORTED with a gr_last_error text that names the value; null required pointers, non-positive n, d, k or an unknown metric:
+ * GR_ERR_INVALID.  Nothing is launched in either case and the context stays usable.  Non-finite elements are outside the contract.
+ * Scratch: gr_knn_dev n doubles (the norms; 8 n bytes, at most 2 MB); gr_lof_dev n doubles (lrd); gr_knn_overlap_dev n + ceil(n / 512) doubles. */
+#define GR_KNN_MAX_N 262144
+#define GR_KNN_MAX_D 256
+#define GR_KNN_MAX_K 128
+int gr_knn_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int k, int metric /*0 euclidean, 1 cosine*/, int32_t* idx_dev /*[n x k]*/,
+               double* dist_dev /*[n x k]*/);
+int gr_lof_dev(gr_ctx* ctx, const int32_t* idx_dev, const double* dist_dev, int64_t n, int k, double* lrd_dev /*[n] nullable*/, double* lof_dev /*[n]*/);
+int gr_knn_overlap_dev(gr_ctx* ctx, const int32_t* idx_a_dev, const int32_t* idx_b_dev, int64_t n, int k, int32_t* count_dev /*[n]*/,
+                       double* mean_dev /*[1]*/);
+
 /* ---- the sampling layer of a variational autoencoder (csrc/vae.hip; new: the reference has no counterpart) ----
  * The layer between an encoder whose head emits a mean and a log-variance and a decoder: the reparameterisation z = mu + exp(logvar / 2) eps, its KL
  * term against the unit Gaussian, and the backward of both.  h [B x 2 nd] floats: columns 0 .. nd - 1 of a row hold mu, columns nd .. 2 nd - 1 hold
