@@ -673,6 +673,23 @@ int launch_lof(const int* idx, const double* dist, long n, int k, double* lrd, d
 size_t knn_overlap_workspace_bytes(long n);
 int launch_knn_overlap(const int* a, const int* b, long n, int k, int* count, double* mean, void* workspace, hipStream_t s);
 
+// ---------------------------------------------------------------- density-based clustering of a device table (density.hip; gr_eps_graph_dev, gr_dbscan_dev)
+// x [n x d] floats; adj [n x ceil(n / 64)] 64-bit words: bit j of row i set iff silhouette.hip's pair distance of (i, j) is <= eps, or j = i; count
+// [n] ints: the rows' popcounts; labels / core (nullable) [n] ints, n_clusters 1 int: all device.  metric 0 euclidean, 1 cosine.  launch_eps_graph
+// returns 1 outside 2 <= n <= DBSCAN_MAX_N, 1 <= d <= 256, eps finite and >= 0, metric 0 / 1; launch_dbscan_begin outside that n or 1 <= min_pts <= n.
+// gr_dbscan_dev's three parts share a carved workspace of dbscan_workspace_bytes: begin (core flags, label = the row itself), then the caller repeats
+// round (one hook-and-compress pass; *w.changed is 1 afterwards where a label fell) until one changes nothing, then finish (border rows, cluster
+// numbers).  n rounds always suffice.
+constexpr long DBSCAN_MAX_N = SIL_MAX_N;
+struct DbscanScratch { int* label; int* rank; int* changed; unsigned long long* mask; };
+size_t eps_graph_workspace_bytes(long n);
+int launch_eps_graph(const float* x, long n, int d, double eps, int metric, unsigned long long* adj, int* count, void* workspace, hipStream_t s);
+size_t dbscan_workspace_bytes(long n);
+DbscanScratch dbscan_carve(void* workspace, long n);
+int launch_dbscan_begin(const int* count, long n, int min_pts, const DbscanScratch& w, hipStream_t s);
+void launch_dbscan_round(const unsigned long long* adj, long n, const DbscanScratch& w, hipStream_t s);
+void launch_dbscan_finish(const unsigned long long* adj, long n, const DbscanScratch& w, int* labels, int* core, int* n_clusters, hipStream_t s);
+
 // ---------------------------------------------------------------- the sampling layer of a VAE (vae.hip; gr_vae_sample_dev, gr_vae_sample_backward_dev)
 // h [B x 2 nd] = (mu | logvar), eps (nullable: 0) / z / gz [B x nd], gh [B x 2 nd], kl_rows [B] floats and kl 1 double nullable: all device; workspace
 // of chain_mean_workspace_bytes(B), read only when kl is given; c = kl_weight / B.  Both return 1 outside 1 <= B < 2^31, 1 <= nd <= 256.

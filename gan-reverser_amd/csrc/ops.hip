@@ -4,6 +4,7 @@
 #include "ctx.h"
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 
 using namespace gr;
@@ -627,6 +628,51 @@ extern "C" int gr_knn_overlap_dev(gr_ctx* c, const int32_t* idx_a, const int32_t
   TRY(knn_graph_check(c, "gr_knn_overlap_dev", n, k));
   return scratch_launch(c, knn_overlap_workspace_bytes(n), [&](void* ws) { return launch_knn_overlap(idx_a, idx_b, n, k, count, mean, ws, c->stream); },
                         {GR_ERR_UNSUPPORTED, "gr_knn_overlap_dev: unsupported size", 0});
+}
+
+// ------------------------------------------------------------------ density-based clustering of a device table (density.hip)
+static int dbscan_rows_check(gr_ctx* c, const char* who, int64_t n) {
+  if (n <= 0) return fail(c, GR_ERR_INVALID, "%s: n %lld must be positive", who, (long long)n);
+  if (n < 2 || n > GR_DBSCAN_MAX_N) return fail(c, GR_ERR_UNSUPPORTED, "%s: n %lld: between 2 and %d rows", who, (long long)n, GR_DBSCAN_MAX_N);
+  return GR_OK;
+}
+extern "C" int gr_eps_graph_dev(gr_ctx* c, const float* x, int64_t n, int d, double eps, int metric, uint64_t* adj, int32_t* count) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !adj || !count) return fail(c, GR_ERR_INVALID, "gr_eps_graph_dev: null pointer");
+  if (d <= 0) return fail(c, GR_ERR_INVALID, "gr_eps_graph_dev: d %d must be positive", d);
+  if (metric != 0 && metric != 1) return fail(c, GR_ERR_INVALID, "gr_eps_graph_dev: metric %d: 0 (euclidean) or 1 (cosine)", metric);
+  if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(c, GR_ERR_INVALID, "gr_eps_graph_dev: eps %g: a finite distance, not below 0", eps);
+  TRY(dbscan_rows_check(c, "gr_eps_graph_dev", n));
+  if (d > GR_DBSCAN_MAX_D) return fail(c, GR_ERR_UNSUPPORTED, "gr_eps_graph_dev: d %d: at most %d columns", d, GR_DBSCAN_MAX_D);
+  return scratch_launch(c, eps_graph_workspace_bytes(n), [&](void* ws) {
+    return launch_eps_graph(x, n, d, eps, metric, reinterpret_cast<unsigned long long*>(adj), count, ws, c->stream);
+  }, {GR_ERR_UNSUPPORTED, "gr_eps_graph_dev: unsupported size", 0});
+}
+// (the one analysis call that waits on the stream: once per round, to read whether a label fell)
+extern "C" int gr_dbscan_dev(gr_ctx* c, const uint64_t* adj, const int32_t* count, int64_t n, int min_pts, int32_t* labels, int32_t* core, int32_t* n_clusters) {
+  if (!c) return GR_ERR_INVALID;
+  if (!adj || !count || !labels || !n_clusters) return fail(c, GR_ERR_INVALID, "gr_dbscan_dev: null pointer");
+  if (min_pts <= 0) return fail(c, GR_ERR_INVALID, "gr_dbscan_dev: min_pts %d must be positive", min_pts);
+  TRY(dbscan_rows_check(c, "gr_dbscan_dev", n));
+  if (min_pts > n) return fail(c, GR_ERR_UNSUPPORTED, "gr_dbscan_dev: min_pts %d: at most n = %lld rows (a neighbourhood holds no more)", min_pts, (long long)n);
+  Staging s(c);
+  auto scratch = s.reserve<char>(dbscan_workspace_bytes(n));
+  TRY(s.grow());
+  const DbscanScratch w = dbscan_carve(s.ptr(scratch), n);
+  const unsigned long long* bitmap = reinterpret_cast<const unsigned long long*>(adj);
+  if (launch_dbscan_begin(count, n, min_pts, w, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_dbscan_dev: unsupported size");
+  LAUNCHCHK(c);
+  bool settled = false;
+  for (int64_t round = 0; round < n && !settled; ++round) {             // n - 1 rounds carry a label along the longest path; the n-th changes nothing
+    launch_dbscan_round(bitmap, n, w, c->stream); LAUNCHCHK(c);
+    int changed = 1;
+    HIPCHK(c, hipMemcpyAsync(&changed, w.changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    TRY(s.finish());
+    settled = changed == 0;
+  }
+  if (!settled) return fail(c, GR_ERR_STATE, "gr_dbscan_dev: the labels did not settle in n = %lld rounds", (long long)n);
+  launch_dbscan_finish(bitmap, n, w, labels, core, n_clusters, c->stream); LAUNCHCHK(c);
+  return GR_OK;
 }
 
 // ------------------------------------------------------------------ the sampling layer of a VAE (vae.hip)

@@ -208,6 +208,8 @@ _SIGS = {
     "gr_knn_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
     "gr_lof_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "gr_knn_overlap_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "gr_eps_graph_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P, _P]),
+    "gr_dbscan_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "gr_vae_sample_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gr_vae_sample_backward_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
@@ -700,6 +702,31 @@ class Context:
         """gr_knn_overlap_dev: two graphs over the same n rows with the same k -> count_dev [n] int32, how many entries of a's row i are in b's row
         i, and mean_dev 1 double, the mean of count / k.  Enqueued; no host wait."""
         self.check(self.lib.gr_knn_overlap_dev(self.h, _ptr(idx_a_dev), _ptr(idx_b_dev), int(n), int(k), _ptr(count_dev), _ptr(mean_dev)), "gr_knn_overlap_dev")
+
+    DBSCAN_MAX_N, DBSCAN_MAX_D = 262144, 256                # gr_eps_graph_dev's limits (include/ganrev.h GR_DBSCAN_MAX_N, GR_DBSCAN_MAX_D)
+    DBSCAN_METRICS = {"euclidean": 0, "cosine": 1}
+
+    @staticmethod
+    def eps_words(n):
+        """GR_EPS_WORDS(n): the 64-bit words of one row of an eps-graph over n rows"""
+        return (int(n) + 63) // 64
+
+    def eps_graph_dev(self, x_dev, n, d, eps, metric, adj_dev, count_dev):
+        """gr_eps_graph_dev (2 <= n <= 262144, d <= 256, eps finite and >= 0): the eps-neighbourhood graph of the device table [n x d] as a bitmap;
+        metric "euclidean" / "cosine" (or 0 / 1) -> adj_dev [n x eps_words(n)] uint64, bit j of row i set iff dist(i, j) <= eps (the diagonal
+        always), and count_dev [n] int32, the rows' popcounts.  Enqueued; no host wait."""
+        if isinstance(metric, str):
+            if metric not in self.DBSCAN_METRICS:
+                raise GanrevError(f"density: metric {metric!r}: one of {sorted(self.DBSCAN_METRICS)}")
+            metric = self.DBSCAN_METRICS[metric]
+        self.check(self.lib.gr_eps_graph_dev(self.h, _ptr(x_dev), int(n), int(d), float(eps), int(metric), _ptr(adj_dev), _ptr(count_dev)), "gr_eps_graph_dev")
+
+    def dbscan_dev(self, adj_dev, count_dev, n, min_pts, labels_dev, core_dev, n_clusters_dev):
+        """gr_dbscan_dev: DBSCAN's labels of an eps-graph as eps_graph_dev leaves it (1 <= min_pts <= n) -> labels_dev [n] int32 (-1: noise),
+        core_dev [n] int32 0 / 1 unless None, n_clusters_dev 1 int32.  WAITS on the stream once per round of the component search to read whether
+        a label changed; the last kernels are enqueued and not waited for."""
+        self.check(self.lib.gr_dbscan_dev(self.h, _ptr(adj_dev), _ptr(count_dev), int(n), int(min_pts), _ptr(labels_dev), _ptr(core_dev),
+                                          _ptr(n_clusters_dev)), "gr_dbscan_dev")
 
     VAE_MAX_ND = 256                 # gr_vae_sample_*: latent dimensions at most (include/ganrev.h GR_VAE_MAX_ND)
 

@@ -20,7 +20,9 @@
   silhouetteStep, silhouetteSweep                    --silhouette, --silhouetteSweep: ganrev.silhouette over the labellings of that table
   outlierStep, mapNeighboursKept                     --outliers, --mapNeighbours: ganrev.knn, the neighbour graph of that table - outlier factors, and
                                                      how much of every row's neighbourhood the map (the whitened projection) kept
-  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions, outlierOptions, mapNeighbourOptions   what a run's options say about each, with the defaults
+  densityStep                                        --density: ganrev.density, DBSCAN over that table - the cluster count it finds, and the rows
+                                                     that belong to no cluster
+  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions, outlierOptions, mapNeighbourOptions, densityOptions   what a run's options say about each, with the defaults
 
 These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
 frames and fields apply_r.lua draws) come from ganrev.render, on the GPU, and main() writes them with --render.
@@ -456,6 +458,24 @@ def mapNeighboursKept(ctx, table, y, M, K, metric):
         return KNN.overlap(ctx, there, here)
 
 
+DENSITY_MAX_ROWS = L.Context.DBSCAN_MAX_N     # gr_eps_graph_dev's limit (GR_DBSCAN_MAX_N)
+DENSITY_MAX_MINPTS_BY_QUANTILE = L.Context.KNN_MAX_K + 1     # the quantile route reads the distance to the (minPts - 1)-th of at most 128 neighbours
+DENSITY_METRICS = ("cosine", "euclidean")
+DENSITY_OPTIONS = ("densityMinPts", "densityEps", "densityQuantile", "densityRows", "densityMetric")
+
+
+def densityOptions(OPT):
+    """(minPts, eps or None, quantile or None, rows, metric) of a run with --density: DBSCAN of the first `rows` rows, the option given, else
+    min(nbImages, 100000); eps as given, else the quantile (0.75 unless given) of the rows' distances to their (minPts - 1)-th neighbour; None
+    without --density"""
+    if not getattr(OPT, "density", False):
+        return None
+    eps = float(OPT.densityEps) if hasattr(OPT, "densityEps") else None
+    quantile = None if eps is not None else float(getattr(OPT, "densityQuantile", 0.75))
+    return (int(getattr(OPT, "densityMinPts", 10)), eps, quantile, int(getattr(OPT, "densityRows", min(OPT.nbImages, 100000))),
+            getattr(OPT, "densityMetric", "cosine"))
+
+
 MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
 
 
@@ -521,6 +541,13 @@ def parse(argv=None):
     p.add_argument("--outlierRows", type=int, default=argparse.SUPPRESS, metavar="M", help=f"with --outliers: the graph of the first M rows (default min(nbImages, 100000); at most {OUTLIER_MAX_ROWS}: every pair of rows is visited, the rows are independent draws, a prefix is a fair sample)")
     p.add_argument("--outlierMetric", choices=list(OUTLIER_METRICS), default=argparse.SUPPRESS, help="with --outliers / --mapNeighbours: the distance of the table's neighbour graph (default cosine, the search's geometry)")
     p.add_argument("--mapNeighbours", type=int, default=argparse.SUPPRESS, metavar="K", help=f"with --map: how many of every mapped row's K nearest rows in the table (at most {OUTLIER_MAX_K}) are still among its K nearest in the map (ganrev.knn); writes map_neighbours_kept.npy [mapRows] and the mean share into summary.json")
+    # the density options: absent from the namespace unless given - densityOptions() supplies the defaults
+    p.add_argument("--density", action="store_true", default=argparse.SUPPRESS, help="density-based clustering of the recovered noise, on the device (ganrev.density: DBSCAN), in the table the clustering read: it finds the number of clusters itself, follows groups of any shape and labels the rows that belong nowhere as noise; writes density_labels (int32, -1 = noise), density_core, density_count (.npy), with the quantile route density_kdist.npy, with --silhouette silhouette_density_{euclidean,cosine}.npy, with --render density_noise.png and density_%%02d.png, the largest clusters")
+    p.add_argument("--densityMinPts", type=int, default=argparse.SUPPRESS, metavar="M", help="with --density: a row is core when its eps-neighbourhood holds M rows, itself included (default 10)")
+    p.add_argument("--densityEps", type=float, default=argparse.SUPPRESS, metavar="E", help="with --density: the neighbourhood radius, a literal distance (not with --densityQuantile)")
+    p.add_argument("--densityQuantile", type=float, default=argparse.SUPPRESS, metavar="Q", help=f"with --density: eps is the Q-quantile of the rows' distances to their (M - 1)-th nearest row (ganrev.knn), so that about that share of the rows is core (default 0.75; 2 <= M <= {DENSITY_MAX_MINPTS_BY_QUANTILE}; not with --densityEps)")
+    p.add_argument("--densityRows", type=int, default=argparse.SUPPRESS, metavar="N", help=f"with --density: the first N rows are clustered (default min(nbImages, 100000); at most {DENSITY_MAX_ROWS}: every pair of rows is visited, the rows are independent draws, a prefix is a fair sample)")
+    p.add_argument("--densityMetric", choices=list(DENSITY_METRICS), default=argparse.SUPPRESS, help="with --density: the distance (default cosine, the search's geometry)")
     p.add_argument("--mixture", type=int, default=argparse.SUPPRESS, metavar="ITER", help="a diagonal Gaussian mixture of the recovered noise, on the device (ganrev.mixture): ITER EM iterations from the clustering's final centroids, --nbClusters components (at most 256), in the table the clustering read; writes mixture_weights, mixture_means, mixture_variances, mixture_loglik [ITER + 1], mixture_labels, mixture_posterior, mixture_row_loglik (.npy), with --render mixture_%%02d.png and mixture_outliers.png, with --needles needle_mixture.npy")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
@@ -623,6 +650,29 @@ def parse(argv=None):
             p.error(f"--mapNeighbours {OPT.mapNeighbours}: 1 to {OUTLIER_MAX_K} neighbours")
         if OPT.mapNeighbours > mapped[0] - 1:
             p.error(f"--mapNeighbours {OPT.mapNeighbours}: at most mapRows - 1 = {mapped[0] - 1} neighbours (a row is not its own)")
+    dense = densityOptions(OPT)
+    for name in DENSITY_OPTIONS:
+        if hasattr(OPT, name) and dense is None:
+            p.error(f"--{name} belongs to the density-based clustering: give --density")
+    if dense is not None:
+        minPts, eps, quantile, denseRows, _ = dense
+        if OPT.host:
+            p.error("--density runs on the device-resident tables: not with --host")
+        if hasattr(OPT, "densityEps") and hasattr(OPT, "densityQuantile"):
+            p.error("--densityEps and --densityQuantile: one of the two (a literal radius, or the quantile that chooses it)")
+        if denseRows > DENSITY_MAX_ROWS:
+            p.error(f"--densityRows {denseRows}: at most {DENSITY_MAX_ROWS} rows (every pair of rows is visited)")
+        if not 2 <= denseRows <= OPT.nbImages:
+            p.error(f"--densityRows {denseRows}: 2 to nbImages = {OPT.nbImages} rows")
+        if not 1 <= minPts <= denseRows:
+            p.error(f"--densityMinPts {minPts}: 1 to rows = {denseRows} (a neighbourhood holds no more)")
+        if eps is not None and not (math.isfinite(eps) and eps >= 0):
+            p.error(f"--densityEps {eps:g}: a finite distance, not below 0")
+        if quantile is not None:
+            if not 2 <= minPts <= DENSITY_MAX_MINPTS_BY_QUANTILE:
+                p.error(f"--densityMinPts {minPts}: 2 to {DENSITY_MAX_MINPTS_BY_QUANTILE} with --densityQuantile (the distance to the (M - 1)-th neighbour): give --densityEps E")
+            if not 0 <= quantile <= 1:
+                p.error(f"--densityQuantile {quantile:g}: 0 to 1")
     if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
         p.error("--needles and --real read their images from --dataset")
     if (OPT.needles or OPT.real) and OPT.host:
@@ -661,6 +711,7 @@ class Run:
         self.by_attr = self.by_pix = self.map_cells = self.rendered = None
         self.pca = self.needle_rows = None                                    # what the steps before the mixture leave for it
         self.mixture_labels = None                                            # ... and the mixture for the silhouette
+        self.density = None                                                   # ... and the density-based clustering (ganrev.density.Clustering)
 
     def out(self, name):
         return os.path.join(self.OPT.writeTo, name)
@@ -923,11 +974,19 @@ def silhouetteStep(S, table, centroids, images=None):
             clusterTableDev(ctx, ptr, N, d, k, 0, m, centroids, closest, labels_into=got)
             np.save(out("silhouette_clusters_labels.npy"), got[0])
             entry = dict(rows=rows, space=S.spaceName)
-            for name, labels in (("clusters", got[0]), ("mixture", S.mixture_labels)):
+            scored = [("clusters", got[0], k), ("mixture", S.mixture_labels, k)]
+            if S.density is not None:
+                if 1 <= S.density.clusters <= MAX_CLUSTERS:               # (rows past --densityRows are nobody's member, like the noise)
+                    padded = np.full(N, -1, np.int32)
+                    padded[:S.density.n] = S.density.labels
+                    scored.append(("density", padded, S.density.clusters))
+                else:
+                    entry["density"] = dict(skipped="%d clusters: the silhouette scores 1 to %d" % (S.density.clusters, MAX_CLUSTERS))
+            for name, labels, nb in scored:
                 if labels is None:
                     continue
                 entry[name] = {}
-                for metric, sc in silhouetteOfLabels(ctx, (ptr, N, d), rows, labels, k).items():
+                for metric, sc in silhouetteOfLabels(ctx, (ptr, N, d), rows, labels, nb).items():
                     np.save(out("silhouette_%s_%s.npy" % (name, metric)), sc.values)
                     entry[name][metric] = sc.summary()
                     S.say("<apply_r> silhouette of the %s, %s distance, %d rows in %s: mean %.4f" % (name, metric, rows, S.spaceName, sc.mean))
@@ -975,11 +1034,41 @@ def outlierStep(S, table, centroids, images=None):
         render.grid(images, worst, int(math.floor(math.sqrt(shown))), S.colorSpace, path=out("outliers_lof.png"))
 
 
+def densityStep(S, table, centroids, images=None):
+    """--density, after the clustering, in the table it read: the eps-graph of the first rows is built once, stays on the device and is labelled
+    there.  Without --densityEps the radius comes from the neighbour graph of the same rows (the k-distance rule)."""
+    from . import density as DN
+    OPT, ctx, out = S.OPT, S.ctx, S.out
+    minPts, eps, quantile, rows, metric = densityOptions(OPT)
+    S.say("Density-based clustering (DBSCAN)...")
+    entry = dict(minPts=minPts, metric=metric, rows=rows, space=S.spaceName)
+    if eps is None:
+        eps, kdist = DN.epsFromNeighbours(ctx, table, minPts, quantile, metric, rows=rows)
+        np.save(out("density_kdist.npy"), kdist)
+        entry["quantile"] = quantile
+    found = S.density = DN.cluster(ctx, table, eps, minPts, metric, rows=rows)
+    np.save(out("density_labels.npy"), found.labels); np.save(out("density_core.npy"), found.core.astype(np.int32))
+    np.save(out("density_count.npy"), found.count)
+    largest = np.argsort(-found.sizes, kind="stable")[:20]                    # largest first, the lower number among equals
+    entry.update(eps=float(eps), clusters=found.clusters, core=int(found.core.sum()), border=found.border, noise=found.noise,
+                 sizes=[int(found.sizes[c]) for c in largest])
+    S.summary["density"] = entry
+    S.say("<apply_r> DBSCAN, eps %.6g, minPts %d, %s distance, %d rows in %s: %d clusters, %d core, %d border and %d noise rows"
+          % (eps, minPts, metric, rows, S.spaceName, found.clusters, entry["core"], found.border, found.noise))
+    if OPT.render and images is not None:
+        noise = np.nonzero(found.labels < 0)[0][:min(512 + 16, OPT.nbImages, 1024)]       # the first noise rows, as many as anomalies.png shows
+        if len(noise):
+            render.grid(images, noise, max(int(math.floor(math.sqrt(len(noise)))), 1), S.colorSpace, path=out("density_noise.png"))
+        for j, c in enumerate(largest):
+            members = np.nonzero(found.labels == c)[0][:64 + 8]                # lowest rows first
+            render.grid(images, members, max(int(math.floor(math.sqrt(len(members)))), 1), S.colorSpace, path=out("density_%02d.png" % (j + 1)))
+
+
 def afterClustering(S):
-    """the steps that follow the clustering in its table - the mixture, then the silhouette, which scores the mixture's labels too, then the
-    outlier factors - as one call (table, centroids, images=None); None when the run asks for none of them"""
-    steps = ([mixtureStep] * (mixtureOptions(S.OPT) is not None) + [silhouetteStep] * (silhouetteOptions(S.OPT) is not None)
-             + [outlierStep] * (outlierOptions(S.OPT) is not None))
+    """the steps that follow the clustering in its table - the mixture, the density-based clustering, then the silhouette, which scores the labels
+    of both too, then the outlier factors - as one call (table, centroids, images=None); None when the run asks for none of them"""
+    steps = ([mixtureStep] * (mixtureOptions(S.OPT) is not None) + [densityStep] * (densityOptions(S.OPT) is not None)
+             + [silhouetteStep] * (silhouetteOptions(S.OPT) is not None) + [outlierStep] * (outlierOptions(S.OPT) is not None))
     if not steps:
         return None
 

@@ -614,6 +614,50 @@ int gr_lof_dev(gr_ctx* ctx, const int32_t* idx_dev, const double* dist_dev, int6
 int gr_knn_overlap_dev(gr_ctx* ctx, const int32_t* idx_a_dev, const int32_t* idx_b_dev, int64_t n, int k, int32_t* count_dev /*[n]*/,
                        double* mean_dev /*[1]*/);
 
+/* ---- density-based clustering of a device table: DBSCAN (csrc/density.hip; new: the reference has no counterpart) ----
+ * Two calls in the manner of gr_knn_dev and gr_lof_dev: one builds an object that stays on the device, the other reads it there.
+ * gr_eps_graph_dev: x_dev [n x d] floats; adj_dev [n x GR_EPS_WORDS(n)] 64-bit words receives the eps-neighbourhood graph as a bitmap: bit j of row i
+ * - word j / 64, bit j % 64 - is set iff dist(i, j) <= eps (equality counts); count_dev [n] int32 receives the popcount of every row.  metric 0:
+ * euclidean distance, 1: cosine distance.  Every pointer is device memory; the work is enqueued on the ctx stream and the call returns without waiting
+ * for it; scratch (n doubles, the cosine norms) comes from the context.
+ * dist is gr_silhouette_dev's and gr_knn_dev's pair distance, operation for operation and bit for bit; everything past the loads is fp64, every
+ * operation rounded on its own (no fused multiply-add); sqrt is the device library's (correctly rounded):
+ * Pair distance, euclidean.  t = x_it - x_jt, D = D + t t in column order from +0.0, dist = sqrt(D).
+ * Pair distance, cosine.  p = p + x_it x_jt in column order from +0.0; q_i = sqrt(Q_i), Q_i = Q_i + x_it x_it by the same chain, once per row;
+ * c = p / (q_i q_j), and 0 where either norm is 0; dist = 1 - c, and 0 where that is not above 0.
+ * The diagonal bit is always set: a row is in its own neighbourhood (as in scikit-learn), so count_i >= 1 counts the row itself.  Bits at and past n
+ * in a row's last word are 0.  The chain is symmetric in i and j - x_it - x_jt and x_jt - x_it square to the same bits, the product commutes - so
+ * the bitmap is symmetric bit for bit: bit j of row i equals bit i of row j.  All n^2 pairs are visited (the symmetry is not used to halve the work).
+ * Because the distances are gr_knn_dev's bits, count_i >= m exactly where column m - 2 of gr_knn_dev's dist (k >= m - 1) is <= eps.
+ * gr_dbscan_dev: the labels of DBSCAN read off such a bitmap (adj_dev, count_dev as gr_eps_graph_dev leaves them; one bitmap serves any min_pts).
+ * The rule, which is scikit-learn's DBSCAN(metric="precomputed") result exactly:
+ *   row i is core iff count_i >= min_pts (the row itself counts);
+ *   the clusters are the connected components of the core rows under adj; they are numbered 0, 1, ... in ascending order of their smallest core row;
+ *   a row that is not core but has a core row in its neighbourhood is a border row: it takes the lowest cluster number among its core neighbours;
+ *   every other row is noise: -1.
+ * labels_dev [n] int32; core_dev [n] int32 (nullable) 0 / 1; n_clusters_dev 1 int32.  gr_silhouette_dev scores such a labelling unchanged: a label
+ * outside [0, k) is nobody's member.
+ * The components come from bounded kernels only: every core row starts with its own index as label; a round gives a wave to every core row, which
+ * takes the smallest label m among its core neighbours and, where m is below its own label l, lowers label[l] and label[i] to m by integer
+ * atomicMin; a second kernel then replaces every label by the fixed point of label[label[...]] (label[x] <= x always, so the walk descends and ends).
+ * Rounds repeat until one changes nothing.  The number of rounds depends on the order the atomics land in, the result does not: the fixed point -
+ * every core row carries the smallest core row of its component - is unique.  n - 1 rounds always suffice; a call that has not settled after n
+ * rounds returns GR_ERR_STATE with the outputs untouched.
+ * UNLIKE ITS NEIGHBOURS, gr_dbscan_dev WAITS ON THE STREAM: once per round, to read whether a label changed (typically a handful of rounds).  The
+ * last kernels (border rows, numbering, outputs) are enqueued and not waited for.  Scratch: 2 n int32 and ceil(n / 64) words from the context.
+ * No floating-point atomics, no grid barrier, no unbounded spin: two runs give the same bits.
+ * Limits: 2 <= n <= GR_DBSCAN_MAX_N (the pair work is n^2 d in fp64; the bitmap is n^2 / 8 bytes: 8 GB at the limit), 1 <= d <= GR_DBSCAN_MAX_D,
+ * eps finite and >= 0, 1 <= min_pts <= n; outside the size limits GR_ERR_UNSUPPORTED with a gr_last_error text that names the value; null required
+ * pointers, non-positive n, d or min_pts, a negative or non-finite eps or an unknown metric: GR_ERR_INVALID.  Nothing is launched in either case,
+ * the outputs are untouched and the context stays usable.  Non-finite elements are outside the contract. */
+#define GR_DBSCAN_MAX_N 262144
+#define GR_DBSCAN_MAX_D 256
+#define GR_EPS_WORDS(n) (((n) + 63) / 64)
+int gr_eps_graph_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, double eps, int metric /*0 euclidean, 1 cosine*/,
+                     uint64_t* adj_dev /*[n x GR_EPS_WORDS(n)]*/, int32_t* count_dev /*[n]*/);
+int gr_dbscan_dev(gr_ctx* ctx, const uint64_t* adj_dev, const int32_t* count_dev, int64_t n, int min_pts, int32_t* labels_dev /*[n]*/,
+                  int32_t* core_dev /*[n] nullable, 0/1*/, int32_t* n_clusters_dev /*[1]*/);
+
 /* ---- the sampling layer of a variational autoencoder (csrc/vae.hip; new: the reference has no counterpart) ----
  * The layer between an encoder whose head emits a mean and a log-variance and a decoder: the reparameterisation z = mu + exp(logvar / 2) eps, its KL
  * term against the unit Gaussian, and the backward of both.  h [B x 2 nd] floats: columns 0 .. nd - 1 of a row hold mu, columns nd .. 2 nd - 1 hold
