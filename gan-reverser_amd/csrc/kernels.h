@@ -690,6 +690,24 @@ int launch_dbscan_begin(const int* count, long n, int min_pts, const DbscanScrat
 void launch_dbscan_round(const unsigned long long* adj, long n, const DbscanScratch& w, hipStream_t s);
 void launch_dbscan_finish(const unsigned long long* adj, long n, const DbscanScratch& w, int* labels, int* core, int* n_clusters, hipStream_t s);
 
+// ---------------------------------------------------------------- the minimum spanning tree of a device table (mst.hip; gr_mst_dev)
+// x [n x d] floats; core (nullable) doubles, row i's at core[i * core_stride]; eu / ev [n - 1] ints, ew [n - 1] doubles: all device.  The weight of
+// the pair (i, j) is silhouette.hip's pair distance, raised to core_i and core_j where they are larger; the tree is the unique one under the order
+// (w, min(i, j), max(i, j)).  launch_mst_begin returns 1 outside 2 <= n <= MST_MAX_N, 1 <= d <= 256, metric 0 / 1.  The three parts share a carved
+// workspace of mst_workspace_bytes: begin (norms, comp[i] = i, *w.n_edges = 0), then the caller repeats round (every component's smallest outgoing
+// edge, hook, compress; *w.n_edges counts the edges emitted so far) until n - 1 edges are out - ceil(log2 n) rounds always suffice - then finish (the
+// edges to eu / ev / ew in the edge order).
+constexpr long MST_MAX_N = SIL_MAX_N;
+struct MstScratch {
+  double* qn; double* best_w; unsigned long long* cw; unsigned long long* ce; unsigned long long* edge_w; unsigned long long* edge_e;
+  int* comp; int* parent; int* best_j; int* n_edges;
+};
+size_t mst_workspace_bytes(long n);
+MstScratch mst_carve(void* workspace, long n);
+int launch_mst_begin(const float* x, long n, int d, int metric, const MstScratch& w, hipStream_t s);
+void launch_mst_round(const float* x, long n, int d, int metric, const double* core, long core_stride, const MstScratch& w, hipStream_t s);
+void launch_mst_finish(long n, const MstScratch& w, int* eu, int* ev, double* ew, hipStream_t s);
+
 // ---------------------------------------------------------------- the sampling layer of a VAE (vae.hip; gr_vae_sample_dev, gr_vae_sample_backward_dev)
 // h [B x 2 nd] = (mu | logvar), eps (nullable: 0) / z / gz [B x nd], gh [B x 2 nd], kl_rows [B] floats and kl 1 double nullable: all device; workspace
 // of chain_mean_workspace_bytes(B), read only when kl is given; c = kl_weight / B.  Both return 1 outside 1 <= B < 2^31, 1 <= nd <= 256.

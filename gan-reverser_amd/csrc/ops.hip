@@ -675,6 +675,39 @@ extern "C" int gr_dbscan_dev(gr_ctx* c, const uint64_t* adj, const int32_t* coun
   return GR_OK;
 }
 
+// ------------------------------------------------------------------ the minimum spanning tree of a device table (mst.hip)
+// (like gr_dbscan_dev it waits on the stream: once per Boruvka round, to read how many edges are out)
+extern "C" int gr_mst_dev(gr_ctx* c, const float* x, int64_t n, int d, int metric, const double* core, int64_t core_stride, int32_t* eu, int32_t* ev,
+                          double* ew, int32_t* rounds_host) {
+  if (!c) return GR_ERR_INVALID;
+  if (!x || !eu || !ev || !ew) return fail(c, GR_ERR_INVALID, "gr_mst_dev: null pointer");
+  if (n <= 0) return fail(c, GR_ERR_INVALID, "gr_mst_dev: n %lld must be positive", (long long)n);
+  if (d <= 0) return fail(c, GR_ERR_INVALID, "gr_mst_dev: d %d must be positive", d);
+  if (metric != 0 && metric != 1) return fail(c, GR_ERR_INVALID, "gr_mst_dev: metric %d: 0 (euclidean) or 1 (cosine)", metric);
+  if (core_stride < 1) return fail(c, GR_ERR_INVALID, "gr_mst_dev: core_stride %lld: at least 1 double from one row's core distance to the next", (long long)core_stride);
+  if (n < 2 || n > GR_MST_MAX_N) return fail(c, GR_ERR_UNSUPPORTED, "gr_mst_dev: n %lld: between 2 and %d rows", (long long)n, GR_MST_MAX_N);
+  if (d > GR_MST_MAX_D) return fail(c, GR_ERR_UNSUPPORTED, "gr_mst_dev: d %d: at most %d columns", d, GR_MST_MAX_D);
+  Staging s(c);
+  auto scratch = s.reserve<char>(mst_workspace_bytes(n));
+  TRY(s.grow());
+  const MstScratch w = mst_carve(s.ptr(scratch), n);
+  if (launch_mst_begin(x, n, d, metric, w, c->stream)) return fail(c, GR_ERR_UNSUPPORTED, "gr_mst_dev: unsupported size");
+  LAUNCHCHK(c);
+  int cap = 0;
+  while (((int64_t)1 << cap) < n) ++cap;                                // ceil(log2 n): every round at least halves the component count
+  int rounds = 0, edges = 0;
+  while (rounds < cap && edges < n - 1) {
+    launch_mst_round(x, n, d, metric, core, core_stride, w, c->stream); LAUNCHCHK(c);
+    HIPCHK(c, hipMemcpyAsync(&edges, w.n_edges, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    TRY(s.finish());
+    ++rounds;
+  }
+  if (edges != n - 1) return fail(c, GR_ERR_STATE, "gr_mst_dev: %d of %lld edges after %d rounds (non-finite elements?)", edges, (long long)(n - 1), rounds);
+  launch_mst_finish(n, w, eu, ev, ew, c->stream); LAUNCHCHK(c);
+  if (rounds_host) *rounds_host = rounds;
+  return GR_OK;
+}
+
 // ------------------------------------------------------------------ the sampling layer of a VAE (vae.hip)
 static int vae_check(gr_ctx* c, const char* who, bool null_ptr, int64_t B, int nd) {
   if (null_ptr) return fail(c, GR_ERR_INVALID, "%s: null pointer", who);

@@ -210,6 +210,8 @@ _SIGS = {
     "gr_knn_overlap_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "gr_eps_graph_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P, _P]),
     "gr_dbscan_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "gr_mst_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "gr_hdbscan_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, C.POINTER(C.c_int32)]),
     "gr_pca_project_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "gr_vae_sample_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gr_vae_sample_backward_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P]),
@@ -294,6 +296,23 @@ def grid_shape(n_tiles, slots, channels, h, w, from_space, nrow, padding=0, marg
 def progress_grid_shape(channels, h, w, from_space, grid_h, grid_w):
     """(Cout, GH, GW) of gr_progress_grid_dev's grid: grid_h x grid_w cells and the seven rows that carry the epoch digits"""
     return (3 if from_space >= 0 else int(channels), int(grid_h) * int(h) + 7, int(grid_w) * int(w))
+
+
+def hdbscan_host(eu, ev, ew, n, min_cluster_size):
+    """gr_hdbscan_host: HDBSCAN's labels (scikit-learn's rules at its defaults, include/ganrev.h) of a spanning tree over n rows as gr_mst_dev
+    leaves it - eu < ev [n - 1] int32, ew [n - 1] float64 ascending - for one min_cluster_size in [2, n] -> (labels [n] int32, -1 noise;
+    prob [n] float64; the number of clusters).  Host work: needs the library, no context and no GPU."""
+    eu, ev = np.ascontiguousarray(eu, np.int32), np.ascontiguousarray(ev, np.int32)
+    ew = np.ascontiguousarray(ew, np.float64)
+    n = int(n)
+    if not (eu.shape == ev.shape == ew.shape == (max(n - 1, 0),)):
+        raise GanrevError(f"gr_hdbscan_host: a spanning tree over n = {n} rows has n - 1 edges, not {eu.shape}, {ev.shape}, {ew.shape}")
+    labels, prob, clusters = np.empty(max(n, 0), np.int32), np.empty(max(n, 0), np.float64), C.c_int32(0)
+    r = load_library().gr_hdbscan_host(_ptr(eu), _ptr(ev), _ptr(ew), n, int(min_cluster_size), _ptr(labels), _ptr(prob), C.byref(clusters))
+    if r:
+        raise GanrevError(f"gr_hdbscan_host: status {r}: n {n} and min_cluster_size {min_cluster_size} with 2 <= min_cluster_size <= n, and n - 1 "
+                          "edges 0 <= eu < ev < n that form a tree, their weights finite, not negative and ascending")
+    return labels, prob, int(clusters.value)
 
 
 SSIM_MAX_WIN, SSIM_MAX_HW = 11, 128      # gr_ssim_*: window and image side at most (include/ganrev.h GR_SSIM_MAX_WIN, GR_SSIM_MAX_HW)
@@ -727,6 +746,24 @@ class Context:
         a label changed; the last kernels are enqueued and not waited for."""
         self.check(self.lib.gr_dbscan_dev(self.h, _ptr(adj_dev), _ptr(count_dev), int(n), int(min_pts), _ptr(labels_dev), _ptr(core_dev),
                                           _ptr(n_clusters_dev)), "gr_dbscan_dev")
+
+    MST_MAX_N, MST_MAX_D = 262144, 256                      # gr_mst_dev's limits (include/ganrev.h GR_MST_MAX_N, GR_MST_MAX_D)
+    MST_METRICS = {"euclidean": 0, "cosine": 1}
+
+    def mst_dev(self, x_dev, n, d, metric, core_dev, core_stride, eu_dev, ev_dev, ew_dev):
+        """gr_mst_dev (2 <= n <= 262144, d <= 256): the exact minimum spanning tree of the device table [n x d] under w_ij = max(dist_ij, core_i,
+        core_j), core_i = core_dev[i * core_stride] doubles (core_dev None: w_ij = dist_ij); metric "euclidean" / "cosine" (or 0 / 1) -> eu_dev,
+        ev_dev [n - 1] int32, eu < ev, and ew_dev [n - 1] doubles: the unique tree under the order (w, lo, hi), ascending by it.  Returns the
+        number of Boruvka rounds (at most ceil(log2 n)).  WAITS on the stream once per round to read how many edges are out; the last kernel
+        (the ranking of the edges) is enqueued and not waited for."""
+        if isinstance(metric, str):
+            if metric not in self.MST_METRICS:
+                raise GanrevError(f"hierarchy: metric {metric!r}: one of {sorted(self.MST_METRICS)}")
+            metric = self.MST_METRICS[metric]
+        rounds = C.c_int32(0)
+        self.check(self.lib.gr_mst_dev(self.h, _ptr(x_dev), int(n), int(d), int(metric), _ptr(core_dev), int(core_stride), _ptr(eu_dev), _ptr(ev_dev),
+                                       _ptr(ew_dev), C.byref(rounds)), "gr_mst_dev")
+        return int(rounds.value)
 
     VAE_MAX_ND = 256                 # gr_vae_sample_*: latent dimensions at most (include/ganrev.h GR_VAE_MAX_ND)
 

@@ -22,7 +22,9 @@
                                                      how much of every row's neighbourhood the map (the whitened projection) kept
   densityStep                                        --density: ganrev.density, DBSCAN over that table - the cluster count it finds, and the rows
                                                      that belong to no cluster
-  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions, outlierOptions, mapNeighbourOptions, densityOptions   what a run's options say about each, with the defaults
+  hierarchyStep                                      --hierarchy: ganrev.hierarchy, HDBSCAN over that table - no eps: the spanning tree on the device,
+                                                     the linkage, the labels and the membership strengths read off it
+  clusterOptions, pcaOptions, mapOptions, mixtureOptions, silhouetteOptions, outlierOptions, mapNeighbourOptions, densityOptions, hierarchyOptions   what a run's options say about each, with the defaults
 
 These functions return the tensors / index lists the reference renders; the pictures themselves (image.toDisplayTensor plus the
 frames and fields apply_r.lua draws) come from ganrev.render, on the GPU, and main() writes them with --render.
@@ -476,6 +478,22 @@ def densityOptions(OPT):
             getattr(OPT, "densityMetric", "cosine"))
 
 
+HIERARCHY_MAX_ROWS = L.Context.MST_MAX_N      # gr_mst_dev's limit (GR_MST_MAX_N)
+HIERARCHY_MAX_MINSAMPLES = L.Context.KNN_MAX_K + 1     # the core distance is the distance to the (S - 1)-th of at most 128 neighbours
+HIERARCHY_METRICS = ("cosine", "euclidean")
+HIERARCHY_OPTIONS = ("hierarchyMinSamples", "hierarchyMinClusterSize", "hierarchyRows", "hierarchyMetric", "hierarchyCut")
+
+
+def hierarchyOptions(OPT):
+    """(minSamples, minClusterSize, rows, metric, cut or None) of a run with --hierarchy: HDBSCAN of the first `rows` rows, the options given,
+    else 10, 25, min(nbImages, 100000), cosine and no cut; None without --hierarchy"""
+    if not getattr(OPT, "hierarchy", False):
+        return None
+    return (int(getattr(OPT, "hierarchyMinSamples", 10)), int(getattr(OPT, "hierarchyMinClusterSize", 25)),
+            int(getattr(OPT, "hierarchyRows", min(OPT.nbImages, 100000))), getattr(OPT, "hierarchyMetric", "cosine"),
+            float(OPT.hierarchyCut) if hasattr(OPT, "hierarchyCut") else None)
+
+
 MAP_MAX_ROWS = L.Context.TSNE_MAX_N     # gr_tsne_*_dev's limit (GR_TSNE_MAX_N)
 
 
@@ -548,6 +566,13 @@ def parse(argv=None):
     p.add_argument("--densityQuantile", type=float, default=argparse.SUPPRESS, metavar="Q", help=f"with --density: eps is the Q-quantile of the rows' distances to their (M - 1)-th nearest row (ganrev.knn), so that about that share of the rows is core (default 0.75; 2 <= M <= {DENSITY_MAX_MINPTS_BY_QUANTILE}; not with --densityEps)")
     p.add_argument("--densityRows", type=int, default=argparse.SUPPRESS, metavar="N", help=f"with --density: the first N rows are clustered (default min(nbImages, 100000); at most {DENSITY_MAX_ROWS}: every pair of rows is visited, the rows are independent draws, a prefix is a fair sample)")
     p.add_argument("--densityMetric", choices=list(DENSITY_METRICS), default=argparse.SUPPRESS, help="with --density: the distance (default cosine, the search's geometry)")
+    # the hierarchy options: absent from the namespace unless given - hierarchyOptions() supplies the defaults
+    p.add_argument("--hierarchy", action="store_true", default=argparse.SUPPRESS, help="clustering without an eps (ganrev.hierarchy: HDBSCAN), in the table the clustering read: the exact minimum spanning tree of the first rows under the mutual-reachability distance, built on the device, and the hierarchy read off it; writes hierarchy_mst_{u,v,w}, hierarchy_core, hierarchy_linkage (SciPy's format), hierarchy_labels (int32, -1 = noise), hierarchy_prob (.npy), with --silhouette silhouette_hierarchy_{euclidean,cosine}.npy, with --render hierarchy_noise.png and hierarchy_%%02d.png, the largest clusters")
+    p.add_argument("--hierarchyMinSamples", type=int, default=argparse.SUPPRESS, metavar="S", help=f"with --hierarchy: a row's core distance is the distance to its (S - 1)-th nearest row - DBSCAN's minPts, the row itself included; 1: plain single linkage (default 10; at most {HIERARCHY_MAX_MINSAMPLES})")
+    p.add_argument("--hierarchyMinClusterSize", type=int, default=argparse.SUPPRESS, metavar="M", help="with --hierarchy: a side of a split with fewer than M rows falls out of its cluster instead of founding one (default 25)")
+    p.add_argument("--hierarchyRows", type=int, default=argparse.SUPPRESS, metavar="N", help=f"with --hierarchy: the first N rows are clustered (default min(nbImages, 100000); at most {HIERARCHY_MAX_ROWS}: every pair of rows is visited once per round)")
+    p.add_argument("--hierarchyMetric", choices=list(HIERARCHY_METRICS), default=argparse.SUPPRESS, help="with --hierarchy: the distance (default cosine, the search's geometry)")
+    p.add_argument("--hierarchyCut", type=float, default=argparse.SUPPRESS, metavar="E", help="with --hierarchy: also write hierarchy_cut_labels.npy, the tree cut at height E - DBSCAN*'s labels at eps = E, minPts = S")
     p.add_argument("--mixture", type=int, default=argparse.SUPPRESS, metavar="ITER", help="a diagonal Gaussian mixture of the recovered noise, on the device (ganrev.mixture): ITER EM iterations from the clustering's final centroids, --nbClusters components (at most 256), in the table the clustering read; writes mixture_weights, mixture_means, mixture_variances, mixture_loglik [ITER + 1], mixture_labels, mixture_posterior, mixture_row_loglik (.npy), with --render mixture_%%02d.png and mixture_outliers.png, with --needles needle_mixture.npy")
     # the clustering options (apply_r.lua:159-161 hard-codes 20, 15, 64 + 7): absent from the namespace unless given - clusterOptions() supplies the defaults
     p.add_argument("--nbClusters", type=int, default=argparse.SUPPRESS, help="clusters of the recovered noise (default 20, apply_r.lua:159; up to 4096, above 32 through gr_cluster_dev)")
@@ -673,6 +698,24 @@ def parse(argv=None):
                 p.error(f"--densityMinPts {minPts}: 2 to {DENSITY_MAX_MINPTS_BY_QUANTILE} with --densityQuantile (the distance to the (M - 1)-th neighbour): give --densityEps E")
             if not 0 <= quantile <= 1:
                 p.error(f"--densityQuantile {quantile:g}: 0 to 1")
+    tree = hierarchyOptions(OPT)
+    for name in HIERARCHY_OPTIONS:
+        if hasattr(OPT, name) and tree is None:
+            p.error(f"--{name} belongs to the hierarchical clustering: give --hierarchy")
+    if tree is not None:
+        minSamples, minClusterSize, treeRows, _, height = tree
+        if OPT.host:
+            p.error("--hierarchy runs on the device-resident tables: not with --host")
+        if treeRows > HIERARCHY_MAX_ROWS:
+            p.error(f"--hierarchyRows {treeRows}: at most {HIERARCHY_MAX_ROWS} rows (every pair of rows is visited)")
+        if not 2 <= treeRows <= OPT.nbImages:
+            p.error(f"--hierarchyRows {treeRows}: 2 to nbImages = {OPT.nbImages} rows")
+        if not 1 <= minSamples <= min(treeRows, HIERARCHY_MAX_MINSAMPLES):
+            p.error(f"--hierarchyMinSamples {minSamples}: 1 to min(rows, {HIERARCHY_MAX_MINSAMPLES}) = {min(treeRows, HIERARCHY_MAX_MINSAMPLES)} (the row itself and its S - 1 nearest rows)")
+        if not 2 <= minClusterSize <= treeRows:
+            p.error(f"--hierarchyMinClusterSize {minClusterSize}: 2 to rows = {treeRows}")
+        if height is not None and not (math.isfinite(height) and height >= 0):
+            p.error(f"--hierarchyCut {height:g}: a finite distance, not below 0")
     if (OPT.needles or OPT.real) and OPT.dataset == "NONE":
         p.error("--needles and --real read their images from --dataset")
     if (OPT.needles or OPT.real) and OPT.host:
@@ -712,6 +755,7 @@ class Run:
         self.pca = self.needle_rows = None                                    # what the steps before the mixture leave for it
         self.mixture_labels = None                                            # ... and the mixture for the silhouette
         self.density = None                                                   # ... and the density-based clustering (ganrev.density.Clustering)
+        self.hierarchy = None                                                 # ... and the hierarchical one (ganrev.hierarchy.Clustering)
 
     def out(self, name):
         return os.path.join(self.OPT.writeTo, name)
@@ -982,6 +1026,13 @@ def silhouetteStep(S, table, centroids, images=None):
                     scored.append(("density", padded, S.density.clusters))
                 else:
                     entry["density"] = dict(skipped="%d clusters: the silhouette scores 1 to %d" % (S.density.clusters, MAX_CLUSTERS))
+            if S.hierarchy is not None:
+                if 1 <= S.hierarchy.clusters <= MAX_CLUSTERS:             # (rows past --hierarchyRows are nobody's member, like the noise)
+                    padded = np.full(N, -1, np.int32)
+                    padded[:S.hierarchy.n] = S.hierarchy.labels
+                    scored.append(("hierarchy", padded, S.hierarchy.clusters))
+                else:
+                    entry["hierarchy"] = dict(skipped="%d clusters: the silhouette scores 1 to %d" % (S.hierarchy.clusters, MAX_CLUSTERS))
             for name, labels, nb in scored:
                 if labels is None:
                     continue
@@ -1064,10 +1115,46 @@ def densityStep(S, table, centroids, images=None):
             render.grid(images, members, max(int(math.floor(math.sqrt(len(members)))), 1), S.colorSpace, path=out("density_%02d.png" % (j + 1)))
 
 
+def hierarchyStep(S, table, centroids, images=None):
+    """--hierarchy, after the clustering, in the table it read: the minimum spanning tree of the first rows under the mutual-reachability distance
+    is built on the device (the core distances from the neighbour graph of the same rows); the linkage matrix, HDBSCAN's labels and, with
+    --hierarchyCut, DBSCAN*'s labels at that height are read off its edges on the host."""
+    from . import hierarchy as HR
+    OPT, ctx, out = S.OPT, S.ctx, S.out
+    minSamples, minClusterSize, rows, metric, height = hierarchyOptions(OPT)
+    S.say("Hierarchical density-based clustering (HDBSCAN)...")
+    found = S.hierarchy = HR.cluster(ctx, table, minSamples, minClusterSize, metric, rows=rows)
+    tree = found.tree
+    np.save(out("hierarchy_mst_u.npy"), tree.u); np.save(out("hierarchy_mst_v.npy"), tree.v); np.save(out("hierarchy_mst_w.npy"), tree.w)
+    np.save(out("hierarchy_core.npy"), tree.core if tree.core is not None else np.zeros(rows))     # minSamples 1: every row is core at any height
+    np.save(out("hierarchy_linkage.npy"), HR.linkage(tree))
+    np.save(out("hierarchy_labels.npy"), found.labels); np.save(out("hierarchy_prob.npy"), found.prob)
+    largest = np.argsort(-found.sizes, kind="stable")[:20]                    # largest first, the lower number among equals
+    entry = dict(minSamples=minSamples, minClusterSize=minClusterSize, metric=metric, rows=rows, space=S.spaceName, rounds=tree.rounds,
+                 clusters=found.clusters, noise=found.noise, sizes=[int(found.sizes[c]) for c in largest],
+                 weight_quartiles=[float(q) for q in np.quantile(tree.w, [0.0, 0.25, 0.5, 0.75, 1.0])])
+    if height is not None:
+        at = HR.cut(tree, height)
+        np.save(out("hierarchy_cut_labels.npy"), at)
+        entry["cut"] = dict(height=height, clusters=int(at.max()) + 1, noise=int((at < 0).sum()))
+    S.summary["hierarchy"] = entry
+    S.say("<apply_r> HDBSCAN, minSamples %d, minClusterSize %d, %s distance, %d rows in %s: %d Boruvka rounds, %d clusters and %d noise rows"
+          % (minSamples, minClusterSize, metric, rows, S.spaceName, tree.rounds, found.clusters, found.noise))
+    if OPT.render and images is not None:
+        noise = np.nonzero(found.labels < 0)[0][:min(512 + 16, OPT.nbImages, 1024)]       # the first noise rows, as many as anomalies.png shows
+        if len(noise):
+            render.grid(images, noise, max(int(math.floor(math.sqrt(len(noise)))), 1), S.colorSpace, path=out("hierarchy_noise.png"))
+        for j, c in enumerate(largest):
+            members = np.nonzero(found.labels == c)[0][:64 + 8]                # lowest rows first
+            render.grid(images, members, max(int(math.floor(math.sqrt(len(members)))), 1), S.colorSpace, path=out("hierarchy_%02d.png" % (j + 1)))
+
+
 def afterClustering(S):
-    """the steps that follow the clustering in its table - the mixture, the density-based clustering, then the silhouette, which scores the labels
-    of both too, then the outlier factors - as one call (table, centroids, images=None); None when the run asks for none of them"""
+    """the steps that follow the clustering in its table - the mixture, the density-based clustering, the hierarchical one, then the silhouette,
+    which scores the labels of all three too, then the outlier factors - as one call (table, centroids, images=None); None when the run asks for
+    none of them"""
     steps = ([mixtureStep] * (mixtureOptions(S.OPT) is not None) + [densityStep] * (densityOptions(S.OPT) is not None)
+             + [hierarchyStep] * (hierarchyOptions(S.OPT) is not None)
              + [silhouetteStep] * (silhouetteOptions(S.OPT) is not None) + [outlierStep] * (outlierOptions(S.OPT) is not None))
     if not steps:
         return None

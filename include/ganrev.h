@@ -658,6 +658,67 @@ int gr_eps_graph_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, double e
 int gr_dbscan_dev(gr_ctx* ctx, const uint64_t* adj_dev, const int32_t* count_dev, int64_t n, int min_pts, int32_t* labels_dev /*[n]*/,
                   int32_t* core_dev /*[n] nullable, 0/1*/, int32_t* n_clusters_dev /*[1]*/);
 
+/* ---- clustering without an eps: the exact minimum spanning tree on the device, HDBSCAN read off it on the host (csrc/mst.hip, csrc/hdbscan.cpp;
+ * new: the reference has no counterpart) ----
+ * gr_mst_dev: x_dev [n x d] floats; core_dev nullable, row i's core distance at core_dev[i * core_stride] (core_stride in doubles, >= 1: column
+ * k - 1 of a gr_knn_dev dist table is read in place with pointer dist + k - 1 and stride k; column minSamples - 2 is the core distance for
+ * DBSCAN's minPts = minSamples, the row itself included); eu_dev, ev_dev [n - 1] int32 and ew_dev [n - 1] doubles receive the tree.  Every pointer
+ * but rounds_host is device memory; scratch comes from the context.
+ * Weights.  dist_ij is gr_silhouette_dev's, gr_knn_dev's and gr_eps_graph_dev's pair distance, operation for operation and bit for bit; everything
+ * past the loads is fp64, every operation rounded on its own (no fused multiply-add); sqrt is the device library's (correctly rounded):
+ * Pair distance, euclidean.  t = x_it - x_jt, D = D + t t in column order from +0.0, dist = sqrt(D).
+ * Pair distance, cosine.  p = p + x_it x_jt in column order from +0.0; q_i = sqrt(Q_i), Q_i = Q_i + x_it x_it by the same chain, once per row;
+ * c = p / (q_i q_j), and 0 where either norm is 0; dist = 1 - c, and 0 where that is not above 0.
+ * w_ij = max(dist_ij, core_i, core_j) - the mutual-reachability distance; with core_dev == NULL, w_ij = dist_ij.  Core distances are >= +0.0
+ * and finite (negative, -0.0 or non-finite ones are outside the contract), so w is never negative and never -0.0.
+ * The tree.  Edges are ordered by the strict total order (w ascending, then min(i, j), then max(i, j)).  Under a strict total order the minimum
+ * spanning tree is unique: that tree is the result.  The outputs hold its n - 1 edges with eu < ev, sorted ascending by that same order - a function
+ * of the inputs alone, whatever the launch geometry or the order in which workgroups and atomics land.
+ * Method: Boruvka rounds from bounded kernels only.  A pair pass finds, for every row i, the smallest edge to a row of another component (all n^2
+ * pairs are visited every round; the symmetry is not used); integer atomicMin on the 64-bit pattern of w, then on (lo << 32 | hi) among the rows
+ * that hold that w, gives every component its smallest outgoing edge; a component hooks under the component that edge reaches, and where two chose
+ * the same edge the lower root emits it and stays; parent pointers are compressed by a walk cut at n steps.  Every round at least halves the
+ * component count, so ceil(log2 n) rounds always suffice; a call that has not finished by then returns GR_ERR_STATE with the outputs untouched.  The
+ * emitted edges are then ranked by counting (rank = the number of smaller keys; the keys are distinct) and scattered.
+ * LIKE gr_dbscan_dev, gr_mst_dev WAITS ON THE STREAM: once per round, to read how many edges are out.  The last kernel (the ranking) is enqueued and
+ * not waited for.  rounds_host (nullable, HOST memory) receives the number of rounds.
+ * Scratch: 6 n 8-byte words and 3 n + 1 int32 from the context (60 n bytes: 15.7 MB at the limit), each array on a 256-byte boundary.
+ * No floating-point atomics, no grid barrier, no unbounded spin: two runs give the same bits.
+ * Limits: 2 <= n <= GR_MST_MAX_N (the pair work is n^2 d in fp64, per round), 1 <= d <= GR_MST_MAX_D; outside them GR_ERR_UNSUPPORTED with a
+ * gr_last_error text that names the value; null required pointers, non-positive n or d, an unknown metric or core_stride < 1: GR_ERR_INVALID.
+ * Nothing is launched in either case, the outputs are untouched and the context stays usable.  Non-finite elements are outside the contract.
+ *
+ * gr_hdbscan_host: HDBSCAN's labels of a spanning tree as gr_mst_dev leaves it, on the host: no context, no GPU.  eu, ev, ew [n - 1]: a spanning
+ * tree over n rows, eu < ev, ew ascending; labels [n] int32 (-1: noise), prob [n] doubles, n_clusters 1 int32: all host memory.
+ * The rules are scikit-learn 1.7's HDBSCAN at its defaults (cluster_selection_method="eom", allow_single_cluster=False,
+ * cluster_selection_epsilon=0, no max_cluster_size); where the paper and scikit-learn differ, scikit-learn's behaviour is the definition.  All fp64:
+ *   hierarchy: the edges are merged in the order given; edge k joins the components of eu[k] (left) and ev[k] (right) into node n + k.
+ *   lambda = 1 / w, and +inf at w = 0.
+ *   condensed tree: the nodes n + k in descending k, skipping nodes inside a side that has fallen out.  The root is cluster 0, born at lambda 0.
+ *     For a node of cluster c whose sides hold L and R rows, m = min_cluster_size: L >= m and R >= m: the left side becomes a new cluster, then the
+ *     right one, both born at lambda; one side below m: its rows fall out of c at lambda, the other side goes on as c; both below m: the rows of both
+ *     fall out of c at lambda.
+ *   stability_c = stability_c + term from +0.0, one term per side that leaves c (a new cluster, or the rows that fall out; s its row count), in
+ *     the order above, left before right: term = (lambda - birth_c) * (double)s, and 0 where lambda == birth_c.  lambda_max_c = the largest lambda
+ *     among c's terms.
+ *   selection (excess of mass): the clusters in descending number (children before parents), the root left out: S = stability_left +
+ *     stability_right for a cluster with children; where S > stability_c the cluster is not selected and stability_c = S, else it is selected and
+ *     no cluster below it is.  The root is never selected.
+ *   label of a row: the selected cluster that the cluster it fell out of is, or lies under; -1 without one.
+ *   prob of a row: q = min(lambda_row, lambda_max_C) / lambda_max_C for its selected cluster C, and 1 where q is not finite; 0 for a row of -1.
+ *   Clusters are numbered 0, 1, ... in ascending order of their smallest member row.
+ * Among equal weights the merge order is the order given (gr_mst_dev's: by (lo, hi)); another implementation may merge ties in another order.
+ * GR_ERR_INVALID with the outputs untouched for: a null pointer, n < 2 (or above 2^30), min_cluster_size outside [2, n], an index outside [0, n),
+ * eu >= ev, a weight that is negative or not finite, weights not ascending, edges that close a cycle.
+ * Not built: `leaf` selection, allow_single_cluster, GLOSH outlier scores, prediction for new rows. */
+#define GR_MST_MAX_N 262144
+#define GR_MST_MAX_D 256
+int gr_mst_dev(gr_ctx* ctx, const float* x_dev, int64_t n, int d, int metric /*0 euclidean, 1 cosine*/, const double* core_dev /*nullable*/,
+               int64_t core_stride /*in doubles, >= 1*/, int32_t* eu_dev, int32_t* ev_dev, double* ew_dev /*[n - 1] each*/,
+               int32_t* rounds_host /*nullable*/);
+int gr_hdbscan_host(const int32_t* eu, const int32_t* ev, const double* ew, int64_t n, int min_cluster_size, int32_t* labels /*[n], -1 noise*/,
+                    double* prob /*[n]*/, int32_t* n_clusters);
+
 /* ---- the sampling layer of a variational autoencoder (csrc/vae.hip; new: the reference has no counterpart) ----
  * The layer between an encoder whose head emits a mean and a log-variance and a decoder: the reparameterisation z = mu + exp(logvar / 2) eps, its KL
  * term against the unit Gaussian, and the backward of both.  h [B x 2 nd] floats: columns 0 .. nd - 1 of a row hold mu, columns nd .. 2 nd - 1 hold
